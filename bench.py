@@ -2,6 +2,7 @@
 """bench.py -- Mpx/s of the full pyramid line-end pass @1080p (BASELINE.json metric), one rank per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--workload config2|config3|config5]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of B device-resident synthetic frames per rank:
 zoom pyramid -> center-surround -> ReLU -> oriented line-end bank -> ReLU -> clip (config 2/5) or the
@@ -15,9 +16,19 @@ non-zero if any rank failed.  It never re-execs a process that has initialised t
 
 Rank 0 prints ONE JSON line.  ``value`` = input-frame megapixels per second over all ranks, inputs
 resident in HBM when the timed region starts; the timed region holds nothing but the K steps (no event
-records, no host reads).  AFTER it, and outside ``value``: ``roofline`` prices the dominant kernel against
-HBM from HIP events recorded around its launches in a loop of their own; ``other_workloads`` carries short
-runs of configs 3 and 5; ``cpu_baseline`` times the CPU oracle on the host cores (N = 1 only).
+records, no host reads); ``ms_per_step`` = the time of one of them.  A plain run does only that: set up,
+tune, settle, W warm-ups, the K timed steps, the line.
+
+``--dump-outputs DIR``: after the timed steps, rank 0 writes what the last of them computed -- the arrays
+LineEndPipeline.outputs() hands a caller -- as DIR/<name>.npy (dense maps float32, a fixed seeded sample of
+at most 2^20 elements each; keypoint rows and counts float64).  The frames are seeded: two builds run with
+the same arguments can be compared file by file.
+
+``--full`` adds, AFTER the timed region and outside ``value``: ``steady_state`` (60 more steps);
+``roofline`` prices the dominant kernel against HBM from HIP events recorded around its launches in a loop
+of their own; ``ingest`` and ``latency`` (host frames in, N = 1 only); ``other_workloads`` carries short
+runs of configs 3 and 5 and the reference's layout; ``cpu_baseline`` times the CPU oracle on the host cores
+(N = 1 only); ``summary`` condenses them.
 """
 import argparse
 import hashlib
@@ -527,6 +538,45 @@ def roofline_of(dom, B):
     return roof
 
 
+DUMP_MAP_ELEMENTS = 1 << 20      # per dense map: at most this many float32 values (4 MiB)
+DUMP_KEYPOINT_ROWS = 1 << 19     # keypoint rows, 4 columns as float64: at most 16 MiB
+
+
+def _sample_positions(n, k, seed=0):
+    """Sorted positions of a fixed, seeded sample of at most k of n elements; None = all of them (n <= k)."""
+    if n <= k:
+        return None
+    return np.unique(np.random.default_rng(seed).integers(0, n, k))
+
+
+def dump_outputs(torch, pipe, outdir):
+    """What the last step computed, as a caller of the timed path receives it (LineEndPipeline.outputs()): every dense map as
+    <outdir>/<name>.npy, float32, flat in the pipeline's packed layout (frames, levels, NHWC), whole or a seeded sample of
+    DUMP_MAP_ELEMENTS positions; rgb workloads add ``keypoints`` (every frame's rows concatenated, a seeded sample of
+    DUMP_KEYPOINT_ROWS rows when there are more) and ``keypoint_counts``, both float64 (exact for these integers).
+    Returns {name: [values written, values the output holds]}."""
+    os.makedirs(outdir, exist_ok=True)
+    res = pipe.outputs()
+    written = {}
+    for name, v in res.items():
+        if name == "keypoints":
+            rows = np.concatenate(v) if v else np.zeros((0, 4), np.int64)
+            idx = _sample_positions(len(rows), DUMP_KEYPOINT_ROWS)
+            arr = (rows if idx is None else rows[idx]).astype(np.float64)
+            total = rows.size
+        elif name == "keypoint_counts":
+            arr, total = np.asarray(v, np.float64), len(v)
+        else:
+            data = v.data
+            idx = _sample_positions(data.numel(), DUMP_MAP_ELEMENTS)
+            if idx is not None:
+                data = data[torch.from_numpy(idx).to(data.device)]
+            arr, total = data.float().cpu().numpy(), v.data.numel()
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+        written[name] = [int(arr.size), int(total)]
+    return written
+
+
 def side_workload(torch, D, name, local, dev, rank, world, label=None, **over):
     """Short run of another BASELINE config on this rank (N = 1 only): ms/step, whole-pass and dominant-kernel
     fractions of the HBM peak, in the same JSON line as the headline."""
@@ -778,15 +828,18 @@ def run_rank(args):
     own_ms = timed_steps.own / args.steps * 1e3
 
     # ---- everything below is outside the timed region ----
-    # Steady state, reported beside `value`, never instead of it: after an idle period the first ~20 back-to-back launches
-    # of the pass run up to 20 % slower than the rate the chip then settles at (profiles/r02/launch_drift.txt: 864 -> 1040
-    # -> 848 us for the dominant kernel; flat with 20 ms idle gaps; a plain device copy does the same) -- a power-management
-    # transient, and with --warmup 5 the K timed steps sit inside it.  60 more steps, timed the same way, show the settled rate.
-    settle_steps = 60
-    steady = timed_steps(torch, D, pipe, frames, settle_steps, 0, dev)
-    dom = dominant_kernel(torch, pipe, frames, wl, B, dev)
-    ingest = ingest_record(torch, pipe, frames, wl, B, dev) if world == 1 and not args.no_ingest else None
-    latency = latency_record() if world == 1 and not args.no_latency else None
+    # (first: the maps still hold the last timed step's results)
+    dumped = dump_outputs(torch, pipe, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    if args.full:
+        # Steady state, reported beside `value`, never instead of it: after an idle period the first ~20 back-to-back launches
+        # of the pass run up to 20 % slower than the rate the chip then settles at (profiles/r02/launch_drift.txt: 864 -> 1040
+        # -> 848 us for the dominant kernel; flat with 20 ms idle gaps; a plain device copy does the same) -- a power-management
+        # transient, and with --warmup 5 the K timed steps sit inside it.  60 more steps, timed the same way, show the settled rate.
+        settle_steps = 60
+        steady = timed_steps(torch, D, pipe, frames, settle_steps, 0, dev)
+        dom = dominant_kernel(torch, pipe, frames, wl, B, dev)
+        ingest = ingest_record(torch, pipe, frames, wl, B, dev) if world == 1 and not args.no_ingest else None
+        latency = latency_record() if world == 1 and not args.no_latency else None
     # the scaling record proves itself: backend, and per rank the device it ran on and its own step time
     dist = dist_record(D, rank, local, D.device_identity(local), own_ms,
                        settle_steps_run=settle_run, streams="two" if pipe.overlap else "one",
@@ -831,19 +884,27 @@ def run_rank(args):
                    "placement_tuning": pipe.placement_tuning,
                    "sharding": "frame i -> rank i mod N; one RCCL broadcast of constants at init",
                    "csrc_revision": csrc_revision()},
-        "roofline": roofline_of(dom, B),
-        "ingest": ingest,
-        "latency": latency,
-        "dist": dist,
-        "steady_state": {"ms_per_step": round(steady / settle_steps * 1e3, 4), "steps": settle_steps,
-                         "value": round(B * world * settle_steps * h * w / steady / 1e6, 2),
-                         "whole_pass_frac_of_hbm_peak": round(pipe.algorithmic_bytes_per_frame() * B * settle_steps / steady / 1e9 / HBM_PEAK_GBS, 4),
-                         "note": "cross-check of the settle loop: the same steps timed again right after the K timed ones "
-                                 "(without a settle loop the first ~20 launches after an idle period run inside a power-management "
-                                 "transient, profiles/r02/launch_drift.txt)"},
     }
+    if args.full:
+        out["roofline"] = roofline_of(dom, B)
+        out["ingest"] = ingest
+        out["latency"] = latency
+    out["dist"] = dist
+    if args.full:
+        out["steady_state"] = {"ms_per_step": round(steady / settle_steps * 1e3, 4), "steps": settle_steps,
+                               "value": round(B * world * settle_steps * h * w / steady / 1e6, 2),
+                               "whole_pass_frac_of_hbm_peak": round(pipe.algorithmic_bytes_per_frame() * B * settle_steps / steady / 1e9 / HBM_PEAK_GBS, 4),
+                               "note": "cross-check of the settle loop: the same steps timed again right after the K timed ones "
+                                       "(without a settle loop the first ~20 launches after an idle period run inside a power-management "
+                                       "transient, profiles/r02/launch_drift.txt)"}
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "values_written_of_total": dumped}
     del pipe, frames
     torch.cuda.empty_cache()
+    if not args.full:
+        emit_line(json.dumps(out))
+        D.finalize()
+        return
     if world == 1 and not args.no_side_workloads:
         out["other_workloads"] = {}
         if args.workload != "config3":
@@ -875,6 +936,12 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--frames", type=int, default=0, help="frames per rank per step (0 = workload default)")
     ap.add_argument("--workload", default="config2", choices=sorted(WORKLOADS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; dense maps float32, "
+                         "a fixed seeded sample of at most 2^20 values each; keypoint rows and counts float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else too: steady state, roofline, ingest, latency, the other "
+                         "workloads, the CPU baselines (the --no-* options below leave parts of it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-side-workloads", action="store_true")
     ap.add_argument("--no-ingest", action="store_true")
@@ -886,6 +953,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, argv))
     run_rank(args)
