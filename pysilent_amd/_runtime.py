@@ -233,9 +233,10 @@ class PackedPyramid(object):
 
 
 class _Operand(object):
-    """Normalised view of an input tensor: geometry + pointer + how to allocate results."""
+    """Normalised view of an input tensor: geometry + pointer + how to allocate results and which entry point to call.
+    ``ctx``: the context to run on (default: the shared one of the tensor's device)."""
 
-    def __init__(self, x, channels=None):
+    def __init__(self, x, channels=None, ctx=None):
         self.packed = isinstance(x, PackedPyramid)
         if self.packed:
             self.src = x
@@ -273,17 +274,28 @@ class _Operand(object):
         self.frame_px = sum(h * w for h, w in self.extents)
         self.levels = (_lib.Extent * len(self.extents))(*[_lib.Extent(h, w) for h, w in self.extents])
         self.n_levels = len(self.extents)
-        self.ctx = get_context(self.device)
+        self.ctx = ctx or get_context(self.device)
 
-    def alloc(self, channels, dtype=np.float32):
-        n = self.n_frames * self.frame_px * channels
+    def empty(self, shape, dtype=np.float32):
+        """A result buffer placed like the operand (torch tensor on its device, or ndarray) and its address."""
         if self.dev:
             import torch
-            tdt = {np.float32: torch.float32, np.int64: torch.int64}[dtype]
-            out = torch.empty(n, dtype=tdt, device=self._torch_device)
+            out = torch.empty(shape, dtype={np.float32: torch.float32, np.int64: torch.int64}[dtype], device=self._torch_device)
             return out, C.c_void_p(out.data_ptr())
-        out = np.empty(n, dtype=dtype)
+        out = np.empty(shape, dtype=dtype)
         return out, C.c_void_p(out.ctypes.data)
+
+    def alloc(self, channels):
+        return self.empty(self.n_frames * self.frame_px * channels)
+
+    def call(self, name, *args):
+        """silent_<name>_dev(ctx, *args, stream) on torch's current stream for a device operand, the synchronous host-pointer
+        silent_<name>(ctx, *args) otherwise."""
+        if self.dev:
+            rc = getattr(_lib.load(), "silent_" + name + "_dev")(self.ctx.handle, *(args + (self.stream,)))
+        else:
+            rc = getattr(_lib.load(), "silent_" + name)(self.ctx.handle, *args)
+        self.ctx.check(rc)
 
     def wrap(self, flat, channels):
         if self.packed:
@@ -317,10 +329,7 @@ def conv2d_same(x, kernel_hwio, relu=False, clip_hi=None):
     kh, kw, _, co = k.shape
     out, optr = op.alloc(co)
     flags = (_lib.RELU if relu else 0) | (_lib.CLIP if clip_hi is not None else 0)
-    lib, ctx = _lib.load(), op.ctx
-    args = (ctx.handle, op.ptr) + op.geom() + (op.c, C.c_void_p(k.ctypes.data), kh, kw, co, flags,
-                                                  float(clip_hi or 0.0), optr)
-    ctx.check(lib.silent_conv2d_same_dev(*(args + (op.stream,))) if op.dev else lib.silent_conv2d_same(*args))
+    op.call("conv2d_same", op.ptr, *op.geom(), op.c, C.c_void_p(k.ctypes.data), kh, kw, co, flags, float(clip_hi or 0.0), optr)
     return op.wrap(out, co)
 
 
@@ -334,10 +343,8 @@ def regulate(x, blur_hwio, regulation_value, regulation_root=0.5, flat_policy="i
     except KeyError:
         raise ValueError("flat_policy must be 'ieee' or 'zero'")
     out, optr = op.alloc(op.c)
-    lib, ctx = _lib.load(), op.ctx
-    args = (ctx.handle, op.ptr) + op.geom() + (op.c, C.c_void_p(k.ctypes.data), k.shape[0], k.shape[1],
-                                                  float(regulation_value), float(regulation_root), pol, optr)
-    ctx.check(lib.silent_regulate_dev(*(args + (op.stream,))) if op.dev else lib.silent_regulate(*args))
+    op.call("regulate", op.ptr, *op.geom(), op.c, C.c_void_p(k.ctypes.data), k.shape[0], k.shape[1], float(regulation_value),
+            float(regulation_root), pol, optr)
     return op.wrap(out, op.c)
 
 
@@ -350,37 +357,29 @@ def gray_line_end(x, cs_kernel, end_bank, clip_hi=255.0, want_cs=True, want_end=
     K = eb.shape[3]
     cs_out, cs_ptr = op.alloc(1) if want_cs else (None, None)
     end_out, end_ptr = op.alloc(K) if want_end else (None, None)
-    lib, ctx = _lib.load(), op.ctx
-    args = (ctx.handle, op.ptr) + op.geom() + (C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K,
-                                                  float(clip_hi), cs_ptr, end_ptr)
-    ctx.check(lib.silent_gray_line_end_dev(*(args + (op.stream,))) if op.dev else lib.silent_gray_line_end(*args))
+    op.call("gray_line_end", op.ptr, *op.geom(), C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi), cs_ptr,
+            end_ptr)
     return (op.wrap(cs_out, 1) if want_cs else None, op.wrap(end_out, K) if want_end else None)
 
 
 def pad_inwards(x, pt, pb, pl, pr):
     op = _Operand(x)
     out, optr = op.alloc(op.c)
-    lib, ctx = _lib.load(), op.ctx
-    args = (ctx.handle, op.ptr) + op.geom() + (op.c, int(pt), int(pb), int(pl), int(pr), optr)
-    ctx.check(lib.silent_pad_inwards_dev(*(args + (op.stream,))) if op.dev else lib.silent_pad_inwards(*args))
+    op.call("pad_inwards", op.ptr, *op.geom(), op.c, int(pt), int(pb), int(pl), int(pr), optr)
     return op.wrap(out, op.c)
 
 
 def value_from_color(x):
     op = _Operand(x)
     out, optr = op.alloc(1)
-    lib, ctx = _lib.load(), op.ctx
-    args = (ctx.handle, op.ptr) + op.geom() + (op.c, optr)
-    ctx.check(lib.silent_value_from_color_dev(*(args + (op.stream,))) if op.dev else lib.silent_value_from_color(*args))
+    op.call("value_from_color", op.ptr, *op.geom(), op.c, optr)
     return op.wrap(out, 1)
 
 
 def bw_from_color(x):
     op = _Operand(x)
     out, optr = op.alloc(1)
-    lib, ctx = _lib.load(), op.ctx
-    args = (ctx.handle, op.ptr) + op.geom() + (op.c, optr)
-    ctx.check(lib.silent_bw_from_color_dev(*(args + (op.stream,))) if op.dev else lib.silent_bw_from_color(*args))
+    op.call("bw_from_color", op.ptr, *op.geom(), op.c, optr)
     return op.wrap(out, 1)
 
 
@@ -391,9 +390,7 @@ def nms3x3(x, mode="product"):
     except KeyError:
         raise ValueError("mode must be 'product' or 'fired'")
     out, optr = op.alloc(op.c)
-    lib, ctx = _lib.load(), op.ctx
-    args = (ctx.handle, op.ptr) + op.geom() + (op.c, m, optr)
-    ctx.check(lib.silent_nms3x3_dev(*(args + (op.stream,))) if op.dev else lib.silent_nms3x3(*args))
+    op.call("nms3x3", op.ptr, *op.geom(), op.c, m, optr)
     return op.wrap(out, op.c)
 
 
@@ -405,9 +402,7 @@ def top_value_points(color, top_percent=0.1, value=None):
         _same_geometry(op, vop, "top_value_points")
         vptr = vop.ptr
     out, optr = op.alloc(op.c)
-    lib, ctx = _lib.load(), op.ctx
-    args = (ctx.handle, op.ptr, vptr) + op.geom() + (op.c, float(top_percent), optr)
-    ctx.check(lib.silent_top_value_points_dev(*(args + (op.stream,))) if op.dev else lib.silent_top_value_points(*args))
+    op.call("top_value_points", op.ptr, vptr, *op.geom(), op.c, float(top_percent), optr)
     return op.wrap(out, op.c)
 
 
@@ -419,19 +414,9 @@ def max_value_indices_region(value, regions, cap_per_frame=None):
         raise ValueError("need one (rH, rW) region per level")
     reg = (_lib.Extent * op.n_levels)(*[_lib.Extent(int(rh), int(rw)) for rh, rw in regions])
     cap = op.frame_px if cap_per_frame is None else int(cap_per_frame)
-    lib, ctx = _lib.load(), op.ctx
-    if op.dev:
-        import torch
-        idx = torch.empty((op.n_frames, cap, 4), dtype=torch.int64, device=op._torch_device)
-        counts = torch.empty(op.n_frames, dtype=torch.int64, device=op._torch_device)
-        ctx.check(lib.silent_max_value_indices_region_dev(ctx.handle, op.ptr, op.levels, op.n_levels, op.n_frames, reg,
-                                                          C.c_void_p(idx.data_ptr()), cap,
-                                                          C.c_void_p(counts.data_ptr()), op.stream))
-        return idx, counts
-    idx = np.empty((op.n_frames, cap, 4), dtype=np.int64)
-    counts = np.empty(op.n_frames, dtype=np.int64)
-    ctx.check(lib.silent_max_value_indices_region(ctx.handle, op.ptr, op.levels, op.n_levels, op.n_frames, reg,
-                                                  C.c_void_p(idx.ctypes.data), cap, C.c_void_p(counts.ctypes.data)))
+    idx, iptr = op.empty((op.n_frames, cap, 4), np.int64)
+    counts, cptr = op.empty(op.n_frames, np.int64)
+    op.call("max_value_indices_region", op.ptr, *op.geom(), reg, iptr, cap, cptr)
     return idx, counts
 
 
@@ -449,9 +434,7 @@ def select_peaks(color, top_percent=0.1, value=None, want=("top", "peaks", "peak
             outs[name], ptrs[name] = op.alloc(ch)
         else:
             ptrs[name] = None
-    lib, ctx = _lib.load(), op.ctx
-    args = (ctx.handle, op.ptr, vptr) + op.geom() + (op.c, float(top_percent), ptrs["top"], ptrs["peaks"], ptrs["peak_value"])
-    ctx.check(lib.silent_select_peaks_dev(*(args + (op.stream,))) if op.dev else lib.silent_select_peaks(*args))
+    op.call("select_peaks", op.ptr, vptr, *op.geom(), op.c, float(top_percent), ptrs["top"], ptrs["peaks"], ptrs["peak_value"])
     return {n: op.wrap(o, 1 if n == "peak_value" else op.c) for n, o in outs.items()}
 
 
@@ -464,16 +447,8 @@ def centroids(value, region_h, region_w):
     cell_ext = [(-(-h // rh), -(-w // rw)) for h, w in op.extents]
     n_cells = op.n_frames * sum(a * b for a, b in cell_ext)
     dist, dptr = op.alloc(1)
-    lib, ctx = _lib.load(), op.ctx
-    if op.dev:
-        import torch
-        tot = torch.empty(n_cells, dtype=torch.float32, device=op._torch_device)
-        tptr = C.c_void_p(tot.data_ptr())
-    else:
-        tot = np.empty(n_cells, dtype=np.float32)
-        tptr = C.c_void_p(tot.ctypes.data)
-    args = (ctx.handle, op.ptr) + op.geom() + (rh, rw, dptr, tptr)
-    ctx.check(lib.silent_centroids_dev(*(args + (op.stream,))) if op.dev else lib.silent_centroids(*args))
+    tot, tptr = op.empty(n_cells)
+    op.call("centroids", op.ptr, *op.geom(), rh, rw, dptr, tptr)
     if op.packed:
         return op.wrap(dist, 1), PackedPyramid(tot, cell_ext, 1, op.n_frames)
     return op.wrap(dist, 1), tot.reshape(op.n_frames, cell_ext[0][0], cell_ext[0][1], 1)
@@ -505,9 +480,7 @@ def boosting_step(x, energy, exhaustion_max=1.0, excitation_max=1.0, recovery_mo
     eout, eptr = op.alloc(c)
     params = _lib.BoostingParams(float(exhaustion_max), float(excitation_max), int(recovery_mode),
                                  float(recovery_amount), float(recovery_percentage), 1 if visualize else 0)
-    lib, ctx = _lib.load(), op.ctx
-    args = (ctx.handle, op.ptr) + op.geom() + (C.byref(params), st.ptr, fptr, eptr)
-    ctx.check(lib.silent_boosting_step_dev(*(args + (op.stream,))) if op.dev else lib.silent_boosting_step(*args))
+    op.call("boosting_step", op.ptr, *op.geom(), C.byref(params), st.ptr, fptr, eptr)
     return op.wrap(fired, c), op.wrap(eout, c)
 
 
@@ -516,10 +489,7 @@ def affine_clip(x, mul=1.0, add=0.0, lo=-float("inf"), hi=float("inf"), post_add
     op = _Operand(x)
     out, optr = op.alloc(op.c)
     params = _lib.AffineParams(float(mul), float(div), float(add), float(lo), float(hi), float(post_add))
-    lib, ctx = _lib.load(), op.ctx
-    n = op.n_frames * op.frame_px * op.c
-    args = (ctx.handle, op.ptr, n, C.byref(params), optr)
-    ctx.check(lib.silent_affine_clip_dev(*(args + (op.stream,))) if op.dev else lib.silent_affine_clip(*args))
+    op.call("affine_clip", op.ptr, op.n_frames * op.frame_px * op.c, C.byref(params), optr)
     return op.wrap(out, op.c)
 
 
@@ -552,17 +522,8 @@ def resize_nearest(x, out_extents):
     if len(out_extents) != op.n_levels or min(min(e) for e in out_extents) < 1:
         raise ValueError("resize_nearest: need one positive (h, w) per level")
     out_levels = (_lib.Extent * op.n_levels)(*[_lib.Extent(h, w) for h, w in out_extents])
-    n = op.n_frames * sum(h * w for h, w in out_extents) * op.c
-    lib, ctx = _lib.load(), op.ctx
-    if op.dev:
-        import torch
-        out = torch.empty(n, dtype=torch.float32, device=op._torch_device)
-        optr = C.c_void_p(out.data_ptr())
-    else:
-        out = np.empty(n, dtype=np.float32)
-        optr = C.c_void_p(out.ctypes.data)
-    args = (ctx.handle, op.ptr) + op.geom() + (op.c, out_levels, optr)
-    ctx.check(lib.silent_resize_nearest_dev(*(args + (op.stream,))) if op.dev else lib.silent_resize_nearest(*args))
+    out, optr = op.empty(op.n_frames * sum(h * w for h, w in out_extents) * op.c)
+    op.call("resize_nearest", op.ptr, *op.geom(), op.c, out_levels, optr)
     if op.packed:
         return PackedPyramid(out, out_extents, op.c, op.n_frames)
     return out.reshape(op.n_frames, out_extents[0][0], out_extents[0][1], op.c)
@@ -590,9 +551,7 @@ def rgb_line_end(x, kernels, regulation_value=1.0, regulation_root=0.1, flat_pol
             outs[name], ptrs[name] = op.alloc(ch)
         else:
             ptrs[name] = None
-    lib, ctx = _lib.load(), op.ctx
-    args = (ctx.handle, op.ptr) + op.geom() + (C.byref(params), ptrs["orient"], ptrs["line_end"], ptrs["value"])
-    ctx.check(lib.silent_rgb_line_end_dev(*(args + (op.stream,))) if op.dev else lib.silent_rgb_line_end(*args))
+    op.call("rgb_line_end", op.ptr, *op.geom(), C.byref(params), ptrs["orient"], ptrs["line_end"], ptrs["value"])
     return {n: op.wrap(o, 1 if n == "value" else 3) for n, o in outs.items()}
 
 
@@ -769,31 +728,20 @@ class PyramidPlan(object):
                                                               C.byref(self.handle)))
         self.frame_px = sum(h * w for h, w in self.extents)
 
+    def _frames(self, frames):
+        """[n, H, W, C] frames of this plan (ndarray, or torch GPU tensor) as an operand on the plan's context."""
+        if not (isinstance(frames, np.ndarray) or is_torch_tensor(frames)):
+            raise TypeError(TYPE_ERROR_MESSAGE)
+        if tuple(frames.shape[1:]) != self.frame_shape:
+            raise ValueError("frames must be [n, %d, %d, %d], got %s" % (self.frame_shape + (tuple(frames.shape),)))
+        return _Operand(frames, ctx=self.ctx)
+
     def run(self, frames):
         """frames: [n, H, W, C] ndarray (host) or torch GPU tensor.  Returns a PackedPyramid."""
-        h, w, c = self.frame_shape
-        lib = _lib.load()
-        if is_torch_tensor(frames):
-            import torch
-            if tuple(frames.shape[1:]) != (h, w, c):
-                raise ValueError("frames must be [n, %d, %d, %d]" % (h, w, c))
-            f = as_float32(frames)
-            n = int(f.shape[0])
-            out = torch.empty(n * self.frame_px * c, dtype=torch.float32, device=f.device)
-            stream = C.c_void_p(torch.cuda.current_stream(f.device).cuda_stream)
-            self.ctx.check(lib.silent_pyramid_dev(self.ctx.handle, self.handle, C.c_void_p(f.data_ptr()), n,
-                                                  C.c_void_p(out.data_ptr()), stream))
-            return PackedPyramid(out, self.extents, c, n)
-        if not isinstance(frames, np.ndarray):
-            raise TypeError(TYPE_ERROR_MESSAGE)
-        if tuple(frames.shape[1:]) != (h, w, c):
-            raise ValueError("frames must be [n, %d, %d, %d], got %s" % (h, w, c, frames.shape))
-        f = np.ascontiguousarray(frames, dtype=np.float32)
-        n = f.shape[0]
-        out = np.empty(n * self.frame_px * c, dtype=np.float32)
-        self.ctx.check(lib.silent_pyramid(self.ctx.handle, self.handle, C.c_void_p(f.ctypes.data), n,
-                                          C.c_void_p(out.ctypes.data)))
-        return PackedPyramid(out, self.extents, c, n)
+        op, c = self._frames(frames), self.frame_shape[2]
+        out, optr = op.empty(op.n_frames * self.frame_px * c)
+        op.call("pyramid", self.handle, op.ptr, op.n_frames, optr)
+        return PackedPyramid(out, self.extents, c, op.n_frames)
 
     @property
     def streamable(self):
@@ -810,41 +758,18 @@ class PyramidPlan(object):
     def gray_pass(self, frames, cs_kernel, end_bank, clip_hi=255.0):
         """Whole grayscale hot path (silent_gray_pass): frames [n,H,W,1] -> (pyramid, cs, end) PackedPyramids.
         Same results as run() + gray_line_end(), one pass less over level 0."""
-        h, w, c = self.frame_shape
-        if c != 1:
+        if self.frame_shape[2] != 1:
             raise ValueError("gray_pass needs a single-channel plan")
         cs = _kernel_arg(cs_kernel, 1)
         eb = _kernel_arg(end_bank, 1)
         if cs.shape != (3, 3, 1, 1) or eb.shape[:3] != (3, 3, 1):
             raise ValueError("gray_pass needs a [3,3,1,1] CS kernel and a [3,3,1,K] end bank")
         K = eb.shape[3]
-        lib = _lib.load()
-        if is_torch_tensor(frames):
-            import torch
-            if tuple(frames.shape[1:]) != (h, w, c):
-                raise ValueError("frames must be [n, %d, %d, 1]" % (h, w))
-            f = as_float32(frames)
-            n = int(f.shape[0])
-            mk = lambda ch: torch.empty(n * self.frame_px * ch, dtype=torch.float32, device=f.device)
-            pyr, cso, endo = mk(1), mk(1), mk(K)
-            stream = C.c_void_p(torch.cuda.current_stream(f.device).cuda_stream)
-            self.ctx.check(lib.silent_gray_pass_dev(self.ctx.handle, self.handle, C.c_void_p(f.data_ptr()), n,
-                                                    C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K,
-                                                    float(clip_hi), C.c_void_p(pyr.data_ptr()),
-                                                    C.c_void_p(cso.data_ptr()), C.c_void_p(endo.data_ptr()), stream))
-        else:
-            if not isinstance(frames, np.ndarray):
-                raise TypeError(TYPE_ERROR_MESSAGE)
-            if tuple(frames.shape[1:]) != (h, w, c):
-                raise ValueError("frames must be [n, %d, %d, 1], got %s" % (h, w, frames.shape))
-            f = np.ascontiguousarray(frames, dtype=np.float32)
-            n = f.shape[0]
-            mk = lambda ch: np.empty(n * self.frame_px * ch, dtype=np.float32)
-            pyr, cso, endo = mk(1), mk(1), mk(K)
-            self.ctx.check(lib.silent_gray_pass(self.ctx.handle, self.handle, C.c_void_p(f.ctypes.data), n,
-                                                C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K,
-                                                float(clip_hi), C.c_void_p(pyr.ctypes.data),
-                                                C.c_void_p(cso.ctypes.data), C.c_void_p(endo.ctypes.data)))
+        op = self._frames(frames)
+        n = op.n_frames
+        (pyr, pp), (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch) for ch in (1, 1, K)]
+        op.call("gray_pass", self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi),
+                pp, cp, ep)
         P = PackedPyramid
         return P(pyr, self.extents, 1, n), P(cso, self.extents, 1, n), P(endo, self.extents, K, n)
 

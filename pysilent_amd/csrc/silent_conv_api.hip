@@ -109,15 +109,12 @@ SILENT_EXPORT int silent_conv2d_same(silent_ctx* ctx, const float* in, const sil
     if (c_in < 1 || c_out < 1) return fail(ctx, SILENT_E_INVALID, "silent_conv2d_same: channels must be >= 1");
     long long px;
     TRY(check_levels(ctx, "silent_conv2d_same", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
-    const size_t bi = (size_t)px * c_in * 4, bo = (size_t)px * c_out * 4;
-    const size_t i_in = st.add(bi), i_out = st.add(bo);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_in), in, bi));
-    TRY(silent_conv2d_same_dev(ctx, st.ptr<float>(i_in), levels, n_levels, n_frames, c_in, k, kh, kw, c_out, flags,
-                               clip_hi, st.ptr<float>(i_out), nullptr));
-    TRY(sync0(ctx));
-    return d2h(ctx, out, st.ptr<float>(i_out), bo);
+    HostStage hs(ctx);
+    const int x = hs.in(in, (size_t)px * c_in * 4), o = hs.out(out, (size_t)px * c_out * 4);
+    return hs.run([&] {
+        return silent_conv2d_same_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, c_in, k, kh, kw, c_out, flags, clip_hi,
+                                      hs.dev<float>(o), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_conv2d_same");
 }
@@ -130,15 +127,13 @@ SILENT_EXPORT int silent_regulate(silent_ctx* ctx, const float* in, const silent
     if (channels < 1) return fail(ctx, SILENT_E_INVALID, "silent_regulate: channels must be >= 1");
     long long px;
     TRY(check_levels(ctx, "silent_regulate", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
+    HostStage hs(ctx);
     const size_t b = (size_t)px * channels * 4;
-    const size_t i_in = st.add(b), i_out = st.add(b);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_in), in, b));
-    TRY(silent_regulate_dev(ctx, st.ptr<float>(i_in), levels, n_levels, n_frames, channels, blur, kh, kw, rv, root,
-                            flat_policy, st.ptr<float>(i_out), nullptr));
-    TRY(sync0(ctx));
-    return d2h(ctx, out, st.ptr<float>(i_out), b);
+    const int x = hs.in(in, b), o = hs.out(out, b);
+    return hs.run([&] {
+        return silent_regulate_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, channels, blur, kh, kw, rv, root, flat_policy,
+                                   hs.dev<float>(o), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_regulate");
 }

@@ -357,16 +357,23 @@ long long pyramid_px(const silent_extent* levels, int n_levels) {
 
 // ------------------------------------------------------------------------------------------ host-pointer twins: staging
 
-int h2d(silent_ctx* ctx, void* d, const void* h, size_t bytes) {
-    HIP_TRY(ctx, hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
+int HostStage::add(void* h, size_t bytes, bool in, bool out, bool staged) {
+    bufs_.push_back({h, used_, bytes, in, out, staged});
+    if (staged) used_ += align_up(bytes ? bytes : 1);
+    return (int)bufs_.size() - 1;
+}
+
+int HostStage::copy_in() {
+    TRY(grow(ctx_, ctx_->arena, used_));
+    for (const Buf& b : bufs_)
+        if (b.in && b.host && b.bytes) HIP_TRY(ctx_, hipMemcpy((char*)ctx_->arena.p + b.off, b.host, b.bytes, hipMemcpyHostToDevice));
     return SILENT_OK;
 }
-int d2h(silent_ctx* ctx, void* h, const void* d, size_t bytes) {
-    HIP_TRY(ctx, hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost));
-    return SILENT_OK;
-}
-int sync0(silent_ctx* ctx) {
-    HIP_TRY(ctx, hipStreamSynchronize(nullptr));
+
+int HostStage::copy_out() {
+    HIP_TRY(ctx_, hipStreamSynchronize(nullptr));
+    for (const Buf& b : bufs_)
+        if (b.out && b.host && b.bytes) HIP_TRY(ctx_, hipMemcpy(b.host, (char*)ctx_->arena.p + b.off, b.bytes, hipMemcpyDeviceToHost));
     return SILENT_OK;
 }
 

@@ -175,18 +175,13 @@ SILENT_EXPORT int silent_gray_line_end(silent_ctx* ctx, const float* pyr, const 
     if (n_orient < 1 || n_orient > 8) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_gray_line_end: n_orient must be 3, 4 or 8");
     long long px;
     TRY(check_levels(ctx, "silent_gray_line_end", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
-    const size_t b1 = (size_t)px * 4, bk = (size_t)px * n_orient * 4;
-    const size_t i_in = st.add(b1), i_cs = st.add(b1), i_end = st.add(bk);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_in), pyr, b1));
-    TRY(silent_gray_line_end_dev(ctx, st.ptr<float>(i_in), levels, n_levels, n_frames, cs_kernel, end_bank, n_orient,
-                                 clip_hi, cs_out ? st.ptr<float>(i_cs) : nullptr,
-                                 end_out ? st.ptr<float>(i_end) : nullptr, nullptr));
-    TRY(sync0(ctx));
-    if (cs_out) TRY(d2h(ctx, cs_out, st.ptr<float>(i_cs), b1));
-    if (end_out) TRY(d2h(ctx, end_out, st.ptr<float>(i_end), bk));
-    return SILENT_OK;
+    HostStage hs(ctx);
+    const size_t b1 = (size_t)px * 4;
+    const int x = hs.in(pyr, b1), cs = hs.out(cs_out, b1), end = hs.out(end_out, b1 * n_orient);
+    return hs.run([&] {
+        return silent_gray_line_end_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, cs_kernel, end_bank, n_orient, clip_hi,
+                                        hs.dev<float>(cs), hs.dev<float>(end), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_gray_line_end");
 }
@@ -198,21 +193,14 @@ SILENT_EXPORT int silent_gray_pass(silent_ctx* ctx, const silent_pyramid_plan* p
     if (!plan || !frames || !pyr) return fail(ctx, SILENT_E_INVALID, "silent_gray_pass: NULL pointer");
     if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, "silent_gray_pass: n_frames must be >= 1");
     if (n_orient < 1 || n_orient > 8) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_gray_pass: n_orient must be 3, 4 or 8");
-    Stage st(ctx);
-    const size_t px = (size_t)plan->tab.frame_px_out * n_frames;
-    const size_t bi = (size_t)plan->tab.H * plan->tab.W * plan->tab.C * 4 * n_frames;
-    const size_t b1 = px * 4, bk = px * n_orient * 4;
-    const size_t i_in = st.add(bi), i_p = st.add(b1), i_cs = st.add(b1), i_end = st.add(bk);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_in), frames, bi));
-    TRY(silent_gray_pass_dev(ctx, plan, st.ptr<float>(i_in), n_frames, cs_kernel, end_bank, n_orient, clip_hi,
-                             st.ptr<float>(i_p), cs_out ? st.ptr<float>(i_cs) : nullptr,
-                             end_out ? st.ptr<float>(i_end) : nullptr, nullptr));
-    TRY(sync0(ctx));
-    TRY(d2h(ctx, pyr, st.ptr<float>(i_p), b1));
-    if (cs_out) TRY(d2h(ctx, cs_out, st.ptr<float>(i_cs), b1));
-    if (end_out) TRY(d2h(ctx, end_out, st.ptr<float>(i_end), bk));
-    return SILENT_OK;
+    HostStage hs(ctx);
+    const size_t b1 = (size_t)plan->tab.frame_px_out * n_frames * 4;
+    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * plan->tab.C * 4 * n_frames), p = hs.out(pyr, b1),
+              cs = hs.out(cs_out, b1), end = hs.out(end_out, b1 * n_orient);
+    return hs.run([&] {
+        return silent_gray_pass_dev(ctx, plan, hs.dev<float>(x), n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
+                                    hs.dev<float>(cs), hs.dev<float>(end), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_gray_pass");
 }

@@ -126,26 +126,36 @@ int check_launch(silent_ctx* ctx, const char* what);
 long long pyramid_px(const silent_extent* levels, int n_levels);
 
 // ------------------------------------------------------------------------------------------ host-pointer twins
-// Synchronous: stage inputs into the context arena, run the *_dev twin on the default stream, copy back.
-
-struct Stage {
-    silent_ctx* ctx;
-    size_t used = 0;
-    std::vector<size_t> offs;
-    explicit Stage(silent_ctx* c) : ctx(c) {}
-    size_t add(size_t bytes) {
-        offs.push_back(used);
-        used += align_up(bytes ? bytes : 1);
-        return offs.size() - 1;
-    }
-    int commit() { return grow(ctx, ctx->arena, used); }
+// Synchronous: stage the buffers in the context arena, run the *_dev twin on the default stream, copy back.  A twin declares
+// its buffers -- in, out, inout, or scratch (a device buffer the *_dev form needs and the caller did not ask for); a NULL host
+// pointer gets a NULL device pointer and no arena space -- then run(call) commits the arena, copies the inputs in, makes the
+// call and, if it succeeded, synchronises and copies the outputs back, each in declaration order.  Zero-byte copies are skipped.
+class HostStage {
+public:
+    explicit HostStage(silent_ctx* ctx) : ctx_(ctx) {}
+    int in(const void* h, size_t bytes) { return add(const_cast<void*>(h), bytes, true, false, h != nullptr); }
+    int out(void* h, size_t bytes) { return add(h, bytes, false, true, h != nullptr); }
+    int inout(void* h, size_t bytes) { return add(h, bytes, true, true, h != nullptr); }
+    int scratch(size_t bytes) { return add(nullptr, bytes, false, false, true); }
     template <class T>
-    T* ptr(size_t i) const { return (T*)((char*)ctx->arena.p + offs[i]); }
+    T* dev(int i) const { return bufs_[i].staged ? (T*)((char*)ctx_->arena.p + bufs_[i].off) : nullptr; }
+    template <class F>
+    int run(F&& call) {
+        TRY(copy_in());
+        TRY(call());
+        return copy_out();
+    }
+
+private:
+    struct Buf { void* host; size_t off, bytes; bool in, out, staged; };
+    int add(void* h, size_t bytes, bool in, bool out, bool staged);
+    int copy_in();   // commit the arena, copy the inputs in
+    int copy_out();  // synchronise the default stream, copy the outputs back
+    silent_ctx* ctx_;
+    size_t used_ = 0;
+    std::vector<Buf> bufs_;
 };
 
-int h2d(silent_ctx* ctx, void* d, const void* h, size_t bytes);
-int d2h(silent_ctx* ctx, void* h, const void* d, size_t bytes);
-int sync0(silent_ctx* ctx);
 int check_levels(silent_ctx* ctx, const char* who, const silent_extent* levels, int n_levels, int n_frames, long long* px);
 
 // ------------------------------------------------------------------------------------------ across the families

@@ -788,15 +788,13 @@ SILENT_EXPORT int silent_pad_inwards(silent_ctx* ctx, const float* in, const sil
     if (channels < 1) return fail(ctx, SILENT_E_INVALID, "silent_pad_inwards: channels must be >= 1");
     long long px;
     TRY(check_levels(ctx, "silent_pad_inwards", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
+    HostStage hs(ctx);
     const size_t b = (size_t)px * channels * 4;
-    const size_t i_in = st.add(b), i_out = st.add(b);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_in), in, b));
-    TRY(silent_pad_inwards_dev(ctx, st.ptr<float>(i_in), levels, n_levels, n_frames, channels, pt, pb, pl, pr,
-                               st.ptr<float>(i_out), nullptr));
-    TRY(sync0(ctx));
-    return d2h(ctx, out, st.ptr<float>(i_out), b);
+    const int x = hs.in(in, b), o = hs.out(out, b);
+    return hs.run([&] {
+        return silent_pad_inwards_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, channels, pt, pb, pl, pr, hs.dev<float>(o),
+                                      nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_pad_inwards");
 }
@@ -808,15 +806,11 @@ SILENT_EXPORT int silent_value_from_color(silent_ctx* ctx, const float* in, cons
     if (channels < 1) return fail(ctx, SILENT_E_INVALID, "silent_value_from_color: channels must be >= 1");
     long long px;
     TRY(check_levels(ctx, "silent_value_from_color", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
-    const size_t bi = (size_t)px * channels * 4, bo = (size_t)px * 4;
-    const size_t i_in = st.add(bi), i_out = st.add(bo);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_in), in, bi));
-    TRY(silent_value_from_color_dev(ctx, st.ptr<float>(i_in), levels, n_levels, n_frames, channels,
-                                    st.ptr<float>(i_out), nullptr));
-    TRY(sync0(ctx));
-    return d2h(ctx, out, st.ptr<float>(i_out), bo);
+    HostStage hs(ctx);
+    const int x = hs.in(in, (size_t)px * channels * 4), o = hs.out(out, (size_t)px * 4);
+    return hs.run([&] {
+        return silent_value_from_color_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, channels, hs.dev<float>(o), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_value_from_color");
 }
@@ -828,15 +822,11 @@ SILENT_EXPORT int silent_bw_from_color(silent_ctx* ctx, const float* in, const s
     if (channels < 1) return fail(ctx, SILENT_E_INVALID, "silent_bw_from_color: channels must be >= 1");
     long long px;
     TRY(check_levels(ctx, "silent_bw_from_color", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
-    const size_t bi = (size_t)px * channels * 4, bo = (size_t)px * 4;
-    const size_t i_in = st.add(bi), i_out = st.add(bo);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_in), in, bi));
-    TRY(silent_bw_from_color_dev(ctx, st.ptr<float>(i_in), levels, n_levels, n_frames, channels,
-                                    st.ptr<float>(i_out), nullptr));
-    TRY(sync0(ctx));
-    return d2h(ctx, out, st.ptr<float>(i_out), bo);
+    HostStage hs(ctx);
+    const int x = hs.in(in, (size_t)px * channels * 4), o = hs.out(out, (size_t)px * 4);
+    return hs.run([&] {
+        return silent_bw_from_color_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, channels, hs.dev<float>(o), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_bw_from_color");
 }
@@ -848,15 +838,12 @@ SILENT_EXPORT int silent_nms3x3(silent_ctx* ctx, const float* in, const silent_e
     if (channels < 1) return fail(ctx, SILENT_E_INVALID, "silent_nms3x3: channels must be >= 1");
     long long px;
     TRY(check_levels(ctx, "silent_nms3x3", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
+    HostStage hs(ctx);
     const size_t b = (size_t)px * channels * 4;
-    const size_t i_in = st.add(b), i_out = st.add(b);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_in), in, b));
-    TRY(silent_nms3x3_dev(ctx, st.ptr<float>(i_in), levels, n_levels, n_frames, channels, mode, st.ptr<float>(i_out),
-                          nullptr));
-    TRY(sync0(ctx));
-    return d2h(ctx, out, st.ptr<float>(i_out), b);
+    const int x = hs.in(in, b), o = hs.out(out, b);
+    return hs.run([&] {
+        return silent_nms3x3_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, channels, mode, hs.dev<float>(o), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_nms3x3");
 }
@@ -869,16 +856,13 @@ SILENT_EXPORT int silent_top_value_points(silent_ctx* ctx, const float* color, c
     if (channels < 1) return fail(ctx, SILENT_E_INVALID, "silent_top_value_points: channels must be >= 1");
     long long px;
     TRY(check_levels(ctx, "silent_top_value_points", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
-    const size_t bc = (size_t)px * channels * 4, bv = (size_t)px * 4;
-    const size_t i_c = st.add(bc), i_v = st.add(bv), i_o = st.add(bc);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_c), color, bc));
-    if (value) TRY(h2d(ctx, st.ptr<float>(i_v), value, bv));
-    TRY(silent_top_value_points_dev(ctx, st.ptr<float>(i_c), value ? st.ptr<float>(i_v) : nullptr, levels, n_levels,
-                                    n_frames, channels, top_percent, st.ptr<float>(i_o), nullptr));
-    TRY(sync0(ctx));
-    return d2h(ctx, out, st.ptr<float>(i_o), bc);
+    HostStage hs(ctx);
+    const size_t bc = (size_t)px * channels * 4;
+    const int c = hs.in(color, bc), v = hs.in(value, (size_t)px * 4), o = hs.out(out, bc);
+    return hs.run([&] {
+        return silent_top_value_points_dev(ctx, hs.dev<float>(c), hs.dev<float>(v), levels, n_levels, n_frames, channels, top_percent,
+                                           hs.dev<float>(o), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_top_value_points");
 }
@@ -890,21 +874,19 @@ SILENT_EXPORT int silent_max_value_indices_region(silent_ctx* ctx, const float* 
     if (!value || !counts) return fail(ctx, SILENT_E_INVALID, "silent_max_value_indices_region: NULL pointer");
     long long px;
     TRY(check_levels(ctx, "silent_max_value_indices_region", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
-    const size_t bv = (size_t)px * 4, bi = (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t);
-    const size_t bc = (size_t)n_frames * sizeof(int64_t);
-    const size_t i_v = st.add(bv), i_i = st.add(bi), i_c = st.add(bc);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_v), value, bv));
-    TRY(silent_max_value_indices_region_dev(ctx, st.ptr<float>(i_v), levels, n_levels, n_frames, regions,
-                                            st.ptr<int64_t>(i_i), cap_per_frame, st.ptr<int64_t>(i_c), nullptr));
-    TRY(sync0(ctx));
-    TRY(d2h(ctx, counts, st.ptr<int64_t>(i_c), bc));
+    HostStage hs(ctx);
+    // idx: only the first min(count, cap) rows of each frame are copied back, below
+    const int v = hs.in(value, (size_t)px * 4), i = hs.scratch((size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
+              c = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
+    TRY(hs.run([&] {
+        return silent_max_value_indices_region_dev(ctx, hs.dev<float>(v), levels, n_levels, n_frames, regions, hs.dev<int64_t>(i),
+                                                   cap_per_frame, hs.dev<int64_t>(c), nullptr);
+    }));
     bool over = false;
     for (int f = 0; f < n_frames; ++f) {
-        const size_t n = (size_t)std::min<int64_t>(counts[f], (int64_t)cap_per_frame);
+        const size_t n = (size_t)std::min<int64_t>(counts[f], (int64_t)cap_per_frame), row = (size_t)f * cap_per_frame * 4;
         if (counts[f] > (int64_t)cap_per_frame) over = true;
-        if (n) TRY(d2h(ctx, idx + (size_t)f * cap_per_frame * 4, st.ptr<int64_t>(i_i) + (size_t)f * cap_per_frame * 4, n * 4 * sizeof(int64_t)));
+        if (n) HIP_TRY(ctx, hipMemcpy(idx + row, hs.dev<int64_t>(i) + row, n * 4 * sizeof(int64_t), hipMemcpyDeviceToHost));
     }
     if (over) return fail(ctx, SILENT_E_CAPACITY, "silent_max_value_indices_region: cap_per_frame too small; counts hold the need");
     return SILENT_OK;
@@ -921,24 +903,18 @@ SILENT_EXPORT int silent_rgb_keypoints(silent_ctx* ctx, const float* pyr, const 
         return fail(ctx, SILENT_E_INVALID, "silent_rgb_keypoints: NULL pointer");
     long long px;
     TRY(check_levels(ctx, "silent_rgb_keypoints", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
-    const size_t b3 = (size_t)px * 3 * 4, b1 = (size_t)px * 4;
-    const size_t bi = (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t), bn = (size_t)n_frames * sizeof(int64_t);
-    const size_t i_in = st.add(b3), i_o = st.add(b3), i_l = st.add(b3), i_v = st.add(b1), i_p = st.add(b1), i_i = st.add(bi),
-                 i_n = st.add(bn);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_in), pyr, b3));
-    TRY(silent_rgb_keypoints_dev(ctx, st.ptr<float>(i_in), levels, n_levels, n_frames, p, top_percent, regions,
-                                 orient_out ? st.ptr<float>(i_o) : nullptr, st.ptr<float>(i_l),
-                                 value_out ? st.ptr<float>(i_v) : nullptr, peak_value_out ? st.ptr<float>(i_p) : nullptr,
-                                 st.ptr<int64_t>(i_i), cap_per_frame, st.ptr<int64_t>(i_n), nullptr));
-    TRY(sync0(ctx));
-    if (orient_out) TRY(d2h(ctx, orient_out, st.ptr<float>(i_o), b3));
-    if (line_end_out) TRY(d2h(ctx, line_end_out, st.ptr<float>(i_l), b3));
-    if (value_out) TRY(d2h(ctx, value_out, st.ptr<float>(i_v), b1));
-    if (peak_value_out) TRY(d2h(ctx, peak_value_out, st.ptr<float>(i_p), b1));
-    if (cap_per_frame) TRY(d2h(ctx, idx, st.ptr<int64_t>(i_i), bi));
-    return d2h(ctx, counts, st.ptr<int64_t>(i_n), bn);
+    HostStage hs(ctx);
+    const size_t b1 = (size_t)px * 4, b3 = b1 * 3;
+    // the *_dev form always needs the line-end map (the keypoints are taken from it)
+    const int x = hs.in(pyr, b3), o = hs.out(orient_out, b3), l = line_end_out ? hs.out(line_end_out, b3) : hs.scratch(b3),
+              v = hs.out(value_out, b1), pv = hs.out(peak_value_out, b1),
+              i = hs.out(idx, (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
+              n = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
+    return hs.run([&] {
+        return silent_rgb_keypoints_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, p, top_percent, regions, hs.dev<float>(o),
+                                        hs.dev<float>(l), hs.dev<float>(v), hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame,
+                                        hs.dev<int64_t>(n), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_rgb_keypoints");
 }
@@ -951,16 +927,13 @@ SILENT_EXPORT int silent_centroids(silent_ctx* ctx, const float* value, const si
     TRY(check_levels(ctx, "silent_centroids", levels, n_levels, n_frames, &px));
     CellTab ct;
     TRY(build_cell_tab(ctx, "silent_centroids", levels, n_levels, region_h, region_w, &ct));
-    Stage st(ctx);
-    const size_t bv = (size_t)px * 4, bt = (size_t)ct.frame_cells * n_frames * 4;
-    const size_t i_v = st.add(bv), i_d = st.add(bv), i_t = st.add(bt);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_v), value, bv));
-    TRY(silent_centroids_dev(ctx, st.ptr<float>(i_v), levels, n_levels, n_frames, region_h, region_w,
-                             st.ptr<float>(i_d), st.ptr<float>(i_t), nullptr));
-    TRY(sync0(ctx));
-    TRY(d2h(ctx, dist_out, st.ptr<float>(i_d), bv));
-    return d2h(ctx, total_out, st.ptr<float>(i_t), bt);
+    HostStage hs(ctx);
+    const int v = hs.in(value, (size_t)px * 4), d = hs.out(dist_out, (size_t)px * 4),
+              t = hs.out(total_out, (size_t)ct.frame_cells * n_frames * 4);
+    return hs.run([&] {
+        return silent_centroids_dev(ctx, hs.dev<float>(v), levels, n_levels, n_frames, region_h, region_w, hs.dev<float>(d),
+                                    hs.dev<float>(t), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_centroids");
 }
@@ -974,18 +947,13 @@ SILENT_EXPORT int silent_boosting_step(silent_ctx* ctx, const float* input, cons
     TRY(check_boost_params(ctx, params, &bp));
     long long px;
     TRY(check_levels(ctx, "silent_boosting_step", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
+    HostStage hs(ctx);
     const size_t b1 = (size_t)px * 4, bc = b1 * (bp.visualize ? 3 : 1);
-    const size_t i_x = st.add(b1), i_e = st.add(b1), i_f = st.add(bc), i_o = st.add(bc);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_x), input, b1));
-    TRY(h2d(ctx, st.ptr<float>(i_e), energy, b1));
-    TRY(silent_boosting_step_dev(ctx, st.ptr<float>(i_x), levels, n_levels, n_frames, params, st.ptr<float>(i_e),
-                                 st.ptr<float>(i_f), energy_out ? st.ptr<float>(i_o) : nullptr, nullptr));
-    TRY(sync0(ctx));
-    TRY(d2h(ctx, energy, st.ptr<float>(i_e), b1));
-    TRY(d2h(ctx, fired_out, st.ptr<float>(i_f), bc));
-    return energy_out ? d2h(ctx, energy_out, st.ptr<float>(i_o), bc) : SILENT_OK;
+    const int x = hs.in(input, b1), e = hs.inout(energy, b1), f = hs.out(fired_out, bc), o = hs.out(energy_out, bc);
+    return hs.run([&] {
+        return silent_boosting_step_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, params, hs.dev<float>(e), hs.dev<float>(f),
+                                        hs.dev<float>(o), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_boosting_step");
 }
@@ -995,14 +963,9 @@ SILENT_EXPORT int silent_affine_clip(silent_ctx* ctx, const float* in, size_t n_
     NEED_CTX(ctx);
     if (!in || !out || !params) return fail(ctx, SILENT_E_INVALID, "silent_affine_clip: NULL pointer");
     if (n_values == 0) return fail(ctx, SILENT_E_INVALID, "silent_affine_clip: empty tensor");
-    Stage st(ctx);
-    const size_t b = n_values * 4;
-    const size_t i_x = st.add(b);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_x), in, b));
-    TRY(silent_affine_clip_dev(ctx, st.ptr<float>(i_x), n_values, params, st.ptr<float>(i_x), nullptr));
-    TRY(sync0(ctx));
-    return d2h(ctx, out, st.ptr<float>(i_x), b);
+    HostStage hs(ctx);
+    const int x = hs.in(in, n_values * 4), o = hs.out(out, n_values * 4);
+    return hs.run([&] { return silent_affine_clip_dev(ctx, hs.dev<float>(x), n_values, params, hs.dev<float>(o), nullptr); });
 } catch (...) {
     return on_exception(ctx, "silent_affine_clip");
 }
@@ -1016,18 +979,15 @@ SILENT_EXPORT int silent_cast_interleave(silent_ctx* ctx, const void* in, int in
     if (n_pixels == 0 || in_stride < 1 || out_stride < 1) return fail(ctx, SILENT_E_INVALID, "silent_cast_interleave: empty tensor");
     if (count < 1 || in_offset < 0 || out_offset < 0 || in_stride < in_offset + count || out_stride < out_offset + count)
         return fail(ctx, SILENT_E_INVALID, "silent_cast_interleave: need 0 <= offset and offset + count <= stride on both sides");
-    Stage st(ctx);
+    HostStage hs(ctx);
     // the last pixel needs offset + count elements, not a whole stride: a caller's buffer may end with its last used element
-    const size_t bi = ((n_pixels - 1) * (size_t)in_stride + (size_t)(in_offset + count)) * es;
-    const size_t bo = ((n_pixels - 1) * (size_t)out_stride + (size_t)(out_offset + count)) * 4;
-    const size_t i_x = st.add(bi), i_o = st.add(bo);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<char>(i_x), in, bi));
-    TRY(h2d(ctx, st.ptr<float>(i_o), out, bo));      // the elements of out that this call does not write keep their values
-    TRY(silent_cast_interleave_dev(ctx, st.ptr<char>(i_x), in_dtype, n_pixels, in_stride, in_offset, count, st.ptr<float>(i_o),
-                                   out_stride, out_offset, nullptr));
-    TRY(sync0(ctx));
-    return d2h(ctx, out, st.ptr<float>(i_o), bo);
+    const int x = hs.in(in, ((n_pixels - 1) * (size_t)in_stride + (size_t)(in_offset + count)) * es);
+    // in / out: the elements of out that this call does not write keep their values
+    const int o = hs.inout(out, ((n_pixels - 1) * (size_t)out_stride + (size_t)(out_offset + count)) * 4);
+    return hs.run([&] {
+        return silent_cast_interleave_dev(ctx, hs.dev<char>(x), in_dtype, n_pixels, in_stride, in_offset, count, hs.dev<float>(o),
+                                          out_stride, out_offset, nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_cast_interleave");
 }
@@ -1040,15 +1000,12 @@ SILENT_EXPORT int silent_resize_nearest(silent_ctx* ctx, const float* in, const 
     long long ipx, opx;
     TRY(check_levels(ctx, "silent_resize_nearest", in_levels, n_levels, n_frames, &ipx));
     TRY(check_levels(ctx, "silent_resize_nearest", out_levels, n_levels, n_frames, &opx));
-    Stage st(ctx);
-    const size_t bi = (size_t)ipx * channels * 4, bo = (size_t)opx * channels * 4;
-    const size_t i_x = st.add(bi), i_o = st.add(bo);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_x), in, bi));
-    TRY(silent_resize_nearest_dev(ctx, st.ptr<float>(i_x), in_levels, n_levels, n_frames, channels, out_levels,
-                                  st.ptr<float>(i_o), nullptr));
-    TRY(sync0(ctx));
-    return d2h(ctx, out, st.ptr<float>(i_o), bo);
+    HostStage hs(ctx);
+    const int x = hs.in(in, (size_t)ipx * channels * 4), o = hs.out(out, (size_t)opx * channels * 4);
+    return hs.run([&] {
+        return silent_resize_nearest_dev(ctx, hs.dev<float>(x), in_levels, n_levels, n_frames, channels, out_levels, hs.dev<float>(o),
+                                         nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_resize_nearest");
 }
@@ -1062,21 +1019,14 @@ SILENT_EXPORT int silent_select_peaks(silent_ctx* ctx, const float* color, const
     if (channels != 1 && channels != 3) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_select_peaks: channels must be 1 or 3");
     long long px;
     TRY(check_levels(ctx, "silent_select_peaks", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
+    HostStage hs(ctx);
     const size_t bc = (size_t)px * channels * 4, bv = (size_t)px * 4;
-    const size_t i_c = st.add(bc), i_v = st.add(bv), i_t = st.add(bc), i_p = st.add(bc), i_o = st.add(bv);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_c), color, bc));
-    if (value) TRY(h2d(ctx, st.ptr<float>(i_v), value, bv));
-    TRY(silent_select_peaks_dev(ctx, st.ptr<float>(i_c), value ? st.ptr<float>(i_v) : nullptr, levels, n_levels, n_frames,
-                                channels, top_percent, top_out ? st.ptr<float>(i_t) : nullptr,
-                                peaks_out ? st.ptr<float>(i_p) : nullptr, peak_value_out ? st.ptr<float>(i_o) : nullptr,
-                                nullptr));
-    TRY(sync0(ctx));
-    if (top_out) TRY(d2h(ctx, top_out, st.ptr<float>(i_t), bc));
-    if (peaks_out) TRY(d2h(ctx, peaks_out, st.ptr<float>(i_p), bc));
-    if (peak_value_out) TRY(d2h(ctx, peak_value_out, st.ptr<float>(i_o), bv));
-    return SILENT_OK;
+    const int c = hs.in(color, bc), v = hs.in(value, bv), t = hs.out(top_out, bc), pk = hs.out(peaks_out, bc),
+              pv = hs.out(peak_value_out, bv);
+    return hs.run([&] {
+        return silent_select_peaks_dev(ctx, hs.dev<float>(c), hs.dev<float>(v), levels, n_levels, n_frames, channels, top_percent,
+                                       hs.dev<float>(t), hs.dev<float>(pk), hs.dev<float>(pv), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_select_peaks");
 }
@@ -1091,20 +1041,15 @@ SILENT_EXPORT int silent_select_keypoints(silent_ctx* ctx, const float* color, c
     if (channels != 1 && channels != 3) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_select_keypoints: channels must be 1 or 3");
     long long px;
     TRY(check_levels(ctx, "silent_select_keypoints", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
-    const size_t bc = (size_t)px * channels * 4, bv = (size_t)px * 4;
-    const size_t bi = (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t), bn = (size_t)n_frames * sizeof(int64_t);
-    const size_t i_c = st.add(bc), i_v = st.add(bv), i_o = st.add(bv), i_i = st.add(bi), i_n = st.add(bn);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_c), color, bc));
-    if (value) TRY(h2d(ctx, st.ptr<float>(i_v), value, bv));
-    TRY(silent_select_keypoints_dev(ctx, st.ptr<float>(i_c), value ? st.ptr<float>(i_v) : nullptr, levels, n_levels, n_frames,
-                                    channels, top_percent, regions, peak_value_out ? st.ptr<float>(i_o) : nullptr,
-                                    st.ptr<int64_t>(i_i), cap_per_frame, st.ptr<int64_t>(i_n), nullptr));
-    TRY(sync0(ctx));
-    if (peak_value_out) TRY(d2h(ctx, peak_value_out, st.ptr<float>(i_o), bv));
-    if (cap_per_frame) TRY(d2h(ctx, idx, st.ptr<int64_t>(i_i), bi));
-    return d2h(ctx, counts, st.ptr<int64_t>(i_n), bn);
+    HostStage hs(ctx);
+    const size_t bv = (size_t)px * 4;
+    const int c = hs.in(color, bv * channels), v = hs.in(value, bv), pv = hs.out(peak_value_out, bv),
+              i = hs.out(idx, (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
+              n = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
+    return hs.run([&] {
+        return silent_select_keypoints_dev(ctx, hs.dev<float>(c), hs.dev<float>(v), levels, n_levels, n_frames, channels, top_percent,
+                                           regions, hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame, hs.dev<int64_t>(n), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_select_keypoints");
 }

@@ -702,15 +702,10 @@ SILENT_EXPORT int silent_pyramid(silent_ctx* ctx, const silent_pyramid_plan* pla
     NEED_CTX(ctx);
     if (!plan || !frames || !pyr) return fail(ctx, SILENT_E_INVALID, "silent_pyramid: NULL pointer");
     if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, "silent_pyramid: n_frames must be >= 1");
-    Stage st(ctx);
-    const size_t bi = (size_t)plan->tab.H * plan->tab.W * plan->tab.C * 4 * n_frames;
-    const size_t bo = (size_t)plan->tab.frame_px_out * plan->tab.C * 4 * n_frames;
-    const size_t i_in = st.add(bi), i_out = st.add(bo);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_in), frames, bi));
-    TRY(silent_pyramid_dev(ctx, plan, st.ptr<float>(i_in), n_frames, st.ptr<float>(i_out), nullptr));
-    TRY(sync0(ctx));
-    return d2h(ctx, pyr, st.ptr<float>(i_out), bo);
+    HostStage hs(ctx);
+    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * plan->tab.C * 4 * n_frames),
+              o = hs.out(pyr, (size_t)plan->tab.frame_px_out * plan->tab.C * 4 * n_frames);
+    return hs.run([&] { return silent_pyramid_dev(ctx, plan, hs.dev<float>(x), n_frames, hs.dev<float>(o), nullptr); });
 } catch (...) {
     return on_exception(ctx, "silent_pyramid");
 }

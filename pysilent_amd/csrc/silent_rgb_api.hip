@@ -443,19 +443,13 @@ SILENT_EXPORT int silent_rgb_line_end(silent_ctx* ctx, const float* pyr, const s
     if (!pyr || !p) return fail(ctx, SILENT_E_INVALID, "silent_rgb_line_end: NULL pointer");
     long long px;
     TRY(check_levels(ctx, "silent_rgb_line_end", levels, n_levels, n_frames, &px));
-    Stage st(ctx);
-    const size_t b3 = (size_t)px * 3 * 4, b1 = (size_t)px * 4;
-    const size_t i_in = st.add(b3), i_o = st.add(b3), i_l = st.add(b3), i_v = st.add(b1);
-    TRY(st.commit());
-    TRY(h2d(ctx, st.ptr<float>(i_in), pyr, b3));
-    TRY(silent_rgb_line_end_dev(ctx, st.ptr<float>(i_in), levels, n_levels, n_frames, p,
-                                orient_out ? st.ptr<float>(i_o) : nullptr, line_end_out ? st.ptr<float>(i_l) : nullptr,
-                                value_out ? st.ptr<float>(i_v) : nullptr, nullptr));
-    TRY(sync0(ctx));
-    if (orient_out) TRY(d2h(ctx, orient_out, st.ptr<float>(i_o), b3));
-    if (line_end_out) TRY(d2h(ctx, line_end_out, st.ptr<float>(i_l), b3));
-    if (value_out) TRY(d2h(ctx, value_out, st.ptr<float>(i_v), b1));
-    return SILENT_OK;
+    HostStage hs(ctx);
+    const size_t b1 = (size_t)px * 4, b3 = b1 * 3;
+    const int x = hs.in(pyr, b3), o = hs.out(orient_out, b3), l = hs.out(line_end_out, b3), v = hs.out(value_out, b1);
+    return hs.run([&] {
+        return silent_rgb_line_end_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, p, hs.dev<float>(o), hs.dev<float>(l),
+                                       hs.dev<float>(v), nullptr);
+    });
 } catch (...) {
     return on_exception(ctx, "silent_rgb_line_end");
 }

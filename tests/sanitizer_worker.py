@@ -78,7 +78,7 @@ def one_plan():
 def one_op():
     n_levels, n_frames = int(rng.integers(1, 7)), int(rng.integers(1, 3))
     ext = extents(n_levels)
-    which = int(rng.integers(0, 16))
+    which = int(rng.integers(0, 17))
     stats["ops"] += 1
     if which == 0:
         kh = int(rng.choice([1, 3, 5, 7]))
@@ -135,6 +135,8 @@ def one_op():
         src = np.zeros((n_px - 1) * cin + io + count, dt)
         dst = np.zeros((n_px - 1) * cout + oo + count, np.float32)
         ctx.check(lib.silent_cast_interleave(ctx.handle, src.ctypes.data, code, n_px, cin, io, count, dst.ctypes.data, cout, oo))
+    elif which == 15:
+        select_keypoints_host(ext, n_frames)
     else:
         fp = C.POINTER(C.c_float)
         ks = {k: np.ascontiguousarray(v, np.float32) for k, v in RGB.items()}
@@ -164,6 +166,24 @@ def rgb_keypoints_host(ext, n_frames, cap=None):
                                   orient.ctypes.data, line.ctypes.data, None, pv.ctypes.data if pv is not None else None,
                                   idx.ctypes.data, cap, counts.ctypes.data)
     assert rc in (_lib.SILENT_OK, _lib.SILENT_E_CAPACITY), _lib.last_error(ctx.handle)
+
+
+def select_keypoints_host(ext, n_frames):
+    """silent_select_keypoints (host form) with and without the peak-value map, at a cap_per_frame below a frame's pixel count
+    (0: no idx at all)."""
+    c = int(rng.choice([1, 3]))
+    x = packed(ext, c, n_frames)
+    px = x.frame_px * n_frames
+    value = rng.random(px, dtype=np.float32) if rng.integers(2) else None
+    levels = (_lib.Extent * len(ext))(*[_lib.Extent(h, w) for h, w in ext])
+    regions = (_lib.Extent * len(ext))(*[_lib.Extent(max(h // 2, 1), max(w // 2, 1)) for h, w in ext])
+    cap = int(rng.integers(0, x.frame_px))
+    idx, counts = np.zeros((n_frames, max(cap, 1), 4), np.int64), np.zeros(n_frames, np.int64)
+    for pv in (None, np.zeros(px, np.float32)):
+        rc = lib.silent_select_keypoints(ctx.handle, x.data.ctypes.data, value.ctypes.data if value is not None else None, levels,
+                                         len(ext), n_frames, c, 0.1, regions, pv.ctypes.data if pv is not None else None,
+                                         idx.ctypes.data if cap else None, cap, counts.ctypes.data)
+        assert rc in (_lib.SILENT_OK, _lib.SILENT_E_CAPACITY), _lib.last_error(ctx.handle)
 
 
 def displayer_frames(n_frames=3, native_dtype=None):
