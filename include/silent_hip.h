@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SILENT_ABI_VERSION 4
+#define SILENT_ABI_VERSION 5
 #define SILENT_MAX_LEVELS 16
 #define SILENT_MAX_KERNEL_FLOATS 784 /* kh*kw*C_in*C_out limit (weights travel as kernel arguments) */
 
@@ -282,7 +282,7 @@ int silent_max_value_indices_region_dev(silent_ctx* ctx, const float* value, con
  * (_experimental/vision_filter.py:88-89) -> get_value_from_color (util/color/get_value.py:6-12) in one streaming
  * pass after the per-level max / min reduction: bit-identical to silent_top_value_points + silent_nms3x3 +
  * silent_value_from_color, without the two intermediate colour maps in HBM.  value may be NULL (computed from color).
- * Any of top_out [C ch], peaks_out [C ch], peak_value_out [1 ch] may be NULL, not all.  channels: 1 or 3. */
+ * Any of top_out [C ch], peaks_out [C ch], peak_value_out [1 ch] may be NULL, not all.  channels: 1, 3, 4 or 8. */
 int silent_select_peaks(silent_ctx* ctx, const float* color, const float* value, const silent_extent* levels,
                         int n_levels, int n_frames, int channels, double top_percent, float* top_out,
                         float* peaks_out, float* peak_value_out);
@@ -443,7 +443,28 @@ int silent_rgb_keypoints_dev(silent_ctx* ctx, const float* pyr, const silent_ext
                              float* orient_out, float* line_end_out, float* value_out, float* peak_value_out, int64_t* idx,
                              size_t cap_per_frame, int64_t* counts, silent_stream stream);
 
-/* What the sparse tail of the LAST silent_rgb_keypoints[_dev] call of this context did (synchronises that call's stream):
+/* BASELINE configs 1 / 2 / 5 with keypoints: silent_gray_pass (pyr, cs_out, end_out bit-identical to it for the same arguments;
+ * end_out stays UNPADDED) followed by the reference graph's tail restricted to one input channel (recognition_testing.py:75-90)
+ * on its K-channel end map: color = pad_inwards(end, pad), value = get_value_from_color(color), then
+ *   selection = 1: top_value_points -> 3x3 NMS (product form) -> get_value_from_color -> max_value_indices_region, i.e.
+ *                  silent_select_keypoints(color, value, channels = K); sparse like silent_rgb_keypoints (the kernels that write
+ *                  `end` leave the per-level extrema, the value summary and NaN flags; SILENT_TUNE_GRAY bit 6 forces the dense kernels);
+ *   selection = 0: max_value_indices_region on value (recognition_testing.py:90).
+ * end_out is required (the keypoints are taken from it; the host form accepts NULL pyr / end_out), cs_out may be NULL;
+ * value_out [1 ch] and peak_value_out [1 ch, selection = 1 only] may be NULL.  regions: one silent_extent per level of the plan.
+ * idx / cap_per_frame / counts as silent_max_value_indices_region (the host form returns SILENT_E_CAPACITY, the _dev form leaves
+ * the overflow in counts).  n_orient: 3, 4 or 8; pad >= 0.  silent_sparse_tail_stats reports on the last call. */
+int silent_gray_keypoints(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
+                          const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out,
+                          float* end_out, int pad, int selection, double top_percent, const silent_extent* regions,
+                          float* value_out, float* peak_value_out, int64_t* idx, size_t cap_per_frame, int64_t* counts);
+int silent_gray_keypoints_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
+                              const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                              float* cs_out, float* end_out, int pad, int selection, double top_percent,
+                              const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+                              size_t cap_per_frame, int64_t* counts, silent_stream stream);
+
+/* What the sparse tail of the LAST silent_rgb_keypoints[_dev] / silent_gray_keypoints[_dev] call of this context did (synchronises that call's stream):
  * stats[0] = 1 if it ran sparse, [1] = (frame, level) pairs, [2] = pairs it handed to the dense kernels, [3] = candidate
  * pixels (value >= threshold) it evaluated, [4] = pairs settled with a synthesised all-zero map (a search window without a
  * positive peak in a level without NaNs: every pixel mapped to it is a keypoint).  stats holds 5 values.  For tests and the

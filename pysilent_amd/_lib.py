@@ -31,7 +31,7 @@ MAX_LEVELS = 16
 TUNE_GRAY, TUNE_RGB, TUNE_PYRAMID = 0, 1, 2
 GRAY_PART_PYRAMID, GRAY_PART_FILTER = 1, 2
 DT_U8, DT_F32, DT_F64, DT_I32, DT_U16, DT_I16, DT_I64 = 0, 1, 2, 3, 4, 5, 6
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class Extent(C.Structure):
@@ -141,6 +141,8 @@ _SIGNATURES = {
     "silent_rgb_chain_structure": [C.POINTER(RgbChainParams), C.POINTER(C.c_uint), C.POINTER(C.c_uint)],
     "silent_rgb_keypoints": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _d, _ep, _fp, _fp, _fp, _fp, _vp, _sz, _vp],
     "silent_rgb_keypoints_dev": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _d, _ep, _fp, _fp, _fp, _fp, _vp, _sz, _vp, _vp],
+    "silent_gray_keypoints": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp],
+    "silent_gray_keypoints_dev": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp, _vp],
     "silent_sparse_tail_stats": [_vp, C.POINTER(C.c_int64)],
     "silent_rgb_chain_stream": [C.POINTER(RgbChainParams), C.c_uint, _fp, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "silent_rgb_line_end": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _fp, _fp, _fp],

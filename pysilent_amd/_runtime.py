@@ -773,6 +773,33 @@ class PyramidPlan(object):
         P = PackedPyramid
         return P(pyr, self.extents, 1, n), P(cso, self.extents, 1, n), P(endo, self.extents, K, n)
 
+    def gray_keypoints(self, frames, cs_kernel, end_bank, clip_hi=255.0, pad=2, selection=True, top_percent=0.1, regions=None,
+                       cap_per_frame=None):
+        """silent_gray_keypoints (host form): gray_pass + pad_inwards -> value -> [top_value_points -> NMS -> value ->]
+        max_value_indices_region on the K-channel end map.  Returns (pyramid, cs, end, idx [n, cap, 4], counts [n])."""
+        if self.frame_shape[2] != 1:
+            raise ValueError("gray_keypoints needs a single-channel plan")
+        cs = _kernel_arg(cs_kernel, 1)
+        eb = _kernel_arg(end_bank, 1)
+        if cs.shape != (3, 3, 1, 1) or eb.shape[:3] != (3, 3, 1):
+            raise ValueError("gray_keypoints needs a [3,3,1,1] CS kernel and a [3,3,1,K] end bank")
+        if regions is None:
+            regions = [(max(h // 2, 1), max(w // 2, 1)) for h, w in self.extents]
+        if len(regions) != len(self.extents):
+            raise ValueError("need one (rH, rW) region per level")
+        reg = (_lib.Extent * len(regions))(*[_lib.Extent(int(rh), int(rw)) for rh, rw in regions])
+        K = eb.shape[3]
+        op = self._frames(frames)
+        n = op.n_frames
+        cap = self.frame_px if cap_per_frame is None else int(cap_per_frame)
+        (pyr, pp), (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch) for ch in (1, 1, K)]
+        idx, iptr = op.empty((n, cap, 4), np.int64)
+        counts, cptr = op.empty(n, np.int64)
+        op.call("gray_keypoints", self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi),
+                pp, cp, ep, int(pad), int(selection), float(top_percent), reg, None, None, iptr, cap, cptr)
+        P = PackedPyramid
+        return P(pyr, self.extents, 1, n), P(cso, self.extents, 1, n), P(endo, self.extents, K, n), idx, counts
+
     def close(self):
         if self.handle:
             _lib.load().silent_pyramid_plan_destroy(self.handle)

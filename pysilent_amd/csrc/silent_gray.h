@@ -57,11 +57,78 @@ __device__ __forceinline__ void store_row_k8(float* __restrict__ row_base /* add
     }
 }
 
-template <int K, int R>
+// ---- keypoint epilogue (KP instantiations, silent_gray_keypoints): the selection tail's inputs from the registers that hold a
+// pixel's K end values, so that nothing re-reads the end map for a reduction.  Per pixel the value of the PADDED map, with the
+// operations of pad_inwards_kernel (m * e) and value_from_color_kernel (sum left to right, one multiply by 1/K); per lane the
+// running max_pool(value) / max_pool(-value) and the summary group's maximum (pool_max: NaNs never win, like level_maxmin_kernel);
+// per wave one atomic pair per tile and a NaN flag.  The summary entry of a pixel pair is stored by its even lane: every wave
+// starts at an even column, so the pair partner is lane ^ 1.  Every pointer of GrayKp may be NULL (that part is skipped).
+struct GrayKp {
+    unsigned* mm;                      // [n_frames][n_levels][2] ordered-uint max_pool(value) / max_pool(-value) (silent_peaks.h)
+    float* sum;                        // value summary (SumTab geometry, th = the kernel's tile height)
+    int* nan_flags;                    // [n_frames][n_levels]: set to 1 when a value of that level is a NaN (with mm)
+    float* value_out;                  // the 1-channel value map
+    long long sum_frame;               // summary entries per frame
+    long long sum_off[kMaxLevels];     // entry offset of level l inside a frame
+    int n_levels, pad, gpt;            // gpt: summary groups per tile row
+    int level[kMaxLevels];             // gray_unit_fused_kernel / gray_stream_kernel: plan level of unit level li
+};
+
+struct GrayKpAcc {
+    float mx = kPoolLowest, nmn = kPoolLowest, grp = kPoolLowest;
+    bool nan = false;
+};
+
+template <int K>
+__device__ __forceinline__ void gray_kp_pixel(const GrayKp& kp, const float (&acc)[K], int y, int x, int H, int W, bool valid,
+                                              float* __restrict__ value_px, GrayKpAcc& a) {
+    const float m = (y >= kp.pad && y < H - kp.pad && x >= kp.pad && x < W - kp.pad) ? 1.0f : 0.0f;
+    float s = __fmul_rn(m, acc[0]);
+#pragma unroll
+    for (int k = 1; k < K; ++k) s = __fadd_rn(s, __fmul_rn(m, acc[k]));
+    const float v = __fmul_rn(s, 1.0f / (float)K);
+    if (valid) {
+        a.mx = pool_max(a.mx, v);
+        a.nmn = pool_max(a.nmn, -v);
+        a.grp = pool_max(a.grp, v);
+        a.nan = a.nan || v != v;
+        if (kp.value_out) *value_px = v;
+    }
+}
+
+// end of summary group g of tile row ty (every lane of the wave calls it)
+__device__ __forceinline__ void gray_kp_group_end(const GrayKp& kp, GrayKpAcc& a, int frame, int level, int ty, int g, int x, int W,
+                                                  bool out_lane) {
+    if (!kp.sum) return;
+    const float pair = pool_max(a.grp, __shfl_xor(a.grp, 1));
+    const int nxp = (W + 1) >> 1;
+    if (out_lane && !(x & 1))
+        kp.sum[(long long)frame * kp.sum_frame + kp.sum_off[level] + ((long long)ty * kp.gpt + g) * nxp + (x >> 1)] = pair;
+    a.grp = kPoolLowest;
+}
+
+// end of the tile (every lane of the wave calls it)
+__device__ __forceinline__ void gray_kp_tile_end(const GrayKp& kp, const GrayKpAcc& a, int frame, int level, int lane) {
+    if (!kp.mm) return;
+    const float mx = wave_max(a.mx), nmn = wave_max(a.nmn);
+    const bool nan = __ballot(a.nan) != 0ull;
+    if (lane == 0) {
+        unsigned* slot = kp.mm + ((long long)frame * kp.n_levels + level) * 2;
+        atomicMax(slot, f2ord(mx));
+        atomicMax(slot + 1, f2ord(nmn));
+        if (nan && kp.nan_flags) kp.nan_flags[frame * kp.n_levels + level] = 1;
+    }
+}
+
+// (summary groups: kSumRows output rows; a tile's last group may be shorter)
+__host__ __device__ constexpr bool kp_group_ends(int k, int R) { return ((k + 1) % kSumRows) == 0 || k == R - 1; }
+
+template <int K, int R, bool KP = false>
 __global__ __launch_bounds__(256) void gray_line_end_kernel(const float* __restrict__ pyr,
                                                             float* __restrict__ cs_out,
                                                             float* __restrict__ end_out, const LevelTab tab,
-                                                            const GrayW wts, float clip_hi, unsigned opts) {
+                                                            const GrayW wts, float clip_hi, unsigned opts,
+                                                            const GrayKp kp = GrayKp{}) {
     __shared__ __attribute__((aligned(16))) float s_slab[K == 8 ? 4 * 512 : 4];  // K = 8 store transpose, per wave
     const TileCoord tc = locate_tile(tab, (opts & 1u) ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x);
     const int H = tab.h[tc.level], W = tab.w[tc.level];
@@ -98,6 +165,7 @@ __global__ __launch_bounds__(256) void gray_line_end_kernel(const float* __restr
 #pragma unroll
         for (int b = 0; b < 3; ++b) iw[a][b] = cw[a][b] = 0.0f;
     const bool out_lane = lane >= 2 && lane < 2 + kGrayCols && x < W;
+    GrayKpAcc ka;
 
 #pragma unroll
     for (int i = 0; i < R + 4; ++i) {
@@ -146,6 +214,7 @@ __global__ __launch_bounds__(256) void gray_line_end_kernel(const float* __restr
                             for (int k = 0; k < K; ++k)
                                 acc[k] = __builtin_fmaf(cw[dy][dx], wts.end[(dy * 3 + dx) * K + k], acc[k]);
                     relu_clip_tf(acc, clip_hi);
+                    if constexpr (KP) gray_kp_pixel<K>(kp, acc, y, x, H, W, out_lane, kp.value_out + px, ka);
                     if constexpr (K == 8) {
                         // lane 0's pixel is column xw0 - 2; valid pixels are lanes 2 .. 2 + ncols
                         const int ncols = min(kGrayCols, W - xw0);
@@ -164,8 +233,12 @@ __global__ __launch_bounds__(256) void gray_line_end_kernel(const float* __restr
                     }
                 }
             }
+            if constexpr (KP) {
+                if (kp_group_ends(i - 4, R)) gray_kp_group_end(kp, ka, tc.frame, tc.level, tc.ty, (i - 4) / kSumRows, x, W, out_lane);
+            }
         }
     }
+    if constexpr (KP) gray_kp_tile_end(kp, ka, tc.frame, tc.level, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -215,11 +288,11 @@ struct FusedTab {
     FusedLevel lv[kMaxLevels];
 };
 
-template <int K, int R>
+template <int K, int R, bool KP = false>
 __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const float* __restrict__ frames,
                                                               float* __restrict__ pyr, float* __restrict__ cs_out,
                                                               float* __restrict__ end_out, const FusedTab tab,
-                                                              const GrayW wts, float clip_hi) {
+                                                              const GrayW wts, float clip_hi, const GrayKp kp = GrayKp{}) {
     __shared__ __attribute__((aligned(16))) float s_slab[K == 8 ? kFusedWaves * 512 : 4];  // K = 8 store transpose, per wave
     const unsigned bid = blockIdx.x;
     const int frame = (int)(bid / (unsigned)tab.tiles_per_frame);
@@ -255,6 +328,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
 
     const bool col_in = ox >= 0 && ox < lv.out_w;                  // inside the level (SAME padding is 0 outside)
     const bool out_lane = lane >= 4 && lane < 4 + kFusedCols && ox < lv.out_w;
+    GrayKpAcc ka;
     float hw[6] = {0, 0, 0, 0, 0, 0};
     float iw[3][3], cw[3][3];
 #pragma unroll
@@ -326,6 +400,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
                             for (int k = 0; k < K; ++k)
                                 acc[k] = __builtin_fmaf(cw[dy][dx], wts.end[(dy * 3 + dx) * K + k], acc[k]);
                     relu_clip_tf(acc, clip_hi);
+                    if constexpr (KP) gray_kp_pixel<K>(kp, acc, y, ox, lv.out_h, lv.out_w, out_lane, kp.value_out + px, ka);
                     if constexpr (K == 8) {
                         const int ncols = min(kFusedCols, lv.out_w - xw0);
                         store_row_k8(end_out + (base_px + (long long)y * lv.out_w + (xw0 - 4)) * 8, acc,
@@ -341,8 +416,12 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
                     }
                 }
             }
+            if constexpr (KP) {
+                if (kp_group_ends(i - 9, R)) gray_kp_group_end(kp, ka, frame, kp.level[li], ty, (i - 9) / kSumRows, ox, lv.out_w, out_lane);
+            }
         }
     }
+    if constexpr (KP) gray_kp_tile_end(kp, ka, frame, kp.level[li], lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -426,11 +505,11 @@ __device__ __forceinline__ StreamCol stream_col(const StreamTab& st, int g, int 
 #endif
 constexpr int kStreamRegLevels = SILENT_STREAM_REG_LEVELS;
 
-template <int K, int G, int L = 0>
+template <int K, int G, int L = 0, bool KP = false>
 __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const float* __restrict__ frames, float* __restrict__ pyr,
                                                           float* __restrict__ cs_out, float* __restrict__ end_out,
                                                           const FusedTab tab, const StreamTab st, const GrayW wts,
-                                                          float clip_hi, unsigned opts) {
+                                                          float clip_hi, unsigned opts, const GrayKp kp = GrayKp{}) {
     constexpr int R = kFusedTH, NR = kStreamRows;
     __shared__ __attribute__((aligned(16))) float s_slab[K == 8 ? kFusedWaves * 512 : 4];
     __shared__ __attribute__((aligned(16))) float s_rows[kFusedWaves][NR][64];  // the streamed rows of each wave (wave private)
@@ -586,6 +665,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
     // placements and + 0.5 ... 1.3 % on fast ones, config 2 + 10 ... 14 % on every placement (the barrier ties four waves that
     // otherwise drift freely).  With the placement tuner choosing the fast relation it only costs: dropped (commit 02244a6 has it).)
     {
+        GrayKpAcc ka;
         float hw[6] = {0, 0, 0, 0, 0, 0};
         float iw[3][3], cw[3][3];
 #pragma unroll
@@ -661,6 +741,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
                                     else acc[k] = __builtin_fmaf(cw[dy][dx], wts.end[wi], acc[k]);
                                 }
                         relu_clip_tf(acc, clip_hi);
+                        if constexpr (KP) gray_kp_pixel<K>(kp, acc, y, ox, lv.out_h, lv.out_w, out_lane, kp.value_out + row_px + lane, ka);
                         if constexpr (K == 8) {
                             const int ncols = min(kFusedCols, lv.out_w - xw0);
                             store_row_k8<true>(end_out + row_px * 8, acc, s_slab + wave * 512, lane, 4, ncols);
@@ -679,8 +760,12 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
                         }
                     }
                 }
+                if constexpr (KP) {
+                    if (kp_group_ends(i - 9, R)) gray_kp_group_end(kp, ka, frame, kp.level[0], ty, (i - 9) / kSumRows, ox, lv.out_w, out_lane);
+                }
             }
         }
+        if constexpr (KP) gray_kp_tile_end(kp, ka, frame, kp.level[0], lane);
     }
 }
 

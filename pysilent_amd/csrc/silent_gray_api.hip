@@ -8,7 +8,7 @@ using namespace silent;
 
 static int launch_gray(silent_ctx* ctx, const char* who, const float* pyr, const silent_extent* levels, int n_levels,
                        int n_frames, const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi,
-                       float* cs_out, float* end_out, hipStream_t s, const bool* skip) {
+                       float* cs_out, float* end_out, hipStream_t s, const bool* skip, const GrayKp* kp = nullptr) {
     if (!pyr || !cs_kernel) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (!cs_out && !end_out) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": both outputs are NULL");
     if (end_out && !end_bank) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": end_bank is NULL");
@@ -27,11 +27,15 @@ static int launch_gray(silent_ctx* ctx, const char* who, const float* pyr, const
     std::memset(&w, 0, sizeof(w));
     std::memcpy(w.cs, cs_kernel, sizeof(float) * 9);
     if (end_bank) std::memcpy(w.end, end_bank, sizeof(float) * 9 * n_orient);
-#define GRAY_LAUNCH(K_, R_) \
-    hipLaunchKernelGGL((gray_line_end_kernel<K_, R_>), dim3((unsigned)blocks), dim3(256), 0, s, pyr, cs_out, end_out, tab, w, clip_hi, opts)
-    if (n_orient == 3) GRAY_LAUNCH(3, kGrayTH);
-    else if (n_orient == 4) GRAY_LAUNCH(4, kGrayTH);
-    else GRAY_LAUNCH(8, kGrayTH);
+#define GRAY_LAUNCH(K_, R_)                                                                                                          \
+    if (kp)                                                                                                                          \
+        hipLaunchKernelGGL((gray_line_end_kernel<K_, R_, true>), dim3((unsigned)blocks), dim3(256), 0, s, pyr, cs_out, end_out, tab, w, \
+                           clip_hi, opts, *kp);                                                                                      \
+    else                                                                                                                             \
+        hipLaunchKernelGGL((gray_line_end_kernel<K_, R_>), dim3((unsigned)blocks), dim3(256), 0, s, pyr, cs_out, end_out, tab, w, clip_hi, opts)
+    if (n_orient == 3) { GRAY_LAUNCH(3, kGrayTH); }
+    else if (n_orient == 4) { GRAY_LAUNCH(4, kGrayTH); }
+    else { GRAY_LAUNCH(8, kGrayTH); }
 #undef GRAY_LAUNCH
     return check_launch(ctx, who);
 }
@@ -51,7 +55,7 @@ SILENT_EXPORT int silent_gray_line_end_dev(silent_ctx* ctx, const float* pyr, co
 // (step 3, which reads the pyramid steps 1 and 2 wrote)
 static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
                            const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
-                           float* cs_out, float* end_out, unsigned parts, silent_stream stream) {
+                           float* cs_out, float* end_out, unsigned parts, silent_stream stream, const GrayKp* kp = nullptr) {
     const char* who = "silent_gray_pass";
     if (!plan || !frames || !pyr || !cs_kernel) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
@@ -75,10 +79,13 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
     std::memset(&ft, 0, sizeof(ft));
     bool is_unit[kMaxLevels] = {false};
     long long tiles = 0, unit_px = 0;
+    GrayKp kpu{};   // the unit levels' plan level numbers travel with the keypoint epilogue's arguments
+    if (kp) kpu = *kp;
     for (int l = 0; l < pt.n_levels; ++l) {
         const PyrLevelDev& d = pt.lv[l];
         if (d.kind != kPyrUnit) continue;
         is_unit[l] = true;
+        if (kp) kpu.level[ft.n] = l;
         if (ft.n == 0)
             for (int j = 0; j < 6; ++j) {  // every unit level has the same taps ([1,26,66,26,1]/120 and the sixth, 2^-53)
                 ft.wx[j] = plan->unit_w[j];
@@ -109,28 +116,36 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
         if (ctx->prof_sample) HIP_TRY(ctx, hipEventRecord(ctx->prof_ev[prof_slot][0], s));
         if (stream_path) {
             const StreamTab& st = plan->stream;
-#define STREAM_LAUNCH(K_, G_, L_) \
-    hipLaunchKernelGGL((gray_stream_kernel<K_, G_, L_>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, (unsigned)((kopts >> 5) & 1))
+#define STREAM_LAUNCH(K_, G_, L_)                                                                                                  \
+    if (kp)                                                                                                                        \
+        hipLaunchKernelGGL((gray_stream_kernel<K_, G_, L_, true>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, \
+                           cs_out, end_out, ft, st, w, clip_hi, (unsigned)((kopts >> 5) & 1), kpu);                                \
+    else                                                                                                                           \
+        hipLaunchKernelGGL((gray_stream_kernel<K_, G_, L_>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, (unsigned)((kopts >> 5) & 1))
             if (plan->stream_layout == 1) {          // zoom ladders of ratio 1.4 .. e^.5: five rows of the first level in flight
-                if (n_orient == 3) STREAM_LAUNCH(3, 7, 1);
-                else if (n_orient == 4) STREAM_LAUNCH(4, 7, 1);
-                else STREAM_LAUNCH(8, 7, 1);
+                if (n_orient == 3) { STREAM_LAUNCH(3, 7, 1); }
+                else if (n_orient == 4) { STREAM_LAUNCH(4, 7, 1); }
+                else { STREAM_LAUNCH(8, 7, 1); }
             } else if (st.G <= 4) {
-                if (n_orient == 3) STREAM_LAUNCH(3, 4, 0);
-                else if (n_orient == 4) STREAM_LAUNCH(4, 4, 0);
-                else STREAM_LAUNCH(8, 4, 0);
+                if (n_orient == 3) { STREAM_LAUNCH(3, 4, 0); }
+                else if (n_orient == 4) { STREAM_LAUNCH(4, 4, 0); }
+                else { STREAM_LAUNCH(8, 4, 0); }
             } else {
-                if (n_orient == 3) STREAM_LAUNCH(3, 7, 0);
-                else if (n_orient == 4) STREAM_LAUNCH(4, 7, 0);
-                else STREAM_LAUNCH(8, 7, 0);
+                if (n_orient == 3) { STREAM_LAUNCH(3, 7, 0); }
+                else if (n_orient == 4) { STREAM_LAUNCH(4, 7, 0); }
+                else { STREAM_LAUNCH(8, 7, 0); }
             }
 #undef STREAM_LAUNCH
         } else {
-#define FUSED_LAUNCH(K_, R_) \
-    hipLaunchKernelGGL((gray_unit_fused_kernel<K_, R_>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, cs_out, end_out, ft, w, clip_hi)
-            if (n_orient == 3) FUSED_LAUNCH(3, kFusedTH);
-            else if (n_orient == 4) FUSED_LAUNCH(4, kFusedTH);
-            else FUSED_LAUNCH(8, kFusedTH);
+#define FUSED_LAUNCH(K_, R_)                                                                                                        \
+    if (kp)                                                                                                                         \
+        hipLaunchKernelGGL((gray_unit_fused_kernel<K_, R_, true>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, \
+                           cs_out, end_out, ft, w, clip_hi, kpu);                                                                   \
+    else                                                                                                                            \
+        hipLaunchKernelGGL((gray_unit_fused_kernel<K_, R_>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, cs_out, end_out, ft, w, clip_hi)
+            if (n_orient == 3) { FUSED_LAUNCH(3, kFusedTH); }
+            else if (n_orient == 4) { FUSED_LAUNCH(4, kFusedTH); }
+            else { FUSED_LAUNCH(8, kFusedTH); }
 #undef FUSED_LAUNCH
         }
         if (ctx->prof_sample) {
@@ -143,8 +158,16 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
     // 3. CS + end on the remaining levels (they read the pyramid written in step 1)
     if (pt.n_general && (parts & 2u))
         TRY(launch_gray(ctx, who, pyr, plan->extents.data(), pt.n_levels, n_frames, cs_kernel, end_bank, n_orient,
-                        clip_hi, cs_out, end_out, s, is_unit));
+                        clip_hi, cs_out, end_out, s, is_unit, kp));
     return SILENT_OK;
+}
+
+// silent_gray_keypoints_dev (silent_peaks_api.hip): the whole pass with the keypoint epilogue in every kernel that writes `end`
+int gray_pass_kp(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames, const float* cs_kernel,
+                 const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const GrayKp& kp,
+                 hipStream_t s) {
+    return gray_pass_parts(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, 3u,
+                           (silent_stream)s, &kp);
 }
 
 SILENT_EXPORT int silent_gray_pass_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames,

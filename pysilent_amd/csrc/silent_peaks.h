@@ -314,12 +314,15 @@ constexpr int kSelCols = 60, kSelTW = 4 * kSelCols, kSelTH = 32;
 // CELLS: also fold the cell maxima of max_value_indices_region (region_cell_max_kernel) over the peak value into this
 // pass -- the lane's column segment is fixed, the row segment is wave-uniform, so it is one running maximum per lane
 // and a segmented wave reduction + one atomic per (row segment, column segment) and tile.
-template <int C, bool CELLS>
+// PAD: `color` is the UNPADDED map and every colour value read is multiplied by pad_inwards' 0 / 1 mask first (pad pixels at each
+// border of the level; silent_gray_keypoints, whose end map stays unpadded) -- the same operation as pad_inwards_kernel, so the
+// results are those of the padded map.
+template <int C, bool CELLS, bool PAD = false>
 __device__ __forceinline__ void select_peaks_tile(const float* __restrict__ color, const float* __restrict__ value,
                                                   float* __restrict__ top_out, float* __restrict__ peaks_out,
                                                   float* __restrict__ pv_out, const LevelTab& tab, float one_minus_p, float p_f,
                                                   const unsigned* __restrict__ mm, const RegionTab& rt, unsigned* __restrict__ cells,
-                                                  const int* __restrict__ dense_flags, unsigned tile) {
+                                                  const int* __restrict__ dense_flags, unsigned tile, int pad = 0) {
     constexpr int R = kSelTH;
     const TileCoord tc = locate_tile(tab, tile);
     // sparse tail (sparse_modes_kernel): only the (frame, level)s in dense mode run this pass
@@ -379,6 +382,12 @@ __device__ __forceinline__ void select_peaks_tile(const float* __restrict__ colo
             const long long px = base_px + (long long)min(max(y, 0), H - 1) * W + xc;
 #pragma unroll
             for (int c = 0; c < C; ++c) col[j][c] = color[px * C + c];
+            if constexpr (PAD) {
+                const int yc = min(max(y, 0), H - 1);
+                const float pm = (yc >= pad && yc < H - pad && xc >= pad && xc < W - pad) ? 1.0f : 0.0f;
+#pragma unroll
+                for (int c = 0; c < C; ++c) col[j][c] = __fmul_rn(pm, col[j][c]);
+            }
             val[j] = value ? value[px] : 0.0f;
         }
 #pragma unroll
@@ -448,7 +457,7 @@ __device__ __forceinline__ void select_peaks_tile(const float* __restrict__ colo
 }
 
 // n_tiles: tiles of `tab` (the sparse tail launches fewer blocks than that: for_live_tiles)
-template <int C, bool CELLS>
+template <int C, bool CELLS, bool PAD = false>
 __global__ __launch_bounds__(256) void select_peaks_kernel(const float* __restrict__ color,
                                                            const float* __restrict__ value,
                                                            float* __restrict__ top_out, float* __restrict__ peaks_out,
@@ -456,14 +465,17 @@ __global__ __launch_bounds__(256) void select_peaks_kernel(const float* __restri
                                                            float one_minus_p, float p_f,
                                                            const unsigned* __restrict__ mm, const RegionTab rt,
                                                            unsigned* __restrict__ cells,
-                                                           const int* __restrict__ dense_flags, unsigned n_tiles) {
+                                                           const int* __restrict__ dense_flags, unsigned n_tiles, int pad = 0) {
     for_live_tiles(
         n_tiles,
         [&](unsigned t) {
             const TileCoord tc = locate_tile(tab, t);
             return dense_flags[tc.frame * tab.n_levels + tc.level] == kTailDense;
         },
-        [&](unsigned t) { select_peaks_tile<C, CELLS>(color, value, top_out, peaks_out, pv_out, tab, one_minus_p, p_f, mm, rt, cells, dense_flags, t); });
+        [&](unsigned t) {
+            select_peaks_tile<C, CELLS, PAD>(color, value, top_out, peaks_out, pv_out, tab, one_minus_p, p_f, mm, rt, cells, dense_flags, t,
+                                             pad);
+        });
 }
 
 
@@ -746,27 +758,40 @@ struct Candidate {
 // t_c = color_c * (value >= thr ? 1 : 0) of pixel (y, x) as select_peaks_kernel computes it; lowest() outside the level
 // (max_pool SAME ignores such taps).  The address is clamped and the load unconditional: the 9 taps of a passer are requested
 // together, not one dependent round trip after the other.
-__device__ __forceinline__ void sparse_top(const float* __restrict__ lev, int H, int W, int y, int x, float thr, float (&t)[3],
-                                           bool* passer = nullptr) {
+// C channels; PAD: the colour values are multiplied by pad_inwards' mask first (select_peaks_tile).
+template <int C, bool PAD = false>
+__device__ __forceinline__ void sparse_top(const float* __restrict__ lev, int H, int W, int y, int x, float thr, float (&t)[C],
+                                           bool* passer = nullptr, int pad = 0) {
     const bool inside = y >= 0 && y < H && x >= 0 && x < W;
-    const float* __restrict__ px = lev + ((long long)min(max(y, 0), H - 1) * W + min(max(x, 0), W - 1)) * 3;
-    const float c0 = px[0], c1 = px[1], c2 = px[2];
-    const float v = __fmul_rn(__fadd_rn(__fadd_rn(c0, c1), c2), 1.0f / 3.0f);
+    const int yc = min(max(y, 0), H - 1), xc = min(max(x, 0), W - 1);
+    const float* __restrict__ px = lev + ((long long)yc * W + xc) * C;
+    float c[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) c[k] = px[k];
+    if constexpr (PAD) {
+        const float pm = (yc >= pad && yc < H - pad && xc >= pad && xc < W - pad) ? 1.0f : 0.0f;
+#pragma unroll
+        for (int k = 0; k < C; ++k) c[k] = __fmul_rn(pm, c[k]);
+    }
+    float v = c[0];
+#pragma unroll
+    for (int k = 1; k < C; ++k) v = __fadd_rn(v, c[k]);
+    v = __fmul_rn(v, 1.0f / (float)C);
     const float m = v >= thr ? 1.0f : 0.0f;
     if (passer) *passer = inside && v >= thr;
-    t[0] = inside ? __fmul_rn(c0, m) : kPoolLowest;
-    t[1] = inside ? __fmul_rn(c1, m) : kPoolLowest;
-    t[2] = inside ? __fmul_rn(c2, m) : kPoolLowest;
+#pragma unroll
+    for (int k = 0; k < C; ++k) t[k] = inside ? __fmul_rn(c[k], m) : kPoolLowest;
 }
 
 // grid: x = 256-entry chunks of one frame's summary, y = frame.  A lane looks at one entry; the entries that reach their level's
 // threshold are then handled one after the other by the WHOLE wave (lane i takes pixel i of the entry's 2 x kSumRows pixels),
 // so that a group costs two memory round trips instead of 32 dependent ones.
+template <int C, bool PAD = false>
 __global__ __launch_bounds__(256) void sparse_select_kernel(const float* __restrict__ color, const LevelTab tab, const SumTab st,
                                                             const float* __restrict__ sum, int n_frames, float one_minus_p,
                                                             float p_f, const unsigned* __restrict__ mm, const RegionTab rt,
                                                             unsigned* __restrict__ cells, Candidate* __restrict__ cand,
-                                                            int* __restrict__ cand_n) {
+                                                            int* __restrict__ cand_n, int pad = 0) {
     static_assert(2 * kSumRows <= 64, "one lane per pixel of a group");
     const int frame = blockIdx.y;
     const int e = (int)(blockIdx.x * 256 + threadIdx.x);   // (entries per frame < 2^31: host-checked)
@@ -792,25 +817,30 @@ __global__ __launch_bounds__(256) void sparse_select_kernel(const float* __restr
         const int ty = gy / st.gpt, k = gy - ty * st.gpt;
         const int r0 = ty * st.th + k * kSumRows;
         const int r1 = min(min(r0 + kSumRows, (ty + 1) * st.th), H);
-        const float* __restrict__ lev = color + ((long long)frame * tab.frame_px + tab.px_off[gl]) * 3;
+        const float* __restrict__ lev = color + ((long long)frame * tab.frame_px + tab.px_off[gl]) * C;
         const int y = r0 + (lane >> 1), x = 2 * xp + (lane & 1);
-        float tc_[3];
+        float tc_[C];
         bool passer = false;
-        sparse_top(lev, H, W, min(y, H - 1), x, gthr, tc_, &passer);
+        sparse_top<C, PAD>(lev, H, W, min(y, H - 1), x, gthr, tc_, &passer, pad);
         passer = passer && lane < 2 * kSumRows && y < r1;
         if (!passer) continue;   // (no wave-level operation below)
-        float mx[3] = {kPoolLowest, kPoolLowest, kPoolLowest};
-        float t[9][3];
+        float mx[C];
 #pragma unroll
-        for (int j = 0; j < 9; ++j) sparse_top(lev, H, W, y + j / 3 - 1, x + j % 3 - 1, gthr, t[j]);
+        for (int c = 0; c < C; ++c) mx[c] = kPoolLowest;
+        float t[9][C];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) sparse_top<C, PAD>(lev, H, W, y + j / 3 - 1, x + j % 3 - 1, gthr, t[j], nullptr, pad);
 #pragma unroll
         for (int j = 0; j < 9; ++j)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) mx[c] = pool_max(mx[c], t[j][c]);   // NaN taps are ignored like out-of-level ones
-        float o[3];
+            for (int c = 0; c < C; ++c) mx[c] = pool_max(mx[c], t[j][c]);   // NaN taps are ignored like out-of-level ones
+        float o[C];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) o[c] = __fmul_rn(tc_[c], tc_[c] == mx[c] ? tc_[c] : 0.0f);
-        const float pv = __fmul_rn(__fadd_rn(__fadd_rn(o[0], o[1]), o[2]), 1.0f / 3.0f);
+        for (int c = 0; c < C; ++c) o[c] = __fmul_rn(tc_[c], tc_[c] == mx[c] ? tc_[c] : 0.0f);
+        float pv = o[0];
+#pragma unroll
+        for (int c = 1; c < C; ++c) pv = __fadd_rn(pv, o[c]);
+        pv = __fmul_rn(pv, 1.0f / (float)C);
         const RegionLevel& rl = rt.lv[gl];
         int rs = 0, cs = 0;
         for (int s_ = 1; s_ < rl.nrs; ++s_) rs = y >= rl.rcut[s_] ? s_ : rs;

@@ -1,9 +1,15 @@
 // libsilent_hip.so -- pointwise ops, per-level thresholds, 3x3 NMS, keypoint indices, centroids, boosting state and the
-// display-graph glue (silent_peaks.h); silent_rgb_keypoints = the fused RGB chain (silent_rgb_api.hip) + the keypoint tail.
+// display-graph glue (silent_peaks.h); silent_rgb_keypoints = the fused RGB chain (silent_rgb_api.hip) + the keypoint tail,
+// silent_gray_keypoints = the gray pass with its keypoint epilogue (silent_gray_api.hip) + the same tail on K channels.
 #include "silent_internal.h"
 #include "silent_peaks.h"
+#include "silent_plan.h"
 
 using namespace silent;
+
+// channel counts the fused selection kernels are instantiated for (1, RGB's 3, the gray line-end banks' 4 and 8; a gray bank of
+// 3 shares RGB's instantiation)
+static bool select_channels_ok(int c) { return c == 1 || c == 3 || c == 4 || c == 8; }
 
 // ------------------------------------------------------------------------------------------ pointwise / nms
 
@@ -128,7 +134,7 @@ SILENT_EXPORT int silent_select_peaks_dev(silent_ctx* ctx, const float* color, c
     const char* who = "silent_select_peaks";
     if (!color) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (!top_out && !peaks_out && !peak_value_out) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": all outputs are NULL");
-    if (channels != 1 && channels != 3) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": channels must be 1 or 3");
+    if (!select_channels_ok(channels)) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": channels must be 1, 3, 4 or 8");
     LevelTab rtab, tab;
     long long rblocks, blocks;
     TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kRedChunk, 0, &rtab, &rblocks));
@@ -143,12 +149,14 @@ SILENT_EXPORT int silent_select_peaks_dev(silent_ctx* ctx, const float* color, c
     const float a = (float)(1.0 - top_percent), b = (float)top_percent;
     RegionTab no_regions;
     std::memset(&no_regions, 0, sizeof(no_regions));
-    if (channels == 3)
-        hipLaunchKernelGGL((select_peaks_kernel<3, false>), dim3((unsigned)blocks), dim3(256), 0, s, color, value, top_out,
-                           peaks_out, peak_value_out, tab, a, b, mm, no_regions, nullptr, nullptr, (unsigned)blocks);
-    else
-        hipLaunchKernelGGL((select_peaks_kernel<1, false>), dim3((unsigned)blocks), dim3(256), 0, s, color, value, top_out,
-                           peaks_out, peak_value_out, tab, a, b, mm, no_regions, nullptr, nullptr, (unsigned)blocks);
+#define SELECT_LAUNCH(C_)                                                                                                     \
+    hipLaunchKernelGGL((select_peaks_kernel<C_, false>), dim3((unsigned)blocks), dim3(256), 0, s, color, value, top_out, peaks_out, \
+                       peak_value_out, tab, a, b, mm, no_regions, nullptr, nullptr, (unsigned)blocks)
+    if (channels == 3) SELECT_LAUNCH(3);
+    else if (channels == 4) SELECT_LAUNCH(4);
+    else if (channels == 8) SELECT_LAUNCH(8);
+    else SELECT_LAUNCH(1);
+#undef SELECT_LAUNCH
     return check_launch(ctx, who);
 } catch (...) {
     return on_exception(ctx, "silent_select_peaks_dev");
@@ -316,6 +324,37 @@ static void keypoint_passes(const float* value, const LevelTab& tab, long long b
                        (long long)cap_per_frame, w.chunk_counts);
 }
 
+// a-11 in two halves: tables + workspace (after `reserve` bytes the caller keeps at the head of the workspace), then the passes --
+// so that silent_gray_keypoints can write the value map into the reserved bytes in between
+struct RegionPlan {
+    LevelTab tab, ctab;
+    long long blocks, cblocks;
+    RegionTab rt;
+    bool general;
+    KeypointWs w;
+};
+
+static int region_prepare(silent_ctx* ctx, const char* who, const silent_extent* levels, int n_levels, int n_frames,
+                          const silent_extent* regions, size_t reserve, hipStream_t s, RegionPlan* rp) {
+    TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kKpChunk, 0, &rp->tab, &rp->blocks));     // count / write chunks
+    TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kRedChunk, 0, &rp->ctab, &rp->cblocks));  // cell maxima
+    TRY(build_region_tab(ctx, who, levels, n_levels, regions, &rp->rt, &rp->general));
+    return keypoint_workspace(ctx, s, n_levels, n_frames, rp->blocks, reserve, rp->rt, rp->general, &rp->w);
+}
+
+static int region_run(silent_ctx* ctx, const char* who, const float* value, const silent_extent* levels, int n_levels, int n_frames,
+                      const RegionPlan& rp, int64_t* idx, size_t cap_per_frame, int64_t* counts, hipStream_t s) {
+    const KeypointWs& w = rp.w;
+    if (rp.general) {
+        TRY(region_window_maxima(ctx, who, value, levels, n_levels, n_frames, rp.rt, w, s));
+    } else {
+        hipLaunchKernelGGL(init_cells_kernel, dim3((unsigned)((w.n_cells + 255) / 256)), dim3(256), 0, s, w.cells, (long long)w.n_cells);
+        hipLaunchKernelGGL(region_cell_max_kernel, dim3((unsigned)rp.cblocks), dim3(256), 0, s, value, rp.ctab, rp.rt, w.cells);
+    }
+    keypoint_passes(value, rp.tab, rp.blocks, rp.rt, w, rp.general, n_frames, idx, cap_per_frame, counts, s);
+    return check_launch(ctx, who);
+}
+
 SILENT_EXPORT int silent_max_value_indices_region_dev(silent_ctx* ctx, const float* value, const silent_extent* levels,
                                                       int n_levels, int n_frames, const silent_extent* regions,
                                                       int64_t* idx, size_t cap_per_frame, int64_t* counts,
@@ -324,24 +363,9 @@ SILENT_EXPORT int silent_max_value_indices_region_dev(silent_ctx* ctx, const flo
     const char* who = "silent_max_value_indices_region";
     if (!value || !regions || !counts || (!idx && cap_per_frame))
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    LevelTab tab, ctab;
-    long long blocks, cblocks;
-    TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kKpChunk, 0, &tab, &blocks));   // count / write chunks
-    TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kRedChunk, 0, &ctab, &cblocks));  // cell maxima
-    RegionTab rt;
-    bool general;
-    TRY(build_region_tab(ctx, who, levels, n_levels, regions, &rt, &general));
-    KeypointWs w;
-    TRY(keypoint_workspace(ctx, (hipStream_t)stream, n_levels, n_frames, blocks, 0, rt, general, &w));
-    hipStream_t s = (hipStream_t)stream;
-    if (general) {
-        TRY(region_window_maxima(ctx, who, value, levels, n_levels, n_frames, rt, w, s));
-    } else {
-        hipLaunchKernelGGL(init_cells_kernel, dim3((unsigned)((w.n_cells + 255) / 256)), dim3(256), 0, s, w.cells, (long long)w.n_cells);
-        hipLaunchKernelGGL(region_cell_max_kernel, dim3((unsigned)cblocks), dim3(256), 0, s, value, ctab, rt, w.cells);
-    }
-    keypoint_passes(value, tab, blocks, rt, w, general, n_frames, idx, cap_per_frame, counts, s);
-    return check_launch(ctx, who);
+    RegionPlan rp;
+    TRY(region_prepare(ctx, who, levels, n_levels, n_frames, regions, 0, (hipStream_t)stream, &rp));
+    return region_run(ctx, who, value, levels, n_levels, n_frames, rp, idx, cap_per_frame, counts, (hipStream_t)stream);
 } catch (...) {
     return on_exception(ctx, "silent_max_value_indices_region_dev");
 }
@@ -400,12 +424,51 @@ static int select_prepare(silent_ctx* ctx, const char* who, const silent_extent*
     return SILENT_OK;
 }
 
+// The selection launches of select_run for C channels; PAD: `color` is unpadded, pad_inwards' mask is applied as it is read
+// (silent_gray_keypoints).  sparse_pass: sparse_select_kernel; otherwise the streaming selection pass.
+template <int C, bool PAD>
+static void select_launches(const SelectPlan& sp, bool sparse_pass, const float* color, const float* value, float* pv_map, float a,
+                            float b, const int* dense_flags, int n_frames, int pad, hipStream_t s) {
+    const RegionTab& rt = sp.rt;
+    const KeypointWs& w = sp.w;
+    if (sparse_pass) {
+        hipLaunchKernelGGL((sparse_select_kernel<C, PAD>), dim3((unsigned)((sp.st.frame_entries + 255) / 256), (unsigned)n_frames), dim3(256), 0, s,
+                           color, sp.tab, sp.st, w.sum, n_frames, a, b, sp.mm, rt, w.cells, w.cand, w.cand_n, pad);
+    } else if (sp.general) {
+        // many windows: the selection pass without the folded cell maxima (the separable window maxima follow)
+        hipLaunchKernelGGL((select_peaks_kernel<C, false, PAD>), dim3((unsigned)sp.sblocks), dim3(256), 0, s, color, value, nullptr, nullptr,
+                           pv_map, sp.stab, a, b, sp.mm, rt, nullptr, nullptr, (unsigned)sp.sblocks, pad);
+    } else {
+        // (sparse tail: a bounded grid -- usually no (frame, level) runs this pass)
+        hipLaunchKernelGGL((select_peaks_kernel<C, true, PAD>), dim3(dense_flags ? sparse_grid(sp.sblocks) : (unsigned)sp.sblocks), dim3(256), 0, s,
+                           color, value, nullptr, nullptr, pv_map, sp.stab, a, b, sp.mm, rt, w.cells, dense_flags, (unsigned)sp.sblocks, pad);
+    }
+}
+
+static void select_launches_for(int channels, int pad, const SelectPlan& sp, bool sparse_pass, const float* color, const float* value,
+                                float* pv_map, float a, float b, const int* dense_flags, int n_frames, hipStream_t s) {
+#define SEL(C_, P_) select_launches<C_, P_>(sp, sparse_pass, color, value, pv_map, a, b, dense_flags, n_frames, pad, s)
+    if (pad > 0) {
+        if (channels == 3) SEL(3, true);
+        else if (channels == 4) SEL(4, true);
+        else if (channels == 8) SEL(8, true);
+        else SEL(1, true);
+    } else {
+        if (channels == 3) SEL(3, false);
+        else if (channels == 4) SEL(4, false);
+        else if (channels == 8) SEL(8, false);
+        else SEL(1, false);
+    }
+#undef SEL
+}
+
 // have_mm: the extrema are already in sp.mm (no reduction pass).  sparse: the chain kernel left its value summary in sp.w.sum
-// (geometry sp.st) -- the sparse tail runs and the dense kernels only where it could not settle a (frame, level).
+// (geometry sp.st) -- the sparse tail runs and the dense kernels only where it could not settle a (frame, level).  pad > 0: `color`
+// is the unpadded map of silent_gray_keypoints (select_launches); the extrema must then be present (have_mm).
 static int select_run(silent_ctx* ctx, const char* who, const float* color, const float* value, const silent_extent* levels,
                       int n_levels, int n_frames, int channels, double top_percent, const SelectPlan& sp, bool have_mm,
                       float* peak_value_out, int64_t* idx, size_t cap_per_frame, int64_t* counts, hipStream_t s,
-                      bool sparse = false) {
+                      bool sparse = false, int pad = 0) {
     unsigned* mm = sp.mm;
     const RegionTab& rt = sp.rt;
     const KeypointWs& w = sp.w;
@@ -416,9 +479,8 @@ static int select_run(silent_ctx* ctx, const char* who, const float* color, cons
     const int* dense_flags = nullptr;
     float* const caller_map = peak_value_out;
     if (sparse) {
-        // (sparse implies: 3 channels, cell tables, extrema present, no caller-side peak-value map; select_prepare zeroed the counters)
-        hipLaunchKernelGGL(sparse_select_kernel, dim3((unsigned)((sp.st.frame_entries + 255) / 256), (unsigned)n_frames), dim3(256), 0, s, color, sp.tab, sp.st, w.sum,
-                           n_frames, a, b, mm, rt, w.cells, w.cand, w.cand_n);
+        // (sparse implies: cell tables, extrema present; select_prepare zeroed the counters)
+        select_launches_for(channels, pad, sp, true, color, value, nullptr, a, b, nullptr, n_frames, s);
         hipLaunchKernelGGL(sparse_modes_kernel, dim3((unsigned)n_frames), dim3(256), 0, s, sp.tab, rt, w.cells, w.cand_n, w.nan_flags,
                            w.dense_flags, peak_value_out ? 1 : 0);
         if (peak_value_out)   // the map the caller takes: zeros wherever the dense pass will not write
@@ -426,23 +488,8 @@ static int select_run(silent_ctx* ctx, const char* who, const float* color, cons
         dense_flags = w.dense_flags;
     }
     if (!peak_value_out) peak_value_out = w.pv;
-    if (sp.general) {
-        // many windows: the selection pass without the folded cell maxima, then the separable window maxima
-        if (channels == 3)
-            hipLaunchKernelGGL((select_peaks_kernel<3, false>), dim3((unsigned)sp.sblocks), dim3(256), 0, s, color, value, nullptr, nullptr,
-                               peak_value_out, sp.stab, a, b, mm, rt, nullptr, nullptr, (unsigned)sp.sblocks);
-        else
-            hipLaunchKernelGGL((select_peaks_kernel<1, false>), dim3((unsigned)sp.sblocks), dim3(256), 0, s, color, value, nullptr, nullptr,
-                               peak_value_out, sp.stab, a, b, mm, rt, nullptr, nullptr, (unsigned)sp.sblocks);
-        TRY(region_window_maxima(ctx, who, peak_value_out, levels, n_levels, n_frames, rt, w, s));
-    } else if (channels == 3) {
-        // (sparse tail: a bounded grid -- usually no (frame, level) runs this pass)
-        hipLaunchKernelGGL((select_peaks_kernel<3, true>), dim3(dense_flags ? sparse_grid(sp.sblocks) : (unsigned)sp.sblocks), dim3(256), 0, s, color, value, nullptr, nullptr,
-                           peak_value_out, sp.stab, a, b, mm, rt, w.cells, dense_flags, (unsigned)sp.sblocks);
-    } else {
-        hipLaunchKernelGGL((select_peaks_kernel<1, true>), dim3((unsigned)sp.sblocks), dim3(256), 0, s, color, value, nullptr, nullptr,
-                           peak_value_out, sp.stab, a, b, mm, rt, w.cells, dense_flags, (unsigned)sp.sblocks);
-    }
+    select_launches_for(channels, pad, sp, false, color, value, peak_value_out, a, b, dense_flags, n_frames, s);
+    if (sp.general) TRY(region_window_maxima(ctx, who, peak_value_out, levels, n_levels, n_frames, rt, w, s));
     keypoint_passes(peak_value_out, sp.tab, sp.blocks, rt, w, sp.general, n_frames, idx, cap_per_frame, counts, s, dense_flags,
                     dense_flags ? caller_map : nullptr);
     return check_launch(ctx, who);
@@ -456,7 +503,7 @@ SILENT_EXPORT int silent_select_keypoints_dev(silent_ctx* ctx, const float* colo
     const char* who = "silent_select_keypoints";
     if (!color || !regions || !counts || (!idx && cap_per_frame))
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    if (channels != 1 && channels != 3) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": channels must be 1 or 3");
+    if (!select_channels_ok(channels)) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": channels must be 1, 3, 4 or 8");
     SelectPlan sp;
     TRY(select_prepare(ctx, who, levels, n_levels, n_frames, regions, (hipStream_t)stream, &sp, 0, !peak_value_out));
     return select_run(ctx, who, color, value, levels, n_levels, n_frames, channels, top_percent, sp, false, peak_value_out, idx,
@@ -759,6 +806,84 @@ SILENT_EXPORT int silent_rgb_keypoints_dev(silent_ctx* ctx, const float* pyr, co
     return on_exception(ctx, "silent_rgb_keypoints_dev");
 }
 
+// ------------------------------------------------------------------------------------------ gray pass + keypoints
+
+// The gray pass (silent_gray_pass_dev, same maps bit for bit) with the keypoint epilogue in every kernel that writes `end`
+// (silent_gray.h, GrayKp): value = value_from_color(pad_inwards(end, pad)) is folded into the per-level extrema, the value summary
+// of the sparse tail and the NaN flags, or written as a map -- the end map is never read back for a reduction.  selection = 1:
+// a-10 -> a-9 -> a-8 -> a-11 on (pad_inwards(end), value) with K channels, sparse like silent_rgb_keypoints (SILENT_TUNE_GRAY bit 6:
+// the dense kernels for every level); selection = 0: a-11 on the value map (recognition_testing.py:90).
+static int gray_keypoints_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const float* frames, int n_frames,
+                                 const float* cs_kernel, const float* end_bank, int n_orient, float* pyr, float* end_out, int pad,
+                                 int selection, const silent_extent* regions, float* peak_value_out, int64_t* idx,
+                                 size_t cap_per_frame, int64_t* counts) {
+    if (!plan || !frames || !pyr || !cs_kernel || !end_bank || !end_out || !regions || !counts || (!idx && cap_per_frame))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
+    if (plan->tab.C != 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": the plan must be single-channel");
+    if (n_orient != 3 && n_orient != 4 && n_orient != 8)
+        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": n_orient must be 3, 4 or 8");
+    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
+    if (pad < 0) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": pad must be >= 0");
+    if (selection != 0 && selection != 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": selection must be 0 or 1");
+    if (!selection && peak_value_out)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": peak_value_out needs selection = 1 (there is no peak-value map without it)");
+    return SILENT_OK;
+}
+
+SILENT_EXPORT int silent_gray_keypoints_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
+                                            const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                            float* cs_out, float* end_out, int pad, int selection, double top_percent,
+                                            const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+                                            size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
+    NEED_CTX(ctx);
+    const char* who = "silent_gray_keypoints";
+    TRY(gray_keypoints_checks(ctx, who, plan, frames, n_frames, cs_kernel, end_bank, n_orient, pyr, end_out, pad, selection, regions,
+                              peak_value_out, idx, cap_per_frame, counts));
+    hipStream_t s = (hipStream_t)stream;
+    const silent_extent* levels = plan->extents.data();
+    const int n_levels = plan->tab.n_levels;
+    GrayKp kp;
+    std::memset(&kp, 0, sizeof(kp));
+    kp.n_levels = n_levels;
+    kp.pad = pad;
+    ctx->sparse_ran = false;
+    if (!selection) {
+        // a-11 straight on the value map: the epilogue writes it (into the head of the workspace unless the caller takes it)
+        const size_t map_bytes = value_out ? 0 : align_up((size_t)plan->tab.frame_px_out * n_frames * sizeof(float));
+        RegionPlan rp;
+        TRY(region_prepare(ctx, who, levels, n_levels, n_frames, regions, map_bytes, s, &rp));
+        kp.value_out = value_out ? value_out : (float*)ctx->ws.p;
+        TRY(gray_pass_kp(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s));
+        return region_run(ctx, who, kp.value_out, levels, n_levels, n_frames, rp, idx, cap_per_frame, counts, s);
+    }
+    // The summary groups are kSumRows rows of a tile row; one SumTab geometry serves all levels, so both filter kernels must tile
+    // with the same height (they do unless a build overrides SILENT_FUSED_TH; then the tail runs dense)
+    const bool want_sparse = kFusedTH == kGrayTH && !(ctx->tune[SILENT_TUNE_GRAY] & 64u);
+    SelectPlan sp;
+    TRY(select_prepare(ctx, who, levels, n_levels, n_frames, regions, s, &sp, want_sparse ? kGrayTH : 0, !peak_value_out));
+    const bool sparse = want_sparse && sp.st.frame_entries > 0;
+    kp.mm = sp.mm;
+    kp.nan_flags = sp.w.nan_flags;
+    kp.value_out = value_out;
+    if (sparse) {
+        kp.sum = sp.w.sum;
+        kp.sum_frame = sp.st.frame_entries;
+        kp.gpt = sp.st.gpt;
+        for (int l = 0; l < n_levels; ++l) kp.sum_off[l] = sp.st.off[l];
+    }
+    TRY(gray_pass_kp(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s));
+    ctx->sparse_ran = sparse;
+    ctx->sparse_stream = s;
+    ctx->sparse_flags_off = (size_t)((char*)sp.w.dense_flags - (char*)ctx->ws.p);
+    ctx->sparse_candn_off = (size_t)((char*)sp.w.cand_n - (char*)ctx->ws.p);
+    ctx->sparse_pairs = n_frames * n_levels;
+    ctx->sparse_frames = n_frames;
+    return select_run(ctx, who, end_out, nullptr, levels, n_levels, n_frames, n_orient, top_percent, sp, true, peak_value_out, idx,
+                      cap_per_frame, counts, s, sparse, pad);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_keypoints_dev");
+}
 
 SILENT_EXPORT int silent_sparse_tail_stats(silent_ctx* ctx, int64_t* stats) try {
     NEED_CTX(ctx);
@@ -919,6 +1044,37 @@ SILENT_EXPORT int silent_rgb_keypoints(silent_ctx* ctx, const float* pyr, const 
     return on_exception(ctx, "silent_rgb_keypoints");
 }
 
+SILENT_EXPORT int silent_gray_keypoints(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
+                                        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                        float* cs_out, float* end_out, int pad, int selection, double top_percent,
+                                        const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+                                        size_t cap_per_frame, int64_t* counts) try {
+    NEED_CTX(ctx);
+    const char* who = "silent_gray_keypoints";
+    // (the host form accepts NULL pyr / end_out: the *_dev form needs both maps, they then live in the staging arena)
+    if (!plan || !frames) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    TRY(gray_keypoints_checks(ctx, who, plan, frames, n_frames, cs_kernel, end_bank, n_orient, (float*)frames, (float*)frames, pad,
+                              selection, regions, peak_value_out, idx, cap_per_frame, counts));
+    HostStage hs(ctx);
+    const size_t b1 = (size_t)plan->tab.frame_px_out * n_frames * 4;
+    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * plan->tab.C * 4 * n_frames),
+              p = pyr ? hs.out(pyr, b1) : hs.scratch(b1), cs = hs.out(cs_out, b1),
+              end = end_out ? hs.out(end_out, b1 * n_orient) : hs.scratch(b1 * n_orient), v = hs.out(value_out, b1),
+              pv = hs.out(peak_value_out, b1), i = hs.out(idx, (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
+              n = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
+    TRY(hs.run([&] {
+        return silent_gray_keypoints_dev(ctx, plan, hs.dev<float>(x), n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
+                                         hs.dev<float>(cs), hs.dev<float>(end), pad, selection, top_percent, regions, hs.dev<float>(v),
+                                         hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame, hs.dev<int64_t>(n), nullptr);
+    }));
+    for (int f = 0; f < n_frames; ++f)
+        if (counts[f] > (int64_t)cap_per_frame)
+            return fail(ctx, SILENT_E_CAPACITY, std::string(who) + ": cap_per_frame too small; counts hold the need");
+    return SILENT_OK;
+} catch (...) {
+    return on_exception(ctx, "silent_gray_keypoints");
+}
+
 SILENT_EXPORT int silent_centroids(silent_ctx* ctx, const float* value, const silent_extent* levels, int n_levels,
                                    int n_frames, int region_h, int region_w, float* dist_out, float* total_out) try {
     NEED_CTX(ctx);
@@ -1016,7 +1172,7 @@ SILENT_EXPORT int silent_select_peaks(silent_ctx* ctx, const float* color, const
     NEED_CTX(ctx);
     if (!color) return fail(ctx, SILENT_E_INVALID, "silent_select_peaks: NULL pointer");
     if (!top_out && !peaks_out && !peak_value_out) return fail(ctx, SILENT_E_INVALID, "silent_select_peaks: all outputs are NULL");
-    if (channels != 1 && channels != 3) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_select_peaks: channels must be 1 or 3");
+    if (!select_channels_ok(channels)) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_select_peaks: channels must be 1, 3, 4 or 8");
     long long px;
     TRY(check_levels(ctx, "silent_select_peaks", levels, n_levels, n_frames, &px));
     HostStage hs(ctx);
@@ -1038,7 +1194,7 @@ SILENT_EXPORT int silent_select_keypoints(silent_ctx* ctx, const float* color, c
     NEED_CTX(ctx);
     if (!color || !regions || !counts || (!idx && cap_per_frame))
         return fail(ctx, SILENT_E_INVALID, "silent_select_keypoints: NULL pointer");
-    if (channels != 1 && channels != 3) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_select_keypoints: channels must be 1 or 3");
+    if (!select_channels_ok(channels)) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_select_keypoints: channels must be 1, 3, 4 or 8");
     long long px;
     TRY(check_levels(ctx, "silent_select_keypoints", levels, n_levels, n_frames, &px));
     HostStage hs(ctx);

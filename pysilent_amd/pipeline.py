@@ -129,8 +129,9 @@ class _RawBlock(object):
 class LineEndPipeline(object):
     def __init__(self, frame_hw, mode="gray", n_levels=5, scale=2.0, n_orient=4, batch=1, device=None,
                  constants=None, center_dimensions=None, clip_hi=255.0, flat_policy="ieee", pad=2,
-                 max_keypoints_per_frame=None, selection=False, top_percent=0.1, keep_selection_maps=False, value_map=True,
-                 peak_value_map=True, orient_map=True, overlap=False, overlap_priorities=True, placement="auto"):
+                 max_keypoints_per_frame=None, selection=False, top_percent=0.1, keep_selection_maps=False, value_map=None,
+                 peak_value_map=None, orient_map=True, overlap=False, overlap_priorities=True, placement="auto", keypoints=False,
+                 regions=None):
         import torch
         self.torch = torch
         self.mode = mode
@@ -176,18 +177,42 @@ class LineEndPipeline(object):
         self.overlap_tuning = None
         self._order_caller = True          # (A/B switch of scripts/ab_overlap.py: order the caller's stream behind the frame read)
         self._chain_stream = self._walk_stream = self._copy_stream = None
+        # keypoints (gray only; rgb always computes them): the gray pass with its keypoint epilogue and the selection tail in one
+        # C-ABI call (silent_gray_keypoints_dev).  value_map / peak_value_map: keep those maps (gray default: no, rgb default: yes)
+        self.keypoints = mode != "gray" or bool(keypoints)
         if mode == "gray":
             self.n_orient = int(self.consts["end"].shape[3])
+            if keypoints:
+                if overlap not in (False, None):
+                    raise ValueError("keypoints=True does not support overlap (the two-part gray step)")
+                if keep_selection_maps:
+                    raise ValueError("keep_selection_maps is for mode 'rgb'; gray keypoints keep value / peak_value maps only")
+                self.selection, self.top_percent = bool(selection), float(top_percent)
+                self.value = torch.empty(n, **f32) if value_map else None
+                self.peak_value = torch.empty(n, **f32) if (peak_value_map and self.selection) else None
+                if peak_value_map and not self.selection:
+                    raise ValueError("peak_value_map needs selection=True")
+            elif regions is not None:
+                raise ValueError("regions need keypoints=True in mode 'gray'")
         else:
+            value_map = True if value_map is None else value_map
+            peak_value_map = True if peak_value_map is None else peak_value_map
             # orient_map=False: SURVEY.md section 8d config 3 returns line_end + keypoints, the orientation map is optional
             self.orient_map = bool(orient_map)
             # value_map=False: the value map (a-8 of the line-end map) is not kept -- with selection the fused step needs it
             # nowhere (silent_rgb_keypoints), and BASELINE config 3 returns line_end + keypoints (+ orient) only
             self.value_map = bool(value_map) or not selection or bool(keep_selection_maps)
         self._adopt_maps(self._alloc_maps())
+        if self.keypoints:
+            if regions is None:
+                regions = [(max(eh // 2, 1), max(ew // 2, 1)) for eh, ew in self.extents]
+            if len(regions) != self.n_levels:
+                raise ValueError("need one (rH, rW) region per level (%d levels, %d regions)" % (self.n_levels, len(regions)))
+            self.regions = (_lib.Extent * self.n_levels)(*[_lib.Extent(int(rh), int(rw)) for rh, rw in regions])
+            self.kp_cap = int(max_keypoints_per_frame or self.frame_px)
+            self.kp_idx = torch.empty((self.batch, self.kp_cap, 4), dtype=torch.int64, device=self.tdev)
+            self.kp_counts = torch.zeros(self.batch, dtype=torch.int64, device=self.tdev)
         if mode != "gray":
-            self.regions = (_lib.Extent * self.n_levels)(*[_lib.Extent(max(eh // 2, 1), max(ew // 2, 1))
-                                                           for eh, ew in self.extents])
             # selection=True: SURVEY.md section 8d config 3 -- top-percent threshold (a-10, p = 0.1), 3x3 NMS (a-9),
             # then the per-region keypoint indices (a-11) of what survives; False: the reference graph
             # (recognition_testing.py:90), keypoints straight from the padded line-end map
@@ -201,9 +226,6 @@ class LineEndPipeline(object):
                 # then runs sparse (silent_rgb_keypoints with peak_value_out = NULL, csrc/silent_peaks.h)
                 self.peak_value_map = bool(peak_value_map) or self.keep_selection_maps
                 self.peak_value = torch.empty(n, **f32) if self.peak_value_map else None
-            self.kp_cap = int(max_keypoints_per_frame or self.frame_px)
-            self.kp_idx = torch.empty((self.batch, self.kp_cap, 4), dtype=torch.int64, device=self.tdev)
-            self.kp_counts = torch.zeros(self.batch, dtype=torch.int64, device=self.tdev)
             fp = C.POINTER(C.c_float)
             self._params = _lib.RgbChainParams(
                 *[self.consts[k].ctypes.data_as(fp) for k in ("rgc", "rgby", "stripe", "blur", "end")],
@@ -413,6 +435,8 @@ class LineEndPipeline(object):
         if that second measurement still wins by more than 2 %.  Otherwise the pipeline stays on one stream and the second
         pyramid buffer is released.  The decision is in ``overlap_tuning``.  Results never depend on the choice (bit-identical
         paths)."""
+        if self.mode == "gray" and self.keypoints:
+            raise ValueError("keypoints=True does not support overlap (the two-part gray step)")
         import time
         torch = self.torch
         pending = self._placement_pending
@@ -577,6 +601,17 @@ class LineEndPipeline(object):
         self.ctx.check(self._lib.silent_max_value_indices_region_dev(
             self.ctx.handle, p(value), *geom, self.regions, p(self.kp_idx), self.kp_cap, p(self.kp_counts), s))
 
+    def run_gray_keypoints(self, frames, stream=None):
+        """gray, keypoints=True: the whole pass + the keypoint tail in one C-ABI call (silent_gray_keypoints_dev): the kernels that
+        write the end map fold the padded value map into what the tail needs; pyramid / cs / end are those of run_gray_pass."""
+        self._check_frames(frames)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self.ctx.check(self._lib.silent_gray_keypoints_dev(
+            self.ctx.handle, self.plan.handle, p(frames), self.batch, C.c_void_p(self.consts["cs"].ctypes.data),
+            C.c_void_p(self.consts["end"].ctypes.data), self.n_orient, self.clip_hi, p(self.pyr), p(self.cs), p(self.end), self.pad,
+            int(self.selection), self.top_percent, self.regions, p(self.value), p(self.peak_value), p(self.kp_idx), self.kp_cap,
+            p(self.kp_counts), stream or self._stream()))
+
     def run_gray_pass(self, frames, stream=None, parts=3):
         """Whole grayscale hot path in one C-ABI call (silent_gray_pass_dev): region kernel for the non-unit
         levels, fused pyramid + CS + end kernel for the unit levels, filter kernel for the rest.  ``parts``: 1 = pyramid + unit
@@ -719,7 +754,10 @@ class LineEndPipeline(object):
             return self._step_overlapped(frames)
         s = self._stream()
         if self.mode == "gray":
-            self.run_gray_pass(frames, s)
+            if self.keypoints:
+                self.run_gray_keypoints(frames, s)
+            else:
+                self.run_gray_pass(frames, s)
             return
         self.run_pyramid(frames, s)
         if self.selection and not self.keep_selection_maps:
@@ -739,6 +777,11 @@ class LineEndPipeline(object):
         if self.mode == "gray":
             out["cs"] = P(self.cs, self.extents, 1, self.batch)
             out["end"] = P(self.end, self.extents, self.n_orient, self.batch)
+            if self.keypoints:
+                for name in ("value", "peak_value"):
+                    if getattr(self, name) is not None:
+                        out[name] = P(getattr(self, name), self.extents, 1, self.batch)
+                self._keypoint_outputs(out, allow_truncated)
         else:
             if self.orient is not None:
                 out["orient"] = P(self.orient, self.extents, 3, self.batch)
@@ -751,13 +794,18 @@ class LineEndPipeline(object):
                     out["peaks"] = P(self.peaks, self.extents, 3, self.batch)
                 if self.peak_value is not None:
                     out["peak_value"] = P(self.peak_value, self.extents, 1, self.batch)
-            counts = self.kp_counts.cpu().numpy()
-            if not allow_truncated and (counts > self.kp_cap).any():
-                # the asynchronous *_dev entry points cannot return SILENT_E_CAPACITY: counts[f] > cap IS the overflow flag
-                raise ValueError("keypoint capacity exceeded: frame %d produced %d rows, max_keypoints_per_frame is %d "
-                                 "(only the first %d were written; pass allow_truncated=True to take them)"
-                                 % (int(np.argmax(counts)), int(counts.max()), self.kp_cap, self.kp_cap))
-            # (only the rows each frame produced: the buffer holds kp_cap rows per frame -- every pyramid pixel by default)
-            out["keypoints"] = [self.kp_idx[f, :min(int(counts[f]), self.kp_cap)].cpu().numpy() for f in range(self.batch)]
-            out["keypoint_counts"] = counts
+            self._keypoint_outputs(out, allow_truncated)
+        return out
+
+    def _keypoint_outputs(self, out, allow_truncated):
+        """keypoints / keypoint_counts into ``out`` (host copies of the rows each frame produced)."""
+        counts = self.kp_counts.cpu().numpy()
+        if not allow_truncated and (counts > self.kp_cap).any():
+            # the asynchronous *_dev entry points cannot return SILENT_E_CAPACITY: counts[f] > cap IS the overflow flag
+            raise ValueError("keypoint capacity exceeded: frame %d produced %d rows, max_keypoints_per_frame is %d "
+                             "(only the first %d were written; pass allow_truncated=True to take them)"
+                             % (int(np.argmax(counts)), int(counts.max()), self.kp_cap, self.kp_cap))
+        # (only the rows each frame produced: the buffer holds kp_cap rows per frame -- every pyramid pixel by default)
+        out["keypoints"] = [self.kp_idx[f, :min(int(counts[f]), self.kp_cap)].cpu().numpy() for f in range(self.batch)]
+        out["keypoint_counts"] = counts
         return out
