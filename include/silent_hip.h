@@ -115,6 +115,19 @@ typedef struct silent_pyr_level {
 
 int silent_pyramid_plan_create(silent_ctx* ctx, int frame_h, int frame_w, int channels,
                                const silent_pyr_level* levels, int n_levels, silent_pyramid_plan** out);
+/* silent_pyramid_plan_create with flags (silent_pyramid_plan_create is this call with flags = 0).
+ * SILENT_PLAN_ACCUM_F64: float64 accumulation inside each op, like the CPU oracle.  Every map is still stored as float32; within
+ * one op the taps are summed in float64 and rounded to float32 once: the 6 x 6 spline taps of a pyramid output (float64 weights,
+ * vertical and horizontal sums, so a stored value may differ from the oracle's 2-D sum by 1 ulp where the double rounding lands
+ * near a midpoint), the 9 CS taps, the 9 * K end taps (in the oracle's order: the CS and end maps of a given pyramid are
+ * bit-identical to it).  Single-channel plans only (channels = 3: SILENT_E_UNSUPPORTED); unknown bits: SILENT_E_INVALID.
+ * Honoured by silent_pyramid[_dev], silent_gray_pass[_dev], silent_gray_pass_parts_dev and silent_gray_keypoints[_dev]; the
+ * per-op silent_gray_line_end[_dev] takes no plan and always accumulates in float32. */
+#define SILENT_PLAN_ACCUM_F64 1u
+int silent_pyramid_plan_create_ex(silent_ctx* ctx, int frame_h, int frame_w, int channels, const silent_pyr_level* levels,
+                                  int n_levels, unsigned flags, silent_pyramid_plan** out);
+/* The flags the plan was created with. */
+int silent_pyramid_plan_flags(const silent_pyramid_plan* plan, unsigned* flags);
 void silent_pyramid_plan_destroy(silent_pyramid_plan* plan);
 /* frames: n_frames x [H, W, C] float32 (values as the reference feeds them: uint8 range cast to f32,
  * recognition_testing.py:141).  pyr: packed pyramid batch with the plan's canvas extents. */
@@ -178,7 +191,8 @@ int silent_gray_pass_parts_dev(silent_ctx* ctx, const silent_pyramid_plan* plan,
 
 /* 1 when silent_gray_pass runs this plan through the single-read stream kernel (one unit-zoom level and every
  * other level resampling the same crop with a step > 1.25: classic whole-frame pyramids), 0 when it falls
- * back to region + unit-fused + filter kernels (e.g. the reference's centred-crop layout). */
+ * back to region + unit-fused + filter kernels (e.g. the reference's centred-crop layout).  The same for
+ * SILENT_PLAN_ACCUM_F64 plans (their own float64 instantiations of the same kernels). */
 int silent_pyramid_plan_is_streamable(const silent_pyramid_plan* plan);
 
 /* 3-channel plans: the number of WALK PLANS silent_pyramid runs this pyramid with in ONE launch of the strip-walk kernel (frame rows

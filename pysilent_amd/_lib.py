@@ -21,6 +21,7 @@ SILENT_E_NOMEM = -5
 
 RELU = 1
 CLIP = 2
+PLAN_ACCUM_F64 = 1   # silent_pyramid_plan_create_ex flag: float64 accumulation inside each op
 FLAT_IEEE = 0
 FLAT_ZERO = 1
 NMS_PRODUCT = 0
@@ -93,6 +94,8 @@ _SIGNATURES = {
     "silent_busy_wait_dev": [_vp, _u, _vp],
     "silent_trace_marker_dev": [_vp, _vp],
     "silent_pyramid_plan_create": [_vp, _i, _i, _i, C.POINTER(PyrLevel), _i, C.POINTER(_vp)],
+    "silent_pyramid_plan_create_ex": [_vp, _i, _i, _i, C.POINTER(PyrLevel), _i, _u, C.POINTER(_vp)],
+    "silent_pyramid_plan_flags": [_vp, C.POINTER(C.c_uint)],
     "silent_pyramid_plan_destroy": [_vp],
     "silent_pyramid": [_vp, _vp, _fp, _i, _fp],
     "silent_pyramid_dev": [_vp, _vp, _fp, _i, _fp, _vp],

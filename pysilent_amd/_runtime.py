@@ -712,20 +712,33 @@ class FrameDisplayer(object):
             pass
 
 
+ACCUMULATIONS = ("float32", "float64")
+
+
+def check_accumulation(accumulation):
+    """The accumulation argument of PyramidPlan / LineEndPipeline: "float32" (default) or "float64"."""
+    if accumulation not in ACCUMULATIONS:
+        raise ValueError("accumulation must be 'float32' or 'float64', got %r" % (accumulation,))
+    return accumulation
+
+
 class PyramidPlan(object):
     """Tap tables of one (frame size, level geometry) on the device.  ``levels`` is a list of dicts / tuples
-    (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w)."""
+    (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w).  accumulation="float64" (single-channel plans): every op of
+    run / gray_pass / gray_keypoints sums its taps in float64 and rounds once, like the CPU oracle (SILENT_PLAN_ACCUM_F64)."""
 
-    def __init__(self, frame_h, frame_w, channels, levels, device=None):
+    def __init__(self, frame_h, frame_w, channels, levels, device=None, accumulation="float32"):
+        self.accumulation = check_accumulation(accumulation)
         self.ctx = get_context(device)
         self.frame_shape = (int(frame_h), int(frame_w), int(channels))
         self.levels = [tuple(int(v) for v in l) for l in levels]
         self.extents = [(l[6], l[7]) for l in self.levels]
         arr = (_lib.PyrLevel * len(self.levels))(*[_lib.PyrLevel(*l) for l in self.levels])
         self.handle = C.c_void_p()
-        self.ctx.check(_lib.load().silent_pyramid_plan_create(self.ctx.handle, self.frame_shape[0], self.frame_shape[1],
-                                                              self.frame_shape[2], arr, len(self.levels),
-                                                              C.byref(self.handle)))
+        flags = _lib.PLAN_ACCUM_F64 if accumulation == "float64" else 0
+        self.ctx.check(_lib.load().silent_pyramid_plan_create_ex(self.ctx.handle, self.frame_shape[0], self.frame_shape[1],
+                                                                 self.frame_shape[2], arr, len(self.levels), flags,
+                                                                 C.byref(self.handle)))
         self.frame_px = sum(h * w for h, w in self.extents)
 
     def _frames(self, frames):
@@ -742,6 +755,13 @@ class PyramidPlan(object):
         out, optr = op.empty(op.n_frames * self.frame_px * c)
         op.call("pyramid", self.handle, op.ptr, op.n_frames, optr)
         return PackedPyramid(out, self.extents, c, op.n_frames)
+
+    @property
+    def flags(self):
+        """The plan's SILENT_PLAN_* flags as the library reports them."""
+        f = C.c_uint(0)
+        self.ctx.check(_lib.load().silent_pyramid_plan_flags(self.handle, C.byref(f)))
+        return int(f.value)
 
     @property
     def streamable(self):

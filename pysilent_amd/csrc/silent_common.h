@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/silent_hip.h"
 
 namespace silent {
@@ -67,6 +69,19 @@ __device__ __forceinline__ float from_lane_above(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, true));
 }
 
+// Float64 accumulation (plans created with SILENT_PLAN_ACCUM_F64; the F64 template flag of the gray and pyramid kernels).  Every
+// map is still stored as float32 between ops; inside one op the taps are summed in acc_t<true> = double and rounded to float32
+// once, like the oracle (oracle/silent_oracle.c).  The product of two float32 values is exact in float64, so a CS or end tap
+// chain in the oracle's order reproduces its value bit for bit.  The F64 = false instantiations keep the float32 code as it
+// was, statement for statement (their machine code is unchanged); the float64 arithmetic sits in `if constexpr (F64)` branches
+// and in the *_f64 helpers below.
+template <bool F64>
+using acc_t = typename std::conditional<F64, double, float>::type;
+// ds_bpermute of a float64 value: two permutes (its two halves)
+__device__ __forceinline__ double bpermute_f64(int addr, double v) {
+    return __hiloint2double(__builtin_amdgcn_ds_bpermute(addr, __double2hiint(v)), __builtin_amdgcn_ds_bpermute(addr, __double2loint(v)));
+}
+
 // scipy 'mirror' extension (d c b | a b c d | c b a) for an index within ONE reflection of [0, n): exact for
 // -(n-1) <= i <= 2(n-1); anything further out is clamped into range (such taps only feed outputs that are
 // never stored).  The streaming kernels reach at most 4 pixels outside, hence kMirrorNearMin.
@@ -100,6 +115,23 @@ __device__ __forceinline__ float unit_taps6(float c0, float edge, const float (&
     h = __builtin_fmaf(w[3], r1, h);
     h = __builtin_fmaf(w[4], r2, h);
     return __builtin_fmaf(w[5], r3, h);
+}
+// The same six taps summed in float64 with float64 weights (F64 kernels).
+template <bool EDGE = true>
+__device__ __forceinline__ double unit_taps6(float c0, float edge, const double (&w)[6]) {
+    const float l1 = from_lane_below(c0), l2 = from_lane_below(l1);
+    float r1;
+    if constexpr (EDGE)
+        r1 = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(c0), 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
+    else
+        r1 = from_lane_above(c0);
+    const float r2 = from_lane_above(r1), r3 = from_lane_above(r2);
+    double h = w[0] * (double)l2;
+    h = __builtin_fma(w[1], (double)l1, h);
+    h = __builtin_fma(w[2], (double)c0, h);
+    h = __builtin_fma(w[3], (double)r1, h);
+    h = __builtin_fma(w[4], (double)r2, h);
+    return __builtin_fma(w[5], (double)r3, h);
 }
 // Stream row i of the column `col` (level coordinates, mirrored inside the crop like every tap; px_stride floats per pixel) in lane i: ONE load per tile
 // for the sixth taps of a wave's last smoothing lane; row i is read back with unit_edge(xcol, i).

@@ -123,7 +123,42 @@ __device__ __forceinline__ void gray_kp_tile_end(const GrayKp& kp, const GrayKpA
 // (summary groups: kSumRows output rows; a tile's last group may be shorter)
 __host__ __device__ constexpr bool kp_group_ends(int k, int R) { return ((k + 1) % kSumRows) == 0 || k == R - 1; }
 
-template <int K, int R, bool KP = false>
+// ---- the F64 kernels' tap chains in the oracle's order (acc = 0, then dy and dx ascending, one fma per tap), summed in float64 and
+// rounded once (the float32 kernels keep their own chains).  gray_cs_f64: the CS sum before its relu; gray_end_f64: the K end values
+// after relu + clip.  w: the float32 weights (registers or kernel arguments), widened in registers -- exact.
+__device__ __forceinline__ float gray_cs_f64(const float (&iw)[3][3], const float* w) {
+    double acc = 0.0;
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) acc = __builtin_fma((double)iw[dy][dx], (double)w[dy * 3 + dx], acc);
+    return (float)acc;
+}
+template <int K>
+__device__ __forceinline__ void gray_end_f64(const float (&cw)[3][3], const float* w, float clip_hi, float (&out)[K]) {
+    double acc[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+            for (int k = 0; k < K; ++k) acc[k] = __builtin_fma((double)cw[dy][dx], (double)w[(dy * 3 + dx) * K + k], acc[k]);
+    // relu + clip in the reference's select forms only: a value rounded from a float64 sum can be -0 (a negative sum below half the
+    // smallest float32 denormal), which the oracle keeps and relu_clip_tf's v_med3 form need not
+#pragma unroll
+    for (int k = 0; k < K; ++k) out[k] = clip_hi_tf(relu_tf((float)acc[k]), clip_hi);
+}
+// vertical six taps of a unit level in float64, rounded once
+__device__ __forceinline__ float unit_vsum_f64(const double (&w)[6], const double (&h)[6]) {
+    double v = w[0] * h[0];
+#pragma unroll
+    for (int j = 1; j < 6; ++j) v = __builtin_fma(w[j], h[j], v);
+    return (float)v;
+}
+
+template <int K, int R, bool KP = false, bool F64 = false>
 __global__ __launch_bounds__(256) void gray_line_end_kernel(const float* __restrict__ pyr,
                                                             float* __restrict__ cs_out,
                                                             float* __restrict__ end_out, const LevelTab tab,
@@ -180,10 +215,14 @@ __global__ __launch_bounds__(256) void gray_line_end_kernel(const float* __restr
         if (i >= 2) {
             const int cy = y0 + i - 3;  // CS row produced by this step
             float acc = 0.0f;
+            if constexpr (F64) {
+                acc = gray_cs_f64(iw, wts.cs);
+            } else {
 #pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
+                for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                for (int dx = 0; dx < 3; ++dx) acc = __builtin_fmaf(iw[dy][dx], wts.cs[dy * 3 + dx], acc);
+                    for (int dx = 0; dx < 3; ++dx) acc = __builtin_fmaf(iw[dy][dx], wts.cs[dy * 3 + dx], acc);
+            }
             float cs = relu_tf(acc);
             cs = (cy >= 0 && cy < H && col_ok) ? cs : 0.0f;
 #pragma unroll
@@ -204,16 +243,20 @@ __global__ __launch_bounds__(256) void gray_line_end_kernel(const float* __restr
                 }
                 if (end_out) {
                     float acc[K];
+                    if constexpr (F64) {
+                        gray_end_f64<K>(cw, wts.end, clip_hi, acc);
+                    } else {
 #pragma unroll
-                    for (int k = 0; k < K; ++k) acc[k] = 0.0f;
+                        for (int k = 0; k < K; ++k) acc[k] = 0.0f;
 #pragma unroll
-                    for (int dy = 0; dy < 3; ++dy)
+                        for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                        for (int dx = 0; dx < 3; ++dx)
+                            for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-                            for (int k = 0; k < K; ++k)
-                                acc[k] = __builtin_fmaf(cw[dy][dx], wts.end[(dy * 3 + dx) * K + k], acc[k]);
-                    relu_clip_tf(acc, clip_hi);
+                                for (int k = 0; k < K; ++k)
+                                    acc[k] = __builtin_fmaf(cw[dy][dx], wts.end[(dy * 3 + dx) * K + k], acc[k]);
+                        relu_clip_tf(acc, clip_hi);
+                    }
                     if constexpr (KP) gray_kp_pixel<K>(kp, acc, y, x, H, W, out_lane, kp.value_out + px, ka);
                     if constexpr (K == 8) {
                         // lane 0's pixel is column xw0 - 2; valid pixels are lanes 2 .. 2 + ncols
@@ -287,11 +330,17 @@ struct FusedTab {
     float wx[6], wy[6];                // scipy's SIX taps of a zoom-1 level: [1, 26, 66, 26, 1] / 120 and 2^-53 (unit_taps6)
     FusedLevel lv[kMaxLevels];
 };
+// F64 kernels: the same taps in float64 (the same on both axes)
+struct FusedTab64 : FusedTab {
+    double w64[6];
+};
+template <bool F64>
+using FusedTabT = typename std::conditional<F64, FusedTab64, FusedTab>::type;
 
-template <int K, int R, bool KP = false>
+template <int K, int R, bool KP = false, bool F64 = false>
 __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const float* __restrict__ frames,
                                                               float* __restrict__ pyr, float* __restrict__ cs_out,
-                                                              float* __restrict__ end_out, const FusedTab tab,
+                                                              float* __restrict__ end_out, const FusedTabT<F64> tab,
                                                               const GrayW wts, float clip_hi, const GrayKp kp = GrayKp{}) {
     __shared__ __attribute__((aligned(16))) float s_slab[K == 8 ? kFusedWaves * 512 : 4];  // K = 8 store transpose, per wave
     const unsigned bid = blockIdx.x;
@@ -329,7 +378,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
     const bool col_in = ox >= 0 && ox < lv.out_w;                  // inside the level (SAME padding is 0 outside)
     const bool out_lane = lane >= 4 && lane < 4 + kFusedCols && ox < lv.out_w;
     GrayKpAcc ka;
-    float hw[6] = {0, 0, 0, 0, 0, 0};
+    acc_t<F64> hw[6] = {0, 0, 0, 0, 0, 0};
     float iw[3][3], cw[3][3];
 #pragma unroll
     for (int a = 0; a < 3; ++a)
@@ -340,7 +389,9 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
     for (int i = 0; i < R + 9; ++i) {
         // ---- horizontal taps of source row y0 - 4 + i
         {
-            const float h = unit_taps6(in[i], unit_edge(xcol, i), tab.wx);
+            acc_t<F64> h;
+            if constexpr (F64) h = unit_taps6(in[i], unit_edge(xcol, i), tab.w64);
+            else h = unit_taps6(in[i], unit_edge(xcol, i), tab.wx);
 #pragma unroll
             for (int j = 0; j < 5; ++j) hw[j] = hw[j + 1];
             hw[5] = h;
@@ -348,9 +399,14 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
         if (i >= 5) {
             // ---- pyramid row p = y0 + i - 7 (vertical taps p - 2 .. p + 3)
             const int p = y0 + i - 7;
-            float v = tab.wy[0] * hw[0];
+            float v;
+            if constexpr (F64) {
+                v = unit_vsum_f64(tab.w64, hw);
+            } else {
+                v = tab.wy[0] * hw[0];
 #pragma unroll
-            for (int j = 1; j < 6; ++j) v = __builtin_fmaf(tab.wy[j], hw[j], v);
+                for (int j = 1; j < 6; ++j) v = __builtin_fmaf(tab.wy[j], hw[j], v);
+            }
             v = (p < lv.zoom_h && ox < lv.zoom_w) ? v : 0.0f;                 // canvas beyond the zoomed crop
             if (p >= y0 && p < y0 + R && p < lv.out_h && out_lane) pyr[base_px + (long long)p * lv.out_w + ox] = v;
             v = (p >= 0 && p < lv.out_h && col_in) ? v : 0.0f;                // SAME zero padding of the first conv
@@ -367,10 +423,14 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
             // ---- CS row c = y0 + i - 8
             const int c = y0 + i - 8;
             float acc = 0.0f;
+            if constexpr (F64) {
+                acc = gray_cs_f64(iw, wts.cs);
+            } else {
 #pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
+                for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                for (int dx = 0; dx < 3; ++dx) acc = __builtin_fmaf(iw[dy][dx], wts.cs[dy * 3 + dx], acc);
+                    for (int dx = 0; dx < 3; ++dx) acc = __builtin_fmaf(iw[dy][dx], wts.cs[dy * 3 + dx], acc);
+            }
             float cs = relu_tf(acc);
             cs = (c >= 0 && c < lv.out_h && col_in) ? cs : 0.0f;
 #pragma unroll
@@ -390,16 +450,20 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
                 if (cs_out && out_lane) cs_out[px] = cw[1][1];  // (non-temporal here: 6 % SLOWER, unlike in gray_stream_kernel)
                 if (end_out) {
                     float acc[K];
+                    if constexpr (F64) {
+                        gray_end_f64<K>(cw, wts.end, clip_hi, acc);
+                    } else {
 #pragma unroll
-                    for (int k = 0; k < K; ++k) acc[k] = 0.0f;
+                        for (int k = 0; k < K; ++k) acc[k] = 0.0f;
 #pragma unroll
-                    for (int dy = 0; dy < 3; ++dy)
+                        for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                        for (int dx = 0; dx < 3; ++dx)
+                            for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-                            for (int k = 0; k < K; ++k)
-                                acc[k] = __builtin_fmaf(cw[dy][dx], wts.end[(dy * 3 + dx) * K + k], acc[k]);
-                    relu_clip_tf(acc, clip_hi);
+                                for (int k = 0; k < K; ++k)
+                                    acc[k] = __builtin_fmaf(cw[dy][dx], wts.end[(dy * 3 + dx) * K + k], acc[k]);
+                        relu_clip_tf(acc, clip_hi);
+                    }
                     if constexpr (KP) gray_kp_pixel<K>(kp, acc, y, ox, lv.out_h, lv.out_w, out_lane, kp.value_out + px, ka);
                     if constexpr (K == 8) {
                         const int ncols = min(kFusedCols, lv.out_w - xw0);
@@ -453,12 +517,17 @@ constexpr int kStreamRows = kFusedTH + 8;
 //   [meta(0) .. meta(Gp-1)] [weights of level 0 (4)] [level 1 (3)] [level 2 (2)] ... ; kStreamProgRow(layout, Gp) dwords.
 // It is wave-uniform data: the kernel reads it with scalar loads, one record ahead of the row it is working on.
 __host__ __device__ constexpr int stream_pad_levels(int g) { return g <= 4 ? 4 : 7; }
-__host__ __device__ constexpr int stream_w_off(int layout, int gp, int g) {
+// F64 plans: every weight is a float64 in two dwords (low, high): [meta] [level 0 (2 x 4)] [level 1 (2 x 3)] ...
+__host__ __device__ constexpr int stream_w_off(int layout, int gp, int g, bool f64 = false) {
     int o = gp;
-    for (int h = 0; h < g; ++h) o += stream_slots(layout, h);
+    for (int h = 0; h < g; ++h) o += stream_slots(layout, h) * (f64 ? 2 : 1);
     return o;
 }
-__host__ __device__ constexpr int kStreamProgRow(int layout, int gp) { return (stream_w_off(layout, gp, gp) + 3) / 4 * 4; }   // layout 0: 16 / 24
+__host__ __device__ constexpr int kStreamProgRow(int layout, int gp, bool f64 = false) {   // layout 0: 16 / 24 (F64: 28 / 36)
+    return (stream_w_off(layout, gp, gp, f64) + 3) / 4 * 4;
+}
+// dwords per column record: lane of tap 0, 6 float32 weights, pad; F64 plans: lane, pad, 6 float64 weights, 2 pad
+__host__ __device__ constexpr int stream_rec_ints(bool f64) { return f64 ? 16 : 8; }
 // meta: bits 0.. "slot restarts", 3 bits completing slot (7 = none), bit 7 "row feeds this level", then the output row
 __host__ __device__ constexpr int stream_done_shift(int layout) { return layout == 0 ? 4 : 8; }
 __host__ __device__ constexpr int stream_row_shift(int layout) { return layout == 0 ? 8 : 12; }
@@ -468,7 +537,7 @@ struct StreamTab {
     int tiles_y, waves_x;         // tile rows of the unit level, 56-column wave tiles per row
     const int* row_prog;          // [tiles_y][kStreamRows][kStreamProgRow(Gp)], Gp = stream_pad_levels(G)
     const int* col_hdr;           // [G][waves_x][2]: first output column, number of outputs
-    const int* col_rec;           // [G][waves_x][64][8]: lane of tap 0, 6 weight bits, pad
+    const int* col_rec;           // [G][waves_x][64][stream_rec_ints(F64)]: lane of tap 0 + the 6 horizontal weights
     long long px_off[8];          // pixel offset of level g inside one pyramid
     int out_w[8];
 };
@@ -496,6 +565,63 @@ __device__ __forceinline__ StreamCol stream_col(const StreamTab& st, int g, int 
     c.w[5] = __int_as_float(b.z);
     return c;
 }
+// the same from an F64 plan's records
+struct StreamCol64 {
+    int x0, n, lane4;
+    double w[6];
+};
+__device__ __forceinline__ StreamCol64 stream_col64(const StreamTab& st, int g, int wx_tile, int lane) {
+    const int gg = min(g, st.G - 1);
+    const int* __restrict__ h = st.col_hdr + ((long long)gg * st.waves_x + wx_tile) * 2;
+    const int4* __restrict__ rec = reinterpret_cast<const int4*>(st.col_rec + (((long long)gg * st.waves_x + wx_tile) * 64 + lane) * 16);
+    const int4 a = rec[0], b = rec[1], d = rec[2], e = rec[3];
+    StreamCol64 c;
+    c.x0 = h[0];
+    c.n = g < st.G ? h[1] : 0;
+    c.lane4 = a.x * 4;
+    c.w[0] = __hiloint2double(a.w, a.z);
+    c.w[1] = __hiloint2double(b.y, b.x);
+    c.w[2] = __hiloint2double(b.w, b.z);
+    c.w[3] = __hiloint2double(d.y, d.x);
+    c.w[4] = __hiloint2double(d.w, d.z);
+    c.w[5] = __hiloint2double(e.y, e.x);
+    return c;
+}
+template <bool F64>
+using StreamColT = typename std::conditional<F64, StreamCol64, StreamCol>::type;
+template <bool F64>
+__device__ __forceinline__ StreamColT<F64> stream_col_t(const StreamTab& st, int g, int wx_tile, int lane) {
+    if constexpr (F64) return stream_col64(st, g, wx_tile, lane);
+    else return stream_col(st, g, wx_tile, lane);
+}
+// Pass 2 of an F64 stream kernel for general level g on stream row value c0 (the float32 kernels spell it out inline): the vertical
+// taps of this row into the level's slots (float64 weights from the row program), and a completed row's horizontal taps -- the
+// float64 vertical sum gathered from the tap lanes with two permutes per tap -- rounded once and stored at px.
+template <int L, int G, int GR, int PR>
+__device__ __forceinline__ void stream_level_f64(int g, const int (&cur)[PR], float c0, double (&vacc)[kStreamSlots],
+                                                 const StreamCol64 (&col)[GR > 0 ? GR : 1], const StreamTab& st, int wx_tile, int lane,
+                                                 float* __restrict__ pyr, long long frame_px0, int C, int ch) {
+    const int meta = cur[g];
+#pragma unroll
+    for (int k = 0; k < stream_slots(L, g); ++k) {
+        const int e = stream_w_off(L, G, g, true) + 2 * k;
+        const double w = __hiloint2double(cur[e + 1], cur[e]);
+        const double prev = (meta >> k) & 1 ? 0.0 : vacc[k];
+        vacc[k] = __builtin_fma(w, (double)c0, prev);
+    }
+    const int done = (meta >> stream_done_shift(L)) & 7;
+    if (done != 7) {  // wave-uniform
+        const int oy = meta >> stream_row_shift(L);
+        double v = vacc[0];
+#pragma unroll
+        for (int k = 1; k < stream_slots(L, g); ++k) v = done == k ? vacc[k] : v;
+        const StreamCol64 cr = g < GR ? col[g < GR ? g : 0] : stream_col64(st, g, wx_tile, lane);
+        double acc = cr.w[0] * bpermute_f64(cr.lane4, v);
+#pragma unroll
+        for (int t = 1; t < 6; ++t) acc = __builtin_fma(cr.w[t], bpermute_f64(cr.lane4 + 4 * t, v), acc);
+        if (lane < cr.n) pyr[(frame_px0 + st.px_off[g] + (long long)oy * st.out_w[g] + cr.x0 + lane) * C + ch] = (float)acc;
+    }
+}
 // The first kStreamRegLevels general levels keep their column records in registers for the whole tile (a row of level 0 completes
 // every other stream row); the smaller levels -- one completed row per 2, 4, 8 tiles -- fetch theirs when a row completes.  With all
 // seven resident the <K, 7> instantiations sat at 125 VGPRs = 4 waves / SIMD (63 registers of records); now they run at the <K, 4>
@@ -505,10 +631,10 @@ __device__ __forceinline__ StreamCol stream_col(const StreamTab& st, int g, int 
 #endif
 constexpr int kStreamRegLevels = SILENT_STREAM_REG_LEVELS;
 
-template <int K, int G, int L = 0, bool KP = false>
+template <int K, int G, int L = 0, bool KP = false, bool F64 = false>
 __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const float* __restrict__ frames, float* __restrict__ pyr,
                                                           float* __restrict__ cs_out, float* __restrict__ end_out,
-                                                          const FusedTab tab, const StreamTab st, const GrayW wts,
+                                                          const FusedTabT<F64> tab, const StreamTab st, const GrayW wts,
                                                           float clip_hi, unsigned opts, const GrayKp kp = GrayKp{}) {
     constexpr int R = kFusedTH, NR = kStreamRows;
     __shared__ __attribute__((aligned(16))) float s_slab[K == 8 ? kFusedWaves * 512 : 4];
@@ -536,7 +662,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
     float in[R + 8];
     float in_last = 0.0f, xcol = 0.0f;   // pass 1's sixth taps: stream row R + 8 and the column right of the wave's 64 (unit_taps6)
     constexpr int GR = G < kStreamRegLevels ? G : kStreamRegLevels;
-    StreamCol col[GR > 0 ? GR : 1];
+    StreamColT<F64> col[GR > 0 ? GR : 1];
 #pragma unroll
     for (int i = 0; i < R + 8; ++i) in[i] = 0.0f;
 #pragma unroll
@@ -552,7 +678,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
         in_last = src[(long long)(mirror_near(y0 + R + 4, lv.src_h) + lv.src_y0) * W + sx];
         xcol = unit_edge_column(src, W, xw0 + 60, lv.src_w, lv.src_x0, y0 - 4, R + 9, lv.src_h, lv.src_y0, lane);
 #pragma unroll
-        for (int g = 0; g < GR; ++g) col[g] = stream_col(st, g, wx_tile, lane);
+        for (int g = 0; g < GR; ++g) col[g] = stream_col_t<F64>(st, g, wx_tile, lane);
     }
     if (!live) return;
 #pragma unroll
@@ -569,13 +695,13 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
 
     // ================= pass 2 (runs first: its registers die before pass 1): every other level of the pyramid,
     // rolled loop over the rows in LDS =================
-    float vacc[G][kStreamSlots];
+    acc_t<F64> vacc[G][kStreamSlots];
 #pragma unroll
     for (int g = 0; g < G; ++g)
 #pragma unroll
         for (int k = 0; k < kStreamSlots; ++k) vacc[g][k] = 0.0f;
     static_assert(G == stream_pad_levels(G), "row programs are padded to 4 or 7 levels");
-    constexpr int PR = kStreamProgRow(L, G);
+    constexpr int PR = kStreamProgRow(L, G, F64);
     // constant address space: with a wave-uniform address these are s_load_dwordx16 (no VGPR, no readfirstlane)
     typedef const __attribute__((address_space(4))) int* const_int_ptr;
     const_int_ptr prog = (const_int_ptr)(st.row_prog + (long long)ty * (NR * PR));
@@ -595,25 +721,29 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
         for (int g = 0; g < G; ++g) {
             const int meta = cur[g];
             if (!(meta & 128)) continue;  // wave-uniform: this stream row carries no tap of level g
+            if constexpr (F64) {
+                stream_level_f64<L, G, GR>(g, cur, c0, vacc[g], col, st, wx_tile, lane, pyr, frame_px0, 1, 0);
+            } else {
 #pragma unroll
-            for (int k = 0; k < stream_slots(L, g); ++k) {
-                const float w = __int_as_float(cur[stream_w_off(L, G, g) + k]);
-                const float prev = (meta >> k) & 1 ? 0.0f : vacc[g][k];
-                vacc[g][k] = __builtin_fmaf(w, c0, prev);
-            }
-            const int done = (meta >> stream_done_shift(L)) & 7;
-            if (done != 7) {  // wave-uniform: slot `done` holds a finished output row of level g
-                const int oy = meta >> stream_row_shift(L);
-                float v = vacc[g][0];
+                for (int k = 0; k < stream_slots(L, g); ++k) {
+                    const float w = __int_as_float(cur[stream_w_off(L, G, g) + k]);
+                    const float prev = (meta >> k) & 1 ? 0.0f : vacc[g][k];
+                    vacc[g][k] = __builtin_fmaf(w, c0, prev);
+                }
+                const int done = (meta >> stream_done_shift(L)) & 7;
+                if (done != 7) {  // wave-uniform: slot `done` holds a finished output row of level g
+                    const int oy = meta >> stream_row_shift(L);
+                    float v = vacc[g][0];
 #pragma unroll
-                for (int k = 1; k < stream_slots(L, g); ++k) v = done == k ? vacc[g][k] : v;
-                const int vbits = __float_as_int(v);
-                const StreamCol cr = g < GR ? col[g < GR ? g : 0] : stream_col(st, g, wx_tile, lane);   // (g is a constant here)
-                float acc = cr.w[0] * __int_as_float(__builtin_amdgcn_ds_bpermute(cr.lane4, vbits));
+                    for (int k = 1; k < stream_slots(L, g); ++k) v = done == k ? vacc[g][k] : v;
+                    const int vbits = __float_as_int(v);
+                    const StreamCol cr = g < GR ? col[g < GR ? g : 0] : stream_col(st, g, wx_tile, lane);   // (g is a constant here)
+                    float acc = cr.w[0] * __int_as_float(__builtin_amdgcn_ds_bpermute(cr.lane4, vbits));
 #pragma unroll
-                for (int t = 1; t < 6; ++t)
-                    acc = __builtin_fmaf(cr.w[t], __int_as_float(__builtin_amdgcn_ds_bpermute(cr.lane4 + 4 * t, vbits)), acc);
-                if (lane < cr.n) pyr[frame_px0 + st.px_off[g] + (long long)oy * st.out_w[g] + cr.x0 + lane] = acc;
+                    for (int t = 1; t < 6; ++t)
+                        acc = __builtin_fmaf(cr.w[t], __int_as_float(__builtin_amdgcn_ds_bpermute(cr.lane4 + 4 * t, vbits)), acc);
+                    if (lane < cr.n) pyr[frame_px0 + st.px_off[g] + (long long)oy * st.out_w[g] + cr.x0 + lane] = acc;
+                }
             }
         }
 #pragma unroll
@@ -627,10 +757,12 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
     // instruction, scripts/ubench/valu_rate.hip), and the ~50 SGPRs they would take no longer force reloads of
     // the weights from the kernarg segment in every row.
     constexpr bool VW = K <= 4;
-    float wv[6], csw[9], endw[VW ? 9 * K : 1];
+    acc_t<F64> wv[6];
+    float csw[9], endw[VW ? 9 * K : 1];
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
-        wv[j] = tab.wx[j];  // the unit level's taps are the same on both axes ([1,26,66,26,1]/120 and scipy's sixth, 2^-53)
+        if constexpr (F64) wv[j] = tab.w64[j];
+        else wv[j] = tab.wx[j];  // the unit level's taps are the same on both axes ([1,26,66,26,1]/120 and scipy's sixth, 2^-53)
         if constexpr (VW) asm volatile("" : "+v"(wv[j]));
     }
 #pragma unroll
@@ -666,7 +798,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
     // otherwise drift freely).  With the placement tuner choosing the fast relation it only costs: dropped (commit 02244a6 has it).)
     {
         GrayKpAcc ka;
-        float hw[6] = {0, 0, 0, 0, 0, 0};
+        acc_t<F64> hw[6] = {0, 0, 0, 0, 0, 0};
         float iw[3][3], cw[3][3];
 #pragma unroll
         for (int a = 0; a < 3; ++a)
@@ -676,16 +808,21 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
         for (int i = 0; i < R + 9; ++i) {
             {
                 const float c0 = i < R + 8 ? s_rows[wave][i < R + 8 ? i : 0][lane] : in_last;   // (the last row stayed in a register)
-                const float h = unit_taps6(c0, unit_edge(xcol, i), wv);
+                const acc_t<F64> h = unit_taps6(c0, unit_edge(xcol, i), wv);
 #pragma unroll
                 for (int j = 0; j < 5; ++j) hw[j] = hw[j + 1];
                 hw[5] = h;
             }
             if (i >= 5) {
                 const int p = y0 + i - 7;
-                float v = wv[0] * hw[0];
+                float v;
+                if constexpr (F64) {
+                    v = unit_vsum_f64(wv, hw);
+                } else {
+                    v = wv[0] * hw[0];
 #pragma unroll
-                for (int j = 1; j < 6; ++j) v = __builtin_fmaf(wv[j], hw[j], v);
+                    for (int j = 1; j < 6; ++j) v = __builtin_fmaf(wv[j], hw[j], v);
+                }
                 v = (p >= 0 && p < eff_h && col_eff) ? v : 0.0f;
                 if (p >= y0 && p < y0 + R && p < lv.out_h) {  // wave-uniform
                     float* __restrict__ prow = pyr + (wave_px + (long long)p * lv.out_w);
@@ -703,10 +840,14 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
             if (i >= 7) {
                 const int c = y0 + i - 8;
                 float acc = 0.0f;
+                if constexpr (F64) {
+                    acc = gray_cs_f64(iw, csw);
+                } else {
 #pragma unroll
-                for (int dy = 0; dy < 3; ++dy)
+                    for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) acc = __builtin_fmaf(iw[dy][dx], csw[dy * 3 + dx], acc);
+                        for (int dx = 0; dx < 3; ++dx) acc = __builtin_fmaf(iw[dy][dx], csw[dy * 3 + dx], acc);
+                }
                 // relu (a NaN stays a NaN) and the zero padding of the end convolution in one select
                 const float cs = (c >= 0 && c < lv.out_h && col_in && !(acc < 0.0f)) ? acc : 0.0f;
 #pragma unroll
@@ -728,19 +869,23 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
                     }
                     if (end_out) {
                         float acc[K];
+                        if constexpr (F64) {
+                            gray_end_f64<K>(cw, VW ? endw : wts.end, clip_hi, acc);
+                        } else {
 #pragma unroll
-                        for (int k = 0; k < K; ++k) acc[k] = 0.0f;
+                            for (int k = 0; k < K; ++k) acc[k] = 0.0f;
 #pragma unroll
-                        for (int dy = 0; dy < 3; ++dy)
+                            for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                            for (int dx = 0; dx < 3; ++dx)
+                                for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-                                for (int k = 0; k < K; ++k) {
-                                    const int wi = (dy * 3 + dx) * K + k;
-                                    if constexpr (VW) acc[k] = __builtin_fmaf(cw[dy][dx], endw[wi], acc[k]);
-                                    else acc[k] = __builtin_fmaf(cw[dy][dx], wts.end[wi], acc[k]);
-                                }
-                        relu_clip_tf(acc, clip_hi);
+                                    for (int k = 0; k < K; ++k) {
+                                        const int wi = (dy * 3 + dx) * K + k;
+                                        if constexpr (VW) acc[k] = __builtin_fmaf(cw[dy][dx], endw[wi], acc[k]);
+                                        else acc[k] = __builtin_fmaf(cw[dy][dx], wts.end[wi], acc[k]);
+                                    }
+                            relu_clip_tf(acc, clip_hi);
+                        }
                         if constexpr (KP) gray_kp_pixel<K>(kp, acc, y, ox, lv.out_h, lv.out_w, out_lane, kp.value_out + row_px + lane, ka);
                         if constexpr (K == 8) {
                             const int ncols = min(kFusedCols, lv.out_w - xw0);
@@ -776,9 +921,9 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
 // read and written at a stride of C floats.  Used for C = 1 only: two-step gray pyramids 0.58 -> 0.51 ms per 64 1080p
 // frames; with C = 3 the stride-3 loads and partial-line stores made it 1.5 ms against 1.0 ms for unit + region
 // kernels on 32 RGB frames (measured, bit-identical either way), so RGB plans are not marked streamable.
-template <int C, int G, int L = 0>
+template <int C, int G, int L = 0, bool F64 = false>
 __global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(const float* __restrict__ frames, float* __restrict__ pyr,
-                                                             const FusedTab tab, const StreamTab st) {
+                                                             const FusedTabT<F64> tab, const StreamTab st) {
     constexpr int R = kFusedTH, NR = kStreamRows;
     __shared__ float s_rows[kFusedWaves][NR][64];
     const unsigned bid = blockIdx.x;
@@ -800,14 +945,14 @@ __global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(const 
     const long long sx = (long long)(mirror_near(ox, lv.src_w) + lv.src_x0) * C;
 
     constexpr int GR = G < kStreamRegLevels ? G : kStreamRegLevels;
-    StreamCol col[GR > 0 ? GR : 1];
+    StreamColT<F64> col[GR > 0 ? GR : 1];
 #pragma unroll
-    for (int g = 0; g < GR; ++g) col[g] = stream_col(st, g, wx_tile, lane);
+    for (int g = 0; g < GR; ++g) col[g] = stream_col_t<F64>(st, g, wx_tile, lane);
     const int eff_h = min(lv.zoom_h, lv.out_h), eff_w = min(lv.zoom_w, lv.out_w);
     const bool col_eff = ox >= 0 && ox < eff_w;
     const bool out_lane = lane >= 4 && lane < 4 + kFusedCols && ox < lv.out_w;
     static_assert(G == stream_pad_levels(G), "row programs are padded to 4 or 7 levels");
-    constexpr int PR = kStreamProgRow(L, G);
+    constexpr int PR = kStreamProgRow(L, G, F64);
     typedef const __attribute__((address_space(4))) int* const_int_ptr;
     const_int_ptr prog = (const_int_ptr)(st.row_prog + (long long)ty * (NR * PR));
 
@@ -824,7 +969,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(const 
 
         // ---- pass 2: the other levels
         {
-            float vacc[G][kStreamSlots];
+            acc_t<F64> vacc[G][kStreamSlots];
 #pragma unroll
             for (int g = 0; g < G; ++g)
 #pragma unroll
@@ -843,26 +988,30 @@ __global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(const 
                 for (int g = 0; g < G; ++g) {
                     const int meta = cur[g];
                     if (!(meta & 128)) continue;
+                    if constexpr (F64) {
+                        stream_level_f64<L, G, GR>(g, cur, c0, vacc[g], col, st, wx_tile, lane, pyr, frame_px0, C, ch);
+                    } else {
 #pragma unroll
-                    for (int k = 0; k < stream_slots(L, g); ++k) {
-                        const float w = __int_as_float(cur[stream_w_off(L, G, g) + k]);
-                        const float prev = (meta >> k) & 1 ? 0.0f : vacc[g][k];
-                        vacc[g][k] = __builtin_fmaf(w, c0, prev);
-                    }
-                    const int done = (meta >> stream_done_shift(L)) & 7;
-                    if (done != 7) {
-                        const int oy = meta >> stream_row_shift(L);
-                        float v = vacc[g][0];
+                        for (int k = 0; k < stream_slots(L, g); ++k) {
+                            const float w = __int_as_float(cur[stream_w_off(L, G, g) + k]);
+                            const float prev = (meta >> k) & 1 ? 0.0f : vacc[g][k];
+                            vacc[g][k] = __builtin_fmaf(w, c0, prev);
+                        }
+                        const int done = (meta >> stream_done_shift(L)) & 7;
+                        if (done != 7) {
+                            const int oy = meta >> stream_row_shift(L);
+                            float v = vacc[g][0];
 #pragma unroll
-                        for (int k = 1; k < stream_slots(L, g); ++k) v = done == k ? vacc[g][k] : v;
-                        const int vbits = __float_as_int(v);
-                        const StreamCol cr = g < GR ? col[g < GR ? g : 0] : stream_col(st, g, wx_tile, lane);   // (g is a constant here)
-                        float acc = cr.w[0] * __int_as_float(__builtin_amdgcn_ds_bpermute(cr.lane4, vbits));
+                            for (int k = 1; k < stream_slots(L, g); ++k) v = done == k ? vacc[g][k] : v;
+                            const int vbits = __float_as_int(v);
+                            const StreamCol cr = g < GR ? col[g < GR ? g : 0] : stream_col(st, g, wx_tile, lane);   // (g is a constant here)
+                            float acc = cr.w[0] * __int_as_float(__builtin_amdgcn_ds_bpermute(cr.lane4, vbits));
 #pragma unroll
-                        for (int q = 1; q < 6; ++q)
-                            acc = __builtin_fmaf(cr.w[q], __int_as_float(__builtin_amdgcn_ds_bpermute(cr.lane4 + 4 * q, vbits)), acc);
-                        if (lane < cr.n)
-                            pyr[(frame_px0 + st.px_off[g] + (long long)oy * st.out_w[g] + cr.x0 + lane) * C + ch] = acc;
+                            for (int q = 1; q < 6; ++q)
+                                acc = __builtin_fmaf(cr.w[q], __int_as_float(__builtin_amdgcn_ds_bpermute(cr.lane4 + 4 * q, vbits)), acc);
+                            if (lane < cr.n)
+                                pyr[(frame_px0 + st.px_off[g] + (long long)oy * st.out_w[g] + cr.x0 + lane) * C + ch] = acc;
+                        }
                     }
                 }
 #pragma unroll
@@ -873,18 +1022,25 @@ __global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(const 
 
         // ---- pass 1: the unit level (same fma order as pyramid_unit_kernel).  The tile's 24 rows and the wave's 4 halo lanes per
         // side hold scipy's sixth taps (row p + 3, column x + 3) of every output without extra loads: no edge column here
-        float hw[6] = {0, 0, 0, 0, 0, 0};
+        acc_t<F64> hw[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int i = 0; i < R + 8; ++i) {
-            const float h = unit_taps6<false>(s_rows[wave][i][lane], 0.0f, tab.wx);
+            acc_t<F64> h;
+            if constexpr (F64) h = unit_taps6<false>(s_rows[wave][i][lane], 0.0f, tab.w64);
+            else h = unit_taps6<false>(s_rows[wave][i][lane], 0.0f, tab.wx);
 #pragma unroll
             for (int j = 0; j < 5; ++j) hw[j] = hw[j + 1];
             hw[5] = h;
             if (i >= 7 && i < R + 7) {
                 const int p = y0 + i - 7;
-                float v = tab.wy[0] * hw[0];
+                float v;
+                if constexpr (F64) {
+                    v = unit_vsum_f64(tab.w64, hw);
+                } else {
+                    v = tab.wy[0] * hw[0];
 #pragma unroll
-                for (int j = 1; j < 6; ++j) v = __builtin_fmaf(tab.wy[j], hw[j], v);
+                    for (int j = 1; j < 6; ++j) v = __builtin_fmaf(tab.wy[j], hw[j], v);
+                }
                 v = (p < eff_h && col_eff) ? v : 0.0f;
                 if (p < lv.out_h && out_lane) pyr[(base_px + (long long)p * lv.out_w + ox) * C + ch] = v;
             }

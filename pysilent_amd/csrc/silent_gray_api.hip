@@ -6,9 +6,21 @@ using namespace silent;
 
 // ------------------------------------------------------------------------------------------ fused gray pass
 
+// f64: the F64 kernel (float64 accumulation; F64 plans only, silent_gray_line_end always runs float32)
+template <int K, bool F64>
+static void launch_line_end(long long blocks, hipStream_t s, const float* pyr, float* cs_out, float* end_out, const LevelTab& tab,
+                            const GrayW& w, float clip_hi, unsigned opts, const GrayKp* kp) {
+    if (kp)
+        hipLaunchKernelGGL((gray_line_end_kernel<K, kGrayTH, true, F64>), dim3((unsigned)blocks), dim3(256), 0, s, pyr, cs_out, end_out,
+                           tab, w, clip_hi, opts, *kp);
+    else
+        hipLaunchKernelGGL((gray_line_end_kernel<K, kGrayTH, false, F64>), dim3((unsigned)blocks), dim3(256), 0, s, pyr, cs_out, end_out,
+                           tab, w, clip_hi, opts);
+}
+
 static int launch_gray(silent_ctx* ctx, const char* who, const float* pyr, const silent_extent* levels, int n_levels,
                        int n_frames, const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi,
-                       float* cs_out, float* end_out, hipStream_t s, const bool* skip, const GrayKp* kp = nullptr) {
+                       float* cs_out, float* end_out, hipStream_t s, const bool* skip, const GrayKp* kp = nullptr, bool f64 = false) {
     if (!pyr || !cs_kernel) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (!cs_out && !end_out) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": both outputs are NULL");
     if (end_out && !end_bank) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": end_bank is NULL");
@@ -27,15 +39,12 @@ static int launch_gray(silent_ctx* ctx, const char* who, const float* pyr, const
     std::memset(&w, 0, sizeof(w));
     std::memcpy(w.cs, cs_kernel, sizeof(float) * 9);
     if (end_bank) std::memcpy(w.end, end_bank, sizeof(float) * 9 * n_orient);
-#define GRAY_LAUNCH(K_, R_)                                                                                                          \
-    if (kp)                                                                                                                          \
-        hipLaunchKernelGGL((gray_line_end_kernel<K_, R_, true>), dim3((unsigned)blocks), dim3(256), 0, s, pyr, cs_out, end_out, tab, w, \
-                           clip_hi, opts, *kp);                                                                                      \
-    else                                                                                                                             \
-        hipLaunchKernelGGL((gray_line_end_kernel<K_, R_>), dim3((unsigned)blocks), dim3(256), 0, s, pyr, cs_out, end_out, tab, w, clip_hi, opts)
-    if (n_orient == 3) { GRAY_LAUNCH(3, kGrayTH); }
-    else if (n_orient == 4) { GRAY_LAUNCH(4, kGrayTH); }
-    else { GRAY_LAUNCH(8, kGrayTH); }
+#define GRAY_LAUNCH(K_)                                                                   \
+    if (f64) launch_line_end<K_, true>(blocks, s, pyr, cs_out, end_out, tab, w, clip_hi, opts, kp); \
+    else launch_line_end<K_, false>(blocks, s, pyr, cs_out, end_out, tab, w, clip_hi, opts, kp)
+    if (n_orient == 3) { GRAY_LAUNCH(3); }
+    else if (n_orient == 4) { GRAY_LAUNCH(4); }
+    else { GRAY_LAUNCH(8); }
 #undef GRAY_LAUNCH
     return check_launch(ctx, who);
 }
@@ -49,6 +58,30 @@ SILENT_EXPORT int silent_gray_line_end_dev(silent_ctx* ctx, const float* pyr, co
                        clip_hi, cs_out, end_out, (hipStream_t)stream, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_gray_line_end_dev");
+}
+
+template <int K, int G, int L, bool F64>
+static void launch_stream(long long blocks, hipStream_t s, const float* frames, float* pyr, float* cs_out, float* end_out,
+                          const FusedTab64& ft, const StreamTab& st, const GrayW& w, float clip_hi, unsigned opts, const GrayKp* kp) {
+    const FusedTabT<F64>& t = ft;
+    if (kp)
+        hipLaunchKernelGGL((gray_stream_kernel<K, G, L, true, F64>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr,
+                           cs_out, end_out, t, st, w, clip_hi, opts, *kp);
+    else
+        hipLaunchKernelGGL((gray_stream_kernel<K, G, L, false, F64>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr,
+                           cs_out, end_out, t, st, w, clip_hi, opts);
+}
+
+template <int K, bool F64>
+static void launch_fused(long long blocks, hipStream_t s, const float* frames, float* pyr, float* cs_out, float* end_out,
+                         const FusedTab64& ft, const GrayW& w, float clip_hi, const GrayKp* kp) {
+    const FusedTabT<F64>& t = ft;
+    if (kp)
+        hipLaunchKernelGGL((gray_unit_fused_kernel<K, kFusedTH, true, F64>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s,
+                           frames, pyr, cs_out, end_out, t, w, clip_hi, *kp);
+    else
+        hipLaunchKernelGGL((gray_unit_fused_kernel<K, kFusedTH, false, F64>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s,
+                           frames, pyr, cs_out, end_out, t, w, clip_hi);
 }
 
 // parts: bit 0 = the pyramid of every level + CS / end of the unit levels (steps 1 and 2), bit 1 = CS + end of the remaining levels
@@ -75,7 +108,7 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
     if (parts & 1u) TRY(launch_pyramid(ctx, who, plan, frames, n_frames, pyr, s, false, !stream_path));
     // 2. unit levels: pyramid + CS + end in one kernel
     const int fth = kFusedTH;
-    FusedTab ft;
+    FusedTab64 ft;   // (the float32 kernels take its FusedTab part)
     std::memset(&ft, 0, sizeof(ft));
     bool is_unit[kMaxLevels] = {false};
     long long tiles = 0, unit_px = 0;
@@ -90,6 +123,7 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
             for (int j = 0; j < 6; ++j) {  // every unit level has the same taps ([1,26,66,26,1]/120 and the sixth, 2^-53)
                 ft.wx[j] = plan->unit_w[j];
                 ft.wy[j] = plan->unit_w[j];
+                ft.w64[j] = plan->unit_w64[j];
             }
         FusedLevel& f = ft.lv[ft.n++];
         f.src_y0 = d.src_y0; f.src_x0 = d.src_x0; f.src_h = d.src_h; f.src_w = d.src_w;
@@ -114,14 +148,13 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
         ctx->prof_sample = ctx->profiling && (ctx->prof_calls++ % ctx->prof_period) == 0;
         const int prof_slot = ctx->prof_recorded % silent_ctx::kProfPairs;
         if (ctx->prof_sample) HIP_TRY(ctx, hipEventRecord(ctx->prof_ev[prof_slot][0], s));
+        const GrayKp* kpp = kp ? &kpu : nullptr;
         if (stream_path) {
             const StreamTab& st = plan->stream;
-#define STREAM_LAUNCH(K_, G_, L_)                                                                                                  \
-    if (kp)                                                                                                                        \
-        hipLaunchKernelGGL((gray_stream_kernel<K_, G_, L_, true>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, \
-                           cs_out, end_out, ft, st, w, clip_hi, (unsigned)((kopts >> 5) & 1), kpu);                                \
-    else                                                                                                                           \
-        hipLaunchKernelGGL((gray_stream_kernel<K_, G_, L_>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, (unsigned)((kopts >> 5) & 1))
+            const unsigned sopts = (unsigned)((kopts >> 5) & 1);
+#define STREAM_LAUNCH(K_, G_, L_)                                                                                  \
+    if (plan->f64) launch_stream<K_, G_, L_, true>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp); \
+    else launch_stream<K_, G_, L_, false>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp)
             if (plan->stream_layout == 1) {          // zoom ladders of ratio 1.4 .. e^.5: five rows of the first level in flight
                 if (n_orient == 3) { STREAM_LAUNCH(3, 7, 1); }
                 else if (n_orient == 4) { STREAM_LAUNCH(4, 7, 1); }
@@ -137,15 +170,12 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
             }
 #undef STREAM_LAUNCH
         } else {
-#define FUSED_LAUNCH(K_, R_)                                                                                                        \
-    if (kp)                                                                                                                         \
-        hipLaunchKernelGGL((gray_unit_fused_kernel<K_, R_, true>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, \
-                           cs_out, end_out, ft, w, clip_hi, kpu);                                                                   \
-    else                                                                                                                            \
-        hipLaunchKernelGGL((gray_unit_fused_kernel<K_, R_>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, cs_out, end_out, ft, w, clip_hi)
-            if (n_orient == 3) { FUSED_LAUNCH(3, kFusedTH); }
-            else if (n_orient == 4) { FUSED_LAUNCH(4, kFusedTH); }
-            else { FUSED_LAUNCH(8, kFusedTH); }
+#define FUSED_LAUNCH(K_)                                                                                   \
+    if (plan->f64) launch_fused<K_, true>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp); \
+    else launch_fused<K_, false>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp)
+            if (n_orient == 3) { FUSED_LAUNCH(3); }
+            else if (n_orient == 4) { FUSED_LAUNCH(4); }
+            else { FUSED_LAUNCH(8); }
 #undef FUSED_LAUNCH
         }
         if (ctx->prof_sample) {
@@ -158,7 +188,7 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
     // 3. CS + end on the remaining levels (they read the pyramid written in step 1)
     if (pt.n_general && (parts & 2u))
         TRY(launch_gray(ctx, who, pyr, plan->extents.data(), pt.n_levels, n_frames, cs_kernel, end_bank, n_orient,
-                        clip_hi, cs_out, end_out, s, is_unit, kp));
+                        clip_hi, cs_out, end_out, s, is_unit, kp, plan->f64));
     return SILENT_OK;
 }
 

@@ -13,6 +13,13 @@ struct silent_pyramid_plan {
     std::vector<silent_extent> extents;
     void* tables = nullptr;
     float unit_w[6] = {0, 0, 0, 0, 0, 0};  // scipy's six taps of a unit-zoom level ([1,26,66,26,1]/120 and 2^-53, as float32)
+    // SILENT_PLAN_ACCUM_F64 (silent_pyramid_plan_create_ex): the F64 kernels, float64 copies of every weight they read -- tab64's
+    // tap tables, unit_w64, and the stream path's row programs and column records are then built with float64 weights
+    unsigned flags = 0;
+    bool f64 = false;
+    void* tables64 = nullptr;
+    silent::PyrTab64 tab64{};            // tab + xw64 / yw64 (F64 plans)
+    double unit_w64[6] = {0, 0, 0, 0, 0, 0};
     // single-read "stream" path (gray_stream_kernel): row programs + column records, when the plan is eligible
     bool stream_ok = false;
     void* stream_tables = nullptr;

@@ -70,6 +70,13 @@ struct PyrTab {
     const int* xreg;   // per general level: first output column anchored at or right of region column rx
     const int* yreg;
 };
+// F64 kernels (single-channel plans created with SILENT_PLAN_ACCUM_F64): the same taps as float64 tables
+struct PyrTab64 : PyrTab {
+    const double* xw64;   // [cols][6]
+    const double* yw64;   // [rows][6]
+};
+template <bool F64>
+using PyrTabT = typename std::conditional<F64, PyrTab64, PyrTab>::type;
 
 __device__ __forceinline__ int mirror_index(int i, int n) {
     // scipy 'mirror' extension (d c b | a b c d | c b a)
@@ -85,9 +92,10 @@ __device__ __forceinline__ int mirror_index(int i, int n) {
 // A wave owns 64 source columns (60 outputs) and walks down kUnitTH rows: per row one coalesced load of
 // its own column (all rows requested up front), DPP shifts for the neighbours x - 2 .. x + 3, 6 horizontal
 // FMAs, a 6-row register window, 6 vertical FMAs, one store (scipy's six taps at zoom 1: unit_taps6, silent_gray.h).
-template <int C>
+// F64: the six taps of each axis summed in float64 with float64 weights (horizontal, then vertical), rounded once.
+template <int C, bool F64 = false>
 __global__ __launch_bounds__(256) void pyramid_unit_kernel(const float* __restrict__ frames,
-                                                           float* __restrict__ pyr, const PyrTab tab) {
+                                                           float* __restrict__ pyr, const PyrTabT<F64> tab) {
     constexpr int R = kUnitTH;
     const unsigned bid = blockIdx.x;
     const int frame = (int)(bid / (unsigned)tab.unit_tiles_per_frame);
@@ -111,11 +119,16 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(const float* __restri
     const float* __restrict__ src = frames + (long long)frame * tab.H * W * C;
     float* __restrict__ dst = pyr + ((long long)frame * tab.frame_px_out + tab.px_off[l]) * C;
 
-    float wx[6], wy[6];
+    acc_t<F64> wx[6], wy[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-        wx[i] = tab.xw[(long long)lv.xtab_off * 6 + i];
-        wy[i] = tab.yw[(long long)lv.ytab_off * 6 + i];
+        if constexpr (F64) {
+            wx[i] = tab.xw64[(long long)lv.xtab_off * 6 + i];
+            wy[i] = tab.yw64[(long long)lv.ytab_off * 6 + i];
+        } else {
+            wx[i] = tab.xw[(long long)lv.xtab_off * 6 + i];
+            wy[i] = tab.yw[(long long)lv.ytab_off * 6 + i];
+        }
     }
     const long long sx = (long long)(mirror_near(ox, lv.src_w) + lv.src_x0) * C;
     float in[R + 5][C];                                   // stream rows y0 - 2 .. y0 + R + 2
@@ -138,7 +151,7 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(const float* __restri
     for (int ch = 0; ch < C; ++ch) asm volatile("" : "+v"(xcol[ch]));
 
     const bool out_lane = lane >= 2 && lane < 2 + kUnitCols && ox < lv.out_w;
-    float hw[6][C];
+    acc_t<F64> hw[6][C];
 #pragma unroll
     for (int j = 0; j < 6; ++j)
 #pragma unroll
@@ -147,7 +160,7 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(const float* __restri
     for (int i = 0; i < R + 5; ++i) {
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) {
-            const float h = unit_taps6(in[i][ch], unit_edge(xcol[ch], i), wx);
+            const acc_t<F64> h = unit_taps6(in[i][ch], unit_edge(xcol[ch], i), wx);
 #pragma unroll
             for (int j = 0; j < 5; ++j) hw[j][ch] = hw[j + 1][ch];
             hw[5][ch] = h;
@@ -159,10 +172,17 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(const float* __restri
                 float* __restrict__ po = dst + ((long long)oy * lv.out_w + ox) * C;
 #pragma unroll
                 for (int ch = 0; ch < C; ++ch) {
-                    float v = wy[0] * hw[0][ch];
+                    if constexpr (F64) {
+                        double v = wy[0] * hw[0][ch];
 #pragma unroll
-                    for (int j = 1; j < 6; ++j) v = __builtin_fmaf(wy[j], hw[j][ch], v);
-                    po[ch] = live ? v : 0.0f;
+                        for (int j = 1; j < 6; ++j) v = __builtin_fma(wy[j], hw[j][ch], v);
+                        po[ch] = live ? (float)v : 0.0f;
+                    } else {
+                        float v = wy[0] * hw[0][ch];
+#pragma unroll
+                        for (int j = 1; j < 6; ++j) v = __builtin_fmaf(wy[j], hw[j][ch], v);
+                        po[ch] = live ? v : 0.0f;
+                    }
                 }
             }
         }
@@ -175,12 +195,13 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(const float* __restri
 // for every staged column, barrier, 6-tap horizontal pass, coalesced store.  The kernel is latency-bound
 // (staging loads, LDS round trips, barriers), so the LDS footprint is kept small: 25 KB (1 channel) / 22 KB
 // (3 channels) -> 6 / 7 blocks per CU that cover each other's waits.
-template <int C>
+// F64: vertical sums in float64 (kept in LDS as float64), horizontal taps in float64, one rounding per output.
+template <int C, bool F64 = false>
 __global__ __launch_bounds__(256) void pyramid_region_kernel(const float* __restrict__ frames,
-                                                             float* __restrict__ pyr, const PyrTab tab) {
+                                                             float* __restrict__ pyr, const PyrTabT<F64> tab) {
     constexpr int RW = region_w(C), SW = region_sw(C), SH = region_sh(C), ROWF = SW * C, VR = region_vr(C);
     __shared__ __attribute__((aligned(16))) float s_src[SH * ROWF];
-    __shared__ __attribute__((aligned(16))) float s_v[VR * ROWF];
+    __shared__ __attribute__((aligned(16))) acc_t<F64> s_v[VR * ROWF];
 
     const int per_frame = tab.regions_x * tab.regions_y;
     // XCD-contiguous order: regions that share halo rows / columns meet in one L2 (-1.5 % on RGB; the same
@@ -263,17 +284,19 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(const float* __rest
         // this lane's horizontal taps (first 64 output columns of the region) are requested before the vertical
         // pass, so their latency is covered by it; the vertical taps are wave-uniform -> scalar loads
         int co0[6];
-        float wx0[6];
+        acc_t<F64> wx0[6];
         {
             const long long xe6 = (long long)(lv.xtab_off + min(xs + lane, xe - 1)) * 6;
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
                 co0[i] = min(max(tab.xidx[xe6 + i] + xshift, 0), SW - 1) * C;
-                wx0[i] = tab.xw[xe6 + i];
+                if constexpr (F64) wx0[i] = tab.xw64[xe6 + i];
+                else wx0[i] = tab.xw[xe6 + i];
             }
         }
         typedef const __attribute__((address_space(4))) int* const_int_ptr;
         typedef const __attribute__((address_space(4))) float* const_float_ptr;
+        typedef const __attribute__((address_space(4))) double* const_double_ptr;
         for (int yc = ys; yc < ye; yc += VR) {
             const int nr = min(VR, ye - yc);
             // vertical 6 taps for every staged float of the rows this chunk needs (lanes = consecutive floats)
@@ -282,24 +305,32 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(const float* __rest
                 const_int_ptr yi = (const_int_ptr)(tab.yidx + ye6);
                 const_float_ptr yw = (const_float_ptr)(tab.yw + ye6);
                 int ro[6];
-                float wy[6];
+                acc_t<F64> wy[6];
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
                     ro[j] = min(max(yi[j] + yshift, 0), SH - 1) * ROWF;
-                    wy[j] = yw[j];
+                    if constexpr (F64) wy[j] = ((const_double_ptr)(tab.yw64 + ye6))[j];
+                    else wy[j] = yw[j];
                 }
                 for (int c = lane; c < ROWF; c += 64) {
-                    float acc = wy[0] * s_src[ro[0] + c];
+                    if constexpr (F64) {
+                        double acc = wy[0] * (double)s_src[ro[0] + c];
 #pragma unroll
-                    for (int j = 1; j < 6; ++j) acc = __builtin_fmaf(wy[j], s_src[ro[j] + c], acc);
-                    s_v[orow * ROWF + c] = acc;
+                        for (int j = 1; j < 6; ++j) acc = __builtin_fma(wy[j], (double)s_src[ro[j] + c], acc);
+                        s_v[orow * ROWF + c] = acc;
+                    } else {
+                        float acc = wy[0] * s_src[ro[0] + c];
+#pragma unroll
+                        for (int j = 1; j < 6; ++j) acc = __builtin_fmaf(wy[j], s_src[ro[j] + c], acc);
+                        s_v[orow * ROWF + c] = acc;
+                    }
                 }
             }
             __syncthreads();
             // horizontal 6 taps and store (lanes = consecutive output columns)
             for (int oc = xs + lane; oc < xe; oc += 64) {
                 int co[6];
-                float wx[6];
+                acc_t<F64> wx[6];
                 if (oc < xs + 64) {  // wave-uniform
 #pragma unroll
                     for (int i = 0; i < 6; ++i) co[i] = co0[i], wx[i] = wx0[i];
@@ -308,17 +339,25 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(const float* __rest
 #pragma unroll
                     for (int i = 0; i < 6; ++i) {
                         co[i] = min(max(tab.xidx[xe6 + i] + xshift, 0), SW - 1) * C;
-                        wx[i] = tab.xw[xe6 + i];
+                        if constexpr (F64) wx[i] = tab.xw64[xe6 + i];
+                        else wx[i] = tab.xw[xe6 + i];
                     }
                 }
                 for (int orow = wave; orow < nr; orow += 4) {
                     float* __restrict__ po = dst + ((long long)(yc + orow) * lv.out_w + oc) * C;
 #pragma unroll
                     for (int ch = 0; ch < C; ++ch) {
-                        float acc = wx[0] * s_v[orow * ROWF + co[0] + ch];
+                        if constexpr (F64) {
+                            double acc = wx[0] * s_v[orow * ROWF + co[0] + ch];
 #pragma unroll
-                        for (int i = 1; i < 6; ++i) acc = __builtin_fmaf(wx[i], s_v[orow * ROWF + co[i] + ch], acc);
-                        po[ch] = acc;
+                            for (int i = 1; i < 6; ++i) acc = __builtin_fma(wx[i], s_v[orow * ROWF + co[i] + ch], acc);
+                            po[ch] = (float)acc;
+                        } else {
+                            float acc = wx[0] * s_v[orow * ROWF + co[0] + ch];
+#pragma unroll
+                            for (int i = 1; i < 6; ++i) acc = __builtin_fmaf(wx[i], s_v[orow * ROWF + co[i] + ch], acc);
+                            po[ch] = acc;
+                        }
                     }
                 }
             }

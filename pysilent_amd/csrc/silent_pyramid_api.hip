@@ -34,7 +34,8 @@ static int host_mirror(long i, int n) {
 
 // scipy.ndimage.zoom, grid_mode=False: output o samples o * (n_in-1)/(n_out-1); mode 'constant'
 // declares a coordinate outside [0, n_in-1] out of bounds (-> cval 0 for the whole row/column).
-static void axis_table(int n_in, int n_out, int* base, int* idx, float* wts) {
+// wts64 (may be NULL): the same weights as scipy's float64 values (F64 plans)
+static void axis_table(int n_in, int n_out, int* base, int* idx, float* wts, double* wts64) {
     const double step = n_out > 1 ? (double)(n_in - 1) / (double)(n_out - 1) : 1.0;
     for (int o = 0; o < n_out; ++o) {
         const double c = (double)o * step;
@@ -49,27 +50,34 @@ static void axis_table(int n_in, int n_out, int* base, int* idx, float* wts) {
             float f = (float)w[j];
             if (w[j] != 0.0 && f == 0.0f) f = std::copysign(std::numeric_limits<float>::denorm_min(), (float)(w[j] < 0.0 ? -1.0 : 1.0));
             wts[6 * o + j] = f;
+            if (wts64) wts64[6 * o + j] = w[j];
             idx[6 * o + j] = host_mirror(b - 2 + j, n_in);
         }
     }
 }
 
-SILENT_EXPORT int silent_pyramid_plan_create(silent_ctx* ctx, int frame_h, int frame_w, int channels,
-                                             const silent_pyr_level* levels, int n_levels,
-                                             silent_pyramid_plan** out) try {
+SILENT_EXPORT int silent_pyramid_plan_create_ex(silent_ctx* ctx, int frame_h, int frame_w, int channels,
+                                                const silent_pyr_level* levels, int n_levels, unsigned flags,
+                                                silent_pyramid_plan** out) try {
     NEED_CTX(ctx);
     const char* who = "silent_pyramid_plan_create";
     if (!out || !levels) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     *out = nullptr;
+    if (flags & ~SILENT_PLAN_ACCUM_F64) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": unknown flag bits");
     if (frame_h < 1 || frame_w < 1 || (long long)frame_h * frame_w > (1ll << 30))
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": bad frame extent");
     if (channels != 1 && channels != 3)
         return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": channels must be 1 or 3");
+    const bool f64 = (flags & SILENT_PLAN_ACCUM_F64) != 0;
+    if (f64 && channels != 1)
+        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": float64 accumulation needs a single-channel plan");
     if (n_levels < 1 || n_levels > kMaxLevels)
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_levels must be in [1, " + std::to_string(kMaxLevels) + "]");
     silent_pyramid_plan* plan = new (std::nothrow) silent_pyramid_plan();
     if (!plan) return fail(ctx, SILENT_E_NOMEM, std::string(who) + ": out of host memory");
     plan->ctx = ctx;
+    plan->flags = flags;
+    plan->f64 = f64;
     PyrTab& tab = plan->tab;
     tab.n_levels = n_levels;
     tab.H = frame_h;
@@ -104,6 +112,7 @@ SILENT_EXPORT int silent_pyramid_plan_create(silent_ctx* ctx, int frame_h, int f
     tab.frame_px_out = px;
     std::vector<int> xbase(cols), xidx(cols * 6), ybase(rows), yidx(rows * 6), xreg, yreg;
     std::vector<float> xw(cols * 6), yw(rows * 6);
+    std::vector<double> xw64(f64 ? cols * 6 : 0), yw64(f64 ? rows * 6 : 0);
     long long unit_tiles = 0, zero_chunks = 0;
     tab.n_general = 0;
     bool tap_range_ok = true;
@@ -113,8 +122,8 @@ SILENT_EXPORT int silent_pyramid_plan_create(silent_ctx* ctx, int frame_h, int f
         int* yb = ybase.data() + d.ytab_off;
         float* xwl = xw.data() + (size_t)d.xtab_off * 6;
         float* ywl = yw.data() + (size_t)d.ytab_off * 6;
-        axis_table(d.src_w, d.zoom_w, xb, xidx.data() + (size_t)d.xtab_off * 6, xwl);
-        axis_table(d.src_h, d.zoom_h, yb, yidx.data() + (size_t)d.ytab_off * 6, ywl);
+        axis_table(d.src_w, d.zoom_w, xb, xidx.data() + (size_t)d.xtab_off * 6, xwl, f64 ? xw64.data() + (size_t)d.xtab_off * 6 : nullptr);
+        axis_table(d.src_h, d.zoom_h, yb, yidx.data() + (size_t)d.ytab_off * 6, ywl, f64 ? yw64.data() + (size_t)d.ytab_off * 6 : nullptr);
         // zoom factor exactly 1 <=> every output samples an integer coordinate: weights [1,26,66,26,1,~0]/120
         // (the streaming unit kernels mirror with one reflection: needs at least kMirrorNearMin source pixels per axis)
         const bool unit = d.zoom_h == d.src_h && d.zoom_w == d.src_w && std::fabs(xwl[5]) < 1e-12f &&
@@ -128,6 +137,8 @@ SILENT_EXPORT int silent_pyramid_plan_create(silent_ctx* ctx, int frame_h, int f
         if (unit) {
             unit_tiles += (long long)tab.unit_tiles_x[l] * ((d.out_h + kUnitTH - 1) / kUnitTH);
             for (int j = 0; j < 6; ++j) plan->unit_w[j] = xwl[j];
+            if (f64)
+                for (int j = 0; j < 6; ++j) plan->unit_w64[j] = xw64[(size_t)d.xtab_off * 6 + j];
             continue;
         }
         ++tab.n_general;
@@ -209,6 +220,22 @@ SILENT_EXPORT int silent_pyramid_plan_create(silent_ctx* ctx, int frame_h, int f
     tab.yw = (const float*)dptr[3];
     tab.xreg = (const int*)dptr[4];
     tab.yreg = (const int*)dptr[5];
+    if (f64) {
+        const size_t bx = align_up(xw64.size() * 8);
+        e = hipMalloc(&plan->tables64, bx + align_up(yw64.size() * 8));
+        if (e == hipSuccess) e = hipMemcpy(plan->tables64, xw64.data(), xw64.size() * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy((char*)plan->tables64 + bx, yw64.data(), yw64.size() * 8, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (plan->tables64) (void)hipFree(plan->tables64);
+            (void)hipFree(plan->tables);
+            delete plan;
+            return fail(ctx, SILENT_E_NOMEM, std::string(who) + ": float64 tap tables: " + hipGetErrorString(e));
+        }
+        static_cast<PyrTab&>(plan->tab64) = tab;
+        plan->tab64.xw64 = (const double*)plan->tables64;
+        plan->tab64.yw64 = (const double*)((char*)plan->tables64 + bx);
+    }
     // ---- single-read stream path (see gray_stream_kernel): eligible when there is exactly one unit level and
     // every other level resamples the same crop with a step large enough for 4 vertical slots
     {
@@ -228,14 +255,14 @@ SILENT_EXPORT int silent_pyramid_plan_create(silent_ctx* ctx, int frame_h, int f
         const bool eligible = ok;
         // slot layouts (silent_gray.h, stream_slots): 0 for ladders of ratio >= e^.5, 1 ("dense", kernels for 7 levels only) down to 1.4
         for (int layout = 0; layout < 2 && eligible && !plan->stream_ok; ++layout) {
-            ok = true;
+            ok = true;   // (F64 plans: every layout; the F64 stream kernels spill nothing to scratch)
             const PyrLevelDev& u = tab.lv[unit];
             const int G = tab.n_general;
             const int tiles_y = (u.out_h + kFusedTH - 1) / kFusedTH;
             const int waves_x = ((u.out_w + kFusedTW - 1) / kFusedTW) * kFusedWaves;
-            const int Gp = layout ? 7 : stream_pad_levels(G), PR = kStreamProgRow(layout, Gp);
+            const int Gp = layout ? 7 : stream_pad_levels(G), PR = kStreamProgRow(layout, Gp, f64), RI = stream_rec_ints(f64);
             const size_t n_rec = (size_t)tiles_y * kStreamRows;
-            std::vector<int> prog(n_rec * PR, 0), hdr((size_t)G * waves_x * 2, 0), rec((size_t)G * waves_x * 64 * 8, 0);
+            std::vector<int> prog(n_rec * PR, 0), hdr((size_t)G * waves_x * 2, 0), rec((size_t)G * waves_x * 64 * RI, 0);
             for (size_t r = 0; r < n_rec; ++r)
                 for (int gg = 0; gg < Gp; ++gg) prog[r * PR + gg] = 7 << stream_done_shift(layout);  // inert: feeds nothing, no slot completes
             std::vector<char> used(n_rec * G * kStreamSlots, 0);
@@ -259,7 +286,8 @@ SILENT_EXPORT int silent_pyramid_plan_create(silent_ctx* ctx, int frame_h, int f
                         used[e * kStreamSlots + slot] = 1;
                         int* pr = prog.data() + r * PR;
                         int& meta = pr[g];
-                        std::memcpy(pr + stream_w_off(layout, Gp, g) + slot, &yw[(size_t)(d.ytab_off + oy) * 6 + j], 4);
+                        if (f64) std::memcpy(pr + stream_w_off(layout, Gp, g, true) + 2 * slot, &yw64[(size_t)(d.ytab_off + oy) * 6 + j], 8);
+                        else std::memcpy(pr + stream_w_off(layout, Gp, g) + slot, &yw[(size_t)(d.ytab_off + oy) * 6 + j], 4);
                         meta |= 128;  // this stream row feeds level g
                         if (j == 0) meta |= 1 << slot;
                         if (j == 5) {
@@ -279,10 +307,11 @@ SILENT_EXPORT int silent_pyramid_plan_create(silent_ctx* ctx, int frame_h, int f
                     hdr[((size_t)g * waves_x + wx) * 2] = ox;
                     hdr[((size_t)g * waves_x + wx) * 2 + 1] = n;
                     for (int j = 0; j < n; ++j) {
-                        int* r = rec.data() + (((size_t)g * waves_x + wx) * 64 + j) * 8;
+                        int* r = rec.data() + (((size_t)g * waves_x + wx) * 64 + j) * RI;
                         r[0] = xb[ox + j] - xw0 + 2;  // lane holding tap 0 (lane 0 <-> column xw0 - 4)
                         if (r[0] < 0 || r[0] + 5 > 63) { ok = false; break; }
-                        std::memcpy(r + 1, &xw[(size_t)(d.xtab_off + ox + j) * 6], 24);
+                        if (f64) std::memcpy(r + 2, &xw64[(size_t)(d.xtab_off + ox + j) * 6], 48);
+                        else std::memcpy(r + 1, &xw[(size_t)(d.xtab_off + ox + j) * 6], 24);
                     }
                     ox += n;
                 }
@@ -540,10 +569,25 @@ SILENT_EXPORT int silent_pyramid_plan_create(silent_ctx* ctx, int frame_h, int f
     return on_exception(ctx, "silent_pyramid_plan_create");
 }
 
+SILENT_EXPORT int silent_pyramid_plan_create(silent_ctx* ctx, int frame_h, int frame_w, int channels,
+                                             const silent_pyr_level* levels, int n_levels,
+                                             silent_pyramid_plan** out) {
+    return silent_pyramid_plan_create_ex(ctx, frame_h, frame_w, channels, levels, n_levels, 0u, out);
+}
+
+SILENT_EXPORT int silent_pyramid_plan_flags(const silent_pyramid_plan* plan, unsigned* flags) try {
+    if (!plan || !flags) return SILENT_E_INVALID;
+    *flags = plan->flags;
+    return SILENT_OK;
+} catch (...) {
+    return on_exception(nullptr, "silent_pyramid_plan_flags");
+}
+
 SILENT_EXPORT void silent_pyramid_plan_destroy(silent_pyramid_plan* plan) try {
     if (!plan) return;
     DeviceGuard guard(plan->ctx ? plan->ctx->device : 0);
     if (plan->tables) (void)hipFree(plan->tables);
+    if (plan->tables64) (void)hipFree(plan->tables64);
     if (plan->stream_tables) (void)hipFree(plan->stream_tables);
     if (plan->walk_tables) (void)hipFree(plan->walk_tables);
     delete plan;
@@ -616,10 +660,11 @@ int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* 
         // single-read pyramid: frame -> every level in one kernel (pyramid_stream_kernel; single-channel plans only:
         // on interleaved RGB the stride-3 accesses of the same kernel made it 1.5x SLOWER than unit + region kernels)
         const PyrLevelDev& d = tab.lv[plan->stream_unit_level];
-        FusedTab ft;
+        FusedTab64 ft;   // (the float32 kernels take its FusedTab part)
         std::memset(&ft, 0, sizeof(ft));
         ft.n = 1;
         for (int j = 0; j < 6; ++j) ft.wx[j] = ft.wy[j] = plan->unit_w[j];
+        for (int j = 0; j < 6; ++j) ft.w64[j] = plan->unit_w64[j];
         FusedLevel& f = ft.lv[0];
         f.src_y0 = d.src_y0; f.src_x0 = d.src_x0; f.src_h = d.src_h; f.src_w = d.src_w;
         f.zoom_h = d.zoom_h; f.zoom_w = d.zoom_w; f.out_h = d.out_h; f.out_w = d.out_w;
@@ -631,11 +676,16 @@ int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* 
         ft.frame_px = tab.frame_px_out;
         const long long blocks = (long long)ft.tiles_per_frame * n_frames;
         if (blocks > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many tiles for one launch");
-#define PYR_STREAM(G_, L_) \
-    hipLaunchKernelGGL((pyramid_stream_kernel<1, G_, L_>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, ft, plan->stream)
-        if (plan->stream_layout == 1) PYR_STREAM(7, 1);
-        else if (plan->stream.G <= 4) PYR_STREAM(4, 0);
-        else PYR_STREAM(7, 0);
+#define PYR_STREAM(G_, L_)                                                                                                                 \
+    if (plan->f64)                                                                                                                         \
+        hipLaunchKernelGGL((pyramid_stream_kernel<1, G_, L_, true>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, ft, \
+                           plan->stream);                                                                                                  \
+    else                                                                                                                                   \
+        hipLaunchKernelGGL((pyramid_stream_kernel<1, G_, L_>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr,          \
+                           static_cast<const FusedTab&>(ft), plan->stream)
+        if (plan->stream_layout == 1) { PYR_STREAM(7, 1); }
+        else if (plan->stream.G <= 4) { PYR_STREAM(4, 0); }
+        else { PYR_STREAM(7, 0); }
 #undef PYR_STREAM
     } else if (tab.C == 3 && plan->walk_pyr_ok && with_unit && with_region && !(kopts & 3u) && walk3_plan(ctx, plan, n_frames, &w3t)) {
         // single-read RGB pyramid (pyramid_walk3_kernel, silent_walk_rgb.h); PYRAMID knob bits 1 / 2: unit + region kernels
@@ -662,6 +712,9 @@ int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* 
 #undef WALK3
         if (bblocks > 0 && !border_inside)
             hipLaunchKernelGGL(pyramid_border_kernel<3>, dim3((unsigned)bblocks), dim3(256), 0, s, frames, pyr, tab, plan->walk_border, n_frames);
+    } else if (plan->f64) {   // (single-channel)
+        if (b_unit) hipLaunchKernelGGL((pyramid_unit_kernel<1, true>), dim3((unsigned)b_unit), dim3(256), 0, s, frames, pyr, plan->tab64);
+        if (b_region) hipLaunchKernelGGL((pyramid_region_kernel<1, true>), dim3((unsigned)b_region), dim3(256), 0, s, frames, pyr, plan->tab64);
     } else if (tab.C == 1) {
         if (b_unit) hipLaunchKernelGGL(pyramid_unit_kernel<1>, dim3((unsigned)b_unit), dim3(256), 0, s, frames, pyr, tab);
         if (b_region) hipLaunchKernelGGL(pyramid_region_kernel<1>, dim3((unsigned)b_region), dim3(256), 0, s, frames, pyr, tab);

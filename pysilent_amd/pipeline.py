@@ -131,7 +131,14 @@ class LineEndPipeline(object):
                  constants=None, center_dimensions=None, clip_hi=255.0, flat_policy="ieee", pad=2,
                  max_keypoints_per_frame=None, selection=False, top_percent=0.1, keep_selection_maps=False, value_map=None,
                  peak_value_map=None, orient_map=True, overlap=False, overlap_priorities=True, placement="auto", keypoints=False,
-                 regions=None):
+                 regions=None, accumulation="float32"):
+        # accumulation="float64" (mode "gray"): every op sums its taps in float64 and rounds once to float32, like the CPU oracle
+        # (SILENT_PLAN_ACCUM_F64: the pyramid within 1 ulp of it, CS and end bit-identical to it on the same pyramid).  Checked first:
+        # no GPU or torch work for a refused argument
+        _runtime.check_accumulation(accumulation)
+        if accumulation == "float64" and mode != "gray":
+            raise ValueError("accumulation='float64' is for mode 'gray' (the RGB chain accumulates in float32)")
+        self.accumulation = accumulation
         import torch
         self.torch = torch
         self.mode = mode
@@ -149,7 +156,7 @@ class LineEndPipeline(object):
             y0 = min(l[0] for l in levels); x0 = min(l[1] for l in levels)
             y1 = max(l[0] + l[2] for l in levels); x1 = max(l[1] + l[3] for l in levels)
             self.crop_px = (y1 - y0) * (x1 - x0)
-        self.plan = _runtime.PyramidPlan(h, w, self.channels, levels, self.device_index)
+        self.plan = _runtime.PyramidPlan(h, w, self.channels, levels, self.device_index, accumulation=accumulation)
         self.extents = self.plan.extents
         self.frame_px = self.plan.frame_px
         self.n_levels = len(self.extents)
@@ -530,7 +537,7 @@ class LineEndPipeline(object):
     def launch_summary(self):
         if self.mode == "gray":
             return ("gray_stream_kernel (whole pyramid + level-0 CS/line-end, frame read once) + "
-                    "gray_line_end_kernel (levels >= 1)")
+                    "gray_line_end_kernel (levels >= 1)" + (", float64 accumulation" if self.accumulation == "float64" else ""))
         return ("single-read RGB pyramid (pyramid_walk3_kernel), fused RGB chain, max/min + fused selection "
                 "(top 10 % > NMS > value), cell-max / count / scan / write keypoint kernels")
 
