@@ -189,6 +189,23 @@ int silent_gray_pass_parts_dev(silent_ctx* ctx, const silent_pyramid_plan* plan,
                                const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
                                float* cs_out, float* end_out, unsigned parts, silent_stream stream);
 
+/* float16 storage of the CS and end maps: the pass above (same op order, recognition_testing.py:136-144, :69-74) with cs_out and
+ * end_out stored as IEEE binary16 -- half the bytes of the two maps a caller keeps (their consumers are a display path that divides
+ * by 255, recognition_testing.py:54, :79, and a selection that reads values in [0, clip_hi]).  Every stored element is float16(v),
+ * v being the float32 value silent_gray_pass[_dev] stores for that element: all arithmetic is the float32 code, the conversion
+ * happens at the store, round-to-nearest-even, overflow to +-inf, NaN stays NaN (sign and payload unspecified), subnormals kept.
+ * pyr stays float32 (an output of the reference's from_image, and the filter of the non-unit levels reads it back).  end_out keeps
+ * its NHWC layout [.., h, w, K], 2 * K bytes per pixel; end_out must be 16-byte and cs_out 2-byte aligned.  cs_out or end_out may
+ * be NULL.  parts as silent_gray_pass_parts_dev (3 = the whole pass).  SILENT_E_UNSUPPORTED: a 3-channel plan, a plan created
+ * with SILENT_PLAN_ACCUM_F64, n_orient other than 3, 4 or 8.  There is no float16 form of silent_gray_keypoints (its tail reads
+ * the end map as float32) nor of the per-op silent_gray_line_end. */
+int silent_gray_pass_h(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
+                       const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                       uint16_t* cs_out, uint16_t* end_out);
+int silent_gray_pass_h_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
+                           const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                           uint16_t* cs_out, uint16_t* end_out, unsigned parts, silent_stream stream);
+
 /* 1 when silent_gray_pass runs this plan through the single-read stream kernel (one unit-zoom level and every
  * other level resampling the same crop with a step > 1.25: classic whole-frame pyramids), 0 when it falls
  * back to region + unit-fused + filter kernels (e.g. the reference's centred-crop layout).  The same for

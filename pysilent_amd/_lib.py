@@ -75,6 +75,7 @@ _lib = None
 
 _vp = C.c_void_p
 _fp = C.c_void_p          # float* passed as an address (host ndarray.ctypes.data or a device pointer)
+_hp = C.POINTER(C.c_uint16)   # a float16 map (silent_gray_pass_h: IEEE binary16 as uint16_t*); half_ptr() makes one from an address
 _ep = C.POINTER(Extent)
 _i, _u, _f, _d, _sz = C.c_int, C.c_uint, C.c_float, C.c_double, C.c_size_t
 
@@ -106,6 +107,8 @@ _SIGNATURES = {
     "silent_gray_pass": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp],
     "silent_gray_pass_dev": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _vp],
     "silent_gray_pass_parts_dev": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _u, _vp],
+    "silent_gray_pass_h": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _hp, _hp],
+    "silent_gray_pass_h_dev": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _hp, _hp, _u, _vp],
     "silent_pyramid_plan_is_streamable": [_vp],
     "silent_pyramid_plan_walk_plans": [_vp, C.POINTER(C.c_int)],
     "silent_gather_d2h": [_vp, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), _i, _vp],
@@ -163,6 +166,11 @@ _SIGNATURES = {
 _RESTYPES = {"silent_destroy": None, "silent_pyramid_plan_destroy": None, "silent_displayer_destroy": None, "silent_last_error": C.c_char_p}
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
+
+
+def half_ptr(address):
+    """A host or device address as the uint16_t* of a float16 map argument (None: NULL)."""
+    return None if address is None else C.cast(C.c_void_p(int(address)), _hp)
 
 
 def _preload_hip_runtime():

@@ -181,9 +181,13 @@ class PackedPyramid(object):
     """A batch of pyramids with per-level extents, packed as the C ABI wants it.
 
     ``data`` is a flat float32 buffer (np.ndarray, or torch tensor on the GPU) of
-    ``n_frames * sum(h_l * w_l) * channels`` elements: frames outermost, then levels, NHWC inside."""
+    ``n_frames * sum(h_l * w_l) * channels`` elements: frames outermost, then levels, NHWC inside.  ``dtype``: np.float32, or
+    np.float16 for the CS / end maps of a gray pass with storage="float16" (a torch buffer keeps its own dtype)."""
 
-    def __init__(self, data, extents, channels, n_frames=1):
+    def __init__(self, data, extents, channels, n_frames=1, dtype=np.float32):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
+            raise ValueError("PackedPyramid: dtype must be float32 or float16, got %s" % (self.dtype,))
         self.extents = [(int(h), int(w)) for h, w in extents]
         self.channels = int(channels)
         self.n_frames = int(n_frames)
@@ -192,9 +196,11 @@ class PackedPyramid(object):
         if is_torch_tensor(data):
             data = data.reshape(-1)
         else:
-            data = np.ascontiguousarray(data, dtype=np.float32).reshape(-1)
+            data = np.ascontiguousarray(data, dtype=self.dtype).reshape(-1)
         if data.shape[0] != n:
             raise ValueError("PackedPyramid: buffer holds %d floats, extents need %d" % (data.shape[0], n))
+        if is_torch_tensor(data) and data.element_size() != self.dtype.itemsize:
+            raise ValueError("PackedPyramid: a %s buffer for dtype %s" % (data.dtype, self.dtype))
         self.data = data
 
     @property
@@ -226,10 +232,10 @@ class PackedPyramid(object):
         if data is None:
             if self.on_device:
                 import torch
-                data = torch.empty(n, dtype=torch.float32, device=self.data.device)
+                data = torch.empty(n, dtype=self.data.dtype, device=self.data.device)
             else:
-                data = np.empty(n, dtype=np.float32)
-        return PackedPyramid(data, self.extents, channels, self.n_frames)
+                data = np.empty(n, dtype=self.dtype)
+        return PackedPyramid(data, self.extents, channels, self.n_frames, dtype=self.dtype)
 
 
 class _Operand(object):
@@ -280,7 +286,8 @@ class _Operand(object):
         """A result buffer placed like the operand (torch tensor on its device, or ndarray) and its address."""
         if self.dev:
             import torch
-            out = torch.empty(shape, dtype={np.float32: torch.float32, np.int64: torch.int64}[dtype], device=self._torch_device)
+            out = torch.empty(shape, dtype={np.float32: torch.float32, np.int64: torch.int64, np.float16: torch.float16}[dtype],
+                              device=self._torch_device)
             return out, C.c_void_p(out.data_ptr())
         out = np.empty(shape, dtype=dtype)
         return out, C.c_void_p(out.ctypes.data)
@@ -722,6 +729,25 @@ def check_accumulation(accumulation):
     return accumulation
 
 
+STORAGES = ("float32", "float16")
+
+
+def check_storage(storage, mode="gray", accumulation="float32", keypoints=False):
+    """The storage argument of PyramidPlan.gray_pass / LineEndPipeline: "float32" (default) or "float16" (the CS and end maps of
+    the gray pass stored as IEEE binary16, silent_gray_pass_h).  The name is checked first; then the combinations float16 storage
+    does not exist for: mode "rgb", accumulation="float64", keypoints=True (the keypoint tail reads the end map as float32)."""
+    if storage not in STORAGES:
+        raise ValueError("storage must be 'float32' or 'float16', got %r" % (storage,))
+    if storage == "float16":
+        if mode != "gray":
+            raise ValueError("storage='float16' is for mode 'gray' (the RGB maps are stored as float32)")
+        if accumulation == "float64":
+            raise ValueError("storage='float16' does not combine with accumulation='float64'")
+        if keypoints:
+            raise ValueError("storage='float16' does not combine with keypoints=True (the keypoint tail reads the end map as float32)")
+    return storage
+
+
 class PyramidPlan(object):
     """Tap tables of one (frame size, level geometry) on the device.  ``levels`` is a list of dicts / tuples
     (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w).  accumulation="float64" (single-channel plans): every op of
@@ -775,9 +801,11 @@ class PyramidPlan(object):
         n = _lib.load().silent_pyramid_plan_walk_plans(self.handle, C.byref(px))
         return int(n), int(px.value)
 
-    def gray_pass(self, frames, cs_kernel, end_bank, clip_hi=255.0):
+    def gray_pass(self, frames, cs_kernel, end_bank, clip_hi=255.0, storage="float32"):
         """Whole grayscale hot path (silent_gray_pass): frames [n,H,W,1] -> (pyramid, cs, end) PackedPyramids.
-        Same results as run() + gray_line_end(), one pass less over level 0."""
+        Same results as run() + gray_line_end(), one pass less over level 0.  storage="float16" (silent_gray_pass_h): cs and end
+        are float16 maps -- each element the float32 result rounded to nearest even -- and the pyramid stays float32."""
+        check_storage(storage, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
         if self.frame_shape[2] != 1:
             raise ValueError("gray_pass needs a single-channel plan")
         cs = _kernel_arg(cs_kernel, 1)
@@ -787,11 +815,20 @@ class PyramidPlan(object):
         K = eb.shape[3]
         op = self._frames(frames)
         n = op.n_frames
-        (pyr, pp), (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch) for ch in (1, 1, K)]
-        op.call("gray_pass", self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi),
-                pp, cp, ep)
+        if storage == "float16":
+            pyr, pp = op.empty(n * self.frame_px)
+            (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch, np.float16) for ch in (1, K)]
+            args = (self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi), pp,
+                    _lib.half_ptr(cp.value), _lib.half_ptr(ep.value))
+            op.call("gray_pass_h", *(args + ((3,) if op.dev else ())))
+            dt = np.float16
+        else:
+            (pyr, pp), (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch) for ch in (1, 1, K)]
+            op.call("gray_pass", self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi),
+                    pp, cp, ep)
+            dt = np.float32
         P = PackedPyramid
-        return P(pyr, self.extents, 1, n), P(cso, self.extents, 1, n), P(endo, self.extents, K, n)
+        return P(pyr, self.extents, 1, n), P(cso, self.extents, 1, n, dtype=dt), P(endo, self.extents, K, n, dtype=dt)
 
     def gray_keypoints(self, frames, cs_kernel, end_bank, clip_hi=255.0, pad=2, selection=True, top_percent=0.1, regions=None,
                        cap_per_frame=None):

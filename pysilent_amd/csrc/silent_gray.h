@@ -57,6 +57,84 @@ __device__ __forceinline__ void store_row_k8(float* __restrict__ row_base /* add
     }
 }
 
+// ---- float16 storage of the CS and end maps (the ST = gray_half instantiations, silent_gray_pass_h): every value is computed as
+// float32 exactly as in the ST = float kernels and converted at the store, round-to-nearest-even (v_cvt_f16_f32: overflow to inf,
+// NaN stays NaN, subnormals kept).  Only the store sites differ.  The pyramid stays float32.
+typedef _Float16 gray_half;
+
+// K = 8 with float16 storage: a pixel's 8 halves ARE one 16-byte piece, so the lanes' own stores already cover one contiguous run
+// (60 x 16 bytes per wave instruction) -- the transpose through the LDS slab that the float32 row needs has nothing left to do.
+template <bool NT = false>
+__device__ __forceinline__ void store_row_k8(gray_half* __restrict__ row_base /* address of pixel of lane 0 */, const float (&acc)[8],
+                                             float* /* no slab */, int lane, int first, int count) {
+    typedef gray_half nh8 __attribute__((ext_vector_type(8)));
+    const nh8 v = {(gray_half)acc[0], (gray_half)acc[1], (gray_half)acc[2], (gray_half)acc[3],
+                   (gray_half)acc[4], (gray_half)acc[5], (gray_half)acc[6], (gray_half)acc[7]};
+    nh8* out8 = reinterpret_cast<nh8*>(row_base);
+    if (lane >= first && lane < first + count) {
+        if constexpr (NT) __builtin_nontemporal_store(v, out8 + lane);
+        else out8[lane] = v;
+    }
+}
+
+// A lane's K end values of one pixel (po: that pixel).  ST = float: the stores of the float32 kernels, verbatim.  ST = gray_half:
+// K = 4 one 8-byte store (8 bytes per pixel: always aligned), K = 3 three 2-byte stores.
+template <int K, bool NT, typename ST>
+__device__ __forceinline__ void store_end_px(ST* __restrict__ po, const float (&acc)[K]) {
+    static_assert(K == 3 || K == 4, "K = 8 rows go through store_row_k8");
+    if constexpr (K == 4) {
+        typedef ST v4 __attribute__((ext_vector_type(4)));
+        const v4 v = {(ST)acc[0], (ST)acc[1], (ST)acc[2], (ST)acc[3]};
+        if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<v4*>(po));
+        else *reinterpret_cast<v4*>(po) = v;
+    } else {
+#pragma unroll
+        for (int k = 0; k < K; ++k) po[k] = (ST)acc[k];
+    }
+}
+
+// One row of the float16 CS map: lanes first .. first + count - 1 of the wave hold the float32 values of consecutive pixels, row0 is
+// the address of lane 0's pixel.  2 bytes per pixel: a plain per-lane store would be a 2-byte store instruction, the slowest per
+// byte of the store table (MI355X_MICROARCH).  PAIRED form: the lane whose pixel sits on a 4-byte boundary takes its right
+// neighbour's half by DPP and stores one dword; which lane parity that is depends on the row's address (rows of an odd-width
+// level, or a level at an odd pixel offset, start on a 2-byte boundary only), so it is chosen per row from row0.  The first pixel
+// of an odd-aligned run and the last pixel of a run that ends on an even one have no partner: those (at most two lanes) store
+// 2 bytes.  SILENT_F16_CS_PAIRED = 0 builds the plain form for A/B timing.
+#ifndef SILENT_F16_CS_PAIRED
+#define SILENT_F16_CS_PAIRED 1
+#endif
+template <bool NT>
+__device__ __forceinline__ void store_cs_row(gray_half* __restrict__ row0, float v, int lane, int first, int count) {
+    const gray_half h = (gray_half)v;
+    const unsigned mine = (unsigned)__builtin_bit_cast(unsigned short, h);
+    const bool own = lane >= first && lane < first + count;
+#if SILENT_F16_CS_PAIRED
+    const unsigned up = (unsigned)__builtin_amdgcn_update_dpp(0, (int)mine, 0x130 /* wave_shl:1 */, 0xf, 0xf, true);   // lane + 1's
+    const int odd0 = (int)((reinterpret_cast<unsigned long long>(row0) >> 1) & 1ull);   // wave-uniform: lane 0's pixel is off the dword grid
+    const bool lead = ((lane + odd0) & 1) == 0;                                          // this lane's pixel starts a dword
+    const bool pair = own && lead && lane + 1 < first + count;
+    const bool single = own && (lead ? lane + 1 >= first + count : lane == first);
+    if (pair) {
+        unsigned* p = reinterpret_cast<unsigned*>(row0 + lane);
+        if constexpr (NT) __builtin_nontemporal_store(mine | (up << 16), p);
+        else *p = mine | (up << 16);
+    }
+    if (single) {
+        unsigned short* p = reinterpret_cast<unsigned short*>(row0 + lane);
+        if constexpr (NT) __builtin_nontemporal_store((unsigned short)mine, p);
+        else *p = (unsigned short)mine;
+    }
+#else
+    if (own) {
+        unsigned short* p = reinterpret_cast<unsigned short*>(row0 + lane);
+        if constexpr (NT) __builtin_nontemporal_store((unsigned short)mine, p);
+        else *p = (unsigned short)mine;
+    }
+#endif
+}
+template <typename ST>
+constexpr bool kStoreHalf = std::is_same<ST, gray_half>::value;
+
 // ---- keypoint epilogue (KP instantiations, silent_gray_keypoints): the selection tail's inputs from the registers that hold a
 // pixel's K end values, so that nothing re-reads the end map for a reduction.  Per pixel the value of the PADDED map, with the
 // operations of pad_inwards_kernel (m * e) and value_from_color_kernel (sum left to right, one multiply by 1/K); per lane the
@@ -158,13 +236,14 @@ __device__ __forceinline__ float unit_vsum_f64(const double (&w)[6], const doubl
     return (float)v;
 }
 
-template <int K, int R, bool KP = false, bool F64 = false>
+template <int K, int R, bool KP = false, bool F64 = false, typename ST = float>
 __global__ __launch_bounds__(256) void gray_line_end_kernel(const float* __restrict__ pyr,
-                                                            float* __restrict__ cs_out,
-                                                            float* __restrict__ end_out, const LevelTab tab,
+                                                            ST* __restrict__ cs_out,
+                                                            ST* __restrict__ end_out, const LevelTab tab,
                                                             const GrayW wts, float clip_hi, unsigned opts,
                                                             const GrayKp kp = GrayKp{}) {
-    __shared__ __attribute__((aligned(16))) float s_slab[K == 8 ? 4 * 512 : 4];  // K = 8 store transpose, per wave
+    static_assert(!kStoreHalf<ST> || (!KP && !F64), "float16 storage: no keypoint epilogue, no float64 accumulation");
+    __shared__ __attribute__((aligned(16))) float s_slab[K == 8 && !kStoreHalf<ST> ? 4 * 512 : 4];  // K = 8 store transpose, per wave
     const TileCoord tc = locate_tile(tab, (opts & 1u) ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x);
     const int H = tab.h[tc.level], W = tab.w[tc.level];
     const long long base_px = (long long)tc.frame * tab.frame_px + tab.px_off[tc.level];
@@ -238,7 +317,9 @@ __global__ __launch_bounds__(256) void gray_line_end_kernel(const float* __restr
             const int y = y0 + i - 4;  // output row
             if (y < H) {               // wave-uniform
                 const long long px = base_px + (long long)y * W + x;
-                if (cs_out && out_lane) {
+                if constexpr (kStoreHalf<ST>) {
+                    if (cs_out) store_cs_row<false>(cs_out + (base_px + (long long)y * W + (xw0 - 2)), cw[1][1], lane, 2, min(kGrayCols, W - xw0));
+                } else if (cs_out && out_lane) {
                     cs_out[px] = cw[1][1];  // (non-temporal here: within noise, unlike in gray_stream_kernel)
                 }
                 if (end_out) {
@@ -264,8 +345,10 @@ __global__ __launch_bounds__(256) void gray_line_end_kernel(const float* __restr
                         store_row_k8(end_out + (base_px + (long long)y * W + (xw0 - 2)) * 8, acc, s_slab + wave * 512, lane,
                                      2, ncols);
                     } else if (out_lane) {
-                        float* __restrict__ po = end_out + px * K;
-                        if constexpr (K == 4) {
+                        ST* __restrict__ po = end_out + px * K;
+                        if constexpr (kStoreHalf<ST>) {
+                            store_end_px<K, false>(po, acc);
+                        } else if constexpr (K == 4) {
                             typedef float nf4 __attribute__((ext_vector_type(4)));
                             const nf4 v4 = {acc[0], acc[1], acc[2], acc[3]};
                             *reinterpret_cast<nf4*>(po) = v4;
@@ -337,12 +420,13 @@ struct FusedTab64 : FusedTab {
 template <bool F64>
 using FusedTabT = typename std::conditional<F64, FusedTab64, FusedTab>::type;
 
-template <int K, int R, bool KP = false, bool F64 = false>
+template <int K, int R, bool KP = false, bool F64 = false, typename ST = float>
 __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const float* __restrict__ frames,
-                                                              float* __restrict__ pyr, float* __restrict__ cs_out,
-                                                              float* __restrict__ end_out, const FusedTabT<F64> tab,
+                                                              float* __restrict__ pyr, ST* __restrict__ cs_out,
+                                                              ST* __restrict__ end_out, const FusedTabT<F64> tab,
                                                               const GrayW wts, float clip_hi, const GrayKp kp = GrayKp{}) {
-    __shared__ __attribute__((aligned(16))) float s_slab[K == 8 ? kFusedWaves * 512 : 4];  // K = 8 store transpose, per wave
+    static_assert(!kStoreHalf<ST> || (!KP && !F64), "float16 storage: no keypoint epilogue, no float64 accumulation");
+    __shared__ __attribute__((aligned(16))) float s_slab[K == 8 && !kStoreHalf<ST> ? kFusedWaves * 512 : 4];  // K = 8 store transpose, per wave
     const unsigned bid = blockIdx.x;
     const int frame = (int)(bid / (unsigned)tab.tiles_per_frame);
     int rem = (int)(bid - (unsigned)frame * (unsigned)tab.tiles_per_frame);
@@ -447,7 +531,11 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
             const int y = y0 + i - 9;
             if (y < lv.out_h) {  // wave-uniform
                 const long long px = base_px + (long long)y * lv.out_w + ox;
-                if (cs_out && out_lane) cs_out[px] = cw[1][1];  // (non-temporal here: 6 % SLOWER, unlike in gray_stream_kernel)
+                if constexpr (kStoreHalf<ST>) {
+                    if (cs_out)
+                        store_cs_row<false>(cs_out + (base_px + (long long)y * lv.out_w + (xw0 - 4)), cw[1][1], lane, 4,
+                                            min(kFusedCols, lv.out_w - xw0));
+                } else if (cs_out && out_lane) cs_out[px] = cw[1][1];  // (non-temporal here: 6 % SLOWER, unlike in gray_stream_kernel)
                 if (end_out) {
                     float acc[K];
                     if constexpr (F64) {
@@ -470,8 +558,10 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
                         store_row_k8(end_out + (base_px + (long long)y * lv.out_w + (xw0 - 4)) * 8, acc,
                                      s_slab + wave * 512, lane, 4, ncols);
                     } else if (out_lane) {
-                        float* __restrict__ po = end_out + px * K;
-                        if constexpr (K == 4) {
+                        ST* __restrict__ po = end_out + px * K;
+                        if constexpr (kStoreHalf<ST>) {
+                            store_end_px<K, false>(po, acc);
+                        } else if constexpr (K == 4) {
                             *reinterpret_cast<float4*>(po) = make_float4(acc[0], acc[1], acc[2], acc[3]);
                         } else {
 #pragma unroll
@@ -631,13 +721,14 @@ __device__ __forceinline__ void stream_level_f64(int g, const int (&cur)[PR], fl
 #endif
 constexpr int kStreamRegLevels = SILENT_STREAM_REG_LEVELS;
 
-template <int K, int G, int L = 0, bool KP = false, bool F64 = false>
+template <int K, int G, int L = 0, bool KP = false, bool F64 = false, typename ST = float>
 __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const float* __restrict__ frames, float* __restrict__ pyr,
-                                                          float* __restrict__ cs_out, float* __restrict__ end_out,
+                                                          ST* __restrict__ cs_out, ST* __restrict__ end_out,
                                                           const FusedTabT<F64> tab, const StreamTab st, const GrayW wts,
                                                           float clip_hi, unsigned opts, const GrayKp kp = GrayKp{}) {
     constexpr int R = kFusedTH, NR = kStreamRows;
-    __shared__ __attribute__((aligned(16))) float s_slab[K == 8 ? kFusedWaves * 512 : 4];
+    static_assert(!kStoreHalf<ST> || (!KP && !F64), "float16 storage: no keypoint epilogue, no float64 accumulation");
+    __shared__ __attribute__((aligned(16))) float s_slab[K == 8 && !kStoreHalf<ST> ? kFusedWaves * 512 : 4];
     __shared__ __attribute__((aligned(16))) float s_rows[kFusedWaves][NR][64];  // the streamed rows of each wave (wave private)
     const unsigned bid = (opts & 1u) ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x;
     const int frame = (int)(bid / (unsigned)tab.tiles_per_frame);
@@ -863,7 +954,9 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
                 const int y = y0 + i - 9;
                 if (y < lv.out_h) {  // wave-uniform
                     const long long row_px = wave_px + (long long)y * lv.out_w;
-                    if (cs_out) {
+                    if constexpr (kStoreHalf<ST>) {
+                        if (cs_out) store_cs_row<true>(cs_out + row_px, cw[1][1], lane, 4, min(kFusedCols, lv.out_w - xw0));
+                    } else if (cs_out) {
                         float* __restrict__ crow = cs_out + row_px;
                         if (out_lane) __builtin_nontemporal_store(cw[1][1], crow + lane);
                     }
@@ -890,6 +983,8 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
                         if constexpr (K == 8) {
                             const int ncols = min(kFusedCols, lv.out_w - xw0);
                             store_row_k8<true>(end_out + row_px * 8, acc, s_slab + wave * 512, lane, 4, ncols);
+                        } else if constexpr (kStoreHalf<ST>) {
+                            if (out_lane) store_end_px<K, K == 4>(end_out + (row_px + lane) * K, acc);   // (non-temporal where the float32 row is: K = 4)
                         } else if constexpr (K == 4) {
                             // non-temporal like the two 4-byte maps: whole pass -1.6 % (the kernel alone -0.7 %: the rest is
                             // gray_line_end_kernel finding more of the pyramid's levels >= 1 in the Infinity Cache)

@@ -6,21 +6,30 @@ using namespace silent;
 
 // ------------------------------------------------------------------------------------------ fused gray pass
 
+// ST: the element type of the CS and end maps -- float, or gray_half (float16 storage: silent_gray_pass_h).  The gray_half kernels
+// exist without keypoint epilogue and without float64 accumulation only (both are refused before a launch), so those template
+// combinations are never instantiated.
 // f64: the F64 kernel (float64 accumulation; F64 plans only, silent_gray_line_end always runs float32)
-template <int K, bool F64>
-static void launch_line_end(long long blocks, hipStream_t s, const float* pyr, float* cs_out, float* end_out, const LevelTab& tab,
+template <int K, bool F64, typename ST>
+static void launch_line_end(long long blocks, hipStream_t s, const float* pyr, ST* cs_out, ST* end_out, const LevelTab& tab,
                             const GrayW& w, float clip_hi, unsigned opts, const GrayKp* kp) {
+    if constexpr (kStoreHalf<ST>) {
+        hipLaunchKernelGGL((gray_line_end_kernel<K, kGrayTH, false, false, ST>), dim3((unsigned)blocks), dim3(256), 0, s, pyr, cs_out,
+                           end_out, tab, w, clip_hi, opts);
+    } else {
     if (kp)
         hipLaunchKernelGGL((gray_line_end_kernel<K, kGrayTH, true, F64>), dim3((unsigned)blocks), dim3(256), 0, s, pyr, cs_out, end_out,
                            tab, w, clip_hi, opts, *kp);
     else
         hipLaunchKernelGGL((gray_line_end_kernel<K, kGrayTH, false, F64>), dim3((unsigned)blocks), dim3(256), 0, s, pyr, cs_out, end_out,
                            tab, w, clip_hi, opts);
+    }
 }
 
+template <typename ST>
 static int launch_gray(silent_ctx* ctx, const char* who, const float* pyr, const silent_extent* levels, int n_levels,
                        int n_frames, const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi,
-                       float* cs_out, float* end_out, hipStream_t s, const bool* skip, const GrayKp* kp = nullptr, bool f64 = false) {
+                       ST* cs_out, ST* end_out, hipStream_t s, const bool* skip, const GrayKp* kp = nullptr, bool f64 = false) {
     if (!pyr || !cs_kernel) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (!cs_out && !end_out) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": both outputs are NULL");
     if (end_out && !end_bank) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": end_bank is NULL");
@@ -40,8 +49,9 @@ static int launch_gray(silent_ctx* ctx, const char* who, const float* pyr, const
     std::memcpy(w.cs, cs_kernel, sizeof(float) * 9);
     if (end_bank) std::memcpy(w.end, end_bank, sizeof(float) * 9 * n_orient);
 #define GRAY_LAUNCH(K_)                                                                   \
-    if (f64) launch_line_end<K_, true>(blocks, s, pyr, cs_out, end_out, tab, w, clip_hi, opts, kp); \
-    else launch_line_end<K_, false>(blocks, s, pyr, cs_out, end_out, tab, w, clip_hi, opts, kp)
+    if constexpr (kStoreHalf<ST>) launch_line_end<K_, false, ST>(blocks, s, pyr, cs_out, end_out, tab, w, clip_hi, opts, nullptr); \
+    else if (f64) launch_line_end<K_, true, ST>(blocks, s, pyr, cs_out, end_out, tab, w, clip_hi, opts, kp); \
+    else launch_line_end<K_, false, ST>(blocks, s, pyr, cs_out, end_out, tab, w, clip_hi, opts, kp)
     if (n_orient == 3) { GRAY_LAUNCH(3); }
     else if (n_orient == 4) { GRAY_LAUNCH(4); }
     else { GRAY_LAUNCH(8); }
@@ -60,11 +70,14 @@ SILENT_EXPORT int silent_gray_line_end_dev(silent_ctx* ctx, const float* pyr, co
     return on_exception(ctx, "silent_gray_line_end_dev");
 }
 
-template <int K, int G, int L, bool F64>
-static void launch_stream(long long blocks, hipStream_t s, const float* frames, float* pyr, float* cs_out, float* end_out,
+template <int K, int G, int L, bool F64, typename ST>
+static void launch_stream(long long blocks, hipStream_t s, const float* frames, float* pyr, ST* cs_out, ST* end_out,
                           const FusedTab64& ft, const StreamTab& st, const GrayW& w, float clip_hi, unsigned opts, const GrayKp* kp) {
     const FusedTabT<F64>& t = ft;
-    if (kp)
+    if constexpr (kStoreHalf<ST>)
+        hipLaunchKernelGGL((gray_stream_kernel<K, G, L, false, false, ST>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames,
+                           pyr, cs_out, end_out, t, st, w, clip_hi, opts);
+    else if (kp)
         hipLaunchKernelGGL((gray_stream_kernel<K, G, L, true, F64>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr,
                            cs_out, end_out, t, st, w, clip_hi, opts, *kp);
     else
@@ -72,11 +85,14 @@ static void launch_stream(long long blocks, hipStream_t s, const float* frames, 
                            cs_out, end_out, t, st, w, clip_hi, opts);
 }
 
-template <int K, bool F64>
-static void launch_fused(long long blocks, hipStream_t s, const float* frames, float* pyr, float* cs_out, float* end_out,
+template <int K, bool F64, typename ST>
+static void launch_fused(long long blocks, hipStream_t s, const float* frames, float* pyr, ST* cs_out, ST* end_out,
                          const FusedTab64& ft, const GrayW& w, float clip_hi, const GrayKp* kp) {
     const FusedTabT<F64>& t = ft;
-    if (kp)
+    if constexpr (kStoreHalf<ST>)
+        hipLaunchKernelGGL((gray_unit_fused_kernel<K, kFusedTH, false, false, ST>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s,
+                           frames, pyr, cs_out, end_out, t, w, clip_hi);
+    else if (kp)
         hipLaunchKernelGGL((gray_unit_fused_kernel<K, kFusedTH, true, F64>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s,
                            frames, pyr, cs_out, end_out, t, w, clip_hi, *kp);
     else
@@ -86,12 +102,17 @@ static void launch_fused(long long blocks, hipStream_t s, const float* frames, f
 
 // parts: bit 0 = the pyramid of every level + CS / end of the unit levels (steps 1 and 2), bit 1 = CS + end of the remaining levels
 // (step 3, which reads the pyramid steps 1 and 2 wrote)
+template <typename ST>
 static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
                            const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
-                           float* cs_out, float* end_out, unsigned parts, silent_stream stream, const GrayKp* kp = nullptr) {
-    const char* who = "silent_gray_pass";
+                           ST* cs_out, ST* end_out, unsigned parts, silent_stream stream, const GrayKp* kp = nullptr) {
+    const char* who = kStoreHalf<ST> ? "silent_gray_pass_h" : "silent_gray_pass";
     if (!plan || !frames || !pyr || !cs_kernel) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
+    if constexpr (kStoreHalf<ST>) {
+        if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": float16 storage is for single-channel plans");
+        if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": float16 storage with a SILENT_PLAN_ACCUM_F64 plan");
+    }
     if (plan->tab.C != 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": the plan must be single-channel");
     if (!cs_out && !end_out) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": both outputs are NULL");
     if (end_out && !end_bank) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": end_bank is NULL");
@@ -153,8 +174,9 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
             const StreamTab& st = plan->stream;
             const unsigned sopts = (unsigned)((kopts >> 5) & 1);
 #define STREAM_LAUNCH(K_, G_, L_)                                                                                  \
-    if (plan->f64) launch_stream<K_, G_, L_, true>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp); \
-    else launch_stream<K_, G_, L_, false>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp)
+    if constexpr (kStoreHalf<ST>) launch_stream<K_, G_, L_, false, ST>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, nullptr); \
+    else if (plan->f64) launch_stream<K_, G_, L_, true, ST>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp); \
+    else launch_stream<K_, G_, L_, false, ST>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp)
             if (plan->stream_layout == 1) {          // zoom ladders of ratio 1.4 .. e^.5: five rows of the first level in flight
                 if (n_orient == 3) { STREAM_LAUNCH(3, 7, 1); }
                 else if (n_orient == 4) { STREAM_LAUNCH(4, 7, 1); }
@@ -171,8 +193,9 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
 #undef STREAM_LAUNCH
         } else {
 #define FUSED_LAUNCH(K_)                                                                                   \
-    if (plan->f64) launch_fused<K_, true>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp); \
-    else launch_fused<K_, false>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp)
+    if constexpr (kStoreHalf<ST>) launch_fused<K_, false, ST>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, nullptr); \
+    else if (plan->f64) launch_fused<K_, true, ST>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp); \
+    else launch_fused<K_, false, ST>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp)
             if (n_orient == 3) { FUSED_LAUNCH(3); }
             else if (n_orient == 4) { FUSED_LAUNCH(4); }
             else { FUSED_LAUNCH(8); }
@@ -256,4 +279,40 @@ SILENT_EXPORT int silent_gray_pass(silent_ctx* ctx, const silent_pyramid_plan* p
     });
 } catch (...) {
     return on_exception(ctx, "silent_gray_pass");
+}
+
+// ------------------------------------------------------------------------------------------ float16 storage of the CS and end maps
+// The same pass, the two maps stored as IEEE binary16 (the ST = gray_half instantiations of the same kernels; silent_hip.h has the
+// contract).  uint16_t in the C ABI: plain C has no half type.
+
+SILENT_EXPORT int silent_gray_pass_h_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
+                                         const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                         uint16_t* cs_out, uint16_t* end_out, unsigned parts, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return gray_pass_parts(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr,
+                           reinterpret_cast<gray_half*>(cs_out), reinterpret_cast<gray_half*>(end_out), parts, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_pass_h_dev");
+}
+
+SILENT_EXPORT int silent_gray_pass_h(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
+                                     const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                     uint16_t* cs_out, uint16_t* end_out) try {
+    NEED_CTX(ctx);
+    if (!plan || !frames || !pyr) return fail(ctx, SILENT_E_INVALID, "silent_gray_pass_h: NULL pointer");
+    if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_gray_pass_h: float16 storage is for single-channel plans");
+    if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_gray_pass_h: float16 storage with a SILENT_PLAN_ACCUM_F64 plan");
+    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, "silent_gray_pass_h: n_frames must be >= 1");
+    if (n_orient != 3 && n_orient != 4 && n_orient != 8)
+        return fail(ctx, SILENT_E_UNSUPPORTED, "silent_gray_pass_h: n_orient must be 3, 4 or 8");
+    HostStage hs(ctx);
+    const size_t px = (size_t)plan->tab.frame_px_out * n_frames;
+    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * 4 * n_frames), p = hs.out(pyr, px * 4), cs = hs.out(cs_out, px * 2),
+              end = hs.out(end_out, px * 2 * n_orient);
+    return hs.run([&] {
+        return silent_gray_pass_h_dev(ctx, plan, hs.dev<float>(x), n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
+                                      hs.dev<uint16_t>(cs), hs.dev<uint16_t>(end), 3u, nullptr);
+    });
+} catch (...) {
+    return on_exception(ctx, "silent_gray_pass_h");
 }

@@ -131,7 +131,7 @@ class LineEndPipeline(object):
                  constants=None, center_dimensions=None, clip_hi=255.0, flat_policy="ieee", pad=2,
                  max_keypoints_per_frame=None, selection=False, top_percent=0.1, keep_selection_maps=False, value_map=None,
                  peak_value_map=None, orient_map=True, overlap=False, overlap_priorities=True, placement="auto", keypoints=False,
-                 regions=None, accumulation="float32"):
+                 regions=None, accumulation="float32", storage="float32"):
         # accumulation="float64" (mode "gray"): every op sums its taps in float64 and rounds once to float32, like the CPU oracle
         # (SILENT_PLAN_ACCUM_F64: the pyramid within 1 ulp of it, CS and end bit-identical to it on the same pyramid).  Checked first:
         # no GPU or torch work for a refused argument
@@ -139,6 +139,10 @@ class LineEndPipeline(object):
         if accumulation == "float64" and mode != "gray":
             raise ValueError("accumulation='float64' is for mode 'gray' (the RGB chain accumulates in float32)")
         self.accumulation = accumulation
+        # storage="float16" (mode "gray"): the CS and end maps are stored as float16 (silent_gray_pass_h_dev) -- every element the
+        # float32 result rounded to nearest even, half the bytes written and kept; the pyramid stays float32.  Also refused before
+        # any GPU or torch work: unknown names, mode "rgb", accumulation="float64", keypoints=True
+        self.storage = _runtime.check_storage(storage, mode, accumulation, bool(keypoints))
         import torch
         self.torch = torch
         self.mode = mode
@@ -262,8 +266,9 @@ class LineEndPipeline(object):
         f32 = dict(dtype=torch.float32, device=self.tdev)
         m = {"pyr": torch.empty(n * self.channels, **f32)}
         if self.mode == "gray":
-            m["cs"] = torch.empty(n, **f32)
-            m["end"] = torch.empty(n * self.n_orient, **f32)
+            maps = dict(f32, dtype=torch.float16) if self.storage == "float16" else f32
+            m["cs"] = torch.empty(n, **maps)
+            m["end"] = torch.empty(n * self.n_orient, **maps)
         else:
             m["orient"] = torch.empty(n * 3, **f32) if self.orient_map else None
             m["line_end"] = torch.empty(n * 3, **f32)
@@ -299,7 +304,7 @@ class LineEndPipeline(object):
         spacers come from here, not from torch's caching allocator: nothing a draw leaves behind stays cached in the process."""
         nbytes = like.numel() * like.element_size()
         owner = _RawBlock(self.ctx, nbytes)
-        typestr = {4: "<f4", 1: "|u1", 8: "<i8"}[like.element_size()]
+        typestr = {4: "<f4", 1: "|u1", 8: "<i8", 2: "<f2"}[like.element_size()]
         owner.__cuda_array_interface__ = {"shape": tuple(like.shape), "typestr": typestr, "data": (owner.ptr, False), "version": 2}
         t = self.torch.as_tensor(owner, device=self.tdev)      # (holds a reference to ``owner`` for as long as the tensor lives)
         assert t.data_ptr() == owner.ptr
@@ -513,18 +518,24 @@ class LineEndPipeline(object):
     # -- byte accounting -------------------------------------------------------
     def algorithmic_bytes_per_frame(self):
         """4*[H*W*C (frame read) + P*C (pyramid written) + P*C (pyramid read) + P*sum(C_out returned)]; for crop layouts the
-        frame read is the largest crop any level resamples (the part of the frame the pyramid depends on)."""
+        frame read is the largest crop any level resamples (the part of the frame the pyramid depends on).  storage="float16":
+        the returned CS and end maps count 2 bytes per element."""
         h, w, c = self.frame_shape
         if self.crop_px is not None:
             h, w = 1, self.crop_px
         outs = (1 + self.n_orient) if self.mode == "gray" else (3 + (3 if self.orient_map else 0) + (1 if self.value_map else 0))
-        return 4 * (h * w * c + 2 * self.frame_px * c + self.frame_px * outs)
+        return 4 * (h * w * c + 2 * self.frame_px * c) + self._map_bytes * self.frame_px * outs
+
+    @property
+    def _map_bytes(self):
+        """Bytes per element of the returned dense maps (not the pyramid)."""
+        return 2 if self.storage == "float16" else 4
 
     def filter_bytes_per_frame(self):
         """The filter pass alone: pyramid read once + every returned map written once."""
         c = self.channels
         outs = (1 + self.n_orient) if self.mode == "gray" else (3 + (3 if self.orient_map else 0) + (1 if self.value_map else 0))
-        return 4 * self.frame_px * (c + outs)
+        return self.frame_px * (4 * c + self._map_bytes * outs)
 
     def pyramid_bytes_per_frame(self):
         h, w, c = self.frame_shape
@@ -537,7 +548,8 @@ class LineEndPipeline(object):
     def launch_summary(self):
         if self.mode == "gray":
             return ("gray_stream_kernel (whole pyramid + level-0 CS/line-end, frame read once) + "
-                    "gray_line_end_kernel (levels >= 1)" + (", float64 accumulation" if self.accumulation == "float64" else ""))
+                    "gray_line_end_kernel (levels >= 1)" + (", float64 accumulation" if self.accumulation == "float64" else "")
+                    + (", float16 CS / end maps" if self.storage == "float16" else ""))
         return ("single-read RGB pyramid (pyramid_walk3_kernel), fused RGB chain, max/min + fused selection "
                 "(top 10 % > NMS > value), cell-max / count / scan / write keypoint kernels")
 
@@ -560,6 +572,8 @@ class LineEndPipeline(object):
     def run_filters(self, stream=None):
         s = stream or self._stream()
         if self.mode == "gray":
+            if self.storage == "float16":
+                raise ValueError("storage='float16' has no per-op filter pass (silent_gray_line_end writes float32): use run_gray_pass")
             self.ctx.check(self._lib.silent_gray_line_end_dev(
                 self.ctx.handle, C.c_void_p(self.pyr.data_ptr()), self.levels_c, self.n_levels, self.batch,
                 C.c_void_p(self.consts["cs"].ctypes.data), C.c_void_p(self.consts["end"].ctypes.data), self.n_orient,
@@ -624,6 +638,13 @@ class LineEndPipeline(object):
         levels, fused pyramid + CS + end kernel for the unit levels, filter kernel for the rest.  ``parts``: 1 = pyramid + unit
         levels only, 2 = the filter of the remaining levels only (silent_gray_pass_parts_dev; the halves of an overlapped step)."""
         self._check_frames(frames)
+        if self.storage == "float16":      # the same pass, cs / end as float16 maps
+            self.ctx.check(self._lib.silent_gray_pass_h_dev(
+                self.ctx.handle, self.plan.handle, C.c_void_p(frames.data_ptr()), self.batch,
+                C.c_void_p(self.consts["cs"].ctypes.data), C.c_void_p(self.consts["end"].ctypes.data), self.n_orient,
+                self.clip_hi, C.c_void_p(self.pyr.data_ptr()), _lib.half_ptr(self.cs.data_ptr()),
+                _lib.half_ptr(self.end.data_ptr()), int(parts), stream or self._stream()))
+            return
         self.ctx.check(self._lib.silent_gray_pass_parts_dev(
             self.ctx.handle, self.plan.handle, C.c_void_p(frames.data_ptr()), self.batch,
             C.c_void_p(self.consts["cs"].ctypes.data), C.c_void_p(self.consts["end"].ctypes.data), self.n_orient,
@@ -782,8 +803,9 @@ class LineEndPipeline(object):
         self.wait()
         out = {"pyramid": P(self.pyr, self.extents, self.channels, self.batch)}
         if self.mode == "gray":
-            out["cs"] = P(self.cs, self.extents, 1, self.batch)
-            out["end"] = P(self.end, self.extents, self.n_orient, self.batch)
+            dt = np.float16 if self.storage == "float16" else np.float32
+            out["cs"] = P(self.cs, self.extents, 1, self.batch, dtype=dt)
+            out["end"] = P(self.end, self.extents, self.n_orient, self.batch, dtype=dt)
             if self.keypoints:
                 for name in ("value", "peak_value"):
                     if getattr(self, name) is not None:
