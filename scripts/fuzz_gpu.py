@@ -29,6 +29,27 @@ def make_kernels():
     return k
 
 
+def draw_weights(rng, k, gray=False):
+    """In half of the cases the class-generic weights of tests/chain_weights.py (a random structure class and seed; gray cases: the
+    CS kernel and banks of a random seed) instead of the reference's own, very symmetric kernels.  Returns (kernels,
+    " weights=<class>/<seed>") -- the label goes into the case description, so a failure names what to rebuild.  The seeds are those
+    at which tests/test_chain_weights.py shows a float32 evaluation inside the tolerance on ITS frames; on random frames the room
+    below the element-wise 1e-5 rule is small (torch float32: up to 8e-6), so replay a failure with weights=reference and with
+    another seed before reading it as a kernel's."""
+    import chain_weights as cw
+    if rng.integers(0, 2) == 0:
+        return k, " weights=reference"
+    name, seed = str(rng.choice(sorted(cw.RGB_BUILDERS))), int(rng.choice(cw.FUZZ_SEEDS))
+    g = dict(k)
+    if gray:
+        g["cs_gray"] = cw.gray_cs(seed)
+        for K in (3, 4, 8):
+            g["end%d" % K] = cw.gray_bank(K, seed)
+        return g, " weights=gray/%d" % seed
+    g.update(cw.RGB_BUILDERS[name](seed))
+    return g, " weights=%s/%d" % (name, seed)
+
+
 def frame(rng, h, w, c):
     seed = int(rng.integers(0, 1 << 30))
     kind = rng.integers(0, 3)
@@ -54,7 +75,8 @@ def case_gray_pass(rng, k):
     kg, kp = int(rng.choice([0, 0, 1, 2, 3, 8, 16, 24])), int(rng.choice([0, 0, 1]))
     rt.get_context().set_tuning(_lib.TUNE_GRAY, kg)
     rt.get_context().set_tuning(_lib.TUNE_PYRAMID, kp)
-    desc = "gray_pass h=%d w=%d scale=%.3f n=%d K=%d B=%d knobs=%s/%s" % (h, w, scale, n, K, B, kg, kp)
+    k, wdesc = draw_weights(rng, k, gray=True)
+    desc = "gray_pass h=%d w=%d scale=%.3f n=%d K=%d B=%d knobs=%s/%s" % (h, w, scale, n, K, B, kg, kp) + wdesc
     try:
         levels = classic_levels((h, w), scale, n)
     except ValueError:
@@ -93,7 +115,8 @@ def case_rgb(rng, k):
     if rng.integers(0, 6) == 0:
         w = int(rng.choice([111, 112, 113, 223, 224, 225, 336, 337, 449])) + int(rng.integers(-1, 2))
     rt.get_context().set_tuning(_lib.TUNE_RGB, kr)
-    desc = "rgb h=%d w=%d scale=%.3f n=%d B=%d knob=%s" % (h, w, scale, n, B, kr)
+    k, wdesc = draw_weights(rng, k)
+    desc = "rgb h=%d w=%d scale=%.3f n=%d B=%d knob=%s" % (h, w, scale, n, B, kr) + wdesc
     try:
         levels = classic_levels((h, w), scale, n)
     except ValueError:
@@ -220,7 +243,8 @@ def case_big(rng, k):
     n = int(rng.integers(2, 8))
     gray = bool(rng.integers(0, 2))
     B = int(rng.integers(1, 3)) if gray else int(rng.integers(1, 5))
-    desc = "big %s h=%d w=%d scale=%.3f n=%d B=%d" % ("gray" if gray else "rgb", h, w, scale, n, B)
+    k, wdesc = draw_weights(rng, k, gray=gray)
+    desc = "big %s h=%d w=%d scale=%.3f n=%d B=%d" % ("gray" if gray else "rgb", h, w, scale, n, B) + wdesc
     try:
         levels = classic_levels((h, w), scale, n)
     except ValueError:
@@ -268,7 +292,8 @@ def case_rgb_keypoints(rng, k):
     policy = "zero" if rng.integers(0, 2) else "ieee"
     vm = bool(rng.integers(0, 2))
     p = float(rng.choice([0.0, 0.1, 0.1, 0.37, 1.0]))
-    desc = "rgb_keypoints h=%d w=%d n=%d B=%d knob=%d %s value_map=%s p=%g" % (h, w, n, B, kr, policy, vm, p)
+    k, wdesc = draw_weights(rng, k)
+    desc = "rgb_keypoints h=%d w=%d n=%d B=%d knob=%d %s value_map=%s p=%g" % (h, w, n, B, kr, policy, vm, p) + wdesc
     try:
         consts = {x: k[x] for x in ("rgc", "rgby", "stripe", "blur", "end")}
         kw = dict(mode="rgb", n_levels=n, batch=B, selection=True, top_percent=p, flat_policy=policy, constants=consts,

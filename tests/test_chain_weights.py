@@ -1,0 +1,428 @@
+"""CPU side of the class-generic weights (tests/chain_weights.py): each builder is detected as the kernel form it is meant for,
+has none of the reference's symmetries beyond those its class forces, makes the oracle SENSITIVE to every index mix-up a fused
+kernel could make (so that a kernel with that bug cannot pass tests/test_gpu_chain_weights.py), and leaves the project's
+tolerance ATTAINABLE by an independent float32 evaluation (torch's convolutions) on the frames and parameters of the GPU tests.
+
+Why this file exists: on the reference's own weights the same mix-ups change nothing (last test)."""
+import numpy as np
+import pytest
+
+import chain_weights as cw
+import err_bound as eb
+import silent_oracle as so
+from conftest import assert_close
+
+RGB = sorted(cw.RGB_BUILDERS)
+POLICIES = ("zero", "ieee")
+
+
+def _lib_or_skip():
+    """Skips only when the shared library has not been built; a library that is there and does not load is a failure."""
+    import os
+    from pysilent_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libsilent_hip.so is not built (%s)" % _lib.LIB_PATH)
+    return _lib.load()
+
+
+# ----------------------------------------------------------------------------- variant selection
+
+def _take_conv(it, pairs):          # for o: for active (dx, i): for dy = 2, 1, 0   ->  K[dy, dx, i, o]
+    k = np.zeros((3, 3, 3, 3), np.float32)
+    for o in range(3):
+        for dx in range(3):
+            for i in range(3):
+                if pairs >> (o * 3 + i) & 1:
+                    for dy in (2, 1, 0):
+                        k[dy, dx, i, o] = next(it)
+    return k
+
+
+def _take_two(it, masks):           # for (dx, i): for dy = 2, 1, 0 (scale); then for term (group, i): for o (mix)
+    scale = np.zeros((3, 3, 3), np.float32)
+    for dx in range(3):
+        for i in range(3):
+            for dy in (2, 1, 0):
+                scale[dy, dx, i] = next(it)
+    mix = np.array([next(it) for _ in range(18)], np.float32).reshape(2, 3, 3)     # [group][i][o]
+    k = np.zeros((3, 3, 3, 3), np.float64)
+    for dy in range(3):
+        for dx in range(3):
+            for i in range(3):
+                grp = 0 if masks[i] >> (dy * 3 + dx) & 1 else 1
+                k[dy, dx, i, :] = np.float64(scale[dy, dx, i]) * mix[grp, i, :]
+    return k
+
+
+def _take_sum(it):                  # for o: for dx: for dy = 2, 1, 0
+    k = np.zeros((3, 3, 3), np.float32)
+    for o in range(3):
+        for dx in range(3):
+            for dy in (2, 1, 0):
+                k[dy, dx, o] = next(it)
+    return k
+
+
+def _take_blur(it):                 # for dx: for k = 0..6 (pending row k takes kernel row 6 - k)
+    b = np.zeros((7, 7), np.float32)
+    for dx in range(7):
+        for k in range(7):
+            b[6 - k, dx] = next(it)
+    return b
+
+
+def _take_blur_folded(it):          # mirror-symmetric form: for j = min(dx, 6 - dx) = 0..3: for d = |dy| = 0..3
+    q = np.zeros((4, 4), np.float32)
+    for j in range(4):
+        for d in range(4):
+            q[d, j] = next(it)
+    b = np.zeros((7, 7), np.float32)
+    for dy in range(7):
+        for dx in range(7):
+            b[dy, dx] = q[abs(dy - 3), min(dx, 6 - dx)]
+    return b
+
+
+def _walk_stream(stream, n, variant, a, masks):
+    """Walks the weight stream the way the pair kernel consumes it (as test_rgb_weight_stream_is_the_kernels_consumption_order of
+    tests/test_host_logic.py does for the reference's kernels) and compares the kernels it rebuilds with the ones that went in."""
+    assert not np.isnan(stream).any() and not stream[n:].any()
+    it = iter(stream[:n])
+    eye = np.eye(3, dtype=np.float32)
+    if variant == 0:
+        for name in ("rgc", "rgby", "stripe"):
+            np.testing.assert_array_equal(_take_conv(it, 0x1ff), a[name])
+        np.testing.assert_array_equal(_take_blur(it), a["blur"][:, :, 0, 0])
+        np.testing.assert_array_equal(_take_conv(it, 0x1ff), a["end"])
+    elif variant == 1:
+        np.testing.assert_array_equal(_take_conv(it, 0x111), a["rgc"] * eye)
+        np.testing.assert_array_equal(_take_conv(it, 0x1ff), a["rgby"])
+        np.testing.assert_array_equal(_take_sum(it), a["stripe"][:, :, 0, :])
+        np.testing.assert_array_equal(_take_blur(it), a["blur"][:, :, 0, 0])
+        np.testing.assert_array_equal(_take_conv(it, 0x1ff), a["end"])
+    elif variant == 2:
+        np.testing.assert_array_equal(_take_conv(it, 0x111), a["rgc"] * eye)
+        np.testing.assert_allclose(_take_two(it, masks[:3]), a["rgby"], rtol=2e-6, atol=1e-9)
+        np.testing.assert_array_equal(_take_sum(it), a["stripe"][:, :, 0, :])
+        np.testing.assert_array_equal(_take_blur_folded(it), a["blur"][:, :, 0, 0])
+        np.testing.assert_allclose(_take_two(it, masks[3:]), a["end"], rtol=2e-6, atol=1e-9)
+    else:
+        q = np.array([next(it) for _ in range(12)], np.float32).reshape(4, 3)            # [corner, edge_v, edge_h, centre][channel]
+        rgc = np.zeros((3, 3, 3, 3), np.float32)
+        for c in range(3):
+            corner, edge_v, edge_h, centre = q[:, c]
+            rgc[:, :, c, c] = [[corner, edge_h, corner], [edge_v, centre, edge_v], [corner, edge_h, corner]]
+        np.testing.assert_array_equal(rgc, a["rgc"])
+        A = np.array([next(it) for _ in range(9)], np.float32).reshape(3, 3)             # [i][o]
+        prof = np.array([next(it) for _ in range(9)], np.float32).reshape(3, 3)          # [corner, edge_v, edge_h][o]
+        assert (prof == prof[:, :1]).all()
+        corner, edge_v, edge_h = prof[:, 0]
+        assert len({float(corner), float(edge_v), float(edge_h)}) == 3                   # the profile is not the reference's
+        S = np.array([[corner, edge_h, corner], [edge_v, 0, edge_v], [corner, edge_h, corner]], np.float64)
+        B = np.array([next(it) for _ in range(9)], np.float32).reshape(3, 3)
+        rgby = S[:, :, None, None] * A[None, None].astype(np.float64)
+        rgby[1, 1] += B
+        np.testing.assert_allclose(rgby, a["rgby"], rtol=2e-6, atol=1e-9)
+        assert next(it) == 0.0                                                            # the pair block starts on an even position
+        stripe = np.zeros((3, 3, 3), np.float32)                                          # [dy][dx][o]
+        for o in range(3):
+            blk = [next(it) for _ in range(16)]
+            for k, dy in enumerate((2, 1, 0)):
+                l, r, c = blk[2 * k], blk[2 * k + 1], blk[6 + k]
+                assert (blk[10 + 2 * k], blk[10 + 2 * k + 1]) == (r, l)
+                stripe[dy, :, o] = (l, c, r)
+            assert blk[9] == 0.0
+        np.testing.assert_array_equal(stripe, a["stripe"][:, :, 0, :])
+        np.testing.assert_array_equal(_take_blur_folded(it), a["blur"][:, :, 0, 0])
+        np.testing.assert_allclose(_take_two(it, masks[3:]), a["end"], rtol=2e-6, atol=1e-9)
+    assert next(it, None) is None
+
+
+@pytest.mark.parametrize("name", sorted(cw.RGB_VARIANTS))
+@pytest.mark.parametrize("seed", sorted(cw.FUZZ_SEEDS))
+def test_each_builder_is_detected_as_the_kernel_form_it_is_built_for(name, seed):
+    _lib_or_skip()
+    from test_host_logic import _chain_stream, _chain_structure
+    ks = cw.RGB_BUILDERS[name](seed)
+    stream, n, variant, a = _chain_stream(ks, 0)
+    assert (variant, n) == cw.RGB_VARIANTS[name]
+    flags, masks = _chain_structure(ks)
+    two = [cw.RGBY_MASK] * 3 + list(cw.END_MASKS)
+    swapped = [cw.RGBY_MASK] * 3 + [cw.END_MASKS[1], cw.END_MASKS[0], cw.END_MASKS[2]]
+    want = {"symmetric": (0b111111, two), "two_group": (0b001111, two), "basic_blur": (0b001111, two),
+            "basic_masks": (0b001111, swapped), "basic_dense": (0b000011, [0] * 6), "dense": (0, [0] * 6)}[name]
+    assert (flags, masks) == want
+    _walk_stream(stream, n, variant, a, masks)
+    # the knob ladder of the GPU test: each knob moves these weights one form down, and every form streams them back
+    if name == "symmetric":
+        for knob, var in ((64, 2), (2, 1), (1, 0)):
+            stream, n, variant, a = _chain_stream(ks, knob)
+            assert variant == var
+            _walk_stream(stream, n, variant, a, masks)
+
+
+def test_the_nonuniform_blur_is_not_channel_uniform():
+    b = cw.rgb_nonuniform_blur(cw.SEED)["blur"].astype(np.float32)
+    assert len(np.unique(b)) == b.size           # what rgb_chain_launch tests before it takes the staged path
+
+
+# ----------------------------------------------------------------------------- asymmetry
+
+# what a class forces: the transforms that leave a kernel of that class unchanged, and its number of distinct magnitudes
+FOLDED = {"flip_y", "flip_x", "rot180", "swap_io"}
+FORCED = {
+    "symmetric": dict(rgc=({"flip_y", "flip_x", "rot180", "swap_io"}, 12), rgby=({"flip_y", "flip_x", "rot180"}, 36), stripe=(set(), 27),
+                      blur=(FOLDED, 16), end=(set(), 81)),
+    "two_group": dict(rgc=({"swap_io"}, 27), rgby=(set(), 81), stripe=(set(), 27), blur=(FOLDED, 16), end=(set(), 81)),
+    "basic_blur": dict(rgc=({"swap_io"}, 27), rgby=(set(), 81), stripe=(set(), 27), blur=({"swap_io"}, 49), end=(set(), 81)),
+    "basic_masks": dict(rgc=({"swap_io"}, 27), rgby=(set(), 81), stripe=(set(), 27), blur=(FOLDED, 16), end=(set(), 81)),
+    "basic_dense": dict(rgc=({"swap_io"}, 27), rgby=(set(), 81), stripe=(set(), 27), blur=(FOLDED, 16), end=(set(), 81)),
+    "dense": dict(rgc=(set(), 81), rgby=(set(), 81), stripe=(set(), 81), blur=({"swap_io"}, 49), end=(set(), 81)),
+    "nonuniform_blur": dict(rgc=({"swap_io"}, 27), rgby=(set(), 81), stripe=(set(), 27), blur=(set(), 441), end=(set(), 81)),
+}
+TRANSFORMS = dict(transpose=cw.transpose, flip_y=cw.flip_y, flip_x=cw.flip_x, rot180=cw.rot180, swap_io=cw.swap_io)
+
+
+def _invariances(k):
+    k32 = np.asarray(k, np.float64).astype(np.float32)
+    return {n for n, f in TRANSFORMS.items() if (n != "swap_io" or k32.shape[2] == k32.shape[3]) and np.array_equal(f(k32), k32)}
+
+
+def _magnitudes(k):
+    k32 = np.abs(np.asarray(k, np.float64).astype(np.float32))
+    return len(np.unique(k32[k32 != 0]))
+
+
+@pytest.mark.parametrize("name", RGB)
+def test_rgb_builders_have_only_the_symmetries_their_class_forces(name):
+    ks = cw.rgb_weights(name)
+    for kname in cw.RGB_NAMES:
+        forced, n_mag = FORCED[name][kname]
+        assert _invariances(ks[kname]) == forced, (name, kname)
+        assert _magnitudes(ks[kname]) == n_mag, (name, kname)
+    if name == "symmetric":
+        b = ks["blur"][3:, :4, 0, 0]             # q[|dy|][min(dx, 6 - dx)]: not a function of the distance
+        assert not np.array_equal(b[:, ::-1][:4, :4].T, b[:, ::-1][:4, :4])
+        assert len({tuple(np.round(ks["rgc"][:, :, c, c].ravel(), 12)) for c in range(3)}) == 3
+        A, B = ks["rgby"][0, 0], ks["rgby"][1, 1]
+        assert (A != 0).all() and (B != 0).all() and not np.allclose(A, A.T) and not np.allclose(B, B.T)
+        for i in range(3):                       # A[i] not parallel to B[i]: the centre tap stays a group of its own
+            assert np.linalg.matrix_rank(np.stack([A[i], B[i]]), tol=1e-3 * np.abs(B).max()) == 2
+    if name == "dense":
+        assert all((np.asarray(ks[k]) != 0).all() for k in cw.RGB_NAMES)
+
+
+@pytest.mark.parametrize("K", [3, 4, 8])
+def test_gray_builders_have_no_symmetry(K):
+    from pysilent_amd.util.normalize import normalize_tensor_positive_negative    # noqa: F401  (what gray_cs normalises with)
+    cs, bank = cw.gray_cs(cw.SEED), cw.gray_bank(K, cw.SEED)
+    assert cs.shape == (3, 3, 1, 1) and bank.shape == (3, 3, 1, K)
+    assert _invariances(cs) == {"swap_io"} and _magnitudes(cs) == 9          # (C_in = C_out = 1: nothing to swap)
+    assert abs(cs[cs > 0].sum() - 1.0) < 1e-12 and abs(cs[cs < 0].sum() + 1.0) < 1e-12
+    assert _invariances(bank) == set() and _magnitudes(bank) == 9 * K
+    b32 = bank.astype(np.float32)
+    for a in range(K):                           # no channel is a transpose, flip or rotation of another (or of itself)
+        for b in range(K):
+            for n, f in TRANSFORMS.items():
+                if n != "swap_io":
+                    assert not np.array_equal(f(b32[..., a:a + 1]), b32[..., b:b + 1]), (a, b, n)
+
+
+# ----------------------------------------------------------------------------- sensitivity
+
+def _raises(got, want, **kw):
+    import conftest
+    try:
+        assert_close(got, want, 1e-5, what="sensitivity", **kw)
+    except AssertionError:
+        return True
+    finally:                         # an oracle-vs-oracle comparison has no place in the end-of-suite error summary
+        conftest.WORST_BOUND.pop("sensitivity", None)
+        conftest.WORST_REL.pop("sensitivity", None)
+    return False
+
+
+def _rgb_mutation_is_seen(x, ks, kname, mut, policy, params=cw.PARAM_SETS[0]):
+    """Would the GPU test's end-to-end assertions fail for a kernel that applies ``mut`` to kernel ``kname``?  (maps that raise)"""
+    rv, root, clip, pad = params
+    want = so.rgb_line_end_chain(x, ks, policy, root, rv, clip, pad)
+    bound = eb.rgb_chain(x, ks, want, policy, root, rv, pad)
+    bad = so.rgb_line_end_chain(x, dict(ks, **{kname: cw.MUTATIONS[mut](ks[kname])}), policy, root, rv, clip, pad)
+    seen = set()
+    for name, ref, scale in (("orient", "orient", None), ("line_end", "padded", clip), ("value", "value", clip)):
+        if _raises(bad[ref], want[ref], scale=scale, bound=bound[ref]):
+            seen.add(name)
+    return seen
+
+
+@pytest.mark.parametrize("name", RGB)
+def test_rgb_index_mixups_cannot_pass_on_generic_weights(name):
+    """Each mix-up that is not the identity inside the class must make the GPU test's assertions raise, on the frames it uses, on
+    orient or line_end (at least), under both flat policies."""
+    ks = cw.rgb_weights(name)
+    frames = {"rgc": cw.rgb_frames(cw.RGB_SHAPES[0]), "rgby": cw.rgb_frames(cw.RGB_SHAPES[0]),
+              "blur": cw.dim_frames()}           # (the blur taps reach a result only where the blurred sum is below 1)
+    n_checked = 0
+    for kname, muts in cw.MUTATIONS_OF.items():
+        if kname == "cs_gray":
+            continue
+        for mut in muts:
+            if mut in FORCED[name][kname][0] or (mut == "channel0" and name == "dense"):
+                continue                         # the identity inside this class (channel0: rgc is not diagonal in the dense class)
+            assert not np.array_equal(cw.MUTATIONS[mut](ks[kname]), ks[kname])
+            for policy in POLICIES:
+                seen = _rgb_mutation_is_seen(frames[kname], ks, kname, mut, policy)
+                assert seen & {"orient", "line_end"}, (name, kname, mut, policy, seen)
+            n_checked += 1
+    # every class sees the dy <-> dx mix-up of all three kernels; the classes without mirror symmetry see the flips as well
+    assert n_checked >= (4 if name == "symmetric" else 7), n_checked
+
+
+@pytest.mark.parametrize("K", [3, 4, 8])
+def test_gray_index_mixups_cannot_pass_on_generic_weights(K):
+    cs_k, bank = cw.gray_cs(cw.SEED), cw.gray_bank(K, cw.SEED)
+    for lev in cw.gray_levels(20 + K)[:3]:
+        want_cs, want_end = so.gray_line_end_pass([lev], cs_k, bank)[0]
+        e_cs, e_end = eb.gray_chain(lev, cs_k, bank, want_cs)
+        for mut in cw.MUTATIONS_OF["cs_gray"]:
+            bad_cs, bad_end = so.gray_line_end_pass([lev], cw.MUTATIONS[mut](cs_k), bank)[0]
+            assert _raises(bad_cs, want_cs, bound=e_cs), (mut, "cs")
+            assert _raises(bad_end, want_end, scale=255.0, bound=e_end), (mut, "end")
+        for mut in ("transpose", "flip_y", "flip_x"):       # the bank's own taps
+            _, bad_end = so.gray_line_end_pass([lev], cs_k, cw.MUTATIONS[mut](bank))[0]
+            assert _raises(bad_end, want_end, scale=255.0, bound=e_end), (mut, "bank")
+
+
+def test_the_same_mixups_are_invisible_on_the_reference_weights(kernels):
+    """Why this file exists: the reference's rgc / rgby / blur / cs_gray are unchanged by every one of these mix-ups, so the
+    oracle's maps are bit-identical and no test on those weights can see them."""
+    ks = {k: kernels[k] for k in cw.RGB_NAMES}
+    for kname in ("rgc", "rgby", "blur"):
+        x = cw.dim_frames() if kname == "blur" else cw.rgb_frames(cw.RGB_SHAPES[0])
+        want = so.rgb_line_end_chain(x, ks, "zero")
+        for mut in cw.MUTATIONS_OF[kname]:
+            bad = so.rgb_line_end_chain(x, dict(ks, **{kname: cw.MUTATIONS[mut](ks[kname])}), "zero")
+            for m in ("orient", "line_end", "padded", "value"):
+                np.testing.assert_array_equal(bad[m], want[m], err_msg="%s %s %s" % (kname, mut, m))
+            assert _rgb_mutation_is_seen(x, ks, kname, mut, "zero") == set()
+    lev = cw.gray_levels(24)[0]
+    want_cs, want_end = so.gray_line_end_pass([lev], kernels["cs_gray"], kernels["end4"])[0]
+    for mut in cw.MUTATIONS_OF["cs_gray"]:
+        bad_cs, bad_end = so.gray_line_end_pass([lev], cw.MUTATIONS[mut](kernels["cs_gray"]), kernels["end4"])[0]
+        np.testing.assert_array_equal(bad_cs, want_cs)
+        np.testing.assert_array_equal(bad_end, want_end)
+
+
+# ----------------------------------------------------------------------------- attainability
+
+def _chain32(x, ks, policy, rv, root, clip, pad):
+    """torch's float32 convolutions composed as the reference graph: a float32 evaluation in ANOTHER order than the HIP kernels'."""
+    import torch
+    F = torch.nn.functional
+
+    def conv(t, k):
+        kt = torch.from_numpy(np.asarray(k, np.float64).astype(np.float32)).permute(3, 2, 0, 1)
+        p = (kt.shape[-1] - 1) // 2
+        return F.conv2d(F.pad(t, (p, p, p, p)), kt)
+
+    t = torch.from_numpy(x).permute(0, 3, 1, 2)
+    stripe = torch.relu(conv(torch.relu(conv(torch.relu(conv(t, ks["rgc"])), ks["rgby"])), ks["stripe"]))
+    b = conv(stripe, ks["blur"])
+    o = stripe * (np.float32(rv) / torch.pow(torch.clamp(b, max=1.0), np.float32(root)))
+    if policy == "zero":
+        o = torch.where(stripe == 0, torch.zeros_like(o), o)
+    le = torch.clamp(torch.relu(conv(o, ks["end"])), max=clip)
+    m = torch.zeros_like(le)
+    h, w = le.shape[2:]
+    if pad == 0:
+        m[:] = 1.0
+    elif h > 2 * pad and w > 2 * pad:
+        m[:, :, pad:-pad, pad:-pad] = 1.0
+    le = le * m
+    g = dict(orient=o, line_end=le, value=le.sum(1, keepdim=True) * np.float32(1 / 3))
+    return {k: v.permute(0, 2, 3, 1).numpy() for k, v in g.items()}
+
+
+def _bounded_share(want, bound, name):
+    e = bound[name]
+    return float((np.isfinite(want[name]) & ~eb.unbounded(e)).mean())
+
+
+def _check_rgb_case(name, ks, x, policy, params, tag):
+    rv, root, clip, pad = params
+    want = so.rgb_line_end_chain(x, ks, policy, root, rv, clip, pad)
+    bound = eb.rgb_chain(x, ks, want, policy, root, rv, pad)
+    got = _chain32(x, ks, policy, rv, root, clip, pad)
+    cw.assert_rgb_chain_close(got, want, bound, clip, "float32 " + tag)
+    # stage isolation, as the GPU tests assert it: the line-end stage against the oracle continued from the evaluation's OWN orient
+    # map, judged on that map's own range (no scale=, as in test_rgb_chain)
+    import torch
+    o = np.ascontiguousarray(got["orient"])
+    kt = torch.from_numpy(np.asarray(ks["end"], np.float64).astype(np.float32)).permute(3, 2, 0, 1)
+    t = torch.nn.functional.pad(torch.from_numpy(o).permute(0, 3, 1, 2), (1, 1, 1, 1))
+    le32 = torch.clamp(torch.relu(torch.nn.functional.conv2d(t, kt)), max=clip).permute(0, 2, 3, 1).numpy()
+    p = [[0, 0], [pad, pad], [pad, pad], [0, 0]]
+    assert_close(so.pad_inwards(le32, p), so.pad_inwards(so.conv2d_same(o, ks["end"], relu=True, clip_hi=clip), p), 1e-5,
+                 what="line_end|own-orient float32 " + tag, bound=eb.pad(eb.conv(o, ks["end"]), pad))
+    # the bound must not be vacuous (the thresholds of test_oracle.py's torch test): finite on nearly all elements, on most of
+    # those behind the regulator under 'ieee'
+    if x.shape[1] * x.shape[2] >= 1000:          # (a share is a statistic of a map, not of the 3 or 285 numbers of a 1 x 1 / 19 x 5 level)
+        for m in ("rgc", "rgby", "stripe", "orient", "line_end", "padded", "value"):
+            floor = 0.5 if policy == "ieee" and m not in ("rgc", "rgby", "stripe") else 0.97
+            assert _bounded_share(want, bound, m) > floor, (tag, m, _bounded_share(want, bound, m))
+
+
+@pytest.mark.parametrize("seed", sorted(cw.FUZZ_SEEDS))
+@pytest.mark.parametrize("policy", POLICIES)
+@pytest.mark.parametrize("name", RGB)
+def test_float32_evaluation_meets_the_gpu_tests_assertions_rgb(name, policy, seed):
+    """At cw.SEED (what the GPU tests use) and at every other seed scripts/fuzz_gpu.py draws."""
+    pytest.importorskip("torch")
+    assert cw.SEED in cw.FUZZ_SEEDS
+    ks = cw.rgb_weights(name, seed)
+    for shape in cw.RGB_SHAPES:
+        _check_rgb_case(name, ks, cw.rgb_frames(shape), policy, cw.PARAM_SETS[0], "%s %s %dx%d" % (name, policy, shape[1], shape[2]))
+    _check_rgb_case(name, ks, cw.dim_frames(), policy, cw.PARAM_SETS[0], "%s %s dim" % (name, policy))
+    for params in cw.PARAM_SETS:
+        _check_rgb_case(name, ks, cw.param_frames(), policy, params, "%s %s %s" % (name, policy, params))
+
+
+@pytest.mark.parametrize("name", RGB)
+def test_the_bound_is_not_vacuous_on_the_other_frames_the_gpu_tests_bound(name):
+    """The cap on what the bound leaves out, on the remaining (builder, frame) pairs tests/test_gpu_chain_weights.py compares with an
+    end-to-end bound: the two large levels of the 16-byte-store pyramid, the packed levels of the staged test (that class only) and
+    level 1 of the fused-keypoints test's noise frame (the oracle's pyramid here; the GPU's differs from it by rounding).  Not
+    covered, because no end-to-end bound is used there: the plateau frames (three-zone rule), the NaN / inf frames (pattern +
+    range-relative) and every bit-exact comparison; the stage-isolation bound is built from the GPU's own orient map."""
+    ks = cw.rgb_weights(name)
+    cases = [("store level %d" % l, lev, "ieee") for l, lev in enumerate(cw.store_levels()[:2])]
+    cases.append(("pipeline level 1", so.classic_pyramid(cw.pipeline_frames()[0], 2.0, 4)[1], "ieee"))
+    if name == "nonuniform_blur":
+        cases += [("staged level %d %s" % (l, pol), lev, pol) for l, lev in enumerate(cw.staged_levels()) for pol in POLICIES]
+    for tag, x, policy in cases:
+        want = so.rgb_line_end_chain(x, ks, policy)
+        bound = eb.rgb_chain(x, ks, want, policy)
+        for m in ("rgc", "rgby", "stripe", "orient", "line_end", "padded", "value"):
+            floor = 0.5 if policy == "ieee" and m not in ("rgc", "rgby", "stripe") else 0.97
+            assert _bounded_share(want, bound, m) > floor, (name, tag, m, _bounded_share(want, bound, m))
+
+
+@pytest.mark.parametrize("K", [3, 4, 8])
+def test_float32_evaluation_meets_the_gpu_tests_assertions_gray(K):
+    torch = pytest.importorskip("torch")
+    F = torch.nn.functional
+    cs_k, bank = cw.gray_cs(cw.SEED), cw.gray_bank(K, cw.SEED)
+
+    def conv(t, k):
+        kt = torch.from_numpy(np.asarray(k, np.float64).astype(np.float32)).permute(3, 2, 0, 1)
+        return F.conv2d(F.pad(t, (1, 1, 1, 1)), kt)
+
+    for l, lev in enumerate(cw.gray_levels(20 + K)):
+        want_cs, want_end = so.gray_line_end_pass([lev], cs_k, bank)[0]
+        t = torch.from_numpy(lev).permute(0, 3, 1, 2)
+        g_cs = torch.relu(conv(t, cs_k))
+        g_end = torch.clamp(torch.relu(conv(g_cs, bank)), max=255.0)
+        cw.assert_gray_chain_close(g_cs.permute(0, 2, 3, 1).numpy(), g_end.permute(0, 2, 3, 1).numpy(), lev, want_cs, want_end, cs_k, bank,
+                                   "float32 K=%d level %d" % (K, l))
+        e_cs, e_end = eb.gray_chain(lev, cs_k, bank, want_cs)
+        assert not eb.unbounded(e_cs).any() and not eb.unbounded(e_end).any()
