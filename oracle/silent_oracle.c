@@ -275,6 +275,8 @@ static void axis_table(int n_in, int n_out, int* idx, double* wts) {
     }
 }
 
+static int dead6(const double* w) { return w[0] == 0.0 && w[1] == 0.0 && w[2] == 0.0 && w[3] == 0.0 && w[4] == 0.0 && w[5] == 0.0; }
+
 /* One level of the zoom pyramid: crop [y0,y0+ch) x [x0,x0+cw) of an H x W x C frame, resampled by the
  * un-prefiltered quintic B-spline to zh x zw, copied into the top-left of an oh x ow canvas (rest 0). */
 SO_API void so_zoom_level(const float* frame, int H, int W, int C, int y0, int x0, int ch, int cw, int zh,
@@ -289,8 +291,10 @@ SO_API void so_zoom_level(const float* frame, int H, int W, int C, int y0, int x
     const int ym = zh < oh ? zh : oh, xm = zw < ow ? zw : ow;
     memset(out, 0, sizeof(float) * (size_t)oh * ow * C);
 #pragma omp parallel for schedule(static)
-    for (int oy = 0; oy < ym; ++oy)
-        for (int ox = 0; ox < xm; ++ox)
+    for (int oy = 0; oy < ym; ++oy) {
+        if (dead6(wy + 6 * oy)) continue; /* out of bounds: scipy emits cval WITHOUT reading a pixel (a NaN under it stays out) */
+        for (int ox = 0; ox < xm; ++ox) {
+            if (dead6(wx + 6 * ox)) continue;
             for (int c = 0; c < C; ++c) {
                 double acc = 0.0;
                 for (int a = 0; a < 6; ++a) {
@@ -300,6 +304,8 @@ SO_API void so_zoom_level(const float* frame, int H, int W, int C, int y0, int x
                 }
                 out[((size_t)oy * ow + ox) * C + c] = (float)acc;
             }
+        }
+    }
     free(iy);
     free(wy);
 }

@@ -386,6 +386,9 @@ def spline5_zoom(plane, out_h, out_w):
         rows = p64[iy[:, a], :]
         for b in range(6):
             acc += (wy[:, a][:, None] * wx[:, b][None, :]) * rows[:, ix[:, b]]
+    # an out-of-bounds row / column is cval = 0 WITHOUT a pixel being read: a NaN / inf under it stays out (0 * NaN would not)
+    acc[~wy.any(axis=1), :] = 0.0
+    acc[:, ~wx.any(axis=1)] = 0.0
     return acc.astype(F32)
 
 

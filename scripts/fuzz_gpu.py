@@ -15,6 +15,10 @@ import silent_oracle as so
 from conftest import assert_close, assert_regulated_close, noise_frame, structured_frame
 from pysilent_amd import _lib, _runtime as rt
 from pysilent_amd.util.zoom.from_image import classic_levels
+try:
+    import plan_geometry as pg          # tests/plan_geometry.py: free-form level geometry
+except ImportError:                     # a tests/ directory from before that helper: the generators' levels only (main() says so)
+    pg = None
 
 RTOL = 1e-5
 
@@ -50,6 +54,41 @@ def draw_weights(rng, k, gray=False):
     return g, " weights=%s/%d" % (name, seed)
 
 
+def draw_levels(rng, h, w, c):
+    """In half of the cases free-form level geometry (tests/plan_geometry.py::random_levels: crops anywhere, unit levels anywhere and
+    any number, anisotropic / upsampled / degenerate axes, canvases around their zoom) instead of a generator's; None: the caller's own."""
+    if pg is None:
+        return None
+    return pg.random_levels(rng, (h, w), c) if rng.integers(0, 2) == 0 else None
+
+
+def free_form(rng, desc, h, w, c, levels, k=None, K=4):
+    """A free-form plan against the per-level oracle (c_oracle.zoom_level) and, bit for bit, the unit + region kernels; single-channel
+    plans also through silent_gray_pass against silent_pyramid + silent_gray_line_end."""
+    import err_bound as eb
+    B = int(rng.integers(1, 4))
+    frames = np.stack([noise_frame(int(rng.integers(0, 1 << 30)), h, w, c) for _ in range(B)])
+    plan = rt.PyramidPlan(h, w, c, levels)           # (every draw is valid: a refusal is a failure)
+    desc += " free-form levels=%s" % (levels,)
+    got = plan.run(frames)
+    rt.get_context().set_tuning(_lib.TUNE_PYRAMID, 2)
+    two = plan.run(frames)
+    rt.get_context().set_tuning(_lib.TUNE_PYRAMID, 0)
+    np.testing.assert_array_equal(got.data, two.data, err_msg=desc)
+    f = int(rng.integers(0, B))
+    want = pg.oracle_pyramid(frames[f], levels)
+    for l, lev in enumerate(pg.split(np.asarray(got.data).reshape(B, -1)[f], levels, c)):
+        assert_close(lev, want[l], RTOL, scale=255.0, what=desc + " pyr %d" % l, bound=eb.zoom(want[l]))
+    if c == 1 and k is not None:
+        pyr, cs, end = plan.gray_pass(frames, k["cs_gray"], k["end%d" % K])
+        cs2, end2 = rt.gray_line_end(got, k["cs_gray"], k["end%d" % K])
+        np.testing.assert_array_equal(pyr.data, got.data, err_msg=desc)
+        np.testing.assert_array_equal(cs.data, cs2.data, err_msg=desc)
+        np.testing.assert_array_equal(end.data, end2.data, err_msg=desc)
+    n_plans, px = plan.walk_plans
+    return desc + (" [stream]" if plan.streamable else " [walk %d x %d]" % (n_plans, px) if n_plans else " [region]")
+
+
 def frame(rng, h, w, c):
     seed = int(rng.integers(0, 1 << 30))
     kind = rng.integers(0, 3)
@@ -77,6 +116,9 @@ def case_gray_pass(rng, k):
     rt.get_context().set_tuning(_lib.TUNE_PYRAMID, kp)
     k, wdesc = draw_weights(rng, k, gray=True)
     desc = "gray_pass h=%d w=%d scale=%.3f n=%d K=%d B=%d knobs=%s/%s" % (h, w, scale, n, K, B, kg, kp) + wdesc
+    free = draw_levels(rng, h, w, 1)
+    if free is not None:
+        return free_form(rng, desc, h, w, 1, free, k, K)
     try:
         levels = classic_levels((h, w), scale, n)
     except ValueError:
@@ -117,6 +159,9 @@ def case_rgb(rng, k):
     rt.get_context().set_tuning(_lib.TUNE_RGB, kr)
     k, wdesc = draw_weights(rng, k)
     desc = "rgb h=%d w=%d scale=%.3f n=%d B=%d knob=%s" % (h, w, scale, n, B, kr) + wdesc
+    free = draw_levels(rng, h, w, 3)
+    if free is not None:
+        return free_form(rng, desc, h, w, 3, free)
     try:
         levels = classic_levels((h, w), scale, n)
     except ValueError:
@@ -379,6 +424,9 @@ def case_crop_walk(rng, k):
     h, w = int(rng.integers(40, 400)), int(rng.integers(10, 160)) * 4 + (int(rng.integers(0, 4)) if rng.integers(0, 2) else 0)   # any width
     scale = float(rng.choice([1.2, 2 ** (1 / 3), 1.3, 2 ** .5, 1.5, 1.6, math.e ** .5, 1.7, 2.0, 2.5]))
     B = int(rng.integers(1, 4))
+    free = draw_levels(rng, h, w, 3)
+    if free is not None:
+        return free_form(rng, "crop_walk h=%d w=%d" % (h, w), h, w, 3, free)
     if rng.integers(0, 3) == 0:
         n = int(rng.integers(2, 10))
         desc = "crop_walk classic h=%d w=%d scale=%.3f n=%d B=%d" % (h, w, scale, n, B)
@@ -425,6 +473,8 @@ def main():
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else int(time.time())
     only = os.environ.get("FUZZ_ONLY")
     k = make_kernels()
+    if pg is None:
+        print("tests/plan_geometry.py not found: no free-form levels, the generators' geometry only")
     rng = np.random.default_rng(seed)
     t0, n, fails = time.time(), 0, 0
     tally = {}

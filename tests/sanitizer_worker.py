@@ -16,7 +16,11 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import numpy as np  # noqa: E402
+
+import plan_geometry as pg  # noqa: E402
 
 from pysilent_amd import _lib, _runtime as rt  # noqa: E402
 from pysilent_amd import constant_convolutions as cc  # noqa: E402
@@ -48,8 +52,35 @@ def packed(ext, c, n_frames):
     return rt.PackedPyramid(rng.random(n_frames * px * c, dtype=np.float32) * 255.0, ext, c, n_frames)
 
 
+def run_plan_levels(h, w, c, levels):
+    plan = rt.PyramidPlan(h, w, c, levels, 0)
+    stats["plans"] += 1
+    _ = plan.streamable, plan.walk_plans
+    frames = rng.random((int(rng.integers(1, 3)), h, w, c), dtype=np.float32)
+    plan.run(frames)
+    if c == 1:
+        K = int(rng.choice([3, 4, 8]))
+        plan.gray_pass(frames, GRAY["cs"], cc.end_bank(K).astype(np.float32))
+    plan.close()
+
+
+def named_plans():
+    """Every case of tests/plan_geometry.py once, 1 and 3 channels: geometry the two generators below never produce.  All of them
+    are valid: a refusal is a failure here."""
+    for name, case in pg.CASES.items():
+        for c in (1, 3):
+            run_plan_levels(case["frame"][0], case["frame"][1], c, case["levels"])
+
+
 def one_plan():
     h, w, c = int(rng.integers(8, 160)), int(rng.integers(8, 200)), int(rng.choice([1, 3]))
+    if rng.random() < 0.5:
+        # free-form levels: crops anywhere, unit levels anywhere and any number, anisotropic / upsampled / degenerate axes
+        levels = pg.random_levels(rng, (h, w), c)
+        try:
+            return run_plan_levels(h, w, c, levels)
+        except ValueError as e:                 # (the loop below counts a ValueError as a geometry that said it is unsupported)
+            raise AssertionError("valid levels were refused: %s (%d x %d x %d, %s)" % (e, h, w, c, levels))
     if rng.random() < 0.5:
         # (ratios below e ** .5: the stream kernels' dense slot layout, the walk's 28 / 24-pixel tiles; up to 10 levels: ladders the
         # single-read paths refuse)
@@ -64,15 +95,7 @@ def one_plan():
         if w < 8:
             return
         levels = classic_levels((h, w), 2.0, int(rng.integers(1, 6)))
-    plan = rt.PyramidPlan(h, w, c, levels, 0)
-    stats["plans"] += 1
-    _ = plan.streamable, plan.walk_plans
-    frames = rng.random((int(rng.integers(1, 3)), h, w, c), dtype=np.float32)
-    plan.run(frames)
-    if c == 1:
-        K = int(rng.choice([3, 4, 8]))
-        plan.gray_pass(frames, GRAY["cs"], cc.end_bank(K).astype(np.float32))
-    plan.close()
+    run_plan_levels(h, w, c, levels)
 
 
 def one_op():
@@ -362,6 +385,7 @@ t0 = time.time()
 bad_arguments()
 exception_barrier()
 plan_eligibility()
+named_plans()
 while time.time() - t0 < budget:
     try:
         r = rng.random()
