@@ -206,6 +206,26 @@ int silent_gray_pass_h_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, con
                            const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
                            uint16_t* cs_out, uint16_t* end_out, unsigned parts, silent_stream stream);
 
+/* uint8 frames, read as they are.  Every real source of frames delivers uint8 (a camera, a decoder; the reference widens with
+ * np.asarray(frame, float32), recognition_testing.py:141); these entry points take them without a widening cast and without a
+ * float32 copy of the batch.  frames: [n_frames, H, W] bytes (one channel), NO alignment requirement.  The frame-reading kernels
+ * load the byte and convert it in a register -- uint8 -> float32 is exact -- so every output is IDENTICAL, bit for bit, to that of
+ * the float32-frame entry point given (float)frames[i]: silent_pyramid[_dev], silent_gray_pass_parts_dev (maps_f16 = 0),
+ * silent_gray_pass_h_dev (maps_f16 = 1: cs_out / end_out are binary16 maps with silent_gray_pass_h's alignment rules) and
+ * silent_gray_keypoints[_dev].  parts as silent_gray_pass_parts_dev.  The host-pointer forms stage H * W * n_frames BYTES of frames.
+ * Status codes as silent_gray_pass_h: SILENT_E_INVALID for a NULL plan / frames / pyr, both outputs NULL, n_frames < 1, parts = 0,
+ * a plan of another context; SILENT_E_UNSUPPORTED for a 3-channel plan, a SILENT_PLAN_ACCUM_F64 plan, n_orient other than 3, 4, 8.
+ * (Not a plan flag: one plan serves both kinds of frames.  ABI additions only: SILENT_ABI_VERSION is unchanged.) */
+int silent_pyramid_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, float* pyr);
+int silent_pyramid_u8_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, float* pyr,
+                          silent_stream stream);
+int silent_gray_pass_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
+                        void* end_out, int maps_f16);
+int silent_gray_pass_u8_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                            const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
+                            void* end_out, int maps_f16, unsigned parts, silent_stream stream);
+
 /* 1 when silent_gray_pass runs this plan through the single-read stream kernel (one unit-zoom level and every
  * other level resampling the same crop with a step > 1.25: classic whole-frame pyramids), 0 when it falls
  * back to region + unit-fused + filter kernels (e.g. the reference's centred-crop layout).  The same for
@@ -494,6 +514,17 @@ int silent_gray_keypoints_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, 
                               float* cs_out, float* end_out, int pad, int selection, double top_percent,
                               const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
                               size_t cap_per_frame, int64_t* counts, silent_stream stream);
+
+/* The same on uint8 frames (see silent_gray_pass_u8): every output is that of silent_gray_keypoints[_dev] given (float)frames[i]. */
+int silent_gray_keypoints_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                             const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out,
+                             float* end_out, int pad, int selection, double top_percent, const silent_extent* regions,
+                             float* value_out, float* peak_value_out, int64_t* idx, size_t cap_per_frame, int64_t* counts);
+int silent_gray_keypoints_u8_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                 const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                 float* cs_out, float* end_out, int pad, int selection, double top_percent,
+                                 const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+                                 size_t cap_per_frame, int64_t* counts, silent_stream stream);
 
 /* What the sparse tail of the LAST silent_rgb_keypoints[_dev] / silent_gray_keypoints[_dev] call of this context did (synchronises that call's stream):
  * stats[0] = 1 if it ran sparse, [1] = (frame, level) pairs, [2] = pairs it handed to the dense kernels, [3] = candidate

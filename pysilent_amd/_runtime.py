@@ -242,8 +242,10 @@ class _Operand(object):
     """Normalised view of an input tensor: geometry + pointer + how to allocate results and which entry point to call.
     ``ctx``: the context to run on (default: the shared one of the tensor's device)."""
 
-    def __init__(self, x, channels=None, ctx=None):
+    def __init__(self, x, channels=None, ctx=None, frame_dtype="float32"):
         self.packed = isinstance(x, PackedPyramid)
+        if frame_dtype == "uint8":
+            _require_uint8(x)
         if self.packed:
             self.src = x
             buf = x.data
@@ -266,16 +268,19 @@ class _Operand(object):
             import torch
             if not buf.is_cuda:
                 raise TypeError("torch tensors must live on the GPU (use a numpy array for host data)")
-            buf = as_float32(buf)
+            if frame_dtype != "uint8":
+                buf = as_float32(buf)
             self.device = buf.device.index or 0
             self.stream = C.c_void_p(torch.cuda.current_stream(buf.device).cuda_stream)
             self.ptr = C.c_void_p(buf.data_ptr())
             self._torch_device = buf.device
         else:
-            buf = np.ascontiguousarray(buf, dtype=np.float32)
+            buf = np.ascontiguousarray(buf, dtype=np.uint8 if frame_dtype == "uint8" else np.float32)
             self.device = None
             self.stream = None
             self.ptr = C.c_void_p(buf.ctypes.data)
+        if frame_dtype == "uint8":
+            self.ptr = _lib.byte_ptr(self.ptr.value)
         self.buf = buf                                  # keep alive
         self.frame_px = sum(h * w for h, w in self.extents)
         self.levels = (_lib.Extent * len(self.extents))(*[_lib.Extent(h, w) for h, w in self.extents])
@@ -312,6 +317,20 @@ class _Operand(object):
 
     def geom(self):
         return (self.levels, self.n_levels, self.n_frames)
+
+
+def _require_uint8(x):
+    """frame_dtype="uint8": the frames are passed as they are, so they must BE uint8 -- an ndarray, or a contiguous GPU tensor."""
+    if isinstance(x, np.ndarray):
+        ok = x.dtype == np.uint8
+    elif is_torch_tensor(x):
+        import torch
+        ok = x.dtype == torch.uint8 and x.is_contiguous()
+    else:
+        raise TypeError(TYPE_ERROR_MESSAGE)
+    if not ok:
+        raise ValueError("frame_dtype='uint8' takes a uint8 ndarray or a contiguous uint8 GPU tensor (nothing is converted), got %s"
+                         % (x.dtype,))
 
 
 def _kernel_arg(k, c_in=None):
@@ -748,6 +767,24 @@ def check_storage(storage, mode="gray", accumulation="float32", keypoints=False)
     return storage
 
 
+FRAME_DTYPES = ("float32", "uint8")
+
+
+def check_frame_dtype(frame_dtype, mode="gray", accumulation="float32"):
+    """The frame_dtype argument of PyramidPlan.run / gray_pass / gray_keypoints and LineEndPipeline: "float32" (default: whatever
+    comes is widened to float32 first) or "uint8" (uint8 frames read as they are by the silent_*_u8 entry points -- no widening cast,
+    no float32 copy of the batch; bit-identical results).  The name is checked first; then the combinations uint8 frames do not
+    exist for: mode "rgb" and accumulation="float64"."""
+    if frame_dtype not in FRAME_DTYPES:
+        raise ValueError("frame_dtype must be 'float32' or 'uint8', got %r" % (frame_dtype,))
+    if frame_dtype == "uint8":
+        if mode != "gray":
+            raise ValueError("frame_dtype='uint8' is for mode 'gray' (the RGB kernels read float32 frames)")
+        if accumulation == "float64":
+            raise ValueError("frame_dtype='uint8' does not combine with accumulation='float64'")
+    return frame_dtype
+
+
 class PyramidPlan(object):
     """Tap tables of one (frame size, level geometry) on the device.  ``levels`` is a list of dicts / tuples
     (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w).  accumulation="float64" (single-channel plans): every op of
@@ -767,19 +804,22 @@ class PyramidPlan(object):
                                                                  C.byref(self.handle)))
         self.frame_px = sum(h * w for h, w in self.extents)
 
-    def _frames(self, frames):
-        """[n, H, W, C] frames of this plan (ndarray, or torch GPU tensor) as an operand on the plan's context."""
+    def _frames(self, frames, frame_dtype="float32"):
+        """[n, H, W, C] frames of this plan (ndarray, or torch GPU tensor) as an operand on the plan's context.  frame_dtype="uint8":
+        a uint8 ndarray or contiguous uint8 GPU tensor, passed as it is (anything else is a ValueError); "float32": widened."""
+        check_frame_dtype(frame_dtype, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
         if not (isinstance(frames, np.ndarray) or is_torch_tensor(frames)):
             raise TypeError(TYPE_ERROR_MESSAGE)
         if tuple(frames.shape[1:]) != self.frame_shape:
             raise ValueError("frames must be [n, %d, %d, %d], got %s" % (self.frame_shape + (tuple(frames.shape),)))
-        return _Operand(frames, ctx=self.ctx)
+        return _Operand(frames, ctx=self.ctx, frame_dtype=frame_dtype)
 
-    def run(self, frames):
-        """frames: [n, H, W, C] ndarray (host) or torch GPU tensor.  Returns a PackedPyramid."""
-        op, c = self._frames(frames), self.frame_shape[2]
+    def run(self, frames, frame_dtype="float32"):
+        """frames: [n, H, W, C] ndarray (host) or torch GPU tensor.  Returns a PackedPyramid.  frame_dtype="uint8" (single-channel
+        plans): uint8 frames read as they are (silent_pyramid_u8), the same pyramid bit for bit."""
+        op, c = self._frames(frames, frame_dtype), self.frame_shape[2]
         out, optr = op.empty(op.n_frames * self.frame_px * c)
-        op.call("pyramid", self.handle, op.ptr, op.n_frames, optr)
+        op.call("pyramid_u8" if frame_dtype == "uint8" else "pyramid", self.handle, op.ptr, op.n_frames, optr)
         return PackedPyramid(out, self.extents, c, op.n_frames)
 
     @property
@@ -801,11 +841,13 @@ class PyramidPlan(object):
         n = _lib.load().silent_pyramid_plan_walk_plans(self.handle, C.byref(px))
         return int(n), int(px.value)
 
-    def gray_pass(self, frames, cs_kernel, end_bank, clip_hi=255.0, storage="float32"):
+    def gray_pass(self, frames, cs_kernel, end_bank, clip_hi=255.0, storage="float32", frame_dtype="float32"):
         """Whole grayscale hot path (silent_gray_pass): frames [n,H,W,1] -> (pyramid, cs, end) PackedPyramids.
         Same results as run() + gray_line_end(), one pass less over level 0.  storage="float16" (silent_gray_pass_h): cs and end
-        are float16 maps -- each element the float32 result rounded to nearest even -- and the pyramid stays float32."""
+        are float16 maps -- each element the float32 result rounded to nearest even -- and the pyramid stays float32.
+        frame_dtype="uint8" (silent_gray_pass_u8): uint8 frames read as they are; the same maps bit for bit, either storage."""
         check_storage(storage, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
+        check_frame_dtype(frame_dtype, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
         if self.frame_shape[2] != 1:
             raise ValueError("gray_pass needs a single-channel plan")
         cs = _kernel_arg(cs_kernel, 1)
@@ -813,9 +855,16 @@ class PyramidPlan(object):
         if cs.shape != (3, 3, 1, 1) or eb.shape[:3] != (3, 3, 1):
             raise ValueError("gray_pass needs a [3,3,1,1] CS kernel and a [3,3,1,K] end bank")
         K = eb.shape[3]
-        op = self._frames(frames)
+        op = self._frames(frames, frame_dtype)
         n = op.n_frames
-        if storage == "float16":
+        if frame_dtype == "uint8":
+            dt = np.float16 if storage == "float16" else np.float32
+            pyr, pp = op.empty(n * self.frame_px)
+            (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch, dt) for ch in (1, K)]
+            args = (self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi), pp, cp, ep,
+                    1 if storage == "float16" else 0)
+            op.call("gray_pass_u8", *(args + ((3,) if op.dev else ())))
+        elif storage == "float16":
             pyr, pp = op.empty(n * self.frame_px)
             (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch, np.float16) for ch in (1, K)]
             args = (self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi), pp,
@@ -831,9 +880,11 @@ class PyramidPlan(object):
         return P(pyr, self.extents, 1, n), P(cso, self.extents, 1, n, dtype=dt), P(endo, self.extents, K, n, dtype=dt)
 
     def gray_keypoints(self, frames, cs_kernel, end_bank, clip_hi=255.0, pad=2, selection=True, top_percent=0.1, regions=None,
-                       cap_per_frame=None):
+                       cap_per_frame=None, frame_dtype="float32"):
         """silent_gray_keypoints (host form): gray_pass + pad_inwards -> value -> [top_value_points -> NMS -> value ->]
-        max_value_indices_region on the K-channel end map.  Returns (pyramid, cs, end, idx [n, cap, 4], counts [n])."""
+        max_value_indices_region on the K-channel end map.  Returns (pyramid, cs, end, idx [n, cap, 4], counts [n]).
+        frame_dtype="uint8" (silent_gray_keypoints_u8): uint8 frames read as they are, the same results."""
+        check_frame_dtype(frame_dtype, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
         if self.frame_shape[2] != 1:
             raise ValueError("gray_keypoints needs a single-channel plan")
         cs = _kernel_arg(cs_kernel, 1)
@@ -846,13 +897,13 @@ class PyramidPlan(object):
             raise ValueError("need one (rH, rW) region per level")
         reg = (_lib.Extent * len(regions))(*[_lib.Extent(int(rh), int(rw)) for rh, rw in regions])
         K = eb.shape[3]
-        op = self._frames(frames)
+        op = self._frames(frames, frame_dtype)
         n = op.n_frames
         cap = self.frame_px if cap_per_frame is None else int(cap_per_frame)
         (pyr, pp), (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch) for ch in (1, 1, K)]
         idx, iptr = op.empty((n, cap, 4), np.int64)
         counts, cptr = op.empty(n, np.int64)
-        op.call("gray_keypoints", self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi),
+        op.call("gray_keypoints_u8" if frame_dtype == "uint8" else "gray_keypoints", self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi),
                 pp, cp, ep, int(pad), int(selection), float(top_percent), reg, None, None, iptr, cap, cptr)
         P = PackedPyramid
         return P(pyr, self.extents, 1, n), P(cso, self.extents, 1, n), P(endo, self.extents, K, n), idx, counts

@@ -133,12 +133,23 @@ __device__ __forceinline__ double unit_taps6(float c0, float edge, const double 
     h = __builtin_fma(w[4], (double)r2, h);
     return __builtin_fma(w[5], (double)r3, h);
 }
+// Frame element type of the single-channel frame-reading kernels (their trailing template parameter FT): float, or unsigned char
+// for uint8 frames (the *_u8 entry points).  A byte enters the arithmetic as (float)byte at the load -- exact, so a uint8 kernel
+// stores the bits its float instantiation stores for the widened frame.  UNSIGNED: a char / signed char load would turn 128 .. 255
+// into negatives.  The FT = float instantiations are the code as it was (their machine code is unchanged).
+template <typename FT>
+constexpr bool kFrameBytes = std::is_same<FT, unsigned char>::value;
+template <typename FT>
+constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameBytes<FT>;
+
 // Stream row i of the column `col` (level coordinates, mirrored inside the crop like every tap; px_stride floats per pixel) in lane i: ONE load per tile
 // for the sixth taps of a wave's last smoothing lane; row i is read back with unit_edge(xcol, i).
-__device__ __forceinline__ float unit_edge_column(const float* __restrict__ src, long long row_stride, int col, int src_w, int src_x0,
+// FT: the frame element type (float, or unsigned char: uint8 frames, widened at the load -- exact).
+template <typename FT = float>
+__device__ __forceinline__ float unit_edge_column(const FT* __restrict__ src, long long row_stride, int col, int src_w, int src_x0,
                                                   int y_first, int n_rows, int src_h, int src_y0, int lane, int px_stride = 1) {
     const long long sx = (long long)(mirror_near(col, src_w) + src_x0) * px_stride;
-    return src[(long long)(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0) * row_stride + sx];
+    return (float)src[(long long)(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0) * row_stride + sx];
 }
 __device__ __forceinline__ float unit_edge(float xcol, int i) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xcol), i));

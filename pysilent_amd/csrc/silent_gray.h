@@ -420,12 +420,13 @@ struct FusedTab64 : FusedTab {
 template <bool F64>
 using FusedTabT = typename std::conditional<F64, FusedTab64, FusedTab>::type;
 
-template <int K, int R, bool KP = false, bool F64 = false, typename ST = float>
-__global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const float* __restrict__ frames,
+template <int K, int R, bool KP = false, bool F64 = false, typename ST = float, typename FT = float>
+__global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const FT* __restrict__ frames,
                                                               float* __restrict__ pyr, ST* __restrict__ cs_out,
                                                               ST* __restrict__ end_out, const FusedTabT<F64> tab,
                                                               const GrayW wts, float clip_hi, const GrayKp kp = GrayKp{}) {
     static_assert(!kStoreHalf<ST> || (!KP && !F64), "float16 storage: no keypoint epilogue, no float64 accumulation");
+    static_assert(kFrameType<FT> && (!kFrameBytes<FT> || !F64), "uint8 frames: float32 accumulation only");
     __shared__ __attribute__((aligned(16))) float s_slab[K == 8 && !kStoreHalf<ST> ? kFusedWaves * 512 : 4];  // K = 8 store transpose, per wave
     const unsigned bid = blockIdx.x;
     const int frame = (int)(bid / (unsigned)tab.tiles_per_frame);
@@ -445,7 +446,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
     const int y0 = ty * R;
     const int ox = xw0 + lane - 4;
     const int W = tab.W;
-    const float* __restrict__ src = frames + (long long)frame * tab.H * W;
+    const FT* __restrict__ src = frames + (long long)frame * tab.H * W;
     const long long base_px = (long long)frame * tab.frame_px + lv.px_off;
 
     // scipy 'mirror' inside the crop, then the crop's offset in the frame
@@ -453,7 +454,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
     float in[R + 9];                                                  // stream rows y0 - 4 .. y0 + R + 4 (the sixth tap: + 1 row)
 #pragma unroll
     for (int i = 0; i < R + 9; ++i)
-        in[i] = src[(long long)(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0) * W + sx];
+        in[i] = (float)src[(long long)(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0) * W + sx];
     float xcol = unit_edge_column(src, W, xw0 + 60, lv.src_w, lv.src_x0, y0 - 4, R + 9, lv.src_h, lv.src_y0, lane);
 #pragma unroll
     for (int i = 0; i < R + 9; ++i) asm volatile("" ::"v"(in[i]));  // retire loads before the first store
@@ -721,13 +722,14 @@ __device__ __forceinline__ void stream_level_f64(int g, const int (&cur)[PR], fl
 #endif
 constexpr int kStreamRegLevels = SILENT_STREAM_REG_LEVELS;
 
-template <int K, int G, int L = 0, bool KP = false, bool F64 = false, typename ST = float>
-__global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const float* __restrict__ frames, float* __restrict__ pyr,
+template <int K, int G, int L = 0, bool KP = false, bool F64 = false, typename ST = float, typename FT = float>
+__global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const FT* __restrict__ frames, float* __restrict__ pyr,
                                                           ST* __restrict__ cs_out, ST* __restrict__ end_out,
                                                           const FusedTabT<F64> tab, const StreamTab st, const GrayW wts,
                                                           float clip_hi, unsigned opts, const GrayKp kp = GrayKp{}) {
     constexpr int R = kFusedTH, NR = kStreamRows;
     static_assert(!kStoreHalf<ST> || (!KP && !F64), "float16 storage: no keypoint epilogue, no float64 accumulation");
+    static_assert(kFrameType<FT> && (!kFrameBytes<FT> || !F64), "uint8 frames: float32 accumulation only");
     __shared__ __attribute__((aligned(16))) float s_slab[K == 8 && !kStoreHalf<ST> ? kFusedWaves * 512 : 4];
     __shared__ __attribute__((aligned(16))) float s_rows[kFusedWaves][NR][64];  // the streamed rows of each wave (wave private)
     const unsigned bid = (opts & 1u) ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x;
@@ -744,7 +746,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
     const int y0 = ty * R;
     const int ox = xw0 + lane - 4;
     const int W = tab.W;
-    const float* __restrict__ src = frames + (long long)frame * tab.H * W;
+    const FT* __restrict__ src = frames + (long long)frame * tab.H * W;
     const long long frame_px0 = (long long)frame * tab.frame_px;
     const long long base_px = frame_px0 + lv.px_off;
 
@@ -765,8 +767,8 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
     if (live) {
 #pragma unroll
         for (int i = 0; i < R + 8; ++i)
-            in[i] = src[(long long)(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0) * W + sx];
-        in_last = src[(long long)(mirror_near(y0 + R + 4, lv.src_h) + lv.src_y0) * W + sx];
+            in[i] = (float)src[(long long)(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0) * W + sx];
+        in_last = (float)src[(long long)(mirror_near(y0 + R + 4, lv.src_h) + lv.src_y0) * W + sx];
         xcol = unit_edge_column(src, W, xw0 + 60, lv.src_w, lv.src_x0, y0 - 4, R + 9, lv.src_h, lv.src_y0, lane);
 #pragma unroll
         for (int g = 0; g < GR; ++g) col[g] = stream_col_t<F64>(st, g, wx_tile, lane);
@@ -1016,9 +1018,10 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const flo
 // read and written at a stride of C floats.  Used for C = 1 only: two-step gray pyramids 0.58 -> 0.51 ms per 64 1080p
 // frames; with C = 3 the stride-3 loads and partial-line stores made it 1.5 ms against 1.0 ms for unit + region
 // kernels on 32 RGB frames (measured, bit-identical either way), so RGB plans are not marked streamable.
-template <int C, int G, int L = 0, bool F64 = false>
-__global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(const float* __restrict__ frames, float* __restrict__ pyr,
+template <int C, int G, int L = 0, bool F64 = false, typename FT = float>
+__global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(const FT* __restrict__ frames, float* __restrict__ pyr,
                                                              const FusedTabT<F64> tab, const StreamTab st) {
+    static_assert(kFrameType<FT> && (!kFrameBytes<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
     constexpr int R = kFusedTH, NR = kStreamRows;
     __shared__ float s_rows[kFusedWaves][NR][64];
     const unsigned bid = blockIdx.x;
@@ -1034,7 +1037,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(const 
     const int y0 = ty * R;
     const int ox = xw0 + lane - 4;
     const long long WC = (long long)tab.W * C;
-    const float* __restrict__ src = frames + (long long)frame * tab.H * WC;
+    const FT* __restrict__ src = frames + (long long)frame * tab.H * WC;
     const long long frame_px0 = (long long)frame * tab.frame_px;
     const long long base_px = frame_px0 + lv.px_off;
     const long long sx = (long long)(mirror_near(ox, lv.src_w) + lv.src_x0) * C;
@@ -1056,7 +1059,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(const 
         float in[R + 8];
 #pragma unroll
         for (int i = 0; i < R + 8; ++i)
-            in[i] = src[(long long)(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0) * WC + sx + ch];
+            in[i] = (float)src[(long long)(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0) * WC + sx + ch];
 #pragma unroll
         for (int i = 0; i < R + 8; ++i) asm volatile("" ::"v"(in[i]));  // retire loads before the first store
 #pragma unroll

@@ -70,45 +70,51 @@ SILENT_EXPORT int silent_gray_line_end_dev(silent_ctx* ctx, const float* pyr, co
     return on_exception(ctx, "silent_gray_line_end_dev");
 }
 
-template <int K, int G, int L, bool F64, typename ST>
-static void launch_stream(long long blocks, hipStream_t s, const float* frames, float* pyr, ST* cs_out, ST* end_out,
+// FT: the frame element type -- float, or unsigned char (uint8 frames: the *_u8 entry points).  The uint8 kernels exist with float32
+// accumulation only (F64 plans are refused before a launch), with and without keypoint epilogue, for both map storages.
+template <int K, int G, int L, bool F64, typename ST, typename FT>
+static void launch_stream(long long blocks, hipStream_t s, const FT* frames, float* pyr, ST* cs_out, ST* end_out,
                           const FusedTab64& ft, const StreamTab& st, const GrayW& w, float clip_hi, unsigned opts, const GrayKp* kp) {
     const FusedTabT<F64>& t = ft;
     if constexpr (kStoreHalf<ST>)
-        hipLaunchKernelGGL((gray_stream_kernel<K, G, L, false, false, ST>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames,
+        hipLaunchKernelGGL((gray_stream_kernel<K, G, L, false, false, ST, FT>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames,
                            pyr, cs_out, end_out, t, st, w, clip_hi, opts);
     else if (kp)
-        hipLaunchKernelGGL((gray_stream_kernel<K, G, L, true, F64>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr,
+        hipLaunchKernelGGL((gray_stream_kernel<K, G, L, true, F64, ST, FT>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr,
                            cs_out, end_out, t, st, w, clip_hi, opts, *kp);
     else
-        hipLaunchKernelGGL((gray_stream_kernel<K, G, L, false, F64>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr,
+        hipLaunchKernelGGL((gray_stream_kernel<K, G, L, false, F64, ST, FT>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr,
                            cs_out, end_out, t, st, w, clip_hi, opts);
 }
 
-template <int K, bool F64, typename ST>
-static void launch_fused(long long blocks, hipStream_t s, const float* frames, float* pyr, ST* cs_out, ST* end_out,
+template <int K, bool F64, typename ST, typename FT>
+static void launch_fused(long long blocks, hipStream_t s, const FT* frames, float* pyr, ST* cs_out, ST* end_out,
                          const FusedTab64& ft, const GrayW& w, float clip_hi, const GrayKp* kp) {
     const FusedTabT<F64>& t = ft;
     if constexpr (kStoreHalf<ST>)
-        hipLaunchKernelGGL((gray_unit_fused_kernel<K, kFusedTH, false, false, ST>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s,
+        hipLaunchKernelGGL((gray_unit_fused_kernel<K, kFusedTH, false, false, ST, FT>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s,
                            frames, pyr, cs_out, end_out, t, w, clip_hi);
     else if (kp)
-        hipLaunchKernelGGL((gray_unit_fused_kernel<K, kFusedTH, true, F64>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s,
+        hipLaunchKernelGGL((gray_unit_fused_kernel<K, kFusedTH, true, F64, ST, FT>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s,
                            frames, pyr, cs_out, end_out, t, w, clip_hi, *kp);
     else
-        hipLaunchKernelGGL((gray_unit_fused_kernel<K, kFusedTH, false, F64>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s,
+        hipLaunchKernelGGL((gray_unit_fused_kernel<K, kFusedTH, false, F64, ST, FT>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s,
                            frames, pyr, cs_out, end_out, t, w, clip_hi);
 }
 
 // parts: bit 0 = the pyramid of every level + CS / end of the unit levels (steps 1 and 2), bit 1 = CS + end of the remaining levels
 // (step 3, which reads the pyramid steps 1 and 2 wrote)
-template <typename ST>
-static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
+template <typename ST, typename FT>
+static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames,
                            const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
                            ST* cs_out, ST* end_out, unsigned parts, silent_stream stream, const GrayKp* kp = nullptr) {
-    const char* who = kStoreHalf<ST> ? "silent_gray_pass_h" : "silent_gray_pass";
+    const char* who = kFrameBytes<FT> ? (kp ? "silent_gray_keypoints_u8" : "silent_gray_pass_u8") : kStoreHalf<ST> ? "silent_gray_pass_h" : "silent_gray_pass";
     if (!plan || !frames || !pyr || !cs_kernel) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
+    if constexpr (kFrameBytes<FT>) {
+        if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
+        if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
+    }
     if constexpr (kStoreHalf<ST>) {
         if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": float16 storage is for single-channel plans");
         if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": float16 storage with a SILENT_PLAN_ACCUM_F64 plan");
@@ -126,7 +132,10 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
     // 1. non-unit levels of the pyramid: by the region kernel, unless the stream kernel of step 2 produces them
     //    from the same single read of the frame; plus the zero fill of canvases larger than their zoomed crop
     if (!(parts & 3u)) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": parts must name step 1 + 2 (bit 0) and / or step 3 (bit 1)");
-    if (parts & 1u) TRY(launch_pyramid(ctx, who, plan, frames, n_frames, pyr, s, false, !stream_path));
+    if (parts & 1u) {
+        if constexpr (kFrameBytes<FT>) TRY(launch_pyramid_u8(ctx, who, plan, frames, n_frames, pyr, s, false, !stream_path));
+        else TRY(launch_pyramid(ctx, who, plan, frames, n_frames, pyr, s, false, !stream_path));
+    }
     // 2. unit levels: pyramid + CS + end in one kernel
     const int fth = kFusedTH;
     FusedTab64 ft;   // (the float32 kernels take its FusedTab part)
@@ -174,9 +183,10 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
             const StreamTab& st = plan->stream;
             const unsigned sopts = (unsigned)((kopts >> 5) & 1);
 #define STREAM_LAUNCH(K_, G_, L_)                                                                                  \
-    if constexpr (kStoreHalf<ST>) launch_stream<K_, G_, L_, false, ST>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, nullptr); \
-    else if (plan->f64) launch_stream<K_, G_, L_, true, ST>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp); \
-    else launch_stream<K_, G_, L_, false, ST>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp)
+    if constexpr (kStoreHalf<ST>) launch_stream<K_, G_, L_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, nullptr); \
+    else if constexpr (kFrameBytes<FT>) launch_stream<K_, G_, L_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp); \
+    else if (plan->f64) launch_stream<K_, G_, L_, true, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp); \
+    else launch_stream<K_, G_, L_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp)
             if (plan->stream_layout == 1) {          // zoom ladders of ratio 1.4 .. e^.5: five rows of the first level in flight
                 if (n_orient == 3) { STREAM_LAUNCH(3, 7, 1); }
                 else if (n_orient == 4) { STREAM_LAUNCH(4, 7, 1); }
@@ -193,9 +203,10 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
 #undef STREAM_LAUNCH
         } else {
 #define FUSED_LAUNCH(K_)                                                                                   \
-    if constexpr (kStoreHalf<ST>) launch_fused<K_, false, ST>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, nullptr); \
-    else if (plan->f64) launch_fused<K_, true, ST>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp); \
-    else launch_fused<K_, false, ST>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp)
+    if constexpr (kStoreHalf<ST>) launch_fused<K_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, nullptr); \
+    else if constexpr (kFrameBytes<FT>) launch_fused<K_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp); \
+    else if (plan->f64) launch_fused<K_, true, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp); \
+    else launch_fused<K_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp)
             if (n_orient == 3) { FUSED_LAUNCH(3); }
             else if (n_orient == 4) { FUSED_LAUNCH(4); }
             else { FUSED_LAUNCH(8); }
@@ -219,6 +230,13 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
 int gray_pass_kp(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames, const float* cs_kernel,
                  const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const GrayKp& kp,
                  hipStream_t s) {
+    return gray_pass_parts(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, 3u,
+                           (silent_stream)s, &kp);
+}
+
+int gray_pass_kp_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, const float* cs_kernel,
+                    const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const GrayKp& kp,
+                    hipStream_t s) {
     return gray_pass_parts(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, 3u,
                            (silent_stream)s, &kp);
 }
@@ -315,4 +333,44 @@ SILENT_EXPORT int silent_gray_pass_h(silent_ctx* ctx, const silent_pyramid_plan*
     });
 } catch (...) {
     return on_exception(ctx, "silent_gray_pass_h");
+}
+
+// ------------------------------------------------------------------------------------------ uint8 frames
+// The same pass reading uint8 frames as they are (the FT = unsigned char instantiations of the frame-reading kernels; silent_hip.h
+// has the contract): the byte is widened in a register at the load, so every output is the float32-frame entry point's, bit for bit.
+
+SILENT_EXPORT int silent_gray_pass_u8_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                          const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                          void* cs_out, void* end_out, int maps_f16, unsigned parts, silent_stream stream) try {
+    NEED_CTX(ctx);
+    if (maps_f16)
+        return gray_pass_parts(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr,
+                               static_cast<gray_half*>(cs_out), static_cast<gray_half*>(end_out), parts, stream);
+    return gray_pass_parts(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, static_cast<float*>(cs_out),
+                           static_cast<float*>(end_out), parts, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_pass_u8_dev");
+}
+
+SILENT_EXPORT int silent_gray_pass_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                      const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                      void* cs_out, void* end_out, int maps_f16) try {
+    NEED_CTX(ctx);
+    if (!plan || !frames || !pyr) return fail(ctx, SILENT_E_INVALID, "silent_gray_pass_u8: NULL pointer");
+    if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_gray_pass_u8: uint8 frames are for single-channel plans");
+    if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_gray_pass_u8: uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
+    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, "silent_gray_pass_u8: n_frames must be >= 1");
+    if (n_orient != 3 && n_orient != 4 && n_orient != 8)
+        return fail(ctx, SILENT_E_UNSUPPORTED, "silent_gray_pass_u8: n_orient must be 3, 4 or 8");
+    HostStage hs(ctx);
+    const size_t px = (size_t)plan->tab.frame_px_out * n_frames, eb = maps_f16 ? 2 : 4;
+    // (the frames are bytes: H * W * n of them, not * 4)
+    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * n_frames), p = hs.out(pyr, px * 4), cs = hs.out(cs_out, px * eb),
+              end = hs.out(end_out, px * eb * n_orient);
+    return hs.run([&] {
+        return silent_gray_pass_u8_dev(ctx, plan, hs.dev<uint8_t>(x), n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
+                                       hs.dev<char>(cs), hs.dev<char>(end), maps_f16, 3u, nullptr);
+    });
+} catch (...) {
+    return on_exception(ctx, "silent_gray_pass_u8");
 }

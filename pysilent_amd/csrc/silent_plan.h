@@ -40,7 +40,13 @@ struct silent_pyramid_plan {
 // (silent_pyramid_api.hip) with_unit: also the unit levels (the gray pass produces them itself); with_region: also the general levels
 int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const float* frames, int n_frames, float* pyr,
                    hipStream_t s, bool with_unit, bool with_region = true);
+// the same on uint8 frames (single-channel plans without SILENT_PLAN_ACCUM_F64; anything else is refused)
+int launch_pyramid_u8(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, float* pyr,
+                      hipStream_t s, bool with_unit, bool with_region = true);
 // (silent_gray_api.hip) silent_gray_pass_dev with the keypoint epilogue (silent_gray.h, GrayKp) in every kernel that writes `end`
 int gray_pass_kp(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames, const float* cs_kernel,
                  const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const silent::GrayKp& kp,
                  hipStream_t s);
+int gray_pass_kp_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, const float* cs_kernel,
+                    const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const silent::GrayKp& kp,
+                    hipStream_t s);

@@ -93,9 +93,10 @@ __device__ __forceinline__ int mirror_index(int i, int n) {
 // its own column (all rows requested up front), DPP shifts for the neighbours x - 2 .. x + 3, 6 horizontal
 // FMAs, a 6-row register window, 6 vertical FMAs, one store (scipy's six taps at zoom 1: unit_taps6, silent_gray.h).
 // F64: the six taps of each axis summed in float64 with float64 weights (horizontal, then vertical), rounded once.
-template <int C, bool F64 = false>
-__global__ __launch_bounds__(256) void pyramid_unit_kernel(const float* __restrict__ frames,
+template <int C, bool F64 = false, typename FT = float>
+__global__ __launch_bounds__(256) void pyramid_unit_kernel(const FT* __restrict__ frames,
                                                            float* __restrict__ pyr, const PyrTabT<F64> tab) {
+    static_assert(kFrameType<FT> && (!kFrameBytes<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
     constexpr int R = kUnitTH;
     const unsigned bid = blockIdx.x;
     const int frame = (int)(bid / (unsigned)tab.unit_tiles_per_frame);
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(const float* __restri
     const int y0 = ty * R;
     const int ox = xw0 + lane - 2;
     const int W = tab.W;
-    const float* __restrict__ src = frames + (long long)frame * tab.H * W * C;
+    const FT* __restrict__ src = frames + (long long)frame * tab.H * W * C;
     float* __restrict__ dst = pyr + ((long long)frame * tab.frame_px_out + tab.px_off[l]) * C;
 
     acc_t<F64> wx[6], wy[6];
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(const float* __restri
     for (int i = 0; i < R + 5; ++i) {
         const long long sy = mirror_near(y0 - 2 + i, lv.src_h) + lv.src_y0;
 #pragma unroll
-        for (int ch = 0; ch < C; ++ch) in[i][ch] = src[sy * W * C + sx + ch];
+        for (int ch = 0; ch < C; ++ch) in[i][ch] = (float)src[sy * W * C + sx + ch];
     }
 #pragma unroll
     for (int ch = 0; ch < C; ++ch)
@@ -196,9 +197,14 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(const float* __restri
 // (staging loads, LDS round trips, barriers), so the LDS footprint is kept small: 25 KB (1 channel) / 22 KB
 // (3 channels) -> 6 / 7 blocks per CU that cover each other's waits.
 // F64: vertical sums in float64 (kept in LDS as float64), horizontal taps in float64, one rounding per output.
-template <int C, bool F64 = false>
-__global__ __launch_bounds__(256) void pyramid_region_kernel(const float* __restrict__ frames,
+// FT = unsigned char (uint8 frames): s_src stays float, the bytes are widened while staging.  The group path then loads 4 bytes
+// (one dword) per lane, which is legal only where the ADDRESS is 4-byte aligned -- and the uint8 frames pointer has no alignment
+// requirement: W % 4 == 0 puts every row start (frame * H * W + sy * W) and every group offset f on the dword grid relative to the
+// base, so the base address decides; any other base or width takes the one-element path.
+template <int C, bool F64 = false, typename FT = float>
+__global__ __launch_bounds__(256) void pyramid_region_kernel(const FT* __restrict__ frames,
                                                              float* __restrict__ pyr, const PyrTabT<F64> tab) {
+    static_assert(kFrameType<FT> && (!kFrameBytes<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
     constexpr int RW = region_w(C), SW = region_sw(C), SH = region_sh(C), ROWF = SW * C, VR = region_vr(C);
     __shared__ __attribute__((aligned(16))) float s_src[SH * ROWF];
     __shared__ __attribute__((aligned(16))) acc_t<F64> s_v[VR * ROWF];
@@ -214,7 +220,7 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(const float* __rest
     const int W = tab.W, H = tab.H;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const float* __restrict__ src = frames + (long long)frame * H * W * C;
+    const FT* __restrict__ src = frames + (long long)frame * H * W * C;
 
     // A region no level has an output in is not staged at all (crop layouts: the reference's nested centre crops leave about half
     // of a 1080p frame's regions outside the outermost crop -- round 5: those blocks used to load their region and find nothing
@@ -234,9 +240,11 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(const float* __rest
 
     // stage rows [Y0-3, Y0+RH+3) x columns [X0-4, X0+RW+4).  Taps are mirrored INTO the crop, so positions
     // outside the frame are never referenced: rows are clamped, out-of-frame column groups are skipped.
-    if (((W * C) & 3) == 0) {
+    bool groups = ((W * C) & 3) == 0;
+    if constexpr (kFrameBytes<FT>) groups = groups && (reinterpret_cast<unsigned long long>(frames) & 3ull) == 0;   // (block-uniform)
+    if (groups) {
         constexpr int V4 = ROWF / 4, NB = (SH * V4 + 255) / 256;
-        float4 v[NB];
+        typename std::conditional<kFrameBytes<FT>, uchar4, float4>::type v[NB];
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
             const int p = min(tid + 256 * k, SH * V4 - 1);
@@ -244,15 +252,20 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(const float* __rest
             const int sy = min(max(Y0 - kRegionHaloT + r, 0), H - 1);
             long long f = (long long)(X0 - kRegionHaloL) * C + q * 4;  // first float of this group in the row
             f = min(max(f, 0ll), (long long)W * C - 4);
-            v[k] = *reinterpret_cast<const float4*>(src + (long long)sy * W * C + f);
+            if constexpr (kFrameBytes<FT>) v[k] = *reinterpret_cast<const uchar4*>(src + (long long)sy * W * C + f);
+            else v[k] = *reinterpret_cast<const float4*>(src + (long long)sy * W * C + f);
         }
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
             const int p = tid + 256 * k;
             const int r = p / V4, q = p - r * V4;
             const long long f = (long long)(X0 - kRegionHaloL) * C + q * 4;
-            if (p < SH * V4 && f >= 0 && f + 4 <= (long long)W * C)
-                *reinterpret_cast<float4*>(s_src + r * ROWF + q * 4) = v[k];
+            if (p < SH * V4 && f >= 0 && f + 4 <= (long long)W * C) {
+                if constexpr (kFrameBytes<FT>)
+                    *reinterpret_cast<float4*>(s_src + r * ROWF + q * 4) = make_float4((float)v[k].x, (float)v[k].y, (float)v[k].z, (float)v[k].w);
+                else
+                    *reinterpret_cast<float4*>(s_src + r * ROWF + q * 4) = v[k];
+            }
         }
     } else {
         constexpr int NB = (SH * ROWF + 255) / 256;
@@ -263,7 +276,7 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(const float* __rest
             const int r = p / ROWF, q = p - r * ROWF;
             const int sy = min(max(Y0 - kRegionHaloT + r, 0), H - 1);
             const long long f = min(max((long long)(X0 - kRegionHaloL) * C + q, 0ll), (long long)W * C - 1);
-            v[k] = src[(long long)sy * W * C + f];
+            v[k] = (float)src[(long long)sy * W * C + f];
         }
 #pragma unroll
         for (int k = 0; k < NB; ++k) {

@@ -131,7 +131,7 @@ class LineEndPipeline(object):
                  constants=None, center_dimensions=None, clip_hi=255.0, flat_policy="ieee", pad=2,
                  max_keypoints_per_frame=None, selection=False, top_percent=0.1, keep_selection_maps=False, value_map=None,
                  peak_value_map=None, orient_map=True, overlap=False, overlap_priorities=True, placement="auto", keypoints=False,
-                 regions=None, accumulation="float32", storage="float32"):
+                 regions=None, accumulation="float32", storage="float32", frame_dtype="float32"):
         # accumulation="float64" (mode "gray"): every op sums its taps in float64 and rounds once to float32, like the CPU oracle
         # (SILENT_PLAN_ACCUM_F64: the pyramid within 1 ulp of it, CS and end bit-identical to it on the same pyramid).  Checked first:
         # no GPU or torch work for a refused argument
@@ -143,6 +143,10 @@ class LineEndPipeline(object):
         # float32 result rounded to nearest even, half the bytes written and kept; the pyramid stays float32.  Also refused before
         # any GPU or torch work: unknown names, mode "rgb", accumulation="float64", keypoints=True
         self.storage = _runtime.check_storage(storage, mode, accumulation, bool(keypoints))
+        # frame_dtype="uint8" (mode "gray"): step() takes uint8 frames as a camera or decoder delivers them and the kernels read the
+        # bytes themselves (the silent_*_u8 entry points) -- no widening cast, no float32 copy of the batch, every map bit-identical
+        # to the float32 pipeline's on the widened frames.  Refused here as well: unknown names, mode "rgb", accumulation="float64"
+        self.frame_dtype = _runtime.check_frame_dtype(frame_dtype, mode, accumulation)
         import torch
         self.torch = torch
         self.mode = mode
@@ -284,6 +288,12 @@ class LineEndPipeline(object):
             if k not in ("pyr", "pyr1"):
                 setattr(self, k, v)
 
+    def _synthetic_frames(self):
+        """Noise frames of the dtype step() takes (the tuners' default batch)."""
+        torch = self.torch
+        frames = torch.randint(0, 256, (self.batch,) + self.frame_shape, device=self.tdev)
+        return frames.to(torch.uint8 if self.frame_dtype == "uint8" else torch.float32)
+
     def _time_step(self, frames, steps, windows=2):
         import time
         torch = self.torch
@@ -336,7 +346,7 @@ class LineEndPipeline(object):
         import time
         torch = self.torch
         if frames is None:
-            frames = torch.randint(0, 256, (self.batch,) + self.frame_shape, device=self.tdev).to(torch.float32)
+            frames = self._synthetic_frames()
         self._placement_pending = False
         self.wait()                                # nothing of an overlapped step in flight on the side streams
         torch.cuda.synchronize(self.tdev)
@@ -457,7 +467,7 @@ class LineEndPipeline(object):
             pending = False
         self._placement_pending = False            # (frames=None, the constructor's call: the placement waits for the caller's first batch)
         if frames is None:
-            frames = torch.randint(0, 256, (self.batch,) + self.frame_shape, device=self.tdev).to(torch.float32)
+            frames = self._synthetic_frames()
         t_start = time.perf_counter()
         self.wait()                                # (an overlapped step still in flight on the side streams: order it, then let it finish)
         torch.cuda.synchronize(self.tdev)
@@ -519,17 +529,22 @@ class LineEndPipeline(object):
     def algorithmic_bytes_per_frame(self):
         """4*[H*W*C (frame read) + P*C (pyramid written) + P*C (pyramid read) + P*sum(C_out returned)]; for crop layouts the
         frame read is the largest crop any level resamples (the part of the frame the pyramid depends on).  storage="float16":
-        the returned CS and end maps count 2 bytes per element."""
+        the returned CS and end maps count 2 bytes per element.  frame_dtype="uint8": the frame read counts 1 byte per pixel."""
         h, w, c = self.frame_shape
         if self.crop_px is not None:
             h, w = 1, self.crop_px
         outs = (1 + self.n_orient) if self.mode == "gray" else (3 + (3 if self.orient_map else 0) + (1 if self.value_map else 0))
-        return 4 * (h * w * c + 2 * self.frame_px * c) + self._map_bytes * self.frame_px * outs
+        return self._frame_bytes * h * w * c + 4 * 2 * self.frame_px * c + self._map_bytes * self.frame_px * outs
 
     @property
     def _map_bytes(self):
         """Bytes per element of the returned dense maps (not the pyramid)."""
         return 2 if self.storage == "float16" else 4
+
+    @property
+    def _frame_bytes(self):
+        """Bytes per frame element as step() reads it."""
+        return 1 if self.frame_dtype == "uint8" else 4
 
     def filter_bytes_per_frame(self):
         """The filter pass alone: pyramid read once + every returned map written once."""
@@ -539,7 +554,7 @@ class LineEndPipeline(object):
 
     def pyramid_bytes_per_frame(self):
         h, w, c = self.frame_shape
-        return 4 * c * (h * w + self.frame_px)
+        return c * (self._frame_bytes * h * w + 4 * self.frame_px)
 
     def dominant_kernel_name(self):
         """Substring of the rocprofv3 kernel name of the launch that moves most bytes (bench.py matches PMC rows by it)."""
@@ -549,7 +564,8 @@ class LineEndPipeline(object):
         if self.mode == "gray":
             return ("gray_stream_kernel (whole pyramid + level-0 CS/line-end, frame read once) + "
                     "gray_line_end_kernel (levels >= 1)" + (", float64 accumulation" if self.accumulation == "float64" else "")
-                    + (", float16 CS / end maps" if self.storage == "float16" else ""))
+                    + (", float16 CS / end maps" if self.storage == "float16" else "")
+                    + (", uint8 frames" if self.frame_dtype == "uint8" else ""))
         return ("single-read RGB pyramid (pyramid_walk3_kernel), fused RGB chain, max/min + fused selection "
                 "(top 10 % > NMS > value), cell-max / count / scan / write keypoint kernels")
 
@@ -558,13 +574,18 @@ class LineEndPipeline(object):
         return C.c_void_p(self.torch.cuda.current_stream(self.tdev).cuda_stream)
 
     def _check_frames(self, frames):
-        if tuple(frames.shape) != (self.batch,) + self.frame_shape or frames.dtype != self.torch.float32 \
+        want = self.torch.uint8 if self.frame_dtype == "uint8" else self.torch.float32
+        if tuple(frames.shape) != (self.batch,) + self.frame_shape or frames.dtype != want \
                 or not frames.is_cuda or not frames.is_contiguous():
-            raise ValueError("frames must be a contiguous float32 GPU tensor of shape %s" %
-                             ((self.batch,) + self.frame_shape,))
+            raise ValueError("frames must be a contiguous %s GPU tensor of shape %s" %
+                             (self.frame_dtype, (self.batch,) + self.frame_shape,))
 
     def run_pyramid(self, frames, stream=None):
         self._check_frames(frames)
+        if self.frame_dtype == "uint8":
+            self.ctx.check(self._lib.silent_pyramid_u8_dev(self.ctx.handle, self.plan.handle, _lib.byte_ptr(frames.data_ptr()),
+                                                           self.batch, C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
+            return
         self.ctx.check(self._lib.silent_pyramid_dev(self.ctx.handle, self.plan.handle, C.c_void_p(frames.data_ptr()),
                                                     self.batch, C.c_void_p(self.pyr.data_ptr()),
                                                     stream or self._stream()))
@@ -627,8 +648,11 @@ class LineEndPipeline(object):
         write the end map fold the padded value map into what the tail needs; pyramid / cs / end are those of run_gray_pass."""
         self._check_frames(frames)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self.ctx.check(self._lib.silent_gray_keypoints_dev(
-            self.ctx.handle, self.plan.handle, p(frames), self.batch, C.c_void_p(self.consts["cs"].ctypes.data),
+        fn, fp = self._lib.silent_gray_keypoints_dev, p(frames)
+        if self.frame_dtype == "uint8":
+            fn, fp = self._lib.silent_gray_keypoints_u8_dev, _lib.byte_ptr(frames.data_ptr())
+        self.ctx.check(fn(
+            self.ctx.handle, self.plan.handle, fp, self.batch, C.c_void_p(self.consts["cs"].ctypes.data),
             C.c_void_p(self.consts["end"].ctypes.data), self.n_orient, self.clip_hi, p(self.pyr), p(self.cs), p(self.end), self.pad,
             int(self.selection), self.top_percent, self.regions, p(self.value), p(self.peak_value), p(self.kp_idx), self.kp_cap,
             p(self.kp_counts), stream or self._stream()))
@@ -638,6 +662,13 @@ class LineEndPipeline(object):
         levels, fused pyramid + CS + end kernel for the unit levels, filter kernel for the rest.  ``parts``: 1 = pyramid + unit
         levels only, 2 = the filter of the remaining levels only (silent_gray_pass_parts_dev; the halves of an overlapped step)."""
         self._check_frames(frames)
+        if self.frame_dtype == "uint8":    # the same pass reading the bytes as they are, either map storage
+            self.ctx.check(self._lib.silent_gray_pass_u8_dev(
+                self.ctx.handle, self.plan.handle, _lib.byte_ptr(frames.data_ptr()), self.batch,
+                C.c_void_p(self.consts["cs"].ctypes.data), C.c_void_p(self.consts["end"].ctypes.data), self.n_orient,
+                self.clip_hi, C.c_void_p(self.pyr.data_ptr()), C.c_void_p(self.cs.data_ptr()), C.c_void_p(self.end.data_ptr()),
+                1 if self.storage == "float16" else 0, int(parts), stream or self._stream()))
+            return
         if self.storage == "float16":      # the same pass, cs / end as float16 maps
             self.ctx.check(self._lib.silent_gray_pass_h_dev(
                 self.ctx.handle, self.plan.handle, C.c_void_p(frames.data_ptr()), self.batch,
@@ -703,7 +734,8 @@ class LineEndPipeline(object):
     def _ingest_slot(self, dtype, pinned_source):
         """Ring of two slots per dtype: [pinned staging buffer (None when the caller's frames are pinned already), device buffer
         of the source dtype, float32 frame buffer, events].  Two batches are in flight: while batch n computes, batch n + 1 is
-        copied (and, for NumPy sources, batch n + 2 staged by the host)."""
+        copied (and, for NumPy sources, batch n + 2 staged by the host).  A uint8 pipeline's slots have no float32 frame buffer:
+        step() reads the uint8 device buffer itself."""
         torch = self.torch
         ring = self._ingest.setdefault(dtype, {"slots": [], "next": 0})
         if not ring["slots"]:
@@ -712,7 +744,7 @@ class LineEndPipeline(object):
                 ring["slots"].append({
                     "pinned": None,
                     "raw": torch.empty(shape, dtype=dtype, device=self.tdev) if dtype != torch.float32 else None,
-                    "f32": torch.empty(shape, dtype=torch.float32, device=self.tdev),
+                    "f32": torch.empty(shape, dtype=torch.float32, device=self.tdev) if self.frame_dtype != "uint8" else None,
                     "h2d_done": torch.cuda.Event(), "raw_free": None, "f32_free": None})
         slot = ring["slots"][ring["next"]]
         ring["next"] ^= 1
@@ -727,7 +759,9 @@ class LineEndPipeline(object):
         through a pinned staging buffer (skipped when ``frames`` is a pinned torch tensor already), an asynchronous host-to-device
         copy on the pipeline's COPY stream, the library's widening cast (silent_cast_interleave_dev: uint8 -> float32 on the GPU,
         a quarter of the PCIe bytes) and step().  Returns at once; two batches are in flight (ring of two slots), so the copy of
-        batch n + 1 overlaps the compute of batch n.  Results are bit-identical to step() on the same frames resident as float32."""
+        batch n + 1 overlaps the compute of batch n.  Results are bit-identical to step() on the same frames resident as float32.
+        A frame_dtype="uint8" pipeline takes uint8 host frames only: staging -> copy into the slot's uint8 device buffer -> step();
+        no cast launch and no float32 frame buffer."""
         torch = self.torch
         if isinstance(frames, np.ndarray):
             src = torch.from_numpy(np.ascontiguousarray(frames))
@@ -735,7 +769,10 @@ class LineEndPipeline(object):
             src = frames.contiguous()
         if src.is_cuda or tuple(src.shape) != (self.batch,) + self.frame_shape:
             raise ValueError("step_host takes host frames of shape %s" % ((self.batch,) + self.frame_shape,))
-        if src.dtype != torch.float32:
+        if self.frame_dtype == "uint8":
+            if src.dtype != torch.uint8:
+                raise ValueError("step_host of a frame_dtype='uint8' pipeline takes uint8 host frames, got %s" % (src.dtype,))
+        elif src.dtype != torch.float32:
             _runtime._torch_dtype_code(src)         # TypeError for dtypes the cast kernel does not take
         if not hasattr(self, "_ingest"):
             # a stream of another priority than the compute stream gets a hardware queue of its own (two equal-priority streams
@@ -752,6 +789,20 @@ class LineEndPipeline(object):
             slot["h2d_done"].synchronize()          # the staging buffer's previous copy has left the host
             _staging_copy(slot["pinned"], src)
             src = slot["pinned"]
+        if self.frame_dtype == "uint8":
+            # the frame-reading kernels read the uint8 device buffer itself: it is free again where THEY finish -- on the walk stream
+            # with overlap, else on the caller's stream (where a float32 pipeline records f32_free)
+            if slot["raw_free"] is not None:
+                cs.wait_event(slot["raw_free"])     # the previous batch of this slot has been read on the device
+            with torch.cuda.stream(cs):
+                slot["raw"].copy_(src, non_blocking=True)
+            slot["h2d_done"].record(cs)
+            cur.wait_event(slot["h2d_done"])
+            self.step(slot["raw"])
+            if slot["raw_free"] is None:
+                slot["raw_free"] = torch.cuda.Event()
+            slot["raw_free"].record(self._walk_stream if self.overlap else cur)
+            return
         dst = slot["f32"] if slot["raw"] is None else slot["raw"]
         for ev in ((slot["f32_free"],) if slot["raw"] is None else (slot["raw_free"],)):
             if ev is not None:
