@@ -226,6 +226,30 @@ int silent_gray_pass_u8_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, co
                             const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
                             void* end_out, int maps_f16, unsigned parts, silent_stream stream);
 
+/* Interleaved 3-channel uint8 frames, read as they are: what a camera or decoder hands over is colour, [H, W, 3] uint8 (the reference's
+ * callback receives exactly that, BGR from OpenCV: recognition_testing.py:141) and the reference's colour-to-one-channel op is
+ * get_value_from_color (util/color/get_value.py:6-12; silent_value_from_color, a-8).  These entry points are the twins of the *_u8 ones
+ * above -- same argument lists, parts / maps_f16 / stream arguments and status codes -- for frames: [n_frames, H, W, 3] bytes, NO
+ * alignment requirement.  The plan is a SINGLE-CHANNEL plan (it describes the pyramid; the frame layout is a property of the call).
+ * Each frame pixel enters the arithmetic as
+ *     v = (float)(b0 + b1 + b2) * float32(1/3)
+ * formed in registers at the load (the sum, at most 765, is exact as an integer and as a float32, so channel order cannot matter; one
+ * multiply by the float32 reciprocal, never a division by 3).  That is silent_value_from_color on the widened frame bit for bit, so
+ * every output is IDENTICAL to that of the float32-frame entry point given the frame of v values: silent_pyramid[_dev],
+ * silent_gray_pass_parts_dev (maps_f16 = 0), silent_gray_pass_h_dev (maps_f16 = 1) and silent_gray_keypoints[_dev] -- without the cast
+ * launch, the value launch and the two float32 copies of the batch.  The host-pointer forms stage 3 * H * W * n_frames BYTES of frames.
+ * SILENT_E_INVALID as for *_u8; SILENT_E_UNSUPPORTED for a 3-channel plan, a SILENT_PLAN_ACCUM_F64 plan, n_orient other than 3, 4, 8.
+ * (ABI additions only: SILENT_ABI_VERSION is unchanged.) */
+int silent_pyramid_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, float* pyr);
+int silent_pyramid_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, float* pyr,
+                            silent_stream stream);
+int silent_gray_pass_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                          const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
+                          void* end_out, int maps_f16);
+int silent_gray_pass_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                              const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
+                              void* end_out, int maps_f16, unsigned parts, silent_stream stream);
+
 /* 1 when silent_gray_pass runs this plan through the single-read stream kernel (one unit-zoom level and every
  * other level resampling the same crop with a step > 1.25: classic whole-frame pyramids), 0 when it falls
  * back to region + unit-fused + filter kernels (e.g. the reference's centred-crop layout).  The same for
@@ -525,6 +549,18 @@ int silent_gray_keypoints_u8_dev(silent_ctx* ctx, const silent_pyramid_plan* pla
                                  float* cs_out, float* end_out, int pad, int selection, double top_percent,
                                  const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
                                  size_t cap_per_frame, int64_t* counts, silent_stream stream);
+
+/* The same on interleaved 3-channel uint8 frames [n, H, W, 3] (see silent_gray_pass_u8x3): every output is that of
+ * silent_gray_keypoints[_dev] given the frame of values (b0 + b1 + b2) * float32(1/3). */
+int silent_gray_keypoints_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                               const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out,
+                               float* end_out, int pad, int selection, double top_percent, const silent_extent* regions,
+                               float* value_out, float* peak_value_out, int64_t* idx, size_t cap_per_frame, int64_t* counts);
+int silent_gray_keypoints_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                   const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                   float* cs_out, float* end_out, int pad, int selection, double top_percent,
+                                   const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+                                   size_t cap_per_frame, int64_t* counts, silent_stream stream);
 
 /* What the sparse tail of the LAST silent_rgb_keypoints[_dev] / silent_gray_keypoints[_dev] call of this context did (synchronises that call's stream):
  * stats[0] = 1 if it ran sparse, [1] = (frame, level) pairs, [2] = pairs it handed to the dense kernels, [3] = candidate

@@ -76,7 +76,7 @@ _lib = None
 _vp = C.c_void_p
 _fp = C.c_void_p          # float* passed as an address (host ndarray.ctypes.data or a device pointer)
 _hp = C.POINTER(C.c_uint16)   # a float16 map (silent_gray_pass_h: IEEE binary16 as uint16_t*); half_ptr() makes one from an address
-_bp = C.POINTER(C.c_uint8)    # uint8 frames (the *_u8 entry points); byte_ptr() makes one from an address
+_bp = C.POINTER(C.c_uint8)    # uint8 frames (the *_u8 and *_u8x3 entry points); byte_ptr() makes one from an address
 _ep = C.POINTER(Extent)
 _i, _u, _f, _d, _sz = C.c_int, C.c_uint, C.c_float, C.c_double, C.c_size_t
 
@@ -111,9 +111,13 @@ _SIGNATURES = {
     "silent_gray_pass_h": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _hp, _hp],
     "silent_gray_pass_h_dev": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _hp, _hp, _u, _vp],
     "silent_pyramid_u8": [_vp, _vp, _bp, _i, _fp],
+    "silent_pyramid_u8x3": [_vp, _vp, _bp, _i, _fp],
     "silent_pyramid_u8_dev": [_vp, _vp, _bp, _i, _fp, _vp],
+    "silent_pyramid_u8x3_dev": [_vp, _vp, _bp, _i, _fp, _vp],
     "silent_gray_pass_u8": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
+    "silent_gray_pass_u8x3": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8_dev": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i, _u, _vp],
+    "silent_gray_pass_u8x3_dev": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i, _u, _vp],
     "silent_pyramid_plan_is_streamable": [_vp],
     "silent_pyramid_plan_walk_plans": [_vp, C.POINTER(C.c_int)],
     "silent_gather_d2h": [_vp, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), _i, _vp],
@@ -155,7 +159,9 @@ _SIGNATURES = {
     "silent_gray_keypoints": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp],
     "silent_gray_keypoints_dev": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp, _vp],
     "silent_gray_keypoints_u8": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp],
+    "silent_gray_keypoints_u8x3": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp],
     "silent_gray_keypoints_u8_dev": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp, _vp],
+    "silent_gray_keypoints_u8x3_dev": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp, _vp],
     "silent_sparse_tail_stats": [_vp, C.POINTER(C.c_int64)],
     "silent_rgb_chain_stream": [C.POINTER(RgbChainParams), C.c_uint, _fp, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "silent_rgb_line_end": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _fp, _fp, _fp],

@@ -785,6 +785,27 @@ def check_frame_dtype(frame_dtype, mode="gray", accumulation="float32"):
     return frame_dtype
 
 
+FRAME_CHANNELS = (1, 3)
+
+
+def check_frame_channels(frame_channels, mode="gray", frame_dtype="float32", accumulation="float32"):
+    """The frame_channels argument of PyramidPlan.run / gray_pass / gray_keypoints and LineEndPipeline: 1 (default: the frames have
+    the channels of the plan / mode) or 3 (interleaved colour uint8 frames [n, H, W, 3] read as they are by the silent_*_u8x3 entry
+    points: each pixel enters as (b0 + b1 + b2) * float32(1/3), the reference's get_value_from_color, formed at the load -- no cast
+    launch, no value launch, no float32 copy of the batch).  The value is checked first (an int 1 or 3: "3", 3.0 and True are not);
+    then what 3 needs: mode "gray", frame_dtype="uint8" and float32 accumulation."""
+    if isinstance(frame_channels, bool) or not isinstance(frame_channels, int) or frame_channels not in FRAME_CHANNELS:
+        raise ValueError("frame_channels must be 1 or 3, got %r" % (frame_channels,))
+    if frame_channels == 3:
+        if mode != "gray":
+            raise ValueError("frame_channels=3 is for mode 'gray' (mode 'rgb' reads float32 colour frames as colour)")
+        if frame_dtype != "uint8":
+            raise ValueError("frame_channels=3 needs frame_dtype='uint8' (interleaved colour frames are read as uint8 only)")
+        if accumulation == "float64":
+            raise ValueError("frame_channels=3 does not combine with accumulation='float64'")
+    return frame_channels
+
+
 class PyramidPlan(object):
     """Tap tables of one (frame size, level geometry) on the device.  ``levels`` is a list of dicts / tuples
     (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w).  accumulation="float64" (single-channel plans): every op of
@@ -804,22 +825,32 @@ class PyramidPlan(object):
                                                                  C.byref(self.handle)))
         self.frame_px = sum(h * w for h, w in self.extents)
 
-    def _frames(self, frames, frame_dtype="float32"):
+    def _frames(self, frames, frame_dtype="float32", frame_channels=1):
         """[n, H, W, C] frames of this plan (ndarray, or torch GPU tensor) as an operand on the plan's context.  frame_dtype="uint8":
-        a uint8 ndarray or contiguous uint8 GPU tensor, passed as it is (anything else is a ValueError); "float32": widened."""
-        check_frame_dtype(frame_dtype, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
+        a uint8 ndarray or contiguous uint8 GPU tensor, passed as it is (anything else is a ValueError); "float32": widened.
+        frame_channels=3 (single-channel plans, uint8): the frames are [n, H, W, 3] interleaved colour."""
+        mode = "gray" if self.frame_shape[2] == 1 else "rgb"
+        check_frame_channels(frame_channels, mode, frame_dtype, self.accumulation)      # (first: a refused 3 is reported as such)
+        check_frame_dtype(frame_dtype, mode, self.accumulation)
         if not (isinstance(frames, np.ndarray) or is_torch_tensor(frames)):
             raise TypeError(TYPE_ERROR_MESSAGE)
-        if tuple(frames.shape[1:]) != self.frame_shape:
-            raise ValueError("frames must be [n, %d, %d, %d], got %s" % (self.frame_shape + (tuple(frames.shape),)))
+        shape = self.frame_shape[:2] + (3,) if frame_channels == 3 else self.frame_shape
+        if tuple(frames.shape[1:]) != shape:
+            raise ValueError("frames must be [n, %d, %d, %d], got %s" % (shape + (tuple(frames.shape),)))
         return _Operand(frames, ctx=self.ctx, frame_dtype=frame_dtype)
 
-    def run(self, frames, frame_dtype="float32"):
+    @staticmethod
+    def _entry(name, frame_dtype, frame_channels):
+        """The entry point family of a frame layout: silent_<name>, silent_<name>_u8 or silent_<name>_u8x3."""
+        return name + ("_u8x3" if frame_channels == 3 else "_u8" if frame_dtype == "uint8" else "")
+
+    def run(self, frames, frame_dtype="float32", frame_channels=1):
         """frames: [n, H, W, C] ndarray (host) or torch GPU tensor.  Returns a PackedPyramid.  frame_dtype="uint8" (single-channel
-        plans): uint8 frames read as they are (silent_pyramid_u8), the same pyramid bit for bit."""
-        op, c = self._frames(frames, frame_dtype), self.frame_shape[2]
+        plans): uint8 frames read as they are (silent_pyramid_u8), the same pyramid bit for bit.  frame_channels=3 (with "uint8"):
+        [n, H, W, 3] interleaved colour frames (silent_pyramid_u8x3), the pyramid of the frame of values (b0 + b1 + b2) * f32(1/3)."""
+        op, c = self._frames(frames, frame_dtype, frame_channels), self.frame_shape[2]
         out, optr = op.empty(op.n_frames * self.frame_px * c)
-        op.call("pyramid_u8" if frame_dtype == "uint8" else "pyramid", self.handle, op.ptr, op.n_frames, optr)
+        op.call(self._entry("pyramid", frame_dtype, frame_channels), self.handle, op.ptr, op.n_frames, optr)
         return PackedPyramid(out, self.extents, c, op.n_frames)
 
     @property
@@ -841,12 +872,15 @@ class PyramidPlan(object):
         n = _lib.load().silent_pyramid_plan_walk_plans(self.handle, C.byref(px))
         return int(n), int(px.value)
 
-    def gray_pass(self, frames, cs_kernel, end_bank, clip_hi=255.0, storage="float32", frame_dtype="float32"):
+    def gray_pass(self, frames, cs_kernel, end_bank, clip_hi=255.0, storage="float32", frame_dtype="float32", frame_channels=1):
         """Whole grayscale hot path (silent_gray_pass): frames [n,H,W,1] -> (pyramid, cs, end) PackedPyramids.
         Same results as run() + gray_line_end(), one pass less over level 0.  storage="float16" (silent_gray_pass_h): cs and end
         are float16 maps -- each element the float32 result rounded to nearest even -- and the pyramid stays float32.
-        frame_dtype="uint8" (silent_gray_pass_u8): uint8 frames read as they are; the same maps bit for bit, either storage."""
+        frame_dtype="uint8" (silent_gray_pass_u8): uint8 frames read as they are; the same maps bit for bit, either storage.
+        frame_channels=3 (with "uint8"; silent_gray_pass_u8x3): frames [n,H,W,3] interleaved colour, each pixel entering as
+        (b0 + b1 + b2) * float32(1/3) -- the maps of the float32 call on that frame of values, bit for bit."""
         check_storage(storage, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
+        check_frame_channels(frame_channels, "gray" if self.frame_shape[2] == 1 else "rgb", frame_dtype, self.accumulation)
         check_frame_dtype(frame_dtype, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
         if self.frame_shape[2] != 1:
             raise ValueError("gray_pass needs a single-channel plan")
@@ -855,7 +889,7 @@ class PyramidPlan(object):
         if cs.shape != (3, 3, 1, 1) or eb.shape[:3] != (3, 3, 1):
             raise ValueError("gray_pass needs a [3,3,1,1] CS kernel and a [3,3,1,K] end bank")
         K = eb.shape[3]
-        op = self._frames(frames, frame_dtype)
+        op = self._frames(frames, frame_dtype, frame_channels)
         n = op.n_frames
         if frame_dtype == "uint8":
             dt = np.float16 if storage == "float16" else np.float32
@@ -863,7 +897,7 @@ class PyramidPlan(object):
             (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch, dt) for ch in (1, K)]
             args = (self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi), pp, cp, ep,
                     1 if storage == "float16" else 0)
-            op.call("gray_pass_u8", *(args + ((3,) if op.dev else ())))
+            op.call(self._entry("gray_pass", frame_dtype, frame_channels), *(args + ((3,) if op.dev else ())))
         elif storage == "float16":
             pyr, pp = op.empty(n * self.frame_px)
             (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch, np.float16) for ch in (1, K)]
@@ -880,10 +914,12 @@ class PyramidPlan(object):
         return P(pyr, self.extents, 1, n), P(cso, self.extents, 1, n, dtype=dt), P(endo, self.extents, K, n, dtype=dt)
 
     def gray_keypoints(self, frames, cs_kernel, end_bank, clip_hi=255.0, pad=2, selection=True, top_percent=0.1, regions=None,
-                       cap_per_frame=None, frame_dtype="float32"):
+                       cap_per_frame=None, frame_dtype="float32", frame_channels=1):
         """silent_gray_keypoints (host form): gray_pass + pad_inwards -> value -> [top_value_points -> NMS -> value ->]
         max_value_indices_region on the K-channel end map.  Returns (pyramid, cs, end, idx [n, cap, 4], counts [n]).
-        frame_dtype="uint8" (silent_gray_keypoints_u8): uint8 frames read as they are, the same results."""
+        frame_dtype="uint8" (silent_gray_keypoints_u8): uint8 frames read as they are, the same results.  frame_channels=3 (with
+        "uint8"; silent_gray_keypoints_u8x3): [n,H,W,3] interleaved colour frames, the results of the frame of values."""
+        check_frame_channels(frame_channels, "gray" if self.frame_shape[2] == 1 else "rgb", frame_dtype, self.accumulation)
         check_frame_dtype(frame_dtype, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
         if self.frame_shape[2] != 1:
             raise ValueError("gray_keypoints needs a single-channel plan")
@@ -897,13 +933,13 @@ class PyramidPlan(object):
             raise ValueError("need one (rH, rW) region per level")
         reg = (_lib.Extent * len(regions))(*[_lib.Extent(int(rh), int(rw)) for rh, rw in regions])
         K = eb.shape[3]
-        op = self._frames(frames, frame_dtype)
+        op = self._frames(frames, frame_dtype, frame_channels)
         n = op.n_frames
         cap = self.frame_px if cap_per_frame is None else int(cap_per_frame)
         (pyr, pp), (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch) for ch in (1, 1, K)]
         idx, iptr = op.empty((n, cap, 4), np.int64)
         counts, cptr = op.empty(n, np.int64)
-        op.call("gray_keypoints_u8" if frame_dtype == "uint8" else "gray_keypoints", self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi),
+        op.call(self._entry("gray_keypoints", frame_dtype, frame_channels), self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi),
                 pp, cp, ep, int(pad), int(selection), float(top_percent), reg, None, None, iptr, cap, cptr)
         P = PackedPyramid
         return P(pyr, self.extents, 1, n), P(cso, self.extents, 1, n), P(endo, self.extents, K, n), idx, counts

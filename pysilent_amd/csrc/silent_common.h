@@ -139,8 +139,31 @@ __device__ __forceinline__ double unit_taps6(float c0, float edge, const double 
 // into negatives.  The FT = float instantiations are the code as it was (their machine code is unchanged).
 template <typename FT>
 constexpr bool kFrameBytes = std::is_same<FT, unsigned char>::value;
+// Interleaved 3-channel uint8 frames (the *_u8x3 entry points: [n, H, W, 3] bytes as a camera or decoder delivers colour).  One frame
+// PIXEL is one element of this type -- size 3, alignment 1 -- so every index, row stride and 64-bit frame offset of the kernels
+// counts pixels as it does for the other frame types, and the `(float)src[i]` at their loads is the reference's get_value_from_color
+// (a-8) on that pixel: ((b0 + b1) + b2) * float32(1/3), ONE rounding (the sum is at most 765: exact as an integer and as a float32,
+// in any channel order) -- bit for bit silent_value_from_color on the widened frame.  Times the float32 reciprocal, never / 3.0f:
+// 254 of the 766 sums differ.  Two loads per lane and row: a 2-byte load at 3 * lane and a byte load at 3 * lane + 2, neither with
+// an alignment requirement (a wave row is 192 contiguous bytes in 2 VMEM requests).  Written as three byte loads the compiler merges
+// the first two as well but keeps 104 - 106 VGPRs in gray_stream_kernel (4 waves per SIMD); this form has the unsigned char
+// kernels' 78 - 103 (5) and measured 1.055 against 1.116 ms per config-2 step (profiles/gray_rgb8/README.md).
+struct FrameRgb8 {
+    unsigned char b[3];
+    __device__ __forceinline__ explicit operator float() const {
+        unsigned short lo;                       // b[0], b[1]: one 2-byte load at alignment 1 (global_load_ushort takes any address)
+        __builtin_memcpy(&lo, b, 2);
+        return __fmul_rn((float)((int)(lo & 0xffu) + (int)(lo >> 8) + (int)b[2]), 1.0f / 3.0f);
+    }
+};
+static_assert(sizeof(FrameRgb8) == 3 && alignof(FrameRgb8) == 1, "one interleaved uint8 colour pixel");
 template <typename FT>
-constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameBytes<FT>;
+constexpr bool kFrameRgb8 = std::is_same<FT, FrameRgb8>::value;
+// the frame types that exist for single-channel plans with float32 accumulation only
+template <typename FT>
+constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT>;
+template <typename FT>
+constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT>;
 
 // Stream row i of the column `col` (level coordinates, mirrored inside the crop like every tap; px_stride floats per pixel) in lane i: ONE load per tile
 // for the sixth taps of a wave's last smoothing lane; row i is read back with unit_edge(xcol, i).

@@ -70,7 +70,8 @@ SILENT_EXPORT int silent_gray_line_end_dev(silent_ctx* ctx, const float* pyr, co
     return on_exception(ctx, "silent_gray_line_end_dev");
 }
 
-// FT: the frame element type -- float, or unsigned char (uint8 frames: the *_u8 entry points).  The uint8 kernels exist with float32
+// FT: the frame element type -- float, unsigned char (uint8 frames: the *_u8 entry points) or FrameRgb8 (interleaved uint8 colour: the
+// *_u8x3 entry points, silent_common.h).  The uint8 kernels of both kinds exist with float32
 // accumulation only (F64 plans are refused before a launch), with and without keypoint epilogue, for both map storages.
 template <int K, int G, int L, bool F64, typename ST, typename FT>
 static void launch_stream(long long blocks, hipStream_t s, const FT* frames, float* pyr, ST* cs_out, ST* end_out,
@@ -108,10 +109,10 @@ template <typename ST, typename FT>
 static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames,
                            const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
                            ST* cs_out, ST* end_out, unsigned parts, silent_stream stream, const GrayKp* kp = nullptr) {
-    const char* who = kFrameBytes<FT> ? (kp ? "silent_gray_keypoints_u8" : "silent_gray_pass_u8") : kStoreHalf<ST> ? "silent_gray_pass_h" : "silent_gray_pass";
+    const char* who = kFrameRgb8<FT> ? (kp ? "silent_gray_keypoints_u8x3" : "silent_gray_pass_u8x3") : kFrameBytes<FT> ? (kp ? "silent_gray_keypoints_u8" : "silent_gray_pass_u8") : kStoreHalf<ST> ? "silent_gray_pass_h" : "silent_gray_pass";
     if (!plan || !frames || !pyr || !cs_kernel) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
-    if constexpr (kFrameBytes<FT>) {
+    if constexpr (kFrameNarrow<FT>) {
         if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
         if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
     }
@@ -133,7 +134,8 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
     //    from the same single read of the frame; plus the zero fill of canvases larger than their zoomed crop
     if (!(parts & 3u)) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": parts must name step 1 + 2 (bit 0) and / or step 3 (bit 1)");
     if (parts & 1u) {
-        if constexpr (kFrameBytes<FT>) TRY(launch_pyramid_u8(ctx, who, plan, frames, n_frames, pyr, s, false, !stream_path));
+        if constexpr (kFrameRgb8<FT>) TRY(launch_pyramid_u8x3(ctx, who, plan, frames, n_frames, pyr, s, false, !stream_path));
+        else if constexpr (kFrameBytes<FT>) TRY(launch_pyramid_u8(ctx, who, plan, frames, n_frames, pyr, s, false, !stream_path));
         else TRY(launch_pyramid(ctx, who, plan, frames, n_frames, pyr, s, false, !stream_path));
     }
     // 2. unit levels: pyramid + CS + end in one kernel
@@ -184,7 +186,7 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
             const unsigned sopts = (unsigned)((kopts >> 5) & 1);
 #define STREAM_LAUNCH(K_, G_, L_)                                                                                  \
     if constexpr (kStoreHalf<ST>) launch_stream<K_, G_, L_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, nullptr); \
-    else if constexpr (kFrameBytes<FT>) launch_stream<K_, G_, L_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp); \
+    else if constexpr (kFrameNarrow<FT>) launch_stream<K_, G_, L_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp); \
     else if (plan->f64) launch_stream<K_, G_, L_, true, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp); \
     else launch_stream<K_, G_, L_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, st, w, clip_hi, sopts, kpp)
             if (plan->stream_layout == 1) {          // zoom ladders of ratio 1.4 .. e^.5: five rows of the first level in flight
@@ -204,7 +206,7 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
         } else {
 #define FUSED_LAUNCH(K_)                                                                                   \
     if constexpr (kStoreHalf<ST>) launch_fused<K_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, nullptr); \
-    else if constexpr (kFrameBytes<FT>) launch_fused<K_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp); \
+    else if constexpr (kFrameNarrow<FT>) launch_fused<K_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp); \
     else if (plan->f64) launch_fused<K_, true, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp); \
     else launch_fused<K_, false, ST, FT>(blocks, s, frames, pyr, cs_out, end_out, ft, w, clip_hi, kpp)
             if (n_orient == 3) { FUSED_LAUNCH(3); }
@@ -237,6 +239,13 @@ int gray_pass_kp(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* 
 int gray_pass_kp_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, const float* cs_kernel,
                     const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const GrayKp& kp,
                     hipStream_t s) {
+    return gray_pass_parts(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, 3u,
+                           (silent_stream)s, &kp);
+}
+
+int gray_pass_kp_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const FrameRgb8* frames, int n_frames, const float* cs_kernel,
+                      const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const GrayKp& kp,
+                      hipStream_t s) {
     return gray_pass_parts(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, 3u,
                            (silent_stream)s, &kp);
 }
@@ -373,4 +382,46 @@ SILENT_EXPORT int silent_gray_pass_u8(silent_ctx* ctx, const silent_pyramid_plan
     });
 } catch (...) {
     return on_exception(ctx, "silent_gray_pass_u8");
+}
+
+// ------------------------------------------------------------------------------------------ interleaved 3-channel uint8 frames
+// The same pass reading [n, H, W, 3] uint8 colour frames as they are (the FT = FrameRgb8 instantiations of the frame-reading kernels;
+// silent_hip.h has the contract): each pixel's value (b0 + b1 + b2) * float32(1/3) is formed in registers at the load, so every output
+// is the float32-frame entry point's on the frame of values, bit for bit.  The plan is single-channel: the layout belongs to the call.
+
+SILENT_EXPORT int silent_gray_pass_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                            const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                            void* cs_out, void* end_out, int maps_f16, unsigned parts, silent_stream stream) try {
+    NEED_CTX(ctx);
+    const FrameRgb8* px = reinterpret_cast<const FrameRgb8*>(frames);
+    if (maps_f16)
+        return gray_pass_parts(ctx, plan, px, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr,
+                               static_cast<gray_half*>(cs_out), static_cast<gray_half*>(end_out), parts, stream);
+    return gray_pass_parts(ctx, plan, px, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, static_cast<float*>(cs_out),
+                           static_cast<float*>(end_out), parts, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_pass_u8x3_dev");
+}
+
+SILENT_EXPORT int silent_gray_pass_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                        void* cs_out, void* end_out, int maps_f16) try {
+    NEED_CTX(ctx);
+    if (!plan || !frames || !pyr) return fail(ctx, SILENT_E_INVALID, "silent_gray_pass_u8x3: NULL pointer");
+    if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_gray_pass_u8x3: uint8 frames are for single-channel plans");
+    if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_gray_pass_u8x3: uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
+    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, "silent_gray_pass_u8x3: n_frames must be >= 1");
+    if (n_orient != 3 && n_orient != 4 && n_orient != 8)
+        return fail(ctx, SILENT_E_UNSUPPORTED, "silent_gray_pass_u8x3: n_orient must be 3, 4 or 8");
+    HostStage hs(ctx);
+    const size_t px = (size_t)plan->tab.frame_px_out * n_frames, eb = maps_f16 ? 2 : 4;
+    // (the frames are interleaved colour bytes: 3 * H * W * n of them)
+    const int x = hs.in(frames, (size_t)3 * plan->tab.H * plan->tab.W * n_frames), p = hs.out(pyr, px * 4), cs = hs.out(cs_out, px * eb),
+              end = hs.out(end_out, px * eb * n_orient);
+    return hs.run([&] {
+        return silent_gray_pass_u8x3_dev(ctx, plan, hs.dev<uint8_t>(x), n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
+                                         hs.dev<char>(cs), hs.dev<char>(end), maps_f16, 3u, nullptr);
+    });
+} catch (...) {
+    return on_exception(ctx, "silent_gray_pass_u8x3");
 }

@@ -831,7 +831,8 @@ static int gray_keypoints_checks(silent_ctx* ctx, const char* who, const silent_
     return SILENT_OK;
 }
 
-// FT: the frame element type -- float, or uint8_t (silent_gray_keypoints_u8[_dev]: single-channel float32-accumulation plans)
+// FT: the frame element type -- float, uint8_t (silent_gray_keypoints_u8[_dev]) or FrameRgb8 (silent_gray_keypoints_u8x3[_dev]); the
+// uint8 kinds: single-channel float32-accumulation plans
 static int gray_pass_kp_any(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames, const float* cs_kernel,
                             const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const GrayKp& kp,
                             hipStream_t s) {
@@ -841,6 +842,11 @@ static int gray_pass_kp_any(silent_ctx* ctx, const silent_pyramid_plan* plan, co
                             const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const GrayKp& kp,
                             hipStream_t s) {
     return gray_pass_kp_u8(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s);
+}
+static int gray_pass_kp_any(silent_ctx* ctx, const silent_pyramid_plan* plan, const FrameRgb8* frames, int n_frames, const float* cs_kernel,
+                            const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const GrayKp& kp,
+                            hipStream_t s) {
+    return gray_pass_kp_u8x3(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s);
 }
 
 template <typename FT>
@@ -920,6 +926,23 @@ SILENT_EXPORT int silent_gray_keypoints_u8_dev(silent_ctx* ctx, const silent_pyr
                               end_out, pad, selection, top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u8_dev");
+}
+
+// interleaved 3-channel uint8 frames [n, H, W, 3], read as they are (silent_hip.h): every output is silent_gray_keypoints_dev's on
+// the frame of values (b0 + b1 + b2) * float32(1/3)
+SILENT_EXPORT int silent_gray_keypoints_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                               const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                               float* cs_out, float* end_out, int pad, int selection, double top_percent,
+                                               const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+                                               size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
+    NEED_CTX(ctx);
+    const char* who = "silent_gray_keypoints_u8x3";
+    if (plan && plan->ctx == ctx && plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
+    if (plan && plan->ctx == ctx && plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
+    return gray_keypoints_dev(ctx, who, plan, reinterpret_cast<const FrameRgb8*>(frames), n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out,
+                              end_out, pad, selection, top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_keypoints_u8x3_dev");
 }
 
 SILENT_EXPORT int silent_sparse_tail_stats(silent_ctx* ctx, int64_t* stats) try {
@@ -1144,6 +1167,40 @@ SILENT_EXPORT int silent_gray_keypoints_u8(silent_ctx* ctx, const silent_pyramid
     return SILENT_OK;
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u8");
+}
+
+// interleaved 3-channel uint8 frames (staged as 3 * H * W * n BYTES)
+SILENT_EXPORT int silent_gray_keypoints_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                        float* cs_out, float* end_out, int pad, int selection, double top_percent,
+                                        const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+                                        size_t cap_per_frame, int64_t* counts) try {
+    NEED_CTX(ctx);
+    const char* who = "silent_gray_keypoints_u8x3";
+    // (the host form accepts NULL pyr / end_out: the *_dev form needs both maps, they then live in the staging arena)
+    if (!plan || !frames) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (plan->ctx == ctx && plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
+    if (plan->ctx == ctx && plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
+    TRY(gray_keypoints_checks(ctx, who, plan, frames, n_frames, cs_kernel, end_bank, n_orient, (float*)(void*)frames, (float*)(void*)frames, pad,
+                              selection, regions, peak_value_out, idx, cap_per_frame, counts));
+    HostStage hs(ctx);
+    const size_t b1 = (size_t)plan->tab.frame_px_out * n_frames * 4;
+    const int x = hs.in(frames, (size_t)3 * plan->tab.H * plan->tab.W * n_frames)   /* bytes */,
+              p = pyr ? hs.out(pyr, b1) : hs.scratch(b1), cs = hs.out(cs_out, b1),
+              end = end_out ? hs.out(end_out, b1 * n_orient) : hs.scratch(b1 * n_orient), v = hs.out(value_out, b1),
+              pv = hs.out(peak_value_out, b1), i = hs.out(idx, (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
+              n = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
+    TRY(hs.run([&] {
+        return silent_gray_keypoints_u8x3_dev(ctx, plan, hs.dev<uint8_t>(x), n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
+                                         hs.dev<float>(cs), hs.dev<float>(end), pad, selection, top_percent, regions, hs.dev<float>(v),
+                                         hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame, hs.dev<int64_t>(n), nullptr);
+    }));
+    for (int f = 0; f < n_frames; ++f)
+        if (counts[f] > (int64_t)cap_per_frame)
+            return fail(ctx, SILENT_E_CAPACITY, std::string(who) + ": cap_per_frame too small; counts hold the need");
+    return SILENT_OK;
+} catch (...) {
+    return on_exception(ctx, "silent_gray_keypoints_u8x3");
 }
 
 SILENT_EXPORT int silent_centroids(silent_ctx* ctx, const float* value, const silent_extent* levels, int n_levels,

@@ -43,6 +43,9 @@ int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* 
 // the same on uint8 frames (single-channel plans without SILENT_PLAN_ACCUM_F64; anything else is refused)
 int launch_pyramid_u8(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, float* pyr,
                       hipStream_t s, bool with_unit, bool with_region = true);
+// the same on interleaved 3-channel uint8 frames (silent::FrameRgb8: one colour pixel, its value formed at the load); the same refusals
+int launch_pyramid_u8x3(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const silent::FrameRgb8* frames, int n_frames,
+                        float* pyr, hipStream_t s, bool with_unit, bool with_region = true);
 // (silent_gray_api.hip) silent_gray_pass_dev with the keypoint epilogue (silent_gray.h, GrayKp) in every kernel that writes `end`
 int gray_pass_kp(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames, const float* cs_kernel,
                  const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const silent::GrayKp& kp,
@@ -50,3 +53,6 @@ int gray_pass_kp(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* 
 int gray_pass_kp_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, const float* cs_kernel,
                     const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const silent::GrayKp& kp,
                     hipStream_t s);
+int gray_pass_kp_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent::FrameRgb8* frames, int n_frames,
+                      const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out,
+                      const silent::GrayKp& kp, hipStream_t s);

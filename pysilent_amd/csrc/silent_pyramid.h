@@ -96,7 +96,7 @@ __device__ __forceinline__ int mirror_index(int i, int n) {
 template <int C, bool F64 = false, typename FT = float>
 __global__ __launch_bounds__(256) void pyramid_unit_kernel(const FT* __restrict__ frames,
                                                            float* __restrict__ pyr, const PyrTabT<F64> tab) {
-    static_assert(kFrameType<FT> && (!kFrameBytes<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
+    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
     constexpr int R = kUnitTH;
     const unsigned bid = blockIdx.x;
     const int frame = (int)(bid / (unsigned)tab.unit_tiles_per_frame);
@@ -201,10 +201,11 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(const FT* __restrict_
 // (one dword) per lane, which is legal only where the ADDRESS is 4-byte aligned -- and the uint8 frames pointer has no alignment
 // requirement: W % 4 == 0 puts every row start (frame * H * W + sy * W) and every group offset f on the dword grid relative to the
 // base, so the base address decides; any other base or width takes the one-element path.
+// FT = FrameRgb8 (interleaved uint8 colour, silent_common.h): always the one-element path, the value formed while staging.
 template <int C, bool F64 = false, typename FT = float>
 __global__ __launch_bounds__(256) void pyramid_region_kernel(const FT* __restrict__ frames,
                                                              float* __restrict__ pyr, const PyrTabT<F64> tab) {
-    static_assert(kFrameType<FT> && (!kFrameBytes<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
+    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
     constexpr int RW = region_w(C), SW = region_sw(C), SH = region_sh(C), ROWF = SW * C, VR = region_vr(C);
     __shared__ __attribute__((aligned(16))) float s_src[SH * ROWF];
     __shared__ __attribute__((aligned(16))) acc_t<F64> s_v[VR * ROWF];
@@ -242,6 +243,7 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(const FT* __restric
     // outside the frame are never referenced: rows are clamped, out-of-frame column groups are skipped.
     bool groups = ((W * C) & 3) == 0;
     if constexpr (kFrameBytes<FT>) groups = groups && (reinterpret_cast<unsigned long long>(frames) & 3ull) == 0;   // (block-uniform)
+    if constexpr (kFrameRgb8<FT>) groups = false;   // interleaved colour bytes: the one-element path (a pixel per element)
     if (groups) {
         constexpr int V4 = ROWF / 4, NB = (SH * V4 + 255) / 256;
         typename std::conditional<kFrameBytes<FT>, uchar4, float4>::type v[NB];

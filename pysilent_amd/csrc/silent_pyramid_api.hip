@@ -643,14 +643,15 @@ static bool walk3_plan(const silent_ctx* ctx, const silent_pyramid_plan* plan, i
     return true;
 }
 
-// FT: the frame element type -- float, or unsigned char (uint8 frames: single-channel plans with float32 accumulation only)
+// FT: the frame element type -- float, or unsigned char / FrameRgb8 (uint8 frames, one channel / interleaved colour: single-channel
+// plans with float32 accumulation only)
 template <typename FT>
 static int launch_pyramid_t(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames,
                             int n_frames, float* pyr, hipStream_t s, bool with_unit, bool with_region) {
     if (!plan || !frames || !pyr) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
     if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
-    if constexpr (kFrameBytes<FT>) {
+    if constexpr (kFrameNarrow<FT>) {
         if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
         if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
     }
@@ -683,7 +684,7 @@ static int launch_pyramid_t(silent_ctx* ctx, const char* who, const silent_pyram
         const long long blocks = (long long)ft.tiles_per_frame * n_frames;
         if (blocks > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many tiles for one launch");
 #define PYR_STREAM(G_, L_)                                                                                                                 \
-    if constexpr (kFrameBytes<FT>)                                                                                                         \
+    if constexpr (kFrameNarrow<FT>)                                                                                                        \
         hipLaunchKernelGGL((pyramid_stream_kernel<1, G_, L_, false, FT>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, \
                            static_cast<const FusedTab&>(ft), plan->stream);                                                                \
     else if (plan->f64)                                                                                                                    \
@@ -696,7 +697,7 @@ static int launch_pyramid_t(silent_ctx* ctx, const char* who, const silent_pyram
         else if (plan->stream.G <= 4) { PYR_STREAM(4, 0); }
         else { PYR_STREAM(7, 0); }
 #undef PYR_STREAM
-    } else if constexpr (kFrameBytes<FT>) {   // (single-channel, float32 accumulation: checked above)
+    } else if constexpr (kFrameNarrow<FT>) {   // (single-channel, float32 accumulation: checked above)
         if (b_unit) hipLaunchKernelGGL((pyramid_unit_kernel<1, false, FT>), dim3((unsigned)b_unit), dim3(256), 0, s, frames, pyr, tab);
         if (b_region) hipLaunchKernelGGL((pyramid_region_kernel<1, false, FT>), dim3((unsigned)b_region), dim3(256), 0, s, frames, pyr, tab);
     } else if (tab.C == 3 && plan->walk_pyr_ok && with_unit && with_region && !(kopts & 3u) && walk3_plan(ctx, plan, n_frames, &w3t)) {
@@ -745,6 +746,10 @@ int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* 
 }
 int launch_pyramid_u8(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, float* pyr,
                       hipStream_t s, bool with_unit, bool with_region) {
+    return launch_pyramid_t(ctx, who, plan, frames, n_frames, pyr, s, with_unit, with_region);
+}
+int launch_pyramid_u8x3(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FrameRgb8* frames, int n_frames,
+                        float* pyr, hipStream_t s, bool with_unit, bool with_region) {
     return launch_pyramid_t(ctx, who, plan, frames, n_frames, pyr, s, with_unit, with_region);
 }
 
@@ -808,4 +813,33 @@ SILENT_EXPORT int silent_pyramid_u8(silent_ctx* ctx, const silent_pyramid_plan* 
     return hs.run([&] { return silent_pyramid_u8_dev(ctx, plan, hs.dev<uint8_t>(x), n_frames, hs.dev<float>(o), nullptr); });
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_u8");
+}
+
+// ------------------------------------------------------------------------------------------ interleaved 3-channel uint8 frames
+// silent_pyramid[_dev] reading [n, H, W, 3] uint8 colour frames as they are (the FT = FrameRgb8 kernels: each pixel's value
+// (b0 + b1 + b2) * float32(1/3) is formed at the load, the pyramid is the float32-frame call's on the frame of values, bit for
+// bit).  Single-channel plans without SILENT_PLAN_ACCUM_F64: the plan describes the pyramid, the frame layout belongs to the call.
+
+SILENT_EXPORT int silent_pyramid_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                          float* pyr, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return launch_pyramid_u8x3(ctx, "silent_pyramid_u8x3", plan, reinterpret_cast<const FrameRgb8*>(frames), n_frames, pyr,
+                               (hipStream_t)stream, true);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_u8x3_dev");
+}
+
+SILENT_EXPORT int silent_pyramid_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                      float* pyr) try {
+    NEED_CTX(ctx);
+    if (!plan || !frames || !pyr) return fail(ctx, SILENT_E_INVALID, "silent_pyramid_u8x3: NULL pointer");
+    if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_pyramid_u8x3: uint8 frames are for single-channel plans");
+    if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_pyramid_u8x3: uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
+    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, "silent_pyramid_u8x3: n_frames must be >= 1");
+    HostStage hs(ctx);
+    const int x = hs.in(frames, (size_t)3 * plan->tab.H * plan->tab.W * n_frames),   // bytes: 3 per frame pixel
+              o = hs.out(pyr, (size_t)plan->tab.frame_px_out * 4 * n_frames);
+    return hs.run([&] { return silent_pyramid_u8x3_dev(ctx, plan, hs.dev<uint8_t>(x), n_frames, hs.dev<float>(o), nullptr); });
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_u8x3");
 }

@@ -131,7 +131,7 @@ class LineEndPipeline(object):
                  constants=None, center_dimensions=None, clip_hi=255.0, flat_policy="ieee", pad=2,
                  max_keypoints_per_frame=None, selection=False, top_percent=0.1, keep_selection_maps=False, value_map=None,
                  peak_value_map=None, orient_map=True, overlap=False, overlap_priorities=True, placement="auto", keypoints=False,
-                 regions=None, accumulation="float32", storage="float32", frame_dtype="float32"):
+                 regions=None, accumulation="float32", storage="float32", frame_dtype="float32", frame_channels=1):
         # accumulation="float64" (mode "gray"): every op sums its taps in float64 and rounds once to float32, like the CPU oracle
         # (SILENT_PLAN_ACCUM_F64: the pyramid within 1 ulp of it, CS and end bit-identical to it on the same pyramid).  Checked first:
         # no GPU or torch work for a refused argument
@@ -146,6 +146,13 @@ class LineEndPipeline(object):
         # frame_dtype="uint8" (mode "gray"): step() takes uint8 frames as a camera or decoder delivers them and the kernels read the
         # bytes themselves (the silent_*_u8 entry points) -- no widening cast, no float32 copy of the batch, every map bit-identical
         # to the float32 pipeline's on the widened frames.  Refused here as well: unknown names, mode "rgb", accumulation="float64"
+        # (checked below, after frame_channels: a refused frame_channels=3 is reported as such)
+        # frame_channels=3 (mode "gray", frame_dtype="uint8"): step() takes [batch, H, W, 3] interleaved colour uint8 frames and the
+        # kernels form each pixel's value (b0 + b1 + b2) * float32(1/3) at the load (the silent_*_u8x3 entry points) -- no cast launch,
+        # no value launch, no float32 buffer; every map bit-identical to the float32 pipeline's on the frame of values.  frame_shape
+        # becomes (H, W, 3); channels, the plan and all maps stay single-channel.  Refused here as well: anything but 1 and 3, and 3
+        # with mode "rgb", frame_dtype="float32" or accumulation="float64"
+        self.frame_channels = _runtime.check_frame_channels(frame_channels, mode, frame_dtype, accumulation)
         self.frame_dtype = _runtime.check_frame_dtype(frame_dtype, mode, accumulation)
         import torch
         self.torch = torch
@@ -156,7 +163,7 @@ class LineEndPipeline(object):
         self.ctx = _runtime.get_context(self.device_index)
         self.batch = int(batch)
         h, w = int(frame_hw[0]), int(frame_hw[1])
-        self.frame_shape = (h, w, self.channels)
+        self.frame_shape = (h, w, 3 if self.frame_channels == 3 else self.channels)
         levels = (reference_levels((h, w), center_dimensions, scale) if center_dimensions is not None
                   else classic_levels((h, w), scale, n_levels))
         self.crop_px = None
@@ -529,12 +536,14 @@ class LineEndPipeline(object):
     def algorithmic_bytes_per_frame(self):
         """4*[H*W*C (frame read) + P*C (pyramid written) + P*C (pyramid read) + P*sum(C_out returned)]; for crop layouts the
         frame read is the largest crop any level resamples (the part of the frame the pyramid depends on).  storage="float16":
-        the returned CS and end maps count 2 bytes per element.  frame_dtype="uint8": the frame read counts 1 byte per pixel."""
-        h, w, c = self.frame_shape
+        the returned CS and end maps count 2 bytes per element.  frame_dtype="uint8": the frame read counts 1 byte per frame element
+        -- frame_shape[2] of them per pixel (3 for interleaved colour frames, whose pyramid and maps stay single-channel)."""
+        h, w, fc = self.frame_shape
+        c = self.channels
         if self.crop_px is not None:
             h, w = 1, self.crop_px
         outs = (1 + self.n_orient) if self.mode == "gray" else (3 + (3 if self.orient_map else 0) + (1 if self.value_map else 0))
-        return self._frame_bytes * h * w * c + 4 * 2 * self.frame_px * c + self._map_bytes * self.frame_px * outs
+        return self._frame_bytes * h * w * fc + 4 * 2 * self.frame_px * c + self._map_bytes * self.frame_px * outs
 
     @property
     def _map_bytes(self):
@@ -546,6 +555,12 @@ class LineEndPipeline(object):
         """Bytes per frame element as step() reads it."""
         return 1 if self.frame_dtype == "uint8" else 4
 
+    @property
+    def _colour_frames(self):
+        """True for a gray pipeline reading interleaved 3-channel uint8 frames (frame_channels=3): the frame has more channels than
+        the maps."""
+        return self.mode == "gray" and self.frame_shape[2] == 3
+
     def filter_bytes_per_frame(self):
         """The filter pass alone: pyramid read once + every returned map written once."""
         c = self.channels
@@ -553,8 +568,8 @@ class LineEndPipeline(object):
         return self.frame_px * (4 * c + self._map_bytes * outs)
 
     def pyramid_bytes_per_frame(self):
-        h, w, c = self.frame_shape
-        return c * (self._frame_bytes * h * w + 4 * self.frame_px)
+        h, w, fc = self.frame_shape
+        return self._frame_bytes * h * w * fc + 4 * self.frame_px * self.channels
 
     def dominant_kernel_name(self):
         """Substring of the rocprofv3 kernel name of the launch that moves most bytes (bench.py matches PMC rows by it)."""
@@ -565,7 +580,8 @@ class LineEndPipeline(object):
             return ("gray_stream_kernel (whole pyramid + level-0 CS/line-end, frame read once) + "
                     "gray_line_end_kernel (levels >= 1)" + (", float64 accumulation" if self.accumulation == "float64" else "")
                     + (", float16 CS / end maps" if self.storage == "float16" else "")
-                    + (", uint8 frames" if self.frame_dtype == "uint8" else ""))
+                    + (", uint8 frames" if self.frame_dtype == "uint8" else "")
+                    + (" of 3 interleaved channels (value formed at the load)" if self._colour_frames else ""))
         return ("single-read RGB pyramid (pyramid_walk3_kernel), fused RGB chain, max/min + fused selection "
                 "(top 10 % > NMS > value), cell-max / count / scan / write keypoint kernels")
 
@@ -583,7 +599,8 @@ class LineEndPipeline(object):
     def run_pyramid(self, frames, stream=None):
         self._check_frames(frames)
         if self.frame_dtype == "uint8":
-            self.ctx.check(self._lib.silent_pyramid_u8_dev(self.ctx.handle, self.plan.handle, _lib.byte_ptr(frames.data_ptr()),
+            fn = self._lib.silent_pyramid_u8x3_dev if self._colour_frames else self._lib.silent_pyramid_u8_dev
+            self.ctx.check(fn(self.ctx.handle, self.plan.handle, _lib.byte_ptr(frames.data_ptr()),
                                                            self.batch, C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
             return
         self.ctx.check(self._lib.silent_pyramid_dev(self.ctx.handle, self.plan.handle, C.c_void_p(frames.data_ptr()),
@@ -650,7 +667,8 @@ class LineEndPipeline(object):
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         fn, fp = self._lib.silent_gray_keypoints_dev, p(frames)
         if self.frame_dtype == "uint8":
-            fn, fp = self._lib.silent_gray_keypoints_u8_dev, _lib.byte_ptr(frames.data_ptr())
+            fn = self._lib.silent_gray_keypoints_u8x3_dev if self._colour_frames else self._lib.silent_gray_keypoints_u8_dev
+            fp = _lib.byte_ptr(frames.data_ptr())
         self.ctx.check(fn(
             self.ctx.handle, self.plan.handle, fp, self.batch, C.c_void_p(self.consts["cs"].ctypes.data),
             C.c_void_p(self.consts["end"].ctypes.data), self.n_orient, self.clip_hi, p(self.pyr), p(self.cs), p(self.end), self.pad,
@@ -663,7 +681,8 @@ class LineEndPipeline(object):
         levels only, 2 = the filter of the remaining levels only (silent_gray_pass_parts_dev; the halves of an overlapped step)."""
         self._check_frames(frames)
         if self.frame_dtype == "uint8":    # the same pass reading the bytes as they are, either map storage
-            self.ctx.check(self._lib.silent_gray_pass_u8_dev(
+            fn = self._lib.silent_gray_pass_u8x3_dev if self._colour_frames else self._lib.silent_gray_pass_u8_dev
+            self.ctx.check(fn(
                 self.ctx.handle, self.plan.handle, _lib.byte_ptr(frames.data_ptr()), self.batch,
                 C.c_void_p(self.consts["cs"].ctypes.data), C.c_void_p(self.consts["end"].ctypes.data), self.n_orient,
                 self.clip_hi, C.c_void_p(self.pyr.data_ptr()), C.c_void_p(self.cs.data_ptr()), C.c_void_p(self.end.data_ptr()),
