@@ -1095,11 +1095,16 @@ SILENT_EXPORT int silent_rgb_keypoints(silent_ctx* ctx, const float* pyr, const 
               v = hs.out(value_out, b1), pv = hs.out(peak_value_out, b1),
               i = hs.out(idx, (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
               n = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
-    return hs.run([&] {
+    TRY(hs.run([&] {
         return silent_rgb_keypoints_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, p, top_percent, regions, hs.dev<float>(o),
                                         hs.dev<float>(l), hs.dev<float>(v), hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame,
                                         hs.dev<int64_t>(n), nullptr);
-    });
+    }));
+    // idx / counts as silent_max_value_indices_region: the host form reports an index buffer that was too small
+    for (int f = 0; f < n_frames; ++f)
+        if (counts[f] > (int64_t)cap_per_frame)
+            return fail(ctx, SILENT_E_CAPACITY, "silent_rgb_keypoints: cap_per_frame too small; counts hold the need");
+    return SILENT_OK;
 } catch (...) {
     return on_exception(ctx, "silent_rgb_keypoints");
 }
@@ -1330,10 +1335,15 @@ SILENT_EXPORT int silent_select_keypoints(silent_ctx* ctx, const float* color, c
     const int c = hs.in(color, bv * channels), v = hs.in(value, bv), pv = hs.out(peak_value_out, bv),
               i = hs.out(idx, (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
               n = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
-    return hs.run([&] {
+    TRY(hs.run([&] {
         return silent_select_keypoints_dev(ctx, hs.dev<float>(c), hs.dev<float>(v), levels, n_levels, n_frames, channels, top_percent,
                                            regions, hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame, hs.dev<int64_t>(n), nullptr);
-    });
+    }));
+    // idx / counts as silent_max_value_indices_region: the host form reports an index buffer that was too small
+    for (int f = 0; f < n_frames; ++f)
+        if (counts[f] > (int64_t)cap_per_frame)
+            return fail(ctx, SILENT_E_CAPACITY, "silent_select_keypoints: cap_per_frame too small; counts hold the need");
+    return SILENT_OK;
 } catch (...) {
     return on_exception(ctx, "silent_select_keypoints");
 }

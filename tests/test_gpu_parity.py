@@ -429,6 +429,34 @@ def test_max_value_indices_capacity_error(rt):
         rt.max_value_indices_region(v, [(8, 8)], cap_per_frame=10)
 
 
+def test_select_and_rgb_keypoints_host_forms_report_capacity(rt, kernels):
+    """include/silent_hip.h: idx / counts of silent_select_keypoints and silent_rgb_keypoints are those of
+    silent_max_value_indices_region -- the host form answers SILENT_E_CAPACITY when a count exceeds cap_per_frame, counts hold the need
+    and the first cap_per_frame rows are written (found by tests/test_gpu_write_coverage.py: both returned SILENT_OK)."""
+    import ctypes as C
+    from pysilent_amd import _lib
+    ctx, lib = rt.get_context(), _lib.load()
+    x = np.zeros((1, 16, 16, 3), np.float32)                    # every pixel of a black map is a keypoint: 256 rows
+    lv, rg = (_lib.Extent * 1)(_lib.Extent(16, 16)), (_lib.Extent * 1)(_lib.Extent(8, 8))
+    want, _ = rt.max_value_indices_region(x[..., :1], [(8, 8)])
+    fp = C.POINTER(C.c_float)
+    ks = {k: np.ascontiguousarray(kernels[k], np.float32) for k in ("rgc", "rgby", "stripe", "blur", "end")}
+    params = _lib.RgbChainParams(*[ks[k].ctypes.data_as(fp) for k in ("rgc", "rgby", "stripe", "blur", "end")], 1.0, 0.1, _lib.FLAT_ZERO, 255.0, 2)
+    line = np.empty(x.size, np.float32)
+    calls = {
+        "select": lambda idx, cap, counts: lib.silent_select_keypoints(ctx.handle, x.ctypes.data, None, lv, 1, 1, 3, C.c_double(0.1), rg, None,
+                                                                       idx.ctypes.data, cap, counts.ctypes.data),
+        "rgb": lambda idx, cap, counts: lib.silent_rgb_keypoints(ctx.handle, x.ctypes.data, lv, 1, 1, C.byref(params), C.c_double(0.1), rg, None,
+                                                                 line.ctypes.data, None, None, idx.ctypes.data, cap, counts.ctypes.data),
+    }
+    for name, call in calls.items():
+        for cap, status in ((256, _lib.SILENT_OK), (10, _lib.SILENT_E_CAPACITY)):
+            idx, counts = np.full((1, cap, 4), -1, np.int64), np.zeros(1, np.int64)
+            assert call(idx, cap, counts) == status, (name, cap, _lib.last_error(ctx.handle))
+            assert counts[0] == 256, (name, cap)
+            np.testing.assert_array_equal(idx[0], want[0, :cap], err_msg="%s cap %d" % (name, cap))
+
+
 # ----------------------------------------------------------------------------- centroids (SURVEY 8f rank 1)
 
 @pytest.mark.parametrize("shape,region", [((2, 192, 288, 1), [1, 3, 3]), ((1, 37, 53, 1), [1, 3, 3]),
