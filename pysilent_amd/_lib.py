@@ -191,6 +191,30 @@ def byte_ptr(address):
     return None if address is None else C.cast(C.c_void_p(int(address)), _bp)
 
 
+def void_ptr(address):
+    """A host or device address as a void* / float* argument (None: NULL)."""
+    return None if address is None else C.c_void_p(int(address))
+
+
+def gray_entry(family, frame_dtype="float32", frame_channels=1, storage="float32", dev=False, parts=None):
+    """The call shape of the gray pass ("gray_pass") or its keypoint form ("gray_keypoints") for a frame layout, a map storage and the
+    host or _dev form: (name, frame_ptr, map_ptr, tail) -- the entry point silent_<name>[_dev], what makes its frames argument and its
+    cs_out / end_out arguments from an address, and the arguments that follow end_out (maps_f16, parts) before the stream.  parts:
+    None = the whole pass; 1 / 2 / 3 = the halves of an overlapped step (_dev forms)."""
+    sfx = "" if frame_dtype != "uint8" else "_u8x3" if frame_channels == 3 else "_u8"
+    frame_ptr = byte_ptr if sfx else void_ptr
+    if family != "gray_pass":
+        return family + sfx, frame_ptr, void_ptr, ()
+    parts_arg = (3 if parts is None else int(parts),) if dev else ()
+    if sfx:
+        return family + sfx, frame_ptr, void_ptr, (int(storage == "float16"),) + parts_arg
+    if storage == "float16":
+        return family + "_h", frame_ptr, half_ptr, parts_arg
+    if dev and parts is not None:
+        return family + "_parts", frame_ptr, void_ptr, parts_arg
+    return family, frame_ptr, void_ptr, ()
+
+
 def _preload_hip_runtime():
     """One HIP runtime per process.  PyTorch-ROCm wheels bundle their own libamdhip64.so with the same
     SONAME as /opt/rocm's; if torch is installed, load ITS copy first (by path, RTLD_GLOBAL) so that our

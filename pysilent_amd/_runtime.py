@@ -842,7 +842,7 @@ class PyramidPlan(object):
     @staticmethod
     def _entry(name, frame_dtype, frame_channels):
         """The entry point family of a frame layout: silent_<name>, silent_<name>_u8 or silent_<name>_u8x3."""
-        return name + ("_u8x3" if frame_channels == 3 else "_u8" if frame_dtype == "uint8" else "")
+        return _lib.gray_entry(name, frame_dtype, frame_channels)[0]
 
     def run(self, frames, frame_dtype="float32", frame_channels=1):
         """frames: [n, H, W, C] ndarray (host) or torch GPU tensor.  Returns a PackedPyramid.  frame_dtype="uint8" (single-channel
@@ -891,25 +891,12 @@ class PyramidPlan(object):
         K = eb.shape[3]
         op = self._frames(frames, frame_dtype, frame_channels)
         n = op.n_frames
-        if frame_dtype == "uint8":
-            dt = np.float16 if storage == "float16" else np.float32
-            pyr, pp = op.empty(n * self.frame_px)
-            (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch, dt) for ch in (1, K)]
-            args = (self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi), pp, cp, ep,
-                    1 if storage == "float16" else 0)
-            op.call(self._entry("gray_pass", frame_dtype, frame_channels), *(args + ((3,) if op.dev else ())))
-        elif storage == "float16":
-            pyr, pp = op.empty(n * self.frame_px)
-            (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch, np.float16) for ch in (1, K)]
-            args = (self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi), pp,
-                    _lib.half_ptr(cp.value), _lib.half_ptr(ep.value))
-            op.call("gray_pass_h", *(args + ((3,) if op.dev else ())))
-            dt = np.float16
-        else:
-            (pyr, pp), (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch) for ch in (1, 1, K)]
-            op.call("gray_pass", self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi),
-                    pp, cp, ep)
-            dt = np.float32
+        name, _, map_ptr, tail = _lib.gray_entry("gray_pass", frame_dtype, frame_channels, storage, op.dev)
+        dt = np.float16 if storage == "float16" else np.float32
+        pyr, pp = op.empty(n * self.frame_px)
+        (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch, dt) for ch in (1, K)]
+        op.call(name, self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi), pp,
+                map_ptr(cp.value), map_ptr(ep.value), *tail)
         P = PackedPyramid
         return P(pyr, self.extents, 1, n), P(cso, self.extents, 1, n, dtype=dt), P(endo, self.extents, K, n, dtype=dt)
 

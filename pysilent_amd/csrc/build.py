@@ -98,23 +98,48 @@ def build(force=False, verbose=False, out=OUT, defines=()):
     return out
 
 
+# the host side under the sanitizers: no GPU code, kernel launches compiled out (silent_host_shim.h)
+HOST_ASAN_FLAGS = ["--offload-host-only", "-cuid=silenthost", "-DSILENT_HOST_ONLY", "-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17",
+                   "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wno-unused-parameter",
+                   "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
+# tests/gray_bytes_host_main.cpp, once per frame type: the entry-point suffix and the bytes of one frame pixel
+HOST_DRIVERS = {"u8": ["-DSILENT_SFX=_u8", "-DSILENT_FRAME_BYTES=1"], "u8x3": ["-DSILENT_SFX=_u8x3", "-DSILENT_FRAME_BYTES=3"],
+                "f32": ["-DSILENT_FRAME_BYTES=4"]}
+
+
+def _fresh(out, dep):
+    """True when `out` exists and none of the files its compilation read (dependency file `dep`) is newer."""
+    deps = _deps(dep) if os.path.exists(out) else None
+    return deps is not None and all(os.path.exists(d) and os.path.getmtime(d) <= os.path.getmtime(out) for d in deps)
+
+
 def build_host_asan(force=False):
     """The host code of the library without a GPU behind it (kernel launches compiled out, device memory = host memory), with
     AddressSanitizer + UndefinedBehaviorSanitizer, as ONE translation unit (silent_unity.hip includes the six).  Never loaded by
     the product; tests/test_sanitizers.py runs it in a python started with LD_PRELOAD=<clang's asan runtime>."""
     dep = os.path.join(HERE, "build", "hostonly_asan.d")
     os.makedirs(os.path.dirname(dep), exist_ok=True)
-    if not force and os.path.exists(HOST_ASAN_OUT):
-        deps = _deps(dep)
-        if deps is not None and all(os.path.exists(d) and os.path.getmtime(d) <= os.path.getmtime(HOST_ASAN_OUT) for d in deps):
-            return HOST_ASAN_OUT
+    if not force and _fresh(HOST_ASAN_OUT, dep):
+        return HOST_ASAN_OUT
     os.makedirs(os.path.dirname(HOST_ASAN_OUT), exist_ok=True)
-    cmd = [hipcc(), "--offload-host-only", "-cuid=silenthost", "-DSILENT_HOST_ONLY", "-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17", "-fPIC",
-           "-shared", "-fvisibility=hidden", "-ffp-contract=off", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=undefined", "-shared-libsan", "-Wl,-Bsymbolic", "-Wno-unused-parameter", "-Wno-unused-variable",
-           "-Wno-unused-but-set-variable", "-MMD", "-MF", dep, "-o", HOST_ASAN_OUT, os.path.join(HERE, "silent_unity.hip")]
-    subprocess.check_call(cmd)
+    subprocess.check_call([hipcc()] + HOST_ASAN_FLAGS + ["-fPIC", "-shared", "-fvisibility=hidden", "-shared-libsan", "-Wl,-Bsymbolic", "-MMD",
+                                                         "-MF", dep, "-o", HOST_ASAN_OUT, os.path.join(HERE, "silent_unity.hip")])
     return HOST_ASAN_OUT
+
+
+def build_host_driver(family, force=False):
+    """tests/gray_bytes_host_main.cpp + the library's host side as one stand-alone executable under the same sanitizers (the runtime
+    is linked in: it is run as a child process, nothing of it is loaded into Python), for one frame type of HOST_DRIVERS.  Returns the
+    path of the executable, build/gray_host_<family>; rebuilt when a file it was compiled from is newer."""
+    exe = os.path.join(HERE, "build", "gray_host_" + family)
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    if force or not _fresh(exe, exe + ".d"):
+        cmd = [hipcc()] + HOST_ASAN_FLAGS + HOST_DRIVERS[family] + ["-MMD", "-MF", exe + ".d", "-o", exe,
+                                                                    os.path.join(os.path.dirname(PKG), "tests", "gray_bytes_host_main.cpp")]
+        c = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if c.returncode != 0:
+            raise RuntimeError("hipcc failed on the host driver (%s):\n%s" % (family, c.stdout[-4000:]))
+    return exe
 
 
 def asan_runtime():

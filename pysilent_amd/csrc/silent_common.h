@@ -164,6 +164,12 @@ template <typename FT>
 constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT>;
 template <typename FT>
 constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT>;
+// (host) the bytes of one frame pixel as the host-pointer forms stage it -- float frames carry the channels of the plan -- and the
+// suffix of a frame type's entry points
+template <typename FT>
+constexpr size_t frame_px_bytes(int plan_channels) { return kFrameRgb8<FT> ? 3 : kFrameBytes<FT> ? 1 : 4 * (size_t)plan_channels; }
+template <typename FT>
+constexpr const char* kFrameSuffix = kFrameRgb8<FT> ? "_u8x3" : kFrameBytes<FT> ? "_u8" : "";
 
 // Stream row i of the column `col` (level coordinates, mirrored inside the crop like every tap; px_stride floats per pixel) in lane i: ONE load per tile
 // for the sixth taps of a wave's last smoothing lane; row i is read back with unit_edge(xcol, i).

@@ -813,13 +813,17 @@ SILENT_EXPORT int silent_rgb_keypoints_dev(silent_ctx* ctx, const float* pyr, co
 // of the sparse tail and the NaN flags, or written as a map -- the end map is never read back for a reduction.  selection = 1:
 // a-10 -> a-9 -> a-8 -> a-11 on (pad_inwards(end), value) with K channels, sparse like silent_rgb_keypoints (SILENT_TUNE_GRAY bit 6:
 // the dense kernels for every level); selection = 0: a-11 on the value map (recognition_testing.py:90).
-static int gray_keypoints_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const void* frames, int n_frames,
-                                 const float* cs_kernel, const float* end_bank, int n_orient, float* pyr, float* end_out, int pad,
+// (everything the *_dev form refuses, before a launch and, in the host forms, before the batch is staged.)  FT: the frame element type
+// -- float, uint8_t (silent_gray_keypoints_u8[_dev]) or FrameRgb8 (silent_gray_keypoints_u8x3[_dev])
+template <typename FT>
+static int gray_keypoints_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames,
+                                 const float* cs_kernel, const float* end_bank, int n_orient, const void* pyr, const void* end_out, int pad,
                                  int selection, const silent_extent* regions, float* peak_value_out, int64_t* idx,
                                  size_t cap_per_frame, int64_t* counts) {
     if (!plan || !frames || !pyr || !cs_kernel || !end_bank || !end_out || !regions || !counts || (!idx && cap_per_frame))
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
+    if constexpr (kFrameNarrow<FT>) TRY(check_narrow_frames(ctx, who, plan));
     if (plan->tab.C != 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": the plan must be single-channel");
     if (n_orient != 3 && n_orient != 4 && n_orient != 8)
         return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": n_orient must be 3, 4 or 8");
@@ -831,30 +835,13 @@ static int gray_keypoints_checks(silent_ctx* ctx, const char* who, const silent_
     return SILENT_OK;
 }
 
-// FT: the frame element type -- float, uint8_t (silent_gray_keypoints_u8[_dev]) or FrameRgb8 (silent_gray_keypoints_u8x3[_dev]); the
-// uint8 kinds: single-channel float32-accumulation plans
-static int gray_pass_kp_any(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames, const float* cs_kernel,
-                            const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const GrayKp& kp,
-                            hipStream_t s) {
-    return gray_pass_kp(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s);
-}
-static int gray_pass_kp_any(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, const float* cs_kernel,
-                            const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const GrayKp& kp,
-                            hipStream_t s) {
-    return gray_pass_kp_u8(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s);
-}
-static int gray_pass_kp_any(silent_ctx* ctx, const silent_pyramid_plan* plan, const FrameRgb8* frames, int n_frames, const float* cs_kernel,
-                            const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const GrayKp& kp,
-                            hipStream_t s) {
-    return gray_pass_kp_u8x3(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s);
-}
-
 template <typename FT>
-static int gray_keypoints_dev(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames,
+static int gray_keypoints_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames,
                               const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
                               float* cs_out, float* end_out, int pad, int selection, double top_percent,
                               const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
                               size_t cap_per_frame, int64_t* counts, silent_stream stream) {
+    const char* who = entry_name<FT>(kGrayKeypoints);
     TRY(gray_keypoints_checks(ctx, who, plan, frames, n_frames, cs_kernel, end_bank, n_orient, pyr, end_out, pad, selection, regions,
                               peak_value_out, idx, cap_per_frame, counts));
     hipStream_t s = (hipStream_t)stream;
@@ -871,7 +858,7 @@ static int gray_keypoints_dev(silent_ctx* ctx, const char* who, const silent_pyr
         RegionPlan rp;
         TRY(region_prepare(ctx, who, levels, n_levels, n_frames, regions, map_bytes, s, &rp));
         kp.value_out = value_out ? value_out : (float*)ctx->ws.p;
-        TRY(gray_pass_kp_any(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s));
+        TRY(gray_pass_kp(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s));
         return region_run(ctx, who, kp.value_out, levels, n_levels, n_frames, rp, idx, cap_per_frame, counts, s);
     }
     // The summary groups are kSumRows rows of a tile row; one SumTab geometry serves all levels, so both filter kernels must tile
@@ -889,7 +876,7 @@ static int gray_keypoints_dev(silent_ctx* ctx, const char* who, const silent_pyr
         kp.gpt = sp.st.gpt;
         for (int l = 0; l < n_levels; ++l) kp.sum_off[l] = sp.st.off[l];
     }
-    TRY(gray_pass_kp_any(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s));
+    TRY(gray_pass_kp(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s));
     ctx->sparse_ran = sparse;
     ctx->sparse_stream = s;
     ctx->sparse_flags_off = (size_t)((char*)sp.w.dense_flags - (char*)ctx->ws.p);
@@ -901,29 +888,24 @@ static int gray_keypoints_dev(silent_ctx* ctx, const char* who, const silent_pyr
 }
 
 SILENT_EXPORT int silent_gray_keypoints_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
-                                            const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
-                                            float* cs_out, float* end_out, int pad, int selection, double top_percent,
-                                            const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-                                            size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
+        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
+        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+        size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
     NEED_CTX(ctx);
-    return gray_keypoints_dev(ctx, "silent_gray_keypoints", plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out,
-                              end_out, pad, selection, top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
+    return gray_keypoints_dev(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
+                              top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_dev");
 }
 
 // uint8 frames, read as they are (silent_hip.h): every output is silent_gray_keypoints_dev's on the widened frames
 SILENT_EXPORT int silent_gray_keypoints_u8_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
-                                               const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
-                                               float* cs_out, float* end_out, int pad, int selection, double top_percent,
-                                               const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-                                               size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
+        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
+        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+        size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
     NEED_CTX(ctx);
-    const char* who = "silent_gray_keypoints_u8";
-    if (plan && plan->ctx == ctx && plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
-    if (plan && plan->ctx == ctx && plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
-    return gray_keypoints_dev(ctx, who, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out,
-                              end_out, pad, selection, top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
+    return gray_keypoints_dev(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
+                              top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u8_dev");
 }
@@ -931,16 +913,12 @@ SILENT_EXPORT int silent_gray_keypoints_u8_dev(silent_ctx* ctx, const silent_pyr
 // interleaved 3-channel uint8 frames [n, H, W, 3], read as they are (silent_hip.h): every output is silent_gray_keypoints_dev's on
 // the frame of values (b0 + b1 + b2) * float32(1/3)
 SILENT_EXPORT int silent_gray_keypoints_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
-                                               const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
-                                               float* cs_out, float* end_out, int pad, int selection, double top_percent,
-                                               const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-                                               size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
+        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
+        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+        size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
     NEED_CTX(ctx);
-    const char* who = "silent_gray_keypoints_u8x3";
-    if (plan && plan->ctx == ctx && plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
-    if (plan && plan->ctx == ctx && plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
-    return gray_keypoints_dev(ctx, who, plan, reinterpret_cast<const FrameRgb8*>(frames), n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out,
-                              end_out, pad, selection, top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
+    return gray_keypoints_dev(ctx, plan, rgb8(frames), n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
+                              top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u8x3_dev");
 }
@@ -1109,101 +1087,63 @@ SILENT_EXPORT int silent_rgb_keypoints(silent_ctx* ctx, const float* pyr, const 
     return on_exception(ctx, "silent_rgb_keypoints");
 }
 
-SILENT_EXPORT int silent_gray_keypoints(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
-                                        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
-                                        float* cs_out, float* end_out, int pad, int selection, double top_percent,
-                                        const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-                                        size_t cap_per_frame, int64_t* counts) try {
-    NEED_CTX(ctx);
-    const char* who = "silent_gray_keypoints";
+// the host-pointer forms of silent_gray_keypoints on any frame type: the frames are staged as they are (frame_px_bytes each pixel)
+template <typename FT>
+static int gray_keypoints_host(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames, const float* cs_kernel,
+                               const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
+                               int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out,
+                               int64_t* idx, size_t cap_per_frame, int64_t* counts) {
+    const char* who = entry_name<FT>(kGrayKeypoints);
     // (the host form accepts NULL pyr / end_out: the *_dev form needs both maps, they then live in the staging arena)
-    if (!plan || !frames) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    TRY(gray_keypoints_checks(ctx, who, plan, frames, n_frames, cs_kernel, end_bank, n_orient, (float*)frames, (float*)frames, pad,
-                              selection, regions, peak_value_out, idx, cap_per_frame, counts));
+    TRY(gray_keypoints_checks(ctx, who, plan, frames, n_frames, cs_kernel, end_bank, n_orient, frames, frames, pad, selection, regions,
+                              peak_value_out, idx, cap_per_frame, counts));
     HostStage hs(ctx);
     const size_t b1 = (size_t)plan->tab.frame_px_out * n_frames * 4;
-    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * plan->tab.C * 4 * n_frames),
+    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * frame_px_bytes<FT>(plan->tab.C) * n_frames),
               p = pyr ? hs.out(pyr, b1) : hs.scratch(b1), cs = hs.out(cs_out, b1),
               end = end_out ? hs.out(end_out, b1 * n_orient) : hs.scratch(b1 * n_orient), v = hs.out(value_out, b1),
               pv = hs.out(peak_value_out, b1), i = hs.out(idx, (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
               n = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
     TRY(hs.run([&] {
-        return silent_gray_keypoints_dev(ctx, plan, hs.dev<float>(x), n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
-                                         hs.dev<float>(cs), hs.dev<float>(end), pad, selection, top_percent, regions, hs.dev<float>(v),
-                                         hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame, hs.dev<int64_t>(n), nullptr);
+        return gray_keypoints_dev(ctx, plan, hs.dev<FT>(x), n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
+                                  hs.dev<float>(cs), hs.dev<float>(end), pad, selection, top_percent, regions, hs.dev<float>(v),
+                                  hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame, hs.dev<int64_t>(n), nullptr);
     }));
     for (int f = 0; f < n_frames; ++f)
         if (counts[f] > (int64_t)cap_per_frame)
             return fail(ctx, SILENT_E_CAPACITY, std::string(who) + ": cap_per_frame too small; counts hold the need");
     return SILENT_OK;
+}
+
+SILENT_EXPORT int silent_gray_keypoints(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
+        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
+        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+        size_t cap_per_frame, int64_t* counts) try {
+    NEED_CTX(ctx);
+    return gray_keypoints_host(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
+                               top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints");
 }
 
-// uint8 frames (staged as H * W * n BYTES)
 SILENT_EXPORT int silent_gray_keypoints_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
-                                        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
-                                        float* cs_out, float* end_out, int pad, int selection, double top_percent,
-                                        const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-                                        size_t cap_per_frame, int64_t* counts) try {
+        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
+        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+        size_t cap_per_frame, int64_t* counts) try {
     NEED_CTX(ctx);
-    const char* who = "silent_gray_keypoints_u8";
-    // (the host form accepts NULL pyr / end_out: the *_dev form needs both maps, they then live in the staging arena)
-    if (!plan || !frames) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    if (plan->ctx == ctx && plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
-    if (plan->ctx == ctx && plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
-    TRY(gray_keypoints_checks(ctx, who, plan, frames, n_frames, cs_kernel, end_bank, n_orient, (float*)(void*)frames, (float*)(void*)frames, pad,
-                              selection, regions, peak_value_out, idx, cap_per_frame, counts));
-    HostStage hs(ctx);
-    const size_t b1 = (size_t)plan->tab.frame_px_out * n_frames * 4;
-    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * n_frames)   /* bytes */,
-              p = pyr ? hs.out(pyr, b1) : hs.scratch(b1), cs = hs.out(cs_out, b1),
-              end = end_out ? hs.out(end_out, b1 * n_orient) : hs.scratch(b1 * n_orient), v = hs.out(value_out, b1),
-              pv = hs.out(peak_value_out, b1), i = hs.out(idx, (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
-              n = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
-    TRY(hs.run([&] {
-        return silent_gray_keypoints_u8_dev(ctx, plan, hs.dev<uint8_t>(x), n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
-                                         hs.dev<float>(cs), hs.dev<float>(end), pad, selection, top_percent, regions, hs.dev<float>(v),
-                                         hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame, hs.dev<int64_t>(n), nullptr);
-    }));
-    for (int f = 0; f < n_frames; ++f)
-        if (counts[f] > (int64_t)cap_per_frame)
-            return fail(ctx, SILENT_E_CAPACITY, std::string(who) + ": cap_per_frame too small; counts hold the need");
-    return SILENT_OK;
+    return gray_keypoints_host(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
+                               top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u8");
 }
 
-// interleaved 3-channel uint8 frames (staged as 3 * H * W * n BYTES)
 SILENT_EXPORT int silent_gray_keypoints_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
-                                        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
-                                        float* cs_out, float* end_out, int pad, int selection, double top_percent,
-                                        const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-                                        size_t cap_per_frame, int64_t* counts) try {
+        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
+        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+        size_t cap_per_frame, int64_t* counts) try {
     NEED_CTX(ctx);
-    const char* who = "silent_gray_keypoints_u8x3";
-    // (the host form accepts NULL pyr / end_out: the *_dev form needs both maps, they then live in the staging arena)
-    if (!plan || !frames) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    if (plan->ctx == ctx && plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
-    if (plan->ctx == ctx && plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
-    TRY(gray_keypoints_checks(ctx, who, plan, frames, n_frames, cs_kernel, end_bank, n_orient, (float*)(void*)frames, (float*)(void*)frames, pad,
-                              selection, regions, peak_value_out, idx, cap_per_frame, counts));
-    HostStage hs(ctx);
-    const size_t b1 = (size_t)plan->tab.frame_px_out * n_frames * 4;
-    const int x = hs.in(frames, (size_t)3 * plan->tab.H * plan->tab.W * n_frames)   /* bytes */,
-              p = pyr ? hs.out(pyr, b1) : hs.scratch(b1), cs = hs.out(cs_out, b1),
-              end = end_out ? hs.out(end_out, b1 * n_orient) : hs.scratch(b1 * n_orient), v = hs.out(value_out, b1),
-              pv = hs.out(peak_value_out, b1), i = hs.out(idx, (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
-              n = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
-    TRY(hs.run([&] {
-        return silent_gray_keypoints_u8x3_dev(ctx, plan, hs.dev<uint8_t>(x), n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
-                                         hs.dev<float>(cs), hs.dev<float>(end), pad, selection, top_percent, regions, hs.dev<float>(v),
-                                         hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame, hs.dev<int64_t>(n), nullptr);
-    }));
-    for (int f = 0; f < n_frames; ++f)
-        if (counts[f] > (int64_t)cap_per_frame)
-            return fail(ctx, SILENT_E_CAPACITY, std::string(who) + ": cap_per_frame too small; counts hold the need");
-    return SILENT_OK;
+    return gray_keypoints_host(ctx, plan, rgb8(frames), n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
+                               top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u8x3");
 }

@@ -37,22 +37,120 @@ struct silent_pyramid_plan {
     silent::BorderTab walk_border{};             // union plans: the inner levels' border outputs (pyramid_border_kernel); n = 0: none
 };
 
-// (silent_pyramid_api.hip) with_unit: also the unit levels (the gray pass produces them itself); with_region: also the general levels
-int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const float* frames, int n_frames, float* pyr,
+// ------------------------------------------------------------------------------------------ shared by the entry points
+// `who` of an entry-point family on a frame type: silent_pyramid_u8x3, silent_gray_pass_h, ...  (float16 storage has a name of its own
+// for float frames only: the *_u8 / *_u8x3 forms take it as an argument)
+enum { kPyramid, kGrayPass, kGrayPassH, kGrayKeypoints };
+template <typename FT>
+const char* entry_name(int family) {
+    static const std::string sfx = silent::kFrameSuffix<FT>;
+    static const std::string names[4] = {"silent_pyramid" + sfx, "silent_gray_pass" + sfx, "silent_gray_pass" + (silent::kFrameNarrow<FT> ? sfx : "_h"),
+                                         "silent_gray_keypoints" + sfx};
+    return names[family].c_str();
+}
+inline const silent::FrameRgb8* rgb8(const uint8_t* frames) { return reinterpret_cast<const silent::FrameRgb8*>(frames); }
+
+// the uint8 frame kinds / float16 storage exist for single-channel plans with float32 accumulation only (plan: not NULL)
+inline int check_narrow_frames(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan) {
+    if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
+    if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
+    return SILENT_OK;
+}
+inline int check_half_storage(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan) {
+    if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": float16 storage is for single-channel plans");
+    if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": float16 storage with a SILENT_PLAN_ACCUM_F64 plan");
+    return SILENT_OK;
+}
+inline int check_gray_outputs(silent_ctx* ctx, const char* who, const void* cs_out, const void* end_out, const float* end_bank, int n_orient) {
+    if (!cs_out && !end_out) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": both outputs are NULL");
+    if (end_out && !end_bank) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": end_bank is NULL");
+    if (n_orient != 3 && n_orient != 4 && n_orient != 8)
+        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": n_orient must be 3, 4 or 8");
+    return SILENT_OK;
+}
+
+// the weights of the CS and end kernels as a kernel argument (end_bank may be NULL when no end map is written)
+inline silent::GrayW gray_weights(const float* cs_kernel, const float* end_bank, int n_orient) {
+    silent::GrayW w;
+    std::memset(&w, 0, sizeof(w));
+    std::memcpy(w.cs, cs_kernel, sizeof(float) * 9);
+    if (end_bank) std::memcpy(w.end, end_bank, sizeof(float) * 9 * n_orient);
+    return w;
+}
+// The table of the fused / stream kernels (they take its FusedTab part, the F64 kernels all of it): the frame and the unit taps of the
+// plan -- every unit level has the same ([1,26,66,26,1]/120 and the sixth, 2^-53) --, no level yet; fused_add_level appends unit level
+// l of the plan, its tiles behind those of the levels before it.
+inline silent::FusedTab64 fused_tab(const silent_pyramid_plan* plan) {
+    silent::FusedTab64 ft;
+    std::memset(&ft, 0, sizeof(ft));
+    for (int j = 0; j < 6; ++j) {
+        ft.wx[j] = ft.wy[j] = plan->unit_w[j];
+        ft.w64[j] = plan->unit_w64[j];
+    }
+    ft.H = plan->tab.H;
+    ft.W = plan->tab.W;
+    ft.frame_px = plan->tab.frame_px_out;
+    return ft;
+}
+inline void fused_add_level(silent::FusedTab64& ft, const silent::PyrTab& pt, int l) {
+    const silent::PyrLevelDev& d = pt.lv[l];
+    silent::FusedLevel& f = ft.lv[ft.n++];
+    f.src_y0 = d.src_y0; f.src_x0 = d.src_x0; f.src_h = d.src_h; f.src_w = d.src_w;
+    f.zoom_h = d.zoom_h; f.zoom_w = d.zoom_w; f.out_h = d.out_h; f.out_w = d.out_w;
+    f.tiles_x = (d.out_w + silent::kFusedTW - 1) / silent::kFusedTW;
+    f.tile_start = ft.tiles_per_frame;
+    f.px_off = pt.px_off[l];
+    ft.tiles_per_frame += f.tiles_x * ((d.out_h + silent::kFusedTH - 1) / silent::kFusedTH);
+}
+
+// ------------------------------------------------------------------------------------------ kernel dispatch
+// Which instantiations of the gray kernels exist: float16 storage (ST = gray_half) has no keypoint epilogue and no float64 accumulation,
+// the uint8 frame kinds no float64 accumulation (the entry points refuse those combinations before a launch).
+template <bool KP, bool F64, typename ST, typename FT>
+constexpr bool kGrayKernel = !(silent::kStoreHalf<ST> && (KP || F64)) && !(silent::kFrameNarrow<FT> && F64);
+// f(KP, F64) with the run-time (kp, f64) as std::bool_constant's; a combination without kernels is never instantiated (nor reached)
+template <typename ST, typename FT, class F>
+void with_gray_mode(bool kp, bool f64, F&& f) {
+    auto go = [&](auto KP, auto F64) {
+        if constexpr (kGrayKernel<decltype(KP)::value, decltype(F64)::value, ST, FT>) f(KP, F64);
+    };
+    if (kp && f64) go(std::true_type{}, std::true_type{});
+    else if (kp) go(std::true_type{}, std::false_type{});
+    else if (f64) go(std::false_type{}, std::true_type{});
+    else go(std::false_type{}, std::false_type{});
+}
+// f(K) with n_orient (3, 4 or 8: checked by the caller) as a std::integral_constant
+template <class F>
+void with_orient(int n_orient, F&& f) {
+    if (n_orient == 3) f(std::integral_constant<int, 3>{});
+    else if (n_orient == 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
+}
+// f(G, L): the general levels and the slot layout the stream kernels of a plan are instantiated for
+template <class F>
+void with_stream_layout(const silent_pyramid_plan* plan, F&& f) {
+    using std::integral_constant;
+    if (plan->stream_layout == 1) f(integral_constant<int, 7>{}, integral_constant<int, 1>{});   // zoom ladders of ratio 1.4 .. e^.5: five rows of the first level in flight
+    else if (plan->stream.G <= 4) f(integral_constant<int, 4>{}, integral_constant<int, 0>{});
+    else f(integral_constant<int, 7>{}, integral_constant<int, 0>{});
+}
+
+// (silent_pyramid_api.hip) FT: the frame element type -- float, or unsigned char / silent::FrameRgb8 (uint8 frames, one channel /
+// interleaved colour, its value formed at the load: single-channel plans without SILENT_PLAN_ACCUM_F64; anything else is refused).
+// with_unit: also the unit levels (the gray pass produces them itself); with_region: also the general levels
+template <typename FT>
+int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames, float* pyr,
                    hipStream_t s, bool with_unit, bool with_region = true);
-// the same on uint8 frames (single-channel plans without SILENT_PLAN_ACCUM_F64; anything else is refused)
-int launch_pyramid_u8(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, float* pyr,
-                      hipStream_t s, bool with_unit, bool with_region = true);
-// the same on interleaved 3-channel uint8 frames (silent::FrameRgb8: one colour pixel, its value formed at the load); the same refusals
-int launch_pyramid_u8x3(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const silent::FrameRgb8* frames, int n_frames,
-                        float* pyr, hipStream_t s, bool with_unit, bool with_region = true);
 // (silent_gray_api.hip) silent_gray_pass_dev with the keypoint epilogue (silent_gray.h, GrayKp) in every kernel that writes `end`
-int gray_pass_kp(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames, const float* cs_kernel,
+template <typename FT>
+int gray_pass_kp(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames, const float* cs_kernel,
                  const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const silent::GrayKp& kp,
                  hipStream_t s);
-int gray_pass_kp_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, const float* cs_kernel,
-                    const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const silent::GrayKp& kp,
-                    hipStream_t s);
-int gray_pass_kp_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent::FrameRgb8* frames, int n_frames,
-                      const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out,
-                      const silent::GrayKp& kp, hipStream_t s);
+// (each is defined, and instantiated for the three frame types, in its unit)
+#define SILENT_FRAME_TYPES(X) X(float) X(unsigned char) X(silent::FrameRgb8)
+#define X(FT)                                                                                                                              \
+    extern template int launch_pyramid<FT>(silent_ctx*, const char*, const silent_pyramid_plan*, const FT*, int, float*, hipStream_t, bool, bool); \
+    extern template int gray_pass_kp<FT>(silent_ctx*, const silent_pyramid_plan*, const FT*, int, const float*, const float*, int, float, float*, \
+                                         float*, float*, const silent::GrayKp&, hipStream_t);
+SILENT_FRAME_TYPES(X)
+#undef X

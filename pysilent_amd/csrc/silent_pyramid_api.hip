@@ -643,18 +643,20 @@ static bool walk3_plan(const silent_ctx* ctx, const silent_pyramid_plan* plan, i
     return true;
 }
 
-// FT: the frame element type -- float, or unsigned char / FrameRgb8 (uint8 frames, one channel / interleaved colour: single-channel
-// plans with float32 accumulation only)
+// everything silent_pyramid*_dev refuses, before a launch (and, in the host forms, before the batch is staged)
 template <typename FT>
-static int launch_pyramid_t(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames,
-                            int n_frames, float* pyr, hipStream_t s, bool with_unit, bool with_region) {
+static int pyramid_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames, const float* pyr) {
     if (!plan || !frames || !pyr) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
     if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
-    if constexpr (kFrameNarrow<FT>) {
-        if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
-        if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
-    }
+    if constexpr (kFrameNarrow<FT>) TRY(check_narrow_frames(ctx, who, plan));
+    return SILENT_OK;
+}
+
+template <typename FT>
+int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames, float* pyr,
+                   hipStream_t s, bool with_unit, bool with_region) {
+    TRY(pyramid_checks(ctx, who, plan, frames, n_frames, pyr));
     const PyrTab& tab = plan->tab;
     const long long b_unit = with_unit ? (long long)tab.unit_tiles_per_frame * n_frames : 0;
     const long long b_region = (with_region && tab.n_general) ? (long long)tab.regions_x * tab.regions_y * n_frames : 0;
@@ -666,37 +668,17 @@ static int launch_pyramid_t(silent_ctx* ctx, const char* who, const silent_pyram
     if (plan->stream_ok && with_unit && with_region && !(kopts & 1u)) {
         // single-read pyramid: frame -> every level in one kernel (pyramid_stream_kernel; single-channel plans only:
         // on interleaved RGB the stride-3 accesses of the same kernel made it 1.5x SLOWER than unit + region kernels)
-        const PyrLevelDev& d = tab.lv[plan->stream_unit_level];
-        FusedTab64 ft;   // (the float32 kernels take its FusedTab part)
-        std::memset(&ft, 0, sizeof(ft));
-        ft.n = 1;
-        for (int j = 0; j < 6; ++j) ft.wx[j] = ft.wy[j] = plan->unit_w[j];
-        for (int j = 0; j < 6; ++j) ft.w64[j] = plan->unit_w64[j];
-        FusedLevel& f = ft.lv[0];
-        f.src_y0 = d.src_y0; f.src_x0 = d.src_x0; f.src_h = d.src_h; f.src_w = d.src_w;
-        f.zoom_h = d.zoom_h; f.zoom_w = d.zoom_w; f.out_h = d.out_h; f.out_w = d.out_w;
-        f.tiles_x = (d.out_w + kFusedTW - 1) / kFusedTW;
-        f.px_off = tab.px_off[plan->stream_unit_level];
-        ft.tiles_per_frame = f.tiles_x * ((d.out_h + kFusedTH - 1) / kFusedTH);
-        ft.H = tab.H;
-        ft.W = tab.W;
-        ft.frame_px = tab.frame_px_out;
+        FusedTab64 ft = fused_tab(plan);
+        fused_add_level(ft, tab, plan->stream_unit_level);
         const long long blocks = (long long)ft.tiles_per_frame * n_frames;
         if (blocks > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many tiles for one launch");
-#define PYR_STREAM(G_, L_)                                                                                                                 \
-    if constexpr (kFrameNarrow<FT>)                                                                                                        \
-        hipLaunchKernelGGL((pyramid_stream_kernel<1, G_, L_, false, FT>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, \
-                           static_cast<const FusedTab&>(ft), plan->stream);                                                                \
-    else if (plan->f64)                                                                                                                    \
-        hipLaunchKernelGGL((pyramid_stream_kernel<1, G_, L_, true>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, ft, \
-                           plan->stream);                                                                                                  \
-    else                                                                                                                                   \
-        hipLaunchKernelGGL((pyramid_stream_kernel<1, G_, L_>), dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr,          \
-                           static_cast<const FusedTab&>(ft), plan->stream)
-        if (plan->stream_layout == 1) { PYR_STREAM(7, 1); }
-        else if (plan->stream.G <= 4) { PYR_STREAM(4, 0); }
-        else { PYR_STREAM(7, 0); }
-#undef PYR_STREAM
+        with_gray_mode<float, FT>(false, plan->f64, [&](auto, auto F64) {
+            const FusedTabT<decltype(F64)::value>& t = ft;   // (the float32 kernels take its FusedTab part)
+            with_stream_layout(plan, [&](auto G, auto L) {
+                hipLaunchKernelGGL((pyramid_stream_kernel<1, decltype(G)::value, decltype(L)::value, decltype(F64)::value, FT>),
+                                   dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, t, plan->stream);
+            });
+        });
     } else if constexpr (kFrameNarrow<FT>) {   // (single-channel, float32 accumulation: checked above)
         if (b_unit) hipLaunchKernelGGL((pyramid_unit_kernel<1, false, FT>), dim3((unsigned)b_unit), dim3(256), 0, s, frames, pyr, tab);
         if (b_region) hipLaunchKernelGGL((pyramid_region_kernel<1, false, FT>), dim3((unsigned)b_region), dim3(256), 0, s, frames, pyr, tab);
@@ -740,18 +722,10 @@ static int launch_pyramid_t(silent_ctx* ctx, const char* who, const silent_pyram
     return check_launch(ctx, who);
 }
 
-int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const float* frames, int n_frames, float* pyr,
-                   hipStream_t s, bool with_unit, bool with_region) {
-    return launch_pyramid_t(ctx, who, plan, frames, n_frames, pyr, s, with_unit, with_region);
-}
-int launch_pyramid_u8(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, float* pyr,
-                      hipStream_t s, bool with_unit, bool with_region) {
-    return launch_pyramid_t(ctx, who, plan, frames, n_frames, pyr, s, with_unit, with_region);
-}
-int launch_pyramid_u8x3(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FrameRgb8* frames, int n_frames,
-                        float* pyr, hipStream_t s, bool with_unit, bool with_region) {
-    return launch_pyramid_t(ctx, who, plan, frames, n_frames, pyr, s, with_unit, with_region);
-}
+#define X(FT) \
+    template int launch_pyramid<FT>(silent_ctx*, const char*, const silent_pyramid_plan*, const FT*, int, float*, hipStream_t, bool, bool);
+SILENT_FRAME_TYPES(X)
+#undef X
 
 SILENT_EXPORT int silent_pyramid_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames,
                                      int n_frames, float* pyr, silent_stream stream) try {
@@ -776,27 +750,31 @@ SILENT_EXPORT int silent_pyramid_plan_walk_plans(const silent_pyramid_plan* plan
     return on_exception(nullptr, "silent_pyramid_plan_walk_plans");
 }
 
+// The host-pointer forms and the uint8 frame kinds (silent_hip.h has the contracts: the pyramid of uint8 frames is the float32-frame
+// call's bit for bit -- a byte is widened at the load, an interleaved colour pixel becomes (b0 + b1 + b2) * float32(1/3) there;
+// single-channel plans without SILENT_PLAN_ACCUM_F64: the plan describes the pyramid, the frame layout belongs to the call).
+template <typename FT>
+static int pyramid_host(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames, float* pyr) {
+    const char* who = entry_name<FT>(kPyramid);
+    TRY(pyramid_checks(ctx, who, plan, frames, n_frames, pyr));
+    HostStage hs(ctx);
+    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * frame_px_bytes<FT>(plan->tab.C) * n_frames),
+              o = hs.out(pyr, (size_t)plan->tab.frame_px_out * plan->tab.C * 4 * n_frames);
+    return hs.run([&] { return launch_pyramid(ctx, who, plan, hs.dev<FT>(x), n_frames, hs.dev<float>(o), nullptr, true); });
+}
+
 SILENT_EXPORT int silent_pyramid(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
                                  float* pyr) try {
     NEED_CTX(ctx);
-    if (!plan || !frames || !pyr) return fail(ctx, SILENT_E_INVALID, "silent_pyramid: NULL pointer");
-    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, "silent_pyramid: n_frames must be >= 1");
-    HostStage hs(ctx);
-    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * plan->tab.C * 4 * n_frames),
-              o = hs.out(pyr, (size_t)plan->tab.frame_px_out * plan->tab.C * 4 * n_frames);
-    return hs.run([&] { return silent_pyramid_dev(ctx, plan, hs.dev<float>(x), n_frames, hs.dev<float>(o), nullptr); });
+    return pyramid_host(ctx, plan, frames, n_frames, pyr);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid");
 }
 
-// ------------------------------------------------------------------------------------------ uint8 frames
-// silent_pyramid[_dev] reading uint8 frames as they are (the FT = unsigned char kernels: the byte is widened at the load, the pyramid
-// is the float32-frame call's bit for bit).  Single-channel plans without SILENT_PLAN_ACCUM_F64.
-
 SILENT_EXPORT int silent_pyramid_u8_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
                                         float* pyr, silent_stream stream) try {
     NEED_CTX(ctx);
-    return launch_pyramid_u8(ctx, "silent_pyramid_u8", plan, frames, n_frames, pyr, (hipStream_t)stream, true);
+    return launch_pyramid(ctx, "silent_pyramid_u8", plan, frames, n_frames, pyr, (hipStream_t)stream, true);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_u8_dev");
 }
@@ -804,27 +782,15 @@ SILENT_EXPORT int silent_pyramid_u8_dev(silent_ctx* ctx, const silent_pyramid_pl
 SILENT_EXPORT int silent_pyramid_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
                                     float* pyr) try {
     NEED_CTX(ctx);
-    if (!plan || !frames || !pyr) return fail(ctx, SILENT_E_INVALID, "silent_pyramid_u8: NULL pointer");
-    if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_pyramid_u8: uint8 frames are for single-channel plans");
-    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, "silent_pyramid_u8: n_frames must be >= 1");
-    HostStage hs(ctx);
-    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * n_frames),   // bytes: 1 per frame pixel
-              o = hs.out(pyr, (size_t)plan->tab.frame_px_out * 4 * n_frames);
-    return hs.run([&] { return silent_pyramid_u8_dev(ctx, plan, hs.dev<uint8_t>(x), n_frames, hs.dev<float>(o), nullptr); });
+    return pyramid_host(ctx, plan, frames, n_frames, pyr);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_u8");
 }
 
-// ------------------------------------------------------------------------------------------ interleaved 3-channel uint8 frames
-// silent_pyramid[_dev] reading [n, H, W, 3] uint8 colour frames as they are (the FT = FrameRgb8 kernels: each pixel's value
-// (b0 + b1 + b2) * float32(1/3) is formed at the load, the pyramid is the float32-frame call's on the frame of values, bit for
-// bit).  Single-channel plans without SILENT_PLAN_ACCUM_F64: the plan describes the pyramid, the frame layout belongs to the call.
-
 SILENT_EXPORT int silent_pyramid_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
                                           float* pyr, silent_stream stream) try {
     NEED_CTX(ctx);
-    return launch_pyramid_u8x3(ctx, "silent_pyramid_u8x3", plan, reinterpret_cast<const FrameRgb8*>(frames), n_frames, pyr,
-                               (hipStream_t)stream, true);
+    return launch_pyramid(ctx, "silent_pyramid_u8x3", plan, rgb8(frames), n_frames, pyr, (hipStream_t)stream, true);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_u8x3_dev");
 }
@@ -832,14 +798,7 @@ SILENT_EXPORT int silent_pyramid_u8x3_dev(silent_ctx* ctx, const silent_pyramid_
 SILENT_EXPORT int silent_pyramid_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
                                       float* pyr) try {
     NEED_CTX(ctx);
-    if (!plan || !frames || !pyr) return fail(ctx, SILENT_E_INVALID, "silent_pyramid_u8x3: NULL pointer");
-    if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_pyramid_u8x3: uint8 frames are for single-channel plans");
-    if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, "silent_pyramid_u8x3: uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
-    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, "silent_pyramid_u8x3: n_frames must be >= 1");
-    HostStage hs(ctx);
-    const int x = hs.in(frames, (size_t)3 * plan->tab.H * plan->tab.W * n_frames),   // bytes: 3 per frame pixel
-              o = hs.out(pyr, (size_t)plan->tab.frame_px_out * 4 * n_frames);
-    return hs.run([&] { return silent_pyramid_u8x3_dev(ctx, plan, hs.dev<uint8_t>(x), n_frames, hs.dev<float>(o), nullptr); });
+    return pyramid_host(ctx, plan, rgb8(frames), n_frames, pyr);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_u8x3");
 }

@@ -665,10 +665,8 @@ class LineEndPipeline(object):
         write the end map fold the padded value map into what the tail needs; pyramid / cs / end are those of run_gray_pass."""
         self._check_frames(frames)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fn, fp = self._lib.silent_gray_keypoints_dev, p(frames)
-        if self.frame_dtype == "uint8":
-            fn = self._lib.silent_gray_keypoints_u8x3_dev if self._colour_frames else self._lib.silent_gray_keypoints_u8_dev
-            fp = _lib.byte_ptr(frames.data_ptr())
+        name, frame_ptr, _, _ = _lib.gray_entry("gray_keypoints", self.frame_dtype, self.frame_shape[2], dev=True)
+        fn, fp = getattr(self._lib, "silent_" + name + "_dev"), frame_ptr(frames.data_ptr())
         self.ctx.check(fn(
             self.ctx.handle, self.plan.handle, fp, self.batch, C.c_void_p(self.consts["cs"].ctypes.data),
             C.c_void_p(self.consts["end"].ctypes.data), self.n_orient, self.clip_hi, p(self.pyr), p(self.cs), p(self.end), self.pad,
@@ -680,26 +678,11 @@ class LineEndPipeline(object):
         levels, fused pyramid + CS + end kernel for the unit levels, filter kernel for the rest.  ``parts``: 1 = pyramid + unit
         levels only, 2 = the filter of the remaining levels only (silent_gray_pass_parts_dev; the halves of an overlapped step)."""
         self._check_frames(frames)
-        if self.frame_dtype == "uint8":    # the same pass reading the bytes as they are, either map storage
-            fn = self._lib.silent_gray_pass_u8x3_dev if self._colour_frames else self._lib.silent_gray_pass_u8_dev
-            self.ctx.check(fn(
-                self.ctx.handle, self.plan.handle, _lib.byte_ptr(frames.data_ptr()), self.batch,
-                C.c_void_p(self.consts["cs"].ctypes.data), C.c_void_p(self.consts["end"].ctypes.data), self.n_orient,
-                self.clip_hi, C.c_void_p(self.pyr.data_ptr()), C.c_void_p(self.cs.data_ptr()), C.c_void_p(self.end.data_ptr()),
-                1 if self.storage == "float16" else 0, int(parts), stream or self._stream()))
-            return
-        if self.storage == "float16":      # the same pass, cs / end as float16 maps
-            self.ctx.check(self._lib.silent_gray_pass_h_dev(
-                self.ctx.handle, self.plan.handle, C.c_void_p(frames.data_ptr()), self.batch,
-                C.c_void_p(self.consts["cs"].ctypes.data), C.c_void_p(self.consts["end"].ctypes.data), self.n_orient,
-                self.clip_hi, C.c_void_p(self.pyr.data_ptr()), _lib.half_ptr(self.cs.data_ptr()),
-                _lib.half_ptr(self.end.data_ptr()), int(parts), stream or self._stream()))
-            return
-        self.ctx.check(self._lib.silent_gray_pass_parts_dev(
-            self.ctx.handle, self.plan.handle, C.c_void_p(frames.data_ptr()), self.batch,
-            C.c_void_p(self.consts["cs"].ctypes.data), C.c_void_p(self.consts["end"].ctypes.data), self.n_orient,
-            self.clip_hi, C.c_void_p(self.pyr.data_ptr()), C.c_void_p(self.cs.data_ptr()),
-            C.c_void_p(self.end.data_ptr()), int(parts), stream or self._stream()))
+        name, frame_ptr, map_ptr, tail = _lib.gray_entry("gray_pass", self.frame_dtype, self.frame_shape[2], self.storage, True, parts)
+        self.ctx.check(getattr(self._lib, "silent_" + name + "_dev")(
+            self.ctx.handle, self.plan.handle, frame_ptr(frames.data_ptr()), self.batch, C.c_void_p(self.consts["cs"].ctypes.data),
+            C.c_void_p(self.consts["end"].ctypes.data), self.n_orient, self.clip_hi, C.c_void_p(self.pyr.data_ptr()),
+            map_ptr(self.cs.data_ptr()), map_ptr(self.end.data_ptr()), *(tail + (stream or self._stream(),))))
 
     def set_profiling(self, every=1):
         """Bracket the dominant kernel with HIP events on every ``every``-th step (0 / False: off)."""

@@ -1,7 +1,7 @@
 """Interleaved 3-channel uint8 frames for the gray pass (frame_channels=3, the silent_*_u8x3 entry points) without a GPU: the
 refusals (before any torch or GPU work), the six symbols beside their *_u8 twins, the byte accounting, and the host side of the new
 entry points -- argument validation and the host-pointer forms' staging of 3 * H * W * n BYTES -- as a stand-alone program
-(tests/gray_rgb8_host_main.cpp) built with the library's host side under ASan + UBSan."""
+(tests/gray_bytes_host_main.cpp) built with the library's host side under ASan + UBSan."""
 import ctypes
 import os
 import subprocess
@@ -141,21 +141,10 @@ def test_rgb_mode_accounting_is_unchanged():
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
-def test_u8x3_entry_points_on_the_host_side_under_asan_and_ubsan(tmp_path):
-    """tests/gray_rgb8_host_main.cpp + the library's host side (silent_unity.hip, -DSILENT_HOST_ONLY) as one executable under
+def test_u8x3_entry_points_on_the_host_side_under_asan_and_ubsan():
+    """tests/gray_bytes_host_main.cpp + the library's host side (silent_unity.hip, -DSILENT_HOST_ONLY) as one executable under
     -fsanitize=address,undefined, run as a child process: every new entry point in host and _dev form on 40 x 57 x 3 frames that are
     heap blocks of exactly 3 * n * H * W bytes, and the status codes of the ABI.  No sanitizer report, one "ok" line.  (A program of
     its own: nothing of it is loaded into Python.)"""
-    sys.path.insert(0, os.path.join(ROOT, "pysilent_amd", "csrc"))
-    import build as B
-    exe = str(tmp_path / "gray_rgb8_host_main")
-    # the flags of test_u8_entry_points_on_the_host_side_under_asan_and_ubsan (build_host_asan's, as an executable)
-    cmd = [B.hipcc(), "--offload-host-only", "-cuid=silenthost", "-DSILENT_HOST_ONLY", "-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17",
-           "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wno-unused-parameter",
-           "-Wno-unused-variable", "-Wno-unused-but-set-variable", "-o", exe, os.path.join(ROOT, "tests", "gray_rgb8_host_main.cpp")]
-    c = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, cwd=str(tmp_path))
-    assert c.returncode == 0, c.stdout[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:alloc_dealloc_mismatch=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300, cwd=str(tmp_path))
-    assert p.returncode == 0 and "gray rgb8 host main ok" in p.stdout, p.stdout[-4000:]
-    assert "AddressSanitizer" not in p.stdout and "runtime error" not in p.stdout, p.stdout[-4000:]
+    from test_gray_uint8_host import run_driver
+    assert "gray rgb8 host main ok" in run_driver("u8x3")

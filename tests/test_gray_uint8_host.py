@@ -1,6 +1,6 @@
 """uint8 frames for the gray pass without a GPU: the refusals (before any torch or GPU work), the six *_u8 symbols, the byte
 accounting, and the host side of the new entry points -- argument validation and the host-pointer forms' staging of H * W * n BYTES
--- as a stand-alone program (tests/gray_u8_host_main.cpp) built with the library's host side under ASan + UBSan."""
+-- as a stand-alone program (tests/gray_bytes_host_main.cpp, also for the float32-frame families and the refusal table) built with the library's host side under ASan + UBSan."""
 import ctypes
 import os
 import subprocess
@@ -118,22 +118,46 @@ def test_byte_accounting_counts_one_byte_per_frame_pixel():
     assert b.dominant_kernel_name() == a.dominant_kernel_name() == "gray_stream_kernel<4,"
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
-def test_u8_entry_points_on_the_host_side_under_asan_and_ubsan(tmp_path):
-    """tests/gray_u8_host_main.cpp + the library's host side (silent_unity.hip, -DSILENT_HOST_ONLY) as one executable under
-    -fsanitize=address,undefined, run as a child process: every new entry point in host and _dev form on 40 x 57 frames that are
-    heap blocks of exactly n * H * W bytes, and the status codes of the ABI.  No sanitizer report, one "ok" line."""
+needs_hipcc = pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
+
+
+def run_driver(family, *args):
+    """tests/gray_bytes_host_main.cpp + the library's host side (silent_unity.hip, -DSILENT_HOST_ONLY) as one executable under
+    -fsanitize=address,undefined (build.py, build_host_driver: "u8", "u8x3" or "f32"), run as a child process -- nothing of it is loaded
+    into Python: exit status 0 and no sanitizer report; returns its output."""
     sys.path.insert(0, os.path.join(ROOT, "pysilent_amd", "csrc"))
     import build as B
-    exe = str(tmp_path / "gray_u8_host_main")
-    # build_host_asan's flags, as an executable (the sanitizer runtime is linked in)
-    cmd = [B.hipcc(), "--offload-host-only", "-cuid=silenthost", "-DSILENT_HOST_ONLY", "-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17",
-           "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wno-unused-parameter",
-           "-Wno-unused-variable", "-Wno-unused-but-set-variable", "-o", exe, os.path.join(ROOT, "tests", "gray_u8_host_main.cpp")]
-    c = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, cwd=str(tmp_path))
-    assert c.returncode == 0, c.stdout[-4000:]
     # (alloc_dealloc_mismatch: the host shim's operator delete is free(); the same options as the other host-side sanitizer runs)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:alloc_dealloc_mismatch=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300, cwd=str(tmp_path))
-    assert p.returncode == 0 and "gray uint8 host main ok" in p.stdout, p.stdout[-4000:]
+    p = subprocess.run([B.build_host_driver(family)] + list(args), env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                       timeout=300)
+    assert p.returncode == 0, p.stdout[-4000:]
     assert "AddressSanitizer" not in p.stdout and "runtime error" not in p.stdout, p.stdout[-4000:]
+    return p.stdout
+
+
+@needs_hipcc
+def test_u8_entry_points_on_the_host_side_under_asan_and_ubsan():
+    """Every *_u8 entry point in host and _dev form on 40 x 57 frames that are heap blocks of exactly n * H * W bytes, and the status
+    codes of the ABI.  No sanitizer report, one "ok" line."""
+    assert "gray uint8 host main ok" in run_driver("u8")
+
+
+@needs_hipcc
+def test_float32_entry_points_on_the_host_side_under_asan_and_ubsan():
+    """The same for silent_pyramid, silent_gray_pass[_parts | _h], silent_gray_line_end and silent_gray_keypoints on float32 frames
+    (heap blocks of exactly 4 * n * H * W bytes)."""
+    assert "gray float32 host main ok" in run_driver("f32")
+
+
+@needs_hipcc
+def test_every_single_fault_is_refused_with_the_recorded_status_and_message():
+    """name | case | status | silent_last_error of every (entry point, single fault) of the 23 entry points against
+    tests/golden/gray_refusals.txt, recorded before the entry points shared their bodies.  Single faults only: the ABI promises no
+    order among simultaneous ones."""
+    got = "".join(run_driver(f, "--refusals") for f in ("f32", "u8", "u8x3")).splitlines()
+    want = open(os.path.join(ROOT, "tests", "golden", "gray_refusals.txt")).read().splitlines()
+    assert len({l.split(" | ")[0] for l in want}) == 23
+    for g, w in zip(got, want):
+        assert g == w
+    assert len(got) == len(want)
