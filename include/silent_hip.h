@@ -250,6 +250,43 @@ int silent_gray_pass_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, 
                               const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
                               void* end_out, int maps_f16, unsigned parts, silent_stream stream);
 
+/* Strided uint8 frames, read in place.  A decoder hands over NV12 surfaces with a row pitch, a camera or compositor BGRA / BGRX, YUYV
+ * carries luma on every second byte, a region of interest is a view with its parent's row step, hipMallocPitch pads rows: none of
+ * these is the packed layout of the *_u8 / *_u8x3 entry points, and packing them first is a launch that reads and writes the whole
+ * batch plus a second copy of it in device memory.  A view is a base pointer and three BYTE strides (byte, not pixel: a pitched BGR
+ * row need not be a multiple of 3); pixel (frame f, row y, column x) is the `channels` bytes at
+ *     data + f * frame_stride + y * row_stride + x * pixel_stride        (64-bit arithmetic)
+ * with H, W the plan's frame size.  A call reads only bytes of [data, data + span),
+ *     span = (n_frames - 1) * frame_stride + (H - 1) * row_stride + (W - 1) * pixel_stride + channels,
+ * and inside it only the `channels` bytes of each addressed pixel: never the fourth byte of a BGRA pixel, never a row's padding. */
+typedef struct silent_frame_view {
+    const uint8_t* data;   /* byte 0 of pixel (0, 0) of frame 0; NO alignment requirement */
+    int channels;          /* 1: value = the byte.  3: value = (b0 + b1 + b2) * float32(1/3) of the bytes at +0, +1, +2 */
+    int64_t pixel_stride;  /* bytes; >= channels */
+    int64_t row_stride;    /* bytes; >= (W - 1) * pixel_stride + channels */
+    int64_t frame_stride;  /* bytes; >= (H - 1) * row_stride + (W - 1) * pixel_stride + channels; not read when n_frames == 1 */
+} silent_frame_view;
+
+/* The twins of the *_u8 entry points on a view: the same argument lists with `const silent_frame_view* frames` in place of the packed
+ * bytes (maps_f16, parts and stream included), the same status codes, and every output IDENTICAL, bit for bit, to that of the *_u8
+ * (channels = 1) / *_u8x3 (channels = 3) entry point on the compacted copy of the same pixels.  Single-channel plans without
+ * SILENT_PLAN_ACCUM_F64, as there.  In addition SILENT_E_INVALID for a NULL view, NULL data, channels other than 1 or 3, or a stride
+ * below its bound (zero and negative strides among them: views are never flipped or broadcast), or a span above 2^63 - 1 bytes.  A view that IS packed --
+ * pixel_stride == channels, row_stride == W * pixel_stride, frame_stride == H * row_stride (or n_frames == 1) -- runs the kernels of
+ * the packed entry point; any other view runs their strided instantiations (frame and row terms of the address in scalar registers,
+ * the column term per lane).  _dev forms: data is a device pointer (the struct itself is host memory, read before the call returns).
+ * Host-pointer forms: data is host memory, exactly `span` bytes of it are staged; they refuse what their _dev form refuses before
+ * anything is staged.  (ABI additions only: SILENT_ABI_VERSION is unchanged.) */
+int silent_pyramid_view(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames, float* pyr);
+int silent_pyramid_view_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+                            float* pyr, silent_stream stream);
+int silent_gray_pass_view(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+                          const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
+                          void* end_out, int maps_f16);
+int silent_gray_pass_view_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+                              const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
+                              void* end_out, int maps_f16, unsigned parts, silent_stream stream);
+
 /* 1 when silent_gray_pass runs this plan through the single-read stream kernel (one unit-zoom level and every
  * other level resampling the same crop with a step > 1.25: classic whole-frame pyramids), 0 when it falls
  * back to region + unit-fused + filter kernels (e.g. the reference's centred-crop layout).  The same for
@@ -557,6 +594,18 @@ int silent_gray_keypoints_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan,
                                float* end_out, int pad, int selection, double top_percent, const silent_extent* regions,
                                float* value_out, float* peak_value_out, int64_t* idx, size_t cap_per_frame, int64_t* counts);
 int silent_gray_keypoints_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                   const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                   float* cs_out, float* end_out, int pad, int selection, double top_percent,
+                                   const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+                                   size_t cap_per_frame, int64_t* counts, silent_stream stream);
+
+/* The same on a strided uint8 view (see silent_gray_pass_view): every output is that of silent_gray_keypoints_u8[_dev] /
+ * silent_gray_keypoints_u8x3[_dev] on the compacted copy of the view's pixels. */
+int silent_gray_keypoints_view(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+                               const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out,
+                               float* end_out, int pad, int selection, double top_percent, const silent_extent* regions,
+                               float* value_out, float* peak_value_out, int64_t* idx, size_t cap_per_frame, int64_t* counts);
+int silent_gray_keypoints_view_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
                                    const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
                                    float* cs_out, float* end_out, int pad, int selection, double top_percent,
                                    const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,

@@ -242,9 +242,10 @@ class _Operand(object):
     """Normalised view of an input tensor: geometry + pointer + how to allocate results and which entry point to call.
     ``ctx``: the context to run on (default: the shared one of the tensor's device)."""
 
-    def __init__(self, x, channels=None, ctx=None, frame_dtype="float32"):
+    def __init__(self, x, channels=None, ctx=None, frame_dtype="float32", frame_layout="packed"):
         self.packed = isinstance(x, PackedPyramid)
-        if frame_dtype == "uint8":
+        strided = frame_layout == "strided"      # (uint8 frames: checked by the caller) the frames are a view, passed as it is
+        if frame_dtype == "uint8" and not strided:
             _require_uint8(x)
         if self.packed:
             self.src = x
@@ -275,11 +276,14 @@ class _Operand(object):
             self.ptr = C.c_void_p(buf.data_ptr())
             self._torch_device = buf.device
         else:
-            buf = np.ascontiguousarray(buf, dtype=np.uint8 if frame_dtype == "uint8" else np.float32)
+            if not strided:
+                buf = np.ascontiguousarray(buf, dtype=np.uint8 if frame_dtype == "uint8" else np.float32)
             self.device = None
             self.stream = None
             self.ptr = C.c_void_p(buf.ctypes.data)
-        if frame_dtype == "uint8":
+        if strided:
+            self.ptr = _lib.view_ptr(frame_view_of(buf, self.c))
+        elif frame_dtype == "uint8":
             self.ptr = _lib.byte_ptr(self.ptr.value)
         self.buf = buf                                  # keep alive
         self.frame_px = sum(h * w for h, w in self.extents)
@@ -331,6 +335,50 @@ def _require_uint8(x):
     if not ok:
         raise ValueError("frame_dtype='uint8' takes a uint8 ndarray or a contiguous uint8 GPU tensor (nothing is converted), got %s"
                          % (x.dtype,))
+
+
+def frame_view_of(frames, channels):
+    """A uint8 array -- torch tensor or ndarray, [n, H, W, channels] with channels 1 or 3, or [n, H, W] for one channel -- as the
+    view the silent_*_view entry points read in place: (address, channels, pixel_stride, row_stride, frame_stride), strides in bytes.
+    Any positive strides do (a pitched surface, bgra[..., :3], yuyv[:, :, ::2, None], a region of a larger frame, every second
+    frame); a ValueError for anything but uint8, for a negative or zero stride ([::-1], a broadcast), for strides under which pixels
+    or rows overlap, and for three channels that are not adjacent bytes.  An axis of length 1 has no stride to speak of: it is
+    given the smallest valid one."""
+    if isinstance(channels, bool) or not isinstance(channels, int) or channels not in FRAME_CHANNELS:
+        raise ValueError("frame_view_of: channels must be 1 or 3, got %r" % (channels,))
+    if isinstance(frames, np.ndarray):
+        ok, strides, address = frames.dtype == np.uint8, tuple(int(s) for s in frames.strides), frames.ctypes.data
+    elif is_torch_tensor(frames):
+        import torch
+        ok, strides, address = frames.dtype == torch.uint8, tuple(int(s) for s in frames.stride()), frames.data_ptr()
+    else:
+        raise TypeError(TYPE_ERROR_MESSAGE)
+    if not ok:
+        raise ValueError("frame_view_of takes uint8 frames (nothing is converted), got %s" % (frames.dtype,))
+    shape = tuple(int(s) for s in frames.shape)
+    if len(shape) == 3 and channels == 1:
+        shape, strides = shape + (1,), strides + (1,)
+    if len(shape) != 4 or shape[3] != channels:
+        raise ValueError("frame_view_of: expected [n, H, W, %d]%s, got shape %s"
+                         % (channels, " or [n, H, W]" if channels == 1 else "", tuple(frames.shape)))
+    n, h, w, _ = shape
+    if min(n, h, w) < 1:
+        raise ValueError("frame_view_of: empty frames, shape %s" % (tuple(frames.shape),))
+    sn, sh, sw, sc = strides
+    if channels == 3 and sc != 1:
+        raise ValueError("frame_view_of: the three channels of a pixel must be adjacent bytes (channel stride 1), got %d" % sc)
+    for name, length, stride in (("frame", n, sn), ("row", h, sh), ("pixel", w, sw)):
+        if length > 1 and stride <= 0:
+            raise ValueError("frame_view_of: %s stride %d: a view is never flipped or broadcast (strides must be positive)"
+                             % (name, stride))
+    pixel = sw if w > 1 else channels
+    row_min = (w - 1) * pixel + channels
+    row = sh if h > 1 else row_min
+    frame_min = (h - 1) * row + row_min
+    frame = sn if n > 1 else frame_min
+    if pixel < channels or row < row_min or frame < frame_min:
+        raise ValueError("frame_view_of: pixels, rows or frames of the view overlap (strides %s for shape %s)" % (strides, shape))
+    return int(address), channels, pixel, row, frame
 
 
 def _kernel_arg(k, c_in=None):
@@ -806,6 +854,27 @@ def check_frame_channels(frame_channels, mode="gray", frame_dtype="float32", acc
     return frame_channels
 
 
+FRAME_LAYOUTS = ("packed", "strided")
+
+
+def check_frame_layout(frame_layout, mode="gray", frame_dtype="float32", accumulation="float32"):
+    """The frame_layout argument of PyramidPlan.run / gray_pass / gray_keypoints and LineEndPipeline: "packed" (default: contiguous
+    [n, H, W] or [n, H, W, 3] frames) or "strided" (any uint8 view with positive strides -- a pitched decoder surface, BGRA, YUYV
+    luma, a region of a larger frame -- read in place by the silent_*_view entry points: no packing launch, no second copy of the
+    batch; bit-identical to the packed path on the compacted pixels).  The name is checked first; then what "strided" needs: mode
+    "gray", frame_dtype="uint8" and float32 accumulation."""
+    if frame_layout not in FRAME_LAYOUTS:
+        raise ValueError("frame_layout must be 'packed' or 'strided', got %r" % (frame_layout,))
+    if frame_layout == "strided":
+        if mode != "gray":
+            raise ValueError("frame_layout='strided' is for mode 'gray' (the RGB kernels read packed float32 frames)")
+        if frame_dtype != "uint8":
+            raise ValueError("frame_layout='strided' needs frame_dtype='uint8' (float32 frames are read packed only)")
+        if accumulation == "float64":
+            raise ValueError("frame_layout='strided' does not combine with accumulation='float64'")
+    return frame_layout
+
+
 class PyramidPlan(object):
     """Tap tables of one (frame size, level geometry) on the device.  ``levels`` is a list of dicts / tuples
     (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w).  accumulation="float64" (single-channel plans): every op of
@@ -825,32 +894,37 @@ class PyramidPlan(object):
                                                                  C.byref(self.handle)))
         self.frame_px = sum(h * w for h, w in self.extents)
 
-    def _frames(self, frames, frame_dtype="float32", frame_channels=1):
+    def _frames(self, frames, frame_dtype="float32", frame_channels=1, frame_layout="packed"):
         """[n, H, W, C] frames of this plan (ndarray, or torch GPU tensor) as an operand on the plan's context.  frame_dtype="uint8":
         a uint8 ndarray or contiguous uint8 GPU tensor, passed as it is (anything else is a ValueError); "float32": widened.
-        frame_channels=3 (single-channel plans, uint8): the frames are [n, H, W, 3] interleaved colour."""
+        frame_channels=3 (single-channel plans, uint8): the frames are [n, H, W, 3] interleaved colour.  frame_layout="strided"
+        (uint8): any view with positive strides (frame_view_of), passed as it is; [n, H, W] does for one channel."""
         mode = "gray" if self.frame_shape[2] == 1 else "rgb"
         check_frame_channels(frame_channels, mode, frame_dtype, self.accumulation)      # (first: a refused 3 is reported as such)
         check_frame_dtype(frame_dtype, mode, self.accumulation)
+        check_frame_layout(frame_layout, mode, frame_dtype, self.accumulation)
         if not (isinstance(frames, np.ndarray) or is_torch_tensor(frames)):
             raise TypeError(TYPE_ERROR_MESSAGE)
+        if frame_layout == "strided" and frame_channels == 1 and frames.ndim == 3:
+            frames = frames[..., None]
         shape = self.frame_shape[:2] + (3,) if frame_channels == 3 else self.frame_shape
         if tuple(frames.shape[1:]) != shape:
             raise ValueError("frames must be [n, %d, %d, %d], got %s" % (shape + (tuple(frames.shape),)))
-        return _Operand(frames, ctx=self.ctx, frame_dtype=frame_dtype)
+        return _Operand(frames, ctx=self.ctx, frame_dtype=frame_dtype, frame_layout=frame_layout)
 
     @staticmethod
-    def _entry(name, frame_dtype, frame_channels):
-        """The entry point family of a frame layout: silent_<name>, silent_<name>_u8 or silent_<name>_u8x3."""
-        return _lib.gray_entry(name, frame_dtype, frame_channels)[0]
+    def _entry(name, frame_dtype, frame_channels, frame_layout="packed"):
+        """The entry point family of a frame layout: silent_<name>, silent_<name>_u8, silent_<name>_u8x3 or silent_<name>_view."""
+        return _lib.gray_entry(name, frame_dtype, frame_channels, frame_layout=frame_layout)[0]
 
-    def run(self, frames, frame_dtype="float32", frame_channels=1):
+    def run(self, frames, frame_dtype="float32", frame_channels=1, frame_layout="packed"):
         """frames: [n, H, W, C] ndarray (host) or torch GPU tensor.  Returns a PackedPyramid.  frame_dtype="uint8" (single-channel
         plans): uint8 frames read as they are (silent_pyramid_u8), the same pyramid bit for bit.  frame_channels=3 (with "uint8"):
-        [n, H, W, 3] interleaved colour frames (silent_pyramid_u8x3), the pyramid of the frame of values (b0 + b1 + b2) * f32(1/3)."""
-        op, c = self._frames(frames, frame_dtype, frame_channels), self.frame_shape[2]
+        [n, H, W, 3] interleaved colour frames (silent_pyramid_u8x3), the pyramid of the frame of values (b0 + b1 + b2) * f32(1/3).
+        frame_layout="strided" (with "uint8"): any uint8 view with positive strides, read in place (silent_pyramid_view)."""
+        op, c = self._frames(frames, frame_dtype, frame_channels, frame_layout), self.frame_shape[2]
         out, optr = op.empty(op.n_frames * self.frame_px * c)
-        op.call(self._entry("pyramid", frame_dtype, frame_channels), self.handle, op.ptr, op.n_frames, optr)
+        op.call(self._entry("pyramid", frame_dtype, frame_channels, frame_layout), self.handle, op.ptr, op.n_frames, optr)
         return PackedPyramid(out, self.extents, c, op.n_frames)
 
     @property
@@ -872,16 +946,19 @@ class PyramidPlan(object):
         n = _lib.load().silent_pyramid_plan_walk_plans(self.handle, C.byref(px))
         return int(n), int(px.value)
 
-    def gray_pass(self, frames, cs_kernel, end_bank, clip_hi=255.0, storage="float32", frame_dtype="float32", frame_channels=1):
+    def gray_pass(self, frames, cs_kernel, end_bank, clip_hi=255.0, storage="float32", frame_dtype="float32", frame_channels=1,
+                  frame_layout="packed"):
         """Whole grayscale hot path (silent_gray_pass): frames [n,H,W,1] -> (pyramid, cs, end) PackedPyramids.
         Same results as run() + gray_line_end(), one pass less over level 0.  storage="float16" (silent_gray_pass_h): cs and end
         are float16 maps -- each element the float32 result rounded to nearest even -- and the pyramid stays float32.
         frame_dtype="uint8" (silent_gray_pass_u8): uint8 frames read as they are; the same maps bit for bit, either storage.
         frame_channels=3 (with "uint8"; silent_gray_pass_u8x3): frames [n,H,W,3] interleaved colour, each pixel entering as
-        (b0 + b1 + b2) * float32(1/3) -- the maps of the float32 call on that frame of values, bit for bit."""
+        (b0 + b1 + b2) * float32(1/3) -- the maps of the float32 call on that frame of values, bit for bit.
+        frame_layout="strided" (with "uint8"; silent_gray_pass_view): any uint8 view with positive strides, read in place."""
         check_storage(storage, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
         check_frame_channels(frame_channels, "gray" if self.frame_shape[2] == 1 else "rgb", frame_dtype, self.accumulation)
         check_frame_dtype(frame_dtype, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
+        check_frame_layout(frame_layout, "gray" if self.frame_shape[2] == 1 else "rgb", frame_dtype, self.accumulation)
         if self.frame_shape[2] != 1:
             raise ValueError("gray_pass needs a single-channel plan")
         cs = _kernel_arg(cs_kernel, 1)
@@ -889,9 +966,9 @@ class PyramidPlan(object):
         if cs.shape != (3, 3, 1, 1) or eb.shape[:3] != (3, 3, 1):
             raise ValueError("gray_pass needs a [3,3,1,1] CS kernel and a [3,3,1,K] end bank")
         K = eb.shape[3]
-        op = self._frames(frames, frame_dtype, frame_channels)
+        op = self._frames(frames, frame_dtype, frame_channels, frame_layout)
         n = op.n_frames
-        name, _, map_ptr, tail = _lib.gray_entry("gray_pass", frame_dtype, frame_channels, storage, op.dev)
+        name, _, map_ptr, tail = _lib.gray_entry("gray_pass", frame_dtype, frame_channels, storage, op.dev, frame_layout=frame_layout)
         dt = np.float16 if storage == "float16" else np.float32
         pyr, pp = op.empty(n * self.frame_px)
         (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch, dt) for ch in (1, K)]
@@ -901,13 +978,15 @@ class PyramidPlan(object):
         return P(pyr, self.extents, 1, n), P(cso, self.extents, 1, n, dtype=dt), P(endo, self.extents, K, n, dtype=dt)
 
     def gray_keypoints(self, frames, cs_kernel, end_bank, clip_hi=255.0, pad=2, selection=True, top_percent=0.1, regions=None,
-                       cap_per_frame=None, frame_dtype="float32", frame_channels=1):
+                       cap_per_frame=None, frame_dtype="float32", frame_channels=1, frame_layout="packed"):
         """silent_gray_keypoints (host form): gray_pass + pad_inwards -> value -> [top_value_points -> NMS -> value ->]
         max_value_indices_region on the K-channel end map.  Returns (pyramid, cs, end, idx [n, cap, 4], counts [n]).
         frame_dtype="uint8" (silent_gray_keypoints_u8): uint8 frames read as they are, the same results.  frame_channels=3 (with
-        "uint8"; silent_gray_keypoints_u8x3): [n,H,W,3] interleaved colour frames, the results of the frame of values."""
+        "uint8"; silent_gray_keypoints_u8x3): [n,H,W,3] interleaved colour frames, the results of the frame of values.
+        frame_layout="strided" (with "uint8"; silent_gray_keypoints_view): any uint8 view with positive strides, read in place."""
         check_frame_channels(frame_channels, "gray" if self.frame_shape[2] == 1 else "rgb", frame_dtype, self.accumulation)
         check_frame_dtype(frame_dtype, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
+        check_frame_layout(frame_layout, "gray" if self.frame_shape[2] == 1 else "rgb", frame_dtype, self.accumulation)
         if self.frame_shape[2] != 1:
             raise ValueError("gray_keypoints needs a single-channel plan")
         cs = _kernel_arg(cs_kernel, 1)
@@ -920,13 +999,13 @@ class PyramidPlan(object):
             raise ValueError("need one (rH, rW) region per level")
         reg = (_lib.Extent * len(regions))(*[_lib.Extent(int(rh), int(rw)) for rh, rw in regions])
         K = eb.shape[3]
-        op = self._frames(frames, frame_dtype, frame_channels)
+        op = self._frames(frames, frame_dtype, frame_channels, frame_layout)
         n = op.n_frames
         cap = self.frame_px if cap_per_frame is None else int(cap_per_frame)
         (pyr, pp), (cso, cp), (endo, ep) = [op.empty(n * self.frame_px * ch) for ch in (1, 1, K)]
         idx, iptr = op.empty((n, cap, 4), np.int64)
         counts, cptr = op.empty(n, np.int64)
-        op.call(self._entry("gray_keypoints", frame_dtype, frame_channels), self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi),
+        op.call(self._entry("gray_keypoints", frame_dtype, frame_channels, frame_layout), self.handle, op.ptr, n, C.c_void_p(cs.ctypes.data), C.c_void_p(eb.ctypes.data), K, float(clip_hi),
                 pp, cp, ep, int(pad), int(selection), float(top_percent), reg, None, None, iptr, cap, cptr)
         P = PackedPyramid
         return P(pyr, self.extents, 1, n), P(cso, self.extents, 1, n), P(endo, self.extents, K, n), idx, counts

@@ -104,7 +104,9 @@ HOST_ASAN_FLAGS = ["--offload-host-only", "-cuid=silenthost", "-DSILENT_HOST_ONL
                    "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 # tests/gray_bytes_host_main.cpp, once per frame type: the entry-point suffix and the bytes of one frame pixel
 HOST_DRIVERS = {"u8": ["-DSILENT_SFX=_u8", "-DSILENT_FRAME_BYTES=1"], "u8x3": ["-DSILENT_SFX=_u8x3", "-DSILENT_FRAME_BYTES=3"],
-                "f32": ["-DSILENT_FRAME_BYTES=4"]}
+                "f32": ["-DSILENT_FRAME_BYTES=4"], "view": []}
+# "view": the strided *_view entry points have a driver of their own (both channel counts in one program)
+HOST_DRIVER_SOURCES = {"view": "gray_view_host_main.cpp"}
 
 
 def _fresh(out, dep):
@@ -128,14 +130,14 @@ def build_host_asan(force=False):
 
 
 def build_host_driver(family, force=False):
-    """tests/gray_bytes_host_main.cpp + the library's host side as one stand-alone executable under the same sanitizers (the runtime
+    """tests/gray_bytes_host_main.cpp (tests/gray_view_host_main.cpp for "view") + the library's host side as one stand-alone executable under the same sanitizers (the runtime
     is linked in: it is run as a child process, nothing of it is loaded into Python), for one frame type of HOST_DRIVERS.  Returns the
     path of the executable, build/gray_host_<family>; rebuilt when a file it was compiled from is newer."""
     exe = os.path.join(HERE, "build", "gray_host_" + family)
     os.makedirs(os.path.dirname(exe), exist_ok=True)
     if force or not _fresh(exe, exe + ".d"):
         cmd = [hipcc()] + HOST_ASAN_FLAGS + HOST_DRIVERS[family] + ["-MMD", "-MF", exe + ".d", "-o", exe,
-                                                                    os.path.join(os.path.dirname(PKG), "tests", "gray_bytes_host_main.cpp")]
+                                                                    os.path.join(os.path.dirname(PKG), "tests", HOST_DRIVER_SOURCES.get(family, "gray_bytes_host_main.cpp"))]
         c = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if c.returncode != 0:
             raise RuntimeError("hipcc failed on the host driver (%s):\n%s" % (family, c.stdout[-4000:]))

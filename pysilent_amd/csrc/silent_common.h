@@ -159,17 +159,63 @@ struct FrameRgb8 {
 static_assert(sizeof(FrameRgb8) == 3 && alignof(FrameRgb8) == 1, "one interleaved uint8 colour pixel");
 template <typename FT>
 constexpr bool kFrameRgb8 = std::is_same<FT, FrameRgb8>::value;
+// Strided uint8 frames (the *_view entry points, silent_frame_view): the pixels PX -- unsigned char or FrameRgb8, read exactly as the
+// packed kinds read them -- of a view with three BYTE strides (a pitched BGR row need not be a multiple of 3), so pixel (frame, y, x)
+// is the PX at data + frame * frame_stride + y * row_stride + x * pixel_stride, in 64-bit bytes.  The type is both the frame kind FT
+// of the kernels and their argument, by value: the strides arrive in SGPRs, and with the wave-uniform row of every load the frame
+// and row terms are scalar arithmetic -- only x * pixel_stride is per lane, formed once per tile where the column is the lane's own.
+// The packed kinds keep `const FT*` and their statements (their machine code is unchanged).
+template <typename PX>
+struct FrameStrided {
+    const unsigned char* data;
+    long long pixel_stride, row_stride, frame_stride;
+};
+template <typename FT>
+constexpr bool kFrameStrided = false;
+template <typename PX>
+constexpr bool kFrameStrided<FrameStrided<PX>> = true;
+// one frame of a strided batch inside a kernel: (float)at(y, x) is the value of its pixel (x, y)
+template <typename PX>
+struct StridedSrc {
+    const unsigned char* p;
+    long long pixel_stride, row_stride;
+    __device__ __forceinline__ float at(long long y, long long x) const {
+        return (float)*reinterpret_cast<const PX*>(p + y * row_stride + x * pixel_stride);
+    }
+};
+// the `frames` parameter of a kernel on frame kind FT, and what `src` (one frame of the batch) is inside it
+template <typename FT>
+struct FrameKind {
+    typedef const FT* __restrict__ param;
+    typedef const FT* __restrict__ src;
+};
+template <typename PX>
+struct FrameKind<FrameStrided<PX>> {
+    typedef FrameStrided<PX> param;
+    typedef StridedSrc<PX> src;
+    typedef PX px;
+};
+template <typename FT>
+using frame_param = typename FrameKind<FT>::param;
+template <typename FT>
+using frame_src = typename FrameKind<FT>::src;
+// frame `frame` of a strided batch (the packed kinds keep their `frames + frame * H * W` and `(float)src[y * W + x]` statements)
+template <typename PX>
+__device__ __forceinline__ StridedSrc<PX> frame_of(const FrameStrided<PX>& frames, int frame) {
+    return StridedSrc<PX>{frames.data + (long long)frame * frames.frame_stride, frames.pixel_stride, frames.row_stride};
+}
+
 // the frame types that exist for single-channel plans with float32 accumulation only
 template <typename FT>
-constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT>;
+constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT> || kFrameStrided<FT>;
 template <typename FT>
 constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT>;
-// (host) the bytes of one frame pixel as the host-pointer forms stage it -- float frames carry the channels of the plan -- and the
-// suffix of a frame type's entry points
+// (host) the bytes of one frame pixel as the host-pointer forms stage it -- float frames carry the channels of the plan; a view is
+// staged by its span -- and the suffix of a frame type's entry points
 template <typename FT>
 constexpr size_t frame_px_bytes(int plan_channels) { return kFrameRgb8<FT> ? 3 : kFrameBytes<FT> ? 1 : 4 * (size_t)plan_channels; }
 template <typename FT>
-constexpr const char* kFrameSuffix = kFrameRgb8<FT> ? "_u8x3" : kFrameBytes<FT> ? "_u8" : "";
+constexpr const char* kFrameSuffix = kFrameStrided<FT> ? "_view" : kFrameRgb8<FT> ? "_u8x3" : kFrameBytes<FT> ? "_u8" : "";
 
 // Stream row i of the column `col` (level coordinates, mirrored inside the crop like every tap; px_stride floats per pixel) in lane i: ONE load per tile
 // for the sixth taps of a wave's last smoothing lane; row i is read back with unit_edge(xcol, i).
@@ -179,6 +225,13 @@ __device__ __forceinline__ float unit_edge_column(const FT* __restrict__ src, lo
                                                   int y_first, int n_rows, int src_h, int src_y0, int lane, int px_stride = 1) {
     const long long sx = (long long)(mirror_near(col, src_w) + src_x0) * px_stride;
     return (float)src[(long long)(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0) * row_stride + sx];
+}
+// the same column of a strided frame: here the ROW is per lane and the column wave-uniform (the view carries its strides, `row_stride`
+// and `px_stride` of the packed form are not used)
+template <typename PX>
+__device__ __forceinline__ float unit_edge_column(const StridedSrc<PX>& src, long long, int col, int src_w, int src_x0, int y_first,
+                                                  int n_rows, int src_h, int src_y0, int lane, int = 1) {
+    return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0);
 }
 __device__ __forceinline__ float unit_edge(float xcol, int i) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xcol), i));

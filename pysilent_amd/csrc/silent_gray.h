@@ -421,7 +421,7 @@ template <bool F64>
 using FusedTabT = typename std::conditional<F64, FusedTab64, FusedTab>::type;
 
 template <int K, int R, bool KP = false, bool F64 = false, typename ST = float, typename FT = float>
-__global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const FT* __restrict__ frames,
+__global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(frame_param<FT> frames,
                                                               float* __restrict__ pyr, ST* __restrict__ cs_out,
                                                               ST* __restrict__ end_out, const FusedTabT<F64> tab,
                                                               const GrayW wts, float clip_hi, const GrayKp kp = GrayKp{}) {
@@ -446,7 +446,9 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
     const int y0 = ty * R;
     const int ox = xw0 + lane - 4;
     const int W = tab.W;
-    const FT* __restrict__ src = frames + (long long)frame * tab.H * W;
+    frame_src<FT> src;
+    if constexpr (kFrameStrided<FT>) src = frame_of(frames, frame);
+    else src = frames + (long long)frame * tab.H * W;
     const long long base_px = (long long)frame * tab.frame_px + lv.px_off;
 
     // scipy 'mirror' inside the crop, then the crop's offset in the frame
@@ -454,7 +456,10 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(const
     float in[R + 9];                                                  // stream rows y0 - 4 .. y0 + R + 4 (the sixth tap: + 1 row)
 #pragma unroll
     for (int i = 0; i < R + 9; ++i)
-        in[i] = (float)src[(long long)(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0) * W + sx];
+    {
+        if constexpr (kFrameStrided<FT>) in[i] = src.at(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0, sx);
+        else in[i] = (float)src[(long long)(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0) * W + sx];
+    }
     float xcol = unit_edge_column(src, W, xw0 + 60, lv.src_w, lv.src_x0, y0 - 4, R + 9, lv.src_h, lv.src_y0, lane);
 #pragma unroll
     for (int i = 0; i < R + 9; ++i) asm volatile("" ::"v"(in[i]));  // retire loads before the first store
@@ -723,7 +728,7 @@ __device__ __forceinline__ void stream_level_f64(int g, const int (&cur)[PR], fl
 constexpr int kStreamRegLevels = SILENT_STREAM_REG_LEVELS;
 
 template <int K, int G, int L = 0, bool KP = false, bool F64 = false, typename ST = float, typename FT = float>
-__global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const FT* __restrict__ frames, float* __restrict__ pyr,
+__global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(frame_param<FT> frames, float* __restrict__ pyr,
                                                           ST* __restrict__ cs_out, ST* __restrict__ end_out,
                                                           const FusedTabT<F64> tab, const StreamTab st, const GrayW wts,
                                                           float clip_hi, unsigned opts, const GrayKp kp = GrayKp{}) {
@@ -746,7 +751,9 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const FT*
     const int y0 = ty * R;
     const int ox = xw0 + lane - 4;
     const int W = tab.W;
-    const FT* __restrict__ src = frames + (long long)frame * tab.H * W;
+    frame_src<FT> src;
+    if constexpr (kFrameStrided<FT>) src = frame_of(frames, frame);
+    else src = frames + (long long)frame * tab.H * W;
     const long long frame_px0 = (long long)frame * tab.frame_px;
     const long long base_px = frame_px0 + lv.px_off;
 
@@ -767,8 +774,12 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const FT*
     if (live) {
 #pragma unroll
         for (int i = 0; i < R + 8; ++i)
-            in[i] = (float)src[(long long)(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0) * W + sx];
-        in_last = (float)src[(long long)(mirror_near(y0 + R + 4, lv.src_h) + lv.src_y0) * W + sx];
+        {
+            if constexpr (kFrameStrided<FT>) in[i] = src.at(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0, sx);
+            else in[i] = (float)src[(long long)(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0) * W + sx];
+        }
+        if constexpr (kFrameStrided<FT>) in_last = src.at(mirror_near(y0 + R + 4, lv.src_h) + lv.src_y0, sx);
+        else in_last = (float)src[(long long)(mirror_near(y0 + R + 4, lv.src_h) + lv.src_y0) * W + sx];
         xcol = unit_edge_column(src, W, xw0 + 60, lv.src_w, lv.src_x0, y0 - 4, R + 9, lv.src_h, lv.src_y0, lane);
 #pragma unroll
         for (int g = 0; g < GR; ++g) col[g] = stream_col_t<F64>(st, g, wx_tile, lane);
@@ -1019,7 +1030,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(const FT*
 // frames; with C = 3 the stride-3 loads and partial-line stores made it 1.5 ms against 1.0 ms for unit + region
 // kernels on 32 RGB frames (measured, bit-identical either way), so RGB plans are not marked streamable.
 template <int C, int G, int L = 0, bool F64 = false, typename FT = float>
-__global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(const FT* __restrict__ frames, float* __restrict__ pyr,
+__global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(frame_param<FT> frames, float* __restrict__ pyr,
                                                              const FusedTabT<F64> tab, const StreamTab st) {
     static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
     constexpr int R = kFusedTH, NR = kStreamRows;
@@ -1037,7 +1048,9 @@ __global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(const 
     const int y0 = ty * R;
     const int ox = xw0 + lane - 4;
     const long long WC = (long long)tab.W * C;
-    const FT* __restrict__ src = frames + (long long)frame * tab.H * WC;
+    frame_src<FT> src;
+    if constexpr (kFrameStrided<FT>) src = frame_of(frames, frame);
+    else src = frames + (long long)frame * tab.H * WC;
     const long long frame_px0 = (long long)frame * tab.frame_px;
     const long long base_px = frame_px0 + lv.px_off;
     const long long sx = (long long)(mirror_near(ox, lv.src_w) + lv.src_x0) * C;
@@ -1059,7 +1072,8 @@ __global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(const 
         float in[R + 8];
 #pragma unroll
         for (int i = 0; i < R + 8; ++i)
-            in[i] = (float)src[(long long)(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0) * WC + sx + ch];
+            if constexpr (kFrameStrided<FT>) in[i] = src.at(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0, sx);   // (C == 1)
+            else in[i] = (float)src[(long long)(mirror_near(y0 - 4 + i, lv.src_h) + lv.src_y0) * WC + sx + ch];
 #pragma unroll
         for (int i = 0; i < R + 8; ++i) asm volatile("" ::"v"(in[i]));  // retire loads before the first store
 #pragma unroll

@@ -49,12 +49,13 @@ SILENT_EXPORT int silent_gray_line_end_dev(silent_ctx* ctx, const float* pyr, co
     return on_exception(ctx, "silent_gray_line_end_dev");
 }
 
-// everything silent_gray_pass*_dev refuses, before a launch (and, in the host forms, before the batch is staged)
+// everything silent_gray_pass*_dev refuses, before a launch (and, in the host forms, before the batch is staged); FT: the frame kind of
+// the ENTRY POINT (the view entry points check as a strided kind whatever kind then reads the view), has_frames: its frames are not NULL
 template <typename FT>
-static int gray_pass_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames,
+static int gray_pass_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, bool has_frames, int n_frames,
                             const float* cs_kernel, const float* end_bank, int n_orient, const float* pyr, const void* cs_out,
                             const void* end_out, bool f16, unsigned parts) {
-    if (!plan || !frames || !pyr || !cs_kernel) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (!plan || !has_frames || !pyr || !cs_kernel) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
     if constexpr (kFrameNarrow<FT>) TRY(check_narrow_frames(ctx, who, plan));
     if (f16) TRY(check_half_storage(ctx, who, plan));
@@ -72,7 +73,7 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
                            const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
                            ST* cs_out, ST* end_out, unsigned parts, silent_stream stream, const GrayKp* kp = nullptr) {
     const char* who = entry_name<FT>(kp ? kGrayKeypoints : kStoreHalf<ST> ? kGrayPassH : kGrayPass);
-    TRY(gray_pass_checks(ctx, who, plan, frames, n_frames, cs_kernel, end_bank, n_orient, pyr, cs_out, end_out, kStoreHalf<ST>, parts));
+    TRY(gray_pass_checks<FT>(ctx, who, plan, frames != nullptr, n_frames, cs_kernel, end_bank, n_orient, pyr, cs_out, end_out, kStoreHalf<ST>, parts));
     hipStream_t s = (hipStream_t)stream;
     const PyrTab& pt = plan->tab;
     const int kopts = (int)ctx->tune[SILENT_TUNE_GRAY];  // A/B knob: bit4 disables the stream path (bit3, 32-row fused tiles, is ignored since round 6)
@@ -111,16 +112,16 @@ static int gray_pass_parts(silent_ctx* ctx, const silent_pyramid_plan* plan, con
                     const unsigned sopts = (unsigned)((kopts >> 5) & 1);
                     with_stream_layout(plan, [&](auto G, auto L) {
 #define STREAM(...) \
-    hipLaunchKernelGGL((gray_stream_kernel<k, decltype(G)::value, decltype(L)::value, with_kp, f64, ST, FT>), grid, block, 0, s, frames, pyr, \
-                       cs_out, end_out, t, st, w, clip_hi, sopts, ##__VA_ARGS__)
+    hipLaunchKernelGGL((gray_stream_kernel<k, decltype(G)::value, decltype(L)::value, with_kp, f64, ST, FT>), grid, block, 0, s, kernel_frames(frames), \
+                       pyr, cs_out, end_out, t, st, w, clip_hi, sopts, ##__VA_ARGS__)
                         if constexpr (with_kp) STREAM(kpu);
                         else STREAM();
 #undef STREAM
                     });
                 } else {
 #define FUSED(...) \
-    hipLaunchKernelGGL((gray_unit_fused_kernel<k, kFusedTH, with_kp, f64, ST, FT>), grid, block, 0, s, frames, pyr, cs_out, end_out, t, w, \
-                       clip_hi, ##__VA_ARGS__)
+    hipLaunchKernelGGL((gray_unit_fused_kernel<k, kFusedTH, with_kp, f64, ST, FT>), grid, block, 0, s, kernel_frames(frames), pyr, cs_out, end_out, \
+                       t, w, clip_hi, ##__VA_ARGS__)
                     if constexpr (with_kp) FUSED(kpu);
                     else FUSED();
 #undef FUSED
@@ -174,14 +175,15 @@ static int gray_pass_maps(silent_ctx* ctx, const silent_pyramid_plan* plan, cons
 template <typename FT>
 static int gray_pass_host(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames, const float* cs_kernel,
                           const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out, void* end_out, bool f16) {
-    TRY(gray_pass_checks(ctx, entry_name<FT>(f16 ? kGrayPassH : kGrayPass), plan, frames, n_frames, cs_kernel, end_bank, n_orient, pyr,
+    TRY(gray_pass_checks<FT>(ctx, entry_name<FT>(f16 ? kGrayPassH : kGrayPass), plan, frames != nullptr, n_frames, cs_kernel, end_bank, n_orient, pyr,
                          cs_out, end_out, f16, 3u));
     HostStage hs(ctx);
     const size_t px = (size_t)plan->tab.frame_px_out * n_frames, eb = f16 ? 2 : 4;
-    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * frame_px_bytes<FT>(plan->tab.C) * n_frames), p = hs.out(pyr, px * 4),
+    const int x = hs.in(frames_host(frames), frames_bytes(plan, frames, n_frames)), p = hs.out(pyr, px * 4),
               cs = hs.out(cs_out, px * eb), end = hs.out(end_out, px * eb * n_orient);
     return hs.run([&] {
-        return gray_pass_maps(ctx, plan, hs.dev<FT>(x), n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p), hs.dev<char>(cs),
+        const StagedFrames<FT> staged(frames, hs.dev<char>(x));
+        return gray_pass_maps(ctx, plan, staged.p, n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p), hs.dev<char>(cs),
                               hs.dev<char>(end), f16, 3u, nullptr);
     });
 }
@@ -288,4 +290,38 @@ SILENT_EXPORT int silent_gray_pass_u8x3(silent_ctx* ctx, const silent_pyramid_pl
     return gray_pass_host(ctx, plan, rgb8(frames), n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, maps_f16 != 0);
 } catch (...) {
     return on_exception(ctx, "silent_gray_pass_u8x3");
+}
+
+// Strided uint8 views (silent_hip.h): the view's own refusals and those of the *_u8 form under the view's name, then the frame kind
+// that reads it (with_view: a packed view takes the packed kernels).
+static int gray_pass_view(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_frame_view* view, int n_frames,
+                          const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out, void* end_out,
+                          bool f16, unsigned parts, silent_stream stream) {
+    const char* who = "silent_gray_pass_view";
+    TRY(check_view(ctx, who, plan, view, n_frames, nullptr));
+    TRY(gray_pass_checks<View8>(ctx, who, plan, true, n_frames, cs_kernel, end_bank, n_orient, pyr, cs_out, end_out, f16, parts));
+    return with_view(plan, view, n_frames, [&](auto frames) {
+        if (host) return gray_pass_host(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, f16);
+        return gray_pass_maps(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, f16, parts, stream);
+    });
+}
+
+SILENT_EXPORT int silent_gray_pass_view_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+                                            const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                            void* cs_out, void* end_out, int maps_f16, unsigned parts, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return gray_pass_view(ctx, false, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, maps_f16 != 0, parts,
+                          stream);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_pass_view_dev");
+}
+
+SILENT_EXPORT int silent_gray_pass_view(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+                                        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                        void* cs_out, void* end_out, int maps_f16) try {
+    NEED_CTX(ctx);
+    return gray_pass_view(ctx, true, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, maps_f16 != 0, 3u,
+                          nullptr);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_pass_view");
 }

@@ -814,13 +814,15 @@ SILENT_EXPORT int silent_rgb_keypoints_dev(silent_ctx* ctx, const float* pyr, co
 // a-10 -> a-9 -> a-8 -> a-11 on (pad_inwards(end), value) with K channels, sparse like silent_rgb_keypoints (SILENT_TUNE_GRAY bit 6:
 // the dense kernels for every level); selection = 0: a-11 on the value map (recognition_testing.py:90).
 // (everything the *_dev form refuses, before a launch and, in the host forms, before the batch is staged.)  FT: the frame element type
-// -- float, uint8_t (silent_gray_keypoints_u8[_dev]) or FrameRgb8 (silent_gray_keypoints_u8x3[_dev])
+// -- float, uint8_t (silent_gray_keypoints_u8[_dev]) or FrameRgb8 (silent_gray_keypoints_u8x3[_dev]) -- of the ENTRY POINT (the view
+// entry points check as a strided kind whatever kind then reads the view); has_frames / has_pyr / has_end: those arguments are not NULL
+// (the host forms need neither map from the caller)
 template <typename FT>
-static int gray_keypoints_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames,
-                                 const float* cs_kernel, const float* end_bank, int n_orient, const void* pyr, const void* end_out, int pad,
+static int gray_keypoints_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, bool has_frames, int n_frames,
+                                 const float* cs_kernel, const float* end_bank, int n_orient, bool has_pyr, bool has_end, int pad,
                                  int selection, const silent_extent* regions, float* peak_value_out, int64_t* idx,
                                  size_t cap_per_frame, int64_t* counts) {
-    if (!plan || !frames || !pyr || !cs_kernel || !end_bank || !end_out || !regions || !counts || (!idx && cap_per_frame))
+    if (!plan || !has_frames || !has_pyr || !cs_kernel || !end_bank || !has_end || !regions || !counts || (!idx && cap_per_frame))
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
     if constexpr (kFrameNarrow<FT>) TRY(check_narrow_frames(ctx, who, plan));
@@ -842,8 +844,8 @@ static int gray_keypoints_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, 
                               const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
                               size_t cap_per_frame, int64_t* counts, silent_stream stream) {
     const char* who = entry_name<FT>(kGrayKeypoints);
-    TRY(gray_keypoints_checks(ctx, who, plan, frames, n_frames, cs_kernel, end_bank, n_orient, pyr, end_out, pad, selection, regions,
-                              peak_value_out, idx, cap_per_frame, counts));
+    TRY(gray_keypoints_checks<FT>(ctx, who, plan, frames != nullptr, n_frames, cs_kernel, end_bank, n_orient, pyr != nullptr, end_out != nullptr,
+                                  pad, selection, regions, peak_value_out, idx, cap_per_frame, counts));
     hipStream_t s = (hipStream_t)stream;
     const silent_extent* levels = plan->extents.data();
     const int n_levels = plan->tab.n_levels;
@@ -1095,17 +1097,18 @@ static int gray_keypoints_host(silent_ctx* ctx, const silent_pyramid_plan* plan,
                                int64_t* idx, size_t cap_per_frame, int64_t* counts) {
     const char* who = entry_name<FT>(kGrayKeypoints);
     // (the host form accepts NULL pyr / end_out: the *_dev form needs both maps, they then live in the staging arena)
-    TRY(gray_keypoints_checks(ctx, who, plan, frames, n_frames, cs_kernel, end_bank, n_orient, frames, frames, pad, selection, regions,
-                              peak_value_out, idx, cap_per_frame, counts));
+    TRY(gray_keypoints_checks<FT>(ctx, who, plan, frames != nullptr, n_frames, cs_kernel, end_bank, n_orient, true, true, pad, selection, regions,
+                                  peak_value_out, idx, cap_per_frame, counts));
     HostStage hs(ctx);
     const size_t b1 = (size_t)plan->tab.frame_px_out * n_frames * 4;
-    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * frame_px_bytes<FT>(plan->tab.C) * n_frames),
+    const int x = hs.in(frames_host(frames), frames_bytes(plan, frames, n_frames)),
               p = pyr ? hs.out(pyr, b1) : hs.scratch(b1), cs = hs.out(cs_out, b1),
               end = end_out ? hs.out(end_out, b1 * n_orient) : hs.scratch(b1 * n_orient), v = hs.out(value_out, b1),
               pv = hs.out(peak_value_out, b1), i = hs.out(idx, (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
               n = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
     TRY(hs.run([&] {
-        return gray_keypoints_dev(ctx, plan, hs.dev<FT>(x), n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
+        const StagedFrames<FT> staged(frames, hs.dev<char>(x));
+        return gray_keypoints_dev(ctx, plan, staged.p, n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
                                   hs.dev<float>(cs), hs.dev<float>(end), pad, selection, top_percent, regions, hs.dev<float>(v),
                                   hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame, hs.dev<int64_t>(n), nullptr);
     }));
@@ -1146,6 +1149,48 @@ SILENT_EXPORT int silent_gray_keypoints_u8x3(silent_ctx* ctx, const silent_pyram
                                top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u8x3");
+}
+
+// Strided uint8 views (silent_hip.h): the view's own refusals and those of the *_u8 form under the view's name, then the frame kind
+// that reads it (with_view: a packed view takes the packed kernels).
+static int gray_keypoints_view(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_frame_view* view, int n_frames,
+                               const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out,
+                               float* end_out, int pad, int selection, double top_percent, const silent_extent* regions, float* value_out,
+                               float* peak_value_out, int64_t* idx, size_t cap_per_frame, int64_t* counts, silent_stream stream) {
+    const char* who = "silent_gray_keypoints_view";
+    TRY(check_view(ctx, who, plan, view, n_frames, nullptr));
+    // (the host form accepts NULL pyr / end_out, see gray_keypoints_host)
+    TRY(gray_keypoints_checks<View8>(ctx, who, plan, true, n_frames, cs_kernel, end_bank, n_orient, host || pyr, host || end_out, pad, selection,
+                                     regions, peak_value_out, idx, cap_per_frame, counts));
+    return with_view(plan, view, n_frames, [&](auto frames) {
+        if (host)
+            return gray_keypoints_host(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
+                                       top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts);
+        return gray_keypoints_dev(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
+                                  top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
+    });
+}
+
+SILENT_EXPORT int silent_gray_keypoints_view_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
+        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+        size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return gray_keypoints_view(ctx, false, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
+                               top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_keypoints_view_dev");
+}
+
+SILENT_EXPORT int silent_gray_keypoints_view(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
+        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+        size_t cap_per_frame, int64_t* counts) try {
+    NEED_CTX(ctx);
+    return gray_keypoints_view(ctx, true, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
+                               top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, nullptr);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_keypoints_view");
 }
 
 SILENT_EXPORT int silent_centroids(silent_ctx* ctx, const float* value, const silent_extent* levels, int n_levels,

@@ -50,6 +50,80 @@ const char* entry_name(int family) {
 }
 inline const silent::FrameRgb8* rgb8(const uint8_t* frames) { return reinterpret_cast<const silent::FrameRgb8*>(frames); }
 
+// ------------------------------------------------------------------------------------------ strided views (the *_view entry points)
+// The two strided frame kinds travel through the host templates as `const FT*` like the packed kinds: a pointer to the HOST struct
+// (strides + the data pointer); kernel_frames turns it into the kernel's argument, the struct by value.
+using View8 = silent::FrameStrided<unsigned char>;
+using View8x3 = silent::FrameStrided<silent::FrameRgb8>;
+template <typename FT>
+inline auto kernel_frames(const FT* frames) {
+    if constexpr (silent::kFrameStrided<FT>) return *frames;
+    else return frames;
+}
+// what a view refuses on its own (silent_hip.h) -- NULL, channels, a stride below its bound, a span of 2^63 bytes or more -- and its
+// span in bytes.  (H and W are read from the plan before the shared checks look at its context: any plan has them.)
+inline int check_view(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const silent_frame_view* v, int n_frames, size_t* span) {
+    if (!plan || !v || !v->data) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (v->channels != 1 && v->channels != 3) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view channels must be 1 or 3");
+    typedef unsigned __int128 u128;
+    const u128 H = (u128)plan->tab.H, W = (u128)plan->tab.W, ch = (u128)v->channels;
+    if (v->pixel_stride < v->channels) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view pixel_stride is below channels");
+    const u128 row = (W - 1) * (u128)v->pixel_stride + ch;
+    if (v->row_stride <= 0 || (u128)v->row_stride < row)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view row_stride is below (W - 1) * pixel_stride + channels");
+    const u128 frame = (H - 1) * (u128)v->row_stride + row;
+    if (n_frames > 1 && (v->frame_stride <= 0 || (u128)v->frame_stride < frame))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view frame_stride is below (H - 1) * row_stride + (W - 1) * pixel_stride + channels");
+    const u128 all = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->frame_stride : 0) + frame;
+    if (all > (u128)0x7fffffffffffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view spans more than 2^63 bytes");
+    if (span) *span = (size_t)all;
+    return SILENT_OK;
+}
+// f(frames) with the view as the frame kind that reads it: a packed view as the packed bytes (the kernels of *_u8 / *_u8x3), any other
+// as a strided kind.  (check_view passed.)
+template <class F>
+int with_view(const silent_pyramid_plan* plan, const silent_frame_view* v, int n_frames, F&& f) {
+    const long long H = plan->tab.H, W = plan->tab.W;
+    const bool packed = v->pixel_stride == v->channels && v->row_stride == W * v->pixel_stride && (n_frames <= 1 || v->frame_stride == H * v->row_stride);
+    if (v->channels == 1) {
+        if (packed) return f(v->data);
+        const View8 s{v->data, v->pixel_stride, v->row_stride, n_frames > 1 ? v->frame_stride : 0};
+        return f(&s);
+    }
+    if (packed) return f(rgb8(v->data));
+    const View8x3 s{v->data, v->pixel_stride, v->row_stride, n_frames > 1 ? v->frame_stride : 0};
+    return f(&s);
+}
+// (host-pointer forms) what is staged for `frames` -- the packed batch, or the span of a view (its strides passed check_view) -- and
+// the `frames` of the _dev form on the staged copy
+template <typename FT>
+inline const void* frames_host(const FT* frames) {
+    if constexpr (silent::kFrameStrided<FT>) return frames ? frames->data : nullptr;
+    else return frames;
+}
+template <typename FT>
+inline size_t frames_bytes(const silent_pyramid_plan* plan, const FT* f, int n_frames) {
+    if constexpr (silent::kFrameStrided<FT>)
+        return (size_t)((n_frames - 1) * f->frame_stride + (plan->tab.H - 1) * f->row_stride + (plan->tab.W - 1) * f->pixel_stride +
+                        (long long)sizeof(typename silent::FrameKind<FT>::px));
+    else
+        return (size_t)plan->tab.H * plan->tab.W * silent::frame_px_bytes<FT>(plan->tab.C) * n_frames;
+}
+template <typename FT>
+struct StagedFrames {
+    FT view{};      // (strided kinds: the view on the staged bytes)
+    const FT* p;
+    StagedFrames(const FT* host, const void* dev) {
+        if constexpr (silent::kFrameStrided<FT>) {
+            view = *host;
+            view.data = static_cast<const unsigned char*>(dev);
+            p = &view;
+        } else {
+            p = static_cast<const FT*>(dev);
+        }
+    }
+};
+
 // the uint8 frame kinds / float16 storage exist for single-channel plans with float32 accumulation only (plan: not NULL)
 inline int check_narrow_frames(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan) {
     if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
@@ -136,7 +210,8 @@ void with_stream_layout(const silent_pyramid_plan* plan, F&& f) {
 }
 
 // (silent_pyramid_api.hip) FT: the frame element type -- float, or unsigned char / silent::FrameRgb8 (uint8 frames, one channel /
-// interleaved colour, its value formed at the load: single-channel plans without SILENT_PLAN_ACCUM_F64; anything else is refused).
+// interleaved colour, its value formed at the load: single-channel plans without SILENT_PLAN_ACCUM_F64; anything else is refused),
+// or View8 / View8x3 (the same pixels in a strided view: `frames` then points to the host struct).
 // with_unit: also the unit levels (the gray pass produces them itself); with_region: also the general levels
 template <typename FT>
 int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames, float* pyr,
@@ -146,8 +221,8 @@ template <typename FT>
 int gray_pass_kp(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames, const float* cs_kernel,
                  const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const silent::GrayKp& kp,
                  hipStream_t s);
-// (each is defined, and instantiated for the three frame types, in its unit)
-#define SILENT_FRAME_TYPES(X) X(float) X(unsigned char) X(silent::FrameRgb8)
+// (each is defined, and instantiated for the five frame types, in its unit)
+#define SILENT_FRAME_TYPES(X) X(float) X(unsigned char) X(silent::FrameRgb8) X(View8) X(View8x3)
 #define X(FT)                                                                                                                              \
     extern template int launch_pyramid<FT>(silent_ctx*, const char*, const silent_pyramid_plan*, const FT*, int, float*, hipStream_t, bool, bool); \
     extern template int gray_pass_kp<FT>(silent_ctx*, const silent_pyramid_plan*, const FT*, int, const float*, const float*, int, float, float*, \

@@ -94,7 +94,7 @@ __device__ __forceinline__ int mirror_index(int i, int n) {
 // FMAs, a 6-row register window, 6 vertical FMAs, one store (scipy's six taps at zoom 1: unit_taps6, silent_gray.h).
 // F64: the six taps of each axis summed in float64 with float64 weights (horizontal, then vertical), rounded once.
 template <int C, bool F64 = false, typename FT = float>
-__global__ __launch_bounds__(256) void pyramid_unit_kernel(const FT* __restrict__ frames,
+__global__ __launch_bounds__(256) void pyramid_unit_kernel(frame_param<FT> frames,
                                                            float* __restrict__ pyr, const PyrTabT<F64> tab) {
     static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
     constexpr int R = kUnitTH;
@@ -117,7 +117,9 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(const FT* __restrict_
     const int y0 = ty * R;
     const int ox = xw0 + lane - 2;
     const int W = tab.W;
-    const FT* __restrict__ src = frames + (long long)frame * tab.H * W * C;
+    frame_src<FT> src;
+    if constexpr (kFrameStrided<FT>) src = frame_of(frames, frame);
+    else src = frames + (long long)frame * tab.H * W * C;
     float* __restrict__ dst = pyr + ((long long)frame * tab.frame_px_out + tab.px_off[l]) * C;
 
     acc_t<F64> wx[6], wy[6];
@@ -138,11 +140,18 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(const FT* __restrict_
     for (int i = 0; i < R + 5; ++i) {
         const long long sy = mirror_near(y0 - 2 + i, lv.src_h) + lv.src_y0;
 #pragma unroll
-        for (int ch = 0; ch < C; ++ch) in[i][ch] = (float)src[sy * W * C + sx + ch];
+        for (int ch = 0; ch < C; ++ch) {
+            if constexpr (kFrameStrided<FT>) in[i][ch] = src.at(sy, sx);   // (C == 1)
+            else in[i][ch] = (float)src[sy * W * C + sx + ch];
+        }
     }
 #pragma unroll
-    for (int ch = 0; ch < C; ++ch)
-        xcol[ch] = unit_edge_column(src + ch, (long long)W * C, xw0 + 62, lv.src_w, lv.src_x0, y0 - 2, R + 5, lv.src_h, lv.src_y0, lane, C);
+    for (int ch = 0; ch < C; ++ch) {
+        if constexpr (kFrameStrided<FT>)
+            xcol[ch] = unit_edge_column(src, W, xw0 + 62, lv.src_w, lv.src_x0, y0 - 2, R + 5, lv.src_h, lv.src_y0, lane);
+        else
+            xcol[ch] = unit_edge_column(src + ch, (long long)W * C, xw0 + 62, lv.src_w, lv.src_x0, y0 - 2, R + 5, lv.src_h, lv.src_y0, lane, C);
+    }
     // retire the loads before the first store (see gray_line_end_kernel)
 #pragma unroll
     for (int i = 0; i < R + 5; ++i)
@@ -202,8 +211,9 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(const FT* __restrict_
 // requirement: W % 4 == 0 puts every row start (frame * H * W + sy * W) and every group offset f on the dword grid relative to the
 // base, so the base address decides; any other base or width takes the one-element path.
 // FT = FrameRgb8 (interleaved uint8 colour, silent_common.h): always the one-element path, the value formed while staging.
+// FT = FrameStrided<PX> (strided views): the one-element path as well -- a pixel stride above the pixel's size has no dword of four pixels.
 template <int C, bool F64 = false, typename FT = float>
-__global__ __launch_bounds__(256) void pyramid_region_kernel(const FT* __restrict__ frames,
+__global__ __launch_bounds__(256) void pyramid_region_kernel(frame_param<FT> frames,
                                                              float* __restrict__ pyr, const PyrTabT<F64> tab) {
     static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
     constexpr int RW = region_w(C), SW = region_sw(C), SH = region_sh(C), ROWF = SW * C, VR = region_vr(C);
@@ -221,7 +231,9 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(const FT* __restric
     const int W = tab.W, H = tab.H;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const FT* __restrict__ src = frames + (long long)frame * H * W * C;
+    frame_src<FT> src;
+    if constexpr (kFrameStrided<FT>) src = frame_of(frames, frame);
+    else src = frames + (long long)frame * H * W * C;
 
     // A region no level has an output in is not staged at all (crop layouts: the reference's nested centre crops leave about half
     // of a 1080p frame's regions outside the outermost crop -- round 5: those blocks used to load their region and find nothing
@@ -243,8 +255,9 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(const FT* __restric
     // outside the frame are never referenced: rows are clamped, out-of-frame column groups are skipped.
     bool groups = ((W * C) & 3) == 0;
     if constexpr (kFrameBytes<FT>) groups = groups && (reinterpret_cast<unsigned long long>(frames) & 3ull) == 0;   // (block-uniform)
-    if constexpr (kFrameRgb8<FT>) groups = false;   // interleaved colour bytes: the one-element path (a pixel per element)
+    if constexpr (kFrameRgb8<FT> || kFrameStrided<FT>) groups = false;   // interleaved colour bytes, strided views: the one-element path (a pixel per element)
     if (groups) {
+      if constexpr (!kFrameStrided<FT>) {
         constexpr int V4 = ROWF / 4, NB = (SH * V4 + 255) / 256;
         typename std::conditional<kFrameBytes<FT>, uchar4, float4>::type v[NB];
 #pragma unroll
@@ -269,6 +282,7 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(const FT* __restric
                     *reinterpret_cast<float4*>(s_src + r * ROWF + q * 4) = v[k];
             }
         }
+      }
     } else {
         constexpr int NB = (SH * ROWF + 255) / 256;
         float v[NB];
@@ -278,7 +292,8 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(const FT* __restric
             const int r = p / ROWF, q = p - r * ROWF;
             const int sy = min(max(Y0 - kRegionHaloT + r, 0), H - 1);
             const long long f = min(max((long long)(X0 - kRegionHaloL) * C + q, 0ll), (long long)W * C - 1);
-            v[k] = (float)src[(long long)sy * W * C + f];
+            if constexpr (kFrameStrided<FT>) v[k] = src.at(sy, f);   // (C == 1: f is the column)
+            else v[k] = (float)src[(long long)sy * W * C + f];
         }
 #pragma unroll
         for (int k = 0; k < NB; ++k) {

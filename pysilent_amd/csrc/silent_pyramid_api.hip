@@ -643,10 +643,11 @@ static bool walk3_plan(const silent_ctx* ctx, const silent_pyramid_plan* plan, i
     return true;
 }
 
-// everything silent_pyramid*_dev refuses, before a launch (and, in the host forms, before the batch is staged)
+// everything silent_pyramid*_dev refuses, before a launch (and, in the host forms, before the batch is staged); FT: the frame kind of
+// the ENTRY POINT (the view entry points check as a strided kind whatever kind then reads the view), has_frames: its frames are not NULL
 template <typename FT>
-static int pyramid_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames, const float* pyr) {
-    if (!plan || !frames || !pyr) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+static int pyramid_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, bool has_frames, int n_frames, const float* pyr) {
+    if (!plan || !has_frames || !pyr) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
     if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
     if constexpr (kFrameNarrow<FT>) TRY(check_narrow_frames(ctx, who, plan));
@@ -656,7 +657,7 @@ static int pyramid_checks(silent_ctx* ctx, const char* who, const silent_pyramid
 template <typename FT>
 int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames, float* pyr,
                    hipStream_t s, bool with_unit, bool with_region) {
-    TRY(pyramid_checks(ctx, who, plan, frames, n_frames, pyr));
+    TRY(pyramid_checks<FT>(ctx, who, plan, frames != nullptr, n_frames, pyr));
     const PyrTab& tab = plan->tab;
     const long long b_unit = with_unit ? (long long)tab.unit_tiles_per_frame * n_frames : 0;
     const long long b_region = (with_region && tab.n_general) ? (long long)tab.regions_x * tab.regions_y * n_frames : 0;
@@ -676,12 +677,13 @@ int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* 
             const FusedTabT<decltype(F64)::value>& t = ft;   // (the float32 kernels take its FusedTab part)
             with_stream_layout(plan, [&](auto G, auto L) {
                 hipLaunchKernelGGL((pyramid_stream_kernel<1, decltype(G)::value, decltype(L)::value, decltype(F64)::value, FT>),
-                                   dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, frames, pyr, t, plan->stream);
+                                   dim3((unsigned)blocks), dim3(64 * kFusedWaves), 0, s, kernel_frames(frames), pyr, t, plan->stream);
             });
         });
     } else if constexpr (kFrameNarrow<FT>) {   // (single-channel, float32 accumulation: checked above)
-        if (b_unit) hipLaunchKernelGGL((pyramid_unit_kernel<1, false, FT>), dim3((unsigned)b_unit), dim3(256), 0, s, frames, pyr, tab);
-        if (b_region) hipLaunchKernelGGL((pyramid_region_kernel<1, false, FT>), dim3((unsigned)b_region), dim3(256), 0, s, frames, pyr, tab);
+        if (b_unit) hipLaunchKernelGGL((pyramid_unit_kernel<1, false, FT>), dim3((unsigned)b_unit), dim3(256), 0, s, kernel_frames(frames), pyr, tab);
+        if (b_region)
+            hipLaunchKernelGGL((pyramid_region_kernel<1, false, FT>), dim3((unsigned)b_region), dim3(256), 0, s, kernel_frames(frames), pyr, tab);
     } else if (tab.C == 3 && plan->walk_pyr_ok && with_unit && with_region && !(kopts & 3u) && walk3_plan(ctx, plan, n_frames, &w3t)) {
         // single-read RGB pyramid (pyramid_walk3_kernel, silent_walk_rgb.h); PYRAMID knob bits 1 / 2: unit + region kernels
         // union plans: the inner levels' first / last output rows and columns -- the last blocks of the same launch (PYRAMID knob 8:
@@ -756,11 +758,42 @@ SILENT_EXPORT int silent_pyramid_plan_walk_plans(const silent_pyramid_plan* plan
 template <typename FT>
 static int pyramid_host(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames, float* pyr) {
     const char* who = entry_name<FT>(kPyramid);
-    TRY(pyramid_checks(ctx, who, plan, frames, n_frames, pyr));
+    TRY(pyramid_checks<FT>(ctx, who, plan, frames != nullptr, n_frames, pyr));
     HostStage hs(ctx);
-    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * frame_px_bytes<FT>(plan->tab.C) * n_frames),
+    const int x = hs.in(frames_host(frames), frames_bytes(plan, frames, n_frames)),
               o = hs.out(pyr, (size_t)plan->tab.frame_px_out * plan->tab.C * 4 * n_frames);
-    return hs.run([&] { return launch_pyramid(ctx, who, plan, hs.dev<FT>(x), n_frames, hs.dev<float>(o), nullptr, true); });
+    return hs.run([&] {
+        const StagedFrames<FT> staged(frames, hs.dev<char>(x));
+        return launch_pyramid(ctx, who, plan, staged.p, n_frames, hs.dev<float>(o), nullptr, true);
+    });
+}
+
+// Strided uint8 views (silent_hip.h): the view's own refusals and those of the *_u8 form under the view's name, then the frame kind
+// that reads it (with_view: a packed view takes the packed kernels).
+static int pyramid_view(silent_ctx* ctx, const char* who, bool host, const silent_pyramid_plan* plan, const silent_frame_view* view, int n_frames,
+                        float* pyr, silent_stream stream) {
+    TRY(check_view(ctx, who, plan, view, n_frames, nullptr));
+    TRY(pyramid_checks<View8>(ctx, who, plan, true, n_frames, pyr));
+    return with_view(plan, view, n_frames, [&](auto frames) {
+        if (host) return pyramid_host(ctx, plan, frames, n_frames, pyr);
+        return launch_pyramid(ctx, who, plan, frames, n_frames, pyr, (hipStream_t)stream, true);
+    });
+}
+
+SILENT_EXPORT int silent_pyramid_view_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+                                          float* pyr, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return pyramid_view(ctx, "silent_pyramid_view", false, plan, frames, n_frames, pyr, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_view_dev");
+}
+
+SILENT_EXPORT int silent_pyramid_view(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+                                      float* pyr) try {
+    NEED_CTX(ctx);
+    return pyramid_view(ctx, "silent_pyramid_view", true, plan, frames, n_frames, pyr, nullptr);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_view");
 }
 
 SILENT_EXPORT int silent_pyramid(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,

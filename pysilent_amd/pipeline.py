@@ -131,7 +131,8 @@ class LineEndPipeline(object):
                  constants=None, center_dimensions=None, clip_hi=255.0, flat_policy="ieee", pad=2,
                  max_keypoints_per_frame=None, selection=False, top_percent=0.1, keep_selection_maps=False, value_map=None,
                  peak_value_map=None, orient_map=True, overlap=False, overlap_priorities=True, placement="auto", keypoints=False,
-                 regions=None, accumulation="float32", storage="float32", frame_dtype="float32", frame_channels=1):
+                 regions=None, accumulation="float32", storage="float32", frame_dtype="float32", frame_channels=1,
+                 frame_layout="packed"):
         # accumulation="float64" (mode "gray"): every op sums its taps in float64 and rounds once to float32, like the CPU oracle
         # (SILENT_PLAN_ACCUM_F64: the pyramid within 1 ulp of it, CS and end bit-identical to it on the same pyramid).  Checked first:
         # no GPU or torch work for a refused argument
@@ -154,6 +155,12 @@ class LineEndPipeline(object):
         # with mode "rgb", frame_dtype="float32" or accumulation="float64"
         self.frame_channels = _runtime.check_frame_channels(frame_channels, mode, frame_dtype, accumulation)
         self.frame_dtype = _runtime.check_frame_dtype(frame_dtype, mode, accumulation)
+        # frame_layout="strided" (mode "gray", frame_dtype="uint8"): step() takes ANY uint8 GPU view of the right shape with positive
+        # strides -- surface[:, :H, :W, None] of a pitched NV12 batch, bgra[..., :3], yuyv[:, :, ::2, None], a region of larger frames
+        # -- and the kernels read it in place (the silent_*_view entry points): no packing launch, no second copy of the batch, every
+        # map bit-identical to the packed pipeline's on the compacted pixels.  step_host is unchanged (its staging copy packs).
+        # Refused here as well: unknown names, mode "rgb", frame_dtype="float32", accumulation="float64"
+        self.frame_layout = _runtime.check_frame_layout(frame_layout, mode, frame_dtype, accumulation)
         import torch
         self.torch = torch
         self.mode = mode
@@ -581,7 +588,8 @@ class LineEndPipeline(object):
                     "gray_line_end_kernel (levels >= 1)" + (", float64 accumulation" if self.accumulation == "float64" else "")
                     + (", float16 CS / end maps" if self.storage == "float16" else "")
                     + (", uint8 frames" if self.frame_dtype == "uint8" else "")
-                    + (" of 3 interleaved channels (value formed at the load)" if self._colour_frames else ""))
+                    + (" of 3 interleaved channels (value formed at the load)" if self._colour_frames else "")
+                    + (", read in place from a strided view" if getattr(self, "frame_layout", "packed") == "strided" else ""))
         return ("single-read RGB pyramid (pyramid_walk3_kernel), fused RGB chain, max/min + fused selection "
                 "(top 10 % > NMS > value), cell-max / count / scan / write keypoint kernels")
 
@@ -590,14 +598,30 @@ class LineEndPipeline(object):
         return C.c_void_p(self.torch.cuda.current_stream(self.tdev).cuda_stream)
 
     def _check_frames(self, frames):
+        if self.frame_layout == "strided":
+            shapes = ((self.batch,) + self.frame_shape,) + (((self.batch,) + self.frame_shape[:2],) if self.frame_shape[2] == 1 else ())
+            if not _runtime.is_torch_tensor(frames) or tuple(frames.shape) not in shapes or frames.dtype != self.torch.uint8 \
+                    or not frames.is_cuda:
+                raise ValueError("frames must be a uint8 GPU tensor (any view with positive strides) of shape %s" % (shapes[0],))
+            return
         want = self.torch.uint8 if self.frame_dtype == "uint8" else self.torch.float32
         if tuple(frames.shape) != (self.batch,) + self.frame_shape or frames.dtype != want \
                 or not frames.is_cuda or not frames.is_contiguous():
             raise ValueError("frames must be a contiguous %s GPU tensor of shape %s" %
                              (self.frame_dtype, (self.batch,) + self.frame_shape,))
 
+    def _frames_arg(self, frame_ptr, frames):
+        """The frames argument of an entry point gray_entry chose: the view of a strided pipeline, the address otherwise."""
+        if self.frame_layout == "strided":
+            return frame_ptr(_runtime.frame_view_of(frames, self.frame_shape[2]))
+        return frame_ptr(frames.data_ptr())
+
     def run_pyramid(self, frames, stream=None):
         self._check_frames(frames)
+        if self.frame_layout == "strided":
+            self.ctx.check(self._lib.silent_pyramid_view_dev(self.ctx.handle, self.plan.handle, self._frames_arg(_lib.view_ptr, frames),
+                                                             self.batch, C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
+            return
         if self.frame_dtype == "uint8":
             fn = self._lib.silent_pyramid_u8x3_dev if self._colour_frames else self._lib.silent_pyramid_u8_dev
             self.ctx.check(fn(self.ctx.handle, self.plan.handle, _lib.byte_ptr(frames.data_ptr()),
@@ -665,8 +689,9 @@ class LineEndPipeline(object):
         write the end map fold the padded value map into what the tail needs; pyramid / cs / end are those of run_gray_pass."""
         self._check_frames(frames)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        name, frame_ptr, _, _ = _lib.gray_entry("gray_keypoints", self.frame_dtype, self.frame_shape[2], dev=True)
-        fn, fp = getattr(self._lib, "silent_" + name + "_dev"), frame_ptr(frames.data_ptr())
+        name, frame_ptr, _, _ = _lib.gray_entry("gray_keypoints", self.frame_dtype, self.frame_shape[2], dev=True,
+                                                frame_layout=self.frame_layout)
+        fn, fp = getattr(self._lib, "silent_" + name + "_dev"), self._frames_arg(frame_ptr, frames)
         self.ctx.check(fn(
             self.ctx.handle, self.plan.handle, fp, self.batch, C.c_void_p(self.consts["cs"].ctypes.data),
             C.c_void_p(self.consts["end"].ctypes.data), self.n_orient, self.clip_hi, p(self.pyr), p(self.cs), p(self.end), self.pad,
@@ -678,9 +703,10 @@ class LineEndPipeline(object):
         levels, fused pyramid + CS + end kernel for the unit levels, filter kernel for the rest.  ``parts``: 1 = pyramid + unit
         levels only, 2 = the filter of the remaining levels only (silent_gray_pass_parts_dev; the halves of an overlapped step)."""
         self._check_frames(frames)
-        name, frame_ptr, map_ptr, tail = _lib.gray_entry("gray_pass", self.frame_dtype, self.frame_shape[2], self.storage, True, parts)
+        name, frame_ptr, map_ptr, tail = _lib.gray_entry("gray_pass", self.frame_dtype, self.frame_shape[2], self.storage, True, parts,
+                                                         frame_layout=self.frame_layout)
         self.ctx.check(getattr(self._lib, "silent_" + name + "_dev")(
-            self.ctx.handle, self.plan.handle, frame_ptr(frames.data_ptr()), self.batch, C.c_void_p(self.consts["cs"].ctypes.data),
+            self.ctx.handle, self.plan.handle, self._frames_arg(frame_ptr, frames), self.batch, C.c_void_p(self.consts["cs"].ctypes.data),
             C.c_void_p(self.consts["end"].ctypes.data), self.n_orient, self.clip_hi, C.c_void_p(self.pyr.data_ptr()),
             map_ptr(self.cs.data_ptr()), map_ptr(self.end.data_ptr()), *(tail + (stream or self._stream(),))))
 
