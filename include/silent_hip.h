@@ -287,6 +287,57 @@ int silent_gray_pass_view_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, 
                               const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
                               void* end_out, int maps_f16, unsigned parts, silent_stream stream);
 
+/* uint16 frames, read as they are: 10 / 12 / 16-bit machine-vision and scientific cameras (Mono10 / Mono12 / Mono16), thermal and
+ * depth sensors (Y16, Z16), 16-bit TIFF / PNG, and the luma of the P010 / P016 surfaces a hardware decoder hands over for 10-bit
+ * HEVC / AV1.  The twins of the *_u8 entry points -- same argument lists, maps_f16 / parts / stream arguments, status codes and order
+ * of refusals -- for frames: [n_frames, H, W] unsigned 16-bit integers in native byte order, 2-BYTE ALIGNED (an odd address is
+ * SILENT_E_INVALID).  The frame-reading kernels load the element UNSIGNED and convert it in a register -- uint16 -> float32 is exact,
+ * 65535 < 2^24 -- so every output is IDENTICAL, bit for bit, to that of the float32-frame entry point given (float)frames[i]:
+ * silent_pyramid[_dev], silent_gray_pass_parts_dev (maps_f16 = 0), silent_gray_pass_h_dev (maps_f16 = 1) and
+ * silent_gray_keypoints[_dev].  The host-pointer forms stage 2 * H * W * n_frames BYTES of frames.
+ * No scaling and no shift.  P010 keeps its 10 bits in the HIGH bits of each element (v << 6): the pass is homogeneous of degree one
+ * up to clip_hi, and a factor of 64 is exact in binary floating point, so a P010 caller passes clip_hi * 64 and reads maps that are
+ * exactly 64 times those of the 10-bit values.
+ * float16 maps (maps_f16 = 1) keep their rule -- the float32 result rounded to nearest even, overflow to +-inf: with full-range
+ * 16-bit data and clip_hi above 65504 a stored map element can be +inf, exactly where silent_gray_pass_h_dev stores it for the
+ * widened frame.
+ * Not built: signed int16, interleaved 16-bit colour, 3-channel plans, SILENT_PLAN_ACCUM_F64 plans (both SILENT_E_UNSUPPORTED),
+ * byte-swapped data.  (ABI additions only: SILENT_ABI_VERSION is unchanged.) */
+int silent_pyramid_u16(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames, float* pyr);
+int silent_pyramid_u16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames, float* pyr,
+                           silent_stream stream);
+int silent_gray_pass_u16(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames,
+                         const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
+                         void* end_out, int maps_f16);
+int silent_gray_pass_u16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames,
+                             const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
+                             void* end_out, int maps_f16, unsigned parts, silent_stream stream);
+
+/* Strided uint16 frames, read in place: the valid part of a pitched P010 / P016 surface, one channel of 16-bit RGBA, a window of
+ * larger frames.  As silent_frame_view with one uint16 element per pixel: pixel (frame f, row y, column x) is the 2 bytes at
+ *     data + f * frame_stride + y * row_stride + x * pixel_stride        (BYTE strides, 64-bit arithmetic)
+ * and a call reads only those 2 bytes of each addressed pixel, all inside [data, data + span),
+ *     span = (n_frames - 1) * frame_stride + (H - 1) * row_stride + (W - 1) * pixel_stride + 2.
+ * The twins of the *_view entry points: every output IDENTICAL, bit for bit, to that of the *_u16 entry point on the compacted copy
+ * of the same pixels; status codes and order of refusals as *_view with 2 for `channels`, and in addition SILENT_E_INVALID for an
+ * odd data address or an odd stride.  A view that IS packed -- pixel_stride == 2, row_stride == 2 * W, frame_stride == H * row_stride
+ * (or n_frames == 1) -- runs the kernels of the *_u16 entry point.  Host-pointer forms stage exactly `span` bytes. */
+typedef struct silent_frame_view16 {
+    const uint16_t* data;  /* pixel (0, 0) of frame 0; 2-byte aligned */
+    int64_t pixel_stride;  /* bytes; even, >= 2 */
+    int64_t row_stride;    /* bytes; even, >= (W - 1) * pixel_stride + 2 */
+    int64_t frame_stride;  /* bytes; even, >= (H - 1) * row_stride + (W - 1) * pixel_stride + 2; not read when n_frames == 1 */
+} silent_frame_view16;
+int silent_pyramid_view16(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view16* frames, int n_frames, float* pyr);
+int silent_pyramid_view16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view16* frames, int n_frames,
+                              float* pyr, silent_stream stream);
+int silent_gray_pass_view16(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view16* frames, int n_frames,
+                            const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
+                            void* end_out, int maps_f16);
+int silent_gray_pass_view16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view16* frames, int n_frames,
+                                const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
+                                void* end_out, int maps_f16, unsigned parts, silent_stream stream);
+
 /* 1 when silent_gray_pass runs this plan through the single-read stream kernel (one unit-zoom level and every
  * other level resampling the same crop with a step > 1.25: classic whole-frame pyramids), 0 when it falls
  * back to region + unit-fused + filter kernels (e.g. the reference's centred-crop layout).  The same for
@@ -610,6 +661,27 @@ int silent_gray_keypoints_view_dev(silent_ctx* ctx, const silent_pyramid_plan* p
                                    float* cs_out, float* end_out, int pad, int selection, double top_percent,
                                    const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
                                    size_t cap_per_frame, int64_t* counts, silent_stream stream);
+
+/* The same on uint16 frames (see silent_gray_pass_u16) and on a strided uint16 view (silent_gray_pass_view16): every output is that
+ * of silent_gray_keypoints[_dev] on the widened frame / of silent_gray_keypoints_u16[_dev] on the compacted copy of the view's pixels. */
+int silent_gray_keypoints_u16(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames,
+                              const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out,
+                              float* end_out, int pad, int selection, double top_percent, const silent_extent* regions,
+                              float* value_out, float* peak_value_out, int64_t* idx, size_t cap_per_frame, int64_t* counts);
+int silent_gray_keypoints_u16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames,
+                                  const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                  float* cs_out, float* end_out, int pad, int selection, double top_percent,
+                                  const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+                                  size_t cap_per_frame, int64_t* counts, silent_stream stream);
+int silent_gray_keypoints_view16(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view16* frames, int n_frames,
+                                 const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out,
+                                 float* end_out, int pad, int selection, double top_percent, const silent_extent* regions,
+                                 float* value_out, float* peak_value_out, int64_t* idx, size_t cap_per_frame, int64_t* counts);
+int silent_gray_keypoints_view16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view16* frames, int n_frames,
+                                     const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
+                                     float* cs_out, float* end_out, int pad, int selection, double top_percent,
+                                     const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
+                                     size_t cap_per_frame, int64_t* counts, silent_stream stream);
 
 /* What the sparse tail of the LAST silent_rgb_keypoints[_dev] / silent_gray_keypoints[_dev] call of this context did (synchronises that call's stream):
  * stats[0] = 1 if it ran sparse, [1] = (frame, level) pairs, [2] = pairs it handed to the dense kernels, [3] = candidate

@@ -73,6 +73,11 @@ class FrameView(C.Structure):
                 ("frame_stride", C.c_int64)]
 
 
+class FrameView16(C.Structure):
+    """silent_frame_view16 (include/silent_hip.h): strided uint16 frames, three BYTE strides (all even)."""
+    _fields_ = [("data", C.c_void_p), ("pixel_stride", C.c_int64), ("row_stride", C.c_int64), ("frame_stride", C.c_int64)]
+
+
 class SilentLibraryError(RuntimeError):
     """libsilent_hip.so is missing or cannot be loaded."""
 
@@ -84,6 +89,8 @@ _fp = C.c_void_p          # float* passed as an address (host ndarray.ctypes.dat
 _hp = C.POINTER(C.c_uint16)   # a float16 map (silent_gray_pass_h: IEEE binary16 as uint16_t*); half_ptr() makes one from an address
 _bp = C.POINTER(C.c_uint8)    # uint8 frames (the *_u8 and *_u8x3 entry points); byte_ptr() makes one from an address
 _wp = C.POINTER(FrameView)    # a strided uint8 view (the *_view entry points); view_ptr() makes one from _runtime.frame_view_of's tuple
+_sp = C.POINTER(C.c_uint16)   # uint16 frames (the *_u16 entry points); short_ptr() makes one from an address
+_xp = C.POINTER(FrameView16)  # a strided uint16 view (the *_view16 entry points); view16_ptr() makes one from frame_view_of's tuple
 _ep = C.POINTER(Extent)
 _i, _u, _f, _d, _sz = C.c_int, C.c_uint, C.c_float, C.c_double, C.c_size_t
 
@@ -129,6 +136,14 @@ _SIGNATURES = {
     "silent_pyramid_view_dev": [_vp, _vp, _wp, _i, _fp, _vp],
     "silent_gray_pass_view": [_vp, _vp, _wp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_view_dev": [_vp, _vp, _wp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i, _u, _vp],
+    "silent_pyramid_u16": [_vp, _vp, _sp, _i, _fp],
+    "silent_pyramid_u16_dev": [_vp, _vp, _sp, _i, _fp, _vp],
+    "silent_gray_pass_u16": [_vp, _vp, _sp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
+    "silent_gray_pass_u16_dev": [_vp, _vp, _sp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i, _u, _vp],
+    "silent_pyramid_view16": [_vp, _vp, _xp, _i, _fp],
+    "silent_pyramid_view16_dev": [_vp, _vp, _xp, _i, _fp, _vp],
+    "silent_gray_pass_view16": [_vp, _vp, _xp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
+    "silent_gray_pass_view16_dev": [_vp, _vp, _xp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i, _u, _vp],
     "silent_pyramid_plan_is_streamable": [_vp],
     "silent_pyramid_plan_walk_plans": [_vp, C.POINTER(C.c_int)],
     "silent_gather_d2h": [_vp, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), _i, _vp],
@@ -175,6 +190,10 @@ _SIGNATURES = {
     "silent_gray_keypoints_u8x3_dev": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp, _vp],
     "silent_gray_keypoints_view": [_vp, _vp, _wp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp],
     "silent_gray_keypoints_view_dev": [_vp, _vp, _wp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp, _vp],
+    "silent_gray_keypoints_u16": [_vp, _vp, _sp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp],
+    "silent_gray_keypoints_u16_dev": [_vp, _vp, _sp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp, _vp],
+    "silent_gray_keypoints_view16": [_vp, _vp, _xp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp],
+    "silent_gray_keypoints_view16_dev": [_vp, _vp, _xp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp, _vp],
     "silent_sparse_tail_stats": [_vp, C.POINTER(C.c_int64)],
     "silent_rgb_chain_stream": [C.POINTER(RgbChainParams), C.c_uint, _fp, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "silent_rgb_line_end": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _fp, _fp, _fp],
@@ -204,6 +223,11 @@ def byte_ptr(address):
     return None if address is None else C.cast(C.c_void_p(int(address)), _bp)
 
 
+def short_ptr(address):
+    """A host or device address as the const uint16_t* of a uint16 frames argument (None: NULL)."""
+    return None if address is None else C.cast(C.c_void_p(int(address)), _sp)
+
+
 def void_ptr(address):
     """A host or device address as a void* / float* argument (None: NULL)."""
     return None if address is None else C.c_void_p(int(address))
@@ -218,14 +242,26 @@ def view_ptr(view):
     return C.pointer(FrameView(int(address), int(channels), int(pixel_stride), int(row_stride), int(frame_stride)))
 
 
+def view16_ptr(view):
+    """The same tuple for a uint16 view (its channels entry is 1) as the const silent_frame_view16* of a *_view16 entry point."""
+    if view is None:
+        return None
+    address, _channels, pixel_stride, row_stride, frame_stride = view
+    return C.pointer(FrameView16(int(address), int(pixel_stride), int(row_stride), int(frame_stride)))
+
+
 def gray_entry(family, frame_dtype="float32", frame_channels=1, storage="float32", dev=False, parts=None, frame_layout="packed"):
     """The call shape of the gray pass ("gray_pass") or its keypoint form ("gray_keypoints") for a frame layout, a map storage and the
     host or _dev form: (name, frame_ptr, map_ptr, tail) -- the entry point silent_<name>[_dev], what makes its frames argument and its
     cs_out / end_out arguments from an address, and the arguments that follow end_out (maps_f16, parts) before the stream.  parts:
-    None = the whole pass; 1 / 2 / 3 = the halves of an overlapped step (_dev forms).  frame_layout="strided" (uint8 frames): the
-    *_view entry points, whose frames argument view_ptr makes from a view tuple (_runtime.frame_view_of), not from an address."""
-    sfx = "" if frame_dtype != "uint8" else "_view" if frame_layout == "strided" else "_u8x3" if frame_channels == 3 else "_u8"
-    frame_ptr = view_ptr if sfx == "_view" else byte_ptr if sfx else void_ptr
+    None = the whole pass; 1 / 2 / 3 = the halves of an overlapped step (_dev forms).  frame_layout="strided" (uint8 / uint16 frames): the
+    *_view / *_view16 entry points, whose frames argument view_ptr / view16_ptr makes from a view tuple (_runtime.frame_view_of), not
+    from an address.  frame_dtype="uint16": the *_u16 / *_view16 entry points (one channel)."""
+    if frame_dtype == "uint16":
+        sfx = "_view16" if frame_layout == "strided" else "_u16"
+    else:
+        sfx = "" if frame_dtype != "uint8" else "_view" if frame_layout == "strided" else "_u8x3" if frame_channels == 3 else "_u8"
+    frame_ptr = view_ptr if sfx == "_view" else view16_ptr if sfx == "_view16" else short_ptr if sfx == "_u16" else byte_ptr if sfx else void_ptr
     if family != "gray_pass":
         return family + sfx, frame_ptr, void_ptr, ()
     parts_arg = (3 if parts is None else int(parts),) if dev else ()

@@ -244,9 +244,10 @@ class _Operand(object):
 
     def __init__(self, x, channels=None, ctx=None, frame_dtype="float32", frame_layout="packed"):
         self.packed = isinstance(x, PackedPyramid)
-        strided = frame_layout == "strided"      # (uint8 frames: checked by the caller) the frames are a view, passed as it is
-        if frame_dtype == "uint8" and not strided:
-            _require_uint8(x)
+        strided = frame_layout == "strided"      # (uint8 / uint16 frames: checked by the caller) the frames are a view, passed as it is
+        narrow = frame_dtype in ("uint8", "uint16")
+        if narrow and not strided:
+            _require_narrow(x, frame_dtype)
         if self.packed:
             self.src = x
             buf = x.data
@@ -269,7 +270,7 @@ class _Operand(object):
             import torch
             if not buf.is_cuda:
                 raise TypeError("torch tensors must live on the GPU (use a numpy array for host data)")
-            if frame_dtype != "uint8":
+            if not narrow:
                 buf = as_float32(buf)
             self.device = buf.device.index or 0
             self.stream = C.c_void_p(torch.cuda.current_stream(buf.device).cuda_stream)
@@ -277,14 +278,17 @@ class _Operand(object):
             self._torch_device = buf.device
         else:
             if not strided:
-                buf = np.ascontiguousarray(buf, dtype=np.uint8 if frame_dtype == "uint8" else np.float32)
+                buf = np.ascontiguousarray(buf, dtype=getattr(np, frame_dtype) if narrow else np.float32)
             self.device = None
             self.stream = None
             self.ptr = C.c_void_p(buf.ctypes.data)
         if strided:
-            self.ptr = _lib.view_ptr(frame_view_of(buf, self.c))
+            view = frame_view_of(buf, self.c, frame_dtype)
+            self.ptr = _lib.view16_ptr(view) if frame_dtype == "uint16" else _lib.view_ptr(view)
         elif frame_dtype == "uint8":
             self.ptr = _lib.byte_ptr(self.ptr.value)
+        elif frame_dtype == "uint16":
+            self.ptr = _lib.short_ptr(self.ptr.value)
         self.buf = buf                                  # keep alive
         self.frame_px = sum(h * w for h, w in self.extents)
         self.levels = (_lib.Extent * len(self.extents))(*[_lib.Extent(h, w) for h, w in self.extents])
@@ -323,38 +327,53 @@ class _Operand(object):
         return (self.levels, self.n_levels, self.n_frames)
 
 
-def _require_uint8(x):
-    """frame_dtype="uint8": the frames are passed as they are, so they must BE uint8 -- an ndarray, or a contiguous GPU tensor."""
+def _require_narrow(x, frame_dtype="uint8"):
+    """frame_dtype="uint8" / "uint16": the frames are passed as they are, so they must BE of that type (uint16: in native byte order)
+    -- an ndarray, or a contiguous GPU tensor."""
     if isinstance(x, np.ndarray):
-        ok = x.dtype == np.uint8
+        ok = x.dtype == getattr(np, frame_dtype) and x.dtype.isnative
     elif is_torch_tensor(x):
         import torch
-        ok = x.dtype == torch.uint8 and x.is_contiguous()
+        ok = x.dtype == getattr(torch, frame_dtype) and x.is_contiguous()
     else:
         raise TypeError(TYPE_ERROR_MESSAGE)
     if not ok:
-        raise ValueError("frame_dtype='uint8' takes a uint8 ndarray or a contiguous uint8 GPU tensor (nothing is converted), got %s"
-                         % (x.dtype,))
+        raise ValueError("frame_dtype='%s' takes a %s ndarray or a contiguous %s GPU tensor (nothing is converted), got %s"
+                         % (frame_dtype, frame_dtype, frame_dtype, x.dtype))
 
 
-def frame_view_of(frames, channels):
+def _require_uint8(x):
+    _require_narrow(x, "uint8")
+
+
+def frame_view_of(frames, channels, frame_dtype=None):
     """A uint8 array -- torch tensor or ndarray, [n, H, W, channels] with channels 1 or 3, or [n, H, W] for one channel -- as the
     view the silent_*_view entry points read in place: (address, channels, pixel_stride, row_stride, frame_stride), strides in bytes.
+    A uint16 array (native byte order; channels 1: [n, H, W] or [n, H, W, 1]) gives the view of the silent_*_view16 entry points in
+    the same form, its strides in BYTES as well (even) -- p010[:, :H, :W] of pitched surfaces, rgba16[..., 1], a window of larger
+    frames.  frame_dtype: None takes either type, "uint8" / "uint16" only that one.
     Any positive strides do (a pitched surface, bgra[..., :3], yuyv[:, :, ::2, None], a region of a larger frame, every second
     frame); a ValueError for anything but uint8, for a negative or zero stride ([::-1], a broadcast), for strides under which pixels
     or rows overlap, and for three channels that are not adjacent bytes.  An axis of length 1 has no stride to speak of: it is
     given the smallest valid one."""
     if isinstance(channels, bool) or not isinstance(channels, int) or channels not in FRAME_CHANNELS:
         raise ValueError("frame_view_of: channels must be 1 or 3, got %r" % (channels,))
+    if frame_dtype not in (None, "uint8", "uint16"):
+        raise ValueError("frame_view_of: frame_dtype must be 'uint8' or 'uint16', got %r" % (frame_dtype,))
     if isinstance(frames, np.ndarray):
-        ok, strides, address = frames.dtype == np.uint8, tuple(int(s) for s in frames.strides), frames.ctypes.data
+        wide = frames.dtype == np.uint16 and frames.dtype.isnative
+        ok, strides, address = frames.dtype == np.uint8 or wide, tuple(int(s) for s in frames.strides), frames.ctypes.data
     elif is_torch_tensor(frames):
         import torch
-        ok, strides, address = frames.dtype == torch.uint8, tuple(int(s) for s in frames.stride()), frames.data_ptr()
+        wide = frames.dtype == torch.uint16
+        ok, strides, address = frames.dtype == torch.uint8 or wide, tuple(int(s) * (2 if wide else 1) for s in frames.stride()), frames.data_ptr()
     else:
         raise TypeError(TYPE_ERROR_MESSAGE)
-    if not ok:
-        raise ValueError("frame_view_of takes uint8 frames (nothing is converted), got %s" % (frames.dtype,))
+    if not ok or (frame_dtype is not None and wide != (frame_dtype == "uint16")):
+        raise ValueError("frame_view_of takes %s frames (nothing is converted), got %s"
+                         % ("uint8 or uint16" if frame_dtype is None else frame_dtype, frames.dtype))
+    if wide:
+        return _frame_view16_of(frames, channels, strides, address)
     shape = tuple(int(s) for s in frames.shape)
     if len(shape) == 3 and channels == 1:
         shape, strides = shape + (1,), strides + (1,)
@@ -379,6 +398,35 @@ def frame_view_of(frames, channels):
     if pixel < channels or row < row_min or frame < frame_min:
         raise ValueError("frame_view_of: pixels, rows or frames of the view overlap (strides %s for shape %s)" % (strides, shape))
     return int(address), channels, pixel, row, frame
+
+
+def _frame_view16_of(frames, channels, strides, address):
+    """frame_view_of for uint16 frames: one 2-byte element per pixel, `strides` in bytes."""
+    if channels != 1:
+        raise ValueError("frame_view_of: uint16 frames have one channel, got channels=%r" % (channels,))
+    shape = tuple(int(s) for s in frames.shape)
+    if len(shape) == 3:
+        shape, strides = shape + (1,), strides + (2,)
+    if len(shape) != 4 or shape[3] != 1:
+        raise ValueError("frame_view_of: expected [n, H, W, 1] or [n, H, W], got shape %s" % (tuple(frames.shape),))
+    n, h, w, _ = shape
+    if min(n, h, w) < 1:
+        raise ValueError("frame_view_of: empty frames, shape %s" % (tuple(frames.shape),))
+    sn, sh, sw, _ = strides
+    for name, length, stride in (("frame", n, sn), ("row", h, sh), ("pixel", w, sw)):
+        if length > 1 and stride <= 0:
+            raise ValueError("frame_view_of: %s stride %d: a view is never flipped or broadcast (strides must be positive)"
+                             % (name, stride))
+    pixel = sw if w > 1 else 2
+    row_min = (w - 1) * pixel + 2
+    row = sh if h > 1 else row_min
+    frame_min = (h - 1) * row + row_min
+    frame = sn if n > 1 else frame_min
+    if pixel < 2 or row < row_min or frame < frame_min:
+        raise ValueError("frame_view_of: pixels, rows or frames of the view overlap (strides %s for shape %s)" % (strides, shape))
+    if (address | pixel | row | frame) & 1:
+        raise ValueError("frame_view_of: uint16 frames need an even address and even byte strides (strides %s)" % (strides,))
+    return int(address), 1, pixel, row, frame
 
 
 def _kernel_arg(k, c_in=None):
@@ -815,21 +863,22 @@ def check_storage(storage, mode="gray", accumulation="float32", keypoints=False)
     return storage
 
 
-FRAME_DTYPES = ("float32", "uint8")
+FRAME_DTYPES = ("float32", "uint8", "uint16")
 
 
 def check_frame_dtype(frame_dtype, mode="gray", accumulation="float32"):
     """The frame_dtype argument of PyramidPlan.run / gray_pass / gray_keypoints and LineEndPipeline: "float32" (default: whatever
     comes is widened to float32 first) or "uint8" (uint8 frames read as they are by the silent_*_u8 entry points -- no widening cast,
-    no float32 copy of the batch; bit-identical results).  The name is checked first; then the combinations uint8 frames do not
-    exist for: mode "rgb" and accumulation="float64"."""
+    no float32 copy of the batch; bit-identical results) or "uint16" (the same for unsigned 16-bit frames in native byte order, the
+    silent_*_u16 entry points: Mono10 / 12 / 16, Y16, the luma of P010 -- the value is (float)v, no shift and no scale).  The name is
+    checked first; then the combinations uint8 / uint16 frames do not exist for: mode "rgb" and accumulation="float64"."""
     if frame_dtype not in FRAME_DTYPES:
-        raise ValueError("frame_dtype must be 'float32' or 'uint8', got %r" % (frame_dtype,))
-    if frame_dtype == "uint8":
+        raise ValueError("frame_dtype must be 'float32' or 'uint8' or 'uint16', got %r" % (frame_dtype,))
+    if frame_dtype != "float32":
         if mode != "gray":
-            raise ValueError("frame_dtype='uint8' is for mode 'gray' (the RGB kernels read float32 frames)")
+            raise ValueError("frame_dtype='%s' is for mode 'gray' (the RGB kernels read float32 frames)" % frame_dtype)
         if accumulation == "float64":
-            raise ValueError("frame_dtype='uint8' does not combine with accumulation='float64'")
+            raise ValueError("frame_dtype='%s' does not combine with accumulation='float64'" % frame_dtype)
     return frame_dtype
 
 
@@ -859,17 +908,17 @@ FRAME_LAYOUTS = ("packed", "strided")
 
 def check_frame_layout(frame_layout, mode="gray", frame_dtype="float32", accumulation="float32"):
     """The frame_layout argument of PyramidPlan.run / gray_pass / gray_keypoints and LineEndPipeline: "packed" (default: contiguous
-    [n, H, W] or [n, H, W, 3] frames) or "strided" (any uint8 view with positive strides -- a pitched decoder surface, BGRA, YUYV
+    [n, H, W] or [n, H, W, 3] frames) or "strided" (any uint8 or uint16 view with positive strides -- a pitched decoder surface, BGRA, YUYV
     luma, a region of a larger frame -- read in place by the silent_*_view entry points: no packing launch, no second copy of the
     batch; bit-identical to the packed path on the compacted pixels).  The name is checked first; then what "strided" needs: mode
-    "gray", frame_dtype="uint8" and float32 accumulation."""
+    "gray", frame_dtype="uint8" or "uint16" and float32 accumulation."""
     if frame_layout not in FRAME_LAYOUTS:
         raise ValueError("frame_layout must be 'packed' or 'strided', got %r" % (frame_layout,))
     if frame_layout == "strided":
         if mode != "gray":
             raise ValueError("frame_layout='strided' is for mode 'gray' (the RGB kernels read packed float32 frames)")
-        if frame_dtype != "uint8":
-            raise ValueError("frame_layout='strided' needs frame_dtype='uint8' (float32 frames are read packed only)")
+        if frame_dtype not in ("uint8", "uint16"):
+            raise ValueError("frame_layout='strided' needs frame_dtype='uint8' or 'uint16' (float32 frames are read packed only)")
         if accumulation == "float64":
             raise ValueError("frame_layout='strided' does not combine with accumulation='float64'")
     return frame_layout
@@ -898,7 +947,8 @@ class PyramidPlan(object):
         """[n, H, W, C] frames of this plan (ndarray, or torch GPU tensor) as an operand on the plan's context.  frame_dtype="uint8":
         a uint8 ndarray or contiguous uint8 GPU tensor, passed as it is (anything else is a ValueError); "float32": widened.
         frame_channels=3 (single-channel plans, uint8): the frames are [n, H, W, 3] interleaved colour.  frame_layout="strided"
-        (uint8): any view with positive strides (frame_view_of), passed as it is; [n, H, W] does for one channel."""
+        (uint8 / uint16): any view with positive strides (frame_view_of), passed as it is; [n, H, W] does for one channel.
+        frame_dtype="uint16": as "uint8" with unsigned 16-bit elements, one channel."""
         mode = "gray" if self.frame_shape[2] == 1 else "rgb"
         check_frame_channels(frame_channels, mode, frame_dtype, self.accumulation)      # (first: a refused 3 is reported as such)
         check_frame_dtype(frame_dtype, mode, self.accumulation)
@@ -914,14 +964,17 @@ class PyramidPlan(object):
 
     @staticmethod
     def _entry(name, frame_dtype, frame_channels, frame_layout="packed"):
-        """The entry point family of a frame layout: silent_<name>, silent_<name>_u8, silent_<name>_u8x3 or silent_<name>_view."""
+        """The entry point family of a frame layout: silent_<name>, silent_<name>_u8, silent_<name>_u8x3, silent_<name>_view,
+        silent_<name>_u16 or silent_<name>_view16."""
         return _lib.gray_entry(name, frame_dtype, frame_channels, frame_layout=frame_layout)[0]
 
     def run(self, frames, frame_dtype="float32", frame_channels=1, frame_layout="packed"):
         """frames: [n, H, W, C] ndarray (host) or torch GPU tensor.  Returns a PackedPyramid.  frame_dtype="uint8" (single-channel
         plans): uint8 frames read as they are (silent_pyramid_u8), the same pyramid bit for bit.  frame_channels=3 (with "uint8"):
         [n, H, W, 3] interleaved colour frames (silent_pyramid_u8x3), the pyramid of the frame of values (b0 + b1 + b2) * f32(1/3).
-        frame_layout="strided" (with "uint8"): any uint8 view with positive strides, read in place (silent_pyramid_view)."""
+        frame_layout="strided" (with "uint8"): any uint8 view with positive strides, read in place (silent_pyramid_view).
+        frame_dtype="uint16": unsigned 16-bit frames read as they are (silent_pyramid_u16; strided: silent_pyramid_view16), the pyramid of
+        frames.astype(float32) bit for bit."""
         op, c = self._frames(frames, frame_dtype, frame_channels, frame_layout), self.frame_shape[2]
         out, optr = op.empty(op.n_frames * self.frame_px * c)
         op.call(self._entry("pyramid", frame_dtype, frame_channels, frame_layout), self.handle, op.ptr, op.n_frames, optr)
@@ -954,7 +1007,10 @@ class PyramidPlan(object):
         frame_dtype="uint8" (silent_gray_pass_u8): uint8 frames read as they are; the same maps bit for bit, either storage.
         frame_channels=3 (with "uint8"; silent_gray_pass_u8x3): frames [n,H,W,3] interleaved colour, each pixel entering as
         (b0 + b1 + b2) * float32(1/3) -- the maps of the float32 call on that frame of values, bit for bit.
-        frame_layout="strided" (with "uint8"; silent_gray_pass_view): any uint8 view with positive strides, read in place."""
+        frame_layout="strided" (with "uint8"; silent_gray_pass_view): any uint8 view with positive strides, read in place.
+        frame_dtype="uint16" (silent_gray_pass_u16; strided: silent_gray_pass_view16): unsigned 16-bit frames read as they are, the maps of
+        frames.astype(float32) bit for bit.  storage="float16" keeps its rule -- the float32 result rounded to nearest even, overflow
+        to +-inf: with full-range 16-bit data and clip_hi above 65504 a stored element can be +inf, as in the float32-frame call."""
         check_storage(storage, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
         check_frame_channels(frame_channels, "gray" if self.frame_shape[2] == 1 else "rgb", frame_dtype, self.accumulation)
         check_frame_dtype(frame_dtype, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
@@ -983,7 +1039,8 @@ class PyramidPlan(object):
         max_value_indices_region on the K-channel end map.  Returns (pyramid, cs, end, idx [n, cap, 4], counts [n]).
         frame_dtype="uint8" (silent_gray_keypoints_u8): uint8 frames read as they are, the same results.  frame_channels=3 (with
         "uint8"; silent_gray_keypoints_u8x3): [n,H,W,3] interleaved colour frames, the results of the frame of values.
-        frame_layout="strided" (with "uint8"; silent_gray_keypoints_view): any uint8 view with positive strides, read in place."""
+        frame_layout="strided" (with "uint8"; silent_gray_keypoints_view): any uint8 view with positive strides, read in place.
+        frame_dtype="uint16" (silent_gray_keypoints_u16; strided: silent_gray_keypoints_view16): unsigned 16-bit frames, the same results."""
         check_frame_channels(frame_channels, "gray" if self.frame_shape[2] == 1 else "rgb", frame_dtype, self.accumulation)
         check_frame_dtype(frame_dtype, "gray" if self.frame_shape[2] == 1 else "rgb", self.accumulation)
         check_frame_layout(frame_layout, "gray" if self.frame_shape[2] == 1 else "rgb", frame_dtype, self.accumulation)

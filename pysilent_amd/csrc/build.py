@@ -19,7 +19,7 @@ import time
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "lib", "libsilent_hip.so")
-UNITS = ["silent_core", "silent_conv_api", "silent_gray_api", "silent_peaks_api", "silent_rgb_api", "silent_pyramid_api", "silent_displayer_api"]
+UNITS = ["silent_core", "silent_conv_api", "silent_gray_api", "silent_gray16_api", "silent_peaks_api", "silent_rgb_api", "silent_pyramid_api", "silent_displayer_api"]
 HOST_ASAN_OUT = os.path.join(PKG, "lib", "libsilent_hostonly_asan.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=off", "-fno-slp-vectorize",
          "-Wall", "-Wextra", "-Wno-unused-parameter"]
@@ -104,9 +104,10 @@ HOST_ASAN_FLAGS = ["--offload-host-only", "-cuid=silenthost", "-DSILENT_HOST_ONL
                    "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 # tests/gray_bytes_host_main.cpp, once per frame type: the entry-point suffix and the bytes of one frame pixel
 HOST_DRIVERS = {"u8": ["-DSILENT_SFX=_u8", "-DSILENT_FRAME_BYTES=1"], "u8x3": ["-DSILENT_SFX=_u8x3", "-DSILENT_FRAME_BYTES=3"],
-                "f32": ["-DSILENT_FRAME_BYTES=4"], "view": []}
-# "view": the strided *_view entry points have a driver of their own (both channel counts in one program)
-HOST_DRIVER_SOURCES = {"view": "gray_view_host_main.cpp"}
+                "f32": ["-DSILENT_FRAME_BYTES=4"], "view": [], "u16": []}
+# "view": the strided *_view entry points have a driver of their own (both channel counts in one program); "u16": so have the twelve
+# uint16 entry points (*_u16 and *_view16)
+HOST_DRIVER_SOURCES = {"view": "gray_view_host_main.cpp", "u16": "gray_u16_host_main.cpp"}
 
 
 def _fresh(out, dep):
@@ -130,7 +131,7 @@ def build_host_asan(force=False):
 
 
 def build_host_driver(family, force=False):
-    """tests/gray_bytes_host_main.cpp (tests/gray_view_host_main.cpp for "view") + the library's host side as one stand-alone executable under the same sanitizers (the runtime
+    """tests/gray_bytes_host_main.cpp (tests/gray_view_host_main.cpp for "view", tests/gray_u16_host_main.cpp for "u16") + the library's host side as one stand-alone executable under the same sanitizers (the runtime
     is linked in: it is run as a child process, nothing of it is loaded into Python), for one frame type of HOST_DRIVERS.  Returns the
     path of the executable, build/gray_host_<family>; rebuilt when a file it was compiled from is newer."""
     exe = os.path.join(HERE, "build", "gray_host_" + family)

@@ -159,7 +159,14 @@ struct FrameRgb8 {
 static_assert(sizeof(FrameRgb8) == 3 && alignof(FrameRgb8) == 1, "one interleaved uint8 colour pixel");
 template <typename FT>
 constexpr bool kFrameRgb8 = std::is_same<FT, FrameRgb8>::value;
-// Strided uint8 frames (the *_view entry points, silent_frame_view): the pixels PX -- unsigned char or FrameRgb8, read exactly as the
+// uint16 frames (the *_u16 entry points: Mono10/12/16, Y16 / Z16, 16-bit TIFF / PNG, the luma of P010 / P016): one frame element is an
+// unsigned 16-bit integer in native byte order, 2-byte aligned, and enters the arithmetic as (float)v at the load -- exact (65535 <
+// 2^24), so a uint16 kernel stores the bits its float instantiation stores for the widened frame.  UNSIGNED: a short load
+// (global_load_sshort) would turn 32768 .. 65535 into negatives.  No shift and no scale: P010 keeps its 10 bits in the high bits.
+template <typename FT>
+constexpr bool kFrameWords = std::is_same<FT, unsigned short>::value;
+// Strided frames (the *_view entry points, silent_frame_view, and *_view16, silent_frame_view16): the pixels PX -- unsigned char,
+// FrameRgb8 or unsigned short (2-byte aligned: even address, even strides), read exactly as the
 // packed kinds read them -- of a view with three BYTE strides (a pitched BGR row need not be a multiple of 3), so pixel (frame, y, x)
 // is the PX at data + frame * frame_stride + y * row_stride + x * pixel_stride, in 64-bit bytes.  The type is both the frame kind FT
 // of the kernels and their argument, by value: the strides arrive in SGPRs, and with the wave-uniform row of every load the frame
@@ -174,6 +181,9 @@ template <typename FT>
 constexpr bool kFrameStrided = false;
 template <typename PX>
 constexpr bool kFrameStrided<FrameStrided<PX>> = true;
+// the two uint16 kinds, packed and strided (their entry points say "uint16 frames")
+template <typename FT>
+constexpr bool kFrame16 = kFrameWords<FT> || std::is_same<FT, FrameStrided<unsigned short>>::value;
 // one frame of a strided batch inside a kernel: (float)at(y, x) is the value of its pixel (x, y)
 template <typename PX>
 struct StridedSrc {
@@ -207,19 +217,20 @@ __device__ __forceinline__ StridedSrc<PX> frame_of(const FrameStrided<PX>& frame
 
 // the frame types that exist for single-channel plans with float32 accumulation only
 template <typename FT>
-constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT> || kFrameStrided<FT>;
+constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT> || kFrameWords<FT> || kFrameStrided<FT>;
 template <typename FT>
 constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT>;
 // (host) the bytes of one frame pixel as the host-pointer forms stage it -- float frames carry the channels of the plan; a view is
 // staged by its span -- and the suffix of a frame type's entry points
 template <typename FT>
-constexpr size_t frame_px_bytes(int plan_channels) { return kFrameRgb8<FT> ? 3 : kFrameBytes<FT> ? 1 : 4 * (size_t)plan_channels; }
+constexpr size_t frame_px_bytes(int plan_channels) { return kFrameRgb8<FT> ? 3 : kFrameWords<FT> ? 2 : kFrameBytes<FT> ? 1 : 4 * (size_t)plan_channels; }
 template <typename FT>
-constexpr const char* kFrameSuffix = kFrameStrided<FT> ? "_view" : kFrameRgb8<FT> ? "_u8x3" : kFrameBytes<FT> ? "_u8" : "";
+constexpr const char* kFrameSuffix =
+    kFrameStrided<FT> ? (kFrame16<FT> ? "_view16" : "_view") : kFrameRgb8<FT> ? "_u8x3" : kFrameWords<FT> ? "_u16" : kFrameBytes<FT> ? "_u8" : "";
 
 // Stream row i of the column `col` (level coordinates, mirrored inside the crop like every tap; px_stride floats per pixel) in lane i: ONE load per tile
 // for the sixth taps of a wave's last smoothing lane; row i is read back with unit_edge(xcol, i).
-// FT: the frame element type (float, or unsigned char: uint8 frames, widened at the load -- exact).
+// FT: the frame element type (float, or unsigned char / unsigned short: uint8 / uint16 frames, widened at the load -- exact).
 template <typename FT = float>
 __device__ __forceinline__ float unit_edge_column(const FT* __restrict__ src, long long row_stride, int col, int src_w, int src_x0,
                                                   int y_first, int n_rows, int src_h, int src_y0, int lane, int px_stride = 1) {

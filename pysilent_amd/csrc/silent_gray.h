@@ -426,7 +426,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_unit_fused_kernel(frame
                                                               ST* __restrict__ end_out, const FusedTabT<F64> tab,
                                                               const GrayW wts, float clip_hi, const GrayKp kp = GrayKp{}) {
     static_assert(!kStoreHalf<ST> || (!KP && !F64), "float16 storage: no keypoint epilogue, no float64 accumulation");
-    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || !F64), "uint8 frames: float32 accumulation only");
+    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || !F64), "uint8 / uint16 frames: float32 accumulation only");
     __shared__ __attribute__((aligned(16))) float s_slab[K == 8 && !kStoreHalf<ST> ? kFusedWaves * 512 : 4];  // K = 8 store transpose, per wave
     const unsigned bid = blockIdx.x;
     const int frame = (int)(bid / (unsigned)tab.tiles_per_frame);
@@ -734,7 +734,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(frame_par
                                                           float clip_hi, unsigned opts, const GrayKp kp = GrayKp{}) {
     constexpr int R = kFusedTH, NR = kStreamRows;
     static_assert(!kStoreHalf<ST> || (!KP && !F64), "float16 storage: no keypoint epilogue, no float64 accumulation");
-    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || !F64), "uint8 frames: float32 accumulation only");
+    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || !F64), "uint8 / uint16 frames: float32 accumulation only");
     __shared__ __attribute__((aligned(16))) float s_slab[K == 8 && !kStoreHalf<ST> ? kFusedWaves * 512 : 4];
     __shared__ __attribute__((aligned(16))) float s_rows[kFusedWaves][NR][64];  // the streamed rows of each wave (wave private)
     const unsigned bid = (opts & 1u) ? xcd_swizzle(blockIdx.x, gridDim.x) : blockIdx.x;
@@ -1032,7 +1032,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void gray_stream_kernel(frame_par
 template <int C, int G, int L = 0, bool F64 = false, typename FT = float>
 __global__ __launch_bounds__(64 * kFusedWaves) void pyramid_stream_kernel(frame_param<FT> frames, float* __restrict__ pyr,
                                                              const FusedTabT<F64> tab, const StreamTab st) {
-    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
+    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 / uint16 frames: one channel, float32 accumulation");
     constexpr int R = kFusedTH, NR = kStreamRows;
     __shared__ float s_rows[kFusedWaves][NR][64];
     const unsigned bid = blockIdx.x;

@@ -825,7 +825,7 @@ static int gray_keypoints_checks(silent_ctx* ctx, const char* who, const silent_
     if (!plan || !has_frames || !has_pyr || !cs_kernel || !end_bank || !has_end || !regions || !counts || (!idx && cap_per_frame))
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
-    if constexpr (kFrameNarrow<FT>) TRY(check_narrow_frames(ctx, who, plan));
+    if constexpr (kFrameNarrow<FT>) TRY(check_narrow_frames<FT>(ctx, who, plan));
     if (plan->tab.C != 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": the plan must be single-channel");
     if (n_orient != 3 && n_orient != 4 && n_orient != 8)
         return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": n_orient must be 3, 4 or 8");
@@ -1192,6 +1192,62 @@ SILENT_EXPORT int silent_gray_keypoints_view(silent_ctx* ctx, const silent_pyram
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_view");
 }
+
+// uint16 frames (silent_hip.h): the *_u8 forms with an unsigned 16-bit element, 2-byte aligned; strided uint16 views as the *_view forms
+#define KP_ARGS                                                                                                                           \
+    const float *cs_kernel, const float *end_bank, int n_orient, float clip_hi, float *pyr, float *cs_out, float *end_out, int pad,       \
+        int selection, double top_percent, const silent_extent *regions, float *value_out, float *peak_value_out, int64_t *idx,           \
+        size_t cap_per_frame, int64_t *counts
+#define KP_PASS                                                                                                                           \
+    cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection, top_percent, regions, value_out, peak_value_out, idx,   \
+        cap_per_frame, counts
+SILENT_EXPORT int silent_gray_keypoints_u16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames, KP_ARGS,
+                                                silent_stream stream) try {
+    NEED_CTX(ctx);
+    TRY(check_u16_aligned(ctx, "silent_gray_keypoints_u16", frames));
+    return gray_keypoints_dev(ctx, plan, frames, n_frames, KP_PASS, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_keypoints_u16_dev");
+}
+
+SILENT_EXPORT int silent_gray_keypoints_u16(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames, KP_ARGS) try {
+    NEED_CTX(ctx);
+    TRY(check_u16_aligned(ctx, "silent_gray_keypoints_u16", frames));
+    return gray_keypoints_host(ctx, plan, frames, n_frames, KP_PASS);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_keypoints_u16");
+}
+
+static int gray_keypoints_view16(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_frame_view16* view, int n_frames, KP_ARGS,
+                                 silent_stream stream) {
+    const char* who = "silent_gray_keypoints_view16";
+    TRY(check_view16(ctx, who, plan, view, n_frames, nullptr));
+    // (the host form accepts NULL pyr / end_out, see gray_keypoints_host)
+    TRY(gray_keypoints_checks<View16>(ctx, who, plan, true, n_frames, cs_kernel, end_bank, n_orient, host || pyr, host || end_out, pad, selection,
+                                      regions, peak_value_out, idx, cap_per_frame, counts));
+    return with_view16(plan, view, n_frames, [&](auto frames) {
+        if (host) return gray_keypoints_host(ctx, plan, frames, n_frames, KP_PASS);
+        return gray_keypoints_dev(ctx, plan, frames, n_frames, KP_PASS, stream);
+    });
+}
+
+SILENT_EXPORT int silent_gray_keypoints_view16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view16* frames, int n_frames,
+                                                   KP_ARGS, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return gray_keypoints_view16(ctx, false, plan, frames, n_frames, KP_PASS, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_keypoints_view16_dev");
+}
+
+SILENT_EXPORT int silent_gray_keypoints_view16(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view16* frames, int n_frames,
+                                               KP_ARGS) try {
+    NEED_CTX(ctx);
+    return gray_keypoints_view16(ctx, true, plan, frames, n_frames, KP_PASS, nullptr);
+} catch (...) {
+    return on_exception(ctx, "silent_gray_keypoints_view16");
+}
+#undef KP_ARGS
+#undef KP_PASS
 
 SILENT_EXPORT int silent_centroids(silent_ctx* ctx, const float* value, const silent_extent* levels, int n_levels,
                                    int n_frames, int region_h, int region_w, float* dist_out, float* total_out) try {

@@ -55,6 +55,7 @@ inline const silent::FrameRgb8* rgb8(const uint8_t* frames) { return reinterpret
 // (strides + the data pointer); kernel_frames turns it into the kernel's argument, the struct by value.
 using View8 = silent::FrameStrided<unsigned char>;
 using View8x3 = silent::FrameStrided<silent::FrameRgb8>;
+using View16 = silent::FrameStrided<unsigned short>;   // (the *_view16 entry points, silent_frame_view16)
 template <typename FT>
 inline auto kernel_frames(const FT* frames) {
     if constexpr (silent::kFrameStrided<FT>) return *frames;
@@ -79,6 +80,33 @@ inline int check_view(silent_ctx* ctx, const char* who, const silent_pyramid_pla
     if (span) *span = (size_t)all;
     return SILENT_OK;
 }
+// The same for a silent_frame_view16: one uint16 element per pixel (the bounds of check_view with 2 for `channels`), and 2-byte alignment
+// of every address a kernel forms -- an even data address and even strides.
+inline int check_view16(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const silent_frame_view16* v, int n_frames, size_t* span) {
+    if (!plan || !v || !v->data) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (reinterpret_cast<uintptr_t>(v->data) & 1u) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view data is not 2-byte aligned (uint16 frames)");
+    typedef unsigned __int128 u128;
+    const u128 H = (u128)plan->tab.H, W = (u128)plan->tab.W;
+    if (v->pixel_stride < 2) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view pixel_stride is below 2 bytes (uint16 frames)");
+    if (v->pixel_stride & 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view pixel_stride is odd (uint16 frames)");
+    const u128 row = (W - 1) * (u128)v->pixel_stride + 2;
+    if (v->row_stride <= 0 || (u128)v->row_stride < row)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view row_stride is below (W - 1) * pixel_stride + 2 (uint16 frames)");
+    if (v->row_stride & 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view row_stride is odd (uint16 frames)");
+    const u128 frame = (H - 1) * (u128)v->row_stride + row;
+    if (n_frames > 1 && (v->frame_stride <= 0 || (u128)v->frame_stride < frame))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view frame_stride is below (H - 1) * row_stride + (W - 1) * pixel_stride + 2 (uint16 frames)");
+    if (n_frames > 1 && (v->frame_stride & 1)) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view frame_stride is odd (uint16 frames)");
+    const u128 all = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->frame_stride : 0) + frame;
+    if (all > (u128)0x7fffffffffffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view spans more than 2^63 bytes (uint16 frames)");
+    if (span) *span = (size_t)all;
+    return SILENT_OK;
+}
+// a packed uint16 batch must be 2-byte aligned (frames: not NULL -- a NULL pointer is reported by the shared checks)
+inline int check_u16_aligned(silent_ctx* ctx, const char* who, const uint16_t* frames) {
+    if (reinterpret_cast<uintptr_t>(frames) & 1u) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": uint16 frames must be 2-byte aligned");
+    return SILENT_OK;
+}
 // f(frames) with the view as the frame kind that reads it: a packed view as the packed bytes (the kernels of *_u8 / *_u8x3), any other
 // as a strided kind.  (check_view passed.)
 template <class F>
@@ -92,6 +120,13 @@ int with_view(const silent_pyramid_plan* plan, const silent_frame_view* v, int n
     }
     if (packed) return f(rgb8(v->data));
     const View8x3 s{v->data, v->pixel_stride, v->row_stride, n_frames > 1 ? v->frame_stride : 0};
+    return f(&s);
+}
+template <class F>
+int with_view16(const silent_pyramid_plan* plan, const silent_frame_view16* v, int n_frames, F&& f) {
+    const long long H = plan->tab.H, W = plan->tab.W;
+    if (v->pixel_stride == 2 && v->row_stride == W * 2 && (n_frames <= 1 || v->frame_stride == H * v->row_stride)) return f(v->data);
+    const View16 s{reinterpret_cast<const unsigned char*>(v->data), v->pixel_stride, v->row_stride, n_frames > 1 ? v->frame_stride : 0};
     return f(&s);
 }
 // (host-pointer forms) what is staged for `frames` -- the packed batch, or the span of a view (its strides passed check_view) -- and
@@ -124,10 +159,12 @@ struct StagedFrames {
     }
 };
 
-// the uint8 frame kinds / float16 storage exist for single-channel plans with float32 accumulation only (plan: not NULL)
+// the uint8 / uint16 frame kinds / float16 storage exist for single-channel plans with float32 accumulation only (plan: not NULL)
+template <typename FT>
 inline int check_narrow_frames(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan) {
-    if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames are for single-channel plans");
-    if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": uint8 frames with a SILENT_PLAN_ACCUM_F64 plan");
+    const std::string what = silent::kFrame16<FT> ? "uint16 frames" : "uint8 frames";
+    if (plan->tab.C != 1) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": " + what + " are for single-channel plans");
+    if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": " + what + " with a SILENT_PLAN_ACCUM_F64 plan");
     return SILENT_OK;
 }
 inline int check_half_storage(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan) {
@@ -179,7 +216,7 @@ inline void fused_add_level(silent::FusedTab64& ft, const silent::PyrTab& pt, in
 
 // ------------------------------------------------------------------------------------------ kernel dispatch
 // Which instantiations of the gray kernels exist: float16 storage (ST = gray_half) has no keypoint epilogue and no float64 accumulation,
-// the uint8 frame kinds no float64 accumulation (the entry points refuse those combinations before a launch).
+// the uint8 / uint16 frame kinds no float64 accumulation (the entry points refuse those combinations before a launch).
 template <bool KP, bool F64, typename ST, typename FT>
 constexpr bool kGrayKernel = !(silent::kStoreHalf<ST> && (KP || F64)) && !(silent::kFrameNarrow<FT> && F64);
 // f(KP, F64) with the run-time (kp, f64) as std::bool_constant's; a combination without kernels is never instantiated (nor reached)
@@ -211,7 +248,7 @@ void with_stream_layout(const silent_pyramid_plan* plan, F&& f) {
 
 // (silent_pyramid_api.hip) FT: the frame element type -- float, or unsigned char / silent::FrameRgb8 (uint8 frames, one channel /
 // interleaved colour, its value formed at the load: single-channel plans without SILENT_PLAN_ACCUM_F64; anything else is refused),
-// or View8 / View8x3 (the same pixels in a strided view: `frames` then points to the host struct).
+// or unsigned short (uint16 frames), or View8 / View8x3 / View16 (the same pixels in a strided view: `frames` then points to the host struct).
 // with_unit: also the unit levels (the gray pass produces them itself); with_region: also the general levels
 template <typename FT>
 int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames, float* pyr,
@@ -221,8 +258,11 @@ template <typename FT>
 int gray_pass_kp(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames, const float* cs_kernel,
                  const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, const silent::GrayKp& kp,
                  hipStream_t s);
-// (each is defined, and instantiated for the five frame types, in its unit)
-#define SILENT_FRAME_TYPES(X) X(float) X(unsigned char) X(silent::FrameRgb8) X(View8) X(View8x3)
+// (each is defined in its unit -- gray_pass_kp in silent_gray_pass.h -- and instantiated for the seven frame types: launch_pyramid in
+// silent_pyramid_api.hip, gray_pass_kp for float and the uint8 kinds in silent_gray_api.hip, for the uint16 kinds in silent_gray16_api.hip)
+#define SILENT_FRAME_TYPES_8(X) X(float) X(unsigned char) X(silent::FrameRgb8) X(View8) X(View8x3)
+#define SILENT_FRAME_TYPES_16(X) X(unsigned short) X(View16)
+#define SILENT_FRAME_TYPES(X) SILENT_FRAME_TYPES_8(X) SILENT_FRAME_TYPES_16(X)
 #define X(FT)                                                                                                                              \
     extern template int launch_pyramid<FT>(silent_ctx*, const char*, const silent_pyramid_plan*, const FT*, int, float*, hipStream_t, bool, bool); \
     extern template int gray_pass_kp<FT>(silent_ctx*, const silent_pyramid_plan*, const FT*, int, const float*, const float*, int, float, float*, \

@@ -96,7 +96,7 @@ __device__ __forceinline__ int mirror_index(int i, int n) {
 template <int C, bool F64 = false, typename FT = float>
 __global__ __launch_bounds__(256) void pyramid_unit_kernel(frame_param<FT> frames,
                                                            float* __restrict__ pyr, const PyrTabT<F64> tab) {
-    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
+    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 / uint16 frames: one channel, float32 accumulation");
     constexpr int R = kUnitTH;
     const unsigned bid = blockIdx.x;
     const int frame = (int)(bid / (unsigned)tab.unit_tiles_per_frame);
@@ -210,12 +210,15 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(frame_param<FT> frame
 // (one dword) per lane, which is legal only where the ADDRESS is 4-byte aligned -- and the uint8 frames pointer has no alignment
 // requirement: W % 4 == 0 puts every row start (frame * H * W + sy * W) and every group offset f on the dword grid relative to the
 // base, so the base address decides; any other base or width takes the one-element path.
+// FT = unsigned short (uint16 frames): the same with 4 elements in 8 bytes (one dwordx2) per lane, legal where the address is 8-byte
+// aligned -- the frames pointer is only 2-byte aligned: W % 4 == 0 puts every frame and row start and every group offset on the 8-byte
+// grid relative to the base, so again the base address decides (block-uniform); any other base or width takes the one-element path.
 // FT = FrameRgb8 (interleaved uint8 colour, silent_common.h): always the one-element path, the value formed while staging.
 // FT = FrameStrided<PX> (strided views): the one-element path as well -- a pixel stride above the pixel's size has no dword of four pixels.
 template <int C, bool F64 = false, typename FT = float>
 __global__ __launch_bounds__(256) void pyramid_region_kernel(frame_param<FT> frames,
                                                              float* __restrict__ pyr, const PyrTabT<F64> tab) {
-    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 frames: one channel, float32 accumulation");
+    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 / uint16 frames: one channel, float32 accumulation");
     constexpr int RW = region_w(C), SW = region_sw(C), SH = region_sh(C), ROWF = SW * C, VR = region_vr(C);
     __shared__ __attribute__((aligned(16))) float s_src[SH * ROWF];
     __shared__ __attribute__((aligned(16))) acc_t<F64> s_v[VR * ROWF];
@@ -255,11 +258,12 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(frame_param<FT> fra
     // outside the frame are never referenced: rows are clamped, out-of-frame column groups are skipped.
     bool groups = ((W * C) & 3) == 0;
     if constexpr (kFrameBytes<FT>) groups = groups && (reinterpret_cast<unsigned long long>(frames) & 3ull) == 0;   // (block-uniform)
+    if constexpr (kFrameWords<FT>) groups = groups && (reinterpret_cast<unsigned long long>(frames) & 7ull) == 0;   // (block-uniform)
     if constexpr (kFrameRgb8<FT> || kFrameStrided<FT>) groups = false;   // interleaved colour bytes, strided views: the one-element path (a pixel per element)
     if (groups) {
       if constexpr (!kFrameStrided<FT>) {
         constexpr int V4 = ROWF / 4, NB = (SH * V4 + 255) / 256;
-        typename std::conditional<kFrameBytes<FT>, uchar4, float4>::type v[NB];
+        typename std::conditional<kFrameBytes<FT>, uchar4, typename std::conditional<kFrameWords<FT>, ushort4, float4>::type>::type v[NB];
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
             const int p = min(tid + 256 * k, SH * V4 - 1);
@@ -268,6 +272,7 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(frame_param<FT> fra
             long long f = (long long)(X0 - kRegionHaloL) * C + q * 4;  // first float of this group in the row
             f = min(max(f, 0ll), (long long)W * C - 4);
             if constexpr (kFrameBytes<FT>) v[k] = *reinterpret_cast<const uchar4*>(src + (long long)sy * W * C + f);
+            else if constexpr (kFrameWords<FT>) v[k] = *reinterpret_cast<const ushort4*>(src + (long long)sy * W * C + f);
             else v[k] = *reinterpret_cast<const float4*>(src + (long long)sy * W * C + f);
         }
 #pragma unroll
@@ -276,7 +281,7 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(frame_param<FT> fra
             const int r = p / V4, q = p - r * V4;
             const long long f = (long long)(X0 - kRegionHaloL) * C + q * 4;
             if (p < SH * V4 && f >= 0 && f + 4 <= (long long)W * C) {
-                if constexpr (kFrameBytes<FT>)
+                if constexpr (kFrameBytes<FT> || kFrameWords<FT>)
                     *reinterpret_cast<float4*>(s_src + r * ROWF + q * 4) = make_float4((float)v[k].x, (float)v[k].y, (float)v[k].z, (float)v[k].w);
                 else
                     *reinterpret_cast<float4*>(s_src + r * ROWF + q * 4) = v[k];

@@ -650,7 +650,7 @@ static int pyramid_checks(silent_ctx* ctx, const char* who, const silent_pyramid
     if (!plan || !has_frames || !pyr) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
     if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
-    if constexpr (kFrameNarrow<FT>) TRY(check_narrow_frames(ctx, who, plan));
+    if constexpr (kFrameNarrow<FT>) TRY(check_narrow_frames<FT>(ctx, who, plan));
     return SILENT_OK;
 }
 
@@ -834,4 +834,50 @@ SILENT_EXPORT int silent_pyramid_u8x3(silent_ctx* ctx, const silent_pyramid_plan
     return pyramid_host(ctx, plan, rgb8(frames), n_frames, pyr);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_u8x3");
+}
+
+// uint16 frames (silent_hip.h): the *_u8 forms with an unsigned 16-bit element, 2-byte aligned; a strided uint16 view with the view's own
+// refusals first (check_view16), then the frame kind that reads it (with_view16: a packed view takes the packed kernels).
+SILENT_EXPORT int silent_pyramid_u16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames,
+                                         float* pyr, silent_stream stream) try {
+    NEED_CTX(ctx);
+    TRY(check_u16_aligned(ctx, "silent_pyramid_u16", frames));
+    return launch_pyramid(ctx, "silent_pyramid_u16", plan, frames, n_frames, pyr, (hipStream_t)stream, true);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_u16_dev");
+}
+
+SILENT_EXPORT int silent_pyramid_u16(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames,
+                                     float* pyr) try {
+    NEED_CTX(ctx);
+    TRY(check_u16_aligned(ctx, "silent_pyramid_u16", frames));
+    return pyramid_host(ctx, plan, frames, n_frames, pyr);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_u16");
+}
+
+static int pyramid_view16(silent_ctx* ctx, const char* who, bool host, const silent_pyramid_plan* plan, const silent_frame_view16* view,
+                          int n_frames, float* pyr, silent_stream stream) {
+    TRY(check_view16(ctx, who, plan, view, n_frames, nullptr));
+    TRY(pyramid_checks<View16>(ctx, who, plan, true, n_frames, pyr));
+    return with_view16(plan, view, n_frames, [&](auto frames) {
+        if (host) return pyramid_host(ctx, plan, frames, n_frames, pyr);
+        return launch_pyramid(ctx, who, plan, frames, n_frames, pyr, (hipStream_t)stream, true);
+    });
+}
+
+SILENT_EXPORT int silent_pyramid_view16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view16* frames, int n_frames,
+                                            float* pyr, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return pyramid_view16(ctx, "silent_pyramid_view16", false, plan, frames, n_frames, pyr, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_view16_dev");
+}
+
+SILENT_EXPORT int silent_pyramid_view16(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view16* frames, int n_frames,
+                                        float* pyr) try {
+    NEED_CTX(ctx);
+    return pyramid_view16(ctx, "silent_pyramid_view16", true, plan, frames, n_frames, pyr, nullptr);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_view16");
 }

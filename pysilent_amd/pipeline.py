@@ -148,17 +148,23 @@ class LineEndPipeline(object):
         # bytes themselves (the silent_*_u8 entry points) -- no widening cast, no float32 copy of the batch, every map bit-identical
         # to the float32 pipeline's on the widened frames.  Refused here as well: unknown names, mode "rgb", accumulation="float64"
         # (checked below, after frame_channels: a refused frame_channels=3 is reported as such)
+        # frame_dtype="uint16" (mode "gray"): the same for unsigned 16-bit frames in native byte order (the silent_*_u16 entry points:
+        # Mono10 / 12 / 16, Y16 / Z16, the luma of P010 / P016) -- the value is (float)v, exact, no shift and no scale: a P010 source
+        # (10 bits in the HIGH bits) passes clip_hi * 64 and reads maps exactly 64 times the 10-bit ones.  Refused here as well: mode
+        # "rgb", accumulation="float64", frame_channels=3
         # frame_channels=3 (mode "gray", frame_dtype="uint8"): step() takes [batch, H, W, 3] interleaved colour uint8 frames and the
         # kernels form each pixel's value (b0 + b1 + b2) * float32(1/3) at the load (the silent_*_u8x3 entry points) -- no cast launch,
         # no value launch, no float32 buffer; every map bit-identical to the float32 pipeline's on the frame of values.  frame_shape
         # becomes (H, W, 3); channels, the plan and all maps stay single-channel.  Refused here as well: anything but 1 and 3, and 3
-        # with mode "rgb", frame_dtype="float32" or accumulation="float64"
+        # with mode "rgb", frame_dtype="float32" or "uint16", or accumulation="float64"
         self.frame_channels = _runtime.check_frame_channels(frame_channels, mode, frame_dtype, accumulation)
         self.frame_dtype = _runtime.check_frame_dtype(frame_dtype, mode, accumulation)
         # frame_layout="strided" (mode "gray", frame_dtype="uint8"): step() takes ANY uint8 GPU view of the right shape with positive
         # strides -- surface[:, :H, :W, None] of a pitched NV12 batch, bgra[..., :3], yuyv[:, :, ::2, None], a region of larger frames
         # -- and the kernels read it in place (the silent_*_view entry points): no packing launch, no second copy of the batch, every
         # map bit-identical to the packed pipeline's on the compacted pixels.  step_host is unchanged (its staging copy packs).
+        # With frame_dtype="uint16" any uint16 GPU view (the silent_*_view16 entry points: p010[:, :H, :W] of pitched surfaces,
+        # rgba16[..., 1], a window of larger frames).
         # Refused here as well: unknown names, mode "rgb", frame_dtype="float32", accumulation="float64"
         self.frame_layout = _runtime.check_frame_layout(frame_layout, mode, frame_dtype, accumulation)
         import torch
@@ -306,7 +312,7 @@ class LineEndPipeline(object):
         """Noise frames of the dtype step() takes (the tuners' default batch)."""
         torch = self.torch
         frames = torch.randint(0, 256, (self.batch,) + self.frame_shape, device=self.tdev)
-        return frames.to(torch.uint8 if self.frame_dtype == "uint8" else torch.float32)
+        return frames.to(self._frame_torch_dtype)
 
     def _time_step(self, frames, steps, windows=2):
         import time
@@ -544,7 +550,7 @@ class LineEndPipeline(object):
         """4*[H*W*C (frame read) + P*C (pyramid written) + P*C (pyramid read) + P*sum(C_out returned)]; for crop layouts the
         frame read is the largest crop any level resamples (the part of the frame the pyramid depends on).  storage="float16":
         the returned CS and end maps count 2 bytes per element.  frame_dtype="uint8": the frame read counts 1 byte per frame element
-        -- frame_shape[2] of them per pixel (3 for interleaved colour frames, whose pyramid and maps stay single-channel)."""
+        ("uint16": 2 bytes) -- frame_shape[2] of them per pixel (3 for interleaved colour frames, whose pyramid and maps stay single-channel)."""
         h, w, fc = self.frame_shape
         c = self.channels
         if self.crop_px is not None:
@@ -560,7 +566,12 @@ class LineEndPipeline(object):
     @property
     def _frame_bytes(self):
         """Bytes per frame element as step() reads it."""
-        return 1 if self.frame_dtype == "uint8" else 4
+        return {"uint8": 1, "uint16": 2}.get(self.frame_dtype, 4)
+
+    @property
+    def _frame_torch_dtype(self):
+        """The torch dtype of the frames step() takes."""
+        return getattr(self.torch, self.frame_dtype)
 
     @property
     def _colour_frames(self):
@@ -587,7 +598,7 @@ class LineEndPipeline(object):
             return ("gray_stream_kernel (whole pyramid + level-0 CS/line-end, frame read once) + "
                     "gray_line_end_kernel (levels >= 1)" + (", float64 accumulation" if self.accumulation == "float64" else "")
                     + (", float16 CS / end maps" if self.storage == "float16" else "")
-                    + (", uint8 frames" if self.frame_dtype == "uint8" else "")
+                    + (", %s frames" % self.frame_dtype if self.frame_dtype != "float32" else "")
                     + (" of 3 interleaved channels (value formed at the load)" if self._colour_frames else "")
                     + (", read in place from a strided view" if getattr(self, "frame_layout", "packed") == "strided" else ""))
         return ("single-read RGB pyramid (pyramid_walk3_kernel), fused RGB chain, max/min + fused selection "
@@ -600,11 +611,11 @@ class LineEndPipeline(object):
     def _check_frames(self, frames):
         if self.frame_layout == "strided":
             shapes = ((self.batch,) + self.frame_shape,) + (((self.batch,) + self.frame_shape[:2],) if self.frame_shape[2] == 1 else ())
-            if not _runtime.is_torch_tensor(frames) or tuple(frames.shape) not in shapes or frames.dtype != self.torch.uint8 \
+            if not _runtime.is_torch_tensor(frames) or tuple(frames.shape) not in shapes or frames.dtype != self._frame_torch_dtype \
                     or not frames.is_cuda:
-                raise ValueError("frames must be a uint8 GPU tensor (any view with positive strides) of shape %s" % (shapes[0],))
+                raise ValueError("frames must be a %s GPU tensor (any view with positive strides) of shape %s" % (self.frame_dtype, shapes[0]))
             return
-        want = self.torch.uint8 if self.frame_dtype == "uint8" else self.torch.float32
+        want = self.torch.float32 if self.frame_dtype == "float32" else self._frame_torch_dtype
         if tuple(frames.shape) != (self.batch,) + self.frame_shape or frames.dtype != want \
                 or not frames.is_cuda or not frames.is_contiguous():
             raise ValueError("frames must be a contiguous %s GPU tensor of shape %s" %
@@ -613,11 +624,16 @@ class LineEndPipeline(object):
     def _frames_arg(self, frame_ptr, frames):
         """The frames argument of an entry point gray_entry chose: the view of a strided pipeline, the address otherwise."""
         if self.frame_layout == "strided":
-            return frame_ptr(_runtime.frame_view_of(frames, self.frame_shape[2]))
+            return frame_ptr(_runtime.frame_view_of(frames, self.frame_shape[2], self.frame_dtype))
         return frame_ptr(frames.data_ptr())
 
     def run_pyramid(self, frames, stream=None):
         self._check_frames(frames)
+        if self.frame_dtype == "uint16":
+            name, frame_ptr, _, _ = _lib.gray_entry("pyramid", "uint16", frame_layout=self.frame_layout)
+            self.ctx.check(getattr(self._lib, "silent_" + name + "_dev")(self.ctx.handle, self.plan.handle, self._frames_arg(frame_ptr, frames),
+                                                                         self.batch, C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
+            return
         if self.frame_layout == "strided":
             self.ctx.check(self._lib.silent_pyramid_view_dev(self.ctx.handle, self.plan.handle, self._frames_arg(_lib.view_ptr, frames),
                                                              self.batch, C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
@@ -762,8 +778,8 @@ class LineEndPipeline(object):
     def _ingest_slot(self, dtype, pinned_source):
         """Ring of two slots per dtype: [pinned staging buffer (None when the caller's frames are pinned already), device buffer
         of the source dtype, float32 frame buffer, events].  Two batches are in flight: while batch n computes, batch n + 1 is
-        copied (and, for NumPy sources, batch n + 2 staged by the host).  A uint8 pipeline's slots have no float32 frame buffer:
-        step() reads the uint8 device buffer itself."""
+        copied (and, for NumPy sources, batch n + 2 staged by the host).  A uint8 / uint16 pipeline's slots have no float32 frame
+        buffer: step() reads the uint8 / uint16 device buffer itself."""
         torch = self.torch
         ring = self._ingest.setdefault(dtype, {"slots": [], "next": 0})
         if not ring["slots"]:
@@ -772,7 +788,7 @@ class LineEndPipeline(object):
                 ring["slots"].append({
                     "pinned": None,
                     "raw": torch.empty(shape, dtype=dtype, device=self.tdev) if dtype != torch.float32 else None,
-                    "f32": torch.empty(shape, dtype=torch.float32, device=self.tdev) if self.frame_dtype != "uint8" else None,
+                    "f32": torch.empty(shape, dtype=torch.float32, device=self.tdev) if self.frame_dtype == "float32" else None,
                     "h2d_done": torch.cuda.Event(), "raw_free": None, "f32_free": None})
         slot = ring["slots"][ring["next"]]
         ring["next"] ^= 1
@@ -789,7 +805,7 @@ class LineEndPipeline(object):
         a quarter of the PCIe bytes) and step().  Returns at once; two batches are in flight (ring of two slots), so the copy of
         batch n + 1 overlaps the compute of batch n.  Results are bit-identical to step() on the same frames resident as float32.
         A frame_dtype="uint8" pipeline takes uint8 host frames only: staging -> copy into the slot's uint8 device buffer -> step();
-        no cast launch and no float32 frame buffer."""
+        no cast launch and no float32 frame buffer.  A frame_dtype="uint16" pipeline likewise takes uint16 host frames only."""
         torch = self.torch
         if isinstance(frames, np.ndarray):
             src = torch.from_numpy(np.ascontiguousarray(frames))
@@ -797,9 +813,10 @@ class LineEndPipeline(object):
             src = frames.contiguous()
         if src.is_cuda or tuple(src.shape) != (self.batch,) + self.frame_shape:
             raise ValueError("step_host takes host frames of shape %s" % ((self.batch,) + self.frame_shape,))
-        if self.frame_dtype == "uint8":
-            if src.dtype != torch.uint8:
-                raise ValueError("step_host of a frame_dtype='uint8' pipeline takes uint8 host frames, got %s" % (src.dtype,))
+        if self.frame_dtype != "float32":
+            if src.dtype != self._frame_torch_dtype:
+                raise ValueError("step_host of a frame_dtype='%s' pipeline takes %s host frames, got %s"
+                                 % (self.frame_dtype, self.frame_dtype, src.dtype))
         elif src.dtype != torch.float32:
             _runtime._torch_dtype_code(src)         # TypeError for dtypes the cast kernel does not take
         if not hasattr(self, "_ingest"):
@@ -817,8 +834,8 @@ class LineEndPipeline(object):
             slot["h2d_done"].synchronize()          # the staging buffer's previous copy has left the host
             _staging_copy(slot["pinned"], src)
             src = slot["pinned"]
-        if self.frame_dtype == "uint8":
-            # the frame-reading kernels read the uint8 device buffer itself: it is free again where THEY finish -- on the walk stream
+        if self.frame_dtype != "float32":
+            # the frame-reading kernels read the uint8 / uint16 device buffer itself: it is free again where THEY finish -- on the walk stream
             # with overlap, else on the caller's stream (where a float32 pipeline records f32_free)
             if slot["raw_free"] is not None:
                 cs.wait_event(slot["raw_free"])     # the previous batch of this slot has been read on the device
