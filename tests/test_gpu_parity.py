@@ -1985,17 +1985,20 @@ def test_rgb_pyramid_walk_takes_zoom_steps_down_to_1_2(rt, shape, scale, n, px):
 
 def test_workspace_follows_the_callers_stream(rt):
     """One workspace per context: a caller that alternates between two streams gets correct results (the library drains
-    the previous stream before the workspace changes hands)."""
+    the previous stream before the workspace changes hands).  Every call has an input of its own: a workspace (the per-level
+    extrema) that the next call overwrote too early, or one left over from the call before, gives another threshold."""
     import torch
     from pysilent_amd.util.selection import top_value_points
-    x = torch.from_numpy(np.stack([noise_frame(s, 64, 96, 3) for s in range(4)])).cuda()
-    want = so.top_value_points(x.cpu().numpy(), 0.3)
+    hosts = [np.stack([noise_frame(10 * i + s, 64, 96, 3) for s in range(4)]) * np.float32(1.0 - 0.125 * i) for i in range(6)]
+    xs = [torch.from_numpy(h).cuda() for h in hosts]
+    wants = [so.top_value_points(h, 0.3) for h in hosts]
+    assert all((wants[i] != wants[j]).any() for i in range(6) for j in range(i))
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
     torch.cuda.synchronize()
     outs = []
     for i in range(6):
         with torch.cuda.stream(s1 if i % 2 == 0 else s2):
-            outs.append(top_value_points(x, 0.3))
+            outs.append(top_value_points(xs[i], 0.3))
     torch.cuda.synchronize()
-    for o in outs:
+    for o, want in zip(outs, wants):
         np.testing.assert_array_equal(o.cpu().numpy(), want)
