@@ -69,6 +69,17 @@ __device__ __forceinline__ float from_lane_above(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, true));
 }
 
+// A wave-uniform row cursor of a streaming kernel: a pointer into global memory that moves on by ADDITION.  The empty asm keeps the
+// sum in its SGPR pair as it is -- from an unrolled loop the compiler would otherwise form base + i * stride again, a 64-bit multiply
+// per row -- and the address space keeps what comes out of the asm a global pointer (a generic one is read with flat loads).
+template <typename T>
+using global_ptr = __attribute__((address_space(1))) T*;
+template <typename T>
+__device__ __forceinline__ void advance_rows(global_ptr<T>& p, long long elements) {
+    p += elements;
+    asm("" : "+s"(p));
+}
+
 // Float64 accumulation (plans created with SILENT_PLAN_ACCUM_F64; the F64 template flag of the gray and pyramid kernels).  Every
 // map is still stored as float32 between ops; inside one op the taps are summed in acc_t<true> = double and rounded to float32
 // once, like the oracle (oracle/silent_oracle.c).  The product of two float32 values is exact in float64, so a CS or end tap

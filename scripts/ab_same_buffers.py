@@ -84,7 +84,8 @@ for al in range(allocs):
             del got
         del ref
     for i, path in enumerate(libs):
-        print("alloc %d  %-28s step %.4f (min %.4f)   dominant kernel %.4f (min %.4f) ms" % (
-            al, os.path.basename(path), np.median(res[i]["step"]), np.min(res[i]["step"]), np.median(res[i]["kernel"]), np.min(res[i]["kernel"])), flush=True)
+        print("alloc %d  %-28s step %.4f (min %.4f max %.4f)   dominant kernel %.4f (min %.4f max %.4f) ms" % (
+            al, os.path.basename(path), np.median(res[i]["step"]), np.min(res[i]["step"]), np.max(res[i]["step"]),
+            np.median(res[i]["kernel"]), np.min(res[i]["kernel"]), np.max(res[i]["kernel"])), flush=True)
 sys.stdout.flush()
 os._exit(0)                              # (no destructors: plans and contexts belong to different builds of the library)
