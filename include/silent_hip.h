@@ -250,7 +250,22 @@ int silent_gray_pass_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, 
                               const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
                               void* end_out, int maps_f16, unsigned parts, silent_stream stream);
 
-/* Strided uint8 frames, read in place.  A decoder hands over NV12 surfaces with a row pitch, a camera or compositor BGRA / BGRX, YUYV
+/* Interleaved 3-channel uint8 frames for 3-CHANNEL plans, read as they are (the *_u8x3 forms above reduce colour to one value for a
+ * single-channel plan; these keep the three channels: the RGB pyramid that silent_rgb_line_end / silent_rgb_keypoints read).
+ * frames: [n_frames, H, W, 3] bytes, packed, ANY alignment.  Byte c of pixel (y, x) enters the arithmetic as (float)byte -- an unsigned
+ * load and an exact conversion in a register -- so pyr is IDENTICAL, bit for bit, to silent_pyramid[_dev] given (float)frames[i], on
+ * every route (the single-read walk kernel, union and per-level plans, the unit + region kernels, under every SILENT_TUNE_PYRAMID
+ * value): no cast launch and no float32 copy of the batch.  No byte outside the n_frames * H * W * 3 bytes of the batch is ever read:
+ * a batch whose address is not 4-byte aligned, or whose W is not a multiple of 4, is read one byte per load, never by aligned-down
+ * dword loads.  The host-pointer form stages n_frames * H * W * 3 BYTES of frames; the _dev form is stream-ordered and asynchronous.
+ * SILENT_E_INVALID: a NULL plan / frames / pyr, a plan of another context, n_frames < 1 (in this order); SILENT_E_UNSUPPORTED: a
+ * single-channel plan (such a plan takes colour bytes through silent_pyramid_u8x3).  (ABI additions only: SILENT_ABI_VERSION is
+ * unchanged.) */
+int silent_pyramid_rgb8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, float* pyr);
+int silent_pyramid_rgb8_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, float* pyr,
+                            silent_stream stream);
+
+/* Strided uint8 frames, read in place. A decoder hands over NV12 surfaces with a row pitch, a camera or compositor BGRA / BGRX, YUYV
  * carries luma on every second byte, a region of interest is a view with its parent's row step, hipMallocPitch pads rows: none of
  * these is the packed layout of the *_u8 / *_u8x3 entry points, and packing them first is a launch that reads and writes the whole
  * batch plus a second copy of it in device memory.  A view is a base pointer and three BYTE strides (byte, not pixel: a pitched BGR

@@ -87,7 +87,7 @@ _lib = None
 _vp = C.c_void_p
 _fp = C.c_void_p          # float* passed as an address (host ndarray.ctypes.data or a device pointer)
 _hp = C.POINTER(C.c_uint16)   # a float16 map (silent_gray_pass_h: IEEE binary16 as uint16_t*); half_ptr() makes one from an address
-_bp = C.POINTER(C.c_uint8)    # uint8 frames (the *_u8 and *_u8x3 entry points); byte_ptr() makes one from an address
+_bp = C.POINTER(C.c_uint8)    # uint8 frames (the *_u8, *_u8x3 and *_rgb8 entry points); byte_ptr() makes one from an address
 _wp = C.POINTER(FrameView)    # a strided uint8 view (the *_view entry points); view_ptr() makes one from _runtime.frame_view_of's tuple
 _sp = C.POINTER(C.c_uint16)   # uint16 frames (the *_u16 entry points); short_ptr() makes one from an address
 _xp = C.POINTER(FrameView16)  # a strided uint16 view (the *_view16 entry points); view16_ptr() makes one from frame_view_of's tuple
@@ -128,6 +128,8 @@ _SIGNATURES = {
     "silent_pyramid_u8x3": [_vp, _vp, _bp, _i, _fp],
     "silent_pyramid_u8_dev": [_vp, _vp, _bp, _i, _fp, _vp],
     "silent_pyramid_u8x3_dev": [_vp, _vp, _bp, _i, _fp, _vp],
+    "silent_pyramid_rgb8": [_vp, _vp, _bp, _i, _fp],
+    "silent_pyramid_rgb8_dev": [_vp, _vp, _bp, _i, _fp, _vp],
     "silent_gray_pass_u8": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8x3": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8_dev": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i, _u, _vp],

@@ -924,6 +924,32 @@ def check_frame_layout(frame_layout, mode="gray", frame_dtype="float32", accumul
     return frame_layout
 
 
+RGB_FRAME_DTYPES = ("float32", "uint8")
+
+
+def check_rgb_frame_dtype(rgb_frame_dtype, mode="rgb", frame_dtype="float32", frame_channels=1, frame_layout="packed"):
+    """The rgb_frame_dtype argument of PyramidPlan.run and LineEndPipeline: "float32" (default: nothing changes) or "uint8" (mode
+    "rgb" / a 3-channel plan: packed interleaved uint8 colour frames [n, H, W, 3] read as they are by silent_pyramid_rgb8 -- byte c of
+    a pixel enters as (float)byte at the load, no cast launch, no float32 copy of the batch; the pyramid is that of
+    frames.astype(float32) bit for bit).  A keyword of its own because frame_dtype="uint8" means single-channel frames and stays
+    refused for mode "rgb".  The name is checked first; then what "uint8" needs: mode "rgb" and the defaults of frame_dtype,
+    frame_channels and frame_layout (those three describe the frames of a gray pass)."""
+    if not isinstance(rgb_frame_dtype, str) or rgb_frame_dtype not in RGB_FRAME_DTYPES:
+        raise ValueError("rgb_frame_dtype must be 'float32' or 'uint8', got %r" % (rgb_frame_dtype,))
+    if rgb_frame_dtype == "uint8":
+        if mode != "rgb":
+            raise ValueError("rgb_frame_dtype='uint8' is for mode 'rgb' (mode 'gray' takes uint8 frames through frame_dtype)")
+        if frame_dtype != "float32":
+            raise ValueError("rgb_frame_dtype='uint8' does not combine with frame_dtype=%r (frame_dtype describes the frames of mode 'gray')"
+                             % (frame_dtype,))
+        if frame_channels != 1:
+            raise ValueError("rgb_frame_dtype='uint8' does not combine with frame_channels=%r (the frames are [n, H, W, 3] already)"
+                             % (frame_channels,))
+        if frame_layout != "packed":
+            raise ValueError("rgb_frame_dtype='uint8' does not combine with frame_layout=%r (packed frames only)" % (frame_layout,))
+    return rgb_frame_dtype
+
+
 class PyramidPlan(object):
     """Tap tables of one (frame size, level geometry) on the device.  ``levels`` is a list of dicts / tuples
     (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w).  accumulation="float64" (single-channel plans): every op of
@@ -968,13 +994,29 @@ class PyramidPlan(object):
         silent_<name>_u16 or silent_<name>_view16."""
         return _lib.gray_entry(name, frame_dtype, frame_channels, frame_layout=frame_layout)[0]
 
-    def run(self, frames, frame_dtype="float32", frame_channels=1, frame_layout="packed"):
+    def _frames_rgb8(self, frames):
+        """[n, H, W, 3] packed uint8 colour frames of this 3-channel plan (uint8 ndarray, or contiguous uint8 GPU tensor) as an
+        operand on the plan's context: passed as they are, anything else is refused, never converted."""
+        _require_narrow(frames, "uint8")
+        if frames.ndim != 4 or tuple(frames.shape[1:]) != self.frame_shape:
+            raise ValueError("frames must be [n, %d, %d, %d], got %s" % (self.frame_shape + (tuple(frames.shape),)))
+        return _Operand(frames, ctx=self.ctx, frame_dtype="uint8")
+
+    def run(self, frames, frame_dtype="float32", frame_channels=1, frame_layout="packed", rgb_frame_dtype="float32"):
         """frames: [n, H, W, C] ndarray (host) or torch GPU tensor.  Returns a PackedPyramid.  frame_dtype="uint8" (single-channel
         plans): uint8 frames read as they are (silent_pyramid_u8), the same pyramid bit for bit.  frame_channels=3 (with "uint8"):
         [n, H, W, 3] interleaved colour frames (silent_pyramid_u8x3), the pyramid of the frame of values (b0 + b1 + b2) * f32(1/3).
         frame_layout="strided" (with "uint8"): any uint8 view with positive strides, read in place (silent_pyramid_view).
         frame_dtype="uint16": unsigned 16-bit frames read as they are (silent_pyramid_u16; strided: silent_pyramid_view16), the pyramid of
-        frames.astype(float32) bit for bit."""
+        frames.astype(float32) bit for bit.
+        rgb_frame_dtype="uint8" (3-channel plans): packed uint8 colour frames [n, H, W, 3] read as they are (silent_pyramid_rgb8),
+        the 3-channel pyramid of frames.astype(float32) bit for bit."""
+        mode = "gray" if self.frame_shape[2] == 1 else "rgb"
+        if check_rgb_frame_dtype(rgb_frame_dtype, mode, frame_dtype, frame_channels, frame_layout) == "uint8":
+            op = self._frames_rgb8(frames)
+            out, optr = op.empty(op.n_frames * self.frame_px * 3)
+            op.call("pyramid_rgb8", self.handle, op.ptr, op.n_frames, optr)
+            return PackedPyramid(out, self.extents, 3, op.n_frames)
         op, c = self._frames(frames, frame_dtype, frame_channels, frame_layout), self.frame_shape[2]
         out, optr = op.empty(op.n_frames * self.frame_px * c)
         op.call(self._entry("pyramid", frame_dtype, frame_channels, frame_layout), self.handle, op.ptr, op.n_frames, optr)

@@ -96,7 +96,8 @@ __device__ __forceinline__ int mirror_index(int i, int n) {
 template <int C, bool F64 = false, typename FT = float>
 __global__ __launch_bounds__(256) void pyramid_unit_kernel(frame_param<FT> frames,
                                                            float* __restrict__ pyr, const PyrTabT<F64> tab) {
-    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 / uint16 frames: one channel, float32 accumulation");
+    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && (C == 1 || (C == 3 && kFrameBytes<FT>)))),
+                  "uint8 / uint16 frames: one channel (packed uint8 also three interleaved channels), float32 accumulation");
     constexpr int R = kUnitTH;
     const unsigned bid = blockIdx.x;
     const int frame = (int)(bid / (unsigned)tab.unit_tiles_per_frame);
@@ -209,7 +210,8 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(frame_param<FT> frame
 // FT = unsigned char (uint8 frames): s_src stays float, the bytes are widened while staging.  The group path then loads 4 bytes
 // (one dword) per lane, which is legal only where the ADDRESS is 4-byte aligned -- and the uint8 frames pointer has no alignment
 // requirement: W % 4 == 0 puts every row start (frame * H * W + sy * W) and every group offset f on the dword grid relative to the
-// base, so the base address decides; any other base or width takes the one-element path.
+// base, so the base address decides; any other base or width takes the one-element path.  The same at C == 3 (packed interleaved uint8
+// colour frames of 3-channel plans, silent_pyramid_rgb8): a group is 4 bytes of the interleaved row, legal where 3 W % 4 == 0.
 // FT = unsigned short (uint16 frames): the same with 4 elements in 8 bytes (one dwordx2) per lane, legal where the address is 8-byte
 // aligned -- the frames pointer is only 2-byte aligned: W % 4 == 0 puts every frame and row start and every group offset on the 8-byte
 // grid relative to the base, so again the base address decides (block-uniform); any other base or width takes the one-element path.
@@ -218,7 +220,8 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(frame_param<FT> frame
 template <int C, bool F64 = false, typename FT = float>
 __global__ __launch_bounds__(256) void pyramid_region_kernel(frame_param<FT> frames,
                                                              float* __restrict__ pyr, const PyrTabT<F64> tab) {
-    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && C == 1)), "uint8 / uint16 frames: one channel, float32 accumulation");
+    static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && (C == 1 || (C == 3 && kFrameBytes<FT>)))),
+                  "uint8 / uint16 frames: one channel (packed uint8 also three interleaved channels), float32 accumulation");
     constexpr int RW = region_w(C), SW = region_sw(C), SH = region_sh(C), ROWF = SW * C, VR = region_vr(C);
     __shared__ __attribute__((aligned(16))) float s_src[SH * ROWF];
     __shared__ __attribute__((aligned(16))) acc_t<F64> s_v[VR * ROWF];
@@ -421,8 +424,9 @@ struct BorderTab {
 
 // border pixel x channel number gid of the launch (frames x bt.per_frame x C of them).  LEAN: one tap column at a time (6 loads in
 // flight instead of 36) -- inside the walk kernel, whose 7 waves per SIMD must not pay for this path's registers
-template <int C, bool LEAN = false>
-__device__ __forceinline__ void pyramid_border_px(const float* __restrict__ frames, float* __restrict__ pyr, const PyrTab& tab,
+// FT: float, or unsigned char at C == 3 (packed interleaved uint8 colour frames: the byte widened at the load)
+template <int C, bool LEAN = false, typename FT = float>
+__device__ __forceinline__ void pyramid_border_px(const FT* __restrict__ frames, float* __restrict__ pyr, const PyrTab& tab,
                                                   const BorderTab& bt, long long gid, int n_frames) {
     const long long per_frame = (long long)bt.per_frame * C;
     if (gid >= per_frame * n_frames) return;
@@ -454,16 +458,16 @@ __device__ __forceinline__ void pyramid_border_px(const float* __restrict__ fram
     }
     (void)ih;
     const PyrLevelDev& lv = tab.lv[b.level];
-    const float* __restrict__ src = frames + (long long)frame * tab.H * tab.W * C;
+    const FT* __restrict__ src = frames + (long long)frame * tab.H * tab.W * C;
     const int* __restrict__ yi = tab.yidx + (long long)(lv.ytab_off + oy) * 6;
     const int* __restrict__ xi = tab.xidx + (long long)(lv.xtab_off + ox) * 6;
     const float* __restrict__ wy = tab.yw + (long long)(lv.ytab_off + oy) * 6;
     const float* __restrict__ wx = tab.xw + (long long)(lv.xtab_off + ox) * 6;
     auto column = [&](int j) {
         const long long col = (long long)(xi[j] + lv.src_x0) * C + ch;
-        float a = __builtin_fmaf(wy[0], src[(long long)(yi[0] + lv.src_y0) * tab.W * C + col], 0.0f);
+        float a = __builtin_fmaf(wy[0], (float)src[(long long)(yi[0] + lv.src_y0) * tab.W * C + col], 0.0f);
 #pragma unroll
-        for (int i = 1; i < 6; ++i) a = __builtin_fmaf(wy[i], src[(long long)(yi[i] + lv.src_y0) * tab.W * C + col], a);
+        for (int i = 1; i < 6; ++i) a = __builtin_fmaf(wy[i], (float)src[(long long)(yi[i] + lv.src_y0) * tab.W * C + col], a);
         return a;
     };
     float acc;
@@ -483,10 +487,10 @@ __device__ __forceinline__ void pyramid_border_px(const float* __restrict__ fram
 }
 
 // (on its own: PYRAMID knob 8; by default these pixels are the first blocks of the walk's launch, silent_walk_rgb.h)
-template <int C>
-__global__ __launch_bounds__(256) void pyramid_border_kernel(const float* __restrict__ frames, float* __restrict__ pyr, const PyrTab tab,
+template <int C, typename FT = float>
+__global__ __launch_bounds__(256) void pyramid_border_kernel(const FT* __restrict__ frames, float* __restrict__ pyr, const PyrTab tab,
                                                              const BorderTab bt, int n_frames) {
-    pyramid_border_px<C>(frames, pyr, tab, bt, (long long)blockIdx.x * 256 + threadIdx.x, n_frames);
+    pyramid_border_px<C, false, FT>(frames, pyr, tab, bt, (long long)blockIdx.x * 256 + threadIdx.x, n_frames);
 }
 
 // ------------------------------------------------------------------------------------------ ZERO FILL

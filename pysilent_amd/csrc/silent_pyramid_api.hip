@@ -594,10 +594,10 @@ SILENT_EXPORT void silent_pyramid_plan_destroy(silent_pyramid_plan* plan) try {
 } catch (...) {
 }
 
-template <int G, int PX>
+template <int G, int PX, typename FT>
 static int walk3_blocks_per_cu() {
     int per_cu = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pyramid_walk3_kernel<G, PX>, kW3Threads, 0);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pyramid_walk3_kernel<G, PX, FT>, kW3Threads, 0);
     (void)hipGetLastError();
     return std::max(per_cu, 1);
 }
@@ -608,12 +608,14 @@ static int walk3_blocks_per_cu() {
 // model is right for one plan of equal blocks that fills the chip a few times (config 3: 4 ... 20 segments per frame measured
 // flat within 3 %, both rules land there) and wrong for the reference layout, where it gave the union plan exactly one round of
 // 224-row blocks beside the unit plan's short ones: 0.199 ms, against 0.165 ms with 12 - 20 segments (profiles/r05_experiments.txt 7).
+// FT: the frame kind of the launch (the occupancy asked about is that of the instantiation that is launched).
+template <typename FT>
 static bool walk3_plan(const silent_ctx* ctx, const silent_pyramid_plan* plan, int n_frames, Walk3Args* wa) {
     if (plan->tab.C != 3 || !plan->walk_pyr_ok) return false;
     *wa = plan->walk;
     const int px = plan->walk_px;
     int per_cu = 1;
-#define PER_CU(PX_) case PX_: per_cu = plan->walk_G <= 4 ? walk3_blocks_per_cu<4, PX_>() : walk3_blocks_per_cu<7, PX_>(); break
+#define PER_CU(PX_) case PX_: per_cu = plan->walk_G <= 4 ? walk3_blocks_per_cu<4, PX_, FT>() : walk3_blocks_per_cu<7, PX_, FT>(); break
     switch (px) { PER_CU(36); PER_CU(32); PER_CU(28); PER_CU(24); default: return false; }
 #undef PER_CU
     const long long resident = (long long)per_cu * ctx->n_cus;
@@ -654,6 +656,46 @@ static int pyramid_checks(silent_ctx* ctx, const char* who, const silent_pyramid
     return SILENT_OK;
 }
 
+// The launches of a 3-channel plan on frame kind FT -- float, or unsigned char (packed interleaved uint8 colour frames,
+// silent_pyramid_rgb8): ONE body, so both kinds take the same route on the same plan under the same PYRAMID knob bits.
+template <typename FT>
+static int launch_pyramid3(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames, float* pyr,
+                           hipStream_t s, bool with_unit, bool with_region, long long b_unit, long long b_region) {
+    const PyrTab& tab = plan->tab;
+    const unsigned kopts = ctx->tune[SILENT_TUNE_PYRAMID];
+    Walk3Args w3t;
+    if (plan->walk_pyr_ok && with_unit && with_region && !(kopts & 3u) && walk3_plan<FT>(ctx, plan, n_frames, &w3t)) {
+        // single-read RGB pyramid (pyramid_walk3_kernel, silent_walk_rgb.h); PYRAMID knob bits 1 / 2: unit + region kernels
+        // union plans: the inner levels' first / last output rows and columns -- the last blocks of the same launch (PYRAMID knob 8:
+        // a launch of their own behind the walk)
+        const long long bthreads = (long long)plan->walk_border.per_frame * 3 * n_frames;
+        const long long bblocks = (bthreads + 255) / 256;
+        const bool border_inside = bblocks > 0 && !(kopts & 8u);
+        const long long wblocks = (long long)n_frames * w3t.blocks_per_frame + (border_inside ? bblocks : 0);
+        if (wblocks > 0x7fffffffll || bblocks > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many blocks for one launch");
+        WalkBorderArgs wb;
+        std::memset(&wb, 0, sizeof(wb));
+        wb.first = 0x7fffffff;
+        if (border_inside) {
+            wb.first = (int)((long long)n_frames * w3t.blocks_per_frame);
+            wb.n_frames = n_frames;
+            wb.tab = tab;
+            wb.bt = plan->walk_border;
+        }
+#define WALK3(G_, PX_) hipLaunchKernelGGL((pyramid_walk3_kernel<G_, PX_, FT>), dim3((unsigned)wblocks), dim3(kW3Threads), 0, s, frames, pyr, w3t, wb)
+#define WALK3_PX(PX_) case PX_: if (plan->walk_G <= 4) WALK3(4, PX_); else WALK3(7, PX_); break
+        switch (plan->walk_px) { WALK3_PX(36); WALK3_PX(32); WALK3_PX(28); WALK3_PX(24); default: break; }   // (walk3_plan refuses any other)
+#undef WALK3_PX
+#undef WALK3
+        if (bblocks > 0 && !border_inside)
+            hipLaunchKernelGGL((pyramid_border_kernel<3, FT>), dim3((unsigned)bblocks), dim3(256), 0, s, frames, pyr, tab, plan->walk_border, n_frames);
+        return SILENT_OK;
+    }
+    if (b_unit) hipLaunchKernelGGL((pyramid_unit_kernel<3, false, FT>), dim3((unsigned)b_unit), dim3(256), 0, s, frames, pyr, tab);
+    if (b_region) hipLaunchKernelGGL((pyramid_region_kernel<3, false, FT>), dim3((unsigned)b_region), dim3(256), 0, s, frames, pyr, tab);
+    return SILENT_OK;
+}
+
 template <typename FT>
 int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames, float* pyr,
                    hipStream_t s, bool with_unit, bool with_region) {
@@ -665,7 +707,6 @@ int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* 
     if (b_unit > 0x7fffffffll || b_region > 0x7fffffffll || b_zero > 0x7fffffffll)
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many tiles for one launch");
     const unsigned kopts = ctx->tune[SILENT_TUNE_PYRAMID];  // 1: no stream kernel
-    Walk3Args w3t;
     if (plan->stream_ok && with_unit && with_region && !(kopts & 1u)) {
         // single-read pyramid: frame -> every level in one kernel (pyramid_stream_kernel; single-channel plans only:
         // on interleaved RGB the stride-3 accesses of the same kernel made it 1.5x SLOWER than unit + region kernels)
@@ -684,40 +725,14 @@ int launch_pyramid(silent_ctx* ctx, const char* who, const silent_pyramid_plan* 
         if (b_unit) hipLaunchKernelGGL((pyramid_unit_kernel<1, false, FT>), dim3((unsigned)b_unit), dim3(256), 0, s, kernel_frames(frames), pyr, tab);
         if (b_region)
             hipLaunchKernelGGL((pyramid_region_kernel<1, false, FT>), dim3((unsigned)b_region), dim3(256), 0, s, kernel_frames(frames), pyr, tab);
-    } else if (tab.C == 3 && plan->walk_pyr_ok && with_unit && with_region && !(kopts & 3u) && walk3_plan(ctx, plan, n_frames, &w3t)) {
-        // single-read RGB pyramid (pyramid_walk3_kernel, silent_walk_rgb.h); PYRAMID knob bits 1 / 2: unit + region kernels
-        // union plans: the inner levels' first / last output rows and columns -- the last blocks of the same launch (PYRAMID knob 8:
-        // a launch of their own behind the walk)
-        const long long bthreads = (long long)plan->walk_border.per_frame * 3 * n_frames;
-        const long long bblocks = (bthreads + 255) / 256;
-        const bool border_inside = bblocks > 0 && !(kopts & 8u);
-        const long long wblocks = (long long)n_frames * w3t.blocks_per_frame + (border_inside ? bblocks : 0);
-        if (wblocks > 0x7fffffffll || bblocks > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many blocks for one launch");
-        WalkBorderArgs wb;
-        std::memset(&wb, 0, sizeof(wb));
-        wb.first = 0x7fffffff;
-        if (border_inside) {
-            wb.first = (int)((long long)n_frames * w3t.blocks_per_frame);
-            wb.n_frames = n_frames;
-            wb.tab = tab;
-            wb.bt = plan->walk_border;
-        }
-#define WALK3(G_, PX_) hipLaunchKernelGGL((pyramid_walk3_kernel<G_, PX_>), dim3((unsigned)wblocks), dim3(kW3Threads), 0, s, frames, pyr, w3t, wb)
-#define WALK3_PX(PX_) case PX_: if (plan->walk_G <= 4) WALK3(4, PX_); else WALK3(7, PX_); break
-        switch (plan->walk_px) { WALK3_PX(36); WALK3_PX(32); WALK3_PX(28); WALK3_PX(24); default: break; }   // (walk3_plan refuses any other)
-#undef WALK3_PX
-#undef WALK3
-        if (bblocks > 0 && !border_inside)
-            hipLaunchKernelGGL(pyramid_border_kernel<3>, dim3((unsigned)bblocks), dim3(256), 0, s, frames, pyr, tab, plan->walk_border, n_frames);
+    } else if (tab.C == 3) {
+        TRY(launch_pyramid3(ctx, who, plan, frames, n_frames, pyr, s, with_unit, with_region, b_unit, b_region));
     } else if (plan->f64) {   // (single-channel)
         if (b_unit) hipLaunchKernelGGL((pyramid_unit_kernel<1, true>), dim3((unsigned)b_unit), dim3(256), 0, s, frames, pyr, plan->tab64);
         if (b_region) hipLaunchKernelGGL((pyramid_region_kernel<1, true>), dim3((unsigned)b_region), dim3(256), 0, s, frames, pyr, plan->tab64);
-    } else if (tab.C == 1) {
+    } else {
         if (b_unit) hipLaunchKernelGGL(pyramid_unit_kernel<1>, dim3((unsigned)b_unit), dim3(256), 0, s, frames, pyr, tab);
         if (b_region) hipLaunchKernelGGL(pyramid_region_kernel<1>, dim3((unsigned)b_region), dim3(256), 0, s, frames, pyr, tab);
-    } else {
-        if (b_unit) hipLaunchKernelGGL(pyramid_unit_kernel<3>, dim3((unsigned)b_unit), dim3(256), 0, s, frames, pyr, tab);
-        if (b_region) hipLaunchKernelGGL(pyramid_region_kernel<3>, dim3((unsigned)b_region), dim3(256), 0, s, frames, pyr, tab);
     }
     if (b_zero && tab.C == 1) hipLaunchKernelGGL(pyramid_zero_kernel<1>, dim3((unsigned)b_zero), dim3(256), 0, s, pyr, tab);
     else if (b_zero) hipLaunchKernelGGL(pyramid_zero_kernel<3>, dim3((unsigned)b_zero), dim3(256), 0, s, pyr, tab);
@@ -880,4 +895,49 @@ SILENT_EXPORT int silent_pyramid_view16(silent_ctx* ctx, const silent_pyramid_pl
     return pyramid_view16(ctx, "silent_pyramid_view16", true, plan, frames, n_frames, pyr, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_view16");
+}
+
+// Packed interleaved uint8 colour frames for 3-channel plans (silent_hip.h): byte c of pixel (y, x) enters as (float)byte at the load,
+// so the pyramid is the float32-frame call's on the widened frames bit for bit, on the route launch_pyramid takes for float frames.
+static int pyramid_rgb8_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                               const float* pyr) {
+    TRY(pyramid_checks<float>(ctx, who, plan, frames != nullptr, n_frames, pyr));
+    if (plan->tab.C != 3)
+        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": interleaved uint8 colour frames are for 3-channel plans (a single-channel plan takes them through silent_pyramid_u8x3)");
+    return SILENT_OK;
+}
+
+static int launch_pyramid_rgb8(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                               float* pyr, hipStream_t s) {
+    TRY(pyramid_rgb8_checks(ctx, who, plan, frames, n_frames, pyr));
+    const PyrTab& tab = plan->tab;
+    const long long b_unit = (long long)tab.unit_tiles_per_frame * n_frames;
+    const long long b_region = tab.n_general ? (long long)tab.regions_x * tab.regions_y * n_frames : 0;
+    const long long b_zero = (long long)tab.zero_chunks_per_frame * n_frames;
+    if (b_unit > 0x7fffffffll || b_region > 0x7fffffffll || b_zero > 0x7fffffffll)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many tiles for one launch");
+    TRY(launch_pyramid3<unsigned char>(ctx, who, plan, frames, n_frames, pyr, s, true, true, b_unit, b_region));
+    if (b_zero) hipLaunchKernelGGL(pyramid_zero_kernel<3>, dim3((unsigned)b_zero), dim3(256), 0, s, pyr, tab);
+    return check_launch(ctx, who);
+}
+
+SILENT_EXPORT int silent_pyramid_rgb8_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                          float* pyr, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return launch_pyramid_rgb8(ctx, "silent_pyramid_rgb8", plan, frames, n_frames, pyr, (hipStream_t)stream);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_rgb8_dev");
+}
+
+SILENT_EXPORT int silent_pyramid_rgb8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+                                      float* pyr) try {
+    NEED_CTX(ctx);
+    const char* who = "silent_pyramid_rgb8";
+    TRY(pyramid_rgb8_checks(ctx, who, plan, frames, n_frames, pyr));
+    HostStage hs(ctx);
+    const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * 3 * n_frames),
+              o = hs.out(pyr, (size_t)plan->tab.frame_px_out * 3 * 4 * n_frames);
+    return hs.run([&] { return launch_pyramid_rgb8(ctx, who, plan, hs.dev<uint8_t>(x), n_frames, hs.dev<float>(o), nullptr); });
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_rgb8");
 }

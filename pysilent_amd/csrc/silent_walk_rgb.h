@@ -127,9 +127,14 @@ struct WalkBorderArgs {
 // of 4 dwords.  meta: bit 0 "an output row of this level completes with this source row", bits 8.. that output row.
 __host__ __device__ constexpr int w3_prog_row(int gp) { return (gp * 7 + 3) / 4 * 4; }
 
-template <int G, int PX>
-__global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const float* __restrict__ frames, float* __restrict__ pyr,
+// FT: the frame element type -- float, or unsigned char (packed interleaved uint8 colour frames [n, H, W, 3], silent_pyramid_rgb8: byte c
+// of pixel (y, x) enters as (float)byte, an unsigned load and an exact conversion).  Only the LOADER touches the frame: the ring stays
+// float32 and the consumers' text is the same for both kinds, so the uint8 kernel stores the bits the float kernel stores for the
+// widened frame.  The FT = float instantiations are the code as it was (their machine code is unchanged).
+template <int G, int PX, typename FT = float>
+__global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const FT* __restrict__ frames, float* __restrict__ pyr,
                                                                     const Walk3Args args, const WalkBorderArgs border) {
+    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT>, "float32 or packed uint8 colour frames");
     static_assert(G == stream_pad_levels(G), "row programs are padded to 4 or 7 levels");
     static_assert(PX == 36 || PX == 32 || PX == 28 || PX == 24, "");
     constexpr int kW3Px = PX, kW3StripPx = kW3NC * PX, kW3RowF = w3_row_f(PX);
@@ -144,7 +149,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const float* 
 
     if (blockIdx.x >= (unsigned)border.first) {   // block-uniform
         if (threadIdx.x < 256)
-            pyramid_border_px<3, true>(frames, pyr, border.tab, border.bt, (long long)(blockIdx.x - (unsigned)border.first) * 256 + threadIdx.x, border.n_frames);
+            pyramid_border_px<3, true, FT>(frames, pyr, border.tab, border.bt, (long long)(blockIdx.x - (unsigned)border.first) * 256 + threadIdx.x, border.n_frames);
         return;
     }
     const unsigned bid = blockIdx.x;
@@ -170,8 +175,8 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const float* 
 
     if (wave == kW3NC) {
         // ------------------------------------------------------------------ loader: LDS-DMA only
-        const float* __restrict__ src = frames + (long long)frame * args.H * args.W * 3;
-        const int rowf = args.W * 3;                           // floats of a FRAME row
+        const FT* __restrict__ src = frames + (long long)frame * args.H * args.W * 3;
+        const int rowf = args.W * 3;                           // floats (uint8 frames: bytes) of a FRAME row
         // ring float r <-> frame-row float A + r, A = the crop's pixel R0 minus the alignment shift.  Frame widths that are a
         // multiple of 4 (every row starts on 16 bytes): A is a multiple of 4 and a lane fetches a 16-byte aligned group of 4 floats,
         // two DMA loads per ring row.  Other widths (round 5): no shift, a lane fetches ONE FLOAT, 5 - 8 loads per ring row -- the
@@ -187,12 +192,26 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const float* 
             for (int k = 0; k < kRowLoads; ++k)
                 f[k] = DWORD_DMA ? min(max(A + lane + 64 * k, 0), rowf - 1) : min(max(A + 256 * k + lane * 4, 0), rowf - 4);
             auto issue = [&](int c, int slot) {
+                // uint8 frames: the same lane -> ring mapping with the frame row counted in BYTES -- a lane's group of 4 ring floats is
+                // one dword of the frame row (4 bytes, widened in registers, one 16-byte LDS write), its single float one byte.  All
+                // loads of the chunk are issued first (8 or 32 in flight: one memory latency per chunk, not one per load), then the
+                // records' DMA, then the rows are widened and written; the chunk is complete -- vmcnt(0), lgkmcnt(0) -- before the loader
+                // goes on to its next barrier, still two chunks ahead of the consumers, who take ~2000 cycles a row
+                typename std::conditional<DWORD_DMA, unsigned char, unsigned>::type v[kFrameBytes<FT> ? kW3CH : 1][kRowLoads];
+                (void)v;
 #pragma unroll
                 for (int r = 0; r < kW3CH; ++r) {
                     const int y = seg_y0 - 4 + c * kW3CH + r;
-                    const float* rp = src + (long long)(mirror_near(y, tab.src_h) + tab.src_y0) * args.W * 3;
+                    const FT* rp = src + (long long)(mirror_near(y, tab.src_h) + tab.src_y0) * args.W * 3;
                     float* dst = &s_ring[slot * kW3CH + r][0];
-                    if constexpr (DWORD_DMA) {
+                    if constexpr (kFrameBytes<FT>) {
+                        (void)dst;
+#pragma unroll
+                        for (int k = 0; k < kRowLoads; ++k) {
+                            if constexpr (DWORD_DMA) v[r][k] = rp[f[k]];
+                            else v[r][k] = *reinterpret_cast<const unsigned*>(rp + f[k]);
+                        }
+                    } else if constexpr (DWORD_DMA) {
 #pragma unroll
                         for (int k = 0; k < kRowLoads; ++k)
                             if (k + 1 < kRowLoads || lane < kW3RowF - 64 * k)
@@ -209,6 +228,24 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const float* 
                 if (lane < NV) __builtin_amdgcn_global_load_lds((walk_glb_ptr)rp, (walk_lds_ptr)dst, 16, 0, 0);
                 if constexpr (NV > 64) {
                     if (lane < NV - 64) __builtin_amdgcn_global_load_lds((walk_glb_ptr)(rp + 256), (walk_lds_ptr)(dst + 256), 16, 0, 0);
+                }
+                if constexpr (kFrameBytes<FT>) {
+#pragma unroll
+                    for (int r = 0; r < kW3CH; ++r) {
+                        float* row = &s_ring[slot * kW3CH + r][0];
+#pragma unroll
+                        for (int k = 0; k < kRowLoads; ++k) {
+                            if constexpr (DWORD_DMA) {
+                                if (k + 1 < kRowLoads || lane < kW3RowF - 64 * k) row[64 * k + lane] = (float)v[r][k];
+                            } else {
+                                const unsigned q = v[r][k];
+                                if (k == 0 || lane < (kW3RowF - 256) / 4)
+                                    *reinterpret_cast<float4*>(row + 256 * k + lane * 4) =
+                                        make_float4((float)(q & 0xffu), (float)((q >> 8) & 0xffu), (float)((q >> 16) & 0xffu), (float)(q >> 24));
+                            }
+                        }
+                    }
+                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // rows written, records landed
                 }
             };
             // scipy mirrors every tap at the CROP's edge (d c b | a b c d | c b a).  The ring row of a strip at the crop's left / right
@@ -233,7 +270,9 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const float* 
             int slot2 = kWalkSlots - 1, slot0 = 0;
             for (int c = 0; c < n_chunks; ++c) {
                 // chunk c has landed when at most the next chunk's loads (three slots: one chunk in flight behind it) are outstanding
-                if (kWalkSlots == 3 && c + 1 < n_chunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kRowLoads * kW3CH + (kW3CH * PR / 4 > 64 ? 2 : 1)) : "memory");
+                // (uint8 frames: nothing is outstanding here, issue() ends with vmcnt(0) -- the counted wait would name a mix of register
+                // loads and DMA loads that the compiler is free to reorder)
+                if (!kFrameBytes<FT> && kWalkSlots == 3 && c + 1 < n_chunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kRowLoads * kW3CH + (kW3CH * PR / 4 > 64 ? 2 : 1)) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (any_fix) {
 #pragma unroll
@@ -249,7 +288,12 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const float* 
                 slot2 = slot2 == kWalkSlots - 1 ? 0 : slot2 + 1;
             }
         };
-        if (rowf & 3) loader(std::true_type{});                 // block-uniform
+        // (uint8 frames: a dword of the frame row needs a 4-byte aligned ADDRESS -- W % 4 == 0 puts every frame and row start and every
+        // group on the dword grid relative to `frames`, which has no alignment requirement: the base decides, and any other base
+        // takes the one-byte path, which never touches a byte outside the batch)
+        bool single = (rowf & 3) != 0;                          // block-uniform
+        if constexpr (kFrameBytes<FT>) single = single || (reinterpret_cast<unsigned long long>(frames) & 3ull) != 0;
+        if (single) loader(std::true_type{});
         else loader(std::false_type{});
         return;
     }

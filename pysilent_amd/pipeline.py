@@ -132,7 +132,14 @@ class LineEndPipeline(object):
                  max_keypoints_per_frame=None, selection=False, top_percent=0.1, keep_selection_maps=False, value_map=None,
                  peak_value_map=None, orient_map=True, overlap=False, overlap_priorities=True, placement="auto", keypoints=False,
                  regions=None, accumulation="float32", storage="float32", frame_dtype="float32", frame_channels=1,
-                 frame_layout="packed"):
+                 frame_layout="packed", rgb_frame_dtype="float32"):
+        # rgb_frame_dtype="uint8" (mode "rgb"): step() takes packed interleaved uint8 colour frames [batch, H, W, 3] as a camera or a
+        # decoder delivers them and the pyramid kernels read the bytes themselves (silent_pyramid_rgb8_dev) -- no widening cast, no
+        # float32 copy of the batch; the pyramid, and with it every map and keypoint, is bit-identical to the float32 pipeline's on
+        # the widened frames.  A keyword of its own: frame_dtype / frame_channels / frame_layout describe the frames of mode "gray" and
+        # keep their refusals on mode "rgb".  Checked first, before any GPU or torch work: unknown names, mode "gray", and "uint8"
+        # beside a non-default frame_dtype / frame_channels / frame_layout
+        self.rgb_frame_dtype = _runtime.check_rgb_frame_dtype(rgb_frame_dtype, mode, frame_dtype, frame_channels, frame_layout)
         # accumulation="float64" (mode "gray"): every op sums its taps in float64 and rounds once to float32, like the CPU oracle
         # (SILENT_PLAN_ACCUM_F64: the pyramid within 1 ulp of it, CS and end bit-identical to it on the same pyramid).  Checked first:
         # no GPU or torch work for a refused argument
@@ -167,6 +174,8 @@ class LineEndPipeline(object):
         # rgba16[..., 1], a window of larger frames).
         # Refused here as well: unknown names, mode "rgb", frame_dtype="float32", accumulation="float64"
         self.frame_layout = _runtime.check_frame_layout(frame_layout, mode, frame_dtype, accumulation)
+        if self.rgb_frame_dtype == "uint8":
+            self.frame_dtype = "uint8"         # what step() takes: the ingest ring, the tuners' frames and the byte accounting follow it
         import torch
         self.torch = torch
         self.mode = mode
@@ -550,7 +559,8 @@ class LineEndPipeline(object):
         """4*[H*W*C (frame read) + P*C (pyramid written) + P*C (pyramid read) + P*sum(C_out returned)]; for crop layouts the
         frame read is the largest crop any level resamples (the part of the frame the pyramid depends on).  storage="float16":
         the returned CS and end maps count 2 bytes per element.  frame_dtype="uint8": the frame read counts 1 byte per frame element
-        ("uint16": 2 bytes) -- frame_shape[2] of them per pixel (3 for interleaved colour frames, whose pyramid and maps stay single-channel)."""
+        ("uint16": 2 bytes) -- frame_shape[2] of them per pixel (3 for interleaved colour frames, whose pyramid and maps stay single-channel;
+        mode "rgb" with rgb_frame_dtype="uint8" reports frame_dtype "uint8" and counts the same 1 byte per frame element)."""
         h, w, fc = self.frame_shape
         c = self.channels
         if self.crop_px is not None:
@@ -602,7 +612,8 @@ class LineEndPipeline(object):
                     + (" of 3 interleaved channels (value formed at the load)" if self._colour_frames else "")
                     + (", read in place from a strided view" if getattr(self, "frame_layout", "packed") == "strided" else ""))
         return ("single-read RGB pyramid (pyramid_walk3_kernel), fused RGB chain, max/min + fused selection "
-                "(top 10 % > NMS > value), cell-max / count / scan / write keypoint kernels")
+                "(top 10 % > NMS > value), cell-max / count / scan / write keypoint kernels"
+                + (", uint8 frames read in place (1 byte per frame element)" if getattr(self, "frame_dtype", "float32") == "uint8" else ""))
 
     # -- launches --------------------------------------------------------------------------------------
     def _stream(self):
@@ -629,6 +640,10 @@ class LineEndPipeline(object):
 
     def run_pyramid(self, frames, stream=None):
         self._check_frames(frames)
+        if self.mode == "rgb" and self.frame_dtype == "uint8":     # (rgb_frame_dtype="uint8")
+            self.ctx.check(self._lib.silent_pyramid_rgb8_dev(self.ctx.handle, self.plan.handle, _lib.byte_ptr(frames.data_ptr()),
+                                                             self.batch, C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
+            return
         if self.frame_dtype == "uint16":
             name, frame_ptr, _, _ = _lib.gray_entry("pyramid", "uint16", frame_layout=self.frame_layout)
             self.ctx.check(getattr(self._lib, "silent_" + name + "_dev")(self.ctx.handle, self.plan.handle, self._frames_arg(frame_ptr, frames),
@@ -805,7 +820,8 @@ class LineEndPipeline(object):
         a quarter of the PCIe bytes) and step().  Returns at once; two batches are in flight (ring of two slots), so the copy of
         batch n + 1 overlaps the compute of batch n.  Results are bit-identical to step() on the same frames resident as float32.
         A frame_dtype="uint8" pipeline takes uint8 host frames only: staging -> copy into the slot's uint8 device buffer -> step();
-        no cast launch and no float32 frame buffer.  A frame_dtype="uint16" pipeline likewise takes uint16 host frames only."""
+        no cast launch and no float32 frame buffer.  A frame_dtype="uint16" pipeline likewise takes uint16 host frames only, and a
+        mode "rgb" pipeline with rgb_frame_dtype="uint8" uint8 host frames [batch, H, W, 3] only."""
         torch = self.torch
         if isinstance(frames, np.ndarray):
             src = torch.from_numpy(np.ascontiguousarray(frames))
