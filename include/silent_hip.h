@@ -302,6 +302,28 @@ int silent_gray_pass_view_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, 
                               const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, void* cs_out,
                               void* end_out, int maps_f16, unsigned parts, silent_stream stream);
 
+/* Strided uint8 COLOUR views for 3-CHANNEL plans, read in place: the twins of silent_pyramid_rgb8[_dev] on a silent_frame_view -- the
+ * first three bytes of BGRA / BGRX / RGBA pixels, a pitched BGR surface, a region of larger frames, every second pixel.  The struct is
+ * taken as it is; channels must be 3.  Pixel (f, y, x) is the three bytes at data + f * frame_stride + y * row_stride + x * pixel_stride
+ * (+0, +1, +2; 64-bit arithmetic), and they enter as the three channels of the plan, each as (float)byte -- an unsigned load and an
+ * exact conversion; they are NOT reduced to a value (that is channels = 3 of silent_pyramid_view, for single-channel plans).  Stride
+ * bounds and span are those of the struct above.  pyr is IDENTICAL, bit for bit, to silent_pyramid_rgb8[_dev] on the compacted copy
+ * of the same pixels -- so to silent_pyramid[_dev] on the widened frames -- on every route: the walk kernel, union plans with their
+ * border blocks inside the walk launch or behind it, per-level plans, the unit + region kernels, every SILENT_TUNE_PYRAMID value.
+ * Reads: only bytes of [data, data + span).  UNLIKE the single-channel view entry points, a byte inside the span that is not a pixel
+ * byte (the X of BGRX, row padding) MAY be loaded and dropped; it never influences a result.  The byte behind the last pixel of the
+ * batch lies outside the span and is never loaded.  (As built, every load is a single channel byte of a pixel of the view, at any
+ * stride and alignment; the wider licence is for a loader that fetches a 4-byte pixel as one dword.)
+ * A packed view -- pixel_stride == 3, row_stride == 3 W, frame_stride == H * row_stride (or n_frames == 1) -- runs the packed uint8
+ * kernels.  Refusals, in this order: a NULL ctx; SILENT_E_INVALID for a NULL plan / view / data, channels != 3, a stride below its
+ * bound, a span above 2^63 - 1 bytes; then those of silent_pyramid_rgb8 (a NULL pyr, a plan of another context, n_frames < 1:
+ * SILENT_E_INVALID; a single-channel plan: SILENT_E_UNSUPPORTED -- such a plan takes a view through silent_pyramid_view).  The host
+ * form stages exactly `span` bytes and refuses everything its _dev form refuses before anything is staged; the _dev form is
+ * stream-ordered and asynchronous.  (ABI additions only: SILENT_ABI_VERSION is unchanged.) */
+int silent_pyramid_rgb8_view(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames, float* pyr);
+int silent_pyramid_rgb8_view_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+                                 float* pyr, silent_stream stream);
+
 /* uint16 frames, read as they are: 10 / 12 / 16-bit machine-vision and scientific cameras (Mono10 / Mono12 / Mono16), thermal and
  * depth sensors (Y16, Z16), 16-bit TIFF / PNG, and the luma of the P010 / P016 surfaces a hardware decoder hands over for 10-bit
  * HEVC / AV1.  The twins of the *_u8 entry points -- same argument lists, maps_f16 / parts / stream arguments, status codes and order

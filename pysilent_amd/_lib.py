@@ -130,6 +130,8 @@ _SIGNATURES = {
     "silent_pyramid_u8x3_dev": [_vp, _vp, _bp, _i, _fp, _vp],
     "silent_pyramid_rgb8": [_vp, _vp, _bp, _i, _fp],
     "silent_pyramid_rgb8_dev": [_vp, _vp, _bp, _i, _fp, _vp],
+    "silent_pyramid_rgb8_view": [_vp, _vp, _wp, _i, _fp],
+    "silent_pyramid_rgb8_view_dev": [_vp, _vp, _wp, _i, _fp, _vp],
     "silent_gray_pass_u8": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8x3": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8_dev": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i, _u, _vp],

@@ -950,6 +950,36 @@ def check_rgb_frame_dtype(rgb_frame_dtype, mode="rgb", frame_dtype="float32", fr
     return rgb_frame_dtype
 
 
+RGB_FRAME_LAYOUTS = ("packed", "strided")
+
+
+def check_rgb_frame_layout(rgb_frame_layout, mode="rgb", rgb_frame_dtype="float32", frame_dtype="float32", frame_channels=1,
+                           frame_layout="packed"):
+    """The rgb_frame_layout argument of PyramidPlan.run and LineEndPipeline: "packed" (default: nothing changes) or "strided" (mode
+    "rgb" / a 3-channel plan with rgb_frame_dtype="uint8": ANY uint8 view [n, H, W, 3] with positive strides and channel stride 1 --
+    bgra[..., :3], a pitched BGR surface, a region of larger frames -- read in place by silent_pyramid_rgb8_view: no packing launch, no
+    second copy of the batch; the pyramid is that of the packed uint8 path on view.contiguous() bit for bit).  A keyword of its own,
+    like rgb_frame_dtype: frame_layout describes the frames of mode "gray".  The name is checked first; then what "strided" needs:
+    mode "rgb", rgb_frame_dtype="uint8" and the defaults of frame_dtype, frame_channels and frame_layout."""
+    if not isinstance(rgb_frame_layout, str) or rgb_frame_layout not in RGB_FRAME_LAYOUTS:
+        raise ValueError("rgb_frame_layout must be 'packed' or 'strided', got %r" % (rgb_frame_layout,))
+    if rgb_frame_layout == "strided":
+        if mode != "rgb":
+            raise ValueError("rgb_frame_layout='strided' is for mode 'rgb' (mode 'gray' takes strided frames through frame_layout)")
+        if rgb_frame_dtype != "uint8":
+            raise ValueError("rgb_frame_layout='strided' needs rgb_frame_dtype='uint8' (float32 colour frames are read packed only)")
+        if frame_dtype != "float32":
+            raise ValueError("rgb_frame_layout='strided' does not combine with frame_dtype=%r (frame_dtype describes the frames of mode 'gray')"
+                             % (frame_dtype,))
+        if frame_channels != 1:
+            raise ValueError("rgb_frame_layout='strided' does not combine with frame_channels=%r (the frames are [n, H, W, 3] already)"
+                             % (frame_channels,))
+        if frame_layout != "packed":
+            raise ValueError("rgb_frame_layout='strided' does not combine with frame_layout=%r (frame_layout describes the frames of mode 'gray')"
+                             % (frame_layout,))
+    return rgb_frame_layout
+
+
 class PyramidPlan(object):
     """Tap tables of one (frame size, level geometry) on the device.  ``levels`` is a list of dicts / tuples
     (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w).  accumulation="float64" (single-channel plans): every op of
@@ -1002,7 +1032,18 @@ class PyramidPlan(object):
             raise ValueError("frames must be [n, %d, %d, %d], got %s" % (self.frame_shape + (tuple(frames.shape),)))
         return _Operand(frames, ctx=self.ctx, frame_dtype="uint8")
 
-    def run(self, frames, frame_dtype="float32", frame_channels=1, frame_layout="packed", rgb_frame_dtype="float32"):
+    def _frames_rgb8_view(self, frames):
+        """[n, H, W, 3] uint8 colour frames of this 3-channel plan as ANY view with positive strides and channel stride 1 (uint8
+        ndarray or uint8 GPU tensor; frame_view_of), passed as it is: a ValueError for another dtype, shape or channel stride and for
+        flipped, broadcast or overlapping views; nothing is converted or copied."""
+        if not (isinstance(frames, np.ndarray) or is_torch_tensor(frames)):
+            raise TypeError(TYPE_ERROR_MESSAGE)
+        if frames.ndim != 4 or tuple(frames.shape[1:]) != self.frame_shape:
+            raise ValueError("frames must be [n, %d, %d, %d], got %s" % (self.frame_shape + (tuple(frames.shape),)))
+        return _Operand(frames, ctx=self.ctx, frame_dtype="uint8", frame_layout="strided")
+
+    def run(self, frames, frame_dtype="float32", frame_channels=1, frame_layout="packed", rgb_frame_dtype="float32",
+            rgb_frame_layout="packed"):
         """frames: [n, H, W, C] ndarray (host) or torch GPU tensor.  Returns a PackedPyramid.  frame_dtype="uint8" (single-channel
         plans): uint8 frames read as they are (silent_pyramid_u8), the same pyramid bit for bit.  frame_channels=3 (with "uint8"):
         [n, H, W, 3] interleaved colour frames (silent_pyramid_u8x3), the pyramid of the frame of values (b0 + b1 + b2) * f32(1/3).
@@ -1010,12 +1051,16 @@ class PyramidPlan(object):
         frame_dtype="uint16": unsigned 16-bit frames read as they are (silent_pyramid_u16; strided: silent_pyramid_view16), the pyramid of
         frames.astype(float32) bit for bit.
         rgb_frame_dtype="uint8" (3-channel plans): packed uint8 colour frames [n, H, W, 3] read as they are (silent_pyramid_rgb8),
-        the 3-channel pyramid of frames.astype(float32) bit for bit."""
+        the 3-channel pyramid of frames.astype(float32) bit for bit.  rgb_frame_layout="strided" (with rgb_frame_dtype="uint8"): any
+        uint8 view [n, H, W, 3] with positive strides and channel stride 1, read in place (silent_pyramid_rgb8_view), the pyramid of the
+        packed uint8 call on the compacted view bit for bit."""
         mode = "gray" if self.frame_shape[2] == 1 else "rgb"
-        if check_rgb_frame_dtype(rgb_frame_dtype, mode, frame_dtype, frame_channels, frame_layout) == "uint8":
-            op = self._frames_rgb8(frames)
+        check_rgb_frame_dtype(rgb_frame_dtype, mode, frame_dtype, frame_channels, frame_layout)
+        strided = check_rgb_frame_layout(rgb_frame_layout, mode, rgb_frame_dtype, frame_dtype, frame_channels, frame_layout) == "strided"
+        if rgb_frame_dtype == "uint8":
+            op = self._frames_rgb8_view(frames) if strided else self._frames_rgb8(frames)
             out, optr = op.empty(op.n_frames * self.frame_px * 3)
-            op.call("pyramid_rgb8", self.handle, op.ptr, op.n_frames, optr)
+            op.call("pyramid_rgb8_view" if strided else "pyramid_rgb8", self.handle, op.ptr, op.n_frames, optr)
             return PackedPyramid(out, self.extents, 3, op.n_frames)
         op, c = self._frames(frames, frame_dtype, frame_channels, frame_layout), self.frame_shape[2]
         out, optr = op.empty(op.n_frames * self.frame_px * c)

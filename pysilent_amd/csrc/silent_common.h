@@ -226,11 +226,45 @@ __device__ __forceinline__ StridedSrc<PX> frame_of(const FrameStrided<PX>& frame
     return StridedSrc<PX>{frames.data + (long long)frame * frames.frame_stride, frames.pixel_stride, frames.row_stride};
 }
 
+// Strided interleaved uint8 colour with the THREE CHANNELS KEPT (silent_pyramid_rgb8_view, 3-channel plans only): channel c of pixel
+// (frame, y, x) is the byte at data + frame * frame_stride + y * row_stride + x * pixel_stride + c and enters as (float)byte, like a
+// byte of the packed kind `unsigned char` at C == 3.  Not FrameStrided<FrameRgb8>: that kind REDUCES the three bytes to one value for
+// a single-channel plan.  The 3-channel kernels index a frame row in floats of the interleaved row; float i of the VIRTUAL PACKED row
+// of a view is pixel i / 3, channel i % 3 -- rgb_view_col below, the one place that maps it to a byte.  Frame and row terms are
+// scalar 64-bit arithmetic as in the other strided kinds; the kernels take the struct by value (strides in SGPRs).
+struct FrameStridedRgb {
+    const unsigned char* data;
+    long long pixel_stride, row_stride, frame_stride;
+};
+template <typename FT>
+constexpr bool kFrameRgbView = std::is_same<FT, FrameStridedRgb>::value;
+// byte offset inside a row of float i of the virtual packed row
+__host__ __device__ __forceinline__ long long rgb_view_col(long long i, long long pixel_stride) {
+    const long long p = i / 3;
+    return p * pixel_stride + (i - 3 * p);
+}
+// one frame of such a batch inside a kernel
+struct StridedRgbSrc {
+    const unsigned char* p;
+    long long pixel_stride, row_stride;
+    // channel ch of pixel (x, y) / float i of the virtual packed row y
+    __device__ __forceinline__ float at(long long y, long long x, int ch) const { return (float)p[y * row_stride + x * pixel_stride + ch]; }
+    __device__ __forceinline__ float atf(long long y, long long i) const { return (float)p[y * row_stride + rgb_view_col(i, pixel_stride)]; }
+};
+template <>
+struct FrameKind<FrameStridedRgb> {
+    typedef FrameStridedRgb param;
+    typedef StridedRgbSrc src;
+};
+__device__ __forceinline__ StridedRgbSrc frame_of(const FrameStridedRgb& frames, int frame) {
+    return StridedRgbSrc{frames.data + (long long)frame * frames.frame_stride, frames.pixel_stride, frames.row_stride};
+}
+
 // the frame types that exist for single-channel plans with float32 accumulation only
 template <typename FT>
 constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT> || kFrameWords<FT> || kFrameStrided<FT>;
 template <typename FT>
-constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT>;
+constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT>;
 // (host) the bytes of one frame pixel as the host-pointer forms stage it -- float frames carry the channels of the plan; a view is
 // staged by its span -- and the suffix of a frame type's entry points
 template <typename FT>
@@ -254,6 +288,11 @@ template <typename PX>
 __device__ __forceinline__ float unit_edge_column(const StridedSrc<PX>& src, long long, int col, int src_w, int src_x0, int y_first,
                                                   int n_rows, int src_h, int src_y0, int lane, int = 1) {
     return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0);
+}
+// and of channel `ch` of a strided colour view with its three channels kept
+__device__ __forceinline__ float unit_edge_column(const StridedRgbSrc& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
+                                                  int src_h, int src_y0, int lane) {
+    return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
 }
 __device__ __forceinline__ float unit_edge(float xcol, int i) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xcol), i));

@@ -56,9 +56,10 @@ inline const silent::FrameRgb8* rgb8(const uint8_t* frames) { return reinterpret
 using View8 = silent::FrameStrided<unsigned char>;
 using View8x3 = silent::FrameStrided<silent::FrameRgb8>;
 using View16 = silent::FrameStrided<unsigned short>;   // (the *_view16 entry points, silent_frame_view16)
+using ViewRgb = silent::FrameStridedRgb;               // (silent_pyramid_rgb8_view: three channels KEPT, 3-channel plans; View8x3 reduces them)
 template <typename FT>
 inline auto kernel_frames(const FT* frames) {
-    if constexpr (silent::kFrameStrided<FT>) return *frames;
+    if constexpr (silent::kFrameStrided<FT> || silent::kFrameRgbView<FT>) return *frames;
     else return frames;
 }
 // what a view refuses on its own (silent_hip.h) -- NULL, channels, a stride below its bound, a span of 2^63 bytes or more -- and its
@@ -79,6 +80,22 @@ inline int check_view(silent_ctx* ctx, const char* who, const silent_pyramid_pla
     if (all > (u128)0x7fffffffffffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view spans more than 2^63 bytes");
     if (span) *span = (size_t)all;
     return SILENT_OK;
+}
+// silent_pyramid_rgb8_view: the same refusals with channels == 3 as the only channel count (the three bytes of a pixel are the three
+// channels of a 3-channel plan)
+inline int check_rgb_view(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const silent_frame_view* v, int n_frames, size_t* span) {
+    if (!plan || !v || !v->data) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (v->channels != 3) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": view channels must be 3");
+    return check_view(ctx, who, plan, v, n_frames, span);
+}
+// f(frames) with a checked colour view as the frame kind that reads it: a packed view as the packed bytes (the kernels of
+// silent_pyramid_rgb8), any other as ViewRgb
+template <class F>
+int with_rgb_view(const silent_pyramid_plan* plan, const silent_frame_view* v, int n_frames, F&& f) {
+    const long long H = plan->tab.H, W = plan->tab.W;
+    if (v->pixel_stride == 3 && v->row_stride == W * 3 && (n_frames <= 1 || v->frame_stride == H * v->row_stride)) return f(v->data);
+    const ViewRgb s{v->data, v->pixel_stride, v->row_stride, n_frames > 1 ? v->frame_stride : 0};
+    return f(&s);
 }
 // The same for a silent_frame_view16: one uint16 element per pixel (the bounds of check_view with 2 for `channels`), and 2-byte alignment
 // of every address a kernel forms -- an even data address and even strides.

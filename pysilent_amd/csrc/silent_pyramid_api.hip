@@ -656,8 +656,9 @@ static int pyramid_checks(silent_ctx* ctx, const char* who, const silent_pyramid
     return SILENT_OK;
 }
 
-// The launches of a 3-channel plan on frame kind FT -- float, or unsigned char (packed interleaved uint8 colour frames,
-// silent_pyramid_rgb8): ONE body, so both kinds take the same route on the same plan under the same PYRAMID knob bits.
+// The launches of a 3-channel plan on frame kind FT -- float, unsigned char (packed interleaved uint8 colour frames,
+// silent_pyramid_rgb8) or ViewRgb (the same bytes in a strided view, silent_pyramid_rgb8_view; `frames` points to the host struct):
+// ONE body, so every kind takes the same route on the same plan under the same PYRAMID knob bits.
 template <typename FT>
 static int launch_pyramid3(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames, float* pyr,
                            hipStream_t s, bool with_unit, bool with_region, long long b_unit, long long b_region) {
@@ -682,17 +683,17 @@ static int launch_pyramid3(silent_ctx* ctx, const char* who, const silent_pyrami
             wb.tab = tab;
             wb.bt = plan->walk_border;
         }
-#define WALK3(G_, PX_) hipLaunchKernelGGL((pyramid_walk3_kernel<G_, PX_, FT>), dim3((unsigned)wblocks), dim3(kW3Threads), 0, s, frames, pyr, w3t, wb)
+#define WALK3(G_, PX_) hipLaunchKernelGGL((pyramid_walk3_kernel<G_, PX_, FT>), dim3((unsigned)wblocks), dim3(kW3Threads), 0, s, kernel_frames(frames), pyr, w3t, wb)
 #define WALK3_PX(PX_) case PX_: if (plan->walk_G <= 4) WALK3(4, PX_); else WALK3(7, PX_); break
         switch (plan->walk_px) { WALK3_PX(36); WALK3_PX(32); WALK3_PX(28); WALK3_PX(24); default: break; }   // (walk3_plan refuses any other)
 #undef WALK3_PX
 #undef WALK3
         if (bblocks > 0 && !border_inside)
-            hipLaunchKernelGGL((pyramid_border_kernel<3, FT>), dim3((unsigned)bblocks), dim3(256), 0, s, frames, pyr, tab, plan->walk_border, n_frames);
+            hipLaunchKernelGGL((pyramid_border_kernel<3, FT>), dim3((unsigned)bblocks), dim3(256), 0, s, kernel_frames(frames), pyr, tab, plan->walk_border, n_frames);
         return SILENT_OK;
     }
-    if (b_unit) hipLaunchKernelGGL((pyramid_unit_kernel<3, false, FT>), dim3((unsigned)b_unit), dim3(256), 0, s, frames, pyr, tab);
-    if (b_region) hipLaunchKernelGGL((pyramid_region_kernel<3, false, FT>), dim3((unsigned)b_region), dim3(256), 0, s, frames, pyr, tab);
+    if (b_unit) hipLaunchKernelGGL((pyramid_unit_kernel<3, false, FT>), dim3((unsigned)b_unit), dim3(256), 0, s, kernel_frames(frames), pyr, tab);
+    if (b_region) hipLaunchKernelGGL((pyramid_region_kernel<3, false, FT>), dim3((unsigned)b_region), dim3(256), 0, s, kernel_frames(frames), pyr, tab);
     return SILENT_OK;
 }
 
@@ -899,24 +900,27 @@ SILENT_EXPORT int silent_pyramid_view16(silent_ctx* ctx, const silent_pyramid_pl
 
 // Packed interleaved uint8 colour frames for 3-channel plans (silent_hip.h): byte c of pixel (y, x) enters as (float)byte at the load,
 // so the pyramid is the float32-frame call's on the widened frames bit for bit, on the route launch_pyramid takes for float frames.
-static int pyramid_rgb8_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
-                               const float* pyr) {
-    TRY(pyramid_checks<float>(ctx, who, plan, frames != nullptr, n_frames, pyr));
+// (single: the entry point a single-channel plan is pointed to)
+static int pyramid_rgb8_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, bool has_frames, int n_frames,
+                               const float* pyr, const char* single = "silent_pyramid_u8x3") {
+    TRY(pyramid_checks<float>(ctx, who, plan, has_frames, n_frames, pyr));
     if (plan->tab.C != 3)
-        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": interleaved uint8 colour frames are for 3-channel plans (a single-channel plan takes them through silent_pyramid_u8x3)");
+        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": interleaved uint8 colour frames are for 3-channel plans (a single-channel plan takes them through " + single + ")");
     return SILENT_OK;
 }
 
-static int launch_pyramid_rgb8(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
+// FT: unsigned char, or ViewRgb (silent_pyramid_rgb8_view on a view that is not packed; checked by the caller)
+template <typename FT>
+static int launch_pyramid_rgb8(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames,
                                float* pyr, hipStream_t s) {
-    TRY(pyramid_rgb8_checks(ctx, who, plan, frames, n_frames, pyr));
+    if constexpr (!silent::kFrameRgbView<FT>) TRY(pyramid_rgb8_checks(ctx, who, plan, frames != nullptr, n_frames, pyr));
     const PyrTab& tab = plan->tab;
     const long long b_unit = (long long)tab.unit_tiles_per_frame * n_frames;
     const long long b_region = tab.n_general ? (long long)tab.regions_x * tab.regions_y * n_frames : 0;
     const long long b_zero = (long long)tab.zero_chunks_per_frame * n_frames;
     if (b_unit > 0x7fffffffll || b_region > 0x7fffffffll || b_zero > 0x7fffffffll)
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many tiles for one launch");
-    TRY(launch_pyramid3<unsigned char>(ctx, who, plan, frames, n_frames, pyr, s, true, true, b_unit, b_region));
+    TRY(launch_pyramid3<FT>(ctx, who, plan, frames, n_frames, pyr, s, true, true, b_unit, b_region));
     if (b_zero) hipLaunchKernelGGL(pyramid_zero_kernel<3>, dim3((unsigned)b_zero), dim3(256), 0, s, pyr, tab);
     return check_launch(ctx, who);
 }
@@ -933,11 +937,46 @@ SILENT_EXPORT int silent_pyramid_rgb8(silent_ctx* ctx, const silent_pyramid_plan
                                       float* pyr) try {
     NEED_CTX(ctx);
     const char* who = "silent_pyramid_rgb8";
-    TRY(pyramid_rgb8_checks(ctx, who, plan, frames, n_frames, pyr));
+    TRY(pyramid_rgb8_checks(ctx, who, plan, frames != nullptr, n_frames, pyr));
     HostStage hs(ctx);
     const int x = hs.in(frames, (size_t)plan->tab.H * plan->tab.W * 3 * n_frames),
               o = hs.out(pyr, (size_t)plan->tab.frame_px_out * 3 * 4 * n_frames);
     return hs.run([&] { return launch_pyramid_rgb8(ctx, who, plan, hs.dev<uint8_t>(x), n_frames, hs.dev<float>(o), nullptr); });
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_rgb8");
+}
+
+// The same pixels in a strided view (silent_hip.h): the view's own refusals, then those of silent_pyramid_rgb8, both under this name;
+// a packed view takes the packed kernels (with_rgb_view).  The host form stages the view's span, not a byte more.
+static int pyramid_rgb8_view(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_frame_view* view, int n_frames, float* pyr,
+                             silent_stream stream) {
+    const char* who = "silent_pyramid_rgb8_view";
+    size_t span = 0;
+    TRY(check_rgb_view(ctx, who, plan, view, n_frames, &span));
+    TRY(pyramid_rgb8_checks(ctx, who, plan, true, n_frames, pyr, "silent_pyramid_view"));
+    if (!host)
+        return with_rgb_view(plan, view, n_frames, [&](auto frames) { return launch_pyramid_rgb8(ctx, who, plan, frames, n_frames, pyr, (hipStream_t)stream); });
+    HostStage hs(ctx);
+    const int x = hs.in(view->data, span), o = hs.out(pyr, (size_t)plan->tab.frame_px_out * 3 * 4 * n_frames);
+    return hs.run([&] {
+        silent_frame_view staged = *view;
+        staged.data = hs.dev<uint8_t>(x);
+        return with_rgb_view(plan, &staged, n_frames, [&](auto frames) { return launch_pyramid_rgb8(ctx, who, plan, frames, n_frames, hs.dev<float>(o), nullptr); });
+    });
+}
+
+SILENT_EXPORT int silent_pyramid_rgb8_view_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+                                               float* pyr, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return pyramid_rgb8_view(ctx, false, plan, frames, n_frames, pyr, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_rgb8_view_dev");
+}
+
+SILENT_EXPORT int silent_pyramid_rgb8_view(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
+                                           float* pyr) try {
+    NEED_CTX(ctx);
+    return pyramid_rgb8_view(ctx, true, plan, frames, n_frames, pyr, nullptr);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_rgb8_view");
 }

@@ -127,14 +127,75 @@ struct WalkBorderArgs {
 // of 4 dwords.  meta: bit 0 "an output row of this level completes with this source row", bits 8.. that output row.
 __host__ __device__ constexpr int w3_prog_row(int gp) { return (gp * 7 + 3) / 4 * 4; }
 
+// ---- the loader's addresses on a strided colour view (FrameStridedRgb, silent_pyramid_rgb8_view).  Host-callable: the kernel forms
+// every address of its view loader through these functions, and tests/rgb8_view_host_main.cpp enumerates the same functions over every
+// block, chunk, row, lane and load slot of a plan (inside the span, pixel bytes covered) without a GPU.
+__host__ __device__ __forceinline__ int w3_mirror_near(int i, int n) {   // mirror_near (silent_common.h), host-callable
+    i = i < 0 ? -i : i;
+    i = i >= n ? 2 * (n - 1) - i : i;
+    return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
+}
+struct W3ViewBlock {
+    int frame, plan;
+    int y_first;                         // crop row of the block's stream row 0 (seg_y0 - 4; mirrored into the crop by w3_view_row)
+    int A;                               // float of the virtual packed FRAME row that ring float 0 holds
+    int n_chunks;
+};
+__host__ __device__ __forceinline__ W3ViewBlock w3_view_block(const Walk3Args& args, int px, unsigned bid) {
+    W3ViewBlock b;
+    b.frame = (int)(bid / (unsigned)args.blocks_per_frame);
+    int rest = (int)(bid - (unsigned)b.frame * (unsigned)args.blocks_per_frame);
+    b.plan = 0;
+    for (int i = 1; i < kW3MaxPlans; ++i)
+        if (i < args.n_plans && rest >= args.plan[i].block0) b.plan = i;
+    const Walk3Plan& p = args.plan[b.plan];
+    rest -= p.block0;
+    const int strip = rest % p.strips_x, seg = rest / p.strips_x;
+    const int seg_h = p.seg_rows < p.out_h - seg * p.seg_rows ? p.seg_rows : p.out_h - seg * p.seg_rows;
+    b.y_first = seg * p.seg_rows - 4;
+    b.A = (p.src_x0 + strip * (kW3NC * px) - kW3HaloL) * 3 - p.shift;
+    b.n_chunks = (seg_h + 8 + kW3CH - 1) / kW3CH;
+    return b;
+}
+// load slot k of a lane fills ring float 64 k + lane <-> float A + 64 k + lane of the virtual packed frame row, clamped into the row
+// (what lies outside the crop is never consumed): its byte offset inside a row of the view.  Per block, not per chunk.
+__host__ __device__ __forceinline__ long long w3_view_col(const Walk3Args& args, long long pixel_stride, int A, int lane, int k) {
+    int f = A + lane + 64 * k;
+    f = f < 0 ? 0 : (f > args.W * 3 - 1 ? args.W * 3 - 1 : f);
+    return rgb_view_col(f, pixel_stride);
+}
+// stream row s of a block: byte offset of its frame row from `data` (scalar 64-bit arithmetic in the kernel)
+__host__ __device__ __forceinline__ long long w3_view_row(const Walk3Args& args, const FrameStridedRgb& v, const W3ViewBlock& b, int s) {
+    const Walk3Plan& p = args.plan[b.plan];
+    return (long long)b.frame * v.frame_stride + (long long)(w3_mirror_near(b.y_first + s, p.src_h) + p.src_y0) * v.row_stride;
+}
+// THE address function: the load of (block, chunk, row of the chunk, lane, load slot) -- byte offset from `data` and width in bytes.
+// (The general loader loads single bytes: width 1 at any stride and alignment.)
+struct W3ViewLoad {
+    long long offset;
+    int width;
+};
+__host__ __device__ __forceinline__ W3ViewLoad w3_view_load(const Walk3Args& args, const FrameStridedRgb& v, int px, unsigned bid, int chunk,
+                                                            int row, int lane, int k) {
+    const W3ViewBlock b = w3_view_block(args, px, bid);
+    return W3ViewLoad{w3_view_row(args, v, b, chunk * kW3CH + row) + w3_view_col(args, v.pixel_stride, b.A, lane, k), 1};
+}
+__host__ __device__ constexpr int w3_view_row_loads(int px) { return (w3_row_f(px) + 63) / 64; }   // load slots per ring row
+
 // FT: the frame element type -- float, or unsigned char (packed interleaved uint8 colour frames [n, H, W, 3], silent_pyramid_rgb8: byte c
 // of pixel (y, x) enters as (float)byte, an unsigned load and an exact conversion).  Only the LOADER touches the frame: the ring stays
 // float32 and the consumers' text is the same for both kinds, so the uint8 kernel stores the bits the float kernel stores for the
 // widened frame.  The FT = float instantiations are the code as it was (their machine code is unchanged).
+// FT = FrameStridedRgb (the same bytes in a strided view, by value): the packed kind's ONE-BYTE loader -- ring float r of a row is the
+// byte of float A + r of the virtual packed frame row, (f / 3) * pixel_stride + f % 3 (w3_view_col, once per block) behind the row's
+// scalar 64-bit offset (w3_view_row); the ring, the shift, the mirror fix-up and the consumers do not know about strides.  All byte
+// loads of a chunk are issued before one is consumed; the chunk is complete (vmcnt(0) lgkmcnt(0)) before the barrier.  Every address
+// is that of a channel byte of a pixel of the view: nothing outside [data, data + span) is loaded.
 template <int G, int PX, typename FT = float>
-__global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const FT* __restrict__ frames, float* __restrict__ pyr,
+__global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<FT> frames, float* __restrict__ pyr,
                                                                     const Walk3Args args, const WalkBorderArgs border) {
-    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT>, "float32 or packed uint8 colour frames");
+    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT>, "float32, packed uint8 or strided uint8 colour frames");
+    constexpr bool kBytes = kFrameBytes<FT> || kFrameRgbView<FT>;   // the loader widens bytes in registers
     static_assert(G == stream_pad_levels(G), "row programs are padded to 4 or 7 levels");
     static_assert(PX == 36 || PX == 32 || PX == 28 || PX == 24, "");
     constexpr int kW3Px = PX, kW3StripPx = kW3NC * PX, kW3RowF = w3_row_f(PX);
@@ -175,7 +236,10 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const FT* __r
 
     if (wave == kW3NC) {
         // ------------------------------------------------------------------ loader: LDS-DMA only
-        const FT* __restrict__ src = frames + (long long)frame * args.H * args.W * 3;
+        typedef typename std::conditional<kFrameRgbView<FT>, unsigned char, FT>::type ET;   // element of a frame row
+        const ET* __restrict__ src;
+        if constexpr (kFrameRgbView<FT>) src = frames.data;    // (rows: w3_view_row)
+        else src = frames + (long long)frame * args.H * args.W * 3;
         const int rowf = args.W * 3;                           // floats (uint8 frames: bytes) of a FRAME row
         // ring float r <-> frame-row float A + r, A = the crop's pixel R0 minus the alignment shift.  Frame widths that are a
         // multiple of 4 (every row starts on 16 bytes): A is a multiple of 4 and a lane fetches a 16-byte aligned group of 4 floats,
@@ -187,24 +251,35 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const FT* __r
         auto loader = [&](auto dword_dma) {
             constexpr bool DWORD_DMA = decltype(dword_dma)::value;
             constexpr int kRowLoads = DWORD_DMA ? (kW3RowF + 63) / 64 : 2;   // DMA instructions per ring row
-            int f[kRowLoads];
+            typename std::conditional<kFrameRgbView<FT>, long long, int>::type f[kRowLoads];
+            W3ViewBlock vb;
+            (void)vb;
+            if constexpr (kFrameRgbView<FT>) {
+                static_assert(kRowLoads == w3_view_row_loads(PX), "");
+                vb = w3_view_block(args, PX, bid);
+#pragma unroll
+                for (int k = 0; k < kRowLoads; ++k) f[k] = w3_view_col(args, frames.pixel_stride, vb.A, lane, k);
+            } else {
 #pragma unroll
             for (int k = 0; k < kRowLoads; ++k)
                 f[k] = DWORD_DMA ? min(max(A + lane + 64 * k, 0), rowf - 1) : min(max(A + 256 * k + lane * 4, 0), rowf - 4);
+            }
             auto issue = [&](int c, int slot) {
                 // uint8 frames: the same lane -> ring mapping with the frame row counted in BYTES -- a lane's group of 4 ring floats is
                 // one dword of the frame row (4 bytes, widened in registers, one 16-byte LDS write), its single float one byte.  All
                 // loads of the chunk are issued first (8 or 32 in flight: one memory latency per chunk, not one per load), then the
                 // records' DMA, then the rows are widened and written; the chunk is complete -- vmcnt(0), lgkmcnt(0) -- before the loader
                 // goes on to its next barrier, still two chunks ahead of the consumers, who take ~2000 cycles a row
-                typename std::conditional<DWORD_DMA, unsigned char, unsigned>::type v[kFrameBytes<FT> ? kW3CH : 1][kRowLoads];
+                typename std::conditional<DWORD_DMA, unsigned char, unsigned>::type v[kBytes ? kW3CH : 1][kRowLoads];
                 (void)v;
 #pragma unroll
                 for (int r = 0; r < kW3CH; ++r) {
                     const int y = seg_y0 - 4 + c * kW3CH + r;
-                    const FT* rp = src + (long long)(mirror_near(y, tab.src_h) + tab.src_y0) * args.W * 3;
+                    const ET* rp;
+                    if constexpr (kFrameRgbView<FT>) rp = src + w3_view_row(args, frames, vb, c * kW3CH + r);
+                    else rp = src + (long long)(mirror_near(y, tab.src_h) + tab.src_y0) * args.W * 3;
                     float* dst = &s_ring[slot * kW3CH + r][0];
-                    if constexpr (kFrameBytes<FT>) {
+                    if constexpr (kBytes) {
                         (void)dst;
 #pragma unroll
                         for (int k = 0; k < kRowLoads; ++k) {
@@ -229,7 +304,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const FT* __r
                 if constexpr (NV > 64) {
                     if (lane < NV - 64) __builtin_amdgcn_global_load_lds((walk_glb_ptr)(rp + 256), (walk_lds_ptr)(dst + 256), 16, 0, 0);
                 }
-                if constexpr (kFrameBytes<FT>) {
+                if constexpr (kBytes) {
 #pragma unroll
                     for (int r = 0; r < kW3CH; ++r) {
                         float* row = &s_ring[slot * kW3CH + r][0];
@@ -272,7 +347,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const FT* __r
                 // chunk c has landed when at most the next chunk's loads (three slots: one chunk in flight behind it) are outstanding
                 // (uint8 frames: nothing is outstanding here, issue() ends with vmcnt(0) -- the counted wait would name a mix of register
                 // loads and DMA loads that the compiler is free to reorder)
-                if (!kFrameBytes<FT> && kWalkSlots == 3 && c + 1 < n_chunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kRowLoads * kW3CH + (kW3CH * PR / 4 > 64 ? 2 : 1)) : "memory");
+                if (!kBytes && kWalkSlots == 3 && c + 1 < n_chunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kRowLoads * kW3CH + (kW3CH * PR / 4 > 64 ? 2 : 1)) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (any_fix) {
 #pragma unroll
@@ -293,7 +368,8 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(const FT* __r
         // takes the one-byte path, which never touches a byte outside the batch)
         bool single = (rowf & 3) != 0;                          // block-uniform
         if constexpr (kFrameBytes<FT>) single = single || (reinterpret_cast<unsigned long long>(frames) & 3ull) != 0;
-        if (single) loader(std::true_type{});
+        if constexpr (kFrameRgbView<FT>) loader(std::true_type{});   // a view: always the one-byte path (any strides, any alignment)
+        else if (single) loader(std::true_type{});
         else loader(std::false_type{});
         return;
     }

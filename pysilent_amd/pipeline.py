@@ -132,7 +132,7 @@ class LineEndPipeline(object):
                  max_keypoints_per_frame=None, selection=False, top_percent=0.1, keep_selection_maps=False, value_map=None,
                  peak_value_map=None, orient_map=True, overlap=False, overlap_priorities=True, placement="auto", keypoints=False,
                  regions=None, accumulation="float32", storage="float32", frame_dtype="float32", frame_channels=1,
-                 frame_layout="packed", rgb_frame_dtype="float32"):
+                 frame_layout="packed", rgb_frame_dtype="float32", rgb_frame_layout="packed"):
         # rgb_frame_dtype="uint8" (mode "rgb"): step() takes packed interleaved uint8 colour frames [batch, H, W, 3] as a camera or a
         # decoder delivers them and the pyramid kernels read the bytes themselves (silent_pyramid_rgb8_dev) -- no widening cast, no
         # float32 copy of the batch; the pyramid, and with it every map and keypoint, is bit-identical to the float32 pipeline's on
@@ -140,6 +140,14 @@ class LineEndPipeline(object):
         # keep their refusals on mode "rgb".  Checked first, before any GPU or torch work: unknown names, mode "gray", and "uint8"
         # beside a non-default frame_dtype / frame_channels / frame_layout
         self.rgb_frame_dtype = _runtime.check_rgb_frame_dtype(rgb_frame_dtype, mode, frame_dtype, frame_channels, frame_layout)
+        # rgb_frame_layout="strided" (mode "rgb", rgb_frame_dtype="uint8"): step() takes ANY uint8 GPU view [batch, H, W, 3] with
+        # positive strides and channel stride 1 -- bgra[..., :3], a pitched BGR surface, a region of larger frames -- and the pyramid
+        # kernels read it in place (silent_pyramid_rgb8_view_dev): no packing launch, no second copy of the batch; pyramid, maps and
+        # keypoints are those of the packed uint8 pipeline on view.contiguous(), bit for bit.  step_host is unchanged (its staging
+        # copy packs).  A keyword of its own like rgb_frame_dtype; refused here: unknown names, mode "gray", rgb_frame_dtype="float32",
+        # a non-default frame_dtype / frame_channels / frame_layout
+        self.rgb_frame_layout = _runtime.check_rgb_frame_layout(rgb_frame_layout, mode, rgb_frame_dtype, frame_dtype, frame_channels,
+                                                                frame_layout)
         # accumulation="float64" (mode "gray"): every op sums its taps in float64 and rounds once to float32, like the CPU oracle
         # (SILENT_PLAN_ACCUM_F64: the pyramid within 1 ulp of it, CS and end bit-identical to it on the same pyramid).  Checked first:
         # no GPU or torch work for a refused argument
@@ -560,7 +568,8 @@ class LineEndPipeline(object):
         frame read is the largest crop any level resamples (the part of the frame the pyramid depends on).  storage="float16":
         the returned CS and end maps count 2 bytes per element.  frame_dtype="uint8": the frame read counts 1 byte per frame element
         ("uint16": 2 bytes) -- frame_shape[2] of them per pixel (3 for interleaved colour frames, whose pyramid and maps stay single-channel;
-        mode "rgb" with rgb_frame_dtype="uint8" reports frame_dtype "uint8" and counts the same 1 byte per frame element)."""
+        mode "rgb" with rgb_frame_dtype="uint8" reports frame_dtype "uint8" and counts the same 1 byte per frame element; a strided
+        view, frame_layout / rgb_frame_layout "strided", is read in place and counts the pixel bytes alone, not the bytes between them)."""
         h, w, fc = self.frame_shape
         c = self.channels
         if self.crop_px is not None:
@@ -613,13 +622,19 @@ class LineEndPipeline(object):
                     + (", read in place from a strided view" if getattr(self, "frame_layout", "packed") == "strided" else ""))
         return ("single-read RGB pyramid (pyramid_walk3_kernel), fused RGB chain, max/min + fused selection "
                 "(top 10 % > NMS > value), cell-max / count / scan / write keypoint kernels"
-                + (", uint8 frames read in place (1 byte per frame element)" if getattr(self, "frame_dtype", "float32") == "uint8" else ""))
+                + (", uint8 frames read in place (1 byte per frame element)" if getattr(self, "frame_dtype", "float32") == "uint8" else "")
+                + (", read in place from a strided view" if getattr(self, "rgb_frame_layout", "packed") == "strided" else ""))
 
     # -- launches --------------------------------------------------------------------------------------
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.tdev).cuda_stream)
 
     def _check_frames(self, frames):
+        if getattr(self, "rgb_frame_layout", "packed") == "strided":
+            shape = (self.batch,) + self.frame_shape
+            if not _runtime.is_torch_tensor(frames) or tuple(frames.shape) != shape or frames.dtype != self.torch.uint8 or not frames.is_cuda:
+                raise ValueError("frames must be a uint8 GPU tensor (any view with positive strides and channel stride 1) of shape %s" % (shape,))
+            return
         if self.frame_layout == "strided":
             shapes = ((self.batch,) + self.frame_shape,) + (((self.batch,) + self.frame_shape[:2],) if self.frame_shape[2] == 1 else ())
             if not _runtime.is_torch_tensor(frames) or tuple(frames.shape) not in shapes or frames.dtype != self._frame_torch_dtype \
@@ -640,6 +655,11 @@ class LineEndPipeline(object):
 
     def run_pyramid(self, frames, stream=None):
         self._check_frames(frames)
+        if getattr(self, "rgb_frame_layout", "packed") == "strided":   # (mode "rgb", rgb_frame_dtype="uint8")
+            self.ctx.check(self._lib.silent_pyramid_rgb8_view_dev(self.ctx.handle, self.plan.handle,
+                                                                  _lib.view_ptr(_runtime.frame_view_of(frames, 3, "uint8")), self.batch,
+                                                                  C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
+            return
         if self.mode == "rgb" and self.frame_dtype == "uint8":     # (rgb_frame_dtype="uint8")
             self.ctx.check(self._lib.silent_pyramid_rgb8_dev(self.ctx.handle, self.plan.handle, _lib.byte_ptr(frames.data_ptr()),
                                                              self.batch, C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
