@@ -324,6 +324,42 @@ int silent_pyramid_rgb8_view(silent_ctx* ctx, const silent_pyramid_plan* plan, c
 int silent_pyramid_rgb8_view_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
                                  float* pyr, silent_stream stream);
 
+/* NV12 decoder surfaces for 3-CHANNEL plans, read in place: a full-resolution luma plane `y` and a half-resolution plane `uv` of
+ * interleaved (U, V) byte pairs, both pitched, as a hardware video decoder emits them.  Strides are in bytes, 64-bit.  For pixel (y, x)
+ * of frame f, with H x W the frame extents of the plan, the value of channel k in {0, 1, 2} is
+ *     Yv = (float)y [f * y_frame_stride  + y * y_row_stride + x] - oy
+ *     Uv = (float)uv[f * uv_frame_stride + (y >> 1) * uv_row_stride + 2 * (x >> 1)    ] - 128
+ *     Vv = (float)uv[f * uv_frame_stride + (y >> 1) * uv_row_stride + 2 * (x >> 1) + 1] - 128
+ *     c_k = min(max((Yv * m[3 k] + Uv * m[3 k + 1]) + Vv * m[3 k + 2], 0), 255)
+ * with every product and every sum a SEPARATELY ROUNDED float32 operation (no fused multiply-add), chroma NEAREST (a 2 x 2 luma block
+ * shares one pair) and NO rounding to an integer: the float32 value enters the pyramid.  Row k of m is channel k, so channel order
+ * (BGR / RGB), BT.601 / BT.709 and limited / full range are the caller's choice of m and oy.  The conversion happens in registers at
+ * the kernels' loads: no conversion launch, no copy of the batch.  pyr is IDENTICAL, bit for bit, to silent_pyramid[_dev] on the frames
+ * silent_nv12_to_rgb[_dev] writes for the same struct, on every route: the walk kernel, union plans with their border blocks, per-level
+ * plans, the unit + region kernels, every SILENT_TUNE_PYRAMID value.  Reads: only bytes of [y, y + y_span) and [uv, uv + uv_span),
+ * y_span = (n - 1) y_frame_stride + (H - 1) y_row_stride + W, uv_span = (n - 1) uv_frame_stride + (H / 2 - 1) uv_row_stride + W; every
+ * load is a luma byte or the pair of a pixel, at any alignment.  A frame stride is not read when n_frames == 1.
+ * Refusals, in this order: a NULL ctx; SILENT_E_INVALID for a NULL plan / struct / y / uv, an odd H or W of the plan (4:2:0), a row
+ * stride below W, a frame stride below its plane's extent (n_frames > 1), a span above 2^63 - 1 bytes, a non-finite m or oy; then a
+ * NULL pyr / rgb, a plan of another context, n_frames < 1 (SILENT_E_INVALID) and a single-channel plan (SILENT_E_UNSUPPORTED: such a
+ * plan reads the luma plane through silent_pyramid_view).  The host forms stage exactly the two spans and refuse everything their _dev
+ * forms refuse before anything is staged; the _dev forms are stream-ordered and asynchronous; the struct is dead at return.
+ * silent_nv12_to_rgb[_dev] writes the converted frames themselves, [n_frames, H, W, 3] float32 -- the frames the pyramid kernels see --
+ * with the same device function, one thread per pixel; H and W are arguments (both even, >= 2), refusals as above under its own name.
+ * (ABI additions only: SILENT_ABI_VERSION is unchanged.) */
+typedef struct silent_nv12_frames {
+    const uint8_t* y;
+    const uint8_t* uv;
+    int64_t y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride;
+    float m[9];
+    float oy;
+} silent_nv12_frames;
+int silent_pyramid_nv12(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_nv12_frames* frames, int n_frames, float* pyr);
+int silent_pyramid_nv12_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_nv12_frames* frames, int n_frames, float* pyr,
+                            silent_stream stream);
+int silent_nv12_to_rgb(silent_ctx* ctx, const silent_nv12_frames* frames, int n_frames, int H, int W, float* rgb);
+int silent_nv12_to_rgb_dev(silent_ctx* ctx, const silent_nv12_frames* frames, int n_frames, int H, int W, float* rgb, silent_stream stream);
+
 /* uint16 frames, read as they are: 10 / 12 / 16-bit machine-vision and scientific cameras (Mono10 / Mono12 / Mono16), thermal and
  * depth sensors (Y16, Z16), 16-bit TIFF / PNG, and the luma of the P010 / P016 surfaces a hardware decoder hands over for 10-bit
  * HEVC / AV1.  The twins of the *_u8 entry points -- same argument lists, maps_f16 / parts / stream arguments, status codes and order

@@ -78,6 +78,13 @@ class FrameView16(C.Structure):
     _fields_ = [("data", C.c_void_p), ("pixel_stride", C.c_int64), ("row_stride", C.c_int64), ("frame_stride", C.c_int64)]
 
 
+class Nv12Frames(C.Structure):
+    """silent_nv12_frames (include/silent_hip.h): an NV12 batch -- luma plane, interleaved (U, V) plane, four BYTE strides, the 3 x 3
+    conversion matrix (row k: output channel k) and the luma offset."""
+    _fields_ = [("y", C.c_void_p), ("uv", C.c_void_p), ("y_row_stride", C.c_int64), ("y_frame_stride", C.c_int64),
+                ("uv_row_stride", C.c_int64), ("uv_frame_stride", C.c_int64), ("m", C.c_float * 9), ("oy", C.c_float)]
+
+
 class SilentLibraryError(RuntimeError):
     """libsilent_hip.so is missing or cannot be loaded."""
 
@@ -91,6 +98,7 @@ _bp = C.POINTER(C.c_uint8)    # uint8 frames (the *_u8, *_u8x3 and *_rgb8 entry 
 _wp = C.POINTER(FrameView)    # a strided uint8 view (the *_view entry points); view_ptr() makes one from _runtime.frame_view_of's tuple
 _sp = C.POINTER(C.c_uint16)   # uint16 frames (the *_u16 entry points); short_ptr() makes one from an address
 _xp = C.POINTER(FrameView16)  # a strided uint16 view (the *_view16 entry points); view16_ptr() makes one from frame_view_of's tuple
+_np = C.POINTER(Nv12Frames)   # an NV12 batch (silent_pyramid_nv12, silent_nv12_to_rgb); nv12_ptr() makes one from _runtime.nv12_frames_of's tuple
 _ep = C.POINTER(Extent)
 _i, _u, _f, _d, _sz = C.c_int, C.c_uint, C.c_float, C.c_double, C.c_size_t
 
@@ -132,6 +140,10 @@ _SIGNATURES = {
     "silent_pyramid_rgb8_dev": [_vp, _vp, _bp, _i, _fp, _vp],
     "silent_pyramid_rgb8_view": [_vp, _vp, _wp, _i, _fp],
     "silent_pyramid_rgb8_view_dev": [_vp, _vp, _wp, _i, _fp, _vp],
+    "silent_pyramid_nv12": [_vp, _vp, _np, _i, _fp],
+    "silent_pyramid_nv12_dev": [_vp, _vp, _np, _i, _fp, _vp],
+    "silent_nv12_to_rgb": [_vp, _np, _i, _i, _i, _fp],
+    "silent_nv12_to_rgb_dev": [_vp, _np, _i, _i, _i, _fp, _vp],
     "silent_gray_pass_u8": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8x3": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8_dev": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i, _u, _vp],
@@ -252,6 +264,16 @@ def view16_ptr(view):
         return None
     address, _channels, pixel_stride, row_stride, frame_stride = view
     return C.pointer(FrameView16(int(address), int(pixel_stride), int(row_stride), int(frame_stride)))
+
+
+def nv12_ptr(frames):
+    """(y address, uv address, y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride, m, oy) -- what _runtime.nv12_frames_of
+    returns; m: 9 floats, row k the output channel k -- as the const silent_nv12_frames* of the NV12 entry points (None: NULL).  The
+    struct is read before the call returns."""
+    if frames is None:
+        return None
+    y, uv, yr, yf, ur, uf, m, oy = frames
+    return C.pointer(Nv12Frames(int(y), int(uv), int(yr), int(yf), int(ur), int(uf), (C.c_float * 9)(*[float(v) for v in m]), float(oy)))
 
 
 def gray_entry(family, frame_dtype="float32", frame_channels=1, storage="float32", dev=False, parts=None, frame_layout="packed"):

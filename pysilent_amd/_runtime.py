@@ -980,6 +980,143 @@ def check_rgb_frame_layout(rgb_frame_layout, mode="rgb", rgb_frame_dtype="float3
     return rgb_frame_layout
 
 
+RGB_FRAME_FORMATS = ("interleaved", "nv12")
+NV12_MATRICES = {"bt601": (.299, .114), "bt709": (.2126, .0722)}      # (Kr, Kb)
+NV12_RANGES = ("limited", "full")
+NV12_ORDERS = ("bgr", "rgb")
+
+
+def check_rgb_frame_format(rgb_frame_format, mode="rgb", rgb_frame_dtype="float32", rgb_frame_layout="packed", frame_dtype="float32",
+                           frame_channels=1, frame_layout="packed", hw=None):
+    """The rgb_frame_format argument of PyramidPlan.run and LineEndPipeline: "interleaved" (default: nothing changes) or "nv12" (mode
+    "rgb" / a 3-channel plan: the frames are a pair (y, uv) of uint8 planes as a hardware video decoder emits them -- luma [n, H, W],
+    interleaved chroma [n, H / 2, W / 2, 2], both pitched -- read in place by silent_pyramid_nv12 and converted to three float32
+    channels in registers: no conversion launch, no copy of the batch; the pyramid is that of the float32 path on the converted
+    frames bit for bit).  The name is checked first; then the mode; then that "nv12" is not combined with rgb_frame_dtype="uint8",
+    rgb_frame_layout="strided" or the gray frame_* keywords; then that H and W (hw, when given) are even."""
+    if not isinstance(rgb_frame_format, str) or rgb_frame_format not in RGB_FRAME_FORMATS:
+        raise ValueError("rgb_frame_format must be 'interleaved' or 'nv12', got %r" % (rgb_frame_format,))
+    if rgb_frame_format == "nv12":
+        if mode != "rgb":
+            raise ValueError("rgb_frame_format='nv12' is for mode 'rgb' (mode 'gray' reads the luma plane through frame_layout='strided')")
+        if rgb_frame_dtype != "float32":
+            raise ValueError("rgb_frame_format='nv12' does not combine with rgb_frame_dtype=%r (the planes are uint8; the converted "
+                             "channels are float32)" % (rgb_frame_dtype,))
+        if rgb_frame_layout != "packed":
+            raise ValueError("rgb_frame_format='nv12' does not combine with rgb_frame_layout=%r (the planes carry their own pitches)"
+                             % (rgb_frame_layout,))
+        if frame_dtype != "float32":
+            raise ValueError("rgb_frame_format='nv12' does not combine with frame_dtype=%r (frame_dtype describes the frames of mode 'gray')"
+                             % (frame_dtype,))
+        if frame_channels != 1:
+            raise ValueError("rgb_frame_format='nv12' does not combine with frame_channels=%r (frame_channels describes the frames of mode 'gray')"
+                             % (frame_channels,))
+        if frame_layout != "packed":
+            raise ValueError("rgb_frame_format='nv12' does not combine with frame_layout=%r (frame_layout describes the frames of mode 'gray')"
+                             % (frame_layout,))
+        if hw is not None and (int(hw[0]) % 2 or int(hw[1]) % 2 or min(int(hw[0]), int(hw[1])) < 2):
+            raise ValueError("rgb_frame_format='nv12' needs even H and W (4:2:0 chroma), got %s" % (tuple(int(v) for v in hw),))
+    return rgb_frame_format
+
+
+def nv12_coefficients(nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr"):
+    """(m, oy) of the NV12 entry points: m [3, 3] float32, row k = output channel k over (Y - oy, U - 128, V - 128), and oy float32.
+    nv12_matrix: "bt601" / "bt709" -- built in float64 from (Kr, Kb), each coefficient rounded once to float32:
+        R = ys Y' + 2 (1 - Kr) cs V',  B = ys Y' + 2 (1 - Kb) cs U',  G = ys Y' - 2 Kb (1 - Kb) / Kg cs U' - 2 Kr (1 - Kr) / Kg cs V'
+    with (ys, cs, oy) = (255 / 219, 255 / 224, 16) for nv12_range="limited" and (1, 1, 0) for "full", rows in nv12_order ("bgr" /
+    "rgb") -- or a 3 x 3 array-like taken as it is (rows = output channels; nv12_order is not applied), nv12_range giving oy."""
+    if nv12_range not in NV12_RANGES:
+        raise ValueError("nv12_range must be 'limited' or 'full', got %r" % (nv12_range,))
+    if nv12_order not in NV12_ORDERS:
+        raise ValueError("nv12_order must be 'bgr' or 'rgb', got %r" % (nv12_order,))
+    ys, cs, oy = (255.0 / 219.0, 255.0 / 224.0, 16.0) if nv12_range == "limited" else (1.0, 1.0, 0.0)
+    if isinstance(nv12_matrix, str):
+        if nv12_matrix not in NV12_MATRICES:
+            raise ValueError("nv12_matrix must be 'bt601', 'bt709' or a 3 x 3 array, got %r" % (nv12_matrix,))
+        kr, kb = NV12_MATRICES[nv12_matrix]
+        kg = 1.0 - kr - kb
+        rows = {"r": (ys, 0.0, 2.0 * (1.0 - kr) * cs),
+                "g": (ys, -2.0 * kb * (1.0 - kb) / kg * cs, -2.0 * kr * (1.0 - kr) / kg * cs),
+                "b": (ys, 2.0 * (1.0 - kb) * cs, 0.0)}
+        m = np.array([rows[c] for c in nv12_order], np.float64)
+    else:
+        try:
+            m = np.array(nv12_matrix, np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("nv12_matrix must be 'bt601', 'bt709' or a 3 x 3 array, got %r" % (nv12_matrix,))
+        if m.shape != (3, 3) or not np.all(np.isfinite(m)):
+            raise ValueError("nv12_matrix must be 'bt601', 'bt709' or a finite 3 x 3 array, got shape %s" % (m.shape,))
+    return m.astype(np.float32), np.float32(oy)
+
+
+def nv12_frames_of(planes, hw, m, oy):
+    """A pair (y, uv) of uint8 planes -- both ndarrays or both GPU tensors; y [n, H, W] with element stride 1, uv [n, H / 2, W / 2, 2]
+    with strides (.., .., 2, 1), positive row / frame strides -- as what _lib.nv12_ptr takes: (y address, uv address, y_row_stride,
+    y_frame_stride, uv_row_stride, uv_frame_stride, m, oy).  Returns (that tuple, n, on_device).  Nothing is converted or copied."""
+    if not isinstance(planes, (tuple, list)) or len(planes) != 2:
+        raise ValueError("NV12 frames are a pair (y, uv) of uint8 planes")
+    y, uv = planes
+    dev = is_torch_tensor(y)
+    if not (dev and is_torch_tensor(uv)) and not (isinstance(y, np.ndarray) and isinstance(uv, np.ndarray)):
+        raise TypeError(TYPE_ERROR_MESSAGE)
+    h, w = int(hw[0]), int(hw[1])
+
+    def geometry(p):
+        if dev:
+            import torch
+            if p.dtype != torch.uint8 or not p.is_cuda:
+                raise ValueError("NV12 planes must be uint8 GPU tensors or uint8 ndarrays (nothing is converted), got %s" % (p.dtype,))
+            return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.stride()), int(p.data_ptr())
+        if p.dtype != np.uint8:
+            raise ValueError("NV12 planes must be uint8 GPU tensors or uint8 ndarrays (nothing is converted), got %s" % (p.dtype,))
+        return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.strides), int(p.ctypes.data)
+
+    ys, yst, ya = geometry(y)
+    cs, cst, ca = geometry(uv)
+    if len(ys) != 3 or ys[1:] != (h, w) or ys[0] < 1:
+        raise ValueError("the NV12 luma plane must be [n, %d, %d], got %s" % (h, w, ys))
+    n = ys[0]
+    if cs != (n, h // 2, w // 2, 2):
+        raise ValueError("the NV12 chroma plane must be [%d, %d, %d, 2], got %s" % (n, h // 2, w // 2, cs))
+    if (w > 1 and yst[2] != 1) or cst[3] != 1 or (w > 2 and cst[2] != 2):
+        raise ValueError("NV12 planes: luma bytes of a row and the (U, V) pairs of a chroma row must be adjacent (strides %s, %s)" % (yst, cst))
+    yr, cr = (yst[1] if h > 1 else w), (cst[1] if h > 2 else w)
+    yf, cf = (yst[0] if n > 1 else (h - 1) * yr + w), (cst[0] if n > 1 else (h // 2 - 1) * cr + w)
+    if yr < w or cr < w or yf < (h - 1) * yr + w or cf < (h // 2 - 1) * cr + w:
+        raise ValueError("NV12 planes: rows or frames overlap, or a stride is not positive (strides %s, %s)" % (yst, cst))
+    return (ya, ca, yr, yf, cr, cf, [float(v) for v in np.asarray(m, np.float32).reshape(9)], float(oy)), n, dev
+
+
+class _Nv12Operand(_Operand):
+    """An NV12 batch (nv12_frames_of) as an operand: results are allocated like the planes (empty) and the entry point is called in
+    its _dev form on torch's current stream for GPU planes, in its host form otherwise (call)."""
+
+    def __init__(self, planes, hw, m, oy, ctx=None):
+        args, self.n_frames, self.dev = nv12_frames_of(planes, hw, m, oy)
+        self.packed, self.c, self.extents = False, 3, [(int(hw[0]), int(hw[1]))]
+        self.device = self.stream = None
+        if self.dev:
+            import torch
+            self._torch_device = planes[0].device
+            self.device = self._torch_device.index or 0
+            self.stream = C.c_void_p(torch.cuda.current_stream(self._torch_device).cuda_stream)
+        self.ptr = _lib.nv12_ptr(args)
+        self.buf = tuple(planes)                        # keep alive
+        self.ctx = ctx or get_context(self.device)
+
+
+def nv12_to_rgb(planes, hw, nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", device=None):
+    """The float32 frames [n, H, W, 3] the pyramid kernels see for an NV12 batch (silent_nv12_to_rgb[_dev]: the loaders' own device
+    function, one thread per pixel) -- for display, and as the reference of the bit-identity contract.  planes: nv12_frames_of."""
+    m, oy = nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
+    check_rgb_frame_format("nv12", hw=hw)
+    op = _Nv12Operand(planes, hw, m, oy, None if device is None else get_context(device))
+    h, w = int(hw[0]), int(hw[1])
+    out, optr = op.empty((op.n_frames, h, w, 3))
+    op.call("nv12_to_rgb", op.ptr, op.n_frames, h, w, optr)
+    return out
+
+
 class PyramidPlan(object):
     """Tap tables of one (frame size, level geometry) on the device.  ``levels`` is a list of dicts / tuples
     (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w).  accumulation="float64" (single-channel plans): every op of
@@ -1043,7 +1180,7 @@ class PyramidPlan(object):
         return _Operand(frames, ctx=self.ctx, frame_dtype="uint8", frame_layout="strided")
 
     def run(self, frames, frame_dtype="float32", frame_channels=1, frame_layout="packed", rgb_frame_dtype="float32",
-            rgb_frame_layout="packed"):
+            rgb_frame_layout="packed", rgb_frame_format="interleaved", nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr"):
         """frames: [n, H, W, C] ndarray (host) or torch GPU tensor.  Returns a PackedPyramid.  frame_dtype="uint8" (single-channel
         plans): uint8 frames read as they are (silent_pyramid_u8), the same pyramid bit for bit.  frame_channels=3 (with "uint8"):
         [n, H, W, 3] interleaved colour frames (silent_pyramid_u8x3), the pyramid of the frame of values (b0 + b1 + b2) * f32(1/3).
@@ -1053,8 +1190,17 @@ class PyramidPlan(object):
         rgb_frame_dtype="uint8" (3-channel plans): packed uint8 colour frames [n, H, W, 3] read as they are (silent_pyramid_rgb8),
         the 3-channel pyramid of frames.astype(float32) bit for bit.  rgb_frame_layout="strided" (with rgb_frame_dtype="uint8"): any
         uint8 view [n, H, W, 3] with positive strides and channel stride 1, read in place (silent_pyramid_rgb8_view), the pyramid of the
-        packed uint8 call on the compacted view bit for bit."""
+        packed uint8 call on the compacted view bit for bit.  rgb_frame_format="nv12" (3-channel plans): frames is a pair (y, uv) of
+        uint8 planes (nv12_frames_of) read in place and converted in registers (silent_pyramid_nv12; nv12_coefficients), the pyramid
+        of the float32 call on nv12_to_rgb(frames) bit for bit."""
         mode = "gray" if self.frame_shape[2] == 1 else "rgb"
+        if check_rgb_frame_format(rgb_frame_format, mode, rgb_frame_dtype, rgb_frame_layout, frame_dtype, frame_channels, frame_layout,
+                                  self.frame_shape[:2]) == "nv12":
+            m, oy = nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
+            op = _Nv12Operand(frames, self.frame_shape[:2], m, oy, self.ctx)
+            out, optr = op.empty(op.n_frames * self.frame_px * 3)
+            op.call("pyramid_nv12", self.handle, op.ptr, op.n_frames, optr)
+            return PackedPyramid(out, self.extents, 3, op.n_frames)
         check_rgb_frame_dtype(rgb_frame_dtype, mode, frame_dtype, frame_channels, frame_layout)
         strided = check_rgb_frame_layout(rgb_frame_layout, mode, rgb_frame_dtype, frame_dtype, frame_channels, frame_layout) == "strided"
         if rgb_frame_dtype == "uint8":

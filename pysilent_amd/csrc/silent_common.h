@@ -260,11 +260,87 @@ __device__ __forceinline__ StridedRgbSrc frame_of(const FrameStridedRgb& frames,
     return StridedRgbSrc{frames.data + (long long)frame * frames.frame_stride, frames.pixel_stride, frames.row_stride};
 }
 
+// NV12 decoder surfaces (silent_pyramid_nv12, 3-channel plans only): a full-resolution luma plane and a half-resolution plane of
+// interleaved (U, V) pairs, both pitched, converted to three float32 channels IN REGISTERS at the load.  Channel k of pixel (frame, y, x):
+//     Yv = (float)Y[frame][y][x] - oy,  Uv = (float)UV[frame][y >> 1][x >> 1][0] - 128,  Vv = (float)UV[frame][y >> 1][x >> 1][1] - 128
+//     c_k = min(max((Yv * m[3 k] + Uv * m[3 k + 1]) + Vv * m[3 k + 2], 0), 255)
+// with every product and sum a separately rounded float32 operation (__fmul_rn / __fadd_rn: `a * b + c` is contracted into an FMA,
+// which gives other bits) and NO rounding to an integer: the float32 value enters the pyramid.  Chroma is nearest (a 2 x 2 luma block
+// shares one pair).  Matrix and offset are arguments: channel order, BT.601 / BT.709 and limited / full range are the caller's choice
+// of m and oy, not kernel variants.  The struct is the kernels' argument, by value: strides and coefficients arrive in SGPRs, frame and
+// row terms (frame row y, chroma row y >> 1) are scalar 64-bit arithmetic.  nv12_channel is THE conversion: the loaders of every
+// pyramid kernel and nv12_to_rgb_kernel (silent_nv12_to_rgb) call it, so the pyramid of a surface is the float32-frame pyramid of the
+// converted frames bit for bit.
+struct FrameNv12 {
+    const unsigned char* y;
+    const unsigned char* uv;
+    long long y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride;
+    float m[9];
+    float oy;
+};
+template <typename FT>
+constexpr bool kFrameNv12 = std::is_same<FT, FrameNv12>::value;
+// the 3-channel kinds that are read through a `src` struct with at(y, x, ch) / atf(y, i) (strided colour views, NV12 surfaces)
+template <typename FT>
+constexpr bool kFrameRgbSrc = kFrameRgbView<FT> || kFrameNv12<FT>;
+__device__ __forceinline__ float nv12_channel(float yv, float uv, float vv, float m0, float m1, float m2) {
+    return fminf(fmaxf(__fadd_rn(__fadd_rn(__fmul_rn(yv, m0), __fmul_rn(uv, m1)), __fmul_rn(vv, m2)), 0.0f), 255.0f);
+}
+// byte offsets of pixel column x inside a luma row and of its (U, V) pair inside a chroma row
+__host__ __device__ __forceinline__ long long nv12_y_col(long long x) { return x; }
+__host__ __device__ __forceinline__ long long nv12_uv_col(long long x) { return (x >> 1) * 2; }
+// one frame of such a batch inside a kernel
+struct Nv12Src {
+    const unsigned char* y;
+    const unsigned char* uv;
+    long long y_row_stride, uv_row_stride;
+    float m[9];
+    float oy;
+    // the (Y, U, V) of pixel (x, y), offsets removed: a byte load and one 2-byte load at any alignment (global_load_ushort)
+    __device__ __forceinline__ void yuv(long long yy, long long x, float& yv, float& uvv, float& vv) const {
+        const unsigned char* c = uv + (yy >> 1) * uv_row_stride + nv12_uv_col(x);
+        unsigned short pair;
+        __builtin_memcpy(&pair, c, 2);
+        yv = __fsub_rn((float)y[yy * y_row_stride + nv12_y_col(x)], oy);
+        uvv = (float)((int)(pair & 0xffu) - 128);
+        vv = (float)((int)(pair >> 8) - 128);
+    }
+    // channel ch of pixel (x, y) / float i of the virtual packed row y (pixel i / 3, channel i % 3)
+    __device__ __forceinline__ float at(long long yy, long long x, int ch) const {
+        float yv, uvv, vv;
+        yuv(yy, x, yv, uvv, vv);
+        // (the nine coefficients are read first and selected as VALUES: a select between loads becomes a dynamically indexed load,
+        // and with it a copy of the struct in scratch)
+        const float a0 = m[0], a1 = m[1], a2 = m[2], b0 = m[3], b1 = m[4], b2 = m[5], c0 = m[6], c1 = m[7], c2 = m[8];
+        return nv12_channel(yv, uvv, vv, ch == 0 ? a0 : (ch == 1 ? b0 : c0), ch == 0 ? a1 : (ch == 1 ? b1 : c1), ch == 0 ? a2 : (ch == 1 ? b2 : c2));
+    }
+    __device__ __forceinline__ float atf(long long yy, long long i) const {
+        const long long p = i / 3;
+        return at(yy, p, (int)(i - 3 * p));
+    }
+};
+template <>
+struct FrameKind<FrameNv12> {
+    typedef FrameNv12 param;
+    typedef Nv12Src src;
+};
+__device__ __forceinline__ Nv12Src frame_of(const FrameNv12& f, int frame) {
+    Nv12Src s;
+    s.y = f.y + (long long)frame * f.y_frame_stride;
+    s.uv = f.uv + (long long)frame * f.uv_frame_stride;
+    s.y_row_stride = f.y_row_stride;
+    s.uv_row_stride = f.uv_row_stride;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) s.m[i] = f.m[i];
+    s.oy = f.oy;
+    return s;
+}
+
 // the frame types that exist for single-channel plans with float32 accumulation only
 template <typename FT>
 constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT> || kFrameWords<FT> || kFrameStrided<FT>;
 template <typename FT>
-constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT>;
+constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT> || kFrameNv12<FT>;
 // (host) the bytes of one frame pixel as the host-pointer forms stage it -- float frames carry the channels of the plan; a view is
 // staged by its span -- and the suffix of a frame type's entry points
 template <typename FT>
@@ -291,6 +367,11 @@ __device__ __forceinline__ float unit_edge_column(const StridedSrc<PX>& src, lon
 }
 // and of channel `ch` of a strided colour view with its three channels kept
 __device__ __forceinline__ float unit_edge_column(const StridedRgbSrc& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
+                                                  int src_h, int src_y0, int lane) {
+    return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
+}
+// and of channel `ch` of an NV12 surface
+__device__ __forceinline__ float unit_edge_column(const Nv12Src& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
                                                   int src_h, int src_y0, int lane) {
     return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
 }

@@ -59,7 +59,7 @@ using View16 = silent::FrameStrided<unsigned short>;   // (the *_view16 entry po
 using ViewRgb = silent::FrameStridedRgb;               // (silent_pyramid_rgb8_view: three channels KEPT, 3-channel plans; View8x3 reduces them)
 template <typename FT>
 inline auto kernel_frames(const FT* frames) {
-    if constexpr (silent::kFrameStrided<FT> || silent::kFrameRgbView<FT>) return *frames;
+    if constexpr (silent::kFrameStrided<FT> || silent::kFrameRgbSrc<FT>) return *frames;
     else return frames;
 }
 // what a view refuses on its own (silent_hip.h) -- NULL, channels, a stride below its bound, a span of 2^63 bytes or more -- and its
@@ -96,6 +96,46 @@ int with_rgb_view(const silent_pyramid_plan* plan, const silent_frame_view* v, i
     if (v->pixel_stride == 3 && v->row_stride == W * 3 && (n_frames <= 1 || v->frame_stride == H * v->row_stride)) return f(v->data);
     const ViewRgb s{v->data, v->pixel_stride, v->row_stride, n_frames > 1 ? v->frame_stride : 0};
     return f(&s);
+}
+// NV12 surfaces (silent_pyramid_nv12, silent_nv12_to_rgb; silent_hip.h): the host struct travels as `const Nv12*` like a view and is
+// the kernels' argument by value.  check_nv12: what the struct refuses on its own for frames of H x W -- NULL, odd extents, a stride
+// below its bound, a span of 2^63 bytes or more, a non-finite coefficient -- and the two spans in bytes.
+using Nv12 = silent::FrameNv12;
+inline int check_nv12(silent_ctx* ctx, const char* who, bool has_plan, long long H, long long W, const silent_nv12_frames* v, int n_frames,
+                      size_t* y_span, size_t* uv_span) {
+    if (!has_plan || !v || !v->y || !v->uv) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NV12 frames need even H and W (4:2:0 chroma)");
+    typedef unsigned __int128 u128;
+    if (v->y_row_stride < W) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_row_stride is below W");
+    if (v->uv_row_stride < W) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": uv_row_stride is below W");
+    const u128 yf = (u128)(H - 1) * (u128)v->y_row_stride + (u128)W, cf = (u128)(H / 2 - 1) * (u128)v->uv_row_stride + (u128)W;
+    if (n_frames > 1 && (v->y_frame_stride <= 0 || (u128)v->y_frame_stride < yf))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_frame_stride is below (H - 1) * y_row_stride + W");
+    if (n_frames > 1 && (v->uv_frame_stride <= 0 || (u128)v->uv_frame_stride < cf))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": uv_frame_stride is below (H / 2 - 1) * uv_row_stride + W");
+    const u128 ya = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->y_frame_stride : 0) + yf;
+    const u128 ca = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->uv_frame_stride : 0) + cf;
+    if (ya > (u128)0x7fffffffffffffffll || ca > (u128)0x7fffffffffffffffll)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a plane spans more than 2^63 bytes");
+    bool finite = std::isfinite(v->oy);
+    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(v->m[i]);
+    if (!finite) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": m and oy must be finite");
+    if (y_span) *y_span = (size_t)ya;
+    if (uv_span) *uv_span = (size_t)ca;
+    return SILENT_OK;
+}
+// the kernels' argument for a checked struct (the planes at y / uv: those of the struct, or their staged copies)
+inline Nv12 nv12_frames(const silent_nv12_frames* v, const uint8_t* y, const uint8_t* uv, int n_frames) {
+    Nv12 s;
+    s.y = y;
+    s.uv = uv;
+    s.y_row_stride = v->y_row_stride;
+    s.uv_row_stride = v->uv_row_stride;
+    s.y_frame_stride = n_frames > 1 ? v->y_frame_stride : 0;
+    s.uv_frame_stride = n_frames > 1 ? v->uv_frame_stride : 0;
+    for (int i = 0; i < 9; ++i) s.m[i] = v->m[i];
+    s.oy = v->oy;
+    return s;
 }
 // The same for a silent_frame_view16: one uint16 element per pixel (the bounds of check_view with 2 for `channels`), and 2-byte alignment
 // of every address a kernel forms -- an even data address and even strides.

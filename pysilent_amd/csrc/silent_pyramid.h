@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(frame_param<FT> frame
                                                            float* __restrict__ pyr, const PyrTabT<F64> tab) {
     static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && (C == 1 || (C == 3 && kFrameBytes<FT>)))),
                   "uint8 / uint16 frames: one channel (packed uint8 also three interleaved channels), float32 accumulation");
-    static_assert(!kFrameRgbView<FT> || (C == 3 && !F64), "strided uint8 colour views with the channels kept: three channels, float32 accumulation");
+    static_assert(!kFrameRgbSrc<FT> || (C == 3 && !F64), "strided uint8 colour views with the channels kept, NV12 surfaces: three channels, float32 accumulation");
     constexpr int R = kUnitTH;
     const unsigned bid = blockIdx.x;
     const int frame = (int)(bid / (unsigned)tab.unit_tiles_per_frame);
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(frame_param<FT> frame
     const int ox = xw0 + lane - 2;
     const int W = tab.W;
     frame_src<FT> src;
-    if constexpr (kFrameStrided<FT> || kFrameRgbView<FT>) src = frame_of(frames, frame);
+    if constexpr (kFrameStrided<FT> || kFrameRgbSrc<FT>) src = frame_of(frames, frame);
     else src = frames + (long long)frame * tab.H * W * C;
     float* __restrict__ dst = pyr + ((long long)frame * tab.frame_px_out + tab.px_off[l]) * C;
 
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(frame_param<FT> frame
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) {
             if constexpr (kFrameStrided<FT>) in[i][ch] = src.at(sy, sx);   // (C == 1)
-            else if constexpr (kFrameRgbView<FT>) in[i][ch] = src.at(sy, mirror_near(ox, lv.src_w) + lv.src_x0, ch);   // (the lane's column: formed once)
+            else if constexpr (kFrameRgbSrc<FT>) in[i][ch] = src.at(sy, mirror_near(ox, lv.src_w) + lv.src_x0, ch);   // (the lane's column: formed once)
             else in[i][ch] = (float)src[sy * W * C + sx + ch];
         }
     }
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(frame_param<FT> frame
     for (int ch = 0; ch < C; ++ch) {
         if constexpr (kFrameStrided<FT>)
             xcol[ch] = unit_edge_column(src, W, xw0 + 62, lv.src_w, lv.src_x0, y0 - 2, R + 5, lv.src_h, lv.src_y0, lane);
-        else if constexpr (kFrameRgbView<FT>)
+        else if constexpr (kFrameRgbSrc<FT>)
             xcol[ch] = unit_edge_column(src, ch, xw0 + 62, lv.src_w, lv.src_x0, y0 - 2, R + 5, lv.src_h, lv.src_y0, lane);
         else
             xcol[ch] = unit_edge_column(src + ch, (long long)W * C, xw0 + 62, lv.src_w, lv.src_x0, y0 - 2, R + 5, lv.src_h, lv.src_y0, lane, C);
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(frame_param<FT> fra
                                                              float* __restrict__ pyr, const PyrTabT<F64> tab) {
     static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && (C == 1 || (C == 3 && kFrameBytes<FT>)))),
                   "uint8 / uint16 frames: one channel (packed uint8 also three interleaved channels), float32 accumulation");
-    static_assert(!kFrameRgbView<FT> || (C == 3 && !F64), "strided uint8 colour views with the channels kept: three channels, float32 accumulation");
+    static_assert(!kFrameRgbSrc<FT> || (C == 3 && !F64), "strided uint8 colour views with the channels kept, NV12 surfaces: three channels, float32 accumulation");
     constexpr int RW = region_w(C), SW = region_sw(C), SH = region_sh(C), ROWF = SW * C, VR = region_vr(C);
     __shared__ __attribute__((aligned(16))) float s_src[SH * ROWF];
     __shared__ __attribute__((aligned(16))) acc_t<F64> s_v[VR * ROWF];
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(frame_param<FT> fra
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     frame_src<FT> src;
-    if constexpr (kFrameStrided<FT> || kFrameRgbView<FT>) src = frame_of(frames, frame);
+    if constexpr (kFrameStrided<FT> || kFrameRgbSrc<FT>) src = frame_of(frames, frame);
     else src = frames + (long long)frame * H * W * C;
 
     // A region no level has an output in is not staged at all (crop layouts: the reference's nested centre crops leave about half
@@ -267,9 +267,9 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(frame_param<FT> fra
     bool groups = ((W * C) & 3) == 0;
     if constexpr (kFrameBytes<FT>) groups = groups && (reinterpret_cast<unsigned long long>(frames) & 3ull) == 0;   // (block-uniform)
     if constexpr (kFrameWords<FT>) groups = groups && (reinterpret_cast<unsigned long long>(frames) & 7ull) == 0;   // (block-uniform)
-    if constexpr (kFrameRgb8<FT> || kFrameStrided<FT> || kFrameRgbView<FT>) groups = false;   // interleaved colour bytes, strided views: the one-element path (a pixel per element; a channel byte at C == 3)
+    if constexpr (kFrameRgb8<FT> || kFrameStrided<FT> || kFrameRgbSrc<FT>) groups = false;   // interleaved colour bytes, strided views: the one-element path (a pixel per element; a channel byte at C == 3)
     if (groups) {
-      if constexpr (!kFrameStrided<FT> && !kFrameRgbView<FT>) {
+      if constexpr (!kFrameStrided<FT> && !kFrameRgbSrc<FT>) {
         constexpr int V4 = ROWF / 4, NB = (SH * V4 + 255) / 256;
         typename std::conditional<kFrameBytes<FT>, uchar4, typename std::conditional<kFrameWords<FT>, ushort4, float4>::type>::type v[NB];
 #pragma unroll
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(frame_param<FT> fra
             const int sy = min(max(Y0 - kRegionHaloT + r, 0), H - 1);
             const long long f = min(max((long long)(X0 - kRegionHaloL) * C + q, 0ll), (long long)W * C - 1);
             if constexpr (kFrameStrided<FT>) v[k] = src.at(sy, f);   // (C == 1: f is the column)
-            else if constexpr (kFrameRgbView<FT>) v[k] = src.atf(sy, f);   // float f of the virtual packed row: pixel f / 3, channel f % 3
+            else if constexpr (kFrameRgbSrc<FT>) v[k] = src.atf(sy, f);   // float f of the virtual packed row: pixel f / 3, channel f % 3
             else v[k] = (float)src[(long long)sy * W * C + f];
         }
 #pragma unroll
@@ -431,7 +431,7 @@ struct BorderTab {
 // border pixel x channel number gid of the launch (frames x bt.per_frame x C of them).  LEAN: one tap column at a time (6 loads in
 // flight instead of 36) -- inside the walk kernel, whose 7 waves per SIMD must not pay for this path's registers
 // FT: float, or unsigned char at C == 3 (packed interleaved uint8 colour frames: the byte widened at the load), or FrameStridedRgb
-// (the same bytes in a strided view, by value)
+// (the same bytes in a strided view, by value), or FrameNv12 (an NV12 surface, by value: the channel converted at the load)
 template <int C, bool LEAN = false, typename FT = float>
 __device__ __forceinline__ void pyramid_border_px(frame_param<FT> frames, float* __restrict__ pyr, const PyrTab& tab,
                                                   const BorderTab& bt, long long gid, int n_frames) {
@@ -466,18 +466,25 @@ __device__ __forceinline__ void pyramid_border_px(frame_param<FT> frames, float*
     (void)ih;
     const PyrLevelDev& lv = tab.lv[b.level];
     frame_src<FT> src;
-    if constexpr (kFrameRgbView<FT>) src = frame_of(frames, frame);
+    if constexpr (kFrameRgbSrc<FT>) src = frame_of(frames, frame);
     else src = frames + (long long)frame * tab.H * tab.W * C;
     const int* __restrict__ yi = tab.yidx + (long long)(lv.ytab_off + oy) * 6;
     const int* __restrict__ xi = tab.xidx + (long long)(lv.xtab_off + ox) * 6;
     const float* __restrict__ wy = tab.yw + (long long)(lv.ytab_off + oy) * 6;
     const float* __restrict__ wx = tab.xw + (long long)(lv.xtab_off + ox) * 6;
     auto column = [&](int j) {
-        if constexpr (kFrameRgbView<FT>) {
+        if constexpr (kFrameRgbSrc<FT>) {
             const long long x = xi[j] + lv.src_x0;
             float a = __builtin_fmaf(wy[0], src.at(yi[0] + lv.src_y0, x, ch), 0.0f);
 #pragma unroll
-            for (int i = 1; i < 6; ++i) a = __builtin_fmaf(wy[i], src.at(yi[i] + lv.src_y0, x, ch), a);
+            for (int i = 1; i < 6; ++i) {
+                // (NV12 inside the walk kernel: a tap is two loads behind two 64-bit addresses; three taps in flight, not six -- the
+                // walk's consumers set the register budget.  The sum and its order are the same.)
+                if constexpr (kFrameNv12<FT> && LEAN) {
+                    if (i == 3) asm volatile("" ::: "memory");
+                }
+                a = __builtin_fmaf(wy[i], src.at(yi[i] + lv.src_y0, x, ch), a);
+            }
             return a;
         } else {
         const long long col = (long long)(xi[j] + lv.src_x0) * C + ch;
@@ -508,6 +515,23 @@ template <int C, typename FT = float>
 __global__ __launch_bounds__(256) void pyramid_border_kernel(frame_param<FT> frames, float* __restrict__ pyr, const PyrTab tab,
                                                              const BorderTab bt, int n_frames) {
     pyramid_border_px<C, false, FT>(frames, pyr, tab, bt, (long long)blockIdx.x * 256 + threadIdx.x, n_frames);
+}
+
+// ------------------------------------------------------------------------------------------ NV12 -> float32 frames
+// silent_nv12_to_rgb: the frames the pyramid kernels see for an NV12 batch, [n, H, W, 3] float32 -- one thread per pixel, the three
+// channels through the loaders' own device function (Nv12Src::yuv + nv12_channel).  Blocks of 256 pixels of one frame.
+template <int C = 3>
+__global__ __launch_bounds__(256) void nv12_to_rgb_kernel(const FrameNv12 frames, float* __restrict__ rgb, int H, int W, int blocks_per_frame) {
+    const int frame = (int)(blockIdx.x / (unsigned)blocks_per_frame);
+    const long long p = (long long)(blockIdx.x - (unsigned)frame * (unsigned)blocks_per_frame) * 256 + threadIdx.x;
+    if (p >= (long long)H * W) return;
+    const int y = (int)(p / W), x = (int)(p - (long long)y * W);
+    const Nv12Src src = frame_of(frames, frame);
+    float yv, uv, vv;
+    src.yuv(y, x, yv, uv, vv);
+    float* __restrict__ dst = rgb + ((long long)frame * H * W + p) * 3;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) dst[ch] = nv12_channel(yv, uv, vv, src.m[3 * ch], src.m[3 * ch + 1], src.m[3 * ch + 2]);
 }
 
 // ------------------------------------------------------------------------------------------ ZERO FILL

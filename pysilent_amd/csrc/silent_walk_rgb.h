@@ -78,6 +78,10 @@ constexpr int kW3Threads = (kW3NC + 1) * 64;
 #ifndef SILENT_W3_CH
 #define SILENT_W3_CH 4
 #endif
+#ifndef SILENT_W3_NV_ROWS
+#define SILENT_W3_NV_ROWS SILENT_W3_CH
+#endif
+static_assert(SILENT_W3_CH % SILENT_W3_NV_ROWS == 0, "NV12 loader: rows of a chunk loaded and converted together");
 constexpr int kW3CH = SILENT_W3_CH;             // rows per chunk: a 12-row ring (22 KB) instead of 24 rows -- the loader is far from
                                                 // being the limit (all loads alone: 0.14 ms), the consumers are latency-bound and
                                                 // want waves: 31 KB of LDS per block = 4 blocks (16 consumer waves) per CU instead of 3
@@ -182,6 +186,41 @@ __host__ __device__ __forceinline__ W3ViewLoad w3_view_load(const Walk3Args& arg
 }
 __host__ __device__ constexpr int w3_view_row_loads(int px) { return (w3_row_f(px) + 63) / 64; }   // load slots per ring row
 
+// ---- the loader's addresses on NV12 surfaces (FrameNv12, silent_pyramid_nv12): ONE PIXEL per lane and load slot -- a byte of the luma
+// row and the 2-byte (U, V) pair of the chroma row -- converted once and written as the pixel's three ring floats.  Ring float r of a
+// row is float A + r of the virtual packed frame row (pixel f / 3, channel f % 3); slot k of a lane holds pixel p0 + 64 k + lane,
+// p0 = floor(A / 3), whose floats are ring floats 3 (64 k + lane) + (3 p0 - A) + {0, 1, 2} (those outside the row are not written).
+// Host-callable like the view's functions: tests/rgb_nv12_host_main.cpp enumerates them over whole launches.
+__host__ __device__ constexpr int w3_nv12_row_loads(int px) { return ((w3_row_f(px) + 4) / 3 + 63) / 64; }   // load slots per ring row
+__host__ __device__ __forceinline__ int w3_nv12_p0(int A) { return (A + 18) / 3 - 6; }   // floor(A / 3); A >= -15 (halo 4, shift <= 3)
+// the frame column of (lane, slot), clamped into the frame row (what lies outside the crop is never consumed).  Per block.
+__host__ __device__ __forceinline__ int w3_nv12_px(const Walk3Args& args, int A, int lane, int k) {
+    const int p = w3_nv12_p0(A) + lane + 64 * k;
+    return p < 0 ? 0 : (p > args.W - 1 ? args.W - 1 : p);
+}
+// stream row s of a block: byte offsets of its luma row from `y` and of its chroma row from `uv` (scalar 64-bit arithmetic in the
+// kernel).  The chroma row is that of the FRAME row: (src_y0 + y) >> 1, not src_y0 / 2 + y / 2.
+struct W3Nv12Row {
+    long long y, uv;
+};
+__host__ __device__ __forceinline__ W3Nv12Row w3_nv12_row(const Walk3Args& args, const FrameNv12& v, const W3ViewBlock& b, int s) {
+    const Walk3Plan& p = args.plan[b.plan];
+    const long long yy = w3_mirror_near(b.y_first + s, p.src_h) + p.src_y0;
+    return W3Nv12Row{(long long)b.frame * v.y_frame_stride + yy * v.y_row_stride, (long long)b.frame * v.uv_frame_stride + (yy >> 1) * v.uv_row_stride};
+}
+// THE address function: the loads of (block, chunk, row of the chunk, lane, load slot) -- one byte at y_offset from `y` and two bytes
+// at uv_offset from `uv` (any alignment)
+struct W3Nv12Load {
+    long long y_offset, uv_offset;
+};
+__host__ __device__ __forceinline__ W3Nv12Load w3_nv12_load(const Walk3Args& args, const FrameNv12& v, int px, unsigned bid, int chunk, int row,
+                                                            int lane, int k) {
+    const W3ViewBlock b = w3_view_block(args, px, bid);
+    const W3Nv12Row r = w3_nv12_row(args, v, b, chunk * kW3CH + row);
+    const int x = w3_nv12_px(args, b.A, lane, k);
+    return W3Nv12Load{r.y + nv12_y_col(x), r.uv + nv12_uv_col(x)};
+}
+
 // FT: the frame element type -- float, or unsigned char (packed interleaved uint8 colour frames [n, H, W, 3], silent_pyramid_rgb8: byte c
 // of pixel (y, x) enters as (float)byte, an unsigned load and an exact conversion).  Only the LOADER touches the frame: the ring stays
 // float32 and the consumers' text is the same for both kinds, so the uint8 kernel stores the bits the float kernel stores for the
@@ -191,10 +230,15 @@ __host__ __device__ constexpr int w3_view_row_loads(int px) { return (w3_row_f(p
 // scalar 64-bit offset (w3_view_row); the ring, the shift, the mirror fix-up and the consumers do not know about strides.  All byte
 // loads of a chunk are issued before one is consumed; the chunk is complete (vmcnt(0) lgkmcnt(0)) before the barrier.  Every address
 // is that of a channel byte of a pixel of the view: nothing outside [data, data + span) is loaded.
+// FT = FrameNv12 (NV12 surfaces, by value): a pixel per lane and load slot (w3_nv12_load), Y byte + (U, V) pair, converted by
+// nv12_channel with the coefficients in SGPRs, three ring floats written; the same issue / wait / barrier order as the byte loaders.
+// Every address is that of a luma byte or of the chroma pair of a pixel of the frame.
 template <int G, int PX, typename FT = float>
 __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<FT> frames, float* __restrict__ pyr,
                                                                     const Walk3Args args, const WalkBorderArgs border) {
-    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT>, "float32, packed uint8 or strided uint8 colour frames");
+    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT> || kFrameNv12<FT>,
+                  "float32, packed uint8 or strided uint8 colour frames, NV12 surfaces");
+    constexpr bool kNv = kFrameNv12<FT>;                             // the loader converts (Y, U, V) in registers
     constexpr bool kBytes = kFrameBytes<FT> || kFrameRgbView<FT>;   // the loader widens bytes in registers
     static_assert(G == stream_pad_levels(G), "row programs are padded to 4 or 7 levels");
     static_assert(PX == 36 || PX == 32 || PX == 28 || PX == 24, "");
@@ -236,9 +280,10 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
 
     if (wave == kW3NC) {
         // ------------------------------------------------------------------ loader: LDS-DMA only
-        typedef typename std::conditional<kFrameRgbView<FT>, unsigned char, FT>::type ET;   // element of a frame row
+        typedef typename std::conditional<kFrameRgbSrc<FT>, unsigned char, FT>::type ET;   // element of a frame row
         const ET* __restrict__ src;
         if constexpr (kFrameRgbView<FT>) src = frames.data;    // (rows: w3_view_row)
+        else if constexpr (kNv) src = frames.y;                // (rows: w3_nv12_row)
         else src = frames + (long long)frame * args.H * args.W * 3;
         const int rowf = args.W * 3;                           // floats (uint8 frames: bytes) of a FRAME row
         // ring float r <-> frame-row float A + r, A = the crop's pixel R0 minus the alignment shift.  Frame widths that are a
@@ -254,7 +299,17 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
             typename std::conditional<kFrameRgbView<FT>, long long, int>::type f[kRowLoads];
             W3ViewBlock vb;
             (void)vb;
-            if constexpr (kFrameRgbView<FT>) {
+            constexpr int kNvLoads = w3_nv12_row_loads(PX);
+            int nvx[kNv ? kNvLoads : 1];                         // NV12: the lane's frame column per load slot
+            int nvd = 0;                                         // and ring float of channel 0 of its slot-0 pixel minus 3 lane
+            (void)nvx;
+            (void)nvd;
+            if constexpr (kNv) {
+                vb = w3_view_block(args, PX, bid);
+                nvd = 3 * w3_nv12_p0(vb.A) - vb.A;
+#pragma unroll
+                for (int k = 0; k < kNvLoads; ++k) nvx[k] = w3_nv12_px(args, vb.A, lane, k);
+            } else if constexpr (kFrameRgbView<FT>) {
                 static_assert(kRowLoads == w3_view_row_loads(PX), "");
                 vb = w3_view_block(args, PX, bid);
 #pragma unroll
@@ -272,8 +327,32 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                 // goes on to its next barrier, still two chunks ahead of the consumers, who take ~2000 cycles a row
                 typename std::conditional<DWORD_DMA, unsigned char, unsigned>::type v[kBytes ? kW3CH : 1][kRowLoads];
                 (void)v;
+                // NV12: the rows of a chunk are loaded and converted in groups of kNvRows (SILENT_W3_NV_ROWS; default: the whole chunk,
+                // one memory latency per chunk) -- a group's loads (Y byte + chroma pair per slot) are all in flight before one is
+                // consumed; a smaller group reuses the registers and pays a latency per group (measured slower:
+                // profiles/rgb_nv12/README.md)
+                constexpr int kNvRows = SILENT_W3_NV_ROWS;
+                unsigned char nvy[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];
+                unsigned short nvc[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];
+                (void)nvy;
+                (void)nvc;
+                auto nv_load = [&](int g, int r) {                // row g + r of the chunk into register row r
+                    if constexpr (kNv) {
+                        const W3Nv12Row row = w3_nv12_row(args, frames, vb, c * kW3CH + g + r);
+                        const unsigned char* yr = src + row.y;
+                        const unsigned char* cr = frames.uv + row.uv;
+#pragma unroll
+                        for (int k = 0; k < kNvLoads; ++k) {
+                            nvy[r][k] = yr[nv12_y_col(nvx[k])];
+                            __builtin_memcpy(&nvc[r][k], cr + nv12_uv_col(nvx[k]), 2);
+                        }
+                    }
+                };
 #pragma unroll
                 for (int r = 0; r < kW3CH; ++r) {
+                    if constexpr (kNv) {
+                        if (r < kNvRows) nv_load(0, r);
+                    } else {
                     const int y = seg_y0 - 4 + c * kW3CH + r;
                     const ET* rp;
                     if constexpr (kFrameRgbView<FT>) rp = src + w3_view_row(args, frames, vb, c * kW3CH + r);
@@ -296,6 +375,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                         if (lane < (kW3RowF - 256) / 4)
                             __builtin_amdgcn_global_load_lds((walk_glb_ptr)(rp + f[1]), (walk_lds_ptr)(dst + 256), 16, 0, 0);
                     }
+                    }
                 }
                 const int* rp = wp.row_prog + ((long long)seg_y0 + (long long)c * kW3CH) * PR + lane * 4;
                 int* dst = s_prog + slot * (kW3CH * PR);
@@ -304,7 +384,31 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                 if constexpr (NV > 64) {
                     if (lane < NV - 64) __builtin_amdgcn_global_load_lds((walk_glb_ptr)(rp + 256), (walk_lds_ptr)(dst + 256), 16, 0, 0);
                 }
-                if constexpr (kBytes) {
+                if constexpr (kNv) {
+#pragma unroll
+                    for (int g = 0; g < kW3CH; g += kNvRows) {
+                        if (g > 0) {
+                            asm volatile("" ::: "memory");           // (the next group's loads stay behind this group's conversion)
+#pragma unroll
+                            for (int r = 0; r < kNvRows; ++r) nv_load(g, r);
+                        }
+#pragma unroll
+                        for (int r = 0; r < kNvRows; ++r) {
+                            float* row = &s_ring[slot * kW3CH + g + r][0];
+#pragma unroll
+                            for (int k = 0; k < kNvLoads; ++k) {
+                                const float yv = __fsub_rn((float)nvy[r][k], frames.oy);
+                                const float uv = (float)((int)(nvc[r][k] & 0xffu) - 128), vv = (float)((int)(nvc[r][k] >> 8) - 128);
+                                const int q = 3 * (lane + 64 * k) + nvd;     // ring float of channel 0
+#pragma unroll
+                                for (int ch = 0; ch < 3; ++ch)
+                                    if (q + ch >= 0 && q + ch < kW3RowF)
+                                        row[q + ch] = nv12_channel(yv, uv, vv, frames.m[3 * ch], frames.m[3 * ch + 1], frames.m[3 * ch + 2]);
+                            }
+                        }
+                    }
+                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // rows written, records landed
+                } else if constexpr (kBytes) {
 #pragma unroll
                     for (int r = 0; r < kW3CH; ++r) {
                         float* row = &s_ring[slot * kW3CH + r][0];
@@ -347,7 +451,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                 // chunk c has landed when at most the next chunk's loads (three slots: one chunk in flight behind it) are outstanding
                 // (uint8 frames: nothing is outstanding here, issue() ends with vmcnt(0) -- the counted wait would name a mix of register
                 // loads and DMA loads that the compiler is free to reorder)
-                if (!kBytes && kWalkSlots == 3 && c + 1 < n_chunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kRowLoads * kW3CH + (kW3CH * PR / 4 > 64 ? 2 : 1)) : "memory");
+                if (!kBytes && !kNv && kWalkSlots == 3 && c + 1 < n_chunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kRowLoads * kW3CH + (kW3CH * PR / 4 > 64 ? 2 : 1)) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (any_fix) {
 #pragma unroll
@@ -368,7 +472,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
         // takes the one-byte path, which never touches a byte outside the batch)
         bool single = (rowf & 3) != 0;                          // block-uniform
         if constexpr (kFrameBytes<FT>) single = single || (reinterpret_cast<unsigned long long>(frames) & 3ull) != 0;
-        if constexpr (kFrameRgbView<FT>) loader(std::true_type{});   // a view: always the one-byte path (any strides, any alignment)
+        if constexpr (kFrameRgbSrc<FT>) loader(std::true_type{});   // a view: always the one-byte path (any strides, any alignment); NV12: its pixel-per-lane loader
         else if (single) loader(std::true_type{});
         else loader(std::false_type{});
         return;

@@ -132,7 +132,8 @@ class LineEndPipeline(object):
                  max_keypoints_per_frame=None, selection=False, top_percent=0.1, keep_selection_maps=False, value_map=None,
                  peak_value_map=None, orient_map=True, overlap=False, overlap_priorities=True, placement="auto", keypoints=False,
                  regions=None, accumulation="float32", storage="float32", frame_dtype="float32", frame_channels=1,
-                 frame_layout="packed", rgb_frame_dtype="float32", rgb_frame_layout="packed"):
+                 frame_layout="packed", rgb_frame_dtype="float32", rgb_frame_layout="packed", rgb_frame_format="interleaved",
+                 nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr"):
         # rgb_frame_dtype="uint8" (mode "rgb"): step() takes packed interleaved uint8 colour frames [batch, H, W, 3] as a camera or a
         # decoder delivers them and the pyramid kernels read the bytes themselves (silent_pyramid_rgb8_dev) -- no widening cast, no
         # float32 copy of the batch; the pyramid, and with it every map and keypoint, is bit-identical to the float32 pipeline's on
@@ -148,6 +149,17 @@ class LineEndPipeline(object):
         # a non-default frame_dtype / frame_channels / frame_layout
         self.rgb_frame_layout = _runtime.check_rgb_frame_layout(rgb_frame_layout, mode, rgb_frame_dtype, frame_dtype, frame_channels,
                                                                 frame_layout)
+        # rgb_frame_format="nv12" (mode "rgb"): step() takes a pair (y, uv) of uint8 GPU planes as a hardware video decoder emits
+        # them -- luma [batch, H, W], interleaved chroma [batch, H / 2, W / 2, 2], both pitched (util.zoom.nv12_planes cuts them out
+        # of surface tensors) -- and the pyramid kernels read them in place, converting (Y, U, V) to three float32 channels in
+        # registers (silent_pyramid_nv12_dev): no conversion launch, no 12 B/px copy of the batch; pyramid, maps and keypoints are
+        # those of the float32 pipeline on _runtime.nv12_to_rgb(planes), bit for bit.  nv12_matrix ("bt601" / "bt709" or a 3 x 3
+        # array), nv12_range ("limited" / "full") and nv12_order ("bgr" / "rgb") choose the coefficients (_runtime.nv12_coefficients).
+        # Refused here, before any GPU or torch work: unknown names, mode "gray", rgb_frame_dtype="uint8", rgb_frame_layout="strided",
+        # non-default frame_dtype / frame_channels / frame_layout, odd H or W
+        self.rgb_frame_format = _runtime.check_rgb_frame_format(rgb_frame_format, mode, rgb_frame_dtype, rgb_frame_layout, frame_dtype,
+                                                                frame_channels, frame_layout, frame_hw)
+        self.nv12_m, self.nv12_oy = _runtime.nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
         # accumulation="float64" (mode "gray"): every op sums its taps in float64 and rounds once to float32, like the CPU oracle
         # (SILENT_PLAN_ACCUM_F64: the pyramid within 1 ulp of it, CS and end bit-identical to it on the same pyramid).  Checked first:
         # no GPU or torch work for a refused argument
@@ -328,6 +340,10 @@ class LineEndPipeline(object):
     def _synthetic_frames(self):
         """Noise frames of the dtype step() takes (the tuners' default batch)."""
         torch = self.torch
+        if self._nv12:
+            h, w = self.frame_shape[:2]
+            return (torch.randint(0, 256, (self.batch, h, w), device=self.tdev).to(torch.uint8),
+                    torch.randint(0, 256, (self.batch, h // 2, w // 2, 2), device=self.tdev).to(torch.uint8))
         frames = torch.randint(0, 256, (self.batch,) + self.frame_shape, device=self.tdev)
         return frames.to(self._frame_torch_dtype)
 
@@ -569,13 +585,14 @@ class LineEndPipeline(object):
         the returned CS and end maps count 2 bytes per element.  frame_dtype="uint8": the frame read counts 1 byte per frame element
         ("uint16": 2 bytes) -- frame_shape[2] of them per pixel (3 for interleaved colour frames, whose pyramid and maps stay single-channel;
         mode "rgb" with rgb_frame_dtype="uint8" reports frame_dtype "uint8" and counts the same 1 byte per frame element; a strided
-        view, frame_layout / rgb_frame_layout "strided", is read in place and counts the pixel bytes alone, not the bytes between them)."""
+        view, frame_layout / rgb_frame_layout "strided", is read in place and counts the pixel bytes alone, not the bytes between them;
+        rgb_frame_format="nv12" counts 1.5 bytes per pixel: the luma byte and half a chroma pair)."""
         h, w, fc = self.frame_shape
         c = self.channels
         if self.crop_px is not None:
             h, w = 1, self.crop_px
         outs = (1 + self.n_orient) if self.mode == "gray" else (3 + (3 if self.orient_map else 0) + (1 if self.value_map else 0))
-        return self._frame_bytes * h * w * fc + 4 * 2 * self.frame_px * c + self._map_bytes * self.frame_px * outs
+        return int(self._frame_bytes * h * w * fc) + 4 * 2 * self.frame_px * c + self._map_bytes * self.frame_px * outs
 
     @property
     def _map_bytes(self):
@@ -584,8 +601,15 @@ class LineEndPipeline(object):
 
     @property
     def _frame_bytes(self):
-        """Bytes per frame element as step() reads it."""
+        """Bytes per frame element as step() reads it (NV12: 1.5 bytes per pixel over the three channels)."""
+        if self._nv12:
+            return 0.5
         return {"uint8": 1, "uint16": 2}.get(self.frame_dtype, 4)
+
+    @property
+    def _nv12(self):
+        """True for a mode "rgb" pipeline reading NV12 planes (rgb_frame_format="nv12")."""
+        return getattr(self, "rgb_frame_format", "interleaved") == "nv12"
 
     @property
     def _frame_torch_dtype(self):
@@ -606,7 +630,7 @@ class LineEndPipeline(object):
 
     def pyramid_bytes_per_frame(self):
         h, w, fc = self.frame_shape
-        return self._frame_bytes * h * w * fc + 4 * self.frame_px * self.channels
+        return int(self._frame_bytes * h * w * fc) + 4 * self.frame_px * self.channels
 
     def dominant_kernel_name(self):
         """Substring of the rocprofv3 kernel name of the launch that moves most bytes (bench.py matches PMC rows by it)."""
@@ -623,11 +647,20 @@ class LineEndPipeline(object):
         return ("single-read RGB pyramid (pyramid_walk3_kernel), fused RGB chain, max/min + fused selection "
                 "(top 10 % > NMS > value), cell-max / count / scan / write keypoint kernels"
                 + (", uint8 frames read in place (1 byte per frame element)" if getattr(self, "frame_dtype", "float32") == "uint8" else "")
-                + (", read in place from a strided view" if getattr(self, "rgb_frame_layout", "packed") == "strided" else ""))
+                + (", read in place from a strided view" if getattr(self, "rgb_frame_layout", "packed") == "strided" else "")
+                + (", NV12 read in place (Y + UV planes, 1.5 bytes per pixel, converted in registers)" if self._nv12 else ""))
 
     # -- launches --------------------------------------------------------------------------------------
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.tdev).cuda_stream)
+
+    def _nv12_arg(self, frames):
+        """The const silent_nv12_frames* of a pair (y, uv) of GPU planes of this pipeline's batch (refused: anything else)."""
+        args, n, dev = _runtime.nv12_frames_of(frames, self.frame_shape[:2], self.nv12_m, self.nv12_oy)
+        if not dev or n != self.batch:
+            raise ValueError("frames must be a pair (y, uv) of uint8 GPU planes [%d, %d, %d] and [%d, %d, %d, 2]"
+                             % ((self.batch,) + self.frame_shape[:2] + (self.batch, self.frame_shape[0] // 2, self.frame_shape[1] // 2)))
+        return _lib.nv12_ptr(args)
 
     def _check_frames(self, frames):
         if getattr(self, "rgb_frame_layout", "packed") == "strided":
@@ -654,6 +687,10 @@ class LineEndPipeline(object):
         return frame_ptr(frames.data_ptr())
 
     def run_pyramid(self, frames, stream=None):
+        if self._nv12:                                               # (mode "rgb", rgb_frame_format="nv12"; the planes: _nv12_arg)
+            self.ctx.check(self._lib.silent_pyramid_nv12_dev(self.ctx.handle, self.plan.handle, self._nv12_arg(frames), self.batch,
+                                                             C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
+            return
         self._check_frames(frames)
         if getattr(self, "rgb_frame_layout", "packed") == "strided":   # (mode "rgb", rgb_frame_dtype="uint8")
             self.ctx.check(self._lib.silent_pyramid_rgb8_view_dev(self.ctx.handle, self.plan.handle,
@@ -843,6 +880,8 @@ class LineEndPipeline(object):
         no cast launch and no float32 frame buffer.  A frame_dtype="uint16" pipeline likewise takes uint16 host frames only, and a
         mode "rgb" pipeline with rgb_frame_dtype="uint8" uint8 host frames [batch, H, W, 3] only."""
         torch = self.torch
+        if self._nv12:
+            return self._step_host_nv12(frames)
         if isinstance(frames, np.ndarray):
             src = torch.from_numpy(np.ascontiguousarray(frames))
         else:
@@ -855,17 +894,10 @@ class LineEndPipeline(object):
                                  % (self.frame_dtype, self.frame_dtype, src.dtype))
         elif src.dtype != torch.float32:
             _runtime._torch_dtype_code(src)         # TypeError for dtypes the cast kernel does not take
-        if not hasattr(self, "_ingest"):
-            # a stream of another priority than the compute stream gets a hardware queue of its own (two equal-priority streams
-            # may share one, and then copy and compute do not overlap): -1 beside a caller's normal stream; with overlap=True the
-            # chain stream holds -1 and the copies queue with the pyramid stream, which has to follow them anyway
-            self._ingest = {}
-            beside = [self._chain_stream, self._walk_stream] if self.overlap else [torch.cuda.current_stream(self.tdev)]
-            self._copy_stream, self.copy_stream_verified = pick_concurrent_stream(torch, self.tdev, beside, priority=0 if self.overlap else -1)
+        cs = self._copy_stream_of_the_ingest()
         pinned_source = src.is_pinned()
         slot = self._ingest_slot(src.dtype, pinned_source)
         cur = torch.cuda.current_stream(self.tdev)
-        cs = self._copy_stream
         if not pinned_source:
             slot["h2d_done"].synchronize()          # the staging buffer's previous copy has left the host
             _staging_copy(slot["pinned"], src)
@@ -905,6 +937,53 @@ class LineEndPipeline(object):
         if slot["f32_free"] is None:
             slot["f32_free"] = torch.cuda.Event()
         slot["f32_free"].record(self._walk_stream if self.overlap else cur)
+
+    def _copy_stream_of_the_ingest(self):
+        """The copy stream of step_host, made with the ingest ring on the first call."""
+        torch = self.torch
+        if not hasattr(self, "_ingest"):
+            # a stream of another priority than the compute stream gets a hardware queue of its own (two equal-priority streams
+            # may share one, and then copy and compute do not overlap): -1 beside a caller's normal stream; with overlap=True the
+            # chain stream holds -1 and the copies queue with the pyramid stream, which has to follow them anyway
+            self._ingest = {}
+            beside = [self._chain_stream, self._walk_stream] if self.overlap else [torch.cuda.current_stream(self.tdev)]
+            self._copy_stream, self.copy_stream_verified = pick_concurrent_stream(torch, self.tdev, beside, priority=0 if self.overlap else -1)
+        return self._copy_stream
+
+    def _step_host_nv12(self, frames):
+        """step_host of an rgb_frame_format="nv12" pipeline: ``frames`` is the pair (y [batch, H, W], uv [batch, H / 2, W / 2, 2]) as
+        uint8 NumPy arrays (any pitch: the staging copy packs).  Both planes go through pinned staging buffers and asynchronous copies
+        on the copy stream into a ring of two device slots, which step() reads in place; no cast, no conversion launch."""
+        torch = self.torch
+        h, w = self.frame_shape[:2]
+        shapes = ((self.batch, h, w), (self.batch, h // 2, w // 2, 2))
+        if not isinstance(frames, (tuple, list)) or len(frames) != 2 or any(
+                not isinstance(p, np.ndarray) or p.dtype != np.uint8 or tuple(p.shape) != sh for p, sh in zip(frames, shapes)):
+            raise ValueError("step_host of an rgb_frame_format='nv12' pipeline takes a pair of uint8 arrays of shapes %s and %s" % shapes)
+        cs = self._copy_stream_of_the_ingest()
+        ring = self._ingest.setdefault("nv12", {"slots": [], "next": 0})
+        if not ring["slots"]:
+            for _ in range(2):
+                ring["slots"].append({"pinned": [torch.empty(sh, dtype=torch.uint8, pin_memory=True) for sh in shapes],
+                                      "raw": [torch.empty(sh, dtype=torch.uint8, device=self.tdev) for sh in shapes],
+                                      "h2d_done": torch.cuda.Event(), "raw_free": None})
+        slot = ring["slots"][ring["next"]]
+        ring["next"] ^= 1
+        cur = torch.cuda.current_stream(self.tdev)
+        slot["h2d_done"].synchronize()              # the staging buffers' previous copies have left the host
+        for pin, p in zip(slot["pinned"], frames):
+            _staging_copy(pin, torch.from_numpy(np.ascontiguousarray(p)))
+        if slot["raw_free"] is not None:
+            cs.wait_event(slot["raw_free"])         # the previous batch of this slot has been read on the device
+        with torch.cuda.stream(cs):
+            for raw, pin in zip(slot["raw"], slot["pinned"]):
+                raw.copy_(pin, non_blocking=True)
+        slot["h2d_done"].record(cs)
+        cur.wait_event(slot["h2d_done"])
+        self.step(tuple(slot["raw"]))
+        if slot["raw_free"] is None:
+            slot["raw_free"] = torch.cuda.Event()
+        slot["raw_free"].record(self._walk_stream if self.overlap else cur)
 
     def step(self, frames):
         """One pass of the hot path over one batch of frames (asynchronous)."""
