@@ -360,6 +360,48 @@ int silent_pyramid_nv12_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, co
 int silent_nv12_to_rgb(silent_ctx* ctx, const silent_nv12_frames* frames, int n_frames, int H, int W, float* rgb);
 int silent_nv12_to_rgb_dev(silent_ctx* ctx, const silent_nv12_frames* frames, int n_frames, int H, int W, float* rgb, silent_stream stream);
 
+/* P010 / P012 / P016 decoder surfaces for 3-CHANNEL plans, read in place: what a hardware decoder emits for 10- and 12-bit HEVC / AV1 /
+ * VP9 -- the NV12 layout with little-endian uint16 elements (native byte order) whose code value of depth d in {10, 12, 16} sits in the
+ * HIGH d bits; shift = 16 - d.  Luma `y` is [n, H, W] elements, chroma `uv` [n, H / 2, W / 2, 2] interleaved (U, V) element pairs, both
+ * pitched; strides are in BYTES, 64-bit, and even.  For pixel (y, x) of frame f, with Y, U, V the pixel's luma element and the first and
+ * second element of its chroma pair (row y >> 1, pair x >> 1), the value of channel k in {0, 1, 2} is
+ *     Yv = (float)(Y >> shift) - oy       Uv = (float)(U >> shift) - oc       Vv = (float)(V >> shift) - oc
+ *     c_k = min(max((Yv * m[3 k] + Uv * m[3 k + 1]) + Vv * m[3 k + 2], 0), 255)
+ * with the elements loaded UNSIGNED (a code >= 0x8000 does not go negative), the low `shift` bits never influencing a result (decoders
+ * do not promise zeros there), every difference, product and sum a SEPARATELY ROUNDED float32 operation (no fused multiply-add), chroma
+ * NEAREST and NO rounding to an integer: the result is on the 0 .. 255 scale, so a 10-bit code lands on a quarter step of it and keeps
+ * its two extra bits.  m, oy, oc and shift are arguments: one set of kernels serves the three depths, every matrix, range and channel
+ * order.  With m the NV12 matrix times 2^-(d - 8), oy = 16 * 2^(d - 8) and oc = 128 * 2^(d - 8) (limited range), a surface of elements
+ * (byte << 8) | anything-in-the-low-bits gives the pyramid silent_pyramid_nv12 gives for the bytes, bit for bit.
+ * The conversion happens in registers at the kernels' loads.  pyr is IDENTICAL, bit for bit, to silent_pyramid[_dev] on the frames
+ * silent_p010_to_rgb[_dev] writes for the same struct, on every route: the walk kernel, union plans with their border blocks, per-level
+ * plans, the unit + region kernels, every SILENT_TUNE_PYRAMID value.  Reads: only bytes of [y, y + y_span) and [uv, uv + uv_span),
+ * y_span = (n - 1) y_frame_stride + (H - 1) y_row_stride + 2 W, uv_span = (n - 1) uv_frame_stride + (H / 2 - 1) uv_row_stride + 2 W;
+ * every load is a luma element (2 bytes) or the pair of a pixel (4 bytes at a 2-byte aligned address), nothing outside an addressed
+ * element.  A frame stride is not read when n_frames == 1.
+ * Refusals, in this order: a NULL ctx; SILENT_E_INVALID for a NULL plan / struct / y / uv, an odd H or W of the plan (4:2:0), a row
+ * stride below 2 W, a frame stride below its plane's extent (n_frames > 1), a span above 2^63 - 1 bytes, a non-finite m, oy or oc, an
+ * odd y or uv address, an odd stride, a shift outside 0 .. 6; then a NULL pyr / rgb, a plan of another context, n_frames < 1
+ * (SILENT_E_INVALID) and a single-channel plan (SILENT_E_UNSUPPORTED: such a plan reads the luma plane through silent_pyramid_view16).
+ * The host forms stage exactly the two spans and refuse everything their _dev forms refuse before anything is staged; the _dev forms
+ * are stream-ordered and asynchronous; the struct is dead at return.  silent_p010_to_rgb[_dev] writes the converted frames themselves,
+ * [n_frames, H, W, 3] float32, with the same device functions, one thread per pixel; H and W are arguments (both even, >= 2), refusals
+ * as above under its own name.  (ABI additions only: SILENT_ABI_VERSION is unchanged.) */
+typedef struct silent_p010_frames {
+    const uint16_t* y;
+    const uint16_t* uv;
+    int64_t y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride;
+    float m[9];
+    float oy;
+    float oc;
+    int shift;
+} silent_p010_frames;
+int silent_pyramid_p010(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_p010_frames* frames, int n_frames, float* pyr);
+int silent_pyramid_p010_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_p010_frames* frames, int n_frames, float* pyr,
+                            silent_stream stream);
+int silent_p010_to_rgb(silent_ctx* ctx, const silent_p010_frames* frames, int n_frames, int H, int W, float* rgb);
+int silent_p010_to_rgb_dev(silent_ctx* ctx, const silent_p010_frames* frames, int n_frames, int H, int W, float* rgb, silent_stream stream);
+
 /* uint16 frames, read as they are: 10 / 12 / 16-bit machine-vision and scientific cameras (Mono10 / Mono12 / Mono16), thermal and
  * depth sensors (Y16, Z16), 16-bit TIFF / PNG, and the luma of the P010 / P016 surfaces a hardware decoder hands over for 10-bit
  * HEVC / AV1.  The twins of the *_u8 entry points -- same argument lists, maps_f16 / parts / stream arguments, status codes and order

@@ -85,6 +85,14 @@ class Nv12Frames(C.Structure):
                 ("uv_row_stride", C.c_int64), ("uv_frame_stride", C.c_int64), ("m", C.c_float * 9), ("oy", C.c_float)]
 
 
+class P010Frames(C.Structure):
+    """silent_p010_frames (include/silent_hip.h): a P010 / P012 / P016 batch -- uint16 luma plane, interleaved (U, V) plane, four BYTE
+    strides, the 3 x 3 conversion matrix (row k: output channel k), the luma and chroma offsets and shift = 16 - depth."""
+    _fields_ = [("y", C.c_void_p), ("uv", C.c_void_p), ("y_row_stride", C.c_int64), ("y_frame_stride", C.c_int64),
+                ("uv_row_stride", C.c_int64), ("uv_frame_stride", C.c_int64), ("m", C.c_float * 9), ("oy", C.c_float), ("oc", C.c_float),
+                ("shift", C.c_int)]
+
+
 class SilentLibraryError(RuntimeError):
     """libsilent_hip.so is missing or cannot be loaded."""
 
@@ -99,6 +107,7 @@ _wp = C.POINTER(FrameView)    # a strided uint8 view (the *_view entry points); 
 _sp = C.POINTER(C.c_uint16)   # uint16 frames (the *_u16 entry points); short_ptr() makes one from an address
 _xp = C.POINTER(FrameView16)  # a strided uint16 view (the *_view16 entry points); view16_ptr() makes one from frame_view_of's tuple
 _np = C.POINTER(Nv12Frames)   # an NV12 batch (silent_pyramid_nv12, silent_nv12_to_rgb); nv12_ptr() makes one from _runtime.nv12_frames_of's tuple
+_pp = C.POINTER(P010Frames)   # a P010 batch (silent_pyramid_p010, silent_p010_to_rgb); p010_ptr() makes one from _runtime.p010_frames_of's tuple
 _ep = C.POINTER(Extent)
 _i, _u, _f, _d, _sz = C.c_int, C.c_uint, C.c_float, C.c_double, C.c_size_t
 
@@ -144,6 +153,10 @@ _SIGNATURES = {
     "silent_pyramid_nv12_dev": [_vp, _vp, _np, _i, _fp, _vp],
     "silent_nv12_to_rgb": [_vp, _np, _i, _i, _i, _fp],
     "silent_nv12_to_rgb_dev": [_vp, _np, _i, _i, _i, _fp, _vp],
+    "silent_pyramid_p010": [_vp, _vp, _pp, _i, _fp],
+    "silent_pyramid_p010_dev": [_vp, _vp, _pp, _i, _fp, _vp],
+    "silent_p010_to_rgb": [_vp, _pp, _i, _i, _i, _fp],
+    "silent_p010_to_rgb_dev": [_vp, _pp, _i, _i, _i, _fp, _vp],
     "silent_gray_pass_u8": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8x3": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8_dev": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i, _u, _vp],
@@ -274,6 +287,17 @@ def nv12_ptr(frames):
         return None
     y, uv, yr, yf, ur, uf, m, oy = frames
     return C.pointer(Nv12Frames(int(y), int(uv), int(yr), int(yf), int(ur), int(uf), (C.c_float * 9)(*[float(v) for v in m]), float(oy)))
+
+
+def p010_ptr(frames):
+    """(y address, uv address, y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride, m, oy, oc, shift) -- what
+    _runtime.p010_frames_of returns -- as the const silent_p010_frames* of the P010 entry points (None: NULL).  The struct is read
+    before the call returns."""
+    if frames is None:
+        return None
+    y, uv, yr, yf, ur, uf, m, oy, oc, shift = frames
+    return C.pointer(P010Frames(int(y), int(uv), int(yr), int(yf), int(ur), int(uf), (C.c_float * 9)(*[float(v) for v in m]), float(oy),
+                                float(oc), int(shift)))
 
 
 def gray_entry(family, frame_dtype="float32", frame_channels=1, storage="float32", dev=False, parts=None, frame_layout="packed"):

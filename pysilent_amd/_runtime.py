@@ -980,42 +980,45 @@ def check_rgb_frame_layout(rgb_frame_layout, mode="rgb", rgb_frame_dtype="float3
     return rgb_frame_layout
 
 
-RGB_FRAME_FORMATS = ("interleaved", "nv12")
+RGB_FRAME_FORMATS = ("interleaved", "nv12", "p010", "p012", "p016")
 NV12_MATRICES = {"bt601": (.299, .114), "bt709": (.2126, .0722)}      # (Kr, Kb)
 NV12_RANGES = ("limited", "full")
 NV12_ORDERS = ("bgr", "rgb")
+P010_DEPTHS = {"p010": 10, "p012": 12, "p016": 16}                   # rgb_frame_format -> bits of a code value (shift = 16 - depth)
+P010_MATRICES = dict(NV12_MATRICES, bt2020=(.2627, .0593))           # Rec. 2020 defines 10- and 12-bit video only
 
 
 def check_rgb_frame_format(rgb_frame_format, mode="rgb", rgb_frame_dtype="float32", rgb_frame_layout="packed", frame_dtype="float32",
                            frame_channels=1, frame_layout="packed", hw=None):
-    """The rgb_frame_format argument of PyramidPlan.run and LineEndPipeline: "interleaved" (default: nothing changes) or "nv12" (mode
+    """The rgb_frame_format argument of PyramidPlan.run and LineEndPipeline: "interleaved" (default: nothing changes), "nv12" (mode
     "rgb" / a 3-channel plan: the frames are a pair (y, uv) of uint8 planes as a hardware video decoder emits them -- luma [n, H, W],
     interleaved chroma [n, H / 2, W / 2, 2], both pitched -- read in place by silent_pyramid_nv12 and converted to three float32
     channels in registers: no conversion launch, no copy of the batch; the pyramid is that of the float32 path on the converted
-    frames bit for bit).  The name is checked first; then the mode; then that "nv12" is not combined with rgb_frame_dtype="uint8",
-    rgb_frame_layout="strided" or the gray frame_* keywords; then that H and W (hw, when given) are even."""
+    frames bit for bit) or "p010" / "p012" / "p016" (the same pair as uint16 planes, the 10 / 12 / 16-bit code in the high bits of
+    each element: silent_pyramid_p010).  The name is checked first; then the mode; then that the format is not combined with
+    rgb_frame_dtype="uint8", rgb_frame_layout="strided" or the gray frame_* keywords; then that H and W (hw, when given) are even."""
     if not isinstance(rgb_frame_format, str) or rgb_frame_format not in RGB_FRAME_FORMATS:
-        raise ValueError("rgb_frame_format must be 'interleaved' or 'nv12', got %r" % (rgb_frame_format,))
-    if rgb_frame_format == "nv12":
+        raise ValueError("rgb_frame_format must be 'interleaved' or 'nv12', or 'p010' / 'p012' / 'p016', got %r" % (rgb_frame_format,))
+    if rgb_frame_format != "interleaved":
+        name = "rgb_frame_format=%r" % (rgb_frame_format,)
+        wide = rgb_frame_format in P010_DEPTHS
         if mode != "rgb":
-            raise ValueError("rgb_frame_format='nv12' is for mode 'rgb' (mode 'gray' reads the luma plane through frame_layout='strided')")
+            raise ValueError("%s is for mode 'rgb' (mode 'gray' reads the luma plane through frame_layout='strided'%s)"
+                             % (name, " with frame_dtype='uint16'" if wide else ""))
         if rgb_frame_dtype != "float32":
-            raise ValueError("rgb_frame_format='nv12' does not combine with rgb_frame_dtype=%r (the planes are uint8; the converted "
-                             "channels are float32)" % (rgb_frame_dtype,))
+            raise ValueError("%s does not combine with rgb_frame_dtype=%r (the planes are %s; the converted "
+                             "channels are float32)" % (name, rgb_frame_dtype, "uint16" if wide else "uint8"))
         if rgb_frame_layout != "packed":
-            raise ValueError("rgb_frame_format='nv12' does not combine with rgb_frame_layout=%r (the planes carry their own pitches)"
-                             % (rgb_frame_layout,))
+            raise ValueError("%s does not combine with rgb_frame_layout=%r (the planes carry their own pitches)" % (name, rgb_frame_layout))
         if frame_dtype != "float32":
-            raise ValueError("rgb_frame_format='nv12' does not combine with frame_dtype=%r (frame_dtype describes the frames of mode 'gray')"
-                             % (frame_dtype,))
+            raise ValueError("%s does not combine with frame_dtype=%r (frame_dtype describes the frames of mode 'gray')" % (name, frame_dtype))
         if frame_channels != 1:
-            raise ValueError("rgb_frame_format='nv12' does not combine with frame_channels=%r (frame_channels describes the frames of mode 'gray')"
-                             % (frame_channels,))
+            raise ValueError("%s does not combine with frame_channels=%r (frame_channels describes the frames of mode 'gray')"
+                             % (name, frame_channels))
         if frame_layout != "packed":
-            raise ValueError("rgb_frame_format='nv12' does not combine with frame_layout=%r (frame_layout describes the frames of mode 'gray')"
-                             % (frame_layout,))
+            raise ValueError("%s does not combine with frame_layout=%r (frame_layout describes the frames of mode 'gray')" % (name, frame_layout))
         if hw is not None and (int(hw[0]) % 2 or int(hw[1]) % 2 or min(int(hw[0]), int(hw[1])) < 2):
-            raise ValueError("rgb_frame_format='nv12' needs even H and W (4:2:0 chroma), got %s" % (tuple(int(v) for v in hw),))
+            raise ValueError("%s needs even H and W (4:2:0 chroma), got %s" % (name, tuple(int(v) for v in hw)))
     return rgb_frame_format
 
 
@@ -1117,6 +1120,113 @@ def nv12_to_rgb(planes, hw, nv12_matrix="bt709", nv12_range="limited", nv12_orde
     return out
 
 
+def p010_coefficients(nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", depth=10):
+    """(m, oy, oc) of the P010 entry points for code values of ``depth`` bits (10, 12, 16): m [3, 3] float32, row k = output channel k
+    over (Y - oy, U - oc, V - oc), oy and oc float32.  With s = 2^(depth - 8): nv12_matrix "bt601" / "bt709" / "bt2020" -- the rows of
+    nv12_coefficients built in float64 from (Kr, Kb), each coefficient rounded once to float32, with (ys, cs, oy, oc) =
+    (255 / (219 s), 255 / (224 s), 16 s, 128 s) for nv12_range="limited" and (255 / (2^depth - 1), 255 / (2^depth - 1), 0, 128 s) for
+    "full", rows in nv12_order -- or a 3 x 3 array-like of coefficients ON THE 8-BIT SCALE, as for NV12 (rows = output channels;
+    nv12_order is not applied): it is multiplied by 2^-(depth - 8), which is exact, and nv12_range gives oy (16 s or 0)."""
+    if depth not in (10, 12, 16):
+        raise ValueError("depth must be 10, 12 or 16, got %r" % (depth,))
+    if nv12_range not in NV12_RANGES:
+        raise ValueError("nv12_range must be 'limited' or 'full', got %r" % (nv12_range,))
+    if nv12_order not in NV12_ORDERS:
+        raise ValueError("nv12_order must be 'bgr' or 'rgb', got %r" % (nv12_order,))
+    s = float(2 ** (depth - 8))
+    full = 255.0 / (2.0 ** depth - 1.0)
+    ys, cs, oy = (255.0 / (219.0 * s), 255.0 / (224.0 * s), 16.0 * s) if nv12_range == "limited" else (full, full, 0.0)
+    if isinstance(nv12_matrix, str):
+        if nv12_matrix not in P010_MATRICES:
+            raise ValueError("nv12_matrix must be 'bt601', 'bt709', 'bt2020' or a 3 x 3 array, got %r" % (nv12_matrix,))
+        kr, kb = P010_MATRICES[nv12_matrix]
+        kg = 1.0 - kr - kb
+        rows = {"r": (ys, 0.0, 2.0 * (1.0 - kr) * cs),
+                "g": (ys, -2.0 * kb * (1.0 - kb) / kg * cs, -2.0 * kr * (1.0 - kr) / kg * cs),
+                "b": (ys, 2.0 * (1.0 - kb) * cs, 0.0)}
+        m = np.array([rows[c] for c in nv12_order], np.float64).astype(np.float32)
+    else:
+        try:
+            m = np.array(nv12_matrix, np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("nv12_matrix must be 'bt601', 'bt709', 'bt2020' or a 3 x 3 array, got %r" % (nv12_matrix,))
+        if m.shape != (3, 3) or not np.all(np.isfinite(m)):
+            raise ValueError("nv12_matrix must be 'bt601', 'bt709', 'bt2020' or a finite 3 x 3 array, got shape %s" % (m.shape,))
+        m = m.astype(np.float32) * np.float32(1.0 / s)          # (a power of two: exact)
+    return m, np.float32(oy), np.float32(128.0 * s)
+
+
+def p010_frames_of(planes, hw, m, oy, oc, depth):
+    """A pair (y, uv) of uint16 planes -- both ndarrays or both torch.uint16 GPU tensors; y [n, H, W] with element stride 2 bytes,
+    uv [n, H / 2, W / 2, 2] with the two elements of a pair and the pairs of a row adjacent, positive non-overlapping row / frame
+    strides -- as what _lib.p010_ptr takes: (y address, uv address, y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride (BYTES),
+    m, oy, oc, shift = 16 - depth).  Returns (that tuple, n, on_device).  Nothing is converted or copied."""
+    if depth not in (10, 12, 16):
+        raise ValueError("depth must be 10, 12 or 16, got %r" % (depth,))
+    if not isinstance(planes, (tuple, list)) or len(planes) != 2:
+        raise ValueError("P010 frames are a pair (y, uv) of uint16 planes")
+    y, uv = planes
+    dev = is_torch_tensor(y)
+    if not (dev and is_torch_tensor(uv)) and not (isinstance(y, np.ndarray) and isinstance(uv, np.ndarray)):
+        raise TypeError(TYPE_ERROR_MESSAGE)
+    h, w = int(hw[0]), int(hw[1])
+
+    def geometry(p):
+        if dev:
+            import torch
+            if p.dtype != torch.uint16 or not p.is_cuda:
+                raise ValueError("P010 planes must be uint16 GPU tensors or uint16 ndarrays (nothing is converted), got %s" % (p.dtype,))
+            return tuple(int(s) for s in p.shape), tuple(2 * int(s) for s in p.stride()), int(p.data_ptr())
+        if p.dtype != np.uint16:
+            raise ValueError("P010 planes must be uint16 GPU tensors or uint16 ndarrays (nothing is converted), got %s" % (p.dtype,))
+        return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.strides), int(p.ctypes.data)
+
+    ys, yst, ya = geometry(y)
+    cs, cst, ca = geometry(uv)
+    if len(ys) != 3 or ys[1:] != (h, w) or ys[0] < 1:
+        raise ValueError("the P010 luma plane must be [n, %d, %d], got %s" % (h, w, ys))
+    n = ys[0]
+    if cs != (n, h // 2, w // 2, 2):
+        raise ValueError("the P010 chroma plane must be [%d, %d, %d, 2], got %s" % (n, h // 2, w // 2, cs))
+    if (w > 1 and yst[2] != 2) or cst[3] != 2 or (w > 2 and cst[2] != 4):
+        raise ValueError("P010 planes: luma elements of a row and the (U, V) pairs of a chroma row must be adjacent (byte strides %s, %s)" % (yst, cst))
+    yr, cr = (yst[1] if h > 1 else 2 * w), (cst[1] if h > 2 else 2 * w)
+    yf, cf = (yst[0] if n > 1 else (h - 1) * yr + 2 * w), (cst[0] if n > 1 else (h // 2 - 1) * cr + 2 * w)
+    if yr < 2 * w or cr < 2 * w or yf < (h - 1) * yr + 2 * w or cf < (h // 2 - 1) * cr + 2 * w:
+        raise ValueError("P010 planes: rows or frames overlap, or a stride is not positive (byte strides %s, %s)" % (yst, cst))
+    return (ya, ca, yr, yf, cr, cf, [float(v) for v in np.asarray(m, np.float32).reshape(9)], float(oy), float(oc), 16 - depth), n, dev
+
+
+class _P010Operand(_Nv12Operand):
+    """A P010 / P012 / P016 batch (p010_frames_of) as an operand (see _Nv12Operand)."""
+
+    def __init__(self, planes, hw, m, oy, oc, depth, ctx=None):
+        args, self.n_frames, self.dev = p010_frames_of(planes, hw, m, oy, oc, depth)
+        self.packed, self.c, self.extents = False, 3, [(int(hw[0]), int(hw[1]))]
+        self.device = self.stream = None
+        if self.dev:
+            import torch
+            self._torch_device = planes[0].device
+            self.device = self._torch_device.index or 0
+            self.stream = C.c_void_p(torch.cuda.current_stream(self._torch_device).cuda_stream)
+        self.ptr = _lib.p010_ptr(args)
+        self.buf = tuple(planes)                        # keep alive
+        self.ctx = ctx or get_context(self.device)
+
+
+def p010_to_rgb(planes, hw, depth=10, nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", device=None):
+    """The float32 frames [n, H, W, 3] the pyramid kernels see for a P010 (depth=10) / P012 (12) / P016 (16) batch
+    (silent_p010_to_rgb[_dev]: the loaders' own device functions, one thread per pixel), on the 0 .. 255 scale and not rounded -- for
+    display, and as the reference of the bit-identity contract.  planes: p010_frames_of."""
+    m, oy, oc = p010_coefficients(nv12_matrix, nv12_range, nv12_order, depth)
+    check_rgb_frame_format({10: "p010", 12: "p012", 16: "p016"}[depth], hw=hw)
+    op = _P010Operand(planes, hw, m, oy, oc, depth, None if device is None else get_context(device))
+    h, w = int(hw[0]), int(hw[1])
+    out, optr = op.empty((op.n_frames, h, w, 3))
+    op.call("p010_to_rgb", op.ptr, op.n_frames, h, w, optr)
+    return out
+
+
 class PyramidPlan(object):
     """Tap tables of one (frame size, level geometry) on the device.  ``levels`` is a list of dicts / tuples
     (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w).  accumulation="float64" (single-channel plans): every op of
@@ -1194,8 +1304,17 @@ class PyramidPlan(object):
         uint8 planes (nv12_frames_of) read in place and converted in registers (silent_pyramid_nv12; nv12_coefficients), the pyramid
         of the float32 call on nv12_to_rgb(frames) bit for bit."""
         mode = "gray" if self.frame_shape[2] == 1 else "rgb"
-        if check_rgb_frame_format(rgb_frame_format, mode, rgb_frame_dtype, rgb_frame_layout, frame_dtype, frame_channels, frame_layout,
-                                  self.frame_shape[:2]) == "nv12":
+        fmt = check_rgb_frame_format(rgb_frame_format, mode, rgb_frame_dtype, rgb_frame_layout, frame_dtype, frame_channels, frame_layout,
+                                     self.frame_shape[:2])
+        if fmt in P010_DEPTHS:
+            # "p010" / "p012" / "p016": the same pair as uint16 planes (p010_frames_of), the code in the high bits of each element
+            # (silent_pyramid_p010; p010_coefficients, which also knows "bt2020"), the pyramid of the float32 call on p010_to_rgb(frames)
+            m, oy, oc = p010_coefficients(nv12_matrix, nv12_range, nv12_order, P010_DEPTHS[fmt])
+            op = _P010Operand(frames, self.frame_shape[:2], m, oy, oc, P010_DEPTHS[fmt], self.ctx)
+            out, optr = op.empty(op.n_frames * self.frame_px * 3)
+            op.call("pyramid_p010", self.handle, op.ptr, op.n_frames, optr)
+            return PackedPyramid(out, self.extents, 3, op.n_frames)
+        if fmt == "nv12":
             m, oy = nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
             op = _Nv12Operand(frames, self.frame_shape[:2], m, oy, self.ctx)
             out, optr = op.empty(op.n_frames * self.frame_px * 3)

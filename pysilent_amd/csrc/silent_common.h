@@ -280,9 +280,20 @@ struct FrameNv12 {
 };
 template <typename FT>
 constexpr bool kFrameNv12 = std::is_same<FT, FrameNv12>::value;
-// the 3-channel kinds that are read through a `src` struct with at(y, x, ch) / atf(y, i) (strided colour views, NV12 surfaces)
+// P010 / P012 / P016 decoder surfaces (silent_pyramid_p010): the NV12 layout with uint16 elements, the code in the high bits (below)
+struct FrameP010 {
+    const unsigned short* y;
+    const unsigned short* uv;
+    long long y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride;   // bytes, even
+    float m[9];
+    float oy, oc;
+    int shift;                                                                // 16 - depth
+};
 template <typename FT>
-constexpr bool kFrameRgbSrc = kFrameRgbView<FT> || kFrameNv12<FT>;
+constexpr bool kFrameP010 = std::is_same<FT, FrameP010>::value;
+// the 3-channel kinds that are read through a `src` struct with at(y, x, ch) / atf(y, i) (strided colour views, NV12 and P010 surfaces)
+template <typename FT>
+constexpr bool kFrameRgbSrc = kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT>;
 __device__ __forceinline__ float nv12_channel(float yv, float uv, float vv, float m0, float m1, float m2) {
     return fminf(fmaxf(__fadd_rn(__fadd_rn(__fmul_rn(yv, m0), __fmul_rn(uv, m1)), __fmul_rn(vv, m2)), 0.0f), 255.0f);
 }
@@ -336,11 +347,75 @@ __device__ __forceinline__ Nv12Src frame_of(const FrameNv12& f, int frame) {
     return s;
 }
 
+// P010 / P012 / P016 decoder surfaces (silent_pyramid_p010, 3-channel plans only): NV12's two planes with little-endian uint16
+// elements whose code value sits in the HIGH d bits (d = 10, 12, 16; shift = 16 - d, a runtime scalar: one set of kernels for the
+// three depths).  Channel k of pixel (frame, y, x), with Y, U, V the pixel's luma element and the two elements of its chroma pair:
+//     Yv = (float)(Y >> shift) - oy,  Uv = (float)(U >> shift) - oc,  Vv = (float)(V >> shift) - oc,  c_k = nv12_channel(Yv, Uv, Vv, row k of m)
+// -- elements loaded UNSIGNED, the low `shift` bits shifted out (decoders do not promise zeros there), the subtractions separately
+// rounded float32 operations like the products and sums of nv12_channel, which stays THE conversion; the result is on the 0 .. 255
+// scale and not rounded to an integer, so a 10-bit code lands on a quarter step.  Strides are BYTES and even, the pointers 2-byte
+// aligned (refused otherwise): every load is a 2-byte luma element or the 4-byte (U, V) pair as ONE dword at a 2-byte aligned address
+// (global_load_dword; the NV12 loaders read their 2-byte pair at any alignment the same way) -- exactly the two addressed elements.
+// p010_values: the element and the pair as they were loaded -> (Yv, Uv, Vv); every loader and p010_to_rgb_kernel go through it.
+__device__ __forceinline__ void p010_values(unsigned e, unsigned pair, float oy, float oc, int shift, float& yv, float& uv, float& vv) {
+    yv = __fsub_rn((float)((e & 0xffffu) >> shift), oy);
+    uv = __fsub_rn((float)((pair & 0xffffu) >> shift), oc);
+    vv = __fsub_rn((float)((pair >> 16) >> shift), oc);
+}
+// byte offsets of pixel column x inside a luma row and of its (U, V) pair inside a chroma row
+__host__ __device__ __forceinline__ long long p010_y_col(long long x) { return 2 * x; }
+__host__ __device__ __forceinline__ long long p010_uv_col(long long x) { return (x >> 1) * 4; }
+// one frame of such a batch inside a kernel (the planes as byte pointers: strides are bytes)
+struct P010Src {
+    const unsigned char* y;
+    const unsigned char* uv;
+    long long y_row_stride, uv_row_stride;
+    float m[9];
+    float oy, oc;
+    int shift;
+    __device__ __forceinline__ void yuv(long long yy, long long x, float& yv, float& uvv, float& vv) const {
+        unsigned short e;
+        unsigned pair;
+        __builtin_memcpy(&e, y + yy * y_row_stride + p010_y_col(x), 2);
+        __builtin_memcpy(&pair, uv + (yy >> 1) * uv_row_stride + p010_uv_col(x), 4);
+        p010_values(e, pair, oy, oc, shift, yv, uvv, vv);
+    }
+    // channel ch of pixel (x, y) / float i of the virtual packed row y (coefficients selected as values: Nv12Src::at)
+    __device__ __forceinline__ float at(long long yy, long long x, int ch) const {
+        float yv, uvv, vv;
+        yuv(yy, x, yv, uvv, vv);
+        const float a0 = m[0], a1 = m[1], a2 = m[2], b0 = m[3], b1 = m[4], b2 = m[5], c0 = m[6], c1 = m[7], c2 = m[8];
+        return nv12_channel(yv, uvv, vv, ch == 0 ? a0 : (ch == 1 ? b0 : c0), ch == 0 ? a1 : (ch == 1 ? b1 : c1), ch == 0 ? a2 : (ch == 1 ? b2 : c2));
+    }
+    __device__ __forceinline__ float atf(long long yy, long long i) const {
+        const long long p = i / 3;
+        return at(yy, p, (int)(i - 3 * p));
+    }
+};
+template <>
+struct FrameKind<FrameP010> {
+    typedef FrameP010 param;
+    typedef P010Src src;
+};
+__device__ __forceinline__ P010Src frame_of(const FrameP010& f, int frame) {
+    P010Src s;
+    s.y = reinterpret_cast<const unsigned char*>(f.y) + (long long)frame * f.y_frame_stride;
+    s.uv = reinterpret_cast<const unsigned char*>(f.uv) + (long long)frame * f.uv_frame_stride;
+    s.y_row_stride = f.y_row_stride;
+    s.uv_row_stride = f.uv_row_stride;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) s.m[i] = f.m[i];
+    s.oy = f.oy;
+    s.oc = f.oc;
+    s.shift = f.shift;
+    return s;
+}
+
 // the frame types that exist for single-channel plans with float32 accumulation only
 template <typename FT>
 constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT> || kFrameWords<FT> || kFrameStrided<FT>;
 template <typename FT>
-constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT> || kFrameNv12<FT>;
+constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT>;
 // (host) the bytes of one frame pixel as the host-pointer forms stage it -- float frames carry the channels of the plan; a view is
 // staged by its span -- and the suffix of a frame type's entry points
 template <typename FT>
@@ -372,6 +447,11 @@ __device__ __forceinline__ float unit_edge_column(const StridedRgbSrc& src, int 
 }
 // and of channel `ch` of an NV12 surface
 __device__ __forceinline__ float unit_edge_column(const Nv12Src& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
+                                                  int src_h, int src_y0, int lane) {
+    return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
+}
+// and of a P010 surface
+__device__ __forceinline__ float unit_edge_column(const P010Src& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
                                                   int src_h, int src_y0, int lane) {
     return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
 }

@@ -137,6 +137,52 @@ inline Nv12 nv12_frames(const silent_nv12_frames* v, const uint8_t* y, const uin
     s.oy = v->oy;
     return s;
 }
+// P010 / P012 / P016 surfaces (silent_pyramid_p010, silent_p010_to_rgb; silent_hip.h): NV12's checks in NV12's order with 2-byte
+// elements (a row holds 2 W bytes), then what uint16 elements add -- an odd plane address, an odd stride, a shift outside 0 .. 6.
+using P010 = silent::FrameP010;
+inline int check_p010(silent_ctx* ctx, const char* who, bool has_plan, long long H, long long W, const silent_p010_frames* v, int n_frames,
+                      size_t* y_span, size_t* uv_span) {
+    if (!has_plan || !v || !v->y || !v->uv) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": P010 frames need even H and W (4:2:0 chroma)");
+    typedef unsigned __int128 u128;
+    if (v->y_row_stride < 2 * W) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_row_stride is below 2 * W");
+    if (v->uv_row_stride < 2 * W) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": uv_row_stride is below 2 * W");
+    const u128 yf = (u128)(H - 1) * (u128)v->y_row_stride + (u128)(2 * W), cf = (u128)(H / 2 - 1) * (u128)v->uv_row_stride + (u128)(2 * W);
+    if (n_frames > 1 && (v->y_frame_stride <= 0 || (u128)v->y_frame_stride < yf))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_frame_stride is below (H - 1) * y_row_stride + 2 * W");
+    if (n_frames > 1 && (v->uv_frame_stride <= 0 || (u128)v->uv_frame_stride < cf))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": uv_frame_stride is below (H / 2 - 1) * uv_row_stride + 2 * W");
+    const u128 ya = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->y_frame_stride : 0) + yf;
+    const u128 ca = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->uv_frame_stride : 0) + cf;
+    if (ya > (u128)0x7fffffffffffffffll || ca > (u128)0x7fffffffffffffffll)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a plane spans more than 2^63 bytes");
+    bool finite = std::isfinite(v->oy) && std::isfinite(v->oc);
+    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(v->m[i]);
+    if (!finite) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": m, oy and oc must be finite");
+    if ((reinterpret_cast<uintptr_t>(v->y) | reinterpret_cast<uintptr_t>(v->uv)) & 1u)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y and uv must be 2-byte aligned (uint16 elements)");
+    if (((v->y_row_stride | v->uv_row_stride) & 1) || (n_frames > 1 && ((v->y_frame_stride | v->uv_frame_stride) & 1)))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a stride is odd (uint16 elements)");
+    if (v->shift < 0 || v->shift > 6) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": shift must be 0 .. 6 (16 - depth)");
+    if (y_span) *y_span = (size_t)ya;
+    if (uv_span) *uv_span = (size_t)ca;
+    return SILENT_OK;
+}
+// the kernels' argument for a checked struct (the planes at y / uv: those of the struct, or their staged copies)
+inline P010 p010_frames(const silent_p010_frames* v, const uint16_t* y, const uint16_t* uv, int n_frames) {
+    P010 s;
+    s.y = y;
+    s.uv = uv;
+    s.y_row_stride = v->y_row_stride;
+    s.uv_row_stride = v->uv_row_stride;
+    s.y_frame_stride = n_frames > 1 ? v->y_frame_stride : 0;
+    s.uv_frame_stride = n_frames > 1 ? v->uv_frame_stride : 0;
+    for (int i = 0; i < 9; ++i) s.m[i] = v->m[i];
+    s.oy = v->oy;
+    s.oc = v->oc;
+    s.shift = v->shift;
+    return s;
+}
 // The same for a silent_frame_view16: one uint16 element per pixel (the bounds of check_view with 2 for `channels`), and 2-byte alignment
 // of every address a kernel forms -- an even data address and even strides.
 inline int check_view16(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const silent_frame_view16* v, int n_frames, size_t* span) {

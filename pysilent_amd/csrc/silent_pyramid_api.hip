@@ -909,8 +909,8 @@ static int pyramid_rgb8_checks(silent_ctx* ctx, const char* who, const silent_py
     return SILENT_OK;
 }
 
-// FT: unsigned char, ViewRgb (silent_pyramid_rgb8_view on a view that is not packed) or Nv12 (silent_pyramid_nv12); the last two are
-// checked by the caller
+// FT: unsigned char, ViewRgb (silent_pyramid_rgb8_view on a view that is not packed), Nv12 (silent_pyramid_nv12) or P010
+// (silent_pyramid_p010); all but the first are checked by the caller
 template <typename FT>
 static int launch_pyramid_rgb8(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames,
                                float* pyr, hipStream_t s) {
@@ -1054,4 +1054,78 @@ SILENT_EXPORT int silent_nv12_to_rgb(silent_ctx* ctx, const silent_nv12_frames* 
     return nv12_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_nv12_to_rgb");
+}
+
+// P010 / P012 / P016 decoder surfaces (silent_hip.h): the NV12 entry points with uint16 elements -- the struct's own refusals, then the
+// shared ones, under the entry point's name; the host forms stage exactly the two spans and rebase the two pointers.
+static int pyramid_p010(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_p010_frames* f, int n_frames, float* pyr,
+                        silent_stream stream) {
+    const char* who = "silent_pyramid_p010";
+    size_t y_span = 0, uv_span = 0;
+    TRY(check_p010(ctx, who, plan != nullptr, plan ? plan->tab.H : 0, plan ? plan->tab.W : 0, f, n_frames, &y_span, &uv_span));
+    TRY(pyramid_checks<float>(ctx, who, plan, true, n_frames, pyr));
+    if (plan->tab.C != 3)
+        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": P010 surfaces are for 3-channel plans (a single-channel plan reads the luma plane through silent_pyramid_view16)");
+    if (!host) {
+        const P010 s = p010_frames(f, f->y, f->uv, n_frames);
+        return launch_pyramid_rgb8(ctx, who, plan, &s, n_frames, pyr, (hipStream_t)stream);
+    }
+    HostStage hs(ctx);
+    const int a = hs.in(f->y, y_span), b = hs.in(f->uv, uv_span), o = hs.out(pyr, (size_t)plan->tab.frame_px_out * 3 * 4 * n_frames);
+    return hs.run([&] {
+        const P010 s = p010_frames(f, hs.dev<uint16_t>(a), hs.dev<uint16_t>(b), n_frames);
+        return launch_pyramid_rgb8(ctx, who, plan, &s, n_frames, hs.dev<float>(o), nullptr);
+    });
+}
+
+SILENT_EXPORT int silent_pyramid_p010_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_p010_frames* frames, int n_frames,
+                                          float* pyr, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return pyramid_p010(ctx, false, plan, frames, n_frames, pyr, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_p010_dev");
+}
+
+SILENT_EXPORT int silent_pyramid_p010(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_p010_frames* frames, int n_frames,
+                                      float* pyr) try {
+    NEED_CTX(ctx);
+    return pyramid_p010(ctx, true, plan, frames, n_frames, pyr, nullptr);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_p010");
+}
+
+// the converted frames themselves, [n_frames, H, W, 3] float32 (p010_to_rgb_kernel: the loaders' device functions)
+static int p010_to_rgb(silent_ctx* ctx, bool host, const silent_p010_frames* f, int n_frames, int H, int W, float* rgb, silent_stream stream) {
+    const char* who = "silent_p010_to_rgb";
+    size_t y_span = 0, uv_span = 0;
+    TRY(check_p010(ctx, who, true, H, W, f, n_frames, &y_span, &uv_span));
+    if (!rgb) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
+    const long long per_frame = ((long long)H * W + 255) / 256;
+    if (per_frame * n_frames > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many blocks for one launch");
+    auto launch = [&](const uint16_t* y, const uint16_t* uv, float* out, hipStream_t s) {
+        const P010 k = p010_frames(f, y, uv, n_frames);
+        hipLaunchKernelGGL(p010_to_rgb_kernel<3>, dim3((unsigned)(per_frame * n_frames)), dim3(256), 0, s, k, out, H, W, (int)per_frame);
+        (void)k;
+        return check_launch(ctx, who);
+    };
+    if (!host) return launch(f->y, f->uv, rgb, (hipStream_t)stream);
+    HostStage hs(ctx);
+    const int a = hs.in(f->y, y_span), b = hs.in(f->uv, uv_span), o = hs.out(rgb, (size_t)H * W * 3 * 4 * n_frames);
+    return hs.run([&] { return launch(hs.dev<uint16_t>(a), hs.dev<uint16_t>(b), hs.dev<float>(o), nullptr); });
+}
+
+SILENT_EXPORT int silent_p010_to_rgb_dev(silent_ctx* ctx, const silent_p010_frames* frames, int n_frames, int H, int W, float* rgb,
+                                         silent_stream stream) try {
+    NEED_CTX(ctx);
+    return p010_to_rgb(ctx, false, frames, n_frames, H, W, rgb, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_p010_to_rgb_dev");
+}
+
+SILENT_EXPORT int silent_p010_to_rgb(silent_ctx* ctx, const silent_p010_frames* frames, int n_frames, int H, int W, float* rgb) try {
+    NEED_CTX(ctx);
+    return p010_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
+} catch (...) {
+    return on_exception(ctx, "silent_p010_to_rgb");
 }

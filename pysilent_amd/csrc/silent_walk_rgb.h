@@ -220,6 +220,23 @@ __host__ __device__ __forceinline__ W3Nv12Load w3_nv12_load(const Walk3Args& arg
     const int x = w3_nv12_px(args, b.A, lane, k);
     return W3Nv12Load{r.y + nv12_y_col(x), r.uv + nv12_uv_col(x)};
 }
+// ---- and on P010 / P012 / P016 surfaces (FrameP010, silent_pyramid_p010): the same pixel per lane and load slot (w3_nv12_p0, the same
+// ring mapping), a 2-byte luma element and the 4-byte (U, V) pair -- byte columns 2 x and 4 (x >> 1) behind the same scalar row terms.
+// tests/rgb_p010_host_main.cpp enumerates them over whole launches (inside the spans, element-aligned, the crops covered).
+__host__ __device__ __forceinline__ int w3_p010_px(const Walk3Args& args, int A, int lane, int k) { return w3_nv12_px(args, A, lane, k); }
+__host__ __device__ __forceinline__ W3Nv12Row w3_p010_row(const Walk3Args& args, const FrameP010& v, const W3ViewBlock& b, int s) {
+    const Walk3Plan& p = args.plan[b.plan];
+    const long long yy = w3_mirror_near(b.y_first + s, p.src_h) + p.src_y0;
+    return W3Nv12Row{(long long)b.frame * v.y_frame_stride + yy * v.y_row_stride, (long long)b.frame * v.uv_frame_stride + (yy >> 1) * v.uv_row_stride};
+}
+// THE address function: two bytes at y_offset from `y` and four bytes at uv_offset from `uv` (both 2-byte aligned)
+__host__ __device__ __forceinline__ W3Nv12Load w3_p010_load(const Walk3Args& args, const FrameP010& v, int px, unsigned bid, int chunk, int row,
+                                                            int lane, int k) {
+    const W3ViewBlock b = w3_view_block(args, px, bid);
+    const W3Nv12Row r = w3_p010_row(args, v, b, chunk * kW3CH + row);
+    const int x = w3_p010_px(args, b.A, lane, k);
+    return W3Nv12Load{r.y + p010_y_col(x), r.uv + p010_uv_col(x)};
+}
 
 // FT: the frame element type -- float, or unsigned char (packed interleaved uint8 colour frames [n, H, W, 3], silent_pyramid_rgb8: byte c
 // of pixel (y, x) enters as (float)byte, an unsigned load and an exact conversion).  Only the LOADER touches the frame: the ring stays
@@ -233,12 +250,15 @@ __host__ __device__ __forceinline__ W3Nv12Load w3_nv12_load(const Walk3Args& arg
 // FT = FrameNv12 (NV12 surfaces, by value): a pixel per lane and load slot (w3_nv12_load), Y byte + (U, V) pair, converted by
 // nv12_channel with the coefficients in SGPRs, three ring floats written; the same issue / wait / barrier order as the byte loaders.
 // Every address is that of a luma byte or of the chroma pair of a pixel of the frame.
+// FT = FrameP010 (P010 / P012 / P016 surfaces, by value): the NV12 loader with uint16 elements (w3_p010_load) -- a 2-byte luma load and
+// the pair as one dword per slot, p010_values (shift, offsets) in front of the same nv12_channel; the depth is a runtime scalar.
 template <int G, int PX, typename FT = float>
 __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<FT> frames, float* __restrict__ pyr,
                                                                     const Walk3Args args, const WalkBorderArgs border) {
-    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT> || kFrameNv12<FT>,
-                  "float32, packed uint8 or strided uint8 colour frames, NV12 surfaces");
-    constexpr bool kNv = kFrameNv12<FT>;                             // the loader converts (Y, U, V) in registers
+    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT>,
+                  "float32, packed uint8 or strided uint8 colour frames, NV12 / P010 surfaces");
+    constexpr bool kP10 = kFrameP010<FT>;                            // (uint16 elements, the code in the high bits)
+    constexpr bool kNv = kFrameNv12<FT> || kP10;                     // the loader converts (Y, U, V) in registers
     constexpr bool kBytes = kFrameBytes<FT> || kFrameRgbView<FT>;   // the loader widens bytes in registers
     static_assert(G == stream_pad_levels(G), "row programs are padded to 4 or 7 levels");
     static_assert(PX == 36 || PX == 32 || PX == 28 || PX == 24, "");
@@ -283,6 +303,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
         typedef typename std::conditional<kFrameRgbSrc<FT>, unsigned char, FT>::type ET;   // element of a frame row
         const ET* __restrict__ src;
         if constexpr (kFrameRgbView<FT>) src = frames.data;    // (rows: w3_view_row)
+        else if constexpr (kP10) src = reinterpret_cast<const unsigned char*>(frames.y);   // (rows: w3_p010_row; strides are bytes)
         else if constexpr (kNv) src = frames.y;                // (rows: w3_nv12_row)
         else src = frames + (long long)frame * args.H * args.W * 3;
         const int rowf = args.W * 3;                           // floats (uint8 frames: bytes) of a FRAME row
@@ -332,12 +353,21 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                 // consumed; a smaller group reuses the registers and pays a latency per group (measured slower:
                 // profiles/rgb_nv12/README.md)
                 constexpr int kNvRows = SILENT_W3_NV_ROWS;
-                unsigned char nvy[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];
-                unsigned short nvc[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];
+                typename std::conditional<kP10, unsigned short, unsigned char>::type nvy[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];
+                typename std::conditional<kP10, unsigned, unsigned short>::type nvc[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];
                 (void)nvy;
                 (void)nvc;
                 auto nv_load = [&](int g, int r) {                // row g + r of the chunk into register row r
-                    if constexpr (kNv) {
+                    if constexpr (kP10) {
+                        const W3Nv12Row row = w3_p010_row(args, frames, vb, c * kW3CH + g + r);
+                        const unsigned char* yr = src + row.y;
+                        const unsigned char* cr = reinterpret_cast<const unsigned char*>(frames.uv) + row.uv;
+#pragma unroll
+                        for (int k = 0; k < kNvLoads; ++k) {
+                            __builtin_memcpy(&nvy[r][k], yr + p010_y_col(nvx[k]), 2);
+                            __builtin_memcpy(&nvc[r][k], cr + p010_uv_col(nvx[k]), 4);
+                        }
+                    } else if constexpr (kNv) {
                         const W3Nv12Row row = w3_nv12_row(args, frames, vb, c * kW3CH + g + r);
                         const unsigned char* yr = src + row.y;
                         const unsigned char* cr = frames.uv + row.uv;
@@ -397,8 +427,13 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                             float* row = &s_ring[slot * kW3CH + g + r][0];
 #pragma unroll
                             for (int k = 0; k < kNvLoads; ++k) {
-                                const float yv = __fsub_rn((float)nvy[r][k], frames.oy);
-                                const float uv = (float)((int)(nvc[r][k] & 0xffu) - 128), vv = (float)((int)(nvc[r][k] >> 8) - 128);
+                                float yv, uv, vv;
+                                if constexpr (kP10) {
+                                    p010_values(nvy[r][k], nvc[r][k], frames.oy, frames.oc, frames.shift, yv, uv, vv);
+                                } else {
+                                    yv = __fsub_rn((float)nvy[r][k], frames.oy);
+                                    uv = (float)((int)(nvc[r][k] & 0xffu) - 128), vv = (float)((int)(nvc[r][k] >> 8) - 128);
+                                }
                                 const int q = 3 * (lane + 64 * k) + nvd;     // ring float of channel 0
 #pragma unroll
                                 for (int ch = 0; ch < 3; ++ch)

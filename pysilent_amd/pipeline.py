@@ -159,7 +159,16 @@ class LineEndPipeline(object):
         # non-default frame_dtype / frame_channels / frame_layout, odd H or W
         self.rgb_frame_format = _runtime.check_rgb_frame_format(rgb_frame_format, mode, rgb_frame_dtype, rgb_frame_layout, frame_dtype,
                                                                 frame_channels, frame_layout, frame_hw)
-        self.nv12_m, self.nv12_oy = _runtime.nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
+        # rgb_frame_format="p010" / "p012" / "p016": the same pair as uint16 planes, as the decoders emit them for 10- and 12-bit
+        # streams -- the code value in the high 10 / 12 / 16 bits of each element (util.zoom.p010_planes) -- read in place by
+        # silent_pyramid_p010_dev; the converted channels are on the 0 .. 255 scale and NOT rounded, so the extra bits of a 10-bit source
+        # reach the pyramid; pyramid, maps and keypoints are those of the float32 pipeline on _runtime.p010_to_rgb(planes, depth=...),
+        # bit for bit.  The nv12_* keywords describe the conversion for these formats too (_runtime.p010_coefficients), and
+        # nv12_matrix="bt2020" exists for them only.
+        if self._p010:
+            self.nv12_m, self.nv12_oy, self.nv12_oc = _runtime.p010_coefficients(nv12_matrix, nv12_range, nv12_order, self._p010)
+        else:
+            self.nv12_m, self.nv12_oy = _runtime.nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
         # accumulation="float64" (mode "gray"): every op sums its taps in float64 and rounds once to float32, like the CPU oracle
         # (SILENT_PLAN_ACCUM_F64: the pyramid within 1 ulp of it, CS and end bit-identical to it on the same pyramid).  Checked first:
         # no GPU or torch work for a refused argument
@@ -340,6 +349,11 @@ class LineEndPipeline(object):
     def _synthetic_frames(self):
         """Noise frames of the dtype step() takes (the tuners' default batch)."""
         torch = self.torch
+        if self._p010:
+            h, w = self.frame_shape[:2]
+            sh = 16 - self._p010
+            return ((torch.randint(0, 1 << self._p010, (self.batch, h, w), device=self.tdev) << sh).to(torch.uint16),
+                    (torch.randint(0, 1 << self._p010, (self.batch, h // 2, w // 2, 2), device=self.tdev) << sh).to(torch.uint16))
         if self._nv12:
             h, w = self.frame_shape[:2]
             return (torch.randint(0, 256, (self.batch, h, w), device=self.tdev).to(torch.uint8),
@@ -586,7 +600,8 @@ class LineEndPipeline(object):
         ("uint16": 2 bytes) -- frame_shape[2] of them per pixel (3 for interleaved colour frames, whose pyramid and maps stay single-channel;
         mode "rgb" with rgb_frame_dtype="uint8" reports frame_dtype "uint8" and counts the same 1 byte per frame element; a strided
         view, frame_layout / rgb_frame_layout "strided", is read in place and counts the pixel bytes alone, not the bytes between them;
-        rgb_frame_format="nv12" counts 1.5 bytes per pixel: the luma byte and half a chroma pair)."""
+        rgb_frame_format="nv12" counts 1.5 bytes per pixel: the luma byte and half a chroma pair; "p010" / "p012" / "p016" 3 bytes per
+        pixel: the luma element and half a pair of elements)."""
         h, w, fc = self.frame_shape
         c = self.channels
         if self.crop_px is not None:
@@ -601,15 +616,22 @@ class LineEndPipeline(object):
 
     @property
     def _frame_bytes(self):
-        """Bytes per frame element as step() reads it (NV12: 1.5 bytes per pixel over the three channels)."""
+        """Bytes per frame element as step() reads it (NV12: 1.5 bytes per pixel over the three channels; P010: 3 bytes per pixel)."""
         if self._nv12:
             return 0.5
+        if self._p010:
+            return 1.0
         return {"uint8": 1, "uint16": 2}.get(self.frame_dtype, 4)
 
     @property
     def _nv12(self):
         """True for a mode "rgb" pipeline reading NV12 planes (rgb_frame_format="nv12")."""
         return getattr(self, "rgb_frame_format", "interleaved") == "nv12"
+
+    @property
+    def _p010(self):
+        """The depth (10, 12, 16) of a mode "rgb" pipeline reading P010 / P012 / P016 planes, None for every other pipeline."""
+        return _runtime.P010_DEPTHS.get(getattr(self, "rgb_frame_format", "interleaved"))
 
     @property
     def _frame_torch_dtype(self):
@@ -648,7 +670,9 @@ class LineEndPipeline(object):
                 "(top 10 % > NMS > value), cell-max / count / scan / write keypoint kernels"
                 + (", uint8 frames read in place (1 byte per frame element)" if getattr(self, "frame_dtype", "float32") == "uint8" else "")
                 + (", read in place from a strided view" if getattr(self, "rgb_frame_layout", "packed") == "strided" else "")
-                + (", NV12 read in place (Y + UV planes, 1.5 bytes per pixel, converted in registers)" if self._nv12 else ""))
+                + (", NV12 read in place (Y + UV planes, 1.5 bytes per pixel, converted in registers)" if self._nv12 else "")
+                + ((", %s read in place (uint16 Y + UV planes, 3 bytes per pixel, converted in registers)" % self.rgb_frame_format.upper())
+                   if self._p010 else ""))
 
     # -- launches --------------------------------------------------------------------------------------
     def _stream(self):
@@ -661,6 +685,14 @@ class LineEndPipeline(object):
             raise ValueError("frames must be a pair (y, uv) of uint8 GPU planes [%d, %d, %d] and [%d, %d, %d, 2]"
                              % ((self.batch,) + self.frame_shape[:2] + (self.batch, self.frame_shape[0] // 2, self.frame_shape[1] // 2)))
         return _lib.nv12_ptr(args)
+
+    def _p010_arg(self, frames):
+        """The const silent_p010_frames* of a pair (y, uv) of uint16 GPU planes of this pipeline's batch (refused: anything else)."""
+        args, n, dev = _runtime.p010_frames_of(frames, self.frame_shape[:2], self.nv12_m, self.nv12_oy, self.nv12_oc, self._p010)
+        if not dev or n != self.batch:
+            raise ValueError("frames must be a pair (y, uv) of uint16 GPU planes [%d, %d, %d] and [%d, %d, %d, 2]"
+                             % ((self.batch,) + self.frame_shape[:2] + (self.batch, self.frame_shape[0] // 2, self.frame_shape[1] // 2)))
+        return _lib.p010_ptr(args)
 
     def _check_frames(self, frames):
         if getattr(self, "rgb_frame_layout", "packed") == "strided":
@@ -687,6 +719,10 @@ class LineEndPipeline(object):
         return frame_ptr(frames.data_ptr())
 
     def run_pyramid(self, frames, stream=None):
+        if self._p010:                                               # (mode "rgb", rgb_frame_format "p010" / "p012" / "p016")
+            self.ctx.check(self._lib.silent_pyramid_p010_dev(self.ctx.handle, self.plan.handle, self._p010_arg(frames), self.batch,
+                                                             C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
+            return
         if self._nv12:                                               # (mode "rgb", rgb_frame_format="nv12"; the planes: _nv12_arg)
             self.ctx.check(self._lib.silent_pyramid_nv12_dev(self.ctx.handle, self.plan.handle, self._nv12_arg(frames), self.batch,
                                                              C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
@@ -880,7 +916,7 @@ class LineEndPipeline(object):
         no cast launch and no float32 frame buffer.  A frame_dtype="uint16" pipeline likewise takes uint16 host frames only, and a
         mode "rgb" pipeline with rgb_frame_dtype="uint8" uint8 host frames [batch, H, W, 3] only."""
         torch = self.torch
-        if self._nv12:
+        if self._nv12 or self._p010:
             return self._step_host_nv12(frames)
         if isinstance(frames, np.ndarray):
             src = torch.from_numpy(np.ascontiguousarray(frames))
@@ -957,15 +993,18 @@ class LineEndPipeline(object):
         torch = self.torch
         h, w = self.frame_shape[:2]
         shapes = ((self.batch, h, w), (self.batch, h // 2, w // 2, 2))
+        # (rgb_frame_format "p010" / "p012" / "p016": the same ring with uint16 planes)
+        np_dtype, t_dtype = (np.uint16, torch.uint16) if self._p010 else (np.uint8, torch.uint8)
         if not isinstance(frames, (tuple, list)) or len(frames) != 2 or any(
-                not isinstance(p, np.ndarray) or p.dtype != np.uint8 or tuple(p.shape) != sh for p, sh in zip(frames, shapes)):
-            raise ValueError("step_host of an rgb_frame_format='nv12' pipeline takes a pair of uint8 arrays of shapes %s and %s" % shapes)
+                not isinstance(p, np.ndarray) or p.dtype != np_dtype or tuple(p.shape) != sh for p, sh in zip(frames, shapes)):
+            raise ValueError("step_host of an rgb_frame_format=%r pipeline takes a pair of %s arrays of shapes %s and %s"
+                             % ((self.rgb_frame_format, np.dtype(np_dtype).name) + shapes))
         cs = self._copy_stream_of_the_ingest()
         ring = self._ingest.setdefault("nv12", {"slots": [], "next": 0})
         if not ring["slots"]:
             for _ in range(2):
-                ring["slots"].append({"pinned": [torch.empty(sh, dtype=torch.uint8, pin_memory=True) for sh in shapes],
-                                      "raw": [torch.empty(sh, dtype=torch.uint8, device=self.tdev) for sh in shapes],
+                ring["slots"].append({"pinned": [torch.empty(sh, dtype=t_dtype, pin_memory=True) for sh in shapes],
+                                      "raw": [torch.empty(sh, dtype=t_dtype, device=self.tdev) for sh in shapes],
                                       "h2d_done": torch.cuda.Event(), "raw_free": None})
         slot = ring["slots"][ring["next"]]
         ring["next"] ^= 1
