@@ -402,6 +402,56 @@ int silent_pyramid_p010_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, co
 int silent_p010_to_rgb(silent_ctx* ctx, const silent_p010_frames* frames, int n_frames, int H, int W, float* rgb);
 int silent_p010_to_rgb_dev(silent_ctx* ctx, const silent_p010_frames* frames, int n_frames, int H, int W, float* rgb, silent_stream stream);
 
+/* Planar and packed 8-bit YUV for 3-CHANNEL plans, read in place: what software decoders (I420 / YV12), GPU JPEG decoders (planar
+ * 4:2:2 / 4:4:4), UVC webcams (YUYV / UYVY) and Android / capture cards (NV21) emit.  These formats differ from NV12 in ADDRESSING
+ * only, so one struct describes them all: three plane pointers (they may overlap: a packed format is three views of one buffer; they
+ * are only read), a pixel stride per plane class, a chroma subsampling shift per axis (0 or 1).  Strides are in BYTES, 64-bit.  With
+ * sx = chroma_shift_x, sy = chroma_shift_y, pixel (y, x) of frame f reads the three bytes
+ *     Y = y[f y_frame_stride + y y_row_stride + x y_pixel_stride]
+ *     U = u[f c_frame_stride + (y >> sy) c_row_stride + (x >> sx) c_pixel_stride]        V = v[the same offset]
+ * and the value of channel k in {0, 1, 2} is
+ *     Yv = (float)Y - oy       Uv = (float)U - 128       Vv = (float)V - 128
+ *     c_k = min(max((Yv * m[3 k] + Uv * m[3 k + 1]) + Vv * m[3 k + 2], 0), 255)
+ * -- NV12's conversion to the letter: every product and sum a SEPARATELY ROUNDED float32 operation (no fused multiply-add), chroma
+ * NEAREST, NO rounding to an integer.
+ *     I420 / YV12: three planes, shifts 1 / 1 (YV12: u and v swapped)      I422, I444, 4:4:0: shifts 1 / 0, 0 / 0, 0 / 1
+ *     NV12: u = uv, v = uv + 1, c_pixel_stride = 2      NV21: v = vu, u = vu + 1      NV16 / NV24: the same with shifts 1 / 0, 0 / 0
+ *     YUYV: y = base, y_pixel_stride = 2, u = base + 1, v = base + 3, c_pixel_stride = 4, shifts 1 / 0 (UYVY: y = base + 1, u = base, v = base + 2)
+ *     VUYA / AYUV: all pixel strides 4, shifts 0 / 0
+ * The conversion happens in registers at the kernels' loads.  pyr is IDENTICAL, bit for bit, to silent_pyramid[_dev] on the frames
+ * silent_yuv_to_rgb[_dev] writes for the same struct, on every route: the walk kernel, union plans with their border blocks (inside
+ * and behind the walk's launch), per-level plans, the unit + region kernels, every SILENT_TUNE_PYRAMID value.  A struct that IS NV12
+ * (y_pixel_stride == 1, c_pixel_stride == 2, v == u + 1, shifts 1 / 1) runs the kernels of silent_pyramid_nv12 and gives its bits.
+ * Reads: every load is ONE BYTE that is some pixel's Y, U or V -- no pair loads, no dword loads; nothing between pixels is ever read
+ * and nothing outside the three spans, the span of a plane being (n - 1) frame_stride + (rows - 1) row_stride + (cols - 1)
+ * pixel_stride + 1 with rows x cols = H x W for y and (H >> sy) x (W >> sx) for u and v.  (The NV12 kernels read the (U, V) bytes of a
+ * pixel as one pair: the same bytes.)  A frame stride is not read when n_frames == 1.
+ * Refusals, in this order: a NULL ctx; SILENT_E_INVALID for a NULL plan / struct / y / u / v, a shift other than 0 or 1, an odd H with
+ * chroma_shift_y = 1 or an odd W with chroma_shift_x = 1 (or H, W < 1), a pixel stride < 1, a row stride below its plane's row extent
+ * (cols - 1) pixel_stride + 1, a frame stride below its plane's extent (n_frames > 1), a span above 2^63 - 1 bytes, a non-finite m or
+ * oy; then a NULL pyr / rgb, a plan of another context, n_frames < 1 (SILENT_E_INVALID) and a single-channel plan
+ * (SILENT_E_UNSUPPORTED: such a plan reads the luma plane through silent_pyramid_view).
+ * The host forms refuse everything their _dev forms refuse before anything is staged, and stage the UNION of the three spans: the
+ * intervals sorted, those that overlap or touch merged, each merged interval copied once, the pointers rebased -- a YUYV buffer
+ * crosses the bus once, not three times.  The _dev forms are stream-ordered and asynchronous; the struct is dead at return.
+ * silent_yuv_to_rgb[_dev] writes the converted frames themselves, [n_frames, H, W, 3] float32, with the same device functions, one
+ * thread per pixel; H and W are arguments, refusals as above under its own name.  (ABI additions only: SILENT_ABI_VERSION is unchanged.) */
+typedef struct silent_yuv_frames {
+    const uint8_t* y;
+    const uint8_t* u;
+    const uint8_t* v;
+    int64_t y_pixel_stride, y_row_stride, y_frame_stride;
+    int64_t c_pixel_stride, c_row_stride, c_frame_stride;
+    int32_t chroma_shift_x, chroma_shift_y;
+    float m[9];
+    float oy;
+} silent_yuv_frames;
+int silent_pyramid_yuv(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_yuv_frames* frames, int n_frames, float* pyr);
+int silent_pyramid_yuv_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_yuv_frames* frames, int n_frames, float* pyr,
+                           silent_stream stream);
+int silent_yuv_to_rgb(silent_ctx* ctx, const silent_yuv_frames* frames, int n_frames, int H, int W, float* rgb);
+int silent_yuv_to_rgb_dev(silent_ctx* ctx, const silent_yuv_frames* frames, int n_frames, int H, int W, float* rgb, silent_stream stream);
+
 /* uint16 frames, read as they are: 10 / 12 / 16-bit machine-vision and scientific cameras (Mono10 / Mono12 / Mono16), thermal and
  * depth sensors (Y16, Z16), 16-bit TIFF / PNG, and the luma of the P010 / P016 surfaces a hardware decoder hands over for 10-bit
  * HEVC / AV1.  The twins of the *_u8 entry points -- same argument lists, maps_f16 / parts / stream arguments, status codes and order

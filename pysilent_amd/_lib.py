@@ -93,6 +93,16 @@ class P010Frames(C.Structure):
                 ("shift", C.c_int)]
 
 
+class YuvFrames(C.Structure):
+    """silent_yuv_frames (include/silent_hip.h): a planar / packed 8-bit YUV batch -- three plane pointers, the luma plane's pixel /
+    row / frame strides and those the two chroma planes share (BYTES), the chroma shifts per axis, the 3 x 3 conversion matrix (row k:
+    output channel k) and the luma offset."""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p),
+                ("y_pixel_stride", C.c_int64), ("y_row_stride", C.c_int64), ("y_frame_stride", C.c_int64),
+                ("c_pixel_stride", C.c_int64), ("c_row_stride", C.c_int64), ("c_frame_stride", C.c_int64),
+                ("chroma_shift_x", C.c_int32), ("chroma_shift_y", C.c_int32), ("m", C.c_float * 9), ("oy", C.c_float)]
+
+
 class SilentLibraryError(RuntimeError):
     """libsilent_hip.so is missing or cannot be loaded."""
 
@@ -108,6 +118,7 @@ _sp = C.POINTER(C.c_uint16)   # uint16 frames (the *_u16 entry points); short_pt
 _xp = C.POINTER(FrameView16)  # a strided uint16 view (the *_view16 entry points); view16_ptr() makes one from frame_view_of's tuple
 _np = C.POINTER(Nv12Frames)   # an NV12 batch (silent_pyramid_nv12, silent_nv12_to_rgb); nv12_ptr() makes one from _runtime.nv12_frames_of's tuple
 _pp = C.POINTER(P010Frames)   # a P010 batch (silent_pyramid_p010, silent_p010_to_rgb); p010_ptr() makes one from _runtime.p010_frames_of's tuple
+_yp = C.POINTER(YuvFrames)    # a planar / packed YUV batch (silent_pyramid_yuv, silent_yuv_to_rgb); yuv_ptr() makes one from _runtime.yuv_frames_of's tuple
 _ep = C.POINTER(Extent)
 _i, _u, _f, _d, _sz = C.c_int, C.c_uint, C.c_float, C.c_double, C.c_size_t
 
@@ -157,6 +168,10 @@ _SIGNATURES = {
     "silent_pyramid_p010_dev": [_vp, _vp, _pp, _i, _fp, _vp],
     "silent_p010_to_rgb": [_vp, _pp, _i, _i, _i, _fp],
     "silent_p010_to_rgb_dev": [_vp, _pp, _i, _i, _i, _fp, _vp],
+    "silent_pyramid_yuv": [_vp, _vp, _yp, _i, _fp],
+    "silent_pyramid_yuv_dev": [_vp, _vp, _yp, _i, _fp, _vp],
+    "silent_yuv_to_rgb": [_vp, _yp, _i, _i, _i, _fp],
+    "silent_yuv_to_rgb_dev": [_vp, _yp, _i, _i, _i, _fp, _vp],
     "silent_gray_pass_u8": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8x3": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8_dev": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i, _u, _vp],
@@ -298,6 +313,17 @@ def p010_ptr(frames):
     y, uv, yr, yf, ur, uf, m, oy, oc, shift = frames
     return C.pointer(P010Frames(int(y), int(uv), int(yr), int(yf), int(ur), int(uf), (C.c_float * 9)(*[float(v) for v in m]), float(oy),
                                 float(oc), int(shift)))
+
+
+def yuv_ptr(frames):
+    """(y, u, v addresses, y_pixel_stride, y_row_stride, y_frame_stride, c_pixel_stride, c_row_stride, c_frame_stride, chroma_shift_x,
+    chroma_shift_y, m, oy) -- what _runtime.yuv_frames_of returns -- as the const silent_yuv_frames* of the YUV entry points (None:
+    NULL).  The struct is read before the call returns."""
+    if frames is None:
+        return None
+    y, u, v, yp, yr, yf, cp, cr, cf, sx, sy, m, oy = frames
+    return C.pointer(YuvFrames(int(y), int(u), int(v), int(yp), int(yr), int(yf), int(cp), int(cr), int(cf), int(sx), int(sy),
+                               (C.c_float * 9)(*[float(c) for c in m]), float(oy)))
 
 
 def gray_entry(family, frame_dtype="float32", frame_channels=1, storage="float32", dev=False, parts=None, frame_layout="packed"):

@@ -981,6 +981,8 @@ def check_rgb_frame_layout(rgb_frame_layout, mode="rgb", rgb_frame_dtype="float3
 
 
 RGB_FRAME_FORMATS = ("interleaved", "nv12", "p010", "p012", "p016")
+# and the formats that take a (y, u, v) triple: rgb_frame_format -> chroma shifts (x, y)
+YUV_SHIFTS = {"yuv420": (1, 1), "yuv422": (1, 0), "yuv444": (0, 0)}
 NV12_MATRICES = {"bt601": (.299, .114), "bt709": (.2126, .0722)}      # (Kr, Kb)
 NV12_RANGES = ("limited", "full")
 NV12_ORDERS = ("bgr", "rgb")
@@ -995,10 +997,13 @@ def check_rgb_frame_format(rgb_frame_format, mode="rgb", rgb_frame_dtype="float3
     interleaved chroma [n, H / 2, W / 2, 2], both pitched -- read in place by silent_pyramid_nv12 and converted to three float32
     channels in registers: no conversion launch, no copy of the batch; the pyramid is that of the float32 path on the converted
     frames bit for bit) or "p010" / "p012" / "p016" (the same pair as uint16 planes, the 10 / 12 / 16-bit code in the high bits of
-    each element: silent_pyramid_p010).  The name is checked first; then the mode; then that the format is not combined with
-    rgb_frame_dtype="uint8", rgb_frame_layout="strided" or the gray frame_* keywords; then that H and W (hw, when given) are even."""
-    if not isinstance(rgb_frame_format, str) or rgb_frame_format not in RGB_FRAME_FORMATS:
-        raise ValueError("rgb_frame_format must be 'interleaved' or 'nv12', or 'p010' / 'p012' / 'p016', got %r" % (rgb_frame_format,))
+    each element: silent_pyramid_p010) or "yuv420" / "yuv422" / "yuv444" (a triple (y, u, v) of uint8 views of ANY positive strides --
+    planar I420 / YV12 / I422 / I444, semi-planar NV12 / NV21 / NV16, packed YUYV / UYVY / VUYA: the layout lives in the strides, the
+    name gives the chroma subsampling -- read in place by silent_pyramid_yuv).  The name is checked first; then the mode; then that the format is not combined with
+    rgb_frame_dtype="uint8", rgb_frame_layout="strided" or the gray frame_* keywords; then that H and W (hw, when given) are even ("yuv422": W; "yuv444": nothing)."""
+    if not isinstance(rgb_frame_format, str) or rgb_frame_format not in RGB_FRAME_FORMATS + tuple(YUV_SHIFTS):
+        raise ValueError("rgb_frame_format must be 'interleaved' or 'nv12', or 'p010' / 'p012' / 'p016', or 'yuv420' / 'yuv422' / "
+                         "'yuv444', got %r" % (rgb_frame_format,))
     if rgb_frame_format != "interleaved":
         name = "rgb_frame_format=%r" % (rgb_frame_format,)
         wide = rgb_frame_format in P010_DEPTHS
@@ -1017,7 +1022,12 @@ def check_rgb_frame_format(rgb_frame_format, mode="rgb", rgb_frame_dtype="float3
                              % (name, frame_channels))
         if frame_layout != "packed":
             raise ValueError("%s does not combine with frame_layout=%r (frame_layout describes the frames of mode 'gray')" % (name, frame_layout))
-        if hw is not None and (int(hw[0]) % 2 or int(hw[1]) % 2 or min(int(hw[0]), int(hw[1])) < 2):
+        if rgb_frame_format in YUV_SHIFTS:
+            sx, sy = YUV_SHIFTS[rgb_frame_format]
+            if hw is not None and ((sy and int(hw[0]) % 2) or (sx and int(hw[1]) % 2) or min(int(hw[0]), int(hw[1])) < 1):
+                raise ValueError("%s needs even %s, got %s" % (name, "H and W (4:2:0 chroma)" if sy else "W (4:2:2 chroma)",
+                                                              tuple(int(v) for v in hw)))
+        elif hw is not None and (int(hw[0]) % 2 or int(hw[1]) % 2 or min(int(hw[0]), int(hw[1])) < 2):
             raise ValueError("%s needs even H and W (4:2:0 chroma), got %s" % (name, tuple(int(v) for v in hw)))
     return rgb_frame_format
 
@@ -1227,6 +1237,90 @@ def p010_to_rgb(planes, hw, depth=10, nv12_matrix="bt709", nv12_range="limited",
     return out
 
 
+def yuv_frames_of(planes, hw, fmt, m, oy):
+    """A triple (y, u, v) of uint8 planes -- all ndarrays or all GPU tensors; y [n, H, W], u and v [n, H >> sy, W >> sx] with (sx, sy)
+    = YUV_SHIFTS[fmt]; each ANY view with positive strides (the layout lives in the strides: yuyv[:, :, 0::2], yuyv[:, :, 1::4],
+    yuyv[:, :, 3::4] is a valid triple), u and v with EQUAL strides -- as what _lib.yuv_ptr takes: (y, u, v addresses, y_pixel_stride,
+    y_row_stride, y_frame_stride, c_pixel_stride, c_row_stride, c_frame_stride (BYTES), sx, sy, m, oy).  Returns (that tuple, n,
+    on_device).  Nothing is converted or copied."""
+    if fmt not in YUV_SHIFTS:
+        raise ValueError("fmt must be 'yuv420', 'yuv422' or 'yuv444', got %r" % (fmt,))
+    sx, sy = YUV_SHIFTS[fmt]
+    if not isinstance(planes, (tuple, list)) or len(planes) != 3:
+        raise ValueError("YUV frames are a triple (y, u, v) of uint8 planes")
+    y, u, v = planes
+    dev = is_torch_tensor(y)
+    if not (dev and is_torch_tensor(u) and is_torch_tensor(v)) and not all(isinstance(p, np.ndarray) for p in planes):
+        raise TypeError(TYPE_ERROR_MESSAGE)
+    h, w = int(hw[0]), int(hw[1])
+
+    def geometry(p):
+        if dev:
+            import torch
+            if p.dtype != torch.uint8 or not p.is_cuda:
+                raise ValueError("YUV planes must be uint8 GPU tensors or uint8 ndarrays (nothing is converted), got %s" % (p.dtype,))
+            return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.stride()), int(p.data_ptr())
+        if p.dtype != np.uint8:
+            raise ValueError("YUV planes must be uint8 GPU tensors or uint8 ndarrays (nothing is converted), got %s" % (p.dtype,))
+        return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.strides), int(p.ctypes.data)
+
+    ys, yst, ya = geometry(y)
+    us, ust, ua = geometry(u)
+    vs, vst, va = geometry(v)
+    if len(ys) != 3 or ys[1:] != (h, w) or ys[0] < 1:
+        raise ValueError("the YUV luma plane must be [n, %d, %d], got %s" % (h, w, ys))
+    n = ys[0]
+    ch, cw = h >> sy, w >> sx
+    if us != (n, ch, cw) or vs != (n, ch, cw):
+        raise ValueError("the %s chroma planes must be [%d, %d, %d], got %s and %s" % (fmt, n, ch, cw, us, vs))
+
+    def strides(st, rows, cols):
+        # (a stride of an axis of extent 1 is never used: the smallest legal value stands in for it)
+        px = st[2] if cols > 1 else 1
+        row = st[1] if rows > 1 else (cols - 1) * px + 1
+        frame = st[0] if n > 1 else (rows - 1) * row + (cols - 1) * px + 1
+        return px, row, frame
+
+    yp, yr, yf = strides(yst, h, w)
+    cp, cr, cf = strides(ust, ch, cw)
+    if strides(vst, ch, cw) != (cp, cr, cf):
+        raise ValueError("YUV planes: u and v must have equal strides, got %s and %s" % (ust, vst))
+    if min(yp, cp) < 1 or yr < (w - 1) * yp + 1 or cr < (cw - 1) * cp + 1 or yf < (h - 1) * yr + (w - 1) * yp + 1 \
+            or cf < (ch - 1) * cr + (cw - 1) * cp + 1:
+        raise ValueError("YUV planes: rows or frames overlap, or a stride is not positive (strides %s, %s)" % (yst, ust))
+    return (ya, ua, va, yp, yr, yf, cp, cr, cf, sx, sy, [float(c) for c in np.asarray(m, np.float32).reshape(9)], float(oy)), n, dev
+
+
+class _YuvOperand(_Nv12Operand):
+    """A planar / packed YUV batch (yuv_frames_of) as an operand (see _Nv12Operand)."""
+
+    def __init__(self, planes, hw, fmt, m, oy, ctx=None):
+        args, self.n_frames, self.dev = yuv_frames_of(planes, hw, fmt, m, oy)
+        self.packed, self.c, self.extents = False, 3, [(int(hw[0]), int(hw[1]))]
+        self.device = self.stream = None
+        if self.dev:
+            import torch
+            self._torch_device = planes[0].device
+            self.device = self._torch_device.index or 0
+            self.stream = C.c_void_p(torch.cuda.current_stream(self._torch_device).cuda_stream)
+        self.ptr = _lib.yuv_ptr(args)
+        self.buf = tuple(planes)                        # keep alive
+        self.ctx = ctx or get_context(self.device)
+
+
+def yuv_to_rgb(planes, hw, fmt="yuv420", nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", device=None):
+    """The float32 frames [n, H, W, 3] the pyramid kernels see for a (y, u, v) triple of format ``fmt`` ("yuv420" / "yuv422" /
+    "yuv444"; silent_yuv_to_rgb[_dev]: the loaders' own device function, one thread per pixel) -- for display, and as the reference
+    of the bit-identity contract.  planes: yuv_frames_of; the conversion: nv12_coefficients."""
+    m, oy = nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
+    check_rgb_frame_format(fmt, hw=hw)
+    op = _YuvOperand(planes, hw, fmt, m, oy, None if device is None else get_context(device))
+    h, w = int(hw[0]), int(hw[1])
+    out, optr = op.empty((op.n_frames, h, w, 3))
+    op.call("yuv_to_rgb", op.ptr, op.n_frames, h, w, optr)
+    return out
+
+
 class PyramidPlan(object):
     """Tap tables of one (frame size, level geometry) on the device.  ``levels`` is a list of dicts / tuples
     (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w).  accumulation="float64" (single-channel plans): every op of
@@ -1302,7 +1396,9 @@ class PyramidPlan(object):
         uint8 view [n, H, W, 3] with positive strides and channel stride 1, read in place (silent_pyramid_rgb8_view), the pyramid of the
         packed uint8 call on the compacted view bit for bit.  rgb_frame_format="nv12" (3-channel plans): frames is a pair (y, uv) of
         uint8 planes (nv12_frames_of) read in place and converted in registers (silent_pyramid_nv12; nv12_coefficients), the pyramid
-        of the float32 call on nv12_to_rgb(frames) bit for bit."""
+        of the float32 call on nv12_to_rgb(frames) bit for bit.  rgb_frame_format="yuv420" / "yuv422" / "yuv444": frames is a triple
+        (y, u, v) of uint8 views of any positive strides (yuv_frames_of; silent_pyramid_yuv), the pyramid of the float32 call on
+        yuv_to_rgb(frames, hw, fmt) bit for bit."""
         mode = "gray" if self.frame_shape[2] == 1 else "rgb"
         fmt = check_rgb_frame_format(rgb_frame_format, mode, rgb_frame_dtype, rgb_frame_layout, frame_dtype, frame_channels, frame_layout,
                                      self.frame_shape[:2])
@@ -1313,6 +1409,14 @@ class PyramidPlan(object):
             op = _P010Operand(frames, self.frame_shape[:2], m, oy, oc, P010_DEPTHS[fmt], self.ctx)
             out, optr = op.empty(op.n_frames * self.frame_px * 3)
             op.call("pyramid_p010", self.handle, op.ptr, op.n_frames, optr)
+            return PackedPyramid(out, self.extents, 3, op.n_frames)
+        if fmt in YUV_SHIFTS:
+            # "yuv420" / "yuv422" / "yuv444": a triple (y, u, v) of uint8 views of any positive strides (yuv_frames_of), read in place
+            # (silent_pyramid_yuv; nv12_coefficients), the pyramid of the float32 call on yuv_to_rgb(frames) bit for bit
+            m, oy = nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
+            op = _YuvOperand(frames, self.frame_shape[:2], fmt, m, oy, self.ctx)
+            out, optr = op.empty(op.n_frames * self.frame_px * 3)
+            op.call("pyramid_yuv", self.handle, op.ptr, op.n_frames, optr)
             return PackedPyramid(out, self.extents, 3, op.n_frames)
         if fmt == "nv12":
             m, oy = nv12_coefficients(nv12_matrix, nv12_range, nv12_order)

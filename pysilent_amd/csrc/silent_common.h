@@ -291,9 +291,23 @@ struct FrameP010 {
 };
 template <typename FT>
 constexpr bool kFrameP010 = std::is_same<FT, FrameP010>::value;
-// the 3-channel kinds that are read through a `src` struct with at(y, x, ch) / atf(y, i) (strided colour views, NV12 and P010 surfaces)
+// planar and packed 8-bit YUV (silent_pyramid_yuv): three byte planes, a pixel stride per plane class, a chroma shift per axis (below)
+struct FrameYuv {
+    const unsigned char* y;
+    const unsigned char* u;
+    const unsigned char* v;
+    long long y_pixel_stride, y_row_stride, y_frame_stride;   // bytes
+    long long c_pixel_stride, c_row_stride, c_frame_stride;   // bytes; shared by u and v
+    int sx, sy;                                               // chroma subsampling shifts, 0 or 1 each
+    float m[9];
+    float oy;
+};
 template <typename FT>
-constexpr bool kFrameRgbSrc = kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT>;
+constexpr bool kFrameYuv = std::is_same<FT, FrameYuv>::value;
+// the 3-channel kinds that are read through a `src` struct with at(y, x, ch) / atf(y, i) (strided colour views, NV12, P010 and YUV
+// surfaces)
+template <typename FT>
+constexpr bool kFrameRgbSrc = kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT> || kFrameYuv<FT>;
 __device__ __forceinline__ float nv12_channel(float yv, float uv, float vv, float m0, float m1, float m2) {
     return fminf(fmaxf(__fadd_rn(__fadd_rn(__fmul_rn(yv, m0), __fmul_rn(uv, m1)), __fmul_rn(vv, m2)), 0.0f), 255.0f);
 }
@@ -411,11 +425,72 @@ __device__ __forceinline__ P010Src frame_of(const FrameP010& f, int frame) {
     return s;
 }
 
+// Planar and packed 8-bit YUV (silent_pyramid_yuv, 3-channel plans only): what differs from NV12 is ADDRESSING alone -- which byte
+// holds a pixel's Y, U and V.  One kind for the family (I420 / YV12 / I422 / I444 / NV12 / NV21 / NV16 / NV24 / YUYV / UYVY / VUYA):
+// three plane pointers (they may point into one buffer), a pixel stride per plane class and a chroma shift per axis.  Pixel (f, y, x):
+//     Y = y[f y_frame_stride + y y_row_stride + x y_pixel_stride]     U = u[f c_frame_stride + (y >> sy) c_row_stride + (x >> sx) c_pixel_stride]
+//     V = v[the offset of U]
+//     Yv = (float)Y - oy,  Uv = (float)U - 128,  Vv = (float)V - 128,  c_k = nv12_channel(Yv, Uv, Vv, row k of m)
+// -- NV12's words to the letter (nv12_channel stays THE conversion; chroma nearest; no rounding to an integer).  Every load is ONE BYTE
+// that is some pixel's Y, U or V: no pair and no dword loads, so nothing between the pixels of a packed format is ever read.
+// byte offsets of pixel column x inside a luma row and inside a chroma row
+__host__ __device__ __forceinline__ long long yuv_y_col(long long x, long long y_pixel_stride) { return x * y_pixel_stride; }
+__host__ __device__ __forceinline__ long long yuv_c_col(long long x, int sx, long long c_pixel_stride) { return (x >> sx) * c_pixel_stride; }
+// one frame of such a batch inside a kernel
+struct YuvSrc {
+    const unsigned char* y;
+    const unsigned char* u;
+    const unsigned char* v;
+    long long y_pixel_stride, y_row_stride, c_pixel_stride, c_row_stride;
+    int sx, sy;
+    float m[9];
+    float oy;
+    // the (Y, U, V) of pixel (x, y), offsets removed: three byte loads
+    __device__ __forceinline__ void yuv(long long yy, long long x, float& yv, float& uvv, float& vv) const {
+        const long long c = (yy >> sy) * c_row_stride + yuv_c_col(x, sx, c_pixel_stride);
+        yv = __fsub_rn((float)y[yy * y_row_stride + yuv_y_col(x, y_pixel_stride)], oy);
+        uvv = (float)((int)u[c] - 128);
+        vv = (float)((int)v[c] - 128);
+    }
+    // channel ch of pixel (x, y) / float i of the virtual packed row y (coefficients selected as values: Nv12Src::at)
+    __device__ __forceinline__ float at(long long yy, long long x, int ch) const {
+        float yv, uvv, vv;
+        yuv(yy, x, yv, uvv, vv);
+        const float a0 = m[0], a1 = m[1], a2 = m[2], b0 = m[3], b1 = m[4], b2 = m[5], c0 = m[6], c1 = m[7], c2 = m[8];
+        return nv12_channel(yv, uvv, vv, ch == 0 ? a0 : (ch == 1 ? b0 : c0), ch == 0 ? a1 : (ch == 1 ? b1 : c1), ch == 0 ? a2 : (ch == 1 ? b2 : c2));
+    }
+    __device__ __forceinline__ float atf(long long yy, long long i) const {
+        const long long p = i / 3;
+        return at(yy, p, (int)(i - 3 * p));
+    }
+};
+template <>
+struct FrameKind<FrameYuv> {
+    typedef FrameYuv param;
+    typedef YuvSrc src;
+};
+__device__ __forceinline__ YuvSrc frame_of(const FrameYuv& f, int frame) {
+    YuvSrc s;
+    s.y = f.y + (long long)frame * f.y_frame_stride;
+    s.u = f.u + (long long)frame * f.c_frame_stride;
+    s.v = f.v + (long long)frame * f.c_frame_stride;
+    s.y_pixel_stride = f.y_pixel_stride;
+    s.y_row_stride = f.y_row_stride;
+    s.c_pixel_stride = f.c_pixel_stride;
+    s.c_row_stride = f.c_row_stride;
+    s.sx = f.sx;
+    s.sy = f.sy;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) s.m[i] = f.m[i];
+    s.oy = f.oy;
+    return s;
+}
+
 // the frame types that exist for single-channel plans with float32 accumulation only
 template <typename FT>
 constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT> || kFrameWords<FT> || kFrameStrided<FT>;
 template <typename FT>
-constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT>;
+constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT> || kFrameYuv<FT>;
 // (host) the bytes of one frame pixel as the host-pointer forms stage it -- float frames carry the channels of the plan; a view is
 // staged by its span -- and the suffix of a frame type's entry points
 template <typename FT>
@@ -452,6 +527,11 @@ __device__ __forceinline__ float unit_edge_column(const Nv12Src& src, int ch, in
 }
 // and of a P010 surface
 __device__ __forceinline__ float unit_edge_column(const P010Src& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
+                                                  int src_h, int src_y0, int lane) {
+    return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
+}
+// and of a planar / packed YUV batch
+__device__ __forceinline__ float unit_edge_column(const YuvSrc& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
                                                   int src_h, int src_y0, int lane) {
     return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
 }

@@ -183,6 +183,110 @@ inline P010 p010_frames(const silent_p010_frames* v, const uint16_t* y, const ui
     s.shift = v->shift;
     return s;
 }
+// Planar / packed 8-bit YUV (silent_pyramid_yuv, silent_yuv_to_rgb; silent_hip.h).  check_yuv: what the struct refuses on its own for
+// frames of H x W, in the header's order, and the spans of the luma plane and of a chroma plane (u and v share it) in bytes.
+using Yuv = silent::FrameYuv;
+inline int check_yuv(silent_ctx* ctx, const char* who, bool has_plan, long long H, long long W, const silent_yuv_frames* v, int n_frames,
+                     size_t* y_span, size_t* c_span) {
+    if (!has_plan || !v || !v->y || !v->u || !v->v) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    const int sx = v->chroma_shift_x, sy = v->chroma_shift_y;
+    if ((sx != 0 && sx != 1) || (sy != 0 && sy != 1)) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a chroma shift must be 0 or 1");
+    if (H < 1 || W < 1 || (sy && (H & 1)) || (sx && (W & 1)))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a subsampled axis needs an even extent (H for chroma_shift_y = 1, W for chroma_shift_x = 1)");
+    if (v->y_pixel_stride < 1 || v->c_pixel_stride < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a pixel stride is below 1");
+    typedef unsigned __int128 u128;
+    const long long ch = H >> sy, cw = W >> sx;
+    const u128 yrow = (u128)(W - 1) * (u128)v->y_pixel_stride + 1, crow = (u128)(cw - 1) * (u128)v->c_pixel_stride + 1;
+    if (v->y_row_stride <= 0 || (u128)v->y_row_stride < yrow)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_row_stride is below (W - 1) * y_pixel_stride + 1");
+    if (v->c_row_stride <= 0 || (u128)v->c_row_stride < crow)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": c_row_stride is below ((W >> sx) - 1) * c_pixel_stride + 1");
+    const u128 yf = (u128)(H - 1) * (u128)v->y_row_stride + yrow, cf = (u128)(ch - 1) * (u128)v->c_row_stride + crow;
+    if (n_frames > 1 && (v->y_frame_stride <= 0 || (u128)v->y_frame_stride < yf))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_frame_stride is below the luma plane's extent");
+    if (n_frames > 1 && (v->c_frame_stride <= 0 || (u128)v->c_frame_stride < cf))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": c_frame_stride is below a chroma plane's extent");
+    const u128 ya = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->y_frame_stride : 0) + yf;
+    const u128 ca = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->c_frame_stride : 0) + cf;
+    if (ya > (u128)0x7fffffffffffffffll || ca > (u128)0x7fffffffffffffffll)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a plane spans more than 2^63 bytes");
+    bool finite = std::isfinite(v->oy);
+    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(v->m[i]);
+    if (!finite) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": m and oy must be finite");
+    if (y_span) *y_span = (size_t)ya;
+    if (c_span) *c_span = (size_t)ca;
+    return SILENT_OK;
+}
+// f(frames) with a checked struct (the planes at y / u / v: those of the struct, or their staged copies) as the frame kind that reads
+// it: a struct that IS NV12 as Nv12 (the kernels of silent_pyramid_nv12, which read the (U, V) bytes of a pixel as one pair), any other
+// as Yuv -- like with_rgb_view for a packed view
+template <class F>
+int with_yuv(const silent_yuv_frames* v, const uint8_t* y, const uint8_t* u, const uint8_t* vv, int n_frames, F&& f) {
+    if (v->y_pixel_stride == 1 && v->c_pixel_stride == 2 && vv == u + 1 && v->chroma_shift_x == 1 && v->chroma_shift_y == 1) {
+        Nv12 s;
+        s.y = y;
+        s.uv = u;
+        s.y_row_stride = v->y_row_stride;
+        s.uv_row_stride = v->c_row_stride;
+        s.y_frame_stride = n_frames > 1 ? v->y_frame_stride : 0;
+        s.uv_frame_stride = n_frames > 1 ? v->c_frame_stride : 0;
+        for (int i = 0; i < 9; ++i) s.m[i] = v->m[i];
+        s.oy = v->oy;
+        return f(&s);
+    }
+    Yuv s;
+    s.y = y;
+    s.u = u;
+    s.v = vv;
+    s.y_pixel_stride = v->y_pixel_stride;
+    s.y_row_stride = v->y_row_stride;
+    s.y_frame_stride = n_frames > 1 ? v->y_frame_stride : 0;
+    s.c_pixel_stride = v->c_pixel_stride;
+    s.c_row_stride = v->c_row_stride;
+    s.c_frame_stride = n_frames > 1 ? v->c_frame_stride : 0;
+    s.sx = v->chroma_shift_x;
+    s.sy = v->chroma_shift_y;
+    for (int i = 0; i < 9; ++i) s.m[i] = v->m[i];
+    s.oy = v->oy;
+    return f(&s);
+}
+// what the host forms stage for a checked struct: the UNION of the three spans -- the intervals sorted by address, those that overlap
+// or touch merged -- and for each plane the merged interval it lies in and its offset inside it
+struct YuvStage {
+    int n;                       // merged intervals, 1 .. 3
+    const uint8_t* start[3];
+    size_t bytes[3];
+    int of[3];                   // plane (y, u, v) -> interval
+    size_t delta[3];             // plane -> offset inside its interval
+};
+inline YuvStage yuv_stage(const silent_yuv_frames* v, size_t y_span, size_t c_span) {
+    const uintptr_t a[3] = {reinterpret_cast<uintptr_t>(v->y), reinterpret_cast<uintptr_t>(v->u), reinterpret_cast<uintptr_t>(v->v)};
+    const size_t len[3] = {y_span, c_span, c_span};
+    int order[3] = {0, 1, 2};
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j)
+            if (a[order[j]] < a[order[i]]) {
+                const int t = order[i];
+                order[i] = order[j];
+                order[j] = t;
+            }
+    YuvStage st{};
+    uintptr_t lo = 0, hi = 0;
+    for (int i = 0; i < 3; ++i) {
+        const int p = order[i];
+        if (st.n == 0 || a[p] > hi) {                    // (a[p] == hi: the intervals touch -- merged)
+            lo = a[p];
+            hi = a[p] + len[p];
+            st.start[st.n++] = reinterpret_cast<const uint8_t*>(lo);
+        } else if (a[p] + len[p] > hi) {
+            hi = a[p] + len[p];
+        }
+        st.bytes[st.n - 1] = (size_t)(hi - lo);
+        st.of[p] = st.n - 1;
+        st.delta[p] = (size_t)(a[p] - lo);
+    }
+    return st;
+}
 // The same for a silent_frame_view16: one uint16 element per pixel (the bounds of check_view with 2 for `channels`), and 2-byte alignment
 // of every address a kernel forms -- an even data address and even strides.
 inline int check_view16(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const silent_frame_view16* v, int n_frames, size_t* span) {

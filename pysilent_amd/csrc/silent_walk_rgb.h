@@ -82,6 +82,10 @@ constexpr int kW3Threads = (kW3NC + 1) * 64;
 #define SILENT_W3_NV_ROWS SILENT_W3_CH
 #endif
 static_assert(SILENT_W3_CH % SILENT_W3_NV_ROWS == 0, "NV12 loader: rows of a chunk loaded and converted together");
+#ifndef SILENT_W3_YUV_ROWS
+#define SILENT_W3_YUV_ROWS SILENT_W3_NV_ROWS    // the same grouping for the planar / packed YUV loader (three bytes per row and slot)
+#endif
+static_assert(SILENT_W3_CH % SILENT_W3_YUV_ROWS == 0, "YUV loader: rows of a chunk loaded and converted together");
 constexpr int kW3CH = SILENT_W3_CH;             // rows per chunk: a 12-row ring (22 KB) instead of 24 rows -- the loader is far from
                                                 // being the limit (all loads alone: 0.14 ms), the consumers are latency-bound and
                                                 // want waves: 31 KB of LDS per block = 4 blocks (16 consumer waves) per CU instead of 3
@@ -237,6 +241,29 @@ __host__ __device__ __forceinline__ W3Nv12Load w3_p010_load(const Walk3Args& arg
     const int x = w3_p010_px(args, b.A, lane, k);
     return W3Nv12Load{r.y + p010_y_col(x), r.uv + p010_uv_col(x)};
 }
+// ---- and on planar / packed 8-bit YUV (FrameYuv, silent_pyramid_yuv): the same pixel per lane and load slot (w3_nv12_p0, the same ring
+// mapping), THREE byte loads per slot -- Y behind the luma row term, U and V behind the chroma row term, at byte columns x * y_pixel_stride
+// and (x >> sx) * c_pixel_stride.  The chroma row is (src_y0 + y) >> sy of the FRAME row.  tests/rgb_yuv_host_main.cpp enumerates them
+// over whole launches: every offset is that of a byte that is some pixel's Y, U or V.
+__host__ __device__ __forceinline__ int w3_yuv_px(const Walk3Args& args, int A, int lane, int k) { return w3_nv12_px(args, A, lane, k); }
+// byte offsets of stream row s of a block: the luma row from `y`, and the chroma row from `u` and from `v` alike (W3Nv12Row::uv)
+__host__ __device__ __forceinline__ W3Nv12Row w3_yuv_row(const Walk3Args& args, const FrameYuv& v, const W3ViewBlock& b, int s) {
+    const Walk3Plan& p = args.plan[b.plan];
+    const long long yy = w3_mirror_near(b.y_first + s, p.src_h) + p.src_y0;
+    return W3Nv12Row{(long long)b.frame * v.y_frame_stride + yy * v.y_row_stride, (long long)b.frame * v.c_frame_stride + (yy >> v.sy) * v.c_row_stride};
+}
+// THE address function: one byte each at y_offset from `y`, u_offset from `u` and v_offset from `v`
+struct W3YuvLoad {
+    long long y_offset, u_offset, v_offset;
+};
+__host__ __device__ __forceinline__ W3YuvLoad w3_yuv_load(const Walk3Args& args, const FrameYuv& v, int px, unsigned bid, int chunk, int row,
+                                                          int lane, int k) {
+    const W3ViewBlock b = w3_view_block(args, px, bid);
+    const W3Nv12Row r = w3_yuv_row(args, v, b, chunk * kW3CH + row);
+    const int x = w3_yuv_px(args, b.A, lane, k);
+    const long long c = r.uv + yuv_c_col(x, v.sx, v.c_pixel_stride);
+    return W3YuvLoad{r.y + yuv_y_col(x, v.y_pixel_stride), c, c};
+}
 
 // FT: the frame element type -- float, or unsigned char (packed interleaved uint8 colour frames [n, H, W, 3], silent_pyramid_rgb8: byte c
 // of pixel (y, x) enters as (float)byte, an unsigned load and an exact conversion).  Only the LOADER touches the frame: the ring stays
@@ -252,13 +279,17 @@ __host__ __device__ __forceinline__ W3Nv12Load w3_p010_load(const Walk3Args& arg
 // Every address is that of a luma byte or of the chroma pair of a pixel of the frame.
 // FT = FrameP010 (P010 / P012 / P016 surfaces, by value): the NV12 loader with uint16 elements (w3_p010_load) -- a 2-byte luma load and
 // the pair as one dword per slot, p010_values (shift, offsets) in front of the same nv12_channel; the depth is a runtime scalar.
+// FT = FrameYuv (planar / packed 8-bit YUV, by value): the NV12 loader with three byte loads per slot (w3_yuv_load) -- the byte columns
+// x * y_pixel_stride and (x >> sx) * c_pixel_stride are computed once per block, the row terms are scalar; issue / wait / barrier order
+// is NV12's.  Every address is that of a byte that is some pixel's Y, U or V.
 template <int G, int PX, typename FT = float>
 __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<FT> frames, float* __restrict__ pyr,
                                                                     const Walk3Args args, const WalkBorderArgs border) {
-    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT>,
-                  "float32, packed uint8 or strided uint8 colour frames, NV12 / P010 surfaces");
+    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT> || kFrameYuv<FT>,
+                  "float32, packed uint8 or strided uint8 colour frames, NV12 / P010 / YUV surfaces");
     constexpr bool kP10 = kFrameP010<FT>;                            // (uint16 elements, the code in the high bits)
-    constexpr bool kNv = kFrameNv12<FT> || kP10;                     // the loader converts (Y, U, V) in registers
+    constexpr bool kYuv = kFrameYuv<FT>;                             // (three byte planes, pixel strides, chroma shifts)
+    constexpr bool kNv = kFrameNv12<FT> || kP10 || kYuv;             // the loader converts (Y, U, V) in registers
     constexpr bool kBytes = kFrameBytes<FT> || kFrameRgbView<FT>;   // the loader widens bytes in registers
     static_assert(G == stream_pad_levels(G), "row programs are padded to 4 or 7 levels");
     static_assert(PX == 36 || PX == 32 || PX == 28 || PX == 24, "");
@@ -323,13 +354,23 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
             constexpr int kNvLoads = w3_nv12_row_loads(PX);
             int nvx[kNv ? kNvLoads : 1];                         // NV12: the lane's frame column per load slot
             int nvd = 0;                                         // and ring float of channel 0 of its slot-0 pixel minus 3 lane
+            long long yuy[kYuv ? kNvLoads : 1], yuc[kYuv ? kNvLoads : 1];   // YUV: its byte column in a luma / chroma row
             (void)nvx;
             (void)nvd;
+            (void)yuy;
+            (void)yuc;
             if constexpr (kNv) {
                 vb = w3_view_block(args, PX, bid);
                 nvd = 3 * w3_nv12_p0(vb.A) - vb.A;
 #pragma unroll
                 for (int k = 0; k < kNvLoads; ++k) nvx[k] = w3_nv12_px(args, vb.A, lane, k);
+                if constexpr (kYuv) {
+#pragma unroll
+                    for (int k = 0; k < kNvLoads; ++k) {
+                        yuy[k] = yuv_y_col(nvx[k], frames.y_pixel_stride);
+                        yuc[k] = yuv_c_col(nvx[k], frames.sx, frames.c_pixel_stride);
+                    }
+                }
             } else if constexpr (kFrameRgbView<FT>) {
                 static_assert(kRowLoads == w3_view_row_loads(PX), "");
                 vb = w3_view_block(args, PX, bid);
@@ -352,13 +393,27 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                 // one memory latency per chunk) -- a group's loads (Y byte + chroma pair per slot) are all in flight before one is
                 // consumed; a smaller group reuses the registers and pays a latency per group (measured slower:
                 // profiles/rgb_nv12/README.md)
-                constexpr int kNvRows = SILENT_W3_NV_ROWS;
+                constexpr int kNvRows = kYuv ? SILENT_W3_YUV_ROWS : SILENT_W3_NV_ROWS;
                 typename std::conditional<kP10, unsigned short, unsigned char>::type nvy[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];
-                typename std::conditional<kP10, unsigned, unsigned short>::type nvc[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];
+                typename std::conditional<kP10, unsigned, typename std::conditional<kYuv, unsigned char, unsigned short>::type>::type
+                    nvc[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];      // (YUV: the U byte)
+                unsigned char nvw[kYuv ? kNvRows : 1][kYuv ? kNvLoads : 1];   // YUV: the V byte
                 (void)nvy;
                 (void)nvc;
+                (void)nvw;
                 auto nv_load = [&](int g, int r) {                // row g + r of the chunk into register row r
-                    if constexpr (kP10) {
+                    if constexpr (kYuv) {
+                        const W3Nv12Row row = w3_yuv_row(args, frames, vb, c * kW3CH + g + r);
+                        const unsigned char* yr = src + row.y;
+                        const unsigned char* ur = frames.u + row.uv;
+                        const unsigned char* vr = frames.v + row.uv;
+#pragma unroll
+                        for (int k = 0; k < kNvLoads; ++k) {
+                            nvy[r][k] = yr[yuy[k]];
+                            nvc[r][k] = ur[yuc[k]];
+                            nvw[r][k] = vr[yuc[k]];
+                        }
+                    } else if constexpr (kP10) {
                         const W3Nv12Row row = w3_p010_row(args, frames, vb, c * kW3CH + g + r);
                         const unsigned char* yr = src + row.y;
                         const unsigned char* cr = reinterpret_cast<const unsigned char*>(frames.uv) + row.uv;
@@ -428,7 +483,10 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
 #pragma unroll
                             for (int k = 0; k < kNvLoads; ++k) {
                                 float yv, uv, vv;
-                                if constexpr (kP10) {
+                                if constexpr (kYuv) {
+                                    yv = __fsub_rn((float)nvy[r][k], frames.oy);
+                                    uv = (float)((int)nvc[r][k] - 128), vv = (float)((int)nvw[r][k] - 128);
+                                } else if constexpr (kP10) {
                                     p010_values(nvy[r][k], nvc[r][k], frames.oy, frames.oc, frames.shift, yv, uv, vv);
                                 } else {
                                     yv = __fsub_rn((float)nvy[r][k], frames.oy);

@@ -13,6 +13,7 @@ All buffers are torch GPU tensors allocated once; every launch goes to torch's c
 PyTorch is used for device memory and streams only.
 """
 import ctypes as C
+import fractions
 
 import numpy as np
 
@@ -165,6 +166,11 @@ class LineEndPipeline(object):
         # reach the pyramid; pyramid, maps and keypoints are those of the float32 pipeline on _runtime.p010_to_rgb(planes, depth=...),
         # bit for bit.  The nv12_* keywords describe the conversion for these formats too (_runtime.p010_coefficients), and
         # nv12_matrix="bt2020" exists for them only.
+        # rgb_frame_format="yuv420" / "yuv422" / "yuv444": the frames are a TRIPLE (y, u, v) of uint8 GPU views of any positive strides
+        # -- planar I420 / YV12 / I422 / I444 as software and JPEG decoders emit them, semi-planar NV21 / NV16, packed YUYV / UYVY of a
+        # UVC webcam (yuyv[:, :, 0::2], yuyv[:, :, 1::4], yuyv[:, :, 3::4]); util.zoom.yuv_planes cuts them out of surfaces -- read in
+        # place by silent_pyramid_yuv_dev, one byte per load; pyramid, maps and keypoints are those of the float32 pipeline on
+        # _runtime.yuv_to_rgb(planes, fmt=...), bit for bit.  The nv12_* keywords describe the conversion, as for "nv12".
         if self._p010:
             self.nv12_m, self.nv12_oy, self.nv12_oc = _runtime.p010_coefficients(nv12_matrix, nv12_range, nv12_order, self._p010)
         else:
@@ -354,6 +360,11 @@ class LineEndPipeline(object):
             sh = 16 - self._p010
             return ((torch.randint(0, 1 << self._p010, (self.batch, h, w), device=self.tdev) << sh).to(torch.uint16),
                     (torch.randint(0, 1 << self._p010, (self.batch, h // 2, w // 2, 2), device=self.tdev) << sh).to(torch.uint16))
+        if self._yuv:
+            h, w = self.frame_shape[:2]
+            sx, sy = self._yuv
+            return tuple(torch.randint(0, 256, sh, device=self.tdev).to(torch.uint8)
+                         for sh in ((self.batch, h, w), (self.batch, h >> sy, w >> sx), (self.batch, h >> sy, w >> sx)))
         if self._nv12:
             h, w = self.frame_shape[:2]
             return (torch.randint(0, 256, (self.batch, h, w), device=self.tdev).to(torch.uint8),
@@ -601,7 +612,9 @@ class LineEndPipeline(object):
         mode "rgb" with rgb_frame_dtype="uint8" reports frame_dtype "uint8" and counts the same 1 byte per frame element; a strided
         view, frame_layout / rgb_frame_layout "strided", is read in place and counts the pixel bytes alone, not the bytes between them;
         rgb_frame_format="nv12" counts 1.5 bytes per pixel: the luma byte and half a chroma pair; "p010" / "p012" / "p016" 3 bytes per
-        pixel: the luma element and half a pair of elements)."""
+        pixel: the luma element and half a pair of elements; "yuv420" / "yuv422" / "yuv444" 1 + 2 / 2^(sx + sy) bytes per pixel --
+        1.5, 2 and 3: the luma byte and the pixel's share of a U and a V byte, whatever lies between them in a packed buffer not
+        counted)."""
         h, w, fc = self.frame_shape
         c = self.channels
         if self.crop_px is not None:
@@ -621,6 +634,8 @@ class LineEndPipeline(object):
             return 0.5
         if self._p010:
             return 1.0
+        if self._yuv:                                                # (1 + 2 / 2^(sx + sy)) / 3 = 0.5, 2 / 3, 1.0 -- exact
+            return fractions.Fraction(2 ** sum(self._yuv) + 2, 3 * 2 ** sum(self._yuv))
         return {"uint8": 1, "uint16": 2}.get(self.frame_dtype, 4)
 
     @property
@@ -632,6 +647,11 @@ class LineEndPipeline(object):
     def _p010(self):
         """The depth (10, 12, 16) of a mode "rgb" pipeline reading P010 / P012 / P016 planes, None for every other pipeline."""
         return _runtime.P010_DEPTHS.get(getattr(self, "rgb_frame_format", "interleaved"))
+
+    @property
+    def _yuv(self):
+        """The chroma shifts (sx, sy) of a mode "rgb" pipeline reading a (y, u, v) triple ("yuv420" / "yuv422" / "yuv444"), else None."""
+        return _runtime.YUV_SHIFTS.get(getattr(self, "rgb_frame_format", "interleaved"))
 
     @property
     def _frame_torch_dtype(self):
@@ -672,7 +692,9 @@ class LineEndPipeline(object):
                 + (", read in place from a strided view" if getattr(self, "rgb_frame_layout", "packed") == "strided" else "")
                 + (", NV12 read in place (Y + UV planes, 1.5 bytes per pixel, converted in registers)" if self._nv12 else "")
                 + ((", %s read in place (uint16 Y + UV planes, 3 bytes per pixel, converted in registers)" % self.rgb_frame_format.upper())
-                   if self._p010 else ""))
+                   if self._p010 else "")
+                + ((", %s read in place (a (y, u, v) triple of uint8 views, %.1f bytes per pixel, converted in registers)"
+                    % (self.rgb_frame_format.upper(), 3 * float(self._frame_bytes))) if self._yuv else ""))
 
     # -- launches --------------------------------------------------------------------------------------
     def _stream(self):
@@ -685,6 +707,15 @@ class LineEndPipeline(object):
             raise ValueError("frames must be a pair (y, uv) of uint8 GPU planes [%d, %d, %d] and [%d, %d, %d, 2]"
                              % ((self.batch,) + self.frame_shape[:2] + (self.batch, self.frame_shape[0] // 2, self.frame_shape[1] // 2)))
         return _lib.nv12_ptr(args)
+
+    def _yuv_arg(self, frames):
+        """The const silent_yuv_frames* of a triple (y, u, v) of uint8 GPU views of this pipeline's batch (refused: anything else)."""
+        args, n, dev = _runtime.yuv_frames_of(frames, self.frame_shape[:2], self.rgb_frame_format, self.nv12_m, self.nv12_oy)
+        if not dev or n != self.batch:
+            sx, sy = self._yuv
+            raise ValueError("frames must be a triple (y, u, v) of uint8 GPU planes [%d, %d, %d], [%d, %d, %d] and [%d, %d, %d]"
+                             % ((self.batch,) + self.frame_shape[:2] + 2 * (self.batch, self.frame_shape[0] >> sy, self.frame_shape[1] >> sx)))
+        return _lib.yuv_ptr(args)
 
     def _p010_arg(self, frames):
         """The const silent_p010_frames* of a pair (y, uv) of uint16 GPU planes of this pipeline's batch (refused: anything else)."""
@@ -719,6 +750,10 @@ class LineEndPipeline(object):
         return frame_ptr(frames.data_ptr())
 
     def run_pyramid(self, frames, stream=None):
+        if self._yuv:                                                # (mode "rgb", rgb_frame_format "yuv420" / "yuv422" / "yuv444")
+            self.ctx.check(self._lib.silent_pyramid_yuv_dev(self.ctx.handle, self.plan.handle, self._yuv_arg(frames), self.batch,
+                                                            C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
+            return
         if self._p010:                                               # (mode "rgb", rgb_frame_format "p010" / "p012" / "p016")
             self.ctx.check(self._lib.silent_pyramid_p010_dev(self.ctx.handle, self.plan.handle, self._p010_arg(frames), self.batch,
                                                              C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
@@ -916,7 +951,7 @@ class LineEndPipeline(object):
         no cast launch and no float32 frame buffer.  A frame_dtype="uint16" pipeline likewise takes uint16 host frames only, and a
         mode "rgb" pipeline with rgb_frame_dtype="uint8" uint8 host frames [batch, H, W, 3] only."""
         torch = self.torch
-        if self._nv12 or self._p010:
+        if self._nv12 or self._p010 or self._yuv:
             return self._step_host_nv12(frames)
         if isinstance(frames, np.ndarray):
             src = torch.from_numpy(np.ascontiguousarray(frames))
@@ -993,12 +1028,15 @@ class LineEndPipeline(object):
         torch = self.torch
         h, w = self.frame_shape[:2]
         shapes = ((self.batch, h, w), (self.batch, h // 2, w // 2, 2))
+        if self._yuv:     # (a (y, u, v) triple of uint8 arrays of any strides: three planes in the ring, packed by the staging copy)
+            shapes = ((self.batch, h, w),) + 2 * ((self.batch, h >> self._yuv[1], w >> self._yuv[0]),)
         # (rgb_frame_format "p010" / "p012" / "p016": the same ring with uint16 planes)
         np_dtype, t_dtype = (np.uint16, torch.uint16) if self._p010 else (np.uint8, torch.uint8)
-        if not isinstance(frames, (tuple, list)) or len(frames) != 2 or any(
+        if not isinstance(frames, (tuple, list)) or len(frames) != len(shapes) or any(
                 not isinstance(p, np.ndarray) or p.dtype != np_dtype or tuple(p.shape) != sh for p, sh in zip(frames, shapes)):
-            raise ValueError("step_host of an rgb_frame_format=%r pipeline takes a pair of %s arrays of shapes %s and %s"
-                             % ((self.rgb_frame_format, np.dtype(np_dtype).name) + shapes))
+            raise ValueError("step_host of an rgb_frame_format=%r pipeline takes a %s of %s arrays of shapes %s"
+                             % (self.rgb_frame_format, "triple" if self._yuv else "pair", np.dtype(np_dtype).name,
+                                " and ".join(str(sh) for sh in shapes)))
         cs = self._copy_stream_of_the_ingest()
         ring = self._ingest.setdefault("nv12", {"slots": [], "next": 0})
         if not ring["slots"]:

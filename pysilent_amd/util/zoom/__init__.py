@@ -3,3 +3,4 @@ from .from_image import image_to_zoom_tensor as from_image, classic_pyramid, cla
 from .to_image_list import zoom_tensor_to_image_list as to_image_list
 from .nv12 import nv12_planes
 from .p010 import p010_planes
+from .yuv import yuv_planes
