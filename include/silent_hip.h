@@ -452,6 +452,70 @@ int silent_pyramid_yuv_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, con
 int silent_yuv_to_rgb(silent_ctx* ctx, const silent_yuv_frames* frames, int n_frames, int H, int W, float* rgb);
 int silent_yuv_to_rgb_dev(silent_ctx* ctx, const silent_yuv_frames* frames, int n_frames, int H, int W, float* rgb, silent_stream stream);
 
+/* Planar, semi-planar and packed 16-BIT YUV for 3-CHANNEL plans, read in place: what software decoders (FFmpeg, dav1d, libaom, libvpx)
+ * emit for HEVC Main10 / AV1 / VP9 profile 2 (yuv420p10le / I010 and its 4:2:2, 4:4:4 and 12-bit siblings: the code in the LOW bits),
+ * the semi-planar 4:2:2 / 4:4:4 surfaces P210 / P216 / P410 / P416 and the packed Y210 / Y216 / Y416 (the code in the HIGH bits).
+ * silent_yuv_frames' addressing with silent_p010_frames' arithmetic: three plane pointers of little-endian uint16 elements (native byte
+ * order; they may overlap: a packed format is three views of one buffer; they are only read), a pixel stride per plane class, a chroma
+ * subsampling shift per axis (0 or 1).  Strides are in BYTES, 64-bit, and EVEN.  With sx = chroma_shift_x, sy = chroma_shift_y, pixel
+ * (y, x) of frame f reads the three elements at the byte offsets
+ *     Y: f y_frame_stride + y y_row_stride + x y_pixel_stride                                       from y
+ *     U: f c_frame_stride + (y >> sy) c_row_stride + (x >> sx) c_pixel_stride   from u,       V: the same offset from v
+ * and the value of channel k in {0, 1, 2} is
+ *     code(e) = (e >> shift) & ((1 << depth) - 1)                     e loaded UNSIGNED (a code >= 0x8000 does not go negative)
+ *     Yv = (float)code(Y) - oy       Uv = (float)code(U) - oc       Vv = (float)code(V) - oc
+ *     c_k = min(max((Yv * m[3 k] + Uv * m[3 k + 1]) + Vv * m[3 k + 2], 0), 255)
+ * -- P010's conversion to the letter: every difference, product and sum a SEPARATELY ROUNDED float32 operation (no fused multiply-add),
+ * chroma NEAREST, NO rounding to an integer, the result on the 0 .. 255 scale.  Bits of an element outside [shift, shift + depth) never
+ * influence a result.  The code in the high bits: shift = 16 - depth; in the low bits: shift = 0.  8 <= depth <= 16, shift >= 0,
+ * shift + depth <= 16.
+ *     I010 / I210 / I410 (yuv420p10le / yuv422p10le / yuv444p10le; I012 ...: depth 12): three planes, y_pixel_stride = c_pixel_stride = 2,
+ *                                                                    shifts 1 / 1, 1 / 0, 0 / 0, shift = 0
+ *     P010 / P210 / P410 (P016 / P216 / P416: depth 16): u = uv, v = uv + 1 element, c_pixel_stride = 4, shifts 1 / 1, 1 / 0, 0 / 0,
+ *                                                                    shift = 16 - depth; a VU order (NV21-like): v = vu, u = vu + 1
+ *     Y210 / Y216 (Y0 U Y1 V): y = base, y_pixel_stride = 4, u = base + 1, v = base + 3 elements, c_pixel_stride = 8, shifts 1 / 0,
+ *                                                                    shift = 16 - depth
+ *     Y416 (U Y V A): u = base, y = base + 1, v = base + 2 elements, all pixel strides 8, shifts 0 / 0, depth 16
+ *     4:4:0: shifts 0 / 1
+ * The conversion happens in registers at the kernels' loads.  pyr is IDENTICAL, bit for bit, to silent_pyramid[_dev] on the frames
+ * silent_yuv16_to_rgb[_dev] writes for the same struct, on every route: the walk kernel, union plans with their border blocks (inside
+ * and behind the walk's launch), per-level plans, the unit + region kernels, every SILENT_TUNE_PYRAMID value.  A struct that IS P010
+ * (y_pixel_stride == 2, c_pixel_stride == 4, v == u + 1 element, shifts 1 / 1, shift == 16 - depth) runs the kernels of
+ * silent_pyramid_p010 and gives its bits.
+ * Reads: every load is ONE 2-byte element at a 2-byte aligned address that is some pixel's Y, U or V: no pair loads, no dword loads,
+ * nothing between pixels, nothing outside the three spans, the span of a plane being (n - 1) frame_stride + (rows - 1) row_stride +
+ * (cols - 1) pixel_stride + 2 bytes with rows x cols = H x W for y and (H >> sy) x (W >> sx) for u and v.  (The P010 kernels read the
+ * (U, V) elements of a pixel as one pair: the same bytes.)  A frame stride is not read when n_frames == 1.
+ * Refusals, in this order: a NULL ctx; SILENT_E_INVALID for a NULL plan / struct / y / u / v, a chroma shift other than 0 or 1, an odd H
+ * with chroma_shift_y = 1 or an odd W with chroma_shift_x = 1 (or H, W < 1), a pixel stride < 2, a row stride below its plane's row
+ * extent (cols - 1) pixel_stride + 2, a frame stride below its plane's extent (n_frames > 1), a span above 2^63 - 1 bytes, a non-finite
+ * m, oy or oc, an odd y, u or v address, an odd stride, a depth outside 8 .. 16 or a shift outside 0 .. 16 - depth; then a NULL pyr /
+ * rgb, a plan of another context, n_frames < 1 (SILENT_E_INVALID) and a single-channel plan (SILENT_E_UNSUPPORTED: such a plan reads
+ * the luma plane through silent_pyramid_view16).
+ * The host forms refuse everything their _dev forms refuse before anything is staged, and stage the UNION of the three spans: the
+ * intervals sorted, those that overlap or touch merged, each merged interval copied once, the pointers rebased -- a Y210 buffer
+ * crosses the bus once, not three times.  The _dev forms are stream-ordered and asynchronous; the struct is dead at return.
+ * silent_yuv16_to_rgb[_dev] writes the converted frames themselves, [n_frames, H, W, 3] float32, with the same device functions, one
+ * thread per pixel; H and W are arguments, refusals as above under its own name.  (ABI additions only: SILENT_ABI_VERSION is unchanged.) */
+typedef struct silent_yuv16_frames {
+    const uint16_t* y;
+    const uint16_t* u;
+    const uint16_t* v;
+    int64_t y_pixel_stride, y_row_stride, y_frame_stride;
+    int64_t c_pixel_stride, c_row_stride, c_frame_stride;
+    int32_t chroma_shift_x, chroma_shift_y;
+    float m[9];
+    float oy;
+    float oc;
+    int32_t shift;
+    int32_t depth;
+} silent_yuv16_frames;
+int silent_pyramid_yuv16(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_yuv16_frames* frames, int n_frames, float* pyr);
+int silent_pyramid_yuv16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_yuv16_frames* frames, int n_frames, float* pyr,
+                             silent_stream stream);
+int silent_yuv16_to_rgb(silent_ctx* ctx, const silent_yuv16_frames* frames, int n_frames, int H, int W, float* rgb);
+int silent_yuv16_to_rgb_dev(silent_ctx* ctx, const silent_yuv16_frames* frames, int n_frames, int H, int W, float* rgb, silent_stream stream);
+
 /* uint16 frames, read as they are: 10 / 12 / 16-bit machine-vision and scientific cameras (Mono10 / Mono12 / Mono16), thermal and
  * depth sensors (Y16, Z16), 16-bit TIFF / PNG, and the luma of the P010 / P016 surfaces a hardware decoder hands over for 10-bit
  * HEVC / AV1.  The twins of the *_u8 entry points -- same argument lists, maps_f16 / parts / stream arguments, status codes and order

@@ -103,6 +103,16 @@ class YuvFrames(C.Structure):
                 ("chroma_shift_x", C.c_int32), ("chroma_shift_y", C.c_int32), ("m", C.c_float * 9), ("oy", C.c_float)]
 
 
+class Yuv16Frames(C.Structure):
+    """silent_yuv16_frames (include/silent_hip.h): a planar / semi-planar / packed 16-bit YUV batch -- YuvFrames with uint16 elements
+    (strides in BYTES, even), the chroma offset, and the position of the code value inside an element: shift bits below it, depth bits."""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p),
+                ("y_pixel_stride", C.c_int64), ("y_row_stride", C.c_int64), ("y_frame_stride", C.c_int64),
+                ("c_pixel_stride", C.c_int64), ("c_row_stride", C.c_int64), ("c_frame_stride", C.c_int64),
+                ("chroma_shift_x", C.c_int32), ("chroma_shift_y", C.c_int32), ("m", C.c_float * 9), ("oy", C.c_float), ("oc", C.c_float),
+                ("shift", C.c_int32), ("depth", C.c_int32)]
+
+
 class SilentLibraryError(RuntimeError):
     """libsilent_hip.so is missing or cannot be loaded."""
 
@@ -119,6 +129,7 @@ _xp = C.POINTER(FrameView16)  # a strided uint16 view (the *_view16 entry points
 _np = C.POINTER(Nv12Frames)   # an NV12 batch (silent_pyramid_nv12, silent_nv12_to_rgb); nv12_ptr() makes one from _runtime.nv12_frames_of's tuple
 _pp = C.POINTER(P010Frames)   # a P010 batch (silent_pyramid_p010, silent_p010_to_rgb); p010_ptr() makes one from _runtime.p010_frames_of's tuple
 _yp = C.POINTER(YuvFrames)    # a planar / packed YUV batch (silent_pyramid_yuv, silent_yuv_to_rgb); yuv_ptr() makes one from _runtime.yuv_frames_of's tuple
+_y16p = C.POINTER(Yuv16Frames)  # a 16-bit YUV batch (silent_pyramid_yuv16, silent_yuv16_to_rgb); yuv16_ptr() makes one from _runtime.yuv16_frames_of's tuple
 _ep = C.POINTER(Extent)
 _i, _u, _f, _d, _sz = C.c_int, C.c_uint, C.c_float, C.c_double, C.c_size_t
 
@@ -172,6 +183,10 @@ _SIGNATURES = {
     "silent_pyramid_yuv_dev": [_vp, _vp, _yp, _i, _fp, _vp],
     "silent_yuv_to_rgb": [_vp, _yp, _i, _i, _i, _fp],
     "silent_yuv_to_rgb_dev": [_vp, _yp, _i, _i, _i, _fp, _vp],
+    "silent_pyramid_yuv16": [_vp, _vp, _y16p, _i, _fp],
+    "silent_pyramid_yuv16_dev": [_vp, _vp, _y16p, _i, _fp, _vp],
+    "silent_yuv16_to_rgb": [_vp, _y16p, _i, _i, _i, _fp],
+    "silent_yuv16_to_rgb_dev": [_vp, _y16p, _i, _i, _i, _fp, _vp],
     "silent_gray_pass_u8": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8x3": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8_dev": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i, _u, _vp],
@@ -324,6 +339,17 @@ def yuv_ptr(frames):
     y, u, v, yp, yr, yf, cp, cr, cf, sx, sy, m, oy = frames
     return C.pointer(YuvFrames(int(y), int(u), int(v), int(yp), int(yr), int(yf), int(cp), int(cr), int(cf), int(sx), int(sy),
                                (C.c_float * 9)(*[float(c) for c in m]), float(oy)))
+
+
+def yuv16_ptr(frames):
+    """(y, u, v addresses, y_pixel_stride, y_row_stride, y_frame_stride, c_pixel_stride, c_row_stride, c_frame_stride, chroma_shift_x,
+    chroma_shift_y, m, oy, oc, shift, depth) -- what _runtime.yuv16_frames_of returns -- as the const silent_yuv16_frames* of the 16-bit
+    YUV entry points (None: NULL).  The struct is read before the call returns."""
+    if frames is None:
+        return None
+    y, u, v, yp, yr, yf, cp, cr, cf, sx, sy, m, oy, oc, shift, depth = frames
+    return C.pointer(Yuv16Frames(int(y), int(u), int(v), int(yp), int(yr), int(yf), int(cp), int(cr), int(cf), int(sx), int(sy),
+                                 (C.c_float * 9)(*[float(c) for c in m]), float(oy), float(oc), int(shift), int(depth)))
 
 
 def gray_entry(family, frame_dtype="float32", frame_channels=1, storage="float32", dev=False, parts=None, frame_layout="packed"):

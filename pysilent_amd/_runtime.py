@@ -983,6 +983,11 @@ def check_rgb_frame_layout(rgb_frame_layout, mode="rgb", rgb_frame_dtype="float3
 RGB_FRAME_FORMATS = ("interleaved", "nv12", "p010", "p012", "p016")
 # and the formats that take a (y, u, v) triple: rgb_frame_format -> chroma shifts (x, y)
 YUV_SHIFTS = {"yuv420": (1, 1), "yuv422": (1, 0), "yuv444": (0, 0)}
+# and the formats that take a (y, u, v) triple of UINT16 views: rgb_frame_format -> (sx, sy, depth, shift).  "yuv4xxp10" / "p12": the
+# code in the LOW bits (FFmpeg's yuv4xxp10le / p12le, I010 ...), "...msb": in the HIGH bits (P210 / P410 / Y210), "p16": all 16 bits
+YUV16_FORMATS = dict(("yuv%sp%d%s" % (x, d, a), (sx, sy, d, 16 - d if a else 0))
+                     for x, (sx, sy) in (("420", (1, 1)), ("422", (1, 0)), ("444", (0, 0)))
+                     for d, a in ((10, ""), (12, ""), (10, "msb"), (12, "msb"), (16, "")))
 NV12_MATRICES = {"bt601": (.299, .114), "bt709": (.2126, .0722)}      # (Kr, Kb)
 NV12_RANGES = ("limited", "full")
 NV12_ORDERS = ("bgr", "rgb")
@@ -999,14 +1004,17 @@ def check_rgb_frame_format(rgb_frame_format, mode="rgb", rgb_frame_dtype="float3
     frames bit for bit) or "p010" / "p012" / "p016" (the same pair as uint16 planes, the 10 / 12 / 16-bit code in the high bits of
     each element: silent_pyramid_p010) or "yuv420" / "yuv422" / "yuv444" (a triple (y, u, v) of uint8 views of ANY positive strides --
     planar I420 / YV12 / I422 / I444, semi-planar NV12 / NV21 / NV16, packed YUYV / UYVY / VUYA: the layout lives in the strides, the
-    name gives the chroma subsampling -- read in place by silent_pyramid_yuv).  The name is checked first; then the mode; then that the format is not combined with
+    name gives the chroma subsampling -- read in place by silent_pyramid_yuv) or one of YUV16_FORMATS, "yuv420p10" ... "yuv444p16" (the
+    same triple as UINT16 views, read in place by silent_pyramid_yuv16: "yuvXp10" / "yuvXp12" with the code in the low bits, FFmpeg's
+    yuvXp10le / yuvXp12le; "yuvXp10msb" / "yuvXp12msb" with the code in the high bits, P210 / P410 / Y210; "yuvXp16").  The name is checked first; then the mode; then that the format is not combined with
     rgb_frame_dtype="uint8", rgb_frame_layout="strided" or the gray frame_* keywords; then that H and W (hw, when given) are even ("yuv422": W; "yuv444": nothing)."""
-    if not isinstance(rgb_frame_format, str) or rgb_frame_format not in RGB_FRAME_FORMATS + tuple(YUV_SHIFTS):
+    if not isinstance(rgb_frame_format, str) or rgb_frame_format not in RGB_FRAME_FORMATS + tuple(YUV_SHIFTS) + tuple(YUV16_FORMATS):
         raise ValueError("rgb_frame_format must be 'interleaved' or 'nv12', or 'p010' / 'p012' / 'p016', or 'yuv420' / 'yuv422' / "
-                         "'yuv444', got %r" % (rgb_frame_format,))
+                         "'yuv444', got %r (or, for uint16 planes, 'yuvXp10' / 'yuvXp12' / 'yuvXp10msb' / 'yuvXp12msb' / 'yuvXp16' with X "
+                         "one of 420, 422, 444)" % (rgb_frame_format,))
     if rgb_frame_format != "interleaved":
         name = "rgb_frame_format=%r" % (rgb_frame_format,)
-        wide = rgb_frame_format in P010_DEPTHS
+        wide = rgb_frame_format in P010_DEPTHS or rgb_frame_format in YUV16_FORMATS
         if mode != "rgb":
             raise ValueError("%s is for mode 'rgb' (mode 'gray' reads the luma plane through frame_layout='strided'%s)"
                              % (name, " with frame_dtype='uint16'" if wide else ""))
@@ -1022,8 +1030,8 @@ def check_rgb_frame_format(rgb_frame_format, mode="rgb", rgb_frame_dtype="float3
                              % (name, frame_channels))
         if frame_layout != "packed":
             raise ValueError("%s does not combine with frame_layout=%r (frame_layout describes the frames of mode 'gray')" % (name, frame_layout))
-        if rgb_frame_format in YUV_SHIFTS:
-            sx, sy = YUV_SHIFTS[rgb_frame_format]
+        if rgb_frame_format in YUV_SHIFTS or rgb_frame_format in YUV16_FORMATS:
+            sx, sy = (YUV_SHIFTS.get(rgb_frame_format) or YUV16_FORMATS[rgb_frame_format])[:2]
             if hw is not None and ((sy and int(hw[0]) % 2) or (sx and int(hw[1]) % 2) or min(int(hw[0]), int(hw[1])) < 1):
                 raise ValueError("%s needs even %s, got %s" % (name, "H and W (4:2:0 chroma)" if sy else "W (4:2:2 chroma)",
                                                               tuple(int(v) for v in hw)))
@@ -1321,6 +1329,97 @@ def yuv_to_rgb(planes, hw, fmt="yuv420", nv12_matrix="bt709", nv12_range="limite
     return out
 
 
+def yuv16_frames_of(planes, hw, fmt, m, oy, oc):
+    """A triple (y, u, v) of uint16 planes -- all torch.uint16 GPU tensors, or all host arrays (ndarrays or torch CPU tensors); y [n, H, W], u and v [n, H >> sy, W >> sx]
+    with (sx, sy, depth, shift) = YUV16_FORMATS[fmt]; each ANY view with positive strides (the layout lives in the strides:
+    y210[:, :, 0::2], y210[:, :, 1::4], y210[:, :, 3::4] is a valid triple), u and v with EQUAL strides -- as what _lib.yuv16_ptr takes:
+    (y, u, v addresses, y_pixel_stride, y_row_stride, y_frame_stride, c_pixel_stride, c_row_stride, c_frame_stride (BYTES, even), sx,
+    sy, m, oy, oc, shift, depth).  Returns (that tuple, n, on_device).  Nothing is converted or copied."""
+    if fmt not in YUV16_FORMATS:
+        raise ValueError("fmt must be one of %s, got %r" % (", ".join(sorted(YUV16_FORMATS)), fmt))
+    sx, sy, depth, shift = YUV16_FORMATS[fmt]
+    if not isinstance(planes, (tuple, list)) or len(planes) != 3:
+        raise ValueError("16-bit YUV frames are a triple (y, u, v) of uint16 planes")
+    y, u, v = planes
+    # (GPU tensors: read in place on the device; ndarrays and torch CPU tensors: host memory, staged by the host forms)
+    dev = all(is_torch_tensor(p) and p.is_cuda for p in planes)
+    if not dev and not all(isinstance(p, np.ndarray) or (is_torch_tensor(p) and not p.is_cuda) for p in planes):
+        raise TypeError(TYPE_ERROR_MESSAGE)
+    h, w = int(hw[0]), int(hw[1])
+
+    def geometry(p):
+        if is_torch_tensor(p):
+            import torch
+            if p.dtype != torch.uint16:
+                raise ValueError("16-bit YUV planes must be uint16 GPU tensors or uint16 ndarrays (nothing is converted), got %s" % (p.dtype,))
+            return tuple(int(s) for s in p.shape), tuple(2 * int(s) for s in p.stride()), int(p.data_ptr())
+        if p.dtype != np.uint16:
+            raise ValueError("16-bit YUV planes must be uint16 GPU tensors or uint16 ndarrays (nothing is converted), got %s" % (p.dtype,))
+        return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.strides), int(p.ctypes.data)
+
+    ys, yst, ya = geometry(y)
+    us, ust, ua = geometry(u)
+    vs, vst, va = geometry(v)
+    if len(ys) != 3 or ys[1:] != (h, w) or ys[0] < 1:
+        raise ValueError("the 16-bit YUV luma plane must be [n, %d, %d], got %s" % (h, w, ys))
+    n = ys[0]
+    ch, cw = h >> sy, w >> sx
+    if us != (n, ch, cw) or vs != (n, ch, cw):
+        raise ValueError("the %s chroma planes must be [%d, %d, %d], got %s and %s" % (fmt, n, ch, cw, us, vs))
+
+    def strides(st, rows, cols):
+        # (a stride of an axis of extent 1 is never used: the smallest legal value stands in for it)
+        px = st[2] if cols > 1 else 2
+        row = st[1] if rows > 1 else (cols - 1) * px + 2
+        frame = st[0] if n > 1 else (rows - 1) * row + (cols - 1) * px + 2
+        return px, row, frame
+
+    yp, yr, yf = strides(yst, h, w)
+    cp, cr, cf = strides(ust, ch, cw)
+    if strides(vst, ch, cw) != (cp, cr, cf):
+        raise ValueError("16-bit YUV planes: u and v must have equal strides, got %s and %s" % (ust, vst))
+    if min(yp, cp) < 2 or yr < (w - 1) * yp + 2 or cr < (cw - 1) * cp + 2 or yf < (h - 1) * yr + (w - 1) * yp + 2 \
+            or cf < (ch - 1) * cr + (cw - 1) * cp + 2:
+        raise ValueError("16-bit YUV planes: rows or frames overlap, or a stride is not positive (byte strides %s, %s)" % (yst, ust))
+    if (yp | yr | yf | cp | cr | cf | ya | ua | va) & 1:
+        raise ValueError("16-bit YUV planes: an address or a byte stride is odd (uint16 elements; byte strides %s, %s)" % (yst, ust))
+    return (ya, ua, va, yp, yr, yf, cp, cr, cf, sx, sy, [float(c) for c in np.asarray(m, np.float32).reshape(9)], float(oy), float(oc),
+            shift, depth), n, dev
+
+
+class _Yuv16Operand(_Nv12Operand):
+    """A planar / semi-planar / packed 16-bit YUV batch (yuv16_frames_of) as an operand (see _Nv12Operand)."""
+
+    def __init__(self, planes, hw, fmt, m, oy, oc, ctx=None):
+        args, self.n_frames, self.dev = yuv16_frames_of(planes, hw, fmt, m, oy, oc)
+        self.packed, self.c, self.extents = False, 3, [(int(hw[0]), int(hw[1]))]
+        self.device = self.stream = None
+        if self.dev:
+            import torch
+            self._torch_device = planes[0].device
+            self.device = self._torch_device.index or 0
+            self.stream = C.c_void_p(torch.cuda.current_stream(self._torch_device).cuda_stream)
+        self.ptr = _lib.yuv16_ptr(args)
+        self.buf = tuple(planes)                        # keep alive
+        self.ctx = ctx or get_context(self.device)
+
+
+def yuv16_to_rgb(planes, hw, fmt="yuv420p10", nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", device=None):
+    """The float32 frames [n, H, W, 3] the pyramid kernels see for a (y, u, v) triple of uint16 views of format ``fmt`` (one of
+    YUV16_FORMATS; silent_yuv16_to_rgb[_dev]: the loaders' own device functions, one thread per pixel), on the 0 .. 255 scale and not
+    rounded -- for display, and as the reference of the bit-identity contract.  planes: yuv16_frames_of; the conversion:
+    p010_coefficients at the format's depth."""
+    if fmt not in YUV16_FORMATS:
+        raise ValueError("fmt must be one of %s, got %r" % (", ".join(sorted(YUV16_FORMATS)), fmt))
+    m, oy, oc = p010_coefficients(nv12_matrix, nv12_range, nv12_order, YUV16_FORMATS[fmt][2])
+    check_rgb_frame_format(fmt, hw=hw)
+    op = _Yuv16Operand(planes, hw, fmt, m, oy, oc, None if device is None else get_context(device))
+    h, w = int(hw[0]), int(hw[1])
+    out, optr = op.empty((op.n_frames, h, w, 3))
+    op.call("yuv16_to_rgb", op.ptr, op.n_frames, h, w, optr)
+    return out
+
+
 class PyramidPlan(object):
     """Tap tables of one (frame size, level geometry) on the device.  ``levels`` is a list of dicts / tuples
     (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w).  accumulation="float64" (single-channel plans): every op of
@@ -1398,7 +1497,9 @@ class PyramidPlan(object):
         uint8 planes (nv12_frames_of) read in place and converted in registers (silent_pyramid_nv12; nv12_coefficients), the pyramid
         of the float32 call on nv12_to_rgb(frames) bit for bit.  rgb_frame_format="yuv420" / "yuv422" / "yuv444": frames is a triple
         (y, u, v) of uint8 views of any positive strides (yuv_frames_of; silent_pyramid_yuv), the pyramid of the float32 call on
-        yuv_to_rgb(frames, hw, fmt) bit for bit."""
+        yuv_to_rgb(frames, hw, fmt) bit for bit.  rgb_frame_format one of YUV16_FORMATS ("yuv420p10" ...): the same triple as uint16
+        views (yuv16_frames_of; silent_pyramid_yuv16; p010_coefficients at the format's depth), the pyramid of the float32 call on
+        yuv16_to_rgb(frames, hw, fmt) bit for bit."""
         mode = "gray" if self.frame_shape[2] == 1 else "rgb"
         fmt = check_rgb_frame_format(rgb_frame_format, mode, rgb_frame_dtype, rgb_frame_layout, frame_dtype, frame_channels, frame_layout,
                                      self.frame_shape[:2])
@@ -1409,6 +1510,12 @@ class PyramidPlan(object):
             op = _P010Operand(frames, self.frame_shape[:2], m, oy, oc, P010_DEPTHS[fmt], self.ctx)
             out, optr = op.empty(op.n_frames * self.frame_px * 3)
             op.call("pyramid_p010", self.handle, op.ptr, op.n_frames, optr)
+            return PackedPyramid(out, self.extents, 3, op.n_frames)
+        if fmt in YUV16_FORMATS:
+            m, oy, oc = p010_coefficients(nv12_matrix, nv12_range, nv12_order, YUV16_FORMATS[fmt][2])
+            op = _Yuv16Operand(frames, self.frame_shape[:2], fmt, m, oy, oc, self.ctx)
+            out, optr = op.empty(op.n_frames * self.frame_px * 3)
+            op.call("pyramid_yuv16", self.handle, op.ptr, op.n_frames, optr)
             return PackedPyramid(out, self.extents, 3, op.n_frames)
         if fmt in YUV_SHIFTS:
             # "yuv420" / "yuv422" / "yuv444": a triple (y, u, v) of uint8 views of any positive strides (yuv_frames_of), read in place

@@ -304,10 +304,26 @@ struct FrameYuv {
 };
 template <typename FT>
 constexpr bool kFrameYuv = std::is_same<FT, FrameYuv>::value;
-// the 3-channel kinds that are read through a `src` struct with at(y, x, ch) / atf(y, i) (strided colour views, NV12, P010 and YUV
-// surfaces)
+// planar, semi-planar and packed 16-bit YUV (silent_pyramid_yuv16): FrameYuv's addressing with uint16 elements, FrameP010's arithmetic
+// with a mask, so that the code may sit in the low bits (below)
+struct FrameYuv16 {
+    const unsigned short* y;
+    const unsigned short* u;
+    const unsigned short* v;
+    long long y_pixel_stride, y_row_stride, y_frame_stride;   // bytes, even
+    long long c_pixel_stride, c_row_stride, c_frame_stride;   // bytes, even; shared by u and v
+    int sx, sy;                                               // chroma subsampling shifts, 0 or 1 each
+    float m[9];
+    float oy, oc;
+    int shift;                                                // bits below the code value
+    unsigned mask;                                            // (1 << depth) - 1
+};
 template <typename FT>
-constexpr bool kFrameRgbSrc = kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT> || kFrameYuv<FT>;
+constexpr bool kFrameYuv16 = std::is_same<FT, FrameYuv16>::value;
+// the 3-channel kinds that are read through a `src` struct with at(y, x, ch) / atf(y, i) (strided colour views, NV12, P010, YUV and
+// 16-bit YUV surfaces)
+template <typename FT>
+constexpr bool kFrameRgbSrc = kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT> || kFrameYuv<FT> || kFrameYuv16<FT>;
 __device__ __forceinline__ float nv12_channel(float yv, float uv, float vv, float m0, float m1, float m2) {
     return fminf(fmaxf(__fadd_rn(__fadd_rn(__fmul_rn(yv, m0), __fmul_rn(uv, m1)), __fmul_rn(vv, m2)), 0.0f), 255.0f);
 }
@@ -486,11 +502,84 @@ __device__ __forceinline__ YuvSrc frame_of(const FrameYuv& f, int frame) {
     return s;
 }
 
+// Planar, semi-planar and packed 16-bit YUV (silent_pyramid_yuv16, 3-channel plans only): FrameYuv's ADDRESSING (three plane pointers,
+// a pixel stride per plane class, a chroma shift per axis; all strides bytes and even) with uint16 elements, and P010's ARITHMETIC with
+// a mask in front, so that the code may sit in the low bits (yuv420p10le / I010: shift 0) or in the high bits (P210, Y210: shift =
+// 16 - depth):
+//     code(e) = (e >> shift) & mask,  Yv = (float)code(Y) - oy,  Uv = (float)code(U) - oc,  Vv = (float)code(V) - oc,
+//     c_k = nv12_channel(Yv, Uv, Vv, row k of m)
+// -- elements loaded UNSIGNED, every difference a separately rounded float32 operation; with shift = 16 - depth the mask changes
+// nothing and these are p010_values' values.  Every load is ONE 2-byte element (global_load_ushort) at a 2-byte aligned address that
+// is some pixel's Y, U or V: no pair and no dword loads, so nothing between the pixels of a packed format is ever read.
+// yuv16_values: the three elements as they were loaded -> (Yv, Uv, Vv); every loader and yuv16_to_rgb_kernel go through it.
+__device__ __forceinline__ void yuv16_values(unsigned ey, unsigned eu, unsigned ev, float oy, float oc, int shift, unsigned mask, float& yv,
+                                             float& uv, float& vv) {
+    yv = __fsub_rn((float)(((ey & 0xffffu) >> shift) & mask), oy);
+    uv = __fsub_rn((float)(((eu & 0xffffu) >> shift) & mask), oc);
+    vv = __fsub_rn((float)(((ev & 0xffffu) >> shift) & mask), oc);
+}
+// one frame of such a batch inside a kernel (the planes as byte pointers: strides are bytes; the columns are yuv_y_col / yuv_c_col)
+struct Yuv16Src {
+    const unsigned char* y;
+    const unsigned char* u;
+    const unsigned char* v;
+    long long y_pixel_stride, y_row_stride, c_pixel_stride, c_row_stride;
+    int sx, sy;
+    float m[9];
+    float oy, oc;
+    int shift;
+    unsigned mask;
+    // the (Y, U, V) of pixel (x, y), offsets removed: three 2-byte loads
+    __device__ __forceinline__ void yuv(long long yy, long long x, float& yv, float& uvv, float& vv) const {
+        const long long c = (yy >> sy) * c_row_stride + yuv_c_col(x, sx, c_pixel_stride);
+        unsigned short ey, eu, ev;
+        __builtin_memcpy(&ey, y + yy * y_row_stride + yuv_y_col(x, y_pixel_stride), 2);
+        __builtin_memcpy(&eu, u + c, 2);
+        __builtin_memcpy(&ev, v + c, 2);
+        yuv16_values(ey, eu, ev, oy, oc, shift, mask, yv, uvv, vv);
+    }
+    // channel ch of pixel (x, y) / float i of the virtual packed row y (coefficients selected as values: Nv12Src::at)
+    __device__ __forceinline__ float at(long long yy, long long x, int ch) const {
+        float yv, uvv, vv;
+        yuv(yy, x, yv, uvv, vv);
+        const float a0 = m[0], a1 = m[1], a2 = m[2], b0 = m[3], b1 = m[4], b2 = m[5], c0 = m[6], c1 = m[7], c2 = m[8];
+        return nv12_channel(yv, uvv, vv, ch == 0 ? a0 : (ch == 1 ? b0 : c0), ch == 0 ? a1 : (ch == 1 ? b1 : c1), ch == 0 ? a2 : (ch == 1 ? b2 : c2));
+    }
+    __device__ __forceinline__ float atf(long long yy, long long i) const {
+        const long long p = i / 3;
+        return at(yy, p, (int)(i - 3 * p));
+    }
+};
+template <>
+struct FrameKind<FrameYuv16> {
+    typedef FrameYuv16 param;
+    typedef Yuv16Src src;
+};
+__device__ __forceinline__ Yuv16Src frame_of(const FrameYuv16& f, int frame) {
+    Yuv16Src s;
+    s.y = reinterpret_cast<const unsigned char*>(f.y) + (long long)frame * f.y_frame_stride;
+    s.u = reinterpret_cast<const unsigned char*>(f.u) + (long long)frame * f.c_frame_stride;
+    s.v = reinterpret_cast<const unsigned char*>(f.v) + (long long)frame * f.c_frame_stride;
+    s.y_pixel_stride = f.y_pixel_stride;
+    s.y_row_stride = f.y_row_stride;
+    s.c_pixel_stride = f.c_pixel_stride;
+    s.c_row_stride = f.c_row_stride;
+    s.sx = f.sx;
+    s.sy = f.sy;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) s.m[i] = f.m[i];
+    s.oy = f.oy;
+    s.oc = f.oc;
+    s.shift = f.shift;
+    s.mask = f.mask;
+    return s;
+}
+
 // the frame types that exist for single-channel plans with float32 accumulation only
 template <typename FT>
 constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT> || kFrameWords<FT> || kFrameStrided<FT>;
 template <typename FT>
-constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT> || kFrameYuv<FT>;
+constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT> || kFrameYuv<FT> || kFrameYuv16<FT>;
 // (host) the bytes of one frame pixel as the host-pointer forms stage it -- float frames carry the channels of the plan; a view is
 // staged by its span -- and the suffix of a frame type's entry points
 template <typename FT>
@@ -532,6 +621,11 @@ __device__ __forceinline__ float unit_edge_column(const P010Src& src, int ch, in
 }
 // and of a planar / packed YUV batch
 __device__ __forceinline__ float unit_edge_column(const YuvSrc& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
+                                                  int src_h, int src_y0, int lane) {
+    return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
+}
+// and of a 16-bit YUV batch
+__device__ __forceinline__ float unit_edge_column(const Yuv16Src& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
                                                   int src_h, int src_y0, int lane) {
     return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
 }

@@ -259,7 +259,9 @@ struct YuvStage {
     int of[3];                   // plane (y, u, v) -> interval
     size_t delta[3];             // plane -> offset inside its interval
 };
-inline YuvStage yuv_stage(const silent_yuv_frames* v, size_t y_span, size_t c_span) {
+// (S: silent_yuv_frames or silent_yuv16_frames -- the planes' addresses and their spans in bytes are all that matters)
+template <class S>
+inline YuvStage yuv_stage(const S* v, size_t y_span, size_t c_span) {
     const uintptr_t a[3] = {reinterpret_cast<uintptr_t>(v->y), reinterpret_cast<uintptr_t>(v->u), reinterpret_cast<uintptr_t>(v->v)};
     const size_t len[3] = {y_span, c_span, c_span};
     int order[3] = {0, 1, 2};
@@ -286,6 +288,86 @@ inline YuvStage yuv_stage(const silent_yuv_frames* v, size_t y_span, size_t c_sp
         st.delta[p] = (size_t)(a[p] - lo);
     }
     return st;
+}
+// Planar / semi-planar / packed 16-bit YUV (silent_pyramid_yuv16, silent_yuv16_to_rgb; silent_hip.h).  check_yuv16: check_yuv's list
+// with 2-byte elements (a row or plane ends 2 bytes behind its last element's offset), then what uint16 elements add, in check_p010's
+// order -- m / oy / oc finite, 2-byte aligned planes, even strides -- and the position of the code (depth, shift).
+using Yuv16 = silent::FrameYuv16;
+inline int check_yuv16(silent_ctx* ctx, const char* who, bool has_plan, long long H, long long W, const silent_yuv16_frames* v, int n_frames,
+                       size_t* y_span, size_t* c_span) {
+    if (!has_plan || !v || !v->y || !v->u || !v->v) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    const int sx = v->chroma_shift_x, sy = v->chroma_shift_y;
+    if ((sx != 0 && sx != 1) || (sy != 0 && sy != 1)) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a chroma shift must be 0 or 1");
+    if (H < 1 || W < 1 || (sy && (H & 1)) || (sx && (W & 1)))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a subsampled axis needs an even extent (H for chroma_shift_y = 1, W for chroma_shift_x = 1)");
+    if (v->y_pixel_stride < 2 || v->c_pixel_stride < 2) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a pixel stride is below 2");
+    typedef unsigned __int128 u128;
+    const long long ch = H >> sy, cw = W >> sx;
+    const u128 yrow = (u128)(W - 1) * (u128)v->y_pixel_stride + 2, crow = (u128)(cw - 1) * (u128)v->c_pixel_stride + 2;
+    if (v->y_row_stride <= 0 || (u128)v->y_row_stride < yrow)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_row_stride is below (W - 1) * y_pixel_stride + 2");
+    if (v->c_row_stride <= 0 || (u128)v->c_row_stride < crow)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": c_row_stride is below ((W >> sx) - 1) * c_pixel_stride + 2");
+    const u128 yf = (u128)(H - 1) * (u128)v->y_row_stride + yrow, cf = (u128)(ch - 1) * (u128)v->c_row_stride + crow;
+    if (n_frames > 1 && (v->y_frame_stride <= 0 || (u128)v->y_frame_stride < yf))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_frame_stride is below the luma plane's extent");
+    if (n_frames > 1 && (v->c_frame_stride <= 0 || (u128)v->c_frame_stride < cf))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": c_frame_stride is below a chroma plane's extent");
+    const u128 ya = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->y_frame_stride : 0) + yf;
+    const u128 ca = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->c_frame_stride : 0) + cf;
+    if (ya > (u128)0x7fffffffffffffffll || ca > (u128)0x7fffffffffffffffll)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a plane spans more than 2^63 bytes");
+    bool finite = std::isfinite(v->oy) && std::isfinite(v->oc);
+    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(v->m[i]);
+    if (!finite) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": m, oy and oc must be finite");
+    if ((reinterpret_cast<uintptr_t>(v->y) | reinterpret_cast<uintptr_t>(v->u) | reinterpret_cast<uintptr_t>(v->v)) & 1u)
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y, u and v must be 2-byte aligned (uint16 elements)");
+    if (((v->y_pixel_stride | v->c_pixel_stride | v->y_row_stride | v->c_row_stride) & 1) || (n_frames > 1 && ((v->y_frame_stride | v->c_frame_stride) & 1)))
+        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a stride is odd (uint16 elements)");
+    if (v->depth < 8 || v->depth > 16) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": depth must be 8 .. 16");
+    if (v->shift < 0 || v->shift + v->depth > 16) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": shift must be 0 .. 16 - depth");
+    if (y_span) *y_span = (size_t)ya;
+    if (c_span) *c_span = (size_t)ca;
+    return SILENT_OK;
+}
+// f(frames) with a checked struct (the planes at y / u / v: those of the struct, or their staged copies) as the frame kind that reads
+// it: a struct that IS P010 as P010 (the kernels of silent_pyramid_p010, which read the (U, V) elements of a pixel as one pair; with
+// shift == 16 - depth the mask changes nothing), any other as Yuv16 -- like with_yuv for a struct that is NV12
+template <class F>
+int with_yuv16(const silent_yuv16_frames* v, const uint16_t* y, const uint16_t* u, const uint16_t* vv, int n_frames, F&& f) {
+    if (v->y_pixel_stride == 2 && v->c_pixel_stride == 4 && vv == u + 1 && v->chroma_shift_x == 1 && v->chroma_shift_y == 1 &&
+        v->shift == 16 - v->depth) {
+        P010 s;
+        s.y = y;
+        s.uv = u;
+        s.y_row_stride = v->y_row_stride;
+        s.uv_row_stride = v->c_row_stride;
+        s.y_frame_stride = n_frames > 1 ? v->y_frame_stride : 0;
+        s.uv_frame_stride = n_frames > 1 ? v->c_frame_stride : 0;
+        for (int i = 0; i < 9; ++i) s.m[i] = v->m[i];
+        s.oy = v->oy;
+        s.oc = v->oc;
+        s.shift = v->shift;
+        return f(&s);
+    }
+    Yuv16 s;
+    s.y = y;
+    s.u = u;
+    s.v = vv;
+    s.y_pixel_stride = v->y_pixel_stride;
+    s.y_row_stride = v->y_row_stride;
+    s.y_frame_stride = n_frames > 1 ? v->y_frame_stride : 0;
+    s.c_pixel_stride = v->c_pixel_stride;
+    s.c_row_stride = v->c_row_stride;
+    s.c_frame_stride = n_frames > 1 ? v->c_frame_stride : 0;
+    s.sx = v->chroma_shift_x;
+    s.sy = v->chroma_shift_y;
+    for (int i = 0; i < 9; ++i) s.m[i] = v->m[i];
+    s.oy = v->oy;
+    s.oc = v->oc;
+    s.shift = v->shift;
+    s.mask = (1u << v->depth) - 1u;
+    return f(&s);
 }
 // The same for a silent_frame_view16: one uint16 element per pixel (the bounds of check_view with 2 for `channels`), and 2-byte alignment
 // of every address a kernel forms -- an even data address and even strides.

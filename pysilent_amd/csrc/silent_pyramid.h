@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void pyramid_unit_kernel(frame_param<FT> frame
                                                            float* __restrict__ pyr, const PyrTabT<F64> tab) {
     static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && (C == 1 || (C == 3 && kFrameBytes<FT>)))),
                   "uint8 / uint16 frames: one channel (packed uint8 also three interleaved channels), float32 accumulation");
-    static_assert(!kFrameRgbSrc<FT> || (C == 3 && !F64), "strided uint8 colour views with the channels kept, NV12 / P010 / YUV surfaces: three channels, float32 accumulation");
+    static_assert(!kFrameRgbSrc<FT> || (C == 3 && !F64), "strided uint8 colour views with the channels kept, NV12 / P010 / YUV / 16-bit YUV surfaces: three channels, float32 accumulation");
     constexpr int R = kUnitTH;
     const unsigned bid = blockIdx.x;
     const int frame = (int)(bid / (unsigned)tab.unit_tiles_per_frame);
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void pyramid_region_kernel(frame_param<FT> fra
                                                              float* __restrict__ pyr, const PyrTabT<F64> tab) {
     static_assert(kFrameType<FT> && (!kFrameNarrow<FT> || (!F64 && (C == 1 || (C == 3 && kFrameBytes<FT>)))),
                   "uint8 / uint16 frames: one channel (packed uint8 also three interleaved channels), float32 accumulation");
-    static_assert(!kFrameRgbSrc<FT> || (C == 3 && !F64), "strided uint8 colour views with the channels kept, NV12 / P010 / YUV surfaces: three channels, float32 accumulation");
+    static_assert(!kFrameRgbSrc<FT> || (C == 3 && !F64), "strided uint8 colour views with the channels kept, NV12 / P010 / YUV / 16-bit YUV surfaces: three channels, float32 accumulation");
     constexpr int RW = region_w(C), SW = region_sw(C), SH = region_sh(C), ROWF = SW * C, VR = region_vr(C);
     __shared__ __attribute__((aligned(16))) float s_src[SH * ROWF];
     __shared__ __attribute__((aligned(16))) acc_t<F64> s_v[VR * ROWF];
@@ -432,7 +432,8 @@ struct BorderTab {
 // flight instead of 36) -- inside the walk kernel, whose 7 waves per SIMD must not pay for this path's registers
 // FT: float, or unsigned char at C == 3 (packed interleaved uint8 colour frames: the byte widened at the load), or FrameStridedRgb
 // (the same bytes in a strided view, by value), or FrameNv12 / FrameP010 (an NV12 / P010 surface, by value: the channel converted at
-// the load), or FrameYuv (planar / packed 8-bit YUV, by value: three byte loads per tap)
+// the load), or FrameYuv (planar / packed 8-bit YUV, by value: three byte loads per tap), or FrameYuv16 (16-bit YUV, by value: three
+// 2-byte loads per tap)
 template <int C, bool LEAN = false, typename FT = float>
 __device__ __forceinline__ void pyramid_border_px(frame_param<FT> frames, float* __restrict__ pyr, const PyrTab& tab,
                                                   const BorderTab& bt, long long gid, int n_frames) {
@@ -485,7 +486,7 @@ __device__ __forceinline__ void pyramid_border_px(frame_param<FT> frames, float*
                 if constexpr ((kFrameNv12<FT> || kFrameP010<FT>) && LEAN) {
                     if (i == 3) asm volatile("" ::: "memory");
                 }
-                if constexpr (kFrameYuv<FT> && LEAN) {
+                if constexpr ((kFrameYuv<FT> || kFrameYuv16<FT>) && LEAN) {
                     if (i == 2 || i == 4) asm volatile("" ::: "memory");
                 }
                 a = __builtin_fmaf(wy[i], src.at(yi[i] + lv.src_y0, x, ch), a);
@@ -562,6 +563,21 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const FrameYuv frames, 
     if (p >= (long long)H * W) return;
     const int y = (int)(p / W), x = (int)(p - (long long)y * W);
     const YuvSrc src = frame_of(frames, frame);
+    float yv, uv, vv;
+    src.yuv(y, x, yv, uv, vv);
+    float* __restrict__ dst = rgb + ((long long)frame * H * W + p) * 3;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) dst[ch] = nv12_channel(yv, uv, vv, src.m[3 * ch], src.m[3 * ch + 1], src.m[3 * ch + 2]);
+}
+
+// silent_yuv16_to_rgb: the same for a planar / semi-planar / packed 16-bit YUV batch (Yuv16Src::yuv, i.e. yuv16_values, + nv12_channel)
+template <int C = 3>
+__global__ __launch_bounds__(256) void yuv16_to_rgb_kernel(const FrameYuv16 frames, float* __restrict__ rgb, int H, int W, int blocks_per_frame) {
+    const int frame = (int)(blockIdx.x / (unsigned)blocks_per_frame);
+    const long long p = (long long)(blockIdx.x - (unsigned)frame * (unsigned)blocks_per_frame) * 256 + threadIdx.x;
+    if (p >= (long long)H * W) return;
+    const int y = (int)(p / W), x = (int)(p - (long long)y * W);
+    const Yuv16Src src = frame_of(frames, frame);
     float yv, uv, vv;
     src.yuv(y, x, yv, uv, vv);
     float* __restrict__ dst = rgb + ((long long)frame * H * W + p) * 3;

@@ -909,8 +909,8 @@ static int pyramid_rgb8_checks(silent_ctx* ctx, const char* who, const silent_py
     return SILENT_OK;
 }
 
-// FT: unsigned char, ViewRgb (silent_pyramid_rgb8_view on a view that is not packed), Nv12 (silent_pyramid_nv12) or P010
-// (silent_pyramid_p010); all but the first are checked by the caller
+// FT: unsigned char, ViewRgb (silent_pyramid_rgb8_view on a view that is not packed), Nv12 (silent_pyramid_nv12), P010
+// (silent_pyramid_p010), Yuv (silent_pyramid_yuv) or Yuv16 (silent_pyramid_yuv16); all but the first are checked by the caller
 template <typename FT>
 static int launch_pyramid_rgb8(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const FT* frames, int n_frames,
                                float* pyr, hipStream_t s) {
@@ -1212,4 +1212,88 @@ SILENT_EXPORT int silent_yuv_to_rgb(silent_ctx* ctx, const silent_yuv_frames* fr
     return yuv_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_yuv_to_rgb");
+}
+
+// Planar / semi-planar / packed 16-bit YUV (silent_hip.h): the struct's own refusals, then the shared ones, under the entry point's
+// name; a struct that is P010 takes the P010 kernels (with_yuv16).  The host forms stage the union of the three spans (yuv_stage: a
+// packed buffer once) and rebase the three pointers; an interval starts at a plane's address, so the staged copies stay 2-byte aligned.
+template <class F>
+static int yuv16_host(silent_ctx* ctx, const silent_yuv16_frames* f, size_t y_span, size_t c_span, int n_frames, void* out, size_t out_bytes, F&& launch) {
+    const YuvStage st = yuv_stage(f, y_span, c_span);
+    HostStage hs(ctx);
+    int in[3] = {0, 0, 0};
+    for (int i = 0; i < st.n; ++i) in[i] = hs.in(st.start[i], st.bytes[i]);
+    const int o = hs.out(out, out_bytes);
+    return hs.run([&] {
+        const uint16_t* p[3];
+        for (int k = 0; k < 3; ++k) p[k] = reinterpret_cast<const uint16_t*>(hs.dev<uint8_t>(in[st.of[k]]) + st.delta[k]);
+        return with_yuv16(f, p[0], p[1], p[2], n_frames, [&](auto frames) { return launch(frames, hs.dev<float>(o), (hipStream_t) nullptr); });
+    });
+}
+
+static int pyramid_yuv16(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_yuv16_frames* f, int n_frames, float* pyr,
+                         silent_stream stream) {
+    const char* who = "silent_pyramid_yuv16";
+    size_t y_span = 0, c_span = 0;
+    TRY(check_yuv16(ctx, who, plan != nullptr, plan ? plan->tab.H : 0, plan ? plan->tab.W : 0, f, n_frames, &y_span, &c_span));
+    TRY(pyramid_checks<float>(ctx, who, plan, true, n_frames, pyr));
+    if (plan->tab.C != 3)
+        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": 16-bit YUV frames are for 3-channel plans (a single-channel plan reads the luma plane through silent_pyramid_view16)");
+    auto launch = [&](auto frames, float* out, hipStream_t s) { return launch_pyramid_rgb8(ctx, who, plan, frames, n_frames, out, s); };
+    if (!host) return with_yuv16(f, f->y, f->u, f->v, n_frames, [&](auto frames) { return launch(frames, pyr, (hipStream_t)stream); });
+    return yuv16_host(ctx, f, y_span, c_span, n_frames, pyr, (size_t)plan->tab.frame_px_out * 3 * 4 * n_frames, launch);
+}
+
+SILENT_EXPORT int silent_pyramid_yuv16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_yuv16_frames* frames, int n_frames,
+                                           float* pyr, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return pyramid_yuv16(ctx, false, plan, frames, n_frames, pyr, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_yuv16_dev");
+}
+
+SILENT_EXPORT int silent_pyramid_yuv16(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_yuv16_frames* frames, int n_frames,
+                                       float* pyr) try {
+    NEED_CTX(ctx);
+    return pyramid_yuv16(ctx, true, plan, frames, n_frames, pyr, nullptr);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_yuv16");
+}
+
+// the converted frames themselves, [n_frames, H, W, 3] float32 (yuv16_to_rgb_kernel, p010_to_rgb_kernel for a struct that is P010)
+static void yuv16_to_rgb_launch(const Yuv16* k, unsigned blocks, hipStream_t s, float* out, int H, int W, int per_frame) {
+    hipLaunchKernelGGL(yuv16_to_rgb_kernel<3>, dim3(blocks), dim3(256), 0, s, *k, out, H, W, per_frame);
+}
+static void yuv16_to_rgb_launch(const P010* k, unsigned blocks, hipStream_t s, float* out, int H, int W, int per_frame) {
+    hipLaunchKernelGGL(p010_to_rgb_kernel<3>, dim3(blocks), dim3(256), 0, s, *k, out, H, W, per_frame);
+}
+static int yuv16_to_rgb(silent_ctx* ctx, bool host, const silent_yuv16_frames* f, int n_frames, int H, int W, float* rgb, silent_stream stream) {
+    const char* who = "silent_yuv16_to_rgb";
+    size_t y_span = 0, c_span = 0;
+    TRY(check_yuv16(ctx, who, true, H, W, f, n_frames, &y_span, &c_span));
+    if (!rgb) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
+    const long long per_frame = ((long long)H * W + 255) / 256;
+    if (per_frame * n_frames > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many blocks for one launch");
+    auto launch = [&](auto frames, float* out, hipStream_t s) {
+        yuv16_to_rgb_launch(frames, (unsigned)(per_frame * n_frames), s, out, H, W, (int)per_frame);
+        return check_launch(ctx, who);
+    };
+    if (!host) return with_yuv16(f, f->y, f->u, f->v, n_frames, [&](auto frames) { return launch(frames, rgb, (hipStream_t)stream); });
+    return yuv16_host(ctx, f, y_span, c_span, n_frames, rgb, (size_t)H * W * 3 * 4 * n_frames, launch);
+}
+
+SILENT_EXPORT int silent_yuv16_to_rgb_dev(silent_ctx* ctx, const silent_yuv16_frames* frames, int n_frames, int H, int W, float* rgb,
+                                          silent_stream stream) try {
+    NEED_CTX(ctx);
+    return yuv16_to_rgb(ctx, false, frames, n_frames, H, W, rgb, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_yuv16_to_rgb_dev");
+}
+
+SILENT_EXPORT int silent_yuv16_to_rgb(silent_ctx* ctx, const silent_yuv16_frames* frames, int n_frames, int H, int W, float* rgb) try {
+    NEED_CTX(ctx);
+    return yuv16_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
+} catch (...) {
+    return on_exception(ctx, "silent_yuv16_to_rgb");
 }

@@ -264,6 +264,25 @@ __host__ __device__ __forceinline__ W3YuvLoad w3_yuv_load(const Walk3Args& args,
     const long long c = r.uv + yuv_c_col(x, v.sx, v.c_pixel_stride);
     return W3YuvLoad{r.y + yuv_y_col(x, v.y_pixel_stride), c, c};
 }
+// ---- and on planar / semi-planar / packed 16-bit YUV (FrameYuv16, silent_pyramid_yuv16): w3_yuv_load with uint16 elements -- THREE
+// 2-byte loads per slot, byte columns x * y_pixel_stride and (x >> sx) * c_pixel_stride (even) behind the same scalar row terms.
+// tests/rgb_yuv16_host_main.cpp enumerates them over whole launches: every offset is the even offset of an element that is some pixel's
+// Y, U or V.
+__host__ __device__ __forceinline__ int w3_yuv16_px(const Walk3Args& args, int A, int lane, int k) { return w3_nv12_px(args, A, lane, k); }
+__host__ __device__ __forceinline__ W3Nv12Row w3_yuv16_row(const Walk3Args& args, const FrameYuv16& v, const W3ViewBlock& b, int s) {
+    const Walk3Plan& p = args.plan[b.plan];
+    const long long yy = w3_mirror_near(b.y_first + s, p.src_h) + p.src_y0;
+    return W3Nv12Row{(long long)b.frame * v.y_frame_stride + yy * v.y_row_stride, (long long)b.frame * v.c_frame_stride + (yy >> v.sy) * v.c_row_stride};
+}
+// THE address function: two bytes each at y_offset from `y`, u_offset from `u` and v_offset from `v` (BYTE offsets, all even)
+__host__ __device__ __forceinline__ W3YuvLoad w3_yuv16_load(const Walk3Args& args, const FrameYuv16& v, int px, unsigned bid, int chunk, int row,
+                                                            int lane, int k) {
+    const W3ViewBlock b = w3_view_block(args, px, bid);
+    const W3Nv12Row r = w3_yuv16_row(args, v, b, chunk * kW3CH + row);
+    const int x = w3_yuv16_px(args, b.A, lane, k);
+    const long long c = r.uv + yuv_c_col(x, v.sx, v.c_pixel_stride);
+    return W3YuvLoad{r.y + yuv_y_col(x, v.y_pixel_stride), c, c};
+}
 
 // FT: the frame element type -- float, or unsigned char (packed interleaved uint8 colour frames [n, H, W, 3], silent_pyramid_rgb8: byte c
 // of pixel (y, x) enters as (float)byte, an unsigned load and an exact conversion).  Only the LOADER touches the frame: the ring stays
@@ -282,14 +301,18 @@ __host__ __device__ __forceinline__ W3YuvLoad w3_yuv_load(const Walk3Args& args,
 // FT = FrameYuv (planar / packed 8-bit YUV, by value): the NV12 loader with three byte loads per slot (w3_yuv_load) -- the byte columns
 // x * y_pixel_stride and (x >> sx) * c_pixel_stride are computed once per block, the row terms are scalar; issue / wait / barrier order
 // is NV12's.  Every address is that of a byte that is some pixel's Y, U or V.
+// FT = FrameYuv16 (16-bit YUV, by value): the FrameYuv loader with three 2-byte loads per slot (w3_yuv16_load) and yuv16_values (shift,
+// mask, offsets) in front of the same nv12_channel; depth and alignment of the code are runtime scalars.
 template <int G, int PX, typename FT = float>
 __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<FT> frames, float* __restrict__ pyr,
                                                                     const Walk3Args args, const WalkBorderArgs border) {
-    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT> || kFrameYuv<FT>,
-                  "float32, packed uint8 or strided uint8 colour frames, NV12 / P010 / YUV surfaces");
+    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT> || kFrameYuv<FT> || kFrameYuv16<FT>,
+                  "float32, packed uint8 or strided uint8 colour frames, NV12 / P010 / YUV / 16-bit YUV surfaces");
     constexpr bool kP10 = kFrameP010<FT>;                            // (uint16 elements, the code in the high bits)
     constexpr bool kYuv = kFrameYuv<FT>;                             // (three byte planes, pixel strides, chroma shifts)
-    constexpr bool kNv = kFrameNv12<FT> || kP10 || kYuv;             // the loader converts (Y, U, V) in registers
+    constexpr bool kY16 = kFrameYuv16<FT>;                           // (three uint16 planes, the code behind shift and mask)
+    constexpr bool kYuv3 = kYuv || kY16;                             // three loads per slot, byte columns per lane
+    constexpr bool kNv = kFrameNv12<FT> || kP10 || kYuv3;            // the loader converts (Y, U, V) in registers
     constexpr bool kBytes = kFrameBytes<FT> || kFrameRgbView<FT>;   // the loader widens bytes in registers
     static_assert(G == stream_pad_levels(G), "row programs are padded to 4 or 7 levels");
     static_assert(PX == 36 || PX == 32 || PX == 28 || PX == 24, "");
@@ -334,7 +357,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
         typedef typename std::conditional<kFrameRgbSrc<FT>, unsigned char, FT>::type ET;   // element of a frame row
         const ET* __restrict__ src;
         if constexpr (kFrameRgbView<FT>) src = frames.data;    // (rows: w3_view_row)
-        else if constexpr (kP10) src = reinterpret_cast<const unsigned char*>(frames.y);   // (rows: w3_p010_row; strides are bytes)
+        else if constexpr (kP10 || kY16) src = reinterpret_cast<const unsigned char*>(frames.y);   // (rows: w3_p010_row / w3_yuv16_row; strides are bytes)
         else if constexpr (kNv) src = frames.y;                // (rows: w3_nv12_row)
         else src = frames + (long long)frame * args.H * args.W * 3;
         const int rowf = args.W * 3;                           // floats (uint8 frames: bytes) of a FRAME row
@@ -354,7 +377,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
             constexpr int kNvLoads = w3_nv12_row_loads(PX);
             int nvx[kNv ? kNvLoads : 1];                         // NV12: the lane's frame column per load slot
             int nvd = 0;                                         // and ring float of channel 0 of its slot-0 pixel minus 3 lane
-            long long yuy[kYuv ? kNvLoads : 1], yuc[kYuv ? kNvLoads : 1];   // YUV: its byte column in a luma / chroma row
+            long long yuy[kYuv3 ? kNvLoads : 1], yuc[kYuv3 ? kNvLoads : 1];   // YUV: its byte column in a luma / chroma row
             (void)nvx;
             (void)nvd;
             (void)yuy;
@@ -364,7 +387,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                 nvd = 3 * w3_nv12_p0(vb.A) - vb.A;
 #pragma unroll
                 for (int k = 0; k < kNvLoads; ++k) nvx[k] = w3_nv12_px(args, vb.A, lane, k);
-                if constexpr (kYuv) {
+                if constexpr (kYuv3) {
 #pragma unroll
                     for (int k = 0; k < kNvLoads; ++k) {
                         yuy[k] = yuv_y_col(nvx[k], frames.y_pixel_stride);
@@ -393,16 +416,28 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                 // one memory latency per chunk) -- a group's loads (Y byte + chroma pair per slot) are all in flight before one is
                 // consumed; a smaller group reuses the registers and pays a latency per group (measured slower:
                 // profiles/rgb_nv12/README.md)
-                constexpr int kNvRows = kYuv ? SILENT_W3_YUV_ROWS : SILENT_W3_NV_ROWS;
-                typename std::conditional<kP10, unsigned short, unsigned char>::type nvy[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];
+                constexpr int kNvRows = kYuv3 ? SILENT_W3_YUV_ROWS : SILENT_W3_NV_ROWS;
+                typename std::conditional<kP10 || kY16, unsigned short, unsigned char>::type nvy[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];
                 typename std::conditional<kP10, unsigned, typename std::conditional<kYuv, unsigned char, unsigned short>::type>::type
-                    nvc[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];      // (YUV: the U byte)
-                unsigned char nvw[kYuv ? kNvRows : 1][kYuv ? kNvLoads : 1];   // YUV: the V byte
+                    nvc[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];      // (YUV: the U byte; 16-bit YUV: the U element)
+                typename std::conditional<kY16, unsigned short, unsigned char>::type
+                    nvw[kYuv3 ? kNvRows : 1][kYuv3 ? kNvLoads : 1];  // YUV: the V byte; 16-bit YUV: the V element
                 (void)nvy;
                 (void)nvc;
                 (void)nvw;
                 auto nv_load = [&](int g, int r) {                // row g + r of the chunk into register row r
-                    if constexpr (kYuv) {
+                    if constexpr (kY16) {
+                        const W3Nv12Row row = w3_yuv16_row(args, frames, vb, c * kW3CH + g + r);
+                        const unsigned char* yr = src + row.y;
+                        const unsigned char* ur = reinterpret_cast<const unsigned char*>(frames.u) + row.uv;
+                        const unsigned char* vr = reinterpret_cast<const unsigned char*>(frames.v) + row.uv;
+#pragma unroll
+                        for (int k = 0; k < kNvLoads; ++k) {
+                            __builtin_memcpy(&nvy[r][k], yr + yuy[k], 2);
+                            __builtin_memcpy(&nvc[r][k], ur + yuc[k], 2);
+                            __builtin_memcpy(&nvw[r][k], vr + yuc[k], 2);
+                        }
+                    } else if constexpr (kYuv) {
                         const W3Nv12Row row = w3_yuv_row(args, frames, vb, c * kW3CH + g + r);
                         const unsigned char* yr = src + row.y;
                         const unsigned char* ur = frames.u + row.uv;
@@ -483,7 +518,9 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
 #pragma unroll
                             for (int k = 0; k < kNvLoads; ++k) {
                                 float yv, uv, vv;
-                                if constexpr (kYuv) {
+                                if constexpr (kY16) {
+                                    yuv16_values(nvy[r][k], nvc[r][k], nvw[r][k], frames.oy, frames.oc, frames.shift, frames.mask, yv, uv, vv);
+                                } else if constexpr (kYuv) {
                                     yv = __fsub_rn((float)nvy[r][k], frames.oy);
                                     uv = (float)((int)nvc[r][k] - 128), vv = (float)((int)nvw[r][k] - 128);
                                 } else if constexpr (kP10) {

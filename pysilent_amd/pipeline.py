@@ -171,8 +171,15 @@ class LineEndPipeline(object):
         # UVC webcam (yuyv[:, :, 0::2], yuyv[:, :, 1::4], yuyv[:, :, 3::4]); util.zoom.yuv_planes cuts them out of surfaces -- read in
         # place by silent_pyramid_yuv_dev, one byte per load; pyramid, maps and keypoints are those of the float32 pipeline on
         # _runtime.yuv_to_rgb(planes, fmt=...), bit for bit.  The nv12_* keywords describe the conversion, as for "nv12".
-        if self._p010:
-            self.nv12_m, self.nv12_oy, self.nv12_oc = _runtime.p010_coefficients(nv12_matrix, nv12_range, nv12_order, self._p010)
+        # rgb_frame_format one of _runtime.YUV16_FORMATS ("yuv420p10", "yuv422p10msb", "yuv444p16" ...): the same triple as UINT16 GPU
+        # views -- yuv420p10le / I010 planes of a software decoder (the code in the low bits), P210 / P410 surfaces and packed Y210 (the
+        # code in the high bits: "...msb"); util.zoom.yuv16_planes cuts them out of surfaces -- read in place by
+        # silent_pyramid_yuv16_dev, one element per load; pyramid, maps and keypoints are those of the float32 pipeline on
+        # _runtime.yuv16_to_rgb(planes, fmt=...), bit for bit.  The conversion is P010's (_runtime.p010_coefficients at the format's
+        # depth; "bt2020" is accepted).
+        if self._p010 or self._yuv16:
+            self.nv12_m, self.nv12_oy, self.nv12_oc = _runtime.p010_coefficients(nv12_matrix, nv12_range, nv12_order,
+                                                                                 self._p010 or self._yuv16[2])
         else:
             self.nv12_m, self.nv12_oy = _runtime.nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
         # accumulation="float64" (mode "gray"): every op sums its taps in float64 and rounds once to float32, like the CPU oracle
@@ -360,6 +367,11 @@ class LineEndPipeline(object):
             sh = 16 - self._p010
             return ((torch.randint(0, 1 << self._p010, (self.batch, h, w), device=self.tdev) << sh).to(torch.uint16),
                     (torch.randint(0, 1 << self._p010, (self.batch, h // 2, w // 2, 2), device=self.tdev) << sh).to(torch.uint16))
+        if self._yuv16:
+            h, w = self.frame_shape[:2]
+            sx, sy, depth, shift = self._yuv16
+            return tuple((torch.randint(0, 1 << depth, sh, device=self.tdev) << shift).to(torch.uint16)
+                         for sh in ((self.batch, h, w), (self.batch, h >> sy, w >> sx), (self.batch, h >> sy, w >> sx)))
         if self._yuv:
             h, w = self.frame_shape[:2]
             sx, sy = self._yuv
@@ -614,7 +626,7 @@ class LineEndPipeline(object):
         rgb_frame_format="nv12" counts 1.5 bytes per pixel: the luma byte and half a chroma pair; "p010" / "p012" / "p016" 3 bytes per
         pixel: the luma element and half a pair of elements; "yuv420" / "yuv422" / "yuv444" 1 + 2 / 2^(sx + sy) bytes per pixel --
         1.5, 2 and 3: the luma byte and the pixel's share of a U and a V byte, whatever lies between them in a packed buffer not
-        counted)."""
+        counted; the 16-bit triples of YUV16_FORMATS twice that -- 3, 4 and 6)."""
         h, w, fc = self.frame_shape
         c = self.channels
         if self.crop_px is not None:
@@ -634,6 +646,8 @@ class LineEndPipeline(object):
             return 0.5
         if self._p010:
             return 1.0
+        if self._yuv16:                                              # 2 (1 + 2 / 2^(sx + sy)) / 3 = 1, 4 / 3, 2 -- exact
+            return fractions.Fraction(2 * (2 ** sum(self._yuv16[:2]) + 2), 3 * 2 ** sum(self._yuv16[:2]))
         if self._yuv:                                                # (1 + 2 / 2^(sx + sy)) / 3 = 0.5, 2 / 3, 1.0 -- exact
             return fractions.Fraction(2 ** sum(self._yuv) + 2, 3 * 2 ** sum(self._yuv))
         return {"uint8": 1, "uint16": 2}.get(self.frame_dtype, 4)
@@ -652,6 +666,11 @@ class LineEndPipeline(object):
     def _yuv(self):
         """The chroma shifts (sx, sy) of a mode "rgb" pipeline reading a (y, u, v) triple ("yuv420" / "yuv422" / "yuv444"), else None."""
         return _runtime.YUV_SHIFTS.get(getattr(self, "rgb_frame_format", "interleaved"))
+
+    @property
+    def _yuv16(self):
+        """(sx, sy, depth, shift) of a mode "rgb" pipeline reading a (y, u, v) triple of uint16 views (_runtime.YUV16_FORMATS), else None."""
+        return _runtime.YUV16_FORMATS.get(getattr(self, "rgb_frame_format", "interleaved"))
 
     @property
     def _frame_torch_dtype(self):
@@ -694,7 +713,9 @@ class LineEndPipeline(object):
                 + ((", %s read in place (uint16 Y + UV planes, 3 bytes per pixel, converted in registers)" % self.rgb_frame_format.upper())
                    if self._p010 else "")
                 + ((", %s read in place (a (y, u, v) triple of uint8 views, %.1f bytes per pixel, converted in registers)"
-                    % (self.rgb_frame_format.upper(), 3 * float(self._frame_bytes))) if self._yuv else ""))
+                    % (self.rgb_frame_format.upper(), 3 * float(self._frame_bytes))) if self._yuv else "")
+                + ((", %s read in place (a (y, u, v) triple of uint16 views, %d bytes per pixel, converted in registers)"
+                    % (self.rgb_frame_format.upper(), int(3 * self._frame_bytes))) if self._yuv16 else ""))
 
     # -- launches --------------------------------------------------------------------------------------
     def _stream(self):
@@ -716,6 +737,15 @@ class LineEndPipeline(object):
             raise ValueError("frames must be a triple (y, u, v) of uint8 GPU planes [%d, %d, %d], [%d, %d, %d] and [%d, %d, %d]"
                              % ((self.batch,) + self.frame_shape[:2] + 2 * (self.batch, self.frame_shape[0] >> sy, self.frame_shape[1] >> sx)))
         return _lib.yuv_ptr(args)
+
+    def _yuv16_arg(self, frames):
+        """The const silent_yuv16_frames* of a triple (y, u, v) of uint16 GPU views of this pipeline's batch (refused: anything else)."""
+        args, n, dev = _runtime.yuv16_frames_of(frames, self.frame_shape[:2], self.rgb_frame_format, self.nv12_m, self.nv12_oy, self.nv12_oc)
+        if not dev or n != self.batch:
+            sx, sy = self._yuv16[:2]
+            raise ValueError("frames must be a triple (y, u, v) of uint16 GPU planes [%d, %d, %d], [%d, %d, %d] and [%d, %d, %d]"
+                             % ((self.batch,) + self.frame_shape[:2] + 2 * (self.batch, self.frame_shape[0] >> sy, self.frame_shape[1] >> sx)))
+        return _lib.yuv16_ptr(args)
 
     def _p010_arg(self, frames):
         """The const silent_p010_frames* of a pair (y, uv) of uint16 GPU planes of this pipeline's batch (refused: anything else)."""
@@ -750,6 +780,10 @@ class LineEndPipeline(object):
         return frame_ptr(frames.data_ptr())
 
     def run_pyramid(self, frames, stream=None):
+        if self._yuv16:                                              # (mode "rgb", rgb_frame_format one of YUV16_FORMATS)
+            self.ctx.check(self._lib.silent_pyramid_yuv16_dev(self.ctx.handle, self.plan.handle, self._yuv16_arg(frames), self.batch,
+                                                              C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
+            return
         if self._yuv:                                                # (mode "rgb", rgb_frame_format "yuv420" / "yuv422" / "yuv444")
             self.ctx.check(self._lib.silent_pyramid_yuv_dev(self.ctx.handle, self.plan.handle, self._yuv_arg(frames), self.batch,
                                                             C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
@@ -951,7 +985,7 @@ class LineEndPipeline(object):
         no cast launch and no float32 frame buffer.  A frame_dtype="uint16" pipeline likewise takes uint16 host frames only, and a
         mode "rgb" pipeline with rgb_frame_dtype="uint8" uint8 host frames [batch, H, W, 3] only."""
         torch = self.torch
-        if self._nv12 or self._p010 or self._yuv:
+        if self._nv12 or self._p010 or self._yuv or self._yuv16:
             return self._step_host_nv12(frames)
         if isinstance(frames, np.ndarray):
             src = torch.from_numpy(np.ascontiguousarray(frames))
@@ -1030,12 +1064,14 @@ class LineEndPipeline(object):
         shapes = ((self.batch, h, w), (self.batch, h // 2, w // 2, 2))
         if self._yuv:     # (a (y, u, v) triple of uint8 arrays of any strides: three planes in the ring, packed by the staging copy)
             shapes = ((self.batch, h, w),) + 2 * ((self.batch, h >> self._yuv[1], w >> self._yuv[0]),)
-        # (rgb_frame_format "p010" / "p012" / "p016": the same ring with uint16 planes)
-        np_dtype, t_dtype = (np.uint16, torch.uint16) if self._p010 else (np.uint8, torch.uint8)
+        if self._yuv16:   # (the same triple as uint16 arrays)
+            shapes = ((self.batch, h, w),) + 2 * ((self.batch, h >> self._yuv16[1], w >> self._yuv16[0]),)
+        # (rgb_frame_format "p010" / "p012" / "p016" and the 16-bit triples: the same ring with uint16 planes)
+        np_dtype, t_dtype = (np.uint16, torch.uint16) if (self._p010 or self._yuv16) else (np.uint8, torch.uint8)
         if not isinstance(frames, (tuple, list)) or len(frames) != len(shapes) or any(
                 not isinstance(p, np.ndarray) or p.dtype != np_dtype or tuple(p.shape) != sh for p, sh in zip(frames, shapes)):
             raise ValueError("step_host of an rgb_frame_format=%r pipeline takes a %s of %s arrays of shapes %s"
-                             % (self.rgb_frame_format, "triple" if self._yuv else "pair", np.dtype(np_dtype).name,
+                             % (self.rgb_frame_format, "triple" if (self._yuv or self._yuv16) else "pair", np.dtype(np_dtype).name,
                                 " and ".join(str(sh) for sh in shapes)))
         cs = self._copy_stream_of_the_ingest()
         ring = self._ingest.setdefault("nv12", {"slots": [], "next": 0})

@@ -4,3 +4,4 @@ from .to_image_list import zoom_tensor_to_image_list as to_image_list
 from .nv12 import nv12_planes
 from .p010 import p010_planes
 from .yuv import yuv_planes
+from .yuv16 import yuv16_planes, YUV16_LAYOUTS
