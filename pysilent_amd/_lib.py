@@ -309,47 +309,35 @@ def view16_ptr(view):
     return C.pointer(FrameView16(int(address), int(pixel_stride), int(row_stride), int(frame_stride)))
 
 
-def nv12_ptr(frames):
-    """(y address, uv address, y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride, m, oy) -- what _runtime.nv12_frames_of
-    returns; m: 9 floats, row k the output channel k -- as the const silent_nv12_frames* of the NV12 entry points (None: NULL).  The
-    struct is read before the call returns."""
-    if frames is None:
+def struct_ptr(struct, fields):
+    """A tuple of the fields of ``struct`` in their order (an array member, the c_float * 9 matrix, as a sequence) as a pointer to the
+    struct (None: NULL).  The struct is read before the call returns."""
+    if fields is None:
         return None
-    y, uv, yr, yf, ur, uf, m, oy = frames
-    return C.pointer(Nv12Frames(int(y), int(uv), int(yr), int(yf), int(ur), int(uf), (C.c_float * 9)(*[float(v) for v in m]), float(oy)))
+    if len(fields) != len(struct._fields_):
+        raise ValueError("%s takes %d fields, got %d" % (struct.__name__, len(struct._fields_), len(fields)))
+    return C.pointer(struct(*[t(*[float(c) for c in v]) if issubclass(t, C.Array) else (float(v) if t is C.c_float else int(v))
+                              for (_, t), v in zip(struct._fields_, fields)]))
+
+
+def nv12_ptr(frames):
+    """_runtime.nv12_frames_of's tuple as the const silent_nv12_frames* of the NV12 entry points."""
+    return struct_ptr(Nv12Frames, frames)
 
 
 def p010_ptr(frames):
-    """(y address, uv address, y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride, m, oy, oc, shift) -- what
-    _runtime.p010_frames_of returns -- as the const silent_p010_frames* of the P010 entry points (None: NULL).  The struct is read
-    before the call returns."""
-    if frames is None:
-        return None
-    y, uv, yr, yf, ur, uf, m, oy, oc, shift = frames
-    return C.pointer(P010Frames(int(y), int(uv), int(yr), int(yf), int(ur), int(uf), (C.c_float * 9)(*[float(v) for v in m]), float(oy),
-                                float(oc), int(shift)))
+    """_runtime.p010_frames_of's tuple as the const silent_p010_frames* of the P010 entry points."""
+    return struct_ptr(P010Frames, frames)
 
 
 def yuv_ptr(frames):
-    """(y, u, v addresses, y_pixel_stride, y_row_stride, y_frame_stride, c_pixel_stride, c_row_stride, c_frame_stride, chroma_shift_x,
-    chroma_shift_y, m, oy) -- what _runtime.yuv_frames_of returns -- as the const silent_yuv_frames* of the YUV entry points (None:
-    NULL).  The struct is read before the call returns."""
-    if frames is None:
-        return None
-    y, u, v, yp, yr, yf, cp, cr, cf, sx, sy, m, oy = frames
-    return C.pointer(YuvFrames(int(y), int(u), int(v), int(yp), int(yr), int(yf), int(cp), int(cr), int(cf), int(sx), int(sy),
-                               (C.c_float * 9)(*[float(c) for c in m]), float(oy)))
+    """_runtime.yuv_frames_of's tuple as the const silent_yuv_frames* of the YUV entry points."""
+    return struct_ptr(YuvFrames, frames)
 
 
 def yuv16_ptr(frames):
-    """(y, u, v addresses, y_pixel_stride, y_row_stride, y_frame_stride, c_pixel_stride, c_row_stride, c_frame_stride, chroma_shift_x,
-    chroma_shift_y, m, oy, oc, shift, depth) -- what _runtime.yuv16_frames_of returns -- as the const silent_yuv16_frames* of the 16-bit
-    YUV entry points (None: NULL).  The struct is read before the call returns."""
-    if frames is None:
-        return None
-    y, u, v, yp, yr, yf, cp, cr, cf, sx, sy, m, oy, oc, shift, depth = frames
-    return C.pointer(Yuv16Frames(int(y), int(u), int(v), int(yp), int(yr), int(yf), int(cp), int(cr), int(cf), int(sx), int(sy),
-                                 (C.c_float * 9)(*[float(c) for c in m]), float(oy), float(oc), int(shift), int(depth)))
+    """_runtime.yuv16_frames_of's tuple as the const silent_yuv16_frames* of the 16-bit YUV entry points."""
+    return struct_ptr(Yuv16Frames, frames)
 
 
 def gray_entry(family, frame_dtype="float32", frame_channels=1, storage="float32", dev=False, parts=None, frame_layout="packed"):

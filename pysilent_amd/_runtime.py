@@ -7,6 +7,7 @@ Tensors the wrappers accept (the reference accepts ``tf.Tensor`` or ``np.ndarray
   * ``PackedPyramid`` (ragged levels, host or device) -> same, result is a PackedPyramid
 Anything else raises the reference's TypeError.
 """
+import collections
 import ctypes as C
 import os
 
@@ -1014,13 +1015,14 @@ def check_rgb_frame_format(rgb_frame_format, mode="rgb", rgb_frame_dtype="float3
                          "one of 420, 422, 444)" % (rgb_frame_format,))
     if rgb_frame_format != "interleaved":
         name = "rgb_frame_format=%r" % (rgb_frame_format,)
-        wide = rgb_frame_format in P010_DEPTHS or rgb_frame_format in YUV16_FORMATS
+        src, sx, sy = rgb_source(rgb_frame_format)[:3]
+        wide = src.elem == 2
         if mode != "rgb":
             raise ValueError("%s is for mode 'rgb' (mode 'gray' reads the luma plane through frame_layout='strided'%s)"
                              % (name, " with frame_dtype='uint16'" if wide else ""))
         if rgb_frame_dtype != "float32":
             raise ValueError("%s does not combine with rgb_frame_dtype=%r (the planes are %s; the converted "
-                             "channels are float32)" % (name, rgb_frame_dtype, "uint16" if wide else "uint8"))
+                             "channels are float32)" % (name, rgb_frame_dtype, src.dtype))
         if rgb_frame_layout != "packed":
             raise ValueError("%s does not combine with rgb_frame_layout=%r (the planes carry their own pitches)" % (name, rgb_frame_layout))
         if frame_dtype != "float32":
@@ -1030,13 +1032,10 @@ def check_rgb_frame_format(rgb_frame_format, mode="rgb", rgb_frame_dtype="float3
                              % (name, frame_channels))
         if frame_layout != "packed":
             raise ValueError("%s does not combine with frame_layout=%r (frame_layout describes the frames of mode 'gray')" % (name, frame_layout))
-        if rgb_frame_format in YUV_SHIFTS or rgb_frame_format in YUV16_FORMATS:
-            sx, sy = (YUV_SHIFTS.get(rgb_frame_format) or YUV16_FORMATS[rgb_frame_format])[:2]
-            if hw is not None and ((sy and int(hw[0]) % 2) or (sx and int(hw[1]) % 2) or min(int(hw[0]), int(hw[1])) < 1):
-                raise ValueError("%s needs even %s, got %s" % (name, "H and W (4:2:0 chroma)" if sy else "W (4:2:2 chroma)",
-                                                              tuple(int(v) for v in hw)))
-        elif hw is not None and (int(hw[0]) % 2 or int(hw[1]) % 2 or min(int(hw[0]), int(hw[1])) < 2):
-            raise ValueError("%s needs even H and W (4:2:0 chroma), got %s" % (name, tuple(int(v) for v in hw)))
+        # (a pair is 4:2:0: sx = sy = 1, and an even extent >= 1 is >= 2)
+        if hw is not None and ((sy and int(hw[0]) % 2) or (sx and int(hw[1]) % 2) or min(int(hw[0]), int(hw[1])) < 1):
+            raise ValueError("%s needs even %s, got %s" % (name, "H and W (4:2:0 chroma)" if sy else "W (4:2:2 chroma)",
+                                                          tuple(int(v) for v in hw)))
     return rgb_frame_format
 
 
@@ -1068,74 +1067,6 @@ def nv12_coefficients(nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr
         if m.shape != (3, 3) or not np.all(np.isfinite(m)):
             raise ValueError("nv12_matrix must be 'bt601', 'bt709' or a finite 3 x 3 array, got shape %s" % (m.shape,))
     return m.astype(np.float32), np.float32(oy)
-
-
-def nv12_frames_of(planes, hw, m, oy):
-    """A pair (y, uv) of uint8 planes -- both ndarrays or both GPU tensors; y [n, H, W] with element stride 1, uv [n, H / 2, W / 2, 2]
-    with strides (.., .., 2, 1), positive row / frame strides -- as what _lib.nv12_ptr takes: (y address, uv address, y_row_stride,
-    y_frame_stride, uv_row_stride, uv_frame_stride, m, oy).  Returns (that tuple, n, on_device).  Nothing is converted or copied."""
-    if not isinstance(planes, (tuple, list)) or len(planes) != 2:
-        raise ValueError("NV12 frames are a pair (y, uv) of uint8 planes")
-    y, uv = planes
-    dev = is_torch_tensor(y)
-    if not (dev and is_torch_tensor(uv)) and not (isinstance(y, np.ndarray) and isinstance(uv, np.ndarray)):
-        raise TypeError(TYPE_ERROR_MESSAGE)
-    h, w = int(hw[0]), int(hw[1])
-
-    def geometry(p):
-        if dev:
-            import torch
-            if p.dtype != torch.uint8 or not p.is_cuda:
-                raise ValueError("NV12 planes must be uint8 GPU tensors or uint8 ndarrays (nothing is converted), got %s" % (p.dtype,))
-            return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.stride()), int(p.data_ptr())
-        if p.dtype != np.uint8:
-            raise ValueError("NV12 planes must be uint8 GPU tensors or uint8 ndarrays (nothing is converted), got %s" % (p.dtype,))
-        return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.strides), int(p.ctypes.data)
-
-    ys, yst, ya = geometry(y)
-    cs, cst, ca = geometry(uv)
-    if len(ys) != 3 or ys[1:] != (h, w) or ys[0] < 1:
-        raise ValueError("the NV12 luma plane must be [n, %d, %d], got %s" % (h, w, ys))
-    n = ys[0]
-    if cs != (n, h // 2, w // 2, 2):
-        raise ValueError("the NV12 chroma plane must be [%d, %d, %d, 2], got %s" % (n, h // 2, w // 2, cs))
-    if (w > 1 and yst[2] != 1) or cst[3] != 1 or (w > 2 and cst[2] != 2):
-        raise ValueError("NV12 planes: luma bytes of a row and the (U, V) pairs of a chroma row must be adjacent (strides %s, %s)" % (yst, cst))
-    yr, cr = (yst[1] if h > 1 else w), (cst[1] if h > 2 else w)
-    yf, cf = (yst[0] if n > 1 else (h - 1) * yr + w), (cst[0] if n > 1 else (h // 2 - 1) * cr + w)
-    if yr < w or cr < w or yf < (h - 1) * yr + w or cf < (h // 2 - 1) * cr + w:
-        raise ValueError("NV12 planes: rows or frames overlap, or a stride is not positive (strides %s, %s)" % (yst, cst))
-    return (ya, ca, yr, yf, cr, cf, [float(v) for v in np.asarray(m, np.float32).reshape(9)], float(oy)), n, dev
-
-
-class _Nv12Operand(_Operand):
-    """An NV12 batch (nv12_frames_of) as an operand: results are allocated like the planes (empty) and the entry point is called in
-    its _dev form on torch's current stream for GPU planes, in its host form otherwise (call)."""
-
-    def __init__(self, planes, hw, m, oy, ctx=None):
-        args, self.n_frames, self.dev = nv12_frames_of(planes, hw, m, oy)
-        self.packed, self.c, self.extents = False, 3, [(int(hw[0]), int(hw[1]))]
-        self.device = self.stream = None
-        if self.dev:
-            import torch
-            self._torch_device = planes[0].device
-            self.device = self._torch_device.index or 0
-            self.stream = C.c_void_p(torch.cuda.current_stream(self._torch_device).cuda_stream)
-        self.ptr = _lib.nv12_ptr(args)
-        self.buf = tuple(planes)                        # keep alive
-        self.ctx = ctx or get_context(self.device)
-
-
-def nv12_to_rgb(planes, hw, nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", device=None):
-    """The float32 frames [n, H, W, 3] the pyramid kernels see for an NV12 batch (silent_nv12_to_rgb[_dev]: the loaders' own device
-    function, one thread per pixel) -- for display, and as the reference of the bit-identity contract.  planes: nv12_frames_of."""
-    m, oy = nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
-    check_rgb_frame_format("nv12", hw=hw)
-    op = _Nv12Operand(planes, hw, m, oy, None if device is None else get_context(device))
-    h, w = int(hw[0]), int(hw[1])
-    out, optr = op.empty((op.n_frames, h, w, 3))
-    op.call("nv12_to_rgb", op.ptr, op.n_frames, h, w, optr)
-    return out
 
 
 def p010_coefficients(nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", depth=10):
@@ -1174,75 +1105,131 @@ def p010_coefficients(nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr
     return m, np.float32(oy), np.float32(128.0 * s)
 
 
-def p010_frames_of(planes, hw, m, oy, oc, depth):
-    """A pair (y, uv) of uint16 planes -- both ndarrays or both torch.uint16 GPU tensors; y [n, H, W] with element stride 2 bytes,
-    uv [n, H / 2, W / 2, 2] with the two elements of a pair and the pairs of a row adjacent, positive non-overlapping row / frame
-    strides -- as what _lib.p010_ptr takes: (y address, uv address, y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride (BYTES),
-    m, oy, oc, shift = 16 - depth).  Returns (that tuple, n, on_device).  Nothing is converted or copied."""
-    if depth not in (10, 12, 16):
-        raise ValueError("depth must be 10, 12 or 16, got %r" % (depth,))
-    if not isinstance(planes, (tuple, list)) or len(planes) != 2:
-        raise ValueError("P010 frames are a pair (y, uv) of uint16 planes")
-    y, uv = planes
-    dev = is_torch_tensor(y)
-    if not (dev and is_torch_tensor(uv)) and not (isinstance(y, np.ndarray) and isinstance(uv, np.ndarray)):
-        raise TypeError(TYPE_ERROR_MESSAGE)
-    h, w = int(hw[0]), int(hw[1])
+# The YUV-family colour sources, ONE description each: kind (the stem of its entry points, silent_pyramid_<kind> / silent_<kind>_to_rgb,
+# and of _lib.<kind>_ptr), the name its messages use, planes (2: a pair (y, uv); 3: a triple (y, u, v)), the bytes and dtype of an
+# element, its coefficient function, and whether torch CPU tensors pass as host planes (16-bit YUV alone accepts them).  A fifth format
+# adds a row here and its names to rgb_source.
+RgbSource = collections.namedtuple("RgbSource", "kind name planes elem dtype coefficients cpu_tensors")
+RGB_SOURCES = dict((s.kind, s) for s in (RgbSource("nv12", "NV12", 2, 1, "uint8", nv12_coefficients, False),
+                                         RgbSource("p010", "P010", 2, 2, "uint16", p010_coefficients, False),
+                                         RgbSource("yuv", "YUV", 3, 1, "uint8", nv12_coefficients, False),
+                                         RgbSource("yuv16", "16-bit YUV", 3, 2, "uint16", p010_coefficients, True)))
 
-    def geometry(p):
-        if dev:
-            import torch
-            if p.dtype != torch.uint16 or not p.is_cuda:
-                raise ValueError("P010 planes must be uint16 GPU tensors or uint16 ndarrays (nothing is converted), got %s" % (p.dtype,))
-            return tuple(int(s) for s in p.shape), tuple(2 * int(s) for s in p.stride()), int(p.data_ptr())
-        if p.dtype != np.uint16:
-            raise ValueError("P010 planes must be uint16 GPU tensors or uint16 ndarrays (nothing is converted), got %s" % (p.dtype,))
-        return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.strides), int(p.ctypes.data)
 
-    ys, yst, ya = geometry(y)
-    cs, cst, ca = geometry(uv)
+def rgb_source(rgb_frame_format):
+    """(source, sx, sy, depth, shift) of a valid rgb_frame_format -- the format's description and parameters: chroma shifts, bits of a
+    code value, bits below it -- or None for "interleaved"."""
+    if rgb_frame_format == "nv12":
+        return RGB_SOURCES["nv12"], 1, 1, 8, 0
+    if rgb_frame_format in P010_DEPTHS:
+        return RGB_SOURCES["p010"], 1, 1, P010_DEPTHS[rgb_frame_format], 16 - P010_DEPTHS[rgb_frame_format]
+    if rgb_frame_format in YUV_SHIFTS:
+        return (RGB_SOURCES["yuv"],) + YUV_SHIFTS[rgb_frame_format] + (8, 0)
+    if rgb_frame_format in YUV16_FORMATS:
+        return (RGB_SOURCES["yuv16"],) + YUV16_FORMATS[rgb_frame_format]
+    return None
+
+
+def _plane_geometry(src, p):
+    """(shape, BYTE strides, address) of one plane of a source; its dtype must be the source's (nothing is converted)."""
+    text = "%s planes must be %s GPU tensors or %s ndarrays (nothing is converted), got %s" % (src.name, src.dtype, src.dtype, p.dtype)
+    if is_torch_tensor(p):
+        import torch
+        if p.dtype != getattr(torch, src.dtype) or not (p.is_cuda or src.cpu_tensors):
+            raise ValueError(text)
+        return tuple(int(s) for s in p.shape), tuple(src.elem * int(s) for s in p.stride()), int(p.data_ptr())
+    if p.dtype != np.dtype(src.dtype):
+        raise ValueError(text)
+    return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.strides), int(p.ctypes.data)
+
+
+def _pair_fields(src, geo, h, w):
+    """(y address, uv address, y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride) and n of a pair (y, uv): y [n, H, W] with
+    adjacent elements, uv [n, H / 2, W / 2, 2] with the two elements of a pair and the pairs of a row adjacent, positive
+    non-overlapping row / frame strides (BYTES; e: the bytes of an element)."""
+    (ys, yst, ya), (cs, cst, ca) = geo
+    e, strides = src.elem, "strides" if src.elem == 1 else "byte strides"
     if len(ys) != 3 or ys[1:] != (h, w) or ys[0] < 1:
-        raise ValueError("the P010 luma plane must be [n, %d, %d], got %s" % (h, w, ys))
+        raise ValueError("the %s luma plane must be [n, %d, %d], got %s" % (src.name, h, w, ys))
     n = ys[0]
     if cs != (n, h // 2, w // 2, 2):
-        raise ValueError("the P010 chroma plane must be [%d, %d, %d, 2], got %s" % (n, h // 2, w // 2, cs))
-    if (w > 1 and yst[2] != 2) or cst[3] != 2 or (w > 2 and cst[2] != 4):
-        raise ValueError("P010 planes: luma elements of a row and the (U, V) pairs of a chroma row must be adjacent (byte strides %s, %s)" % (yst, cst))
-    yr, cr = (yst[1] if h > 1 else 2 * w), (cst[1] if h > 2 else 2 * w)
-    yf, cf = (yst[0] if n > 1 else (h - 1) * yr + 2 * w), (cst[0] if n > 1 else (h // 2 - 1) * cr + 2 * w)
-    if yr < 2 * w or cr < 2 * w or yf < (h - 1) * yr + 2 * w or cf < (h // 2 - 1) * cr + 2 * w:
-        raise ValueError("P010 planes: rows or frames overlap, or a stride is not positive (byte strides %s, %s)" % (yst, cst))
-    return (ya, ca, yr, yf, cr, cf, [float(v) for v in np.asarray(m, np.float32).reshape(9)], float(oy), float(oc), 16 - depth), n, dev
+        raise ValueError("the %s chroma plane must be [%d, %d, %d, 2], got %s" % (src.name, n, h // 2, w // 2, cs))
+    if (w > 1 and yst[2] != e) or cst[3] != e or (w > 2 and cst[2] != 2 * e):
+        raise ValueError("%s planes: luma %s of a row and the (U, V) pairs of a chroma row must be adjacent (%s %s, %s)"
+                         % (src.name, "bytes" if e == 1 else "elements", strides, yst, cst))
+    yr, cr = (yst[1] if h > 1 else e * w), (cst[1] if h > 2 else e * w)
+    yf, cf = (yst[0] if n > 1 else (h - 1) * yr + e * w), (cst[0] if n > 1 else (h // 2 - 1) * cr + e * w)
+    if yr < e * w or cr < e * w or yf < (h - 1) * yr + e * w or cf < (h // 2 - 1) * cr + e * w:
+        raise ValueError("%s planes: rows or frames overlap, or a stride is not positive (%s %s, %s)" % (src.name, strides, yst, cst))
+    return (ya, ca, yr, yf, cr, cf), n
 
 
-class _P010Operand(_Nv12Operand):
-    """A P010 / P012 / P016 batch (p010_frames_of) as an operand (see _Nv12Operand)."""
+def _triple_fields(src, geo, h, w, sx, sy, fmt):
+    """(y, u, v addresses, y_pixel_stride, y_row_stride, y_frame_stride, c_pixel_stride, c_row_stride, c_frame_stride) and n of a triple
+    (y, u, v): y [n, H, W], u and v [n, H >> sy, W >> sx]; each ANY view with positive strides, u and v with EQUAL strides (BYTES; e:
+    the bytes of an element, uint16 elements at even addresses and strides)."""
+    (ys, yst, ya), (us, ust, ua), (vs, vst, va) = geo
+    e, strides = src.elem, "strides" if src.elem == 1 else "byte strides"
+    if len(ys) != 3 or ys[1:] != (h, w) or ys[0] < 1:
+        raise ValueError("the %s luma plane must be [n, %d, %d], got %s" % (src.name, h, w, ys))
+    n = ys[0]
+    ch, cw = h >> sy, w >> sx
+    if us != (n, ch, cw) or vs != (n, ch, cw):
+        raise ValueError("the %s chroma planes must be [%d, %d, %d], got %s and %s" % (fmt, n, ch, cw, us, vs))
 
-    def __init__(self, planes, hw, m, oy, oc, depth, ctx=None):
-        args, self.n_frames, self.dev = p010_frames_of(planes, hw, m, oy, oc, depth)
-        self.packed, self.c, self.extents = False, 3, [(int(hw[0]), int(hw[1]))]
-        self.device = self.stream = None
-        if self.dev:
-            import torch
-            self._torch_device = planes[0].device
-            self.device = self._torch_device.index or 0
-            self.stream = C.c_void_p(torch.cuda.current_stream(self._torch_device).cuda_stream)
-        self.ptr = _lib.p010_ptr(args)
-        self.buf = tuple(planes)                        # keep alive
-        self.ctx = ctx or get_context(self.device)
+    def fields(st, rows, cols):
+        # (a stride of an axis of extent 1 is never used: the smallest legal value stands in for it)
+        px = st[2] if cols > 1 else e
+        row = st[1] if rows > 1 else (cols - 1) * px + e
+        frame = st[0] if n > 1 else (rows - 1) * row + (cols - 1) * px + e
+        return px, row, frame
+
+    yp, yr, yf = fields(yst, h, w)
+    cp, cr, cf = fields(ust, ch, cw)
+    if fields(vst, ch, cw) != (cp, cr, cf):
+        raise ValueError("%s planes: u and v must have equal strides, got %s and %s" % (src.name, ust, vst))
+    if min(yp, cp) < e or yr < (w - 1) * yp + e or cr < (cw - 1) * cp + e or yf < (h - 1) * yr + (w - 1) * yp + e \
+            or cf < (ch - 1) * cr + (cw - 1) * cp + e:
+        raise ValueError("%s planes: rows or frames overlap, or a stride is not positive (%s %s, %s)" % (src.name, strides, yst, ust))
+    if e == 2 and (yp | yr | yf | cp | cr | cf | ya | ua | va) & 1:
+        raise ValueError("%s planes: an address or a byte stride is odd (uint16 elements; byte strides %s, %s)" % (src.name, yst, ust))
+    return (ya, ua, va, yp, yr, yf, cp, cr, cf), n
 
 
-def p010_to_rgb(planes, hw, depth=10, nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", device=None):
-    """The float32 frames [n, H, W, 3] the pyramid kernels see for a P010 (depth=10) / P012 (12) / P016 (16) batch
-    (silent_p010_to_rgb[_dev]: the loaders' own device functions, one thread per pixel), on the 0 .. 255 scale and not rounded -- for
-    display, and as the reference of the bit-identity contract.  planes: p010_frames_of."""
-    m, oy, oc = p010_coefficients(nv12_matrix, nv12_range, nv12_order, depth)
-    check_rgb_frame_format({10: "p010", 12: "p012", 16: "p016"}[depth], hw=hw)
-    op = _P010Operand(planes, hw, m, oy, oc, depth, None if device is None else get_context(device))
+def rgb_source_frames_of(src, planes, hw, coeffs, sx=1, sy=1, depth=8, shift=0, fmt=None):
+    """The planes of a source -- all GPU tensors, or all ndarrays (torch CPU tensors too where the source takes them) -- as what
+    _lib.<kind>_ptr takes: the fields of the struct in their order, coeffs = (m, oy[, oc]).  Returns (that tuple, n, on_device).
+    Nothing is converted or copied."""
+    if not isinstance(planes, (tuple, list)) or len(planes) != src.planes:
+        raise ValueError("%s frames are a %s of %s planes" % (src.name, "pair (y, uv)" if src.planes == 2 else "triple (y, u, v)", src.dtype))
+    # (GPU tensors: read in place on the device; ndarrays -- and torch CPU tensors, 16-bit YUV -- host memory, staged by the host forms)
+    dev = all(is_torch_tensor(p) and (p.is_cuda or not src.cpu_tensors) for p in planes)
+    if not dev and not all(isinstance(p, np.ndarray) or (src.cpu_tensors and is_torch_tensor(p) and not p.is_cuda) for p in planes):
+        raise TypeError(TYPE_ERROR_MESSAGE)
     h, w = int(hw[0]), int(hw[1])
-    out, optr = op.empty((op.n_frames, h, w, 3))
-    op.call("p010_to_rgb", op.ptr, op.n_frames, h, w, optr)
-    return out
+    geo = [_plane_geometry(src, p) for p in planes]
+    tail = ([float(c) for c in np.asarray(coeffs[0], np.float32).reshape(9)],) + tuple(float(c) for c in coeffs[1:])
+    if src.planes == 2:
+        fields, n = _pair_fields(src, geo, h, w)
+        return fields + tail + ((shift,) if src.elem == 2 else ()), n, dev
+    fields, n = _triple_fields(src, geo, h, w, sx, sy, fmt)
+    return fields + (sx, sy) + tail + ((shift, depth) if src.elem == 2 else ()), n, dev
+
+
+def nv12_frames_of(planes, hw, m, oy):
+    """A pair (y, uv) of uint8 planes -- both ndarrays or both GPU tensors; y [n, H, W] with element stride 1, uv [n, H / 2, W / 2, 2]
+    with strides (.., .., 2, 1), positive row / frame strides -- as what _lib.nv12_ptr takes: (y address, uv address, y_row_stride,
+    y_frame_stride, uv_row_stride, uv_frame_stride, m, oy).  Returns (that tuple, n, on_device).  Nothing is converted or copied."""
+    return rgb_source_frames_of(RGB_SOURCES["nv12"], planes, hw, (m, oy))
+
+
+def p010_frames_of(planes, hw, m, oy, oc, depth):
+    """The same pair as uint16 planes -- both ndarrays or both torch.uint16 GPU tensors -- as what _lib.p010_ptr takes: (y address, uv
+    address, y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride (BYTES), m, oy, oc, shift = 16 - depth).  Returns (that tuple,
+    n, on_device)."""
+    if depth not in (10, 12, 16):
+        raise ValueError("depth must be 10, 12 or 16, got %r" % (depth,))
+    return rgb_source_frames_of(RGB_SOURCES["p010"], planes, hw, (m, oy, oc), depth=depth, shift=16 - depth)
 
 
 def yuv_frames_of(planes, hw, fmt, m, oy):
@@ -1250,148 +1237,37 @@ def yuv_frames_of(planes, hw, fmt, m, oy):
     = YUV_SHIFTS[fmt]; each ANY view with positive strides (the layout lives in the strides: yuyv[:, :, 0::2], yuyv[:, :, 1::4],
     yuyv[:, :, 3::4] is a valid triple), u and v with EQUAL strides -- as what _lib.yuv_ptr takes: (y, u, v addresses, y_pixel_stride,
     y_row_stride, y_frame_stride, c_pixel_stride, c_row_stride, c_frame_stride (BYTES), sx, sy, m, oy).  Returns (that tuple, n,
-    on_device).  Nothing is converted or copied."""
+    on_device)."""
     if fmt not in YUV_SHIFTS:
         raise ValueError("fmt must be 'yuv420', 'yuv422' or 'yuv444', got %r" % (fmt,))
-    sx, sy = YUV_SHIFTS[fmt]
-    if not isinstance(planes, (tuple, list)) or len(planes) != 3:
-        raise ValueError("YUV frames are a triple (y, u, v) of uint8 planes")
-    y, u, v = planes
-    dev = is_torch_tensor(y)
-    if not (dev and is_torch_tensor(u) and is_torch_tensor(v)) and not all(isinstance(p, np.ndarray) for p in planes):
-        raise TypeError(TYPE_ERROR_MESSAGE)
-    h, w = int(hw[0]), int(hw[1])
-
-    def geometry(p):
-        if dev:
-            import torch
-            if p.dtype != torch.uint8 or not p.is_cuda:
-                raise ValueError("YUV planes must be uint8 GPU tensors or uint8 ndarrays (nothing is converted), got %s" % (p.dtype,))
-            return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.stride()), int(p.data_ptr())
-        if p.dtype != np.uint8:
-            raise ValueError("YUV planes must be uint8 GPU tensors or uint8 ndarrays (nothing is converted), got %s" % (p.dtype,))
-        return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.strides), int(p.ctypes.data)
-
-    ys, yst, ya = geometry(y)
-    us, ust, ua = geometry(u)
-    vs, vst, va = geometry(v)
-    if len(ys) != 3 or ys[1:] != (h, w) or ys[0] < 1:
-        raise ValueError("the YUV luma plane must be [n, %d, %d], got %s" % (h, w, ys))
-    n = ys[0]
-    ch, cw = h >> sy, w >> sx
-    if us != (n, ch, cw) or vs != (n, ch, cw):
-        raise ValueError("the %s chroma planes must be [%d, %d, %d], got %s and %s" % (fmt, n, ch, cw, us, vs))
-
-    def strides(st, rows, cols):
-        # (a stride of an axis of extent 1 is never used: the smallest legal value stands in for it)
-        px = st[2] if cols > 1 else 1
-        row = st[1] if rows > 1 else (cols - 1) * px + 1
-        frame = st[0] if n > 1 else (rows - 1) * row + (cols - 1) * px + 1
-        return px, row, frame
-
-    yp, yr, yf = strides(yst, h, w)
-    cp, cr, cf = strides(ust, ch, cw)
-    if strides(vst, ch, cw) != (cp, cr, cf):
-        raise ValueError("YUV planes: u and v must have equal strides, got %s and %s" % (ust, vst))
-    if min(yp, cp) < 1 or yr < (w - 1) * yp + 1 or cr < (cw - 1) * cp + 1 or yf < (h - 1) * yr + (w - 1) * yp + 1 \
-            or cf < (ch - 1) * cr + (cw - 1) * cp + 1:
-        raise ValueError("YUV planes: rows or frames overlap, or a stride is not positive (strides %s, %s)" % (yst, ust))
-    return (ya, ua, va, yp, yr, yf, cp, cr, cf, sx, sy, [float(c) for c in np.asarray(m, np.float32).reshape(9)], float(oy)), n, dev
-
-
-class _YuvOperand(_Nv12Operand):
-    """A planar / packed YUV batch (yuv_frames_of) as an operand (see _Nv12Operand)."""
-
-    def __init__(self, planes, hw, fmt, m, oy, ctx=None):
-        args, self.n_frames, self.dev = yuv_frames_of(planes, hw, fmt, m, oy)
-        self.packed, self.c, self.extents = False, 3, [(int(hw[0]), int(hw[1]))]
-        self.device = self.stream = None
-        if self.dev:
-            import torch
-            self._torch_device = planes[0].device
-            self.device = self._torch_device.index or 0
-            self.stream = C.c_void_p(torch.cuda.current_stream(self._torch_device).cuda_stream)
-        self.ptr = _lib.yuv_ptr(args)
-        self.buf = tuple(planes)                        # keep alive
-        self.ctx = ctx or get_context(self.device)
-
-
-def yuv_to_rgb(planes, hw, fmt="yuv420", nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", device=None):
-    """The float32 frames [n, H, W, 3] the pyramid kernels see for a (y, u, v) triple of format ``fmt`` ("yuv420" / "yuv422" /
-    "yuv444"; silent_yuv_to_rgb[_dev]: the loaders' own device function, one thread per pixel) -- for display, and as the reference
-    of the bit-identity contract.  planes: yuv_frames_of; the conversion: nv12_coefficients."""
-    m, oy = nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
-    check_rgb_frame_format(fmt, hw=hw)
-    op = _YuvOperand(planes, hw, fmt, m, oy, None if device is None else get_context(device))
-    h, w = int(hw[0]), int(hw[1])
-    out, optr = op.empty((op.n_frames, h, w, 3))
-    op.call("yuv_to_rgb", op.ptr, op.n_frames, h, w, optr)
-    return out
+    return rgb_source_frames_of(RGB_SOURCES["yuv"], planes, hw, (m, oy), *YUV_SHIFTS[fmt], fmt=fmt)
 
 
 def yuv16_frames_of(planes, hw, fmt, m, oy, oc):
-    """A triple (y, u, v) of uint16 planes -- all torch.uint16 GPU tensors, or all host arrays (ndarrays or torch CPU tensors); y [n, H, W], u and v [n, H >> sy, W >> sx]
-    with (sx, sy, depth, shift) = YUV16_FORMATS[fmt]; each ANY view with positive strides (the layout lives in the strides:
-    y210[:, :, 0::2], y210[:, :, 1::4], y210[:, :, 3::4] is a valid triple), u and v with EQUAL strides -- as what _lib.yuv16_ptr takes:
-    (y, u, v addresses, y_pixel_stride, y_row_stride, y_frame_stride, c_pixel_stride, c_row_stride, c_frame_stride (BYTES, even), sx,
-    sy, m, oy, oc, shift, depth).  Returns (that tuple, n, on_device).  Nothing is converted or copied."""
+    """The same triple as uint16 planes -- all torch.uint16 GPU tensors, or all host arrays (ndarrays or torch CPU tensors) -- with
+    (sx, sy, depth, shift) = YUV16_FORMATS[fmt] (y210[:, :, 0::2], y210[:, :, 1::4], y210[:, :, 3::4] is a valid triple), as what
+    _lib.yuv16_ptr takes: (y, u, v addresses, y_pixel_stride, y_row_stride, y_frame_stride, c_pixel_stride, c_row_stride, c_frame_stride
+    (BYTES, even), sx, sy, m, oy, oc, shift, depth).  Returns (that tuple, n, on_device)."""
     if fmt not in YUV16_FORMATS:
         raise ValueError("fmt must be one of %s, got %r" % (", ".join(sorted(YUV16_FORMATS)), fmt))
-    sx, sy, depth, shift = YUV16_FORMATS[fmt]
-    if not isinstance(planes, (tuple, list)) or len(planes) != 3:
-        raise ValueError("16-bit YUV frames are a triple (y, u, v) of uint16 planes")
-    y, u, v = planes
-    # (GPU tensors: read in place on the device; ndarrays and torch CPU tensors: host memory, staged by the host forms)
-    dev = all(is_torch_tensor(p) and p.is_cuda for p in planes)
-    if not dev and not all(isinstance(p, np.ndarray) or (is_torch_tensor(p) and not p.is_cuda) for p in planes):
-        raise TypeError(TYPE_ERROR_MESSAGE)
-    h, w = int(hw[0]), int(hw[1])
-
-    def geometry(p):
-        if is_torch_tensor(p):
-            import torch
-            if p.dtype != torch.uint16:
-                raise ValueError("16-bit YUV planes must be uint16 GPU tensors or uint16 ndarrays (nothing is converted), got %s" % (p.dtype,))
-            return tuple(int(s) for s in p.shape), tuple(2 * int(s) for s in p.stride()), int(p.data_ptr())
-        if p.dtype != np.uint16:
-            raise ValueError("16-bit YUV planes must be uint16 GPU tensors or uint16 ndarrays (nothing is converted), got %s" % (p.dtype,))
-        return tuple(int(s) for s in p.shape), tuple(int(s) for s in p.strides), int(p.ctypes.data)
-
-    ys, yst, ya = geometry(y)
-    us, ust, ua = geometry(u)
-    vs, vst, va = geometry(v)
-    if len(ys) != 3 or ys[1:] != (h, w) or ys[0] < 1:
-        raise ValueError("the 16-bit YUV luma plane must be [n, %d, %d], got %s" % (h, w, ys))
-    n = ys[0]
-    ch, cw = h >> sy, w >> sx
-    if us != (n, ch, cw) or vs != (n, ch, cw):
-        raise ValueError("the %s chroma planes must be [%d, %d, %d], got %s and %s" % (fmt, n, ch, cw, us, vs))
-
-    def strides(st, rows, cols):
-        # (a stride of an axis of extent 1 is never used: the smallest legal value stands in for it)
-        px = st[2] if cols > 1 else 2
-        row = st[1] if rows > 1 else (cols - 1) * px + 2
-        frame = st[0] if n > 1 else (rows - 1) * row + (cols - 1) * px + 2
-        return px, row, frame
-
-    yp, yr, yf = strides(yst, h, w)
-    cp, cr, cf = strides(ust, ch, cw)
-    if strides(vst, ch, cw) != (cp, cr, cf):
-        raise ValueError("16-bit YUV planes: u and v must have equal strides, got %s and %s" % (ust, vst))
-    if min(yp, cp) < 2 or yr < (w - 1) * yp + 2 or cr < (cw - 1) * cp + 2 or yf < (h - 1) * yr + (w - 1) * yp + 2 \
-            or cf < (ch - 1) * cr + (cw - 1) * cp + 2:
-        raise ValueError("16-bit YUV planes: rows or frames overlap, or a stride is not positive (byte strides %s, %s)" % (yst, ust))
-    if (yp | yr | yf | cp | cr | cf | ya | ua | va) & 1:
-        raise ValueError("16-bit YUV planes: an address or a byte stride is odd (uint16 elements; byte strides %s, %s)" % (yst, ust))
-    return (ya, ua, va, yp, yr, yf, cp, cr, cf, sx, sy, [float(c) for c in np.asarray(m, np.float32).reshape(9)], float(oy), float(oc),
-            shift, depth), n, dev
+    return rgb_source_frames_of(RGB_SOURCES["yuv16"], planes, hw, (m, oy, oc), *YUV16_FORMATS[fmt], fmt=fmt)
 
 
-class _Yuv16Operand(_Nv12Operand):
-    """A planar / semi-planar / packed 16-bit YUV batch (yuv16_frames_of) as an operand (see _Nv12Operand)."""
+def source_frames_of(fmt, planes, hw, nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr"):
+    """(source, frames_of result) of a batch of a valid rgb_frame_format other than "interleaved": the coefficients of the format
+    (nv12_coefficients; p010_coefficients at the format's depth for uint16 planes), then its *_frames_of."""
+    src, sx, sy, depth, shift = rgb_source(fmt)
+    coeffs = src.coefficients(nv12_matrix, nv12_range, nv12_order, *((depth,) if src.elem == 2 else ()))
+    return src, rgb_source_frames_of(src, planes, hw, coeffs, sx, sy, depth, shift, fmt)
 
-    def __init__(self, planes, hw, fmt, m, oy, oc, ctx=None):
-        args, self.n_frames, self.dev = yuv16_frames_of(planes, hw, fmt, m, oy, oc)
+
+class _SourceOperand(_Operand):
+    """A batch of a YUV-family source (the result of its *_frames_of) as an operand: results are allocated like the planes (empty) and
+    the entry point is called in its _dev form on torch's current stream for GPU planes, in its host form otherwise (call)."""
+
+    def __init__(self, src, planes, hw, frames, ctx=None):
+        args, self.n_frames, self.dev = frames
+        self.kind = src.kind
         self.packed, self.c, self.extents = False, 3, [(int(hw[0]), int(hw[1]))]
         self.device = self.stream = None
         if self.dev:
@@ -1399,25 +1275,48 @@ class _Yuv16Operand(_Nv12Operand):
             self._torch_device = planes[0].device
             self.device = self._torch_device.index or 0
             self.stream = C.c_void_p(torch.cuda.current_stream(self._torch_device).cuda_stream)
-        self.ptr = _lib.yuv16_ptr(args)
+        self.ptr = getattr(_lib, src.kind + "_ptr")(args)
         self.buf = tuple(planes)                        # keep alive
         self.ctx = ctx or get_context(self.device)
 
 
+def _to_rgb(kind, fmt, planes, hw, frames_of, device):
+    """The float32 frames [n, H, W, 3] the pyramid kernels see for a batch of format ``fmt`` (silent_<kind>_to_rgb[_dev]: the loaders'
+    own device functions, one thread per pixel), on the 0 .. 255 scale and not rounded."""
+    check_rgb_frame_format(fmt, hw=hw)
+    op = _SourceOperand(RGB_SOURCES[kind], planes, hw, frames_of(), None if device is None else get_context(device))
+    h, w = int(hw[0]), int(hw[1])
+    out, optr = op.empty((op.n_frames, h, w, 3))
+    op.call(kind + "_to_rgb", op.ptr, op.n_frames, h, w, optr)
+    return out
+
+
+def nv12_to_rgb(planes, hw, nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", device=None):
+    """_to_rgb for an NV12 batch -- for display, and as the reference of the bit-identity contract.  planes: nv12_frames_of."""
+    m, oy = nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
+    return _to_rgb("nv12", "nv12", planes, hw, lambda: nv12_frames_of(planes, hw, m, oy), device)
+
+
+def p010_to_rgb(planes, hw, depth=10, nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", device=None):
+    """_to_rgb for a P010 (depth=10) / P012 (12) / P016 (16) batch.  planes: p010_frames_of."""
+    m, oy, oc = p010_coefficients(nv12_matrix, nv12_range, nv12_order, depth)
+    return _to_rgb("p010", {10: "p010", 12: "p012", 16: "p016"}[depth], planes, hw, lambda: p010_frames_of(planes, hw, m, oy, oc, depth), device)
+
+
+def yuv_to_rgb(planes, hw, fmt="yuv420", nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", device=None):
+    """_to_rgb for a (y, u, v) triple of format ``fmt`` ("yuv420" / "yuv422" / "yuv444").  planes: yuv_frames_of; the conversion:
+    nv12_coefficients."""
+    m, oy = nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
+    return _to_rgb("yuv", fmt, planes, hw, lambda: yuv_frames_of(planes, hw, fmt, m, oy), device)
+
+
 def yuv16_to_rgb(planes, hw, fmt="yuv420p10", nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr", device=None):
-    """The float32 frames [n, H, W, 3] the pyramid kernels see for a (y, u, v) triple of uint16 views of format ``fmt`` (one of
-    YUV16_FORMATS; silent_yuv16_to_rgb[_dev]: the loaders' own device functions, one thread per pixel), on the 0 .. 255 scale and not
-    rounded -- for display, and as the reference of the bit-identity contract.  planes: yuv16_frames_of; the conversion:
-    p010_coefficients at the format's depth."""
+    """_to_rgb for a (y, u, v) triple of uint16 views of format ``fmt`` (one of YUV16_FORMATS).  planes: yuv16_frames_of; the
+    conversion: p010_coefficients at the format's depth."""
     if fmt not in YUV16_FORMATS:
         raise ValueError("fmt must be one of %s, got %r" % (", ".join(sorted(YUV16_FORMATS)), fmt))
     m, oy, oc = p010_coefficients(nv12_matrix, nv12_range, nv12_order, YUV16_FORMATS[fmt][2])
-    check_rgb_frame_format(fmt, hw=hw)
-    op = _Yuv16Operand(planes, hw, fmt, m, oy, oc, None if device is None else get_context(device))
-    h, w = int(hw[0]), int(hw[1])
-    out, optr = op.empty((op.n_frames, h, w, 3))
-    op.call("yuv16_to_rgb", op.ptr, op.n_frames, h, w, optr)
-    return out
+    return _to_rgb("yuv16", fmt, planes, hw, lambda: yuv16_frames_of(planes, hw, fmt, m, oy, oc), device)
 
 
 class PyramidPlan(object):
@@ -1503,33 +1402,13 @@ class PyramidPlan(object):
         mode = "gray" if self.frame_shape[2] == 1 else "rgb"
         fmt = check_rgb_frame_format(rgb_frame_format, mode, rgb_frame_dtype, rgb_frame_layout, frame_dtype, frame_channels, frame_layout,
                                      self.frame_shape[:2])
-        if fmt in P010_DEPTHS:
-            # "p010" / "p012" / "p016": the same pair as uint16 planes (p010_frames_of), the code in the high bits of each element
-            # (silent_pyramid_p010; p010_coefficients, which also knows "bt2020"), the pyramid of the float32 call on p010_to_rgb(frames)
-            m, oy, oc = p010_coefficients(nv12_matrix, nv12_range, nv12_order, P010_DEPTHS[fmt])
-            op = _P010Operand(frames, self.frame_shape[:2], m, oy, oc, P010_DEPTHS[fmt], self.ctx)
+        if fmt != "interleaved":
+            # a YUV-family source (rgb_source): the planes read in place (silent_pyramid_<kind>; the format's coefficients --
+            # p010_coefficients also knows "bt2020"), the pyramid of the float32 call on <kind>_to_rgb(frames) bit for bit
+            src, args = source_frames_of(fmt, frames, self.frame_shape[:2], nv12_matrix, nv12_range, nv12_order)
+            op = _SourceOperand(src, frames, self.frame_shape[:2], args, self.ctx)
             out, optr = op.empty(op.n_frames * self.frame_px * 3)
-            op.call("pyramid_p010", self.handle, op.ptr, op.n_frames, optr)
-            return PackedPyramid(out, self.extents, 3, op.n_frames)
-        if fmt in YUV16_FORMATS:
-            m, oy, oc = p010_coefficients(nv12_matrix, nv12_range, nv12_order, YUV16_FORMATS[fmt][2])
-            op = _Yuv16Operand(frames, self.frame_shape[:2], fmt, m, oy, oc, self.ctx)
-            out, optr = op.empty(op.n_frames * self.frame_px * 3)
-            op.call("pyramid_yuv16", self.handle, op.ptr, op.n_frames, optr)
-            return PackedPyramid(out, self.extents, 3, op.n_frames)
-        if fmt in YUV_SHIFTS:
-            # "yuv420" / "yuv422" / "yuv444": a triple (y, u, v) of uint8 views of any positive strides (yuv_frames_of), read in place
-            # (silent_pyramid_yuv; nv12_coefficients), the pyramid of the float32 call on yuv_to_rgb(frames) bit for bit
-            m, oy = nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
-            op = _YuvOperand(frames, self.frame_shape[:2], fmt, m, oy, self.ctx)
-            out, optr = op.empty(op.n_frames * self.frame_px * 3)
-            op.call("pyramid_yuv", self.handle, op.ptr, op.n_frames, optr)
-            return PackedPyramid(out, self.extents, 3, op.n_frames)
-        if fmt == "nv12":
-            m, oy = nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
-            op = _Nv12Operand(frames, self.frame_shape[:2], m, oy, self.ctx)
-            out, optr = op.empty(op.n_frames * self.frame_px * 3)
-            op.call("pyramid_nv12", self.handle, op.ptr, op.n_frames, optr)
+            op.call("pyramid_" + src.kind, self.handle, op.ptr, op.n_frames, optr)
             return PackedPyramid(out, self.extents, 3, op.n_frames)
         check_rgb_frame_dtype(rgb_frame_dtype, mode, frame_dtype, frame_channels, frame_layout)
         strided = check_rgb_frame_layout(rgb_frame_layout, mode, rgb_frame_dtype, frame_dtype, frame_channels, frame_layout) == "strided"

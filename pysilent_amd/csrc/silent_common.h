@@ -269,7 +269,7 @@ __device__ __forceinline__ StridedRgbSrc frame_of(const FrameStridedRgb& frames,
 // shares one pair).  Matrix and offset are arguments: channel order, BT.601 / BT.709 and limited / full range are the caller's choice
 // of m and oy, not kernel variants.  The struct is the kernels' argument, by value: strides and coefficients arrive in SGPRs, frame and
 // row terms (frame row y, chroma row y >> 1) are scalar 64-bit arithmetic.  nv12_channel is THE conversion: the loaders of every
-// pyramid kernel and nv12_to_rgb_kernel (silent_nv12_to_rgb) call it, so the pyramid of a surface is the float32-frame pyramid of the
+// pyramid kernel and source_to_rgb_kernel (silent_nv12_to_rgb) call it, so the pyramid of a surface is the float32-frame pyramid of the
 // converted frames bit for bit.
 struct FrameNv12 {
     const unsigned char* y;
@@ -320,18 +320,45 @@ struct FrameYuv16 {
 };
 template <typename FT>
 constexpr bool kFrameYuv16 = std::is_same<FT, FrameYuv16>::value;
-// the 3-channel kinds that are read through a `src` struct with at(y, x, ch) / atf(y, i) (strided colour views, NV12, P010, YUV and
-// 16-bit YUV surfaces)
+// the YUV family as ONE set of traits: pair kinds (two planes, the (U, V) of a pixel behind one load), triple kinds (three planes, a
+// pixel stride per plane class, a chroma shift per axis), wide kinds (uint16 elements: oc and shift).  A fifth source names itself here.
 template <typename FT>
-constexpr bool kFrameRgbSrc = kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT> || kFrameYuv<FT> || kFrameYuv16<FT>;
+constexpr bool kFrameYuvPair = kFrameNv12<FT> || kFrameP010<FT>;
+template <typename FT>
+constexpr bool kFrameYuvTriple = kFrameYuv<FT> || kFrameYuv16<FT>;
+template <typename FT>
+constexpr bool kFrameYuvWide = kFrameP010<FT> || kFrameYuv16<FT>;
+template <typename FT>
+constexpr bool kFrameYuvFamily = kFrameYuvPair<FT> || kFrameYuvTriple<FT>;
+// the 3-channel kinds that are read through a `src` struct with at(y, x, ch) / atf(y, i) (strided colour views and the YUV family)
+template <typename FT>
+constexpr bool kFrameRgbSrc = kFrameRgbView<FT> || kFrameYuvFamily<FT>;
 __device__ __forceinline__ float nv12_channel(float yv, float uv, float vv, float m0, float m1, float m2) {
     return fminf(fmaxf(__fadd_rn(__fadd_rn(__fmul_rn(yv, m0), __fmul_rn(uv, m1)), __fmul_rn(vv, m2)), 0.0f), 255.0f);
 }
 // byte offsets of pixel column x inside a luma row and of its (U, V) pair inside a chroma row
 __host__ __device__ __forceinline__ long long nv12_y_col(long long x) { return x; }
 __host__ __device__ __forceinline__ long long nv12_uv_col(long long x) { return (x >> 1) * 2; }
+// at() / atf() of the family's `src` structs (one frame of a batch inside a kernel), once: D has yuv(y, x, Yv, Uv, Vv) and m
+template <class D>
+struct YuvSrcOps {
+    // channel ch of pixel (x, y) / float i of the virtual packed row y (pixel i / 3, channel i % 3)
+    __device__ __forceinline__ float at(long long yy, long long x, int ch) const {
+        const D& d = *static_cast<const D*>(this);
+        float yv, uvv, vv;
+        d.yuv(yy, x, yv, uvv, vv);
+        // (the nine coefficients are read first and selected as VALUES: a select between loads becomes a dynamically indexed load,
+        // and with it a copy of the struct in scratch)
+        const float a0 = d.m[0], a1 = d.m[1], a2 = d.m[2], b0 = d.m[3], b1 = d.m[4], b2 = d.m[5], c0 = d.m[6], c1 = d.m[7], c2 = d.m[8];
+        return nv12_channel(yv, uvv, vv, ch == 0 ? a0 : (ch == 1 ? b0 : c0), ch == 0 ? a1 : (ch == 1 ? b1 : c1), ch == 0 ? a2 : (ch == 1 ? b2 : c2));
+    }
+    __device__ __forceinline__ float atf(long long yy, long long i) const {
+        const long long p = i / 3;
+        return at(yy, p, (int)(i - 3 * p));
+    }
+};
 // one frame of such a batch inside a kernel
-struct Nv12Src {
+struct Nv12Src : YuvSrcOps<Nv12Src> {
     const unsigned char* y;
     const unsigned char* uv;
     long long y_row_stride, uv_row_stride;
@@ -346,36 +373,12 @@ struct Nv12Src {
         uvv = (float)((int)(pair & 0xffu) - 128);
         vv = (float)((int)(pair >> 8) - 128);
     }
-    // channel ch of pixel (x, y) / float i of the virtual packed row y (pixel i / 3, channel i % 3)
-    __device__ __forceinline__ float at(long long yy, long long x, int ch) const {
-        float yv, uvv, vv;
-        yuv(yy, x, yv, uvv, vv);
-        // (the nine coefficients are read first and selected as VALUES: a select between loads becomes a dynamically indexed load,
-        // and with it a copy of the struct in scratch)
-        const float a0 = m[0], a1 = m[1], a2 = m[2], b0 = m[3], b1 = m[4], b2 = m[5], c0 = m[6], c1 = m[7], c2 = m[8];
-        return nv12_channel(yv, uvv, vv, ch == 0 ? a0 : (ch == 1 ? b0 : c0), ch == 0 ? a1 : (ch == 1 ? b1 : c1), ch == 0 ? a2 : (ch == 1 ? b2 : c2));
-    }
-    __device__ __forceinline__ float atf(long long yy, long long i) const {
-        const long long p = i / 3;
-        return at(yy, p, (int)(i - 3 * p));
-    }
 };
 template <>
 struct FrameKind<FrameNv12> {
     typedef FrameNv12 param;
     typedef Nv12Src src;
 };
-__device__ __forceinline__ Nv12Src frame_of(const FrameNv12& f, int frame) {
-    Nv12Src s;
-    s.y = f.y + (long long)frame * f.y_frame_stride;
-    s.uv = f.uv + (long long)frame * f.uv_frame_stride;
-    s.y_row_stride = f.y_row_stride;
-    s.uv_row_stride = f.uv_row_stride;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) s.m[i] = f.m[i];
-    s.oy = f.oy;
-    return s;
-}
 
 // P010 / P012 / P016 decoder surfaces (silent_pyramid_p010, 3-channel plans only): NV12's two planes with little-endian uint16
 // elements whose code value sits in the HIGH d bits (d = 10, 12, 16; shift = 16 - d, a runtime scalar: one set of kernels for the
@@ -386,7 +389,7 @@ __device__ __forceinline__ Nv12Src frame_of(const FrameNv12& f, int frame) {
 // scale and not rounded to an integer, so a 10-bit code lands on a quarter step.  Strides are BYTES and even, the pointers 2-byte
 // aligned (refused otherwise): every load is a 2-byte luma element or the 4-byte (U, V) pair as ONE dword at a 2-byte aligned address
 // (global_load_dword; the NV12 loaders read their 2-byte pair at any alignment the same way) -- exactly the two addressed elements.
-// p010_values: the element and the pair as they were loaded -> (Yv, Uv, Vv); every loader and p010_to_rgb_kernel go through it.
+// p010_values: the element and the pair as they were loaded -> (Yv, Uv, Vv); every loader and source_to_rgb_kernel go through it.
 __device__ __forceinline__ void p010_values(unsigned e, unsigned pair, float oy, float oc, int shift, float& yv, float& uv, float& vv) {
     yv = __fsub_rn((float)((e & 0xffffu) >> shift), oy);
     uv = __fsub_rn((float)((pair & 0xffffu) >> shift), oc);
@@ -396,7 +399,7 @@ __device__ __forceinline__ void p010_values(unsigned e, unsigned pair, float oy,
 __host__ __device__ __forceinline__ long long p010_y_col(long long x) { return 2 * x; }
 __host__ __device__ __forceinline__ long long p010_uv_col(long long x) { return (x >> 1) * 4; }
 // one frame of such a batch inside a kernel (the planes as byte pointers: strides are bytes)
-struct P010Src {
+struct P010Src : YuvSrcOps<P010Src> {
     const unsigned char* y;
     const unsigned char* uv;
     long long y_row_stride, uv_row_stride;
@@ -410,36 +413,12 @@ struct P010Src {
         __builtin_memcpy(&pair, uv + (yy >> 1) * uv_row_stride + p010_uv_col(x), 4);
         p010_values(e, pair, oy, oc, shift, yv, uvv, vv);
     }
-    // channel ch of pixel (x, y) / float i of the virtual packed row y (coefficients selected as values: Nv12Src::at)
-    __device__ __forceinline__ float at(long long yy, long long x, int ch) const {
-        float yv, uvv, vv;
-        yuv(yy, x, yv, uvv, vv);
-        const float a0 = m[0], a1 = m[1], a2 = m[2], b0 = m[3], b1 = m[4], b2 = m[5], c0 = m[6], c1 = m[7], c2 = m[8];
-        return nv12_channel(yv, uvv, vv, ch == 0 ? a0 : (ch == 1 ? b0 : c0), ch == 0 ? a1 : (ch == 1 ? b1 : c1), ch == 0 ? a2 : (ch == 1 ? b2 : c2));
-    }
-    __device__ __forceinline__ float atf(long long yy, long long i) const {
-        const long long p = i / 3;
-        return at(yy, p, (int)(i - 3 * p));
-    }
 };
 template <>
 struct FrameKind<FrameP010> {
     typedef FrameP010 param;
     typedef P010Src src;
 };
-__device__ __forceinline__ P010Src frame_of(const FrameP010& f, int frame) {
-    P010Src s;
-    s.y = reinterpret_cast<const unsigned char*>(f.y) + (long long)frame * f.y_frame_stride;
-    s.uv = reinterpret_cast<const unsigned char*>(f.uv) + (long long)frame * f.uv_frame_stride;
-    s.y_row_stride = f.y_row_stride;
-    s.uv_row_stride = f.uv_row_stride;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) s.m[i] = f.m[i];
-    s.oy = f.oy;
-    s.oc = f.oc;
-    s.shift = f.shift;
-    return s;
-}
 
 // Planar and packed 8-bit YUV (silent_pyramid_yuv, 3-channel plans only): what differs from NV12 is ADDRESSING alone -- which byte
 // holds a pixel's Y, U and V.  One kind for the family (I420 / YV12 / I422 / I444 / NV12 / NV21 / NV16 / NV24 / YUYV / UYVY / VUYA):
@@ -453,7 +432,7 @@ __device__ __forceinline__ P010Src frame_of(const FrameP010& f, int frame) {
 __host__ __device__ __forceinline__ long long yuv_y_col(long long x, long long y_pixel_stride) { return x * y_pixel_stride; }
 __host__ __device__ __forceinline__ long long yuv_c_col(long long x, int sx, long long c_pixel_stride) { return (x >> sx) * c_pixel_stride; }
 // one frame of such a batch inside a kernel
-struct YuvSrc {
+struct YuvSrc : YuvSrcOps<YuvSrc> {
     const unsigned char* y;
     const unsigned char* u;
     const unsigned char* v;
@@ -468,39 +447,12 @@ struct YuvSrc {
         uvv = (float)((int)u[c] - 128);
         vv = (float)((int)v[c] - 128);
     }
-    // channel ch of pixel (x, y) / float i of the virtual packed row y (coefficients selected as values: Nv12Src::at)
-    __device__ __forceinline__ float at(long long yy, long long x, int ch) const {
-        float yv, uvv, vv;
-        yuv(yy, x, yv, uvv, vv);
-        const float a0 = m[0], a1 = m[1], a2 = m[2], b0 = m[3], b1 = m[4], b2 = m[5], c0 = m[6], c1 = m[7], c2 = m[8];
-        return nv12_channel(yv, uvv, vv, ch == 0 ? a0 : (ch == 1 ? b0 : c0), ch == 0 ? a1 : (ch == 1 ? b1 : c1), ch == 0 ? a2 : (ch == 1 ? b2 : c2));
-    }
-    __device__ __forceinline__ float atf(long long yy, long long i) const {
-        const long long p = i / 3;
-        return at(yy, p, (int)(i - 3 * p));
-    }
 };
 template <>
 struct FrameKind<FrameYuv> {
     typedef FrameYuv param;
     typedef YuvSrc src;
 };
-__device__ __forceinline__ YuvSrc frame_of(const FrameYuv& f, int frame) {
-    YuvSrc s;
-    s.y = f.y + (long long)frame * f.y_frame_stride;
-    s.u = f.u + (long long)frame * f.c_frame_stride;
-    s.v = f.v + (long long)frame * f.c_frame_stride;
-    s.y_pixel_stride = f.y_pixel_stride;
-    s.y_row_stride = f.y_row_stride;
-    s.c_pixel_stride = f.c_pixel_stride;
-    s.c_row_stride = f.c_row_stride;
-    s.sx = f.sx;
-    s.sy = f.sy;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) s.m[i] = f.m[i];
-    s.oy = f.oy;
-    return s;
-}
 
 // Planar, semi-planar and packed 16-bit YUV (silent_pyramid_yuv16, 3-channel plans only): FrameYuv's ADDRESSING (three plane pointers,
 // a pixel stride per plane class, a chroma shift per axis; all strides bytes and even) with uint16 elements, and P010's ARITHMETIC with
@@ -511,7 +463,7 @@ __device__ __forceinline__ YuvSrc frame_of(const FrameYuv& f, int frame) {
 // -- elements loaded UNSIGNED, every difference a separately rounded float32 operation; with shift = 16 - depth the mask changes
 // nothing and these are p010_values' values.  Every load is ONE 2-byte element (global_load_ushort) at a 2-byte aligned address that
 // is some pixel's Y, U or V: no pair and no dword loads, so nothing between the pixels of a packed format is ever read.
-// yuv16_values: the three elements as they were loaded -> (Yv, Uv, Vv); every loader and yuv16_to_rgb_kernel go through it.
+// yuv16_values: the three elements as they were loaded -> (Yv, Uv, Vv); every loader and source_to_rgb_kernel go through it.
 __device__ __forceinline__ void yuv16_values(unsigned ey, unsigned eu, unsigned ev, float oy, float oc, int shift, unsigned mask, float& yv,
                                              float& uv, float& vv) {
     yv = __fsub_rn((float)(((ey & 0xffffu) >> shift) & mask), oy);
@@ -519,7 +471,7 @@ __device__ __forceinline__ void yuv16_values(unsigned ey, unsigned eu, unsigned 
     vv = __fsub_rn((float)(((ev & 0xffffu) >> shift) & mask), oc);
 }
 // one frame of such a batch inside a kernel (the planes as byte pointers: strides are bytes; the columns are yuv_y_col / yuv_c_col)
-struct Yuv16Src {
+struct Yuv16Src : YuvSrcOps<Yuv16Src> {
     const unsigned char* y;
     const unsigned char* u;
     const unsigned char* v;
@@ -538,40 +490,38 @@ struct Yuv16Src {
         __builtin_memcpy(&ev, v + c, 2);
         yuv16_values(ey, eu, ev, oy, oc, shift, mask, yv, uvv, vv);
     }
-    // channel ch of pixel (x, y) / float i of the virtual packed row y (coefficients selected as values: Nv12Src::at)
-    __device__ __forceinline__ float at(long long yy, long long x, int ch) const {
-        float yv, uvv, vv;
-        yuv(yy, x, yv, uvv, vv);
-        const float a0 = m[0], a1 = m[1], a2 = m[2], b0 = m[3], b1 = m[4], b2 = m[5], c0 = m[6], c1 = m[7], c2 = m[8];
-        return nv12_channel(yv, uvv, vv, ch == 0 ? a0 : (ch == 1 ? b0 : c0), ch == 0 ? a1 : (ch == 1 ? b1 : c1), ch == 0 ? a2 : (ch == 1 ? b2 : c2));
-    }
-    __device__ __forceinline__ float atf(long long yy, long long i) const {
-        const long long p = i / 3;
-        return at(yy, p, (int)(i - 3 * p));
-    }
 };
 template <>
 struct FrameKind<FrameYuv16> {
     typedef FrameYuv16 param;
     typedef Yuv16Src src;
 };
-__device__ __forceinline__ Yuv16Src frame_of(const FrameYuv16& f, int frame) {
-    Yuv16Src s;
+// frame `frame` of a batch of the family
+template <typename FT, typename std::enable_if<kFrameYuvFamily<FT>, int>::type = 0>
+__device__ __forceinline__ frame_src<FT> frame_of(const FT& f, int frame) {
+    frame_src<FT> s;
     s.y = reinterpret_cast<const unsigned char*>(f.y) + (long long)frame * f.y_frame_stride;
-    s.u = reinterpret_cast<const unsigned char*>(f.u) + (long long)frame * f.c_frame_stride;
-    s.v = reinterpret_cast<const unsigned char*>(f.v) + (long long)frame * f.c_frame_stride;
-    s.y_pixel_stride = f.y_pixel_stride;
     s.y_row_stride = f.y_row_stride;
-    s.c_pixel_stride = f.c_pixel_stride;
-    s.c_row_stride = f.c_row_stride;
-    s.sx = f.sx;
-    s.sy = f.sy;
+    if constexpr (kFrameYuvPair<FT>) {
+        s.uv = reinterpret_cast<const unsigned char*>(f.uv) + (long long)frame * f.uv_frame_stride;
+        s.uv_row_stride = f.uv_row_stride;
+    } else {
+        s.u = reinterpret_cast<const unsigned char*>(f.u) + (long long)frame * f.c_frame_stride;
+        s.v = reinterpret_cast<const unsigned char*>(f.v) + (long long)frame * f.c_frame_stride;
+        s.y_pixel_stride = f.y_pixel_stride;
+        s.c_pixel_stride = f.c_pixel_stride;
+        s.c_row_stride = f.c_row_stride;
+        s.sx = f.sx;
+        s.sy = f.sy;
+    }
 #pragma unroll
     for (int i = 0; i < 9; ++i) s.m[i] = f.m[i];
     s.oy = f.oy;
-    s.oc = f.oc;
-    s.shift = f.shift;
-    s.mask = f.mask;
+    if constexpr (kFrameYuvWide<FT>) {
+        s.oc = f.oc;
+        s.shift = f.shift;
+    }
+    if constexpr (kFrameYuv16<FT>) s.mask = f.mask;
     return s;
 }
 
@@ -579,7 +529,7 @@ __device__ __forceinline__ Yuv16Src frame_of(const FrameYuv16& f, int frame) {
 template <typename FT>
 constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT> || kFrameWords<FT> || kFrameStrided<FT>;
 template <typename FT>
-constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT> || kFrameYuv<FT> || kFrameYuv16<FT>;
+constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT> || kFrameYuvFamily<FT>;
 // (host) the bytes of one frame pixel as the host-pointer forms stage it -- float frames carry the channels of the plan; a view is
 // staged by its span -- and the suffix of a frame type's entry points
 template <typename FT>
@@ -609,23 +559,9 @@ __device__ __forceinline__ float unit_edge_column(const StridedRgbSrc& src, int 
                                                   int src_h, int src_y0, int lane) {
     return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
 }
-// and of channel `ch` of an NV12 surface
-__device__ __forceinline__ float unit_edge_column(const Nv12Src& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
-                                                  int src_h, int src_y0, int lane) {
-    return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
-}
-// and of a P010 surface
-__device__ __forceinline__ float unit_edge_column(const P010Src& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
-                                                  int src_h, int src_y0, int lane) {
-    return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
-}
-// and of a planar / packed YUV batch
-__device__ __forceinline__ float unit_edge_column(const YuvSrc& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
-                                                  int src_h, int src_y0, int lane) {
-    return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
-}
-// and of a 16-bit YUV batch
-__device__ __forceinline__ float unit_edge_column(const Yuv16Src& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
+// and of channel `ch` of a frame of the YUV family
+template <class D>
+__device__ __forceinline__ float unit_edge_column(const YuvSrcOps<D>& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
                                                   int src_h, int src_y0, int lane) {
     return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
 }

@@ -97,80 +97,82 @@ int with_rgb_view(const silent_pyramid_plan* plan, const silent_frame_view* v, i
     const ViewRgb s{v->data, v->pixel_stride, v->row_stride, n_frames > 1 ? v->frame_stride : 0};
     return f(&s);
 }
-// NV12 surfaces (silent_pyramid_nv12, silent_nv12_to_rgb; silent_hip.h): the host struct travels as `const Nv12*` like a view and is
-// the kernels' argument by value.  check_nv12: what the struct refuses on its own for frames of H x W -- NULL, odd extents, a stride
-// below its bound, a span of 2^63 bytes or more, a non-finite coefficient -- and the two spans in bytes.
+// ------------------------------------------------------------------------------------------ the YUV-family colour sources
+// NV12, P010 / P012 / P016, planar / packed 8-bit YUV and 16-bit YUV (silent_pyramid_{nv12,p010,yuv,yuv16}, silent_*_to_rgb;
+// silent_hip.h).  A host struct travels as a pointer to the kernels' frame kind like a view and is the kernels' argument by value.
+// Source<S>: the ONE description of a source struct S -- its entry points, the noun of its messages, its element type; the two PAIR
+// structs (y, uv) share check_pair / pair_frames, the two TRIPLE structs (y, u, v) check_triple / with_yuv / yuv_stage, each written
+// once over the element size.  A fifth source adds a Source<S> and, if it is neither a pair nor a triple, a check and a marshaller.
 using Nv12 = silent::FrameNv12;
-inline int check_nv12(silent_ctx* ctx, const char* who, bool has_plan, long long H, long long W, const silent_nv12_frames* v, int n_frames,
-                      size_t* y_span, size_t* uv_span) {
-    if (!has_plan || !v || !v->y || !v->uv) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NV12 frames need even H and W (4:2:0 chroma)");
-    typedef unsigned __int128 u128;
-    if (v->y_row_stride < W) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_row_stride is below W");
-    if (v->uv_row_stride < W) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": uv_row_stride is below W");
-    const u128 yf = (u128)(H - 1) * (u128)v->y_row_stride + (u128)W, cf = (u128)(H / 2 - 1) * (u128)v->uv_row_stride + (u128)W;
-    if (n_frames > 1 && (v->y_frame_stride <= 0 || (u128)v->y_frame_stride < yf))
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_frame_stride is below (H - 1) * y_row_stride + W");
-    if (n_frames > 1 && (v->uv_frame_stride <= 0 || (u128)v->uv_frame_stride < cf))
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": uv_frame_stride is below (H / 2 - 1) * uv_row_stride + W");
-    const u128 ya = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->y_frame_stride : 0) + yf;
-    const u128 ca = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->uv_frame_stride : 0) + cf;
-    if (ya > (u128)0x7fffffffffffffffll || ca > (u128)0x7fffffffffffffffll)
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a plane spans more than 2^63 bytes");
-    bool finite = std::isfinite(v->oy);
-    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(v->m[i]);
-    if (!finite) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": m and oy must be finite");
-    if (y_span) *y_span = (size_t)ya;
-    if (uv_span) *uv_span = (size_t)ca;
-    return SILENT_OK;
-}
-// the kernels' argument for a checked struct (the planes at y / uv: those of the struct, or their staged copies)
-inline Nv12 nv12_frames(const silent_nv12_frames* v, const uint8_t* y, const uint8_t* uv, int n_frames) {
-    Nv12 s;
-    s.y = y;
-    s.uv = uv;
-    s.y_row_stride = v->y_row_stride;
-    s.uv_row_stride = v->uv_row_stride;
-    s.y_frame_stride = n_frames > 1 ? v->y_frame_stride : 0;
-    s.uv_frame_stride = n_frames > 1 ? v->uv_frame_stride : 0;
-    for (int i = 0; i < 9; ++i) s.m[i] = v->m[i];
-    s.oy = v->oy;
-    return s;
-}
-// P010 / P012 / P016 surfaces (silent_pyramid_p010, silent_p010_to_rgb; silent_hip.h): NV12's checks in NV12's order with 2-byte
-// elements (a row holds 2 W bytes), then what uint16 elements add -- an odd plane address, an odd stride, a shift outside 0 .. 6.
 using P010 = silent::FrameP010;
-inline int check_p010(silent_ctx* ctx, const char* who, bool has_plan, long long H, long long W, const silent_p010_frames* v, int n_frames,
-                      size_t* y_span, size_t* uv_span) {
-    if (!has_plan || !v || !v->y || !v->uv) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": P010 frames need even H and W (4:2:0 chroma)");
+using Yuv = silent::FrameYuv;
+using Yuv16 = silent::FrameYuv16;
+template <class S>
+struct Source;
+template <>
+struct Source<silent_nv12_frames> {
+    typedef uint8_t elem;
+    static constexpr bool pair = true;
+    static constexpr const char *pyramid = "silent_pyramid_nv12", *to_rgb = "silent_nv12_to_rgb", *noun = "NV12 surfaces", *family = "NV12";
+};
+template <>
+struct Source<silent_p010_frames> {
+    typedef uint16_t elem;
+    static constexpr bool pair = true;
+    static constexpr const char *pyramid = "silent_pyramid_p010", *to_rgb = "silent_p010_to_rgb", *noun = "P010 surfaces", *family = "P010";
+};
+template <>
+struct Source<silent_yuv_frames> {
+    typedef uint8_t elem;
+    static constexpr bool pair = false;
+    static constexpr const char *pyramid = "silent_pyramid_yuv", *to_rgb = "silent_yuv_to_rgb", *noun = "YUV frames";
+};
+template <>
+struct Source<silent_yuv16_frames> {
+    typedef uint16_t elem;
+    static constexpr bool pair = false;
+    static constexpr const char *pyramid = "silent_pyramid_yuv16", *to_rgb = "silent_yuv16_to_rgb", *noun = "16-bit YUV frames";
+};
+// What a pair struct refuses on its own for frames of H x W, in the header's order -- NULL, odd extents, a stride below its bound (a
+// row holds E * W bytes, E the element size), a span of 2^63 bytes or more, a non-finite coefficient; then what uint16 elements add:
+// an odd plane address, an odd stride, a shift outside 0 .. 6 -- and the two spans in bytes.
+template <class S>
+inline int check_pair(silent_ctx* ctx, const char* who, bool has_plan, long long H, long long W, const S* v, int n_frames, size_t* y_span,
+                      size_t* uv_span) {
+    constexpr bool wide = sizeof(typename Source<S>::elem) == 2;
+    auto bad = [&](const std::string& what) { return fail(ctx, SILENT_E_INVALID, std::string(who) + ": " + what); };
+    const std::string row = wide ? "2 * W" : "W";
+    if (!has_plan || !v || !v->y || !v->uv) return bad("NULL pointer");
+    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return bad(std::string(Source<S>::family) + " frames need even H and W (4:2:0 chroma)");
     typedef unsigned __int128 u128;
-    if (v->y_row_stride < 2 * W) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_row_stride is below 2 * W");
-    if (v->uv_row_stride < 2 * W) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": uv_row_stride is below 2 * W");
-    const u128 yf = (u128)(H - 1) * (u128)v->y_row_stride + (u128)(2 * W), cf = (u128)(H / 2 - 1) * (u128)v->uv_row_stride + (u128)(2 * W);
-    if (n_frames > 1 && (v->y_frame_stride <= 0 || (u128)v->y_frame_stride < yf))
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_frame_stride is below (H - 1) * y_row_stride + 2 * W");
+    const long long rb = (wide ? 2 : 1) * W;
+    if (v->y_row_stride < rb) return bad("y_row_stride is below " + row);
+    if (v->uv_row_stride < rb) return bad("uv_row_stride is below " + row);
+    const u128 yf = (u128)(H - 1) * (u128)v->y_row_stride + (u128)rb, cf = (u128)(H / 2 - 1) * (u128)v->uv_row_stride + (u128)rb;
+    if (n_frames > 1 && (v->y_frame_stride <= 0 || (u128)v->y_frame_stride < yf)) return bad("y_frame_stride is below (H - 1) * y_row_stride + " + row);
     if (n_frames > 1 && (v->uv_frame_stride <= 0 || (u128)v->uv_frame_stride < cf))
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": uv_frame_stride is below (H / 2 - 1) * uv_row_stride + 2 * W");
+        return bad("uv_frame_stride is below (H / 2 - 1) * uv_row_stride + " + row);
     const u128 ya = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->y_frame_stride : 0) + yf;
     const u128 ca = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->uv_frame_stride : 0) + cf;
-    if (ya > (u128)0x7fffffffffffffffll || ca > (u128)0x7fffffffffffffffll)
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a plane spans more than 2^63 bytes");
-    bool finite = std::isfinite(v->oy) && std::isfinite(v->oc);
+    if (ya > (u128)0x7fffffffffffffffll || ca > (u128)0x7fffffffffffffffll) return bad("a plane spans more than 2^63 bytes");
+    bool finite = std::isfinite(v->oy);
+    if constexpr (wide) finite = finite && std::isfinite(v->oc);
     for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(v->m[i]);
-    if (!finite) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": m, oy and oc must be finite");
-    if ((reinterpret_cast<uintptr_t>(v->y) | reinterpret_cast<uintptr_t>(v->uv)) & 1u)
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y and uv must be 2-byte aligned (uint16 elements)");
-    if (((v->y_row_stride | v->uv_row_stride) & 1) || (n_frames > 1 && ((v->y_frame_stride | v->uv_frame_stride) & 1)))
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a stride is odd (uint16 elements)");
-    if (v->shift < 0 || v->shift > 6) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": shift must be 0 .. 6 (16 - depth)");
+    if (!finite) return bad(wide ? "m, oy and oc must be finite" : "m and oy must be finite");
+    if constexpr (wide) {
+        if ((reinterpret_cast<uintptr_t>(v->y) | reinterpret_cast<uintptr_t>(v->uv)) & 1u) return bad("y and uv must be 2-byte aligned (uint16 elements)");
+        if (((v->y_row_stride | v->uv_row_stride) & 1) || (n_frames > 1 && ((v->y_frame_stride | v->uv_frame_stride) & 1)))
+            return bad("a stride is odd (uint16 elements)");
+        if (v->shift < 0 || v->shift > 6) return bad("shift must be 0 .. 6 (16 - depth)");
+    }
     if (y_span) *y_span = (size_t)ya;
     if (uv_span) *uv_span = (size_t)ca;
     return SILENT_OK;
 }
-// the kernels' argument for a checked struct (the planes at y / uv: those of the struct, or their staged copies)
-inline P010 p010_frames(const silent_p010_frames* v, const uint16_t* y, const uint16_t* uv, int n_frames) {
-    P010 s;
+// the kernels' argument for a checked pair struct (the planes at y / uv: those of the struct, or their staged copies)
+template <class K, class S, class E>
+inline K pair_frames(const S* v, const E* y, const E* uv, int n_frames) {
+    K s;
     s.y = y;
     s.uv = uv;
     s.y_row_stride = v->y_row_stride;
@@ -179,51 +181,75 @@ inline P010 p010_frames(const silent_p010_frames* v, const uint16_t* y, const ui
     s.uv_frame_stride = n_frames > 1 ? v->uv_frame_stride : 0;
     for (int i = 0; i < 9; ++i) s.m[i] = v->m[i];
     s.oy = v->oy;
-    s.oc = v->oc;
-    s.shift = v->shift;
+    if constexpr (sizeof(E) == 2) {
+        s.oc = v->oc;
+        s.shift = v->shift;
+    }
     return s;
 }
-// Planar / packed 8-bit YUV (silent_pyramid_yuv, silent_yuv_to_rgb; silent_hip.h).  check_yuv: what the struct refuses on its own for
-// frames of H x W, in the header's order, and the spans of the luma plane and of a chroma plane (u and v share it) in bytes.
-using Yuv = silent::FrameYuv;
-inline int check_yuv(silent_ctx* ctx, const char* who, bool has_plan, long long H, long long W, const silent_yuv_frames* v, int n_frames,
-                     size_t* y_span, size_t* c_span) {
-    if (!has_plan || !v || !v->y || !v->u || !v->v) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+inline Nv12 nv12_frames(const silent_nv12_frames* v, const uint8_t* y, const uint8_t* uv, int n_frames) { return pair_frames<Nv12>(v, y, uv, n_frames); }
+inline P010 p010_frames(const silent_p010_frames* v, const uint16_t* y, const uint16_t* uv, int n_frames) { return pair_frames<P010>(v, y, uv, n_frames); }
+// What a triple struct refuses on its own for frames of H x W, in the header's order (a row or plane ends E bytes behind its last
+// element's offset, E the element size); then what uint16 elements add, in check_pair's order -- m / oy / oc finite, 2-byte aligned
+// planes, even strides -- and the position of the code (depth, shift).  The spans of the luma plane and of a chroma plane (u and v
+// share it) in bytes.
+template <class S>
+inline int check_triple(silent_ctx* ctx, const char* who, bool has_plan, long long H, long long W, const S* v, int n_frames, size_t* y_span,
+                        size_t* c_span) {
+    constexpr bool wide = sizeof(typename Source<S>::elem) == 2;
+    constexpr int E = wide ? 2 : 1;
+    auto bad = [&](const std::string& what) { return fail(ctx, SILENT_E_INVALID, std::string(who) + ": " + what); };
+    const std::string e = wide ? "2" : "1";
+    if (!has_plan || !v || !v->y || !v->u || !v->v) return bad("NULL pointer");
     const int sx = v->chroma_shift_x, sy = v->chroma_shift_y;
-    if ((sx != 0 && sx != 1) || (sy != 0 && sy != 1)) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a chroma shift must be 0 or 1");
+    if ((sx != 0 && sx != 1) || (sy != 0 && sy != 1)) return bad("a chroma shift must be 0 or 1");
     if (H < 1 || W < 1 || (sy && (H & 1)) || (sx && (W & 1)))
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a subsampled axis needs an even extent (H for chroma_shift_y = 1, W for chroma_shift_x = 1)");
-    if (v->y_pixel_stride < 1 || v->c_pixel_stride < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a pixel stride is below 1");
+        return bad("a subsampled axis needs an even extent (H for chroma_shift_y = 1, W for chroma_shift_x = 1)");
+    if (v->y_pixel_stride < E || v->c_pixel_stride < E) return bad("a pixel stride is below " + e);
     typedef unsigned __int128 u128;
     const long long ch = H >> sy, cw = W >> sx;
-    const u128 yrow = (u128)(W - 1) * (u128)v->y_pixel_stride + 1, crow = (u128)(cw - 1) * (u128)v->c_pixel_stride + 1;
-    if (v->y_row_stride <= 0 || (u128)v->y_row_stride < yrow)
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_row_stride is below (W - 1) * y_pixel_stride + 1");
-    if (v->c_row_stride <= 0 || (u128)v->c_row_stride < crow)
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": c_row_stride is below ((W >> sx) - 1) * c_pixel_stride + 1");
+    const u128 yrow = (u128)(W - 1) * (u128)v->y_pixel_stride + E, crow = (u128)(cw - 1) * (u128)v->c_pixel_stride + E;
+    if (v->y_row_stride <= 0 || (u128)v->y_row_stride < yrow) return bad("y_row_stride is below (W - 1) * y_pixel_stride + " + e);
+    if (v->c_row_stride <= 0 || (u128)v->c_row_stride < crow) return bad("c_row_stride is below ((W >> sx) - 1) * c_pixel_stride + " + e);
     const u128 yf = (u128)(H - 1) * (u128)v->y_row_stride + yrow, cf = (u128)(ch - 1) * (u128)v->c_row_stride + crow;
-    if (n_frames > 1 && (v->y_frame_stride <= 0 || (u128)v->y_frame_stride < yf))
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_frame_stride is below the luma plane's extent");
-    if (n_frames > 1 && (v->c_frame_stride <= 0 || (u128)v->c_frame_stride < cf))
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": c_frame_stride is below a chroma plane's extent");
+    if (n_frames > 1 && (v->y_frame_stride <= 0 || (u128)v->y_frame_stride < yf)) return bad("y_frame_stride is below the luma plane's extent");
+    if (n_frames > 1 && (v->c_frame_stride <= 0 || (u128)v->c_frame_stride < cf)) return bad("c_frame_stride is below a chroma plane's extent");
     const u128 ya = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->y_frame_stride : 0) + yf;
     const u128 ca = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->c_frame_stride : 0) + cf;
-    if (ya > (u128)0x7fffffffffffffffll || ca > (u128)0x7fffffffffffffffll)
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a plane spans more than 2^63 bytes");
+    if (ya > (u128)0x7fffffffffffffffll || ca > (u128)0x7fffffffffffffffll) return bad("a plane spans more than 2^63 bytes");
     bool finite = std::isfinite(v->oy);
+    if constexpr (wide) finite = finite && std::isfinite(v->oc);
     for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(v->m[i]);
-    if (!finite) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": m and oy must be finite");
+    if (!finite) return bad(wide ? "m, oy and oc must be finite" : "m and oy must be finite");
+    if constexpr (wide) {
+        if ((reinterpret_cast<uintptr_t>(v->y) | reinterpret_cast<uintptr_t>(v->u) | reinterpret_cast<uintptr_t>(v->v)) & 1u)
+            return bad("y, u and v must be 2-byte aligned (uint16 elements)");
+        if (((v->y_pixel_stride | v->c_pixel_stride | v->y_row_stride | v->c_row_stride) & 1) || (n_frames > 1 && ((v->y_frame_stride | v->c_frame_stride) & 1)))
+            return bad("a stride is odd (uint16 elements)");
+        if (v->depth < 8 || v->depth > 16) return bad("depth must be 8 .. 16");
+        if (v->shift < 0 || v->shift + v->depth > 16) return bad("shift must be 0 .. 16 - depth");
+    }
     if (y_span) *y_span = (size_t)ya;
     if (c_span) *c_span = (size_t)ca;
     return SILENT_OK;
 }
-// f(frames) with a checked struct (the planes at y / u / v: those of the struct, or their staged copies) as the frame kind that reads
-// it: a struct that IS NV12 as Nv12 (the kernels of silent_pyramid_nv12, which read the (U, V) bytes of a pixel as one pair), any other
-// as Yuv -- like with_rgb_view for a packed view
-template <class F>
-int with_yuv(const silent_yuv_frames* v, const uint8_t* y, const uint8_t* u, const uint8_t* vv, int n_frames, F&& f) {
-    if (v->y_pixel_stride == 1 && v->c_pixel_stride == 2 && vv == u + 1 && v->chroma_shift_x == 1 && v->chroma_shift_y == 1) {
-        Nv12 s;
+template <class S>
+inline int check_source(silent_ctx* ctx, const char* who, bool has_plan, long long H, long long W, const S* v, int n_frames, size_t* y_span,
+                        size_t* c_span) {
+    if constexpr (Source<S>::pair) return check_pair(ctx, who, has_plan, H, W, v, n_frames, y_span, c_span);
+    else return check_triple(ctx, who, has_plan, H, W, v, n_frames, y_span, c_span);
+}
+// f(frames) with a checked triple struct (the planes at y / u / v: those of the struct, or their staged copies) as the frame kind that
+// reads it: a struct that IS NV12 as Nv12, one that IS P010 as P010 (the kernels of silent_pyramid_nv12 / _p010, which read the (U, V)
+// of a pixel as one pair; with shift == 16 - depth P010's missing mask changes nothing), any other as Yuv / Yuv16 -- like
+// with_rgb_view for a packed view
+template <class S, class E, class F>
+int with_yuv(const S* v, const E* y, const E* u, const E* vv, int n_frames, F&& f) {
+    constexpr bool wide = sizeof(E) == 2;
+    bool is_pair = v->y_pixel_stride == (int)sizeof(E) && v->c_pixel_stride == 2 * (int)sizeof(E) && vv == u + 1 && v->chroma_shift_x == 1 && v->chroma_shift_y == 1;
+    if constexpr (wide) is_pair = is_pair && v->shift == 16 - v->depth;
+    if (is_pair) {
+        typename std::conditional<wide, P010, Nv12>::type s;
         s.y = y;
         s.uv = u;
         s.y_row_stride = v->y_row_stride;
@@ -232,9 +258,13 @@ int with_yuv(const silent_yuv_frames* v, const uint8_t* y, const uint8_t* u, con
         s.uv_frame_stride = n_frames > 1 ? v->c_frame_stride : 0;
         for (int i = 0; i < 9; ++i) s.m[i] = v->m[i];
         s.oy = v->oy;
+        if constexpr (wide) {
+            s.oc = v->oc;
+            s.shift = v->shift;
+        }
         return f(&s);
     }
-    Yuv s;
+    typename std::conditional<wide, Yuv16, Yuv>::type s;
     s.y = y;
     s.u = u;
     s.v = vv;
@@ -248,7 +278,22 @@ int with_yuv(const silent_yuv_frames* v, const uint8_t* y, const uint8_t* u, con
     s.sy = v->chroma_shift_y;
     for (int i = 0; i < 9; ++i) s.m[i] = v->m[i];
     s.oy = v->oy;
+    if constexpr (wide) {
+        s.oc = v->oc;
+        s.shift = v->shift;
+        s.mask = (1u << v->depth) - 1u;
+    }
     return f(&s);
+}
+// f(frames) with a checked source struct and its planes p[0 .. 2] (a pair: y, uv) as the kernels' argument
+template <class S, class F>
+int with_source(const S* v, const typename Source<S>::elem* const* p, int n_frames, F&& f) {
+    if constexpr (Source<S>::pair) {
+        const auto s = pair_frames<typename std::conditional<sizeof(typename Source<S>::elem) == 2, P010, Nv12>::type>(v, p[0], p[1], n_frames);
+        return f(&s);
+    } else {
+        return with_yuv(v, p[0], p[1], p[2], n_frames, f);
+    }
 }
 // what the host forms stage for a checked struct: the UNION of the three spans -- the intervals sorted by address, those that overlap
 // or touch merged -- and for each plane the merged interval it lies in and its offset inside it
@@ -288,86 +333,6 @@ inline YuvStage yuv_stage(const S* v, size_t y_span, size_t c_span) {
         st.delta[p] = (size_t)(a[p] - lo);
     }
     return st;
-}
-// Planar / semi-planar / packed 16-bit YUV (silent_pyramid_yuv16, silent_yuv16_to_rgb; silent_hip.h).  check_yuv16: check_yuv's list
-// with 2-byte elements (a row or plane ends 2 bytes behind its last element's offset), then what uint16 elements add, in check_p010's
-// order -- m / oy / oc finite, 2-byte aligned planes, even strides -- and the position of the code (depth, shift).
-using Yuv16 = silent::FrameYuv16;
-inline int check_yuv16(silent_ctx* ctx, const char* who, bool has_plan, long long H, long long W, const silent_yuv16_frames* v, int n_frames,
-                       size_t* y_span, size_t* c_span) {
-    if (!has_plan || !v || !v->y || !v->u || !v->v) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    const int sx = v->chroma_shift_x, sy = v->chroma_shift_y;
-    if ((sx != 0 && sx != 1) || (sy != 0 && sy != 1)) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a chroma shift must be 0 or 1");
-    if (H < 1 || W < 1 || (sy && (H & 1)) || (sx && (W & 1)))
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a subsampled axis needs an even extent (H for chroma_shift_y = 1, W for chroma_shift_x = 1)");
-    if (v->y_pixel_stride < 2 || v->c_pixel_stride < 2) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a pixel stride is below 2");
-    typedef unsigned __int128 u128;
-    const long long ch = H >> sy, cw = W >> sx;
-    const u128 yrow = (u128)(W - 1) * (u128)v->y_pixel_stride + 2, crow = (u128)(cw - 1) * (u128)v->c_pixel_stride + 2;
-    if (v->y_row_stride <= 0 || (u128)v->y_row_stride < yrow)
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_row_stride is below (W - 1) * y_pixel_stride + 2");
-    if (v->c_row_stride <= 0 || (u128)v->c_row_stride < crow)
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": c_row_stride is below ((W >> sx) - 1) * c_pixel_stride + 2");
-    const u128 yf = (u128)(H - 1) * (u128)v->y_row_stride + yrow, cf = (u128)(ch - 1) * (u128)v->c_row_stride + crow;
-    if (n_frames > 1 && (v->y_frame_stride <= 0 || (u128)v->y_frame_stride < yf))
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y_frame_stride is below the luma plane's extent");
-    if (n_frames > 1 && (v->c_frame_stride <= 0 || (u128)v->c_frame_stride < cf))
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": c_frame_stride is below a chroma plane's extent");
-    const u128 ya = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->y_frame_stride : 0) + yf;
-    const u128 ca = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->c_frame_stride : 0) + cf;
-    if (ya > (u128)0x7fffffffffffffffll || ca > (u128)0x7fffffffffffffffll)
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a plane spans more than 2^63 bytes");
-    bool finite = std::isfinite(v->oy) && std::isfinite(v->oc);
-    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(v->m[i]);
-    if (!finite) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": m, oy and oc must be finite");
-    if ((reinterpret_cast<uintptr_t>(v->y) | reinterpret_cast<uintptr_t>(v->u) | reinterpret_cast<uintptr_t>(v->v)) & 1u)
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": y, u and v must be 2-byte aligned (uint16 elements)");
-    if (((v->y_pixel_stride | v->c_pixel_stride | v->y_row_stride | v->c_row_stride) & 1) || (n_frames > 1 && ((v->y_frame_stride | v->c_frame_stride) & 1)))
-        return fail(ctx, SILENT_E_INVALID, std::string(who) + ": a stride is odd (uint16 elements)");
-    if (v->depth < 8 || v->depth > 16) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": depth must be 8 .. 16");
-    if (v->shift < 0 || v->shift + v->depth > 16) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": shift must be 0 .. 16 - depth");
-    if (y_span) *y_span = (size_t)ya;
-    if (c_span) *c_span = (size_t)ca;
-    return SILENT_OK;
-}
-// f(frames) with a checked struct (the planes at y / u / v: those of the struct, or their staged copies) as the frame kind that reads
-// it: a struct that IS P010 as P010 (the kernels of silent_pyramid_p010, which read the (U, V) elements of a pixel as one pair; with
-// shift == 16 - depth the mask changes nothing), any other as Yuv16 -- like with_yuv for a struct that is NV12
-template <class F>
-int with_yuv16(const silent_yuv16_frames* v, const uint16_t* y, const uint16_t* u, const uint16_t* vv, int n_frames, F&& f) {
-    if (v->y_pixel_stride == 2 && v->c_pixel_stride == 4 && vv == u + 1 && v->chroma_shift_x == 1 && v->chroma_shift_y == 1 &&
-        v->shift == 16 - v->depth) {
-        P010 s;
-        s.y = y;
-        s.uv = u;
-        s.y_row_stride = v->y_row_stride;
-        s.uv_row_stride = v->c_row_stride;
-        s.y_frame_stride = n_frames > 1 ? v->y_frame_stride : 0;
-        s.uv_frame_stride = n_frames > 1 ? v->c_frame_stride : 0;
-        for (int i = 0; i < 9; ++i) s.m[i] = v->m[i];
-        s.oy = v->oy;
-        s.oc = v->oc;
-        s.shift = v->shift;
-        return f(&s);
-    }
-    Yuv16 s;
-    s.y = y;
-    s.u = u;
-    s.v = vv;
-    s.y_pixel_stride = v->y_pixel_stride;
-    s.y_row_stride = v->y_row_stride;
-    s.y_frame_stride = n_frames > 1 ? v->y_frame_stride : 0;
-    s.c_pixel_stride = v->c_pixel_stride;
-    s.c_row_stride = v->c_row_stride;
-    s.c_frame_stride = n_frames > 1 ? v->c_frame_stride : 0;
-    s.sx = v->chroma_shift_x;
-    s.sy = v->chroma_shift_y;
-    for (int i = 0; i < 9; ++i) s.m[i] = v->m[i];
-    s.oy = v->oy;
-    s.oc = v->oc;
-    s.shift = v->shift;
-    s.mask = (1u << v->depth) - 1u;
-    return f(&s);
 }
 // The same for a silent_frame_view16: one uint16 element per pixel (the bounds of check_view with 2 for `channels`), and 2-byte alignment
 // of every address a kernel forms -- an even data address and even strides.

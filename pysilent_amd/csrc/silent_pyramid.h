@@ -483,10 +483,10 @@ __device__ __forceinline__ void pyramid_border_px(frame_param<FT> frames, float*
                 // (NV12 / P010 inside the walk kernel: a tap is two loads behind two 64-bit addresses; three taps in flight, not six -- the
                 // walk's consumers set the register budget.  The sum and its order are the same.  YUV: three loads a tap, TWO taps in
                 // flight -- with three the walk kernel needs 73 - 74 VGPRs and loses a wave per SIMD, with two 67 - 70 like NV12.)
-                if constexpr ((kFrameNv12<FT> || kFrameP010<FT>) && LEAN) {
+                if constexpr (kFrameYuvPair<FT> && LEAN) {
                     if (i == 3) asm volatile("" ::: "memory");
                 }
-                if constexpr ((kFrameYuv<FT> || kFrameYuv16<FT>) && LEAN) {
+                if constexpr (kFrameYuvTriple<FT> && LEAN) {
                     if (i == 2 || i == 4) asm volatile("" ::: "memory");
                 }
                 a = __builtin_fmaf(wy[i], src.at(yi[i] + lv.src_y0, x, ch), a);
@@ -523,61 +523,18 @@ __global__ __launch_bounds__(256) void pyramid_border_kernel(frame_param<FT> fra
     pyramid_border_px<C, false, FT>(frames, pyr, tab, bt, (long long)blockIdx.x * 256 + threadIdx.x, n_frames);
 }
 
-// ------------------------------------------------------------------------------------------ NV12 -> float32 frames
-// silent_nv12_to_rgb: the frames the pyramid kernels see for an NV12 batch, [n, H, W, 3] float32 -- one thread per pixel, the three
-// channels through the loaders' own device function (Nv12Src::yuv + nv12_channel).  Blocks of 256 pixels of one frame.
-template <int C = 3>
-__global__ __launch_bounds__(256) void nv12_to_rgb_kernel(const FrameNv12 frames, float* __restrict__ rgb, int H, int W, int blocks_per_frame) {
+// ------------------------------------------------------------------------------------------ YUV family -> float32 frames
+// silent_nv12_to_rgb / silent_p010_to_rgb / silent_yuv_to_rgb / silent_yuv16_to_rgb: the frames the pyramid kernels see for a batch of
+// frame kind FT, [n, H, W, 3] float32 -- one thread per pixel, the three channels through the loaders' own device functions (the kind's
+// yuv(), i.e. p010_values / yuv16_values for the uint16 kinds, + nv12_channel).  Blocks of 256 pixels of one frame.
+template <typename FT>
+__global__ __launch_bounds__(256) void source_to_rgb_kernel(const FT frames, float* __restrict__ rgb, int H, int W, int blocks_per_frame) {
+    static_assert(kFrameYuvFamily<FT>, "NV12 / P010 / YUV / 16-bit YUV surfaces");
     const int frame = (int)(blockIdx.x / (unsigned)blocks_per_frame);
     const long long p = (long long)(blockIdx.x - (unsigned)frame * (unsigned)blocks_per_frame) * 256 + threadIdx.x;
     if (p >= (long long)H * W) return;
     const int y = (int)(p / W), x = (int)(p - (long long)y * W);
-    const Nv12Src src = frame_of(frames, frame);
-    float yv, uv, vv;
-    src.yuv(y, x, yv, uv, vv);
-    float* __restrict__ dst = rgb + ((long long)frame * H * W + p) * 3;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) dst[ch] = nv12_channel(yv, uv, vv, src.m[3 * ch], src.m[3 * ch + 1], src.m[3 * ch + 2]);
-}
-
-// silent_p010_to_rgb: the same for a P010 / P012 / P016 batch (P010Src::yuv + nv12_channel)
-template <int C = 3>
-__global__ __launch_bounds__(256) void p010_to_rgb_kernel(const FrameP010 frames, float* __restrict__ rgb, int H, int W, int blocks_per_frame) {
-    const int frame = (int)(blockIdx.x / (unsigned)blocks_per_frame);
-    const long long p = (long long)(blockIdx.x - (unsigned)frame * (unsigned)blocks_per_frame) * 256 + threadIdx.x;
-    if (p >= (long long)H * W) return;
-    const int y = (int)(p / W), x = (int)(p - (long long)y * W);
-    const P010Src src = frame_of(frames, frame);
-    float yv, uv, vv;
-    src.yuv(y, x, yv, uv, vv);
-    float* __restrict__ dst = rgb + ((long long)frame * H * W + p) * 3;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) dst[ch] = nv12_channel(yv, uv, vv, src.m[3 * ch], src.m[3 * ch + 1], src.m[3 * ch + 2]);
-}
-
-// silent_yuv_to_rgb: the same for a planar / packed 8-bit YUV batch (YuvSrc::yuv + nv12_channel)
-template <int C = 3>
-__global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const FrameYuv frames, float* __restrict__ rgb, int H, int W, int blocks_per_frame) {
-    const int frame = (int)(blockIdx.x / (unsigned)blocks_per_frame);
-    const long long p = (long long)(blockIdx.x - (unsigned)frame * (unsigned)blocks_per_frame) * 256 + threadIdx.x;
-    if (p >= (long long)H * W) return;
-    const int y = (int)(p / W), x = (int)(p - (long long)y * W);
-    const YuvSrc src = frame_of(frames, frame);
-    float yv, uv, vv;
-    src.yuv(y, x, yv, uv, vv);
-    float* __restrict__ dst = rgb + ((long long)frame * H * W + p) * 3;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) dst[ch] = nv12_channel(yv, uv, vv, src.m[3 * ch], src.m[3 * ch + 1], src.m[3 * ch + 2]);
-}
-
-// silent_yuv16_to_rgb: the same for a planar / semi-planar / packed 16-bit YUV batch (Yuv16Src::yuv, i.e. yuv16_values, + nv12_channel)
-template <int C = 3>
-__global__ __launch_bounds__(256) void yuv16_to_rgb_kernel(const FrameYuv16 frames, float* __restrict__ rgb, int H, int W, int blocks_per_frame) {
-    const int frame = (int)(blockIdx.x / (unsigned)blocks_per_frame);
-    const long long p = (long long)(blockIdx.x - (unsigned)frame * (unsigned)blocks_per_frame) * 256 + threadIdx.x;
-    if (p >= (long long)H * W) return;
-    const int y = (int)(p / W), x = (int)(p - (long long)y * W);
-    const Yuv16Src src = frame_of(frames, frame);
+    const frame_src<FT> src = frame_of(frames, frame);
     float yv, uv, vv;
     src.yuv(y, x, yv, uv, vv);
     float* __restrict__ dst = rgb + ((long long)frame * H * W + p) * 3;

@@ -982,32 +982,81 @@ SILENT_EXPORT int silent_pyramid_rgb8_view(silent_ctx* ctx, const silent_pyramid
     return on_exception(ctx, "silent_pyramid_rgb8_view");
 }
 
-// NV12 decoder surfaces (silent_hip.h): the struct's own refusals, then the shared ones, all under the entry point's name.  The host
-// forms stage exactly the luma span and the chroma span and rebase the two pointers.
-static int pyramid_nv12(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_nv12_frames* f, int n_frames, float* pyr,
-                        silent_stream stream) {
-    const char* who = "silent_pyramid_nv12";
-    size_t y_span = 0, uv_span = 0;
-    TRY(check_nv12(ctx, who, plan != nullptr, plan ? plan->tab.H : 0, plan ? plan->tab.W : 0, f, n_frames, &y_span, &uv_span));
+// The YUV-family colour sources (silent_hip.h; Source<S>, silent_plan.h): NV12 and P010 / P012 / P016 decoder surfaces, planar / packed
+// 8-bit YUV, 16-bit YUV.  The struct's own refusals, then the shared ones, all under the entry point's name.  A triple struct that IS
+// NV12 / P010 takes the pair kernels (with_yuv).  What the host forms stage: a pair struct exactly the luma span and the chroma span, as
+// two inputs; a triple struct the union of its three spans (yuv_stage: a packed buffer once; an interval starts at a plane's address,
+// so staged uint16 planes stay 2-byte aligned) -- and the plane pointers are rebased.
+template <class S, class F>
+static int source_host(silent_ctx* ctx, const S* f, size_t y_span, size_t c_span, int n_frames, void* out, size_t out_bytes, F&& launch) {
+    typedef typename Source<S>::elem E;
+    HostStage hs(ctx);
+    int in[3] = {0, 0, 0}, of[3] = {0, 1, 1};
+    size_t delta[3] = {0, 0, 0};
+    if constexpr (Source<S>::pair) {
+        in[0] = hs.in(f->y, y_span);
+        in[1] = hs.in(f->uv, c_span);
+    } else {
+        const YuvStage st = yuv_stage(f, y_span, c_span);
+        for (int i = 0; i < st.n; ++i) in[i] = hs.in(st.start[i], st.bytes[i]);
+        for (int k = 0; k < 3; ++k) of[k] = st.of[k], delta[k] = st.delta[k];
+    }
+    const int o = hs.out(out, out_bytes);
+    return hs.run([&] {
+        const E* p[3];
+        for (int k = 0; k < 3; ++k) p[k] = reinterpret_cast<const E*>(hs.dev<uint8_t>(in[of[k]]) + delta[k]);
+        return with_source(f, p, n_frames, [&](auto frames) { return launch(frames, hs.dev<float>(o), (hipStream_t) nullptr); });
+    });
+}
+// f(frames) with the struct's own planes (the _dev forms)
+template <class S, class F>
+static int source_dev(const S* f, int n_frames, F&& launch) {
+    const typename Source<S>::elem* p[3];
+    p[0] = f->y;
+    if constexpr (Source<S>::pair) p[1] = p[2] = f->uv;
+    else p[1] = f->u, p[2] = f->v;
+    return with_source(f, p, n_frames, launch);
+}
+
+template <class S>
+static int pyramid_source(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const S* f, int n_frames, float* pyr, silent_stream stream) {
+    const char* who = Source<S>::pyramid;
+    size_t y_span = 0, c_span = 0;
+    TRY(check_source(ctx, who, plan != nullptr, plan ? plan->tab.H : 0, plan ? plan->tab.W : 0, f, n_frames, &y_span, &c_span));
     TRY(pyramid_checks<float>(ctx, who, plan, true, n_frames, pyr));
     if (plan->tab.C != 3)
-        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": NV12 surfaces are for 3-channel plans (a single-channel plan reads the luma plane through silent_pyramid_view)");
-    if (!host) {
-        const Nv12 s = nv12_frames(f, f->y, f->uv, n_frames);
-        return launch_pyramid_rgb8(ctx, who, plan, &s, n_frames, pyr, (hipStream_t)stream);
-    }
-    HostStage hs(ctx);
-    const int a = hs.in(f->y, y_span), b = hs.in(f->uv, uv_span), o = hs.out(pyr, (size_t)plan->tab.frame_px_out * 3 * 4 * n_frames);
-    return hs.run([&] {
-        const Nv12 s = nv12_frames(f, hs.dev<uint8_t>(a), hs.dev<uint8_t>(b), n_frames);
-        return launch_pyramid_rgb8(ctx, who, plan, &s, n_frames, hs.dev<float>(o), nullptr);
-    });
+        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": " + Source<S>::noun + " are for 3-channel plans (a single-channel plan reads the luma plane through " +
+                                                   (sizeof(typename Source<S>::elem) == 2 ? "silent_pyramid_view16)" : "silent_pyramid_view)"));
+    auto launch = [&](auto frames, float* out, hipStream_t s) { return launch_pyramid_rgb8(ctx, who, plan, frames, n_frames, out, s); };
+    if (!host) return source_dev(f, n_frames, [&](auto frames) { return launch(frames, pyr, (hipStream_t)stream); });
+    return source_host(ctx, f, y_span, c_span, n_frames, pyr, (size_t)plan->tab.frame_px_out * 3 * 4 * n_frames, launch);
+}
+
+// the converted frames themselves, [n_frames, H, W, 3] float32 (source_to_rgb_kernel on the frame kind that reads the struct: the
+// loaders' own device functions)
+template <class S>
+static int source_to_rgb(silent_ctx* ctx, bool host, const S* f, int n_frames, int H, int W, float* rgb, silent_stream stream) {
+    const char* who = Source<S>::to_rgb;
+    size_t y_span = 0, c_span = 0;
+    TRY(check_source(ctx, who, true, H, W, f, n_frames, &y_span, &c_span));
+    if (!rgb) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
+    const long long per_frame = ((long long)H * W + 255) / 256;
+    if (per_frame * n_frames > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many blocks for one launch");
+    auto launch = [&](auto frames, float* out, hipStream_t s) {
+        typedef typename std::remove_cv<typename std::remove_pointer<decltype(frames)>::type>::type FT;
+        hipLaunchKernelGGL(silent::source_to_rgb_kernel<FT>, dim3((unsigned)(per_frame * n_frames)), dim3(256), 0, s, *frames, out, H, W, (int)per_frame);
+        (void)frames;
+        return check_launch(ctx, who);
+    };
+    if (!host) return source_dev(f, n_frames, [&](auto frames) { return launch(frames, rgb, (hipStream_t)stream); });
+    return source_host(ctx, f, y_span, c_span, n_frames, rgb, (size_t)H * W * 3 * 4 * n_frames, launch);
 }
 
 SILENT_EXPORT int silent_pyramid_nv12_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_nv12_frames* frames, int n_frames,
                                           float* pyr, silent_stream stream) try {
     NEED_CTX(ctx);
-    return pyramid_nv12(ctx, false, plan, frames, n_frames, pyr, stream);
+    return pyramid_source(ctx, false, plan, frames, n_frames, pyr, stream);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_nv12_dev");
 }
@@ -1015,73 +1064,30 @@ SILENT_EXPORT int silent_pyramid_nv12_dev(silent_ctx* ctx, const silent_pyramid_
 SILENT_EXPORT int silent_pyramid_nv12(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_nv12_frames* frames, int n_frames,
                                       float* pyr) try {
     NEED_CTX(ctx);
-    return pyramid_nv12(ctx, true, plan, frames, n_frames, pyr, nullptr);
+    return pyramid_source(ctx, true, plan, frames, n_frames, pyr, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_nv12");
-}
-
-// the converted frames themselves, [n_frames, H, W, 3] float32 (nv12_to_rgb_kernel: the loaders' device function)
-static int nv12_to_rgb(silent_ctx* ctx, bool host, const silent_nv12_frames* f, int n_frames, int H, int W, float* rgb, silent_stream stream) {
-    const char* who = "silent_nv12_to_rgb";
-    size_t y_span = 0, uv_span = 0;
-    TRY(check_nv12(ctx, who, true, H, W, f, n_frames, &y_span, &uv_span));
-    if (!rgb) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
-    const long long per_frame = ((long long)H * W + 255) / 256;
-    if (per_frame * n_frames > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many blocks for one launch");
-    auto launch = [&](const uint8_t* y, const uint8_t* uv, float* out, hipStream_t s) {
-        const Nv12 k = nv12_frames(f, y, uv, n_frames);
-        hipLaunchKernelGGL(nv12_to_rgb_kernel<3>, dim3((unsigned)(per_frame * n_frames)), dim3(256), 0, s, k, out, H, W, (int)per_frame);
-        (void)k;
-        return check_launch(ctx, who);
-    };
-    if (!host) return launch(f->y, f->uv, rgb, (hipStream_t)stream);
-    HostStage hs(ctx);
-    const int a = hs.in(f->y, y_span), b = hs.in(f->uv, uv_span), o = hs.out(rgb, (size_t)H * W * 3 * 4 * n_frames);
-    return hs.run([&] { return launch(hs.dev<uint8_t>(a), hs.dev<uint8_t>(b), hs.dev<float>(o), nullptr); });
 }
 
 SILENT_EXPORT int silent_nv12_to_rgb_dev(silent_ctx* ctx, const silent_nv12_frames* frames, int n_frames, int H, int W, float* rgb,
                                          silent_stream stream) try {
     NEED_CTX(ctx);
-    return nv12_to_rgb(ctx, false, frames, n_frames, H, W, rgb, stream);
+    return source_to_rgb(ctx, false, frames, n_frames, H, W, rgb, stream);
 } catch (...) {
     return on_exception(ctx, "silent_nv12_to_rgb_dev");
 }
 
 SILENT_EXPORT int silent_nv12_to_rgb(silent_ctx* ctx, const silent_nv12_frames* frames, int n_frames, int H, int W, float* rgb) try {
     NEED_CTX(ctx);
-    return nv12_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
+    return source_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_nv12_to_rgb");
-}
-
-// P010 / P012 / P016 decoder surfaces (silent_hip.h): the NV12 entry points with uint16 elements -- the struct's own refusals, then the
-// shared ones, under the entry point's name; the host forms stage exactly the two spans and rebase the two pointers.
-static int pyramid_p010(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_p010_frames* f, int n_frames, float* pyr,
-                        silent_stream stream) {
-    const char* who = "silent_pyramid_p010";
-    size_t y_span = 0, uv_span = 0;
-    TRY(check_p010(ctx, who, plan != nullptr, plan ? plan->tab.H : 0, plan ? plan->tab.W : 0, f, n_frames, &y_span, &uv_span));
-    TRY(pyramid_checks<float>(ctx, who, plan, true, n_frames, pyr));
-    if (plan->tab.C != 3)
-        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": P010 surfaces are for 3-channel plans (a single-channel plan reads the luma plane through silent_pyramid_view16)");
-    if (!host) {
-        const P010 s = p010_frames(f, f->y, f->uv, n_frames);
-        return launch_pyramid_rgb8(ctx, who, plan, &s, n_frames, pyr, (hipStream_t)stream);
-    }
-    HostStage hs(ctx);
-    const int a = hs.in(f->y, y_span), b = hs.in(f->uv, uv_span), o = hs.out(pyr, (size_t)plan->tab.frame_px_out * 3 * 4 * n_frames);
-    return hs.run([&] {
-        const P010 s = p010_frames(f, hs.dev<uint16_t>(a), hs.dev<uint16_t>(b), n_frames);
-        return launch_pyramid_rgb8(ctx, who, plan, &s, n_frames, hs.dev<float>(o), nullptr);
-    });
 }
 
 SILENT_EXPORT int silent_pyramid_p010_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_p010_frames* frames, int n_frames,
                                           float* pyr, silent_stream stream) try {
     NEED_CTX(ctx);
-    return pyramid_p010(ctx, false, plan, frames, n_frames, pyr, stream);
+    return pyramid_source(ctx, false, plan, frames, n_frames, pyr, stream);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_p010_dev");
 }
@@ -1089,81 +1095,30 @@ SILENT_EXPORT int silent_pyramid_p010_dev(silent_ctx* ctx, const silent_pyramid_
 SILENT_EXPORT int silent_pyramid_p010(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_p010_frames* frames, int n_frames,
                                       float* pyr) try {
     NEED_CTX(ctx);
-    return pyramid_p010(ctx, true, plan, frames, n_frames, pyr, nullptr);
+    return pyramid_source(ctx, true, plan, frames, n_frames, pyr, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_p010");
-}
-
-// the converted frames themselves, [n_frames, H, W, 3] float32 (p010_to_rgb_kernel: the loaders' device functions)
-static int p010_to_rgb(silent_ctx* ctx, bool host, const silent_p010_frames* f, int n_frames, int H, int W, float* rgb, silent_stream stream) {
-    const char* who = "silent_p010_to_rgb";
-    size_t y_span = 0, uv_span = 0;
-    TRY(check_p010(ctx, who, true, H, W, f, n_frames, &y_span, &uv_span));
-    if (!rgb) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
-    const long long per_frame = ((long long)H * W + 255) / 256;
-    if (per_frame * n_frames > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many blocks for one launch");
-    auto launch = [&](const uint16_t* y, const uint16_t* uv, float* out, hipStream_t s) {
-        const P010 k = p010_frames(f, y, uv, n_frames);
-        hipLaunchKernelGGL(p010_to_rgb_kernel<3>, dim3((unsigned)(per_frame * n_frames)), dim3(256), 0, s, k, out, H, W, (int)per_frame);
-        (void)k;
-        return check_launch(ctx, who);
-    };
-    if (!host) return launch(f->y, f->uv, rgb, (hipStream_t)stream);
-    HostStage hs(ctx);
-    const int a = hs.in(f->y, y_span), b = hs.in(f->uv, uv_span), o = hs.out(rgb, (size_t)H * W * 3 * 4 * n_frames);
-    return hs.run([&] { return launch(hs.dev<uint16_t>(a), hs.dev<uint16_t>(b), hs.dev<float>(o), nullptr); });
 }
 
 SILENT_EXPORT int silent_p010_to_rgb_dev(silent_ctx* ctx, const silent_p010_frames* frames, int n_frames, int H, int W, float* rgb,
                                          silent_stream stream) try {
     NEED_CTX(ctx);
-    return p010_to_rgb(ctx, false, frames, n_frames, H, W, rgb, stream);
+    return source_to_rgb(ctx, false, frames, n_frames, H, W, rgb, stream);
 } catch (...) {
     return on_exception(ctx, "silent_p010_to_rgb_dev");
 }
 
 SILENT_EXPORT int silent_p010_to_rgb(silent_ctx* ctx, const silent_p010_frames* frames, int n_frames, int H, int W, float* rgb) try {
     NEED_CTX(ctx);
-    return p010_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
+    return source_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_p010_to_rgb");
-}
-
-// Planar / packed 8-bit YUV (silent_hip.h): the struct's own refusals, then the shared ones, under the entry point's name; a struct that
-// is NV12 takes the NV12 kernels (with_yuv).  The host forms stage the union of the three spans (yuv_stage: a packed buffer once) and
-// rebase the three pointers.
-template <class F>
-static int yuv_host(silent_ctx* ctx, const silent_yuv_frames* f, size_t y_span, size_t c_span, int n_frames, void* out, size_t out_bytes, F&& launch) {
-    const YuvStage st = yuv_stage(f, y_span, c_span);
-    HostStage hs(ctx);
-    int in[3] = {0, 0, 0};
-    for (int i = 0; i < st.n; ++i) in[i] = hs.in(st.start[i], st.bytes[i]);
-    const int o = hs.out(out, out_bytes);
-    return hs.run([&] {
-        const uint8_t* p[3];
-        for (int k = 0; k < 3; ++k) p[k] = hs.dev<uint8_t>(in[st.of[k]]) + st.delta[k];
-        return with_yuv(f, p[0], p[1], p[2], n_frames, [&](auto frames) { return launch(frames, hs.dev<float>(o), (hipStream_t) nullptr); });
-    });
-}
-
-static int pyramid_yuv(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_yuv_frames* f, int n_frames, float* pyr,
-                       silent_stream stream) {
-    const char* who = "silent_pyramid_yuv";
-    size_t y_span = 0, c_span = 0;
-    TRY(check_yuv(ctx, who, plan != nullptr, plan ? plan->tab.H : 0, plan ? plan->tab.W : 0, f, n_frames, &y_span, &c_span));
-    TRY(pyramid_checks<float>(ctx, who, plan, true, n_frames, pyr));
-    if (plan->tab.C != 3)
-        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": YUV frames are for 3-channel plans (a single-channel plan reads the luma plane through silent_pyramid_view)");
-    auto launch = [&](auto frames, float* out, hipStream_t s) { return launch_pyramid_rgb8(ctx, who, plan, frames, n_frames, out, s); };
-    if (!host) return with_yuv(f, f->y, f->u, f->v, n_frames, [&](auto frames) { return launch(frames, pyr, (hipStream_t)stream); });
-    return yuv_host(ctx, f, y_span, c_span, n_frames, pyr, (size_t)plan->tab.frame_px_out * 3 * 4 * n_frames, launch);
 }
 
 SILENT_EXPORT int silent_pyramid_yuv_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_yuv_frames* frames, int n_frames,
                                          float* pyr, silent_stream stream) try {
     NEED_CTX(ctx);
-    return pyramid_yuv(ctx, false, plan, frames, n_frames, pyr, stream);
+    return pyramid_source(ctx, false, plan, frames, n_frames, pyr, stream);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_yuv_dev");
 }
@@ -1171,83 +1126,30 @@ SILENT_EXPORT int silent_pyramid_yuv_dev(silent_ctx* ctx, const silent_pyramid_p
 SILENT_EXPORT int silent_pyramid_yuv(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_yuv_frames* frames, int n_frames,
                                      float* pyr) try {
     NEED_CTX(ctx);
-    return pyramid_yuv(ctx, true, plan, frames, n_frames, pyr, nullptr);
+    return pyramid_source(ctx, true, plan, frames, n_frames, pyr, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_yuv");
-}
-
-// the converted frames themselves, [n_frames, H, W, 3] float32 (yuv_to_rgb_kernel, nv12_to_rgb_kernel for a struct that is NV12)
-static void yuv_to_rgb_launch(const Yuv* k, unsigned blocks, hipStream_t s, float* out, int H, int W, int per_frame) {
-    hipLaunchKernelGGL(yuv_to_rgb_kernel<3>, dim3(blocks), dim3(256), 0, s, *k, out, H, W, per_frame);
-}
-static void yuv_to_rgb_launch(const Nv12* k, unsigned blocks, hipStream_t s, float* out, int H, int W, int per_frame) {
-    hipLaunchKernelGGL(nv12_to_rgb_kernel<3>, dim3(blocks), dim3(256), 0, s, *k, out, H, W, per_frame);
-}
-static int yuv_to_rgb(silent_ctx* ctx, bool host, const silent_yuv_frames* f, int n_frames, int H, int W, float* rgb, silent_stream stream) {
-    const char* who = "silent_yuv_to_rgb";
-    size_t y_span = 0, c_span = 0;
-    TRY(check_yuv(ctx, who, true, H, W, f, n_frames, &y_span, &c_span));
-    if (!rgb) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
-    const long long per_frame = ((long long)H * W + 255) / 256;
-    if (per_frame * n_frames > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many blocks for one launch");
-    auto launch = [&](auto frames, float* out, hipStream_t s) {
-        yuv_to_rgb_launch(frames, (unsigned)(per_frame * n_frames), s, out, H, W, (int)per_frame);
-        return check_launch(ctx, who);
-    };
-    if (!host) return with_yuv(f, f->y, f->u, f->v, n_frames, [&](auto frames) { return launch(frames, rgb, (hipStream_t)stream); });
-    return yuv_host(ctx, f, y_span, c_span, n_frames, rgb, (size_t)H * W * 3 * 4 * n_frames, launch);
 }
 
 SILENT_EXPORT int silent_yuv_to_rgb_dev(silent_ctx* ctx, const silent_yuv_frames* frames, int n_frames, int H, int W, float* rgb,
                                         silent_stream stream) try {
     NEED_CTX(ctx);
-    return yuv_to_rgb(ctx, false, frames, n_frames, H, W, rgb, stream);
+    return source_to_rgb(ctx, false, frames, n_frames, H, W, rgb, stream);
 } catch (...) {
     return on_exception(ctx, "silent_yuv_to_rgb_dev");
 }
 
 SILENT_EXPORT int silent_yuv_to_rgb(silent_ctx* ctx, const silent_yuv_frames* frames, int n_frames, int H, int W, float* rgb) try {
     NEED_CTX(ctx);
-    return yuv_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
+    return source_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_yuv_to_rgb");
-}
-
-// Planar / semi-planar / packed 16-bit YUV (silent_hip.h): the struct's own refusals, then the shared ones, under the entry point's
-// name; a struct that is P010 takes the P010 kernels (with_yuv16).  The host forms stage the union of the three spans (yuv_stage: a
-// packed buffer once) and rebase the three pointers; an interval starts at a plane's address, so the staged copies stay 2-byte aligned.
-template <class F>
-static int yuv16_host(silent_ctx* ctx, const silent_yuv16_frames* f, size_t y_span, size_t c_span, int n_frames, void* out, size_t out_bytes, F&& launch) {
-    const YuvStage st = yuv_stage(f, y_span, c_span);
-    HostStage hs(ctx);
-    int in[3] = {0, 0, 0};
-    for (int i = 0; i < st.n; ++i) in[i] = hs.in(st.start[i], st.bytes[i]);
-    const int o = hs.out(out, out_bytes);
-    return hs.run([&] {
-        const uint16_t* p[3];
-        for (int k = 0; k < 3; ++k) p[k] = reinterpret_cast<const uint16_t*>(hs.dev<uint8_t>(in[st.of[k]]) + st.delta[k]);
-        return with_yuv16(f, p[0], p[1], p[2], n_frames, [&](auto frames) { return launch(frames, hs.dev<float>(o), (hipStream_t) nullptr); });
-    });
-}
-
-static int pyramid_yuv16(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_yuv16_frames* f, int n_frames, float* pyr,
-                         silent_stream stream) {
-    const char* who = "silent_pyramid_yuv16";
-    size_t y_span = 0, c_span = 0;
-    TRY(check_yuv16(ctx, who, plan != nullptr, plan ? plan->tab.H : 0, plan ? plan->tab.W : 0, f, n_frames, &y_span, &c_span));
-    TRY(pyramid_checks<float>(ctx, who, plan, true, n_frames, pyr));
-    if (plan->tab.C != 3)
-        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": 16-bit YUV frames are for 3-channel plans (a single-channel plan reads the luma plane through silent_pyramid_view16)");
-    auto launch = [&](auto frames, float* out, hipStream_t s) { return launch_pyramid_rgb8(ctx, who, plan, frames, n_frames, out, s); };
-    if (!host) return with_yuv16(f, f->y, f->u, f->v, n_frames, [&](auto frames) { return launch(frames, pyr, (hipStream_t)stream); });
-    return yuv16_host(ctx, f, y_span, c_span, n_frames, pyr, (size_t)plan->tab.frame_px_out * 3 * 4 * n_frames, launch);
 }
 
 SILENT_EXPORT int silent_pyramid_yuv16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_yuv16_frames* frames, int n_frames,
                                            float* pyr, silent_stream stream) try {
     NEED_CTX(ctx);
-    return pyramid_yuv16(ctx, false, plan, frames, n_frames, pyr, stream);
+    return pyramid_source(ctx, false, plan, frames, n_frames, pyr, stream);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_yuv16_dev");
 }
@@ -1255,45 +1157,22 @@ SILENT_EXPORT int silent_pyramid_yuv16_dev(silent_ctx* ctx, const silent_pyramid
 SILENT_EXPORT int silent_pyramid_yuv16(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_yuv16_frames* frames, int n_frames,
                                        float* pyr) try {
     NEED_CTX(ctx);
-    return pyramid_yuv16(ctx, true, plan, frames, n_frames, pyr, nullptr);
+    return pyramid_source(ctx, true, plan, frames, n_frames, pyr, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_pyramid_yuv16");
-}
-
-// the converted frames themselves, [n_frames, H, W, 3] float32 (yuv16_to_rgb_kernel, p010_to_rgb_kernel for a struct that is P010)
-static void yuv16_to_rgb_launch(const Yuv16* k, unsigned blocks, hipStream_t s, float* out, int H, int W, int per_frame) {
-    hipLaunchKernelGGL(yuv16_to_rgb_kernel<3>, dim3(blocks), dim3(256), 0, s, *k, out, H, W, per_frame);
-}
-static void yuv16_to_rgb_launch(const P010* k, unsigned blocks, hipStream_t s, float* out, int H, int W, int per_frame) {
-    hipLaunchKernelGGL(p010_to_rgb_kernel<3>, dim3(blocks), dim3(256), 0, s, *k, out, H, W, per_frame);
-}
-static int yuv16_to_rgb(silent_ctx* ctx, bool host, const silent_yuv16_frames* f, int n_frames, int H, int W, float* rgb, silent_stream stream) {
-    const char* who = "silent_yuv16_to_rgb";
-    size_t y_span = 0, c_span = 0;
-    TRY(check_yuv16(ctx, who, true, H, W, f, n_frames, &y_span, &c_span));
-    if (!rgb) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
-    const long long per_frame = ((long long)H * W + 255) / 256;
-    if (per_frame * n_frames > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many blocks for one launch");
-    auto launch = [&](auto frames, float* out, hipStream_t s) {
-        yuv16_to_rgb_launch(frames, (unsigned)(per_frame * n_frames), s, out, H, W, (int)per_frame);
-        return check_launch(ctx, who);
-    };
-    if (!host) return with_yuv16(f, f->y, f->u, f->v, n_frames, [&](auto frames) { return launch(frames, rgb, (hipStream_t)stream); });
-    return yuv16_host(ctx, f, y_span, c_span, n_frames, rgb, (size_t)H * W * 3 * 4 * n_frames, launch);
 }
 
 SILENT_EXPORT int silent_yuv16_to_rgb_dev(silent_ctx* ctx, const silent_yuv16_frames* frames, int n_frames, int H, int W, float* rgb,
                                           silent_stream stream) try {
     NEED_CTX(ctx);
-    return yuv16_to_rgb(ctx, false, frames, n_frames, H, W, rgb, stream);
+    return source_to_rgb(ctx, false, frames, n_frames, H, W, rgb, stream);
 } catch (...) {
     return on_exception(ctx, "silent_yuv16_to_rgb_dev");
 }
 
 SILENT_EXPORT int silent_yuv16_to_rgb(silent_ctx* ctx, const silent_yuv16_frames* frames, int n_frames, int H, int W, float* rgb) try {
     NEED_CTX(ctx);
-    return yuv16_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
+    return source_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_yuv16_to_rgb");
 }

@@ -202,86 +202,127 @@ __host__ __device__ __forceinline__ int w3_nv12_px(const Walk3Args& args, int A,
     const int p = w3_nv12_p0(A) + lane + 64 * k;
     return p < 0 ? 0 : (p > args.W - 1 ? args.W - 1 : p);
 }
-// stream row s of a block: byte offsets of its luma row from `y` and of its chroma row from `uv` (scalar 64-bit arithmetic in the
-// kernel).  The chroma row is that of the FRAME row: (src_y0 + y) >> 1, not src_y0 / 2 + y / 2.
+// stream row s of a block: byte offsets of its luma row from `y` and of its chroma row from `uv` (triple kinds: from `u` and from `v`
+// alike) -- scalar 64-bit arithmetic in the kernel.  The chroma row is that of the FRAME row: (src_y0 + y) >> 1, not src_y0 / 2 + y / 2.
+// One function for the four kinds; what differs is read through three accessors: the chroma planes' frame and row strides and the
+// vertical chroma shift (pair kinds: 1).
 struct W3Nv12Row {
     long long y, uv;
 };
-__host__ __device__ __forceinline__ W3Nv12Row w3_nv12_row(const Walk3Args& args, const FrameNv12& v, const W3ViewBlock& b, int s) {
+template <typename FT>
+__host__ __device__ __forceinline__ long long w3_c_frame_stride(const FT& v) {
+    if constexpr (kFrameYuvPair<FT>) return v.uv_frame_stride;
+    else return v.c_frame_stride;
+}
+template <typename FT>
+__host__ __device__ __forceinline__ long long w3_c_row_stride(const FT& v) {
+    if constexpr (kFrameYuvPair<FT>) return v.uv_row_stride;
+    else return v.c_row_stride;
+}
+template <typename FT>
+__host__ __device__ __forceinline__ int w3_c_row_shift(const FT& v) {
+    if constexpr (kFrameYuvPair<FT>) return 1;
+    else return v.sy;
+}
+template <typename FT>
+__host__ __device__ __forceinline__ W3Nv12Row w3_yuv_row(const Walk3Args& args, const FT& v, const W3ViewBlock& b, int s) {
     const Walk3Plan& p = args.plan[b.plan];
     const long long yy = w3_mirror_near(b.y_first + s, p.src_h) + p.src_y0;
-    return W3Nv12Row{(long long)b.frame * v.y_frame_stride + yy * v.y_row_stride, (long long)b.frame * v.uv_frame_stride + (yy >> 1) * v.uv_row_stride};
+    return W3Nv12Row{(long long)b.frame * v.y_frame_stride + yy * v.y_row_stride,
+                     (long long)b.frame * w3_c_frame_stride(v) + (yy >> w3_c_row_shift(v)) * w3_c_row_stride(v)};
 }
-// THE address function: the loads of (block, chunk, row of the chunk, lane, load slot) -- one byte at y_offset from `y` and two bytes
-// at uv_offset from `uv` (any alignment)
+// THE address function: the loads of (block, chunk, row of the chunk, lane, load slot), BYTE offsets from the planes.
+//   FrameNv12:  one byte at y_offset from `y`, two bytes at uv_offset from `uv` (any alignment)
+//   FrameP010:  two bytes at y_offset, four bytes at uv_offset (byte columns 2 x and 4 (x >> 1); both 2-byte aligned)
+//   FrameYuv:   one byte each at y_offset from `y`, u_offset from `u`, v_offset from `v` (columns x * y_pixel_stride, (x >> sx) * c_pixel_stride)
+//   FrameYuv16: two bytes each at the same three offsets (all even)
+// tests/rgb_{nv12,p010,yuv,yuv16}_host_main.cpp enumerate it over whole launches through the four spellings below: every offset is
+// inside the spans, element-aligned, and that of an element that is some pixel's Y, U or V.
 struct W3Nv12Load {
     long long y_offset, uv_offset;
 };
-__host__ __device__ __forceinline__ W3Nv12Load w3_nv12_load(const Walk3Args& args, const FrameNv12& v, int px, unsigned bid, int chunk, int row,
-                                                            int lane, int k) {
-    const W3ViewBlock b = w3_view_block(args, px, bid);
-    const W3Nv12Row r = w3_nv12_row(args, v, b, chunk * kW3CH + row);
-    const int x = w3_nv12_px(args, b.A, lane, k);
-    return W3Nv12Load{r.y + nv12_y_col(x), r.uv + nv12_uv_col(x)};
+// byte columns of frame column x in a luma row and in a chroma row of a pair kind
+template <typename FT>
+__host__ __device__ __forceinline__ long long w3_pair_y_col(int x) {
+    if constexpr (kFrameP010<FT>) return p010_y_col(x);
+    else return nv12_y_col(x);
 }
-// ---- and on P010 / P012 / P016 surfaces (FrameP010, silent_pyramid_p010): the same pixel per lane and load slot (w3_nv12_p0, the same
-// ring mapping), a 2-byte luma element and the 4-byte (U, V) pair -- byte columns 2 x and 4 (x >> 1) behind the same scalar row terms.
-// tests/rgb_p010_host_main.cpp enumerates them over whole launches (inside the spans, element-aligned, the crops covered).
-__host__ __device__ __forceinline__ int w3_p010_px(const Walk3Args& args, int A, int lane, int k) { return w3_nv12_px(args, A, lane, k); }
-__host__ __device__ __forceinline__ W3Nv12Row w3_p010_row(const Walk3Args& args, const FrameP010& v, const W3ViewBlock& b, int s) {
-    const Walk3Plan& p = args.plan[b.plan];
-    const long long yy = w3_mirror_near(b.y_first + s, p.src_h) + p.src_y0;
-    return W3Nv12Row{(long long)b.frame * v.y_frame_stride + yy * v.y_row_stride, (long long)b.frame * v.uv_frame_stride + (yy >> 1) * v.uv_row_stride};
+template <typename FT>
+__host__ __device__ __forceinline__ long long w3_pair_uv_col(int x) {
+    if constexpr (kFrameP010<FT>) return p010_uv_col(x);
+    else return nv12_uv_col(x);
 }
-// THE address function: two bytes at y_offset from `y` and four bytes at uv_offset from `uv` (both 2-byte aligned)
-__host__ __device__ __forceinline__ W3Nv12Load w3_p010_load(const Walk3Args& args, const FrameP010& v, int px, unsigned bid, int chunk, int row,
-                                                            int lane, int k) {
-    const W3ViewBlock b = w3_view_block(args, px, bid);
-    const W3Nv12Row r = w3_p010_row(args, v, b, chunk * kW3CH + row);
-    const int x = w3_p010_px(args, b.A, lane, k);
-    return W3Nv12Load{r.y + p010_y_col(x), r.uv + p010_uv_col(x)};
-}
-// ---- and on planar / packed 8-bit YUV (FrameYuv, silent_pyramid_yuv): the same pixel per lane and load slot (w3_nv12_p0, the same ring
-// mapping), THREE byte loads per slot -- Y behind the luma row term, U and V behind the chroma row term, at byte columns x * y_pixel_stride
-// and (x >> sx) * c_pixel_stride.  The chroma row is (src_y0 + y) >> sy of the FRAME row.  tests/rgb_yuv_host_main.cpp enumerates them
-// over whole launches: every offset is that of a byte that is some pixel's Y, U or V.
-__host__ __device__ __forceinline__ int w3_yuv_px(const Walk3Args& args, int A, int lane, int k) { return w3_nv12_px(args, A, lane, k); }
-// byte offsets of stream row s of a block: the luma row from `y`, and the chroma row from `u` and from `v` alike (W3Nv12Row::uv)
-__host__ __device__ __forceinline__ W3Nv12Row w3_yuv_row(const Walk3Args& args, const FrameYuv& v, const W3ViewBlock& b, int s) {
-    const Walk3Plan& p = args.plan[b.plan];
-    const long long yy = w3_mirror_near(b.y_first + s, p.src_h) + p.src_y0;
-    return W3Nv12Row{(long long)b.frame * v.y_frame_stride + yy * v.y_row_stride, (long long)b.frame * v.c_frame_stride + (yy >> v.sy) * v.c_row_stride};
-}
-// THE address function: one byte each at y_offset from `y`, u_offset from `u` and v_offset from `v`
 struct W3YuvLoad {
     long long y_offset, u_offset, v_offset;
 };
-__host__ __device__ __forceinline__ W3YuvLoad w3_yuv_load(const Walk3Args& args, const FrameYuv& v, int px, unsigned bid, int chunk, int row,
-                                                          int lane, int k) {
+template <typename FT>
+__host__ __device__ __forceinline__ auto w3_yuv_family_load(const Walk3Args& args, const FT& v, int px, unsigned bid, int chunk, int row, int lane, int k) {
     const W3ViewBlock b = w3_view_block(args, px, bid);
     const W3Nv12Row r = w3_yuv_row(args, v, b, chunk * kW3CH + row);
-    const int x = w3_yuv_px(args, b.A, lane, k);
-    const long long c = r.uv + yuv_c_col(x, v.sx, v.c_pixel_stride);
-    return W3YuvLoad{r.y + yuv_y_col(x, v.y_pixel_stride), c, c};
+    const int x = w3_nv12_px(args, b.A, lane, k);
+    if constexpr (kFrameYuvPair<FT>) {
+        return W3Nv12Load{r.y + w3_pair_y_col<FT>(x), r.uv + w3_pair_uv_col<FT>(x)};
+    } else {
+        const long long c = r.uv + yuv_c_col(x, v.sx, v.c_pixel_stride);
+        return W3YuvLoad{r.y + yuv_y_col(x, v.y_pixel_stride), c, c};
+    }
 }
-// ---- and on planar / semi-planar / packed 16-bit YUV (FrameYuv16, silent_pyramid_yuv16): w3_yuv_load with uint16 elements -- THREE
-// 2-byte loads per slot, byte columns x * y_pixel_stride and (x >> sx) * c_pixel_stride (even) behind the same scalar row terms.
-// tests/rgb_yuv16_host_main.cpp enumerates them over whole launches: every offset is the even offset of an element that is some pixel's
-// Y, U or V.
-__host__ __device__ __forceinline__ int w3_yuv16_px(const Walk3Args& args, int A, int lane, int k) { return w3_nv12_px(args, A, lane, k); }
-__host__ __device__ __forceinline__ W3Nv12Row w3_yuv16_row(const Walk3Args& args, const FrameYuv16& v, const W3ViewBlock& b, int s) {
-    const Walk3Plan& p = args.plan[b.plan];
-    const long long yy = w3_mirror_near(b.y_first + s, p.src_h) + p.src_y0;
-    return W3Nv12Row{(long long)b.frame * v.y_frame_stride + yy * v.y_row_stride, (long long)b.frame * v.c_frame_stride + (yy >> v.sy) * v.c_row_stride};
+__host__ __device__ __forceinline__ W3Nv12Load w3_nv12_load(const Walk3Args& args, const FrameNv12& v, int px, unsigned bid, int chunk, int row, int lane, int k) {
+    return w3_yuv_family_load(args, v, px, bid, chunk, row, lane, k);
 }
-// THE address function: two bytes each at y_offset from `y`, u_offset from `u` and v_offset from `v` (BYTE offsets, all even)
-__host__ __device__ __forceinline__ W3YuvLoad w3_yuv16_load(const Walk3Args& args, const FrameYuv16& v, int px, unsigned bid, int chunk, int row,
-                                                            int lane, int k) {
-    const W3ViewBlock b = w3_view_block(args, px, bid);
-    const W3Nv12Row r = w3_yuv16_row(args, v, b, chunk * kW3CH + row);
-    const int x = w3_yuv16_px(args, b.A, lane, k);
-    const long long c = r.uv + yuv_c_col(x, v.sx, v.c_pixel_stride);
-    return W3YuvLoad{r.y + yuv_y_col(x, v.y_pixel_stride), c, c};
+__host__ __device__ __forceinline__ W3Nv12Load w3_p010_load(const Walk3Args& args, const FrameP010& v, int px, unsigned bid, int chunk, int row, int lane, int k) {
+    return w3_yuv_family_load(args, v, px, bid, chunk, row, lane, k);
+}
+__host__ __device__ __forceinline__ W3YuvLoad w3_yuv_load(const Walk3Args& args, const FrameYuv& v, int px, unsigned bid, int chunk, int row, int lane, int k) {
+    return w3_yuv_family_load(args, v, px, bid, chunk, row, lane, k);
+}
+__host__ __device__ __forceinline__ W3YuvLoad w3_yuv16_load(const Walk3Args& args, const FrameYuv16& v, int px, unsigned bid, int chunk, int row, int lane, int k) {
+    return w3_yuv_family_load(args, v, px, bid, chunk, row, lane, k);
+}
+
+// ---- the loader's registers on the family: the element types of a load slot (luma element; the chroma pair, or the U element; the V
+// element of the triple kinds), "fetch slot k of a row" (one template: the loads are the register types' sizes) and "loaded elements ->
+// (Yv, Uv, Vv)" per frame kind.  yr / ur / vr: the row's
+// plane pointers (pair kinds: ur is the pair's plane); ycol / ccol: the slot's byte columns in a luma and in a chroma row.
+template <typename FT>
+struct W3YuvRegs {
+    typedef unsigned char y, c, w;                          // FrameYuv
+};
+template <>
+struct W3YuvRegs<FrameNv12> {
+    typedef unsigned char y, w;
+    typedef unsigned short c;                               // the (U, V) bytes as one 2-byte load
+};
+template <>
+struct W3YuvRegs<FrameP010> {
+    typedef unsigned short y;
+    typedef unsigned c;                                     // the (U, V) elements as one dword
+    typedef unsigned char w;
+};
+template <>
+struct W3YuvRegs<FrameYuv16> {
+    typedef unsigned short y, c, w;
+};
+template <typename FT, typename EY, typename EC, typename EW>
+__device__ __forceinline__ void w3_yuv_fetch(const unsigned char* yr, const unsigned char* ur, const unsigned char* vr, long long ycol, long long ccol,
+                                             EY& ey, EC& ec, EW& ew) {
+    __builtin_memcpy(&ey, yr + ycol, sizeof(EY));
+    __builtin_memcpy(&ec, ur + ccol, sizeof(EC));          // (a pair kind: both chroma elements in one load)
+    if constexpr (kFrameYuvTriple<FT>) __builtin_memcpy(&ew, vr + ccol, sizeof(EW));
+}
+__device__ __forceinline__ void w3_yuv_values(const FrameNv12& f, unsigned char ey, unsigned short ec, const unsigned char&, float& yv, float& uv, float& vv) {
+    yv = __fsub_rn((float)ey, f.oy);
+    uv = (float)((int)(ec & 0xffu) - 128), vv = (float)((int)(ec >> 8) - 128);
+}
+__device__ __forceinline__ void w3_yuv_values(const FrameP010& f, unsigned short ey, unsigned ec, const unsigned char&, float& yv, float& uv, float& vv) {
+    p010_values(ey, ec, f.oy, f.oc, f.shift, yv, uv, vv);
+}
+__device__ __forceinline__ void w3_yuv_values(const FrameYuv& f, unsigned char ey, unsigned char ec, const unsigned char& ew, float& yv, float& uv, float& vv) {
+    yv = __fsub_rn((float)ey, f.oy);
+    uv = (float)((int)ec - 128), vv = (float)((int)ew - 128);
+}
+__device__ __forceinline__ void w3_yuv_values(const FrameYuv16& f, unsigned short ey, unsigned short ec, const unsigned short& ew, float& yv, float& uv, float& vv) {
+    yuv16_values(ey, ec, ew, f.oy, f.oc, f.shift, f.mask, yv, uv, vv);
 }
 
 // FT: the frame element type -- float, or unsigned char (packed interleaved uint8 colour frames [n, H, W, 3], silent_pyramid_rgb8: byte c
@@ -293,7 +334,7 @@ __host__ __device__ __forceinline__ W3YuvLoad w3_yuv16_load(const Walk3Args& arg
 // scalar 64-bit offset (w3_view_row); the ring, the shift, the mirror fix-up and the consumers do not know about strides.  All byte
 // loads of a chunk are issued before one is consumed; the chunk is complete (vmcnt(0) lgkmcnt(0)) before the barrier.  Every address
 // is that of a channel byte of a pixel of the view: nothing outside [data, data + span) is loaded.
-// FT = FrameNv12 (NV12 surfaces, by value): a pixel per lane and load slot (w3_nv12_load), Y byte + (U, V) pair, converted by
+// FT = FrameNv12 (NV12 surfaces, by value): a pixel per lane and load slot (w3_nv12_load; w3_yuv_fetch / w3_yuv_values per kind), Y byte + (U, V) pair, converted by
 // nv12_channel with the coefficients in SGPRs, three ring floats written; the same issue / wait / barrier order as the byte loaders.
 // Every address is that of a luma byte or of the chroma pair of a pixel of the frame.
 // FT = FrameP010 (P010 / P012 / P016 surfaces, by value): the NV12 loader with uint16 elements (w3_p010_load) -- a 2-byte luma load and
@@ -306,13 +347,10 @@ __host__ __device__ __forceinline__ W3YuvLoad w3_yuv16_load(const Walk3Args& arg
 template <int G, int PX, typename FT = float>
 __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<FT> frames, float* __restrict__ pyr,
                                                                     const Walk3Args args, const WalkBorderArgs border) {
-    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT> || kFrameNv12<FT> || kFrameP010<FT> || kFrameYuv<FT> || kFrameYuv16<FT>,
+    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT> || kFrameYuvFamily<FT>,
                   "float32, packed uint8 or strided uint8 colour frames, NV12 / P010 / YUV / 16-bit YUV surfaces");
-    constexpr bool kP10 = kFrameP010<FT>;                            // (uint16 elements, the code in the high bits)
-    constexpr bool kYuv = kFrameYuv<FT>;                             // (three byte planes, pixel strides, chroma shifts)
-    constexpr bool kY16 = kFrameYuv16<FT>;                           // (three uint16 planes, the code behind shift and mask)
-    constexpr bool kYuv3 = kYuv || kY16;                             // three loads per slot, byte columns per lane
-    constexpr bool kNv = kFrameNv12<FT> || kP10 || kYuv3;            // the loader converts (Y, U, V) in registers
+    constexpr bool kYuv3 = kFrameYuvTriple<FT>;                      // three loads per slot, byte columns per lane
+    constexpr bool kNv = kFrameYuvFamily<FT>;                        // the loader converts (Y, U, V) in registers
     constexpr bool kBytes = kFrameBytes<FT> || kFrameRgbView<FT>;   // the loader widens bytes in registers
     static_assert(G == stream_pad_levels(G), "row programs are padded to 4 or 7 levels");
     static_assert(PX == 36 || PX == 32 || PX == 28 || PX == 24, "");
@@ -357,8 +395,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
         typedef typename std::conditional<kFrameRgbSrc<FT>, unsigned char, FT>::type ET;   // element of a frame row
         const ET* __restrict__ src;
         if constexpr (kFrameRgbView<FT>) src = frames.data;    // (rows: w3_view_row)
-        else if constexpr (kP10 || kY16) src = reinterpret_cast<const unsigned char*>(frames.y);   // (rows: w3_p010_row / w3_yuv16_row; strides are bytes)
-        else if constexpr (kNv) src = frames.y;                // (rows: w3_nv12_row)
+        else if constexpr (kNv) src = reinterpret_cast<const unsigned char*>(frames.y);   // (rows: w3_yuv_row; strides are bytes)
         else src = frames + (long long)frame * args.H * args.W * 3;
         const int rowf = args.W * 3;                           // floats (uint8 frames: bytes) of a FRAME row
         // ring float r <-> frame-row float A + r, A = the crop's pixel R0 minus the alignment shift.  Frame widths that are a
@@ -417,54 +454,28 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                 // consumed; a smaller group reuses the registers and pays a latency per group (measured slower:
                 // profiles/rgb_nv12/README.md)
                 constexpr int kNvRows = kYuv3 ? SILENT_W3_YUV_ROWS : SILENT_W3_NV_ROWS;
-                typename std::conditional<kP10 || kY16, unsigned short, unsigned char>::type nvy[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];
-                typename std::conditional<kP10, unsigned, typename std::conditional<kYuv, unsigned char, unsigned short>::type>::type
-                    nvc[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];      // (YUV: the U byte; 16-bit YUV: the U element)
-                typename std::conditional<kY16, unsigned short, unsigned char>::type
-                    nvw[kYuv3 ? kNvRows : 1][kYuv3 ? kNvLoads : 1];  // YUV: the V byte; 16-bit YUV: the V element
+                typedef W3YuvRegs<typename std::conditional<kNv, FT, FrameYuv>::type> NvRegs;
+                typename NvRegs::y nvy[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];   // the luma element
+                typename NvRegs::c nvc[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];   // the chroma pair; YUV: the U element
+                typename NvRegs::w nvw[kNv ? kNvRows : 1][kNv ? kNvLoads : 1];   // YUV: the V element (pair kinds: not used)
                 (void)nvy;
                 (void)nvc;
                 (void)nvw;
                 auto nv_load = [&](int g, int r) {                // row g + r of the chunk into register row r
-                    if constexpr (kY16) {
-                        const W3Nv12Row row = w3_yuv16_row(args, frames, vb, c * kW3CH + g + r);
-                        const unsigned char* yr = src + row.y;
-                        const unsigned char* ur = reinterpret_cast<const unsigned char*>(frames.u) + row.uv;
-                        const unsigned char* vr = reinterpret_cast<const unsigned char*>(frames.v) + row.uv;
-#pragma unroll
-                        for (int k = 0; k < kNvLoads; ++k) {
-                            __builtin_memcpy(&nvy[r][k], yr + yuy[k], 2);
-                            __builtin_memcpy(&nvc[r][k], ur + yuc[k], 2);
-                            __builtin_memcpy(&nvw[r][k], vr + yuc[k], 2);
-                        }
-                    } else if constexpr (kYuv) {
+                    if constexpr (kNv) {
                         const W3Nv12Row row = w3_yuv_row(args, frames, vb, c * kW3CH + g + r);
                         const unsigned char* yr = src + row.y;
-                        const unsigned char* ur = frames.u + row.uv;
-                        const unsigned char* vr = frames.v + row.uv;
-#pragma unroll
-                        for (int k = 0; k < kNvLoads; ++k) {
-                            nvy[r][k] = yr[yuy[k]];
-                            nvc[r][k] = ur[yuc[k]];
-                            nvw[r][k] = vr[yuc[k]];
+                        const unsigned char *ur, *vr;
+                        if constexpr (kYuv3) {
+                            ur = reinterpret_cast<const unsigned char*>(frames.u) + row.uv;
+                            vr = reinterpret_cast<const unsigned char*>(frames.v) + row.uv;
+                        } else {
+                            ur = vr = reinterpret_cast<const unsigned char*>(frames.uv) + row.uv;
                         }
-                    } else if constexpr (kP10) {
-                        const W3Nv12Row row = w3_p010_row(args, frames, vb, c * kW3CH + g + r);
-                        const unsigned char* yr = src + row.y;
-                        const unsigned char* cr = reinterpret_cast<const unsigned char*>(frames.uv) + row.uv;
 #pragma unroll
                         for (int k = 0; k < kNvLoads; ++k) {
-                            __builtin_memcpy(&nvy[r][k], yr + p010_y_col(nvx[k]), 2);
-                            __builtin_memcpy(&nvc[r][k], cr + p010_uv_col(nvx[k]), 4);
-                        }
-                    } else if constexpr (kNv) {
-                        const W3Nv12Row row = w3_nv12_row(args, frames, vb, c * kW3CH + g + r);
-                        const unsigned char* yr = src + row.y;
-                        const unsigned char* cr = frames.uv + row.uv;
-#pragma unroll
-                        for (int k = 0; k < kNvLoads; ++k) {
-                            nvy[r][k] = yr[nv12_y_col(nvx[k])];
-                            __builtin_memcpy(&nvc[r][k], cr + nv12_uv_col(nvx[k]), 2);
+                            if constexpr (kYuv3) w3_yuv_fetch<FT>(yr, ur, vr, yuy[k], yuc[k], nvy[r][k], nvc[r][k], nvw[r][k]);
+                            else w3_yuv_fetch<FT>(yr, ur, vr, w3_pair_y_col<FT>(nvx[k]), w3_pair_uv_col<FT>(nvx[k]), nvy[r][k], nvc[r][k], nvw[r][k]);
                         }
                     }
                 };
@@ -518,17 +529,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
 #pragma unroll
                             for (int k = 0; k < kNvLoads; ++k) {
                                 float yv, uv, vv;
-                                if constexpr (kY16) {
-                                    yuv16_values(nvy[r][k], nvc[r][k], nvw[r][k], frames.oy, frames.oc, frames.shift, frames.mask, yv, uv, vv);
-                                } else if constexpr (kYuv) {
-                                    yv = __fsub_rn((float)nvy[r][k], frames.oy);
-                                    uv = (float)((int)nvc[r][k] - 128), vv = (float)((int)nvw[r][k] - 128);
-                                } else if constexpr (kP10) {
-                                    p010_values(nvy[r][k], nvc[r][k], frames.oy, frames.oc, frames.shift, yv, uv, vv);
-                                } else {
-                                    yv = __fsub_rn((float)nvy[r][k], frames.oy);
-                                    uv = (float)((int)(nvc[r][k] & 0xffu) - 128), vv = (float)((int)(nvc[r][k] >> 8) - 128);
-                                }
+                                w3_yuv_values(frames, nvy[r][k], nvc[r][k], nvw[r][k], yv, uv, vv);
                                 const int q = 3 * (lane + 64 * k) + nvd;     // ring float of channel 0
 #pragma unroll
                                 for (int ch = 0; ch < 3; ++ch)

@@ -177,9 +177,8 @@ class LineEndPipeline(object):
         # silent_pyramid_yuv16_dev, one element per load; pyramid, maps and keypoints are those of the float32 pipeline on
         # _runtime.yuv16_to_rgb(planes, fmt=...), bit for bit.  The conversion is P010's (_runtime.p010_coefficients at the format's
         # depth; "bt2020" is accepted).
-        if self._p010 or self._yuv16:
-            self.nv12_m, self.nv12_oy, self.nv12_oc = _runtime.p010_coefficients(nv12_matrix, nv12_range, nv12_order,
-                                                                                 self._p010 or self._yuv16[2])
+        if self._source and self._source[0].elem == 2:
+            self.nv12_m, self.nv12_oy, self.nv12_oc = _runtime.p010_coefficients(nv12_matrix, nv12_range, nv12_order, self._source[3])
         else:
             self.nv12_m, self.nv12_oy = _runtime.nv12_coefficients(nv12_matrix, nv12_range, nv12_order)
         # accumulation="float64" (mode "gray"): every op sums its taps in float64 and rounds once to float32, like the CPU oracle
@@ -362,25 +361,9 @@ class LineEndPipeline(object):
     def _synthetic_frames(self):
         """Noise frames of the dtype step() takes (the tuners' default batch)."""
         torch = self.torch
-        if self._p010:
-            h, w = self.frame_shape[:2]
-            sh = 16 - self._p010
-            return ((torch.randint(0, 1 << self._p010, (self.batch, h, w), device=self.tdev) << sh).to(torch.uint16),
-                    (torch.randint(0, 1 << self._p010, (self.batch, h // 2, w // 2, 2), device=self.tdev) << sh).to(torch.uint16))
-        if self._yuv16:
-            h, w = self.frame_shape[:2]
-            sx, sy, depth, shift = self._yuv16
-            return tuple((torch.randint(0, 1 << depth, sh, device=self.tdev) << shift).to(torch.uint16)
-                         for sh in ((self.batch, h, w), (self.batch, h >> sy, w >> sx), (self.batch, h >> sy, w >> sx)))
-        if self._yuv:
-            h, w = self.frame_shape[:2]
-            sx, sy = self._yuv
-            return tuple(torch.randint(0, 256, sh, device=self.tdev).to(torch.uint8)
-                         for sh in ((self.batch, h, w), (self.batch, h >> sy, w >> sx), (self.batch, h >> sy, w >> sx)))
-        if self._nv12:
-            h, w = self.frame_shape[:2]
-            return (torch.randint(0, 256, (self.batch, h, w), device=self.tdev).to(torch.uint8),
-                    torch.randint(0, 256, (self.batch, h // 2, w // 2, 2), device=self.tdev).to(torch.uint8))
+        if self._source:
+            src, _, _, depth, shift = self._source
+            return tuple((torch.randint(0, 1 << depth, sh, device=self.tdev) << shift).to(getattr(torch, src.dtype)) for sh in self._plane_shapes())
         frames = torch.randint(0, 256, (self.batch,) + self.frame_shape, device=self.tdev)
         return frames.to(self._frame_torch_dtype)
 
@@ -642,15 +625,17 @@ class LineEndPipeline(object):
     @property
     def _frame_bytes(self):
         """Bytes per frame element as step() reads it (NV12: 1.5 bytes per pixel over the three channels; P010: 3 bytes per pixel)."""
-        if self._nv12:
-            return 0.5
-        if self._p010:
-            return 1.0
-        if self._yuv16:                                              # 2 (1 + 2 / 2^(sx + sy)) / 3 = 1, 4 / 3, 2 -- exact
-            return fractions.Fraction(2 * (2 ** sum(self._yuv16[:2]) + 2), 3 * 2 ** sum(self._yuv16[:2]))
-        if self._yuv:                                                # (1 + 2 / 2^(sx + sy)) / 3 = 0.5, 2 / 3, 1.0 -- exact
-            return fractions.Fraction(2 ** sum(self._yuv) + 2, 3 * 2 ** sum(self._yuv))
+        if self._source:                                             # elem (1 + 2 / 2^(sx + sy)) / 3: 0.5, 2 / 3, 1 -- 1, 4 / 3, 2 for uint16 -- exact
+            src, sx, sy = self._source[:3]
+            f = fractions.Fraction(src.elem * (2 ** (sx + sy) + 2), 3 * 2 ** (sx + sy))
+            return float(f) if src.planes == 2 else f
         return {"uint8": 1, "uint16": 2}.get(self.frame_dtype, 4)
+
+    @property
+    def _source(self):
+        """(source description, sx, sy, depth, shift) of a mode "rgb" pipeline reading a YUV-family rgb_frame_format (_runtime.rgb_source:
+        the one place that resolves the name), None for every other pipeline."""
+        return _runtime.rgb_source(getattr(self, "rgb_frame_format", "interleaved"))
 
     @property
     def _nv12(self):
@@ -709,51 +694,38 @@ class LineEndPipeline(object):
                 "(top 10 % > NMS > value), cell-max / count / scan / write keypoint kernels"
                 + (", uint8 frames read in place (1 byte per frame element)" if getattr(self, "frame_dtype", "float32") == "uint8" else "")
                 + (", read in place from a strided view" if getattr(self, "rgb_frame_layout", "packed") == "strided" else "")
-                + (", NV12 read in place (Y + UV planes, 1.5 bytes per pixel, converted in registers)" if self._nv12 else "")
-                + ((", %s read in place (uint16 Y + UV planes, 3 bytes per pixel, converted in registers)" % self.rgb_frame_format.upper())
-                   if self._p010 else "")
-                + ((", %s read in place (a (y, u, v) triple of uint8 views, %.1f bytes per pixel, converted in registers)"
-                    % (self.rgb_frame_format.upper(), 3 * float(self._frame_bytes))) if self._yuv else "")
-                + ((", %s read in place (a (y, u, v) triple of uint16 views, %d bytes per pixel, converted in registers)"
-                    % (self.rgb_frame_format.upper(), int(3 * self._frame_bytes))) if self._yuv16 else ""))
+                + self._source_summary())
+
+    def _source_summary(self):
+        """launch_summary's words on a YUV-family source: its planes and the bytes step() reads per pixel."""
+        if not self._source:
+            return ""
+        src = self._source[0]
+        planes = ("uint16 Y + UV planes" if src.elem == 2 else "Y + UV planes") if src.planes == 2 else "a (y, u, v) triple of %s views" % src.dtype
+        return ", %s read in place (%s, %s bytes per pixel, converted in registers)" % (
+            self.rgb_frame_format.upper(), planes, ("%d" if src.elem == 2 else "%.1f") % (3 * self._frame_bytes))
+
+    def _plane_shapes(self):
+        """The shapes of the planes step() takes for a YUV-family source: (y, uv) of a pair, (y, u, v) of a triple."""
+        src, sx, sy = self._source[:3]
+        (h, w), b = self.frame_shape[:2], self.batch
+        return ((b, h, w), (b, h // 2, w // 2, 2)) if src.planes == 2 else ((b, h, w),) + 2 * ((b, h >> sy, w >> sx),)
 
     # -- launches --------------------------------------------------------------------------------------
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.tdev).cuda_stream)
 
-    def _nv12_arg(self, frames):
-        """The const silent_nv12_frames* of a pair (y, uv) of GPU planes of this pipeline's batch (refused: anything else)."""
-        args, n, dev = _runtime.nv12_frames_of(frames, self.frame_shape[:2], self.nv12_m, self.nv12_oy)
+    def _source_arg(self, frames):
+        """The const silent_<kind>_frames* of a pair (y, uv) / a triple (y, u, v) of GPU planes of this pipeline's batch (refused:
+        anything else)."""
+        src, sx, sy, depth, shift = self._source
+        coeffs = (self.nv12_m, self.nv12_oy) + ((self.nv12_oc,) if src.elem == 2 else ())
+        args, n, dev = _runtime.rgb_source_frames_of(src, frames, self.frame_shape[:2], coeffs, sx, sy, depth, shift, self.rgb_frame_format)
         if not dev or n != self.batch:
-            raise ValueError("frames must be a pair (y, uv) of uint8 GPU planes [%d, %d, %d] and [%d, %d, %d, 2]"
-                             % ((self.batch,) + self.frame_shape[:2] + (self.batch, self.frame_shape[0] // 2, self.frame_shape[1] // 2)))
-        return _lib.nv12_ptr(args)
-
-    def _yuv_arg(self, frames):
-        """The const silent_yuv_frames* of a triple (y, u, v) of uint8 GPU views of this pipeline's batch (refused: anything else)."""
-        args, n, dev = _runtime.yuv_frames_of(frames, self.frame_shape[:2], self.rgb_frame_format, self.nv12_m, self.nv12_oy)
-        if not dev or n != self.batch:
-            sx, sy = self._yuv
-            raise ValueError("frames must be a triple (y, u, v) of uint8 GPU planes [%d, %d, %d], [%d, %d, %d] and [%d, %d, %d]"
-                             % ((self.batch,) + self.frame_shape[:2] + 2 * (self.batch, self.frame_shape[0] >> sy, self.frame_shape[1] >> sx)))
-        return _lib.yuv_ptr(args)
-
-    def _yuv16_arg(self, frames):
-        """The const silent_yuv16_frames* of a triple (y, u, v) of uint16 GPU views of this pipeline's batch (refused: anything else)."""
-        args, n, dev = _runtime.yuv16_frames_of(frames, self.frame_shape[:2], self.rgb_frame_format, self.nv12_m, self.nv12_oy, self.nv12_oc)
-        if not dev or n != self.batch:
-            sx, sy = self._yuv16[:2]
-            raise ValueError("frames must be a triple (y, u, v) of uint16 GPU planes [%d, %d, %d], [%d, %d, %d] and [%d, %d, %d]"
-                             % ((self.batch,) + self.frame_shape[:2] + 2 * (self.batch, self.frame_shape[0] >> sy, self.frame_shape[1] >> sx)))
-        return _lib.yuv16_ptr(args)
-
-    def _p010_arg(self, frames):
-        """The const silent_p010_frames* of a pair (y, uv) of uint16 GPU planes of this pipeline's batch (refused: anything else)."""
-        args, n, dev = _runtime.p010_frames_of(frames, self.frame_shape[:2], self.nv12_m, self.nv12_oy, self.nv12_oc, self._p010)
-        if not dev or n != self.batch:
-            raise ValueError("frames must be a pair (y, uv) of uint16 GPU planes [%d, %d, %d] and [%d, %d, %d, 2]"
-                             % ((self.batch,) + self.frame_shape[:2] + (self.batch, self.frame_shape[0] // 2, self.frame_shape[1] // 2)))
-        return _lib.p010_ptr(args)
+            shapes = [str(list(sh)) for sh in self._plane_shapes()]
+            raise ValueError("frames must be a %s of %s GPU planes %s" % ("pair (y, uv)" if src.planes == 2 else "triple (y, u, v)", src.dtype,
+                                                                          ", ".join(shapes[:-1]) + " and " + shapes[-1]))
+        return getattr(_lib, src.kind + "_ptr")(args)
 
     def _check_frames(self, frames):
         if getattr(self, "rgb_frame_layout", "packed") == "strided":
@@ -780,21 +752,10 @@ class LineEndPipeline(object):
         return frame_ptr(frames.data_ptr())
 
     def run_pyramid(self, frames, stream=None):
-        if self._yuv16:                                              # (mode "rgb", rgb_frame_format one of YUV16_FORMATS)
-            self.ctx.check(self._lib.silent_pyramid_yuv16_dev(self.ctx.handle, self.plan.handle, self._yuv16_arg(frames), self.batch,
-                                                              C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
-            return
-        if self._yuv:                                                # (mode "rgb", rgb_frame_format "yuv420" / "yuv422" / "yuv444")
-            self.ctx.check(self._lib.silent_pyramid_yuv_dev(self.ctx.handle, self.plan.handle, self._yuv_arg(frames), self.batch,
-                                                            C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
-            return
-        if self._p010:                                               # (mode "rgb", rgb_frame_format "p010" / "p012" / "p016")
-            self.ctx.check(self._lib.silent_pyramid_p010_dev(self.ctx.handle, self.plan.handle, self._p010_arg(frames), self.batch,
-                                                             C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
-            return
-        if self._nv12:                                               # (mode "rgb", rgb_frame_format="nv12"; the planes: _nv12_arg)
-            self.ctx.check(self._lib.silent_pyramid_nv12_dev(self.ctx.handle, self.plan.handle, self._nv12_arg(frames), self.batch,
-                                                             C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
+        if self._source:                                             # (mode "rgb", a YUV-family rgb_frame_format; the planes: _source_arg)
+            entry = getattr(self._lib, "silent_pyramid_%s_dev" % self._source[0].kind)
+            self.ctx.check(entry(self.ctx.handle, self.plan.handle, self._source_arg(frames), self.batch, C.c_void_p(self.pyr.data_ptr()),
+                                 stream or self._stream()))
             return
         self._check_frames(frames)
         if getattr(self, "rgb_frame_layout", "packed") == "strided":   # (mode "rgb", rgb_frame_dtype="uint8")
@@ -985,7 +946,7 @@ class LineEndPipeline(object):
         no cast launch and no float32 frame buffer.  A frame_dtype="uint16" pipeline likewise takes uint16 host frames only, and a
         mode "rgb" pipeline with rgb_frame_dtype="uint8" uint8 host frames [batch, H, W, 3] only."""
         torch = self.torch
-        if self._nv12 or self._p010 or self._yuv or self._yuv16:
+        if self._source:
             return self._step_host_nv12(frames)
         if isinstance(frames, np.ndarray):
             src = torch.from_numpy(np.ascontiguousarray(frames))
@@ -1060,18 +1021,13 @@ class LineEndPipeline(object):
         uint8 NumPy arrays (any pitch: the staging copy packs).  Both planes go through pinned staging buffers and asynchronous copies
         on the copy stream into a ring of two device slots, which step() reads in place; no cast, no conversion launch."""
         torch = self.torch
-        h, w = self.frame_shape[:2]
-        shapes = ((self.batch, h, w), (self.batch, h // 2, w // 2, 2))
-        if self._yuv:     # (a (y, u, v) triple of uint8 arrays of any strides: three planes in the ring, packed by the staging copy)
-            shapes = ((self.batch, h, w),) + 2 * ((self.batch, h >> self._yuv[1], w >> self._yuv[0]),)
-        if self._yuv16:   # (the same triple as uint16 arrays)
-            shapes = ((self.batch, h, w),) + 2 * ((self.batch, h >> self._yuv16[1], w >> self._yuv16[0]),)
-        # (rgb_frame_format "p010" / "p012" / "p016" and the 16-bit triples: the same ring with uint16 planes)
-        np_dtype, t_dtype = (np.uint16, torch.uint16) if (self._p010 or self._yuv16) else (np.uint8, torch.uint8)
+        # (a triple: three planes of any strides in the ring, packed by the staging copy; uint16 sources: the same ring with uint16 planes)
+        src, shapes = self._source[0], self._plane_shapes()
+        np_dtype, t_dtype = np.dtype(src.dtype).type, getattr(torch, src.dtype)
         if not isinstance(frames, (tuple, list)) or len(frames) != len(shapes) or any(
                 not isinstance(p, np.ndarray) or p.dtype != np_dtype or tuple(p.shape) != sh for p, sh in zip(frames, shapes)):
             raise ValueError("step_host of an rgb_frame_format=%r pipeline takes a %s of %s arrays of shapes %s"
-                             % (self.rgb_frame_format, "triple" if (self._yuv or self._yuv16) else "pair", np.dtype(np_dtype).name,
+                             % (self.rgb_frame_format, "triple" if src.planes == 3 else "pair", src.dtype,
                                 " and ".join(str(sh) for sh in shapes)))
         cs = self._copy_stream_of_the_ingest()
         ring = self._ingest.setdefault("nv12", {"slots": [], "next": 0})
