@@ -1,5 +1,6 @@
-// silent_pyramid_plan: the host object behind silent_pyramid_plan_create (silent_pyramid_api.hip builds it; the gray pass of
-// silent_gray_api.hip reads its unit levels and stream tables).
+// silent_pyramid_plan: the host object behind silent_pyramid_plan_create.  silent_plan_build.h builds its tables on the host (tap and region
+// tables, the stream path's row programs and column records, the walk plans: no HIP call), silent_pyramid_api.hip validates, uploads them and
+// wires the pointers; the gray pass of silent_gray_api.hip reads its unit levels and stream tables.  tests/golden/plan_tables.txt pins them.
 #pragma once
 
 #include "silent_internal.h"
@@ -35,6 +36,15 @@ struct silent_pyramid_plan {
     void* walk_tables = nullptr;
     silent::Walk3Args walk{};                    // everything but the per-launch decomposition (strips / segments / block0)
     silent::BorderTab walk_border{};             // union plans: the inner levels' border outputs (pyramid_border_kernel); n = 0: none
+
+    silent_pyramid_plan() = default;
+    silent_pyramid_plan(const silent_pyramid_plan&) = delete;
+    silent_pyramid_plan& operator=(const silent_pyramid_plan&) = delete;
+    ~silent_pyramid_plan() {                     // the plan owns its four device allocations
+        DeviceGuard guard(ctx ? ctx->device : 0);
+        for (void* t : {tables, tables64, stream_tables, walk_tables})
+            if (t) (void)hipFree(t);
+    }
 };
 
 // ------------------------------------------------------------------------------------------ shared by the entry points
