@@ -627,7 +627,7 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// Geometry of that value summary (host: build_sum_tab in silent_peaks_api.hip)
+// Geometry of that value summary (host: build_sum_tab in silent_peaks_plan.h)
 struct SumTab {
     int th, gpt;                       // tile height of the chain launch, groups per tile = ceil(th / kSumRows)
     long long frame_entries;

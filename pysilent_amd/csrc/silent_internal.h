@@ -1,5 +1,5 @@
-// Host side shared by the translation units of libsilent_hip.so (one per kernel family: silent_core.hip, silent_conv_api.hip,
-// silent_gray_api.hip, silent_peaks_api.hip, silent_rgb_api.hip, silent_pyramid_api.hip): the context, the exception barrier
+// Host side shared by the eight translation units of libsilent_hip.so (one per kernel family: silent_core.hip, silent_conv_api.hip, silent_gray_api.hip,
+// silent_gray16_api.hip, silent_peaks_api.hip, silent_rgb_api.hip, silent_pyramid_api.hip, silent_displayer_api.hip): the context, the exception barrier
 // of the C ABI, workspace / staging helpers and the tile tables.  Nothing here is exported (-fvisibility=hidden).
 #pragma once
 
@@ -47,7 +47,7 @@ struct silent_ctx {
     // kernel-selection knobs (silent_set_tuning; initial values from SILENT_GRAY_OPTS / SILENT_RGB_OPTS /
     // SILENT_PYRAMID_OPTS read ONCE, in silent_create): tests and A/B scripts pick alternative kernels with them
     unsigned tune[SILENT_TUNE_COUNT] = {0, 0, 0};
-    // the last silent_rgb_keypoints_dev call's sparse tail (silent_sparse_tail_stats): where its flags / counters live in ws
+    // the last silent_rgb_keypoints_dev / silent_gray_keypoints*_dev call's sparse tail (silent_sparse_tail_stats): where its flags / counters live in ws
     bool sparse_ran = false;
     hipStream_t sparse_stream = nullptr;
     size_t sparse_flags_off = 0, sparse_candn_off = 0;

@@ -3,13 +3,27 @@
 // silent_gray_keypoints = the gray pass with its keypoint epilogue (silent_gray_api.hip) + the same tail on K channels.
 #include "silent_internal.h"
 #include "silent_peaks.h"
+#include "silent_peaks_plan.h"
 #include "silent_plan.h"
 
 using namespace silent;
 
+// a refusal of the planning (silent_peaks_plan.h) under the entry point's name
+static int refuse(silent_ctx* ctx, const char* who, const Refusal& r) {
+    return r.status == SILENT_OK ? SILENT_OK : fail(ctx, r.status, std::string(who) + r.tail);
+}
+
 // channel counts the fused selection kernels are instantiated for (1, RGB's 3, the gray line-end banks' 4 and 8; a gray bank of
 // 3 shares RGB's instantiation)
 static bool select_channels_ok(int c) { return c == 1 || c == 3 || c == 4 || c == 8; }
+// f(std::integral_constant<int, C>) for the instantiation that serves `channels` (anything but 3, 4, 8: 1)
+template <class F>
+static void with_channels(int channels, F&& f) {
+    if (channels == 3) f(std::integral_constant<int, 3>{});
+    else if (channels == 4) f(std::integral_constant<int, 4>{});
+    else if (channels == 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 1>{});
+}
 
 // ------------------------------------------------------------------------------------------ pointwise / nms
 
@@ -31,11 +45,9 @@ SILENT_EXPORT int silent_pad_inwards_dev(silent_ctx* ctx, const float* in, const
     return on_exception(ctx, "silent_pad_inwards_dev");
 }
 
-SILENT_EXPORT int silent_value_from_color_dev(silent_ctx* ctx, const float* in, const silent_extent* levels,
-                                              int n_levels, int n_frames, int channels, float* out,
-                                              silent_stream stream) try {
-    NEED_CTX(ctx);
-    const char* who = "silent_value_from_color";
+// value_from_color / bw_from_color: one body over the two kernels
+static int from_color_dev(silent_ctx* ctx, const char* who, void (*kernel)(const float*, float*, long long, int), const float* in,
+                          const silent_extent* levels, int n_levels, int n_frames, int channels, float* out, silent_stream stream) {
     if (!in || !out) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (channels < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": channels must be >= 1");
     LevelTab tab;
@@ -43,9 +55,15 @@ SILENT_EXPORT int silent_value_from_color_dev(silent_ctx* ctx, const float* in, 
     TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, 0, 0, &tab, &blocks));
     const long long npx = tab.frame_px * n_frames;
     const long long grid = std::min<long long>((npx + 255) / 256, 256 * 32);
-    hipLaunchKernelGGL(value_from_color_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, in, out, npx,
-                       channels);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, in, out, npx, channels);
     return check_launch(ctx, who);
+}
+
+SILENT_EXPORT int silent_value_from_color_dev(silent_ctx* ctx, const float* in, const silent_extent* levels,
+                                              int n_levels, int n_frames, int channels, float* out,
+                                              silent_stream stream) try {
+    NEED_CTX(ctx);
+    return from_color_dev(ctx, "silent_value_from_color", value_from_color_kernel, in, levels, n_levels, n_frames, channels, out, stream);
 } catch (...) {
     return on_exception(ctx, "silent_value_from_color_dev");
 }
@@ -54,17 +72,7 @@ SILENT_EXPORT int silent_bw_from_color_dev(silent_ctx* ctx, const float* in, con
                                               int n_levels, int n_frames, int channels, float* out,
                                               silent_stream stream) try {
     NEED_CTX(ctx);
-    const char* who = "silent_bw_from_color";
-    if (!in || !out) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
-    if (channels < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": channels must be >= 1");
-    LevelTab tab;
-    long long blocks;
-    TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, 0, 0, &tab, &blocks));
-    const long long npx = tab.frame_px * n_frames;
-    const long long grid = std::min<long long>((npx + 255) / 256, 256 * 32);
-    hipLaunchKernelGGL(bw_from_color_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, in, out, npx,
-                       channels);
-    return check_launch(ctx, who);
+    return from_color_dev(ctx, "silent_bw_from_color", bw_from_color_kernel, in, levels, n_levels, n_frames, channels, out, stream);
 } catch (...) {
     return on_exception(ctx, "silent_bw_from_color_dev");
 }
@@ -149,14 +157,10 @@ SILENT_EXPORT int silent_select_peaks_dev(silent_ctx* ctx, const float* color, c
     const float a = (float)(1.0 - top_percent), b = (float)top_percent;
     RegionTab no_regions;
     std::memset(&no_regions, 0, sizeof(no_regions));
-#define SELECT_LAUNCH(C_)                                                                                                     \
-    hipLaunchKernelGGL((select_peaks_kernel<C_, false>), dim3((unsigned)blocks), dim3(256), 0, s, color, value, top_out, peaks_out, \
-                       peak_value_out, tab, a, b, mm, no_regions, nullptr, nullptr, (unsigned)blocks)
-    if (channels == 3) SELECT_LAUNCH(3);
-    else if (channels == 4) SELECT_LAUNCH(4);
-    else if (channels == 8) SELECT_LAUNCH(8);
-    else SELECT_LAUNCH(1);
-#undef SELECT_LAUNCH
+    with_channels(channels, [&](auto C) {
+        hipLaunchKernelGGL((select_peaks_kernel<decltype(C)::value, false>), dim3((unsigned)blocks), dim3(256), 0, s, color, value, top_out,
+                           peaks_out, peak_value_out, tab, a, b, mm, no_regions, nullptr, nullptr, (unsigned)blocks);
+    });
     return check_launch(ctx, who);
 } catch (...) {
     return on_exception(ctx, "silent_select_peaks_dev");
@@ -164,74 +168,7 @@ SILENT_EXPORT int silent_select_peaks_dev(silent_ctx* ctx, const float* color, c
 
 // ------------------------------------------------------------------------------------------ keypoint indices
 
-// TF1 max_pool SAME geometry with window == full extent
-static int region_axis(int size, int stride, int* n_win, int* nseg, int* cut, int* w_lo, int* w_hi, float* scale) {
-    if (stride < 1) return -1;
-    const int out = (size + stride - 1) / stride;
-    *n_win = out;
-    *scale = (float)out / (float)size;
-    if (out > kMaxWin) return -2;
-    const int pad_before = ((out - 1) * stride) / 2;
-    int lo[kMaxWin], hi[kMaxWin];
-    std::vector<int> cuts = {0, size};
-    for (int j = 0; j < out; ++j) {
-        const int a = j * stride - pad_before, b = a + size;
-        lo[j] = a < 0 ? 0 : a;
-        hi[j] = b > size ? size : b;
-        cuts.push_back(lo[j]);
-        cuts.push_back(hi[j]);
-    }
-    std::sort(cuts.begin(), cuts.end());
-    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
-    const int ns = (int)cuts.size() - 1;
-    if (ns > kMaxSeg) return -2;
-    for (int i = 0; i <= ns; ++i) cut[i] = cuts[i];
-    for (int j = 0; j < out; ++j) {
-        int a = 0, b = 0;
-        for (int i = 0; i <= ns; ++i) {
-            if (cuts[i] == lo[j]) a = i;
-            if (cuts[i] == hi[j]) b = i;
-        }
-        w_lo[j] = a;
-        w_hi[j] = b;
-    }
-    *n_win = out;
-    *nseg = ns;
-    *scale = (float)out / (float)size;
-    return 0;
-}
-
-// Region tables of max_value_indices_region (TF1 max_pool geometry per level).  *general = true when some level has more
-// than kMaxWin windows per axis: the cell tables (kernarg-resident) do not apply then and the separable prefix / suffix
-// path runs (region_rowmax_kernel / region_colmax_kernel) -- any region_shape the reference accepts
-// (slam_recognition/util/selection/top_value_points.py:32-45).
-static int build_region_tab(silent_ctx* ctx, const char* who, const silent_extent* levels, int n_levels,
-                            const silent_extent* regions, RegionTab* rt, bool* general) {
-    std::memset(rt, 0, sizeof(*rt));
-    *general = false;
-    long long m1 = 0, pooled = 0;
-    for (int l = 0; l < n_levels; ++l) {
-        RegionLevel& r = rt->lv[l];
-        if (regions[l].h < 1 || regions[l].w < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": region extents must be >= 1");
-        const int rc0 = region_axis(levels[l].h, regions[l].h, &r.oh, &r.nrs, r.rcut, r.wy_lo, r.wy_hi, &r.yscale);
-        const int rc1 = region_axis(levels[l].w, regions[l].w, &r.ow, &r.ncs, r.ccut, r.wx_lo, r.wx_hi, &r.xscale);
-        if (rc0 == -2 || rc1 == -2) *general = true;
-        r.ry = regions[l].h;
-        r.rx = regions[l].w;
-        r.pad_y = ((r.oh - 1) * r.ry) / 2;
-        r.pad_x = ((r.ow - 1) * r.rx) / 2;
-        r.m1_off = m1;
-        r.pooled_off = pooled;
-        m1 += (long long)levels[l].h * r.ow;
-        pooled += (long long)r.oh * r.ow;
-    }
-    rt->m1_per_frame = m1;
-    rt->pooled_per_frame = pooled;
-    return SILENT_OK;
-}
-
-// workspace of the keypoint passes, after `reserve` bytes the caller keeps for itself:
-// cells | chunk_counts | hit_masks | cand_n | nan flags | offsets | m1 | pooled | summary | candidates | modes | peak-value map
+// workspace of the keypoint passes, after `reserve` bytes the caller keeps for itself (the order: keypoint_layout, silent_peaks_plan.h)
 struct KeypointWs {
     unsigned* cells;
     int* chunk_counts;
@@ -250,41 +187,6 @@ struct KeypointWs {
     void* zero_from = nullptr;       // chunk_counts | hit_masks | cand_n | nan flags: one memset before a sparse tail's chain launch
     size_t zero_bytes = 0;
 };
-
-static int keypoint_workspace(silent_ctx* ctx, hipStream_t stream, int n_levels, int n_frames, long long blocks, size_t reserve,
-                              const RegionTab& rt, bool general, KeypointWs* w, long long sum_entries = 0, long long pv_px = 0) {
-    w->n_cells = (size_t)n_frames * n_levels * kCells;
-    const size_t off_cells = align_up(reserve);
-    const size_t off_counts = off_cells + align_up(w->n_cells * sizeof(unsigned));
-    const size_t off_masks = off_counts + align_up((size_t)blocks * sizeof(int));
-    const size_t off_candn = off_masks + align_up((size_t)blocks * 4 * kKpPer * sizeof(unsigned long long));
-    const size_t off_nanf = off_candn + align_up((size_t)n_frames * sizeof(int));
-    const size_t off_offsets = off_nanf + align_up((size_t)n_frames * n_levels * sizeof(int));
-    const size_t off_m1 = off_offsets + align_up((size_t)blocks * sizeof(long long));
-    const size_t off_pooled = off_m1 + (general ? align_up((size_t)n_frames * rt.m1_per_frame * sizeof(float)) : 0);
-    const size_t off_sum = off_pooled + (general ? align_up((size_t)n_frames * rt.pooled_per_frame * sizeof(float)) : 0);
-    const size_t off_cand = off_sum + align_up((size_t)sum_entries * n_frames * sizeof(float));
-    const size_t off_flags = off_cand + (sum_entries ? align_up((size_t)n_frames * kCandCap * sizeof(Candidate)) : 0);
-    const size_t off_pv = off_flags + align_up((size_t)n_frames * n_levels * sizeof(int));
-    const size_t total = off_pv + align_up((size_t)pv_px * n_frames * sizeof(float));
-    TRY(workspace(ctx, (hipStream_t)stream, total));
-    char* base = (char*)ctx->ws.p;
-    w->cells = (unsigned*)(base + off_cells);
-    w->chunk_counts = (int*)(base + off_counts);
-    w->chunk_offsets = (long long*)(base + off_offsets);
-    w->m1 = (float*)(base + off_m1);
-    w->pooled = (float*)(base + off_pooled);
-    w->hit_masks = (unsigned long long*)(base + off_masks);
-    w->cand_n = (int*)(base + off_candn);
-    w->nan_flags = (int*)(base + off_nanf);
-    w->sum = sum_entries ? (float*)(base + off_sum) : nullptr;
-    w->cand = sum_entries ? (Candidate*)(base + off_cand) : nullptr;
-    w->dense_flags = (int*)(base + off_flags);
-    w->pv = pv_px ? (float*)(base + off_pv) : nullptr;
-    w->zero_from = base + off_counts;
-    w->zero_bytes = off_offsets - off_counts;
-    return SILENT_OK;
-}
 
 // general path: window maxima of every level into w.pooled (two launches)
 static int region_window_maxima(silent_ctx* ctx, const char* who, const float* value, const silent_extent* levels, int n_levels,
@@ -334,12 +236,41 @@ struct RegionPlan {
     KeypointWs w;
 };
 
+static int keypoint_workspace(silent_ctx* ctx, hipStream_t stream, int n_levels, int n_frames, size_t reserve, RegionPlan* rp,
+                              long long sum_entries = 0, long long pv_px = 0) {
+    const KeypointLayout k = keypoint_layout(n_levels, n_frames, rp->blocks, reserve, rp->rt, rp->general, sum_entries, pv_px);
+    TRY(workspace(ctx, stream, k.total));
+    char* base = (char*)ctx->ws.p;
+    KeypointWs* w = &rp->w;
+    w->n_cells = k.n_cells;
+    w->cells = (unsigned*)(base + k.cells);
+    w->chunk_counts = (int*)(base + k.chunk_counts);
+    w->hit_masks = (unsigned long long*)(base + k.hit_masks);
+    w->cand_n = (int*)(base + k.cand_n);
+    w->nan_flags = (int*)(base + k.nan_flags);
+    w->chunk_offsets = (long long*)(base + k.chunk_offsets);
+    w->m1 = (float*)(base + k.m1);
+    w->pooled = (float*)(base + k.pooled);
+    w->sum = sum_entries ? (float*)(base + k.sum) : nullptr;
+    w->cand = sum_entries ? (Candidate*)(base + k.cand) : nullptr;
+    w->dense_flags = (int*)(base + k.dense_flags);
+    w->pv = pv_px ? (float*)(base + k.pv) : nullptr;
+    w->zero_from = base + k.zero_from;
+    w->zero_bytes = k.zero_bytes;
+    return SILENT_OK;
+}
+
+static int region_tables(silent_ctx* ctx, const char* who, const silent_extent* levels, int n_levels, int n_frames,
+                         const silent_extent* regions, RegionPlan* rp) {
+    TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kKpChunk, 0, &rp->tab, &rp->blocks));     // count / write chunks
+    TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kRedChunk, 0, &rp->ctab, &rp->cblocks));  // cell maxima, per-level extrema
+    return refuse(ctx, who, build_region_tab(levels, n_levels, regions, &rp->rt, &rp->general));
+}
+
 static int region_prepare(silent_ctx* ctx, const char* who, const silent_extent* levels, int n_levels, int n_frames,
                           const silent_extent* regions, size_t reserve, hipStream_t s, RegionPlan* rp) {
-    TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kKpChunk, 0, &rp->tab, &rp->blocks));     // count / write chunks
-    TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kRedChunk, 0, &rp->ctab, &rp->cblocks));  // cell maxima
-    TRY(build_region_tab(ctx, who, levels, n_levels, regions, &rp->rt, &rp->general));
-    return keypoint_workspace(ctx, s, n_levels, n_frames, rp->blocks, reserve, rp->rt, rp->general, &rp->w);
+    TRY(region_tables(ctx, who, levels, n_levels, n_frames, regions, rp));
+    return keypoint_workspace(ctx, s, n_levels, n_frames, reserve, rp);
 }
 
 static int region_run(silent_ctx* ctx, const char* who, const float* value, const silent_extent* levels, int n_levels, int n_frames,
@@ -373,48 +304,23 @@ SILENT_EXPORT int silent_max_value_indices_region_dev(silent_ctx* ctx, const flo
 // SURVEY 8d config 3 as one call: top-percent -> NMS -> value -> per-region keypoint indices of the peak value.
 // = silent_select_peaks + silent_max_value_indices_region, with the cell maxima folded into the selection pass.
 // Two halves so that silent_rgb_keypoints can run the chain kernel in between (it fills the per-level extrema itself).
-struct SelectPlan {
-    LevelTab rtab, stab, tab;
-    long long rblocks, sblocks, blocks;
-    RegionTab rt;
-    bool general;
-    KeypointWs w;
+struct SelectPlan : RegionPlan {   // (ctab also serves the reduction pass of the per-level extrema)
+    LevelTab stab;  // the selection pass's tiles
+    long long sblocks;
     unsigned* mm;   // [n_frames][n_levels][2] ordered-uint extrema, at the head of the context workspace
     int nmm;
     SumTab st;      // sparse tail: geometry of the chain kernel's value summary (frame_entries = 0: none)
 };
 
-// Geometry of the value summary a chain launch with tile height th leaves (silent_rgb2.h): per level
-// [tiles_y * gpt][ceil(w / 2)] entries, gpt = ceil(th / kSumRows).
-static void build_sum_tab(const silent_extent* levels, int n_levels, int th, SumTab* st) {
-    std::memset(st, 0, sizeof(*st));
-    st->th = th;
-    st->gpt = (th + kSumRows - 1) / kSumRows;
-    long long e = 0;
-    for (int l = 0; l < n_levels; ++l) {
-        st->off[l] = e;
-        e += (long long)((levels[l].h + th - 1) / th) * st->gpt * ((levels[l].w + 1) / 2);
-    }
-    for (int l = n_levels; l <= kMaxLevels; ++l) st->off[l] = e;
-    st->frame_entries = e;
-}
-
 // tables, workspace, and the init kernels.  sparse_th > 0: also lay out the sparse tail for a chain launch with that tile
 // height; pv_ws: keep room for a peak-value map in the workspace (the caller has none)
 static int select_prepare(silent_ctx* ctx, const char* who, const silent_extent* levels, int n_levels, int n_frames,
                           const silent_extent* regions, hipStream_t s, SelectPlan* sp, int sparse_th = 0, bool pv_ws = false) {
-    TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kRedChunk, 0, &sp->rtab, &sp->rblocks));
     TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kSelTW, kSelTH, &sp->stab, &sp->sblocks));
-    TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kKpChunk, 0, &sp->tab, &sp->blocks));
-    TRY(build_region_tab(ctx, who, levels, n_levels, regions, &sp->rt, &sp->general));
+    TRY(region_tables(ctx, who, levels, n_levels, n_frames, regions, sp));
     sp->nmm = n_frames * n_levels;
-    std::memset(&sp->st, 0, sizeof(sp->st));
-    if (sparse_th > 0 && !sp->general && n_frames <= 65535) {
-        build_sum_tab(levels, n_levels, sparse_th, &sp->st);
-        if (sp->st.frame_entries >= (1ll << 31)) std::memset(&sp->st, 0, sizeof(sp->st));   // (sparse_select_kernel indexes a frame with int)
-    }
-    TRY(keypoint_workspace(ctx, s, n_levels, n_frames, sp->blocks, sizeof(unsigned) * 2 * (size_t)sp->nmm, sp->rt, sp->general, &sp->w,
-                           sp->st.frame_entries, pv_ws ? sp->tab.frame_px : 0));
+    build_sum_tab(levels, n_levels, n_frames, sparse_th, sp->general, &sp->st);
+    TRY(keypoint_workspace(ctx, s, n_levels, n_frames, sizeof(unsigned) * 2 * (size_t)sp->nmm, sp, sp->st.frame_entries, pv_ws ? sp->tab.frame_px : 0));
     sp->mm = (unsigned*)ctx->ws.p;
     const long long n_init = std::max<long long>(2ll * sp->nmm, (long long)sp->w.n_cells);
     const long long n_zero16 = sp->st.frame_entries > 0 ? (long long)(sp->w.zero_bytes / 16) : 0;   // (every piece of the workspace is align_up'ed)
@@ -445,23 +351,6 @@ static void select_launches(const SelectPlan& sp, bool sparse_pass, const float*
     }
 }
 
-static void select_launches_for(int channels, int pad, const SelectPlan& sp, bool sparse_pass, const float* color, const float* value,
-                                float* pv_map, float a, float b, const int* dense_flags, int n_frames, hipStream_t s) {
-#define SEL(C_, P_) select_launches<C_, P_>(sp, sparse_pass, color, value, pv_map, a, b, dense_flags, n_frames, pad, s)
-    if (pad > 0) {
-        if (channels == 3) SEL(3, true);
-        else if (channels == 4) SEL(4, true);
-        else if (channels == 8) SEL(8, true);
-        else SEL(1, true);
-    } else {
-        if (channels == 3) SEL(3, false);
-        else if (channels == 4) SEL(4, false);
-        else if (channels == 8) SEL(8, false);
-        else SEL(1, false);
-    }
-#undef SEL
-}
-
 // have_mm: the extrema are already in sp.mm (no reduction pass).  sparse: the chain kernel left its value summary in sp.w.sum
 // (geometry sp.st) -- the sparse tail runs and the dense kernels only where it could not settle a (frame, level).  pad > 0: `color`
 // is the unpadded map of silent_gray_keypoints (select_launches); the extrema must then be present (have_mm).
@@ -473,14 +362,20 @@ static int select_run(silent_ctx* ctx, const char* who, const float* color, cons
     const RegionTab& rt = sp.rt;
     const KeypointWs& w = sp.w;
     if (!have_mm)
-        hipLaunchKernelGGL(level_maxmin_kernel, dim3((unsigned)sp.rblocks), dim3(256), 0, s, value, value ? nullptr : color,
-                           channels, sp.rtab, mm);
+        hipLaunchKernelGGL(level_maxmin_kernel, dim3((unsigned)sp.cblocks), dim3(256), 0, s, value, value ? nullptr : color,
+                           channels, sp.ctab, mm);
     const float a = (float)(1.0 - top_percent), b = (float)top_percent;
     const int* dense_flags = nullptr;
     float* const caller_map = peak_value_out;
+    auto launches = [&](bool sparse_pass, float* pv_map) {
+        with_channels(channels, [&](auto C) {
+            if (pad > 0) select_launches<decltype(C)::value, true>(sp, sparse_pass, color, value, pv_map, a, b, dense_flags, n_frames, pad, s);
+            else select_launches<decltype(C)::value, false>(sp, sparse_pass, color, value, pv_map, a, b, dense_flags, n_frames, pad, s);
+        });
+    };
     if (sparse) {
         // (sparse implies: cell tables, extrema present; select_prepare zeroed the counters)
-        select_launches_for(channels, pad, sp, true, color, value, nullptr, a, b, nullptr, n_frames, s);
+        launches(true, nullptr);
         hipLaunchKernelGGL(sparse_modes_kernel, dim3((unsigned)n_frames), dim3(256), 0, s, sp.tab, rt, w.cells, w.cand_n, w.nan_flags,
                            w.dense_flags, peak_value_out ? 1 : 0);
         if (peak_value_out)   // the map the caller takes: zeros wherever the dense pass will not write
@@ -488,7 +383,7 @@ static int select_run(silent_ctx* ctx, const char* who, const float* color, cons
         dense_flags = w.dense_flags;
     }
     if (!peak_value_out) peak_value_out = w.pv;
-    select_launches_for(channels, pad, sp, false, color, value, peak_value_out, a, b, dense_flags, n_frames, s);
+    launches(false, peak_value_out);
     if (sp.general) TRY(region_window_maxima(ctx, who, peak_value_out, levels, n_levels, n_frames, rt, w, s));
     keypoint_passes(peak_value_out, sp.tab, sp.blocks, rt, w, sp.general, n_frames, idx, cap_per_frame, counts, s, dense_flags,
                     dense_flags ? caller_map : nullptr);
@@ -514,28 +409,6 @@ SILENT_EXPORT int silent_select_keypoints_dev(silent_ctx* ctx, const float* colo
 
 // ------------------------------------------------------------------------------------------ centroids
 
-static int build_cell_tab(silent_ctx* ctx, const char* who, const silent_extent* levels, int n_levels, int rh, int rw,
-                          CellTab* ct) {
-    if (rh < 1 || rw < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": region extents must be >= 1");
-    std::memset(ct, 0, sizeof(*ct));
-    ct->rh = rh;
-    ct->rw = rw;
-    long long cells = 0;
-    for (int l = 0; l < n_levels; ++l) {
-        const int h = levels[l].h, w = levels[l].w;
-        ct->oh[l] = (h + rh - 1) / rh;
-        ct->ow[l] = (w + rw - 1) / rw;
-        ct->y_first[l] = -(std::max((ct->oh[l] - 1) * rh + rh - h, 0) / 2);
-        ct->x_first[l] = -(std::max((ct->ow[l] - 1) * rw + rw - w, 0) / 2);
-        ct->yscale[l] = (float)ct->oh[l] / (float)h;
-        ct->xscale[l] = (float)ct->ow[l] / (float)w;
-        ct->cell_off[l] = cells;
-        cells += (long long)ct->oh[l] * ct->ow[l];
-    }
-    ct->frame_cells = cells;
-    return SILENT_OK;
-}
-
 SILENT_EXPORT int silent_centroids_dev(silent_ctx* ctx, const float* value, const silent_extent* levels, int n_levels,
                                        int n_frames, int region_h, int region_w, float* dist_out, float* total_out,
                                        silent_stream stream) try {
@@ -546,7 +419,7 @@ SILENT_EXPORT int silent_centroids_dev(silent_ctx* ctx, const float* value, cons
     long long blocks;
     TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, 0, 0, &tab, &blocks));
     CellTab ct;
-    TRY(build_cell_tab(ctx, who, levels, n_levels, region_h, region_w, &ct));
+    TRY(refuse(ctx, who, build_cell_tab(levels, n_levels, region_h, region_w, &ct)));
     const long long cells = ct.frame_cells * n_frames;
     if ((cells + 255) / 256 > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many cells");
     TRY(workspace(ctx, (hipStream_t)stream, (size_t)cells * 2 * sizeof(float)));
@@ -562,22 +435,6 @@ SILENT_EXPORT int silent_centroids_dev(silent_ctx* ctx, const float* value, cons
 
 // ------------------------------------------------------------------------------------------ boosting state
 
-static int check_boost_params(silent_ctx* ctx, const silent_boosting_params* p, BoostP* bp) {
-    if (!p) return fail(ctx, SILENT_E_INVALID, "silent_boosting_step: NULL params");
-    if (p->recovery_mode < 1 || p->recovery_mode > 3)
-        return fail(ctx, SILENT_E_INVALID, "silent_boosting_step: You must choose a type of recovery");
-    bp->lo = -p->exhaustion_max;
-    bp->hi = p->excitation_max;
-    bp->recovery_mode = (int)p->recovery_mode;
-    bp->recovery_amount = p->recovery_amount;
-    bp->recovery_percentage = p->recovery_percentage;
-    bp->visualize = p->visualize ? 1 : 0;
-    const double span = (double)p->exhaustion_max + (double)p->excitation_max;
-    bp->normer = (float)(255.0 / span);
-    bp->centerer = (float)(((double)p->excitation_max / span) * 255.0);
-    return SILENT_OK;
-}
-
 SILENT_EXPORT int silent_boosting_step_dev(silent_ctx* ctx, const float* input, const silent_extent* levels,
                                            int n_levels, int n_frames, const silent_boosting_params* params,
                                            float* energy, float* fired_out, float* energy_out, silent_stream stream) try {
@@ -585,7 +442,7 @@ SILENT_EXPORT int silent_boosting_step_dev(silent_ctx* ctx, const float* input, 
     const char* who = "silent_boosting_step";
     if (!input || !energy || !fired_out) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     BoostP bp;
-    TRY(check_boost_params(ctx, params, &bp));
+    TRY(refuse(ctx, "silent_boosting_step", boost_params(params, &bp)));
     LevelTab tab;
     long long blocks;
     TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, 0, 0, &tab, &blocks));
@@ -619,14 +476,27 @@ SILENT_EXPORT int silent_affine_clip_dev(silent_ctx* ctx, const float* in, size_
     return on_exception(ctx, "silent_affine_clip_dev");
 }
 
-static size_t dtype_size(int dt) {
+// f(TypeTag<T>) for the element type of a SILENT_DT_*; false: no such dtype (f was not called)
+template <class T>
+struct TypeTag { using type = T; };
+template <class F>
+static bool with_dtype(int dt, F&& f) {
     switch (dt) {
-        case SILENT_DT_U8: return 1;
-        case SILENT_DT_U16: case SILENT_DT_I16: return 2;
-        case SILENT_DT_F32: case SILENT_DT_I32: return 4;
-        case SILENT_DT_F64: case SILENT_DT_I64: return 8;
-        default: return 0;
+        case SILENT_DT_U8: f(TypeTag<unsigned char>{}); return true;
+        case SILENT_DT_F32: f(TypeTag<float>{}); return true;
+        case SILENT_DT_F64: f(TypeTag<double>{}); return true;
+        case SILENT_DT_I32: f(TypeTag<int>{}); return true;
+        case SILENT_DT_U16: f(TypeTag<unsigned short>{}); return true;
+        case SILENT_DT_I16: f(TypeTag<short>{}); return true;
+        case SILENT_DT_I64: f(TypeTag<long long>{}); return true;
+        default: return false;
     }
+}
+
+static size_t dtype_size(int dt) {
+    size_t bytes = 0;   // (0: no such dtype)
+    (void)with_dtype(dt, [&](auto tag) { bytes = sizeof(typename decltype(tag)::type); });
+    return bytes;
 }
 
 SILENT_EXPORT int silent_cast_interleave_dev(silent_ctx* ctx, const void* in, int in_dtype, size_t n_pixels, int in_stride,
@@ -643,18 +513,10 @@ SILENT_EXPORT int silent_cast_interleave_dev(silent_ctx* ctx, const void* in, in
     const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 256ll * 64);
     hipStream_t s = (hipStream_t)stream;
     const long long n = (long long)n_pixels;
-#define CAST_CASE(DT, T) \
-    case DT: hipLaunchKernelGGL(cast_interleave_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)in, out, n, in_stride, in_offset, count, out_stride, out_offset); break
-    switch (in_dtype) {
-        CAST_CASE(SILENT_DT_U8, unsigned char);
-        CAST_CASE(SILENT_DT_F32, float);
-        CAST_CASE(SILENT_DT_F64, double);
-        CAST_CASE(SILENT_DT_I32, int);
-        CAST_CASE(SILENT_DT_U16, unsigned short);
-        CAST_CASE(SILENT_DT_I16, short);
-        CAST_CASE(SILENT_DT_I64, long long);
-    }
-#undef CAST_CASE
+    (void)with_dtype(in_dtype, [&](auto tag) {   // (an unknown dtype was refused above)
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(cast_interleave_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)in, out, n, in_stride, in_offset, count, out_stride, out_offset);
+    });
     return check_launch(ctx, who);
 } catch (...) {
     return on_exception(ctx, "silent_cast_interleave_dev");
@@ -666,19 +528,11 @@ int cast_rect_launch(silent_ctx* ctx, const void* in, int in_dtype, int W, int C
     if (!in || !out || h < 1 || w < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": bad cast rectangle");
     const long long total = (long long)h * w * C;
     const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 256ll * 64);
-#define CAST_CASE(DT, T) \
-    case DT: hipLaunchKernelGGL(cast_rect_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)in, out, W, C, y0, x0, h, w); break
-    switch (in_dtype) {
-        CAST_CASE(SILENT_DT_U8, unsigned char);
-        CAST_CASE(SILENT_DT_F32, float);
-        CAST_CASE(SILENT_DT_F64, double);
-        CAST_CASE(SILENT_DT_I32, int);
-        CAST_CASE(SILENT_DT_U16, unsigned short);
-        CAST_CASE(SILENT_DT_I16, short);
-        CAST_CASE(SILENT_DT_I64, long long);
-        default: return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": frame dtype");
-    }
-#undef CAST_CASE
+    const bool known = with_dtype(in_dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(cast_rect_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)in, out, W, C, y0, x0, h, w);
+    });
+    if (!known) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": frame dtype");
     return check_launch(ctx, who);
 }
 
@@ -721,11 +575,11 @@ int displayer_tail(silent_ctx* ctx, int L, int h, int w, int rh, int rw, int h2,
     const char* who = "silent_displayer_step";
     DispTail t;
     std::memset(&t, 0, sizeof(t));
-    TRY(check_boost_params(ctx, boost, &t.bp));
+    TRY(refuse(ctx, "silent_boosting_step", boost_params(boost, &t.bp)));
     const silent_extent full = {h, w}, half = {h2, w2};
     CellTab c1, c2;
-    TRY(build_cell_tab(ctx, who, &full, 1, rh, rw, &c1));
-    TRY(build_cell_tab(ctx, who, &half, 1, rh, rw, &c2));
+    TRY(refuse(ctx, who, build_cell_tab(&full, 1, rh, rw, &c1)));
+    TRY(refuse(ctx, who, build_cell_tab(&half, 1, rh, rw, &c2)));
     t.L = L; t.h = h; t.w = w; t.h2 = h2; t.w2 = w2; t.rh = rh; t.rw = rw;
     t.ch = c1.oh[0]; t.cw = c1.ow[0]; t.ch2 = c2.oh[0]; t.cw2 = c2.ow[0];
     t.y_first = c1.y_first[0]; t.x_first = c1.x_first[0]; t.y_first2 = c2.y_first[0]; t.x_first2 = c2.x_first[0];
@@ -752,6 +606,16 @@ int displayer_tail(silent_ctx* ctx, int L, int h, int w, int rh, int rw, int h2,
 }
 
 // ------------------------------------------------------------------------------------------ RGB chain + keypoints
+
+// what silent_sparse_tail_stats reads back of the call that just laid its tail out: whether it ran sparse, where its flags / counters live
+static void publish_sparse_tail(silent_ctx* ctx, const SelectPlan& sp, hipStream_t s, int n_frames, int n_levels, bool sparse) {
+    ctx->sparse_ran = sparse;
+    ctx->sparse_stream = s;
+    ctx->sparse_flags_off = (size_t)((char*)sp.w.dense_flags - (char*)ctx->ws.p);
+    ctx->sparse_candn_off = (size_t)((char*)sp.w.cand_n - (char*)ctx->ws.p);
+    ctx->sparse_pairs = n_frames * n_levels;
+    ctx->sparse_frames = n_frames;
+}
 
 // Config 3 from the pyramid on in one call: silent_rgb_line_end + silent_select_keypoints on its line_end / value maps.
 // When the chain runs as the pair kernel's two-group instantiation, that kernel also accumulates the per-level extrema of the
@@ -794,12 +658,7 @@ SILENT_EXPORT int silent_rgb_keypoints_dev(silent_ctx* ctx, const float* pyr, co
     TRY(rgb_chain_launch(ctx, who, pyr, levels, n_levels, n_frames, p, orient_out, line_end_out, value_out, sp.mm, &mm_done, stream,
                          &sp.st, sp.w.sum, sp.w.nan_flags));
     const bool sparse = want_sparse && mm_done && sp.st.frame_entries > 0;
-    ctx->sparse_ran = sparse;
-    ctx->sparse_stream = s;
-    ctx->sparse_flags_off = (size_t)((char*)sp.w.dense_flags - (char*)ctx->ws.p);
-    ctx->sparse_candn_off = (size_t)((char*)sp.w.cand_n - (char*)ctx->ws.p);
-    ctx->sparse_pairs = n_frames * n_levels;
-    ctx->sparse_frames = n_frames;
+    publish_sparse_tail(ctx, sp, s, n_frames, n_levels, sparse);
     return select_run(ctx, who, line_end_out, mm_done ? nullptr : value_out, levels, n_levels, n_frames, 3, top_percent, sp, mm_done,
                       peak_value_out, idx, cap_per_frame, counts, s, sparse);
 } catch (...) {
@@ -813,114 +672,112 @@ SILENT_EXPORT int silent_rgb_keypoints_dev(silent_ctx* ctx, const float* pyr, co
 // of the sparse tail and the NaN flags, or written as a map -- the end map is never read back for a reduction.  selection = 1:
 // a-10 -> a-9 -> a-8 -> a-11 on (pad_inwards(end), value) with K channels, sparse like silent_rgb_keypoints (SILENT_TUNE_GRAY bit 6:
 // the dense kernels for every level); selection = 0: a-11 on the value map (recognition_testing.py:90).
+// The 16 arguments every silent_gray_keypoints* entry point has between n_frames and the stream, packed once at the ABI boundary
+struct GrayKpArgs {
+    const float *cs_kernel, *end_bank;
+    int n_orient;
+    float clip_hi, *pyr, *cs_out, *end_out;
+    int pad, selection;
+    double top_percent;
+    const silent_extent* regions;
+    float *value_out, *peak_value_out;
+    int64_t* idx;
+    size_t cap_per_frame;
+    int64_t* counts;
+};
+#define KP_ARGS                                                                                                                           \
+    const float *cs_kernel, const float *end_bank, int n_orient, float clip_hi, float *pyr, float *cs_out, float *end_out, int pad,       \
+        int selection, double top_percent, const silent_extent *regions, float *value_out, float *peak_value_out, int64_t *idx,           \
+        size_t cap_per_frame, int64_t *counts
+#define KP_PACK \
+    GrayKpArgs { cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection, top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts }
+
 // (everything the *_dev form refuses, before a launch and, in the host forms, before the batch is staged.)  FT: the frame element type
 // -- float, uint8_t (silent_gray_keypoints_u8[_dev]) or FrameRgb8 (silent_gray_keypoints_u8x3[_dev]) -- of the ENTRY POINT (the view
-// entry points check as a strided kind whatever kind then reads the view); has_frames / has_pyr / has_end: those arguments are not NULL
-// (the host forms need neither map from the caller)
+// entry points check as a strided kind whatever kind then reads the view); has_frames: that argument is not NULL; maps_optional: pyr and
+// end_out may be NULL (the host forms need neither map from the caller)
 template <typename FT>
 static int gray_keypoints_checks(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, bool has_frames, int n_frames,
-                                 const float* cs_kernel, const float* end_bank, int n_orient, bool has_pyr, bool has_end, int pad,
-                                 int selection, const silent_extent* regions, float* peak_value_out, int64_t* idx,
-                                 size_t cap_per_frame, int64_t* counts) {
-    if (!plan || !has_frames || !has_pyr || !cs_kernel || !end_bank || !has_end || !regions || !counts || (!idx && cap_per_frame))
+                                 const GrayKpArgs& a, bool maps_optional) {
+    const bool has_pyr = maps_optional || a.pyr, has_end = maps_optional || a.end_out;
+    if (!plan || !has_frames || !has_pyr || !a.cs_kernel || !a.end_bank || !has_end || !a.regions || !a.counts || (!a.idx && a.cap_per_frame))
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (plan->ctx != ctx) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": plan belongs to another context");
     if constexpr (kFrameNarrow<FT>) TRY(check_narrow_frames<FT>(ctx, who, plan));
     if (plan->tab.C != 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": the plan must be single-channel");
-    if (n_orient != 3 && n_orient != 4 && n_orient != 8)
+    if (a.n_orient != 3 && a.n_orient != 4 && a.n_orient != 8)
         return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": n_orient must be 3, 4 or 8");
     if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
-    if (pad < 0) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": pad must be >= 0");
-    if (selection != 0 && selection != 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": selection must be 0 or 1");
-    if (!selection && peak_value_out)
+    if (a.pad < 0) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": pad must be >= 0");
+    if (a.selection != 0 && a.selection != 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": selection must be 0 or 1");
+    if (!a.selection && a.peak_value_out)
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": peak_value_out needs selection = 1 (there is no peak-value map without it)");
     return SILENT_OK;
 }
 
 template <typename FT>
-static int gray_keypoints_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames,
-                              const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr,
-                              float* cs_out, float* end_out, int pad, int selection, double top_percent,
-                              const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-                              size_t cap_per_frame, int64_t* counts, silent_stream stream) {
+static int gray_keypoints_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames, const GrayKpArgs& a,
+                              silent_stream stream) {
     const char* who = entry_name<FT>(kGrayKeypoints);
-    TRY(gray_keypoints_checks<FT>(ctx, who, plan, frames != nullptr, n_frames, cs_kernel, end_bank, n_orient, pyr != nullptr, end_out != nullptr,
-                                  pad, selection, regions, peak_value_out, idx, cap_per_frame, counts));
+    TRY(gray_keypoints_checks<FT>(ctx, who, plan, frames != nullptr, n_frames, a, false));
     hipStream_t s = (hipStream_t)stream;
     const silent_extent* levels = plan->extents.data();
     const int n_levels = plan->tab.n_levels;
     GrayKp kp;
     std::memset(&kp, 0, sizeof(kp));
     kp.n_levels = n_levels;
-    kp.pad = pad;
+    kp.pad = a.pad;
     ctx->sparse_ran = false;
-    if (!selection) {
+    if (!a.selection) {
         // a-11 straight on the value map: the epilogue writes it (into the head of the workspace unless the caller takes it)
-        const size_t map_bytes = value_out ? 0 : align_up((size_t)plan->tab.frame_px_out * n_frames * sizeof(float));
+        const size_t map_bytes = a.value_out ? 0 : align_up((size_t)plan->tab.frame_px_out * n_frames * sizeof(float));
         RegionPlan rp;
-        TRY(region_prepare(ctx, who, levels, n_levels, n_frames, regions, map_bytes, s, &rp));
-        kp.value_out = value_out ? value_out : (float*)ctx->ws.p;
-        TRY(gray_pass_kp(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s));
-        return region_run(ctx, who, kp.value_out, levels, n_levels, n_frames, rp, idx, cap_per_frame, counts, s);
+        TRY(region_prepare(ctx, who, levels, n_levels, n_frames, a.regions, map_bytes, s, &rp));
+        kp.value_out = a.value_out ? a.value_out : (float*)ctx->ws.p;
+        TRY(gray_pass_kp(ctx, plan, frames, n_frames, a.cs_kernel, a.end_bank, a.n_orient, a.clip_hi, a.pyr, a.cs_out, a.end_out, kp, s));
+        return region_run(ctx, who, kp.value_out, levels, n_levels, n_frames, rp, a.idx, a.cap_per_frame, a.counts, s);
     }
     // The summary groups are kSumRows rows of a tile row; one SumTab geometry serves all levels, so both filter kernels must tile
     // with the same height (they do unless a build overrides SILENT_FUSED_TH; then the tail runs dense)
     const bool want_sparse = kFusedTH == kGrayTH && !(ctx->tune[SILENT_TUNE_GRAY] & 64u);
     SelectPlan sp;
-    TRY(select_prepare(ctx, who, levels, n_levels, n_frames, regions, s, &sp, want_sparse ? kGrayTH : 0, !peak_value_out));
+    TRY(select_prepare(ctx, who, levels, n_levels, n_frames, a.regions, s, &sp, want_sparse ? kGrayTH : 0, !a.peak_value_out));
     const bool sparse = want_sparse && sp.st.frame_entries > 0;
     kp.mm = sp.mm;
     kp.nan_flags = sp.w.nan_flags;
-    kp.value_out = value_out;
+    kp.value_out = a.value_out;
     if (sparse) {
         kp.sum = sp.w.sum;
         kp.sum_frame = sp.st.frame_entries;
         kp.gpt = sp.st.gpt;
         for (int l = 0; l < n_levels; ++l) kp.sum_off[l] = sp.st.off[l];
     }
-    TRY(gray_pass_kp(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, kp, s));
-    ctx->sparse_ran = sparse;
-    ctx->sparse_stream = s;
-    ctx->sparse_flags_off = (size_t)((char*)sp.w.dense_flags - (char*)ctx->ws.p);
-    ctx->sparse_candn_off = (size_t)((char*)sp.w.cand_n - (char*)ctx->ws.p);
-    ctx->sparse_pairs = n_frames * n_levels;
-    ctx->sparse_frames = n_frames;
-    return select_run(ctx, who, end_out, nullptr, levels, n_levels, n_frames, n_orient, top_percent, sp, true, peak_value_out, idx,
-                      cap_per_frame, counts, s, sparse, pad);
+    TRY(gray_pass_kp(ctx, plan, frames, n_frames, a.cs_kernel, a.end_bank, a.n_orient, a.clip_hi, a.pyr, a.cs_out, a.end_out, kp, s));
+    publish_sparse_tail(ctx, sp, s, n_frames, n_levels, sparse);
+    return select_run(ctx, who, a.end_out, nullptr, levels, n_levels, n_frames, a.n_orient, a.top_percent, sp, true, a.peak_value_out, a.idx,
+                      a.cap_per_frame, a.counts, s, sparse, a.pad);
 }
 
-SILENT_EXPORT int silent_gray_keypoints_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
-        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
-        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-        size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
+SILENT_EXPORT int silent_gray_keypoints_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames, KP_ARGS, silent_stream stream) try {
     NEED_CTX(ctx);
-    return gray_keypoints_dev(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
-                              top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
+    return gray_keypoints_dev(ctx, plan, frames, n_frames, KP_PACK, stream);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_dev");
 }
 
 // uint8 frames, read as they are (silent_hip.h): every output is silent_gray_keypoints_dev's on the widened frames
-SILENT_EXPORT int silent_gray_keypoints_u8_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
-        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
-        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-        size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
+SILENT_EXPORT int silent_gray_keypoints_u8_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, KP_ARGS, silent_stream stream) try {
     NEED_CTX(ctx);
-    return gray_keypoints_dev(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
-                              top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
+    return gray_keypoints_dev(ctx, plan, frames, n_frames, KP_PACK, stream);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u8_dev");
 }
 
 // interleaved 3-channel uint8 frames [n, H, W, 3], read as they are (silent_hip.h): every output is silent_gray_keypoints_dev's on
 // the frame of values (b0 + b1 + b2) * float32(1/3)
-SILENT_EXPORT int silent_gray_keypoints_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
-        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
-        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-        size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
+SILENT_EXPORT int silent_gray_keypoints_u8x3_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, KP_ARGS, silent_stream stream) try {
     NEED_CTX(ctx);
-    return gray_keypoints_dev(ctx, plan, rgb8(frames), n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
-                              top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
+    return gray_keypoints_dev(ctx, plan, rgb8(frames), n_frames, KP_PACK, stream);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u8x3_dev");
 }
@@ -946,6 +803,11 @@ SILENT_EXPORT int silent_sparse_tail_stats(silent_ctx* ctx, int64_t* stats) try 
 
 // ------------------------------------------------------------------------------------------ host-pointer twins
 
+// some frame holds more keypoints than the caller's index buffer takes (the host forms report it: SILENT_E_CAPACITY)
+static bool over_capacity(const int64_t* counts, int n_frames, size_t cap_per_frame) {
+    return std::any_of(counts, counts + n_frames, [&](int64_t c) { return c > (int64_t)cap_per_frame; });
+}
+
 SILENT_EXPORT int silent_pad_inwards(silent_ctx* ctx, const float* in, const silent_extent* levels, int n_levels,
                                      int n_frames, int channels, int pt, int pb, int pl, int pr, float* out) try {
     NEED_CTX(ctx);
@@ -964,18 +826,22 @@ SILENT_EXPORT int silent_pad_inwards(silent_ctx* ctx, const float* in, const sil
     return on_exception(ctx, "silent_pad_inwards");
 }
 
+static int from_color_host(silent_ctx* ctx, const char* who,
+                           int (*dev)(silent_ctx*, const float*, const silent_extent*, int, int, int, float*, silent_stream), const float* in,
+                           const silent_extent* levels, int n_levels, int n_frames, int channels, float* out) {
+    if (!in || !out) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (channels < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": channels must be >= 1");
+    long long px;
+    TRY(check_levels(ctx, who, levels, n_levels, n_frames, &px));
+    HostStage hs(ctx);
+    const int x = hs.in(in, (size_t)px * channels * 4), o = hs.out(out, (size_t)px * 4);
+    return hs.run([&] { return dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, channels, hs.dev<float>(o), nullptr); });
+}
+
 SILENT_EXPORT int silent_value_from_color(silent_ctx* ctx, const float* in, const silent_extent* levels, int n_levels,
                                           int n_frames, int channels, float* out) try {
     NEED_CTX(ctx);
-    if (!in || !out) return fail(ctx, SILENT_E_INVALID, "silent_value_from_color: NULL pointer");
-    if (channels < 1) return fail(ctx, SILENT_E_INVALID, "silent_value_from_color: channels must be >= 1");
-    long long px;
-    TRY(check_levels(ctx, "silent_value_from_color", levels, n_levels, n_frames, &px));
-    HostStage hs(ctx);
-    const int x = hs.in(in, (size_t)px * channels * 4), o = hs.out(out, (size_t)px * 4);
-    return hs.run([&] {
-        return silent_value_from_color_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, channels, hs.dev<float>(o), nullptr);
-    });
+    return from_color_host(ctx, "silent_value_from_color", silent_value_from_color_dev, in, levels, n_levels, n_frames, channels, out);
 } catch (...) {
     return on_exception(ctx, "silent_value_from_color");
 }
@@ -983,15 +849,7 @@ SILENT_EXPORT int silent_value_from_color(silent_ctx* ctx, const float* in, cons
 SILENT_EXPORT int silent_bw_from_color(silent_ctx* ctx, const float* in, const silent_extent* levels, int n_levels,
                                           int n_frames, int channels, float* out) try {
     NEED_CTX(ctx);
-    if (!in || !out) return fail(ctx, SILENT_E_INVALID, "silent_bw_from_color: NULL pointer");
-    if (channels < 1) return fail(ctx, SILENT_E_INVALID, "silent_bw_from_color: channels must be >= 1");
-    long long px;
-    TRY(check_levels(ctx, "silent_bw_from_color", levels, n_levels, n_frames, &px));
-    HostStage hs(ctx);
-    const int x = hs.in(in, (size_t)px * channels * 4), o = hs.out(out, (size_t)px * 4);
-    return hs.run([&] {
-        return silent_bw_from_color_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, channels, hs.dev<float>(o), nullptr);
-    });
+    return from_color_host(ctx, "silent_bw_from_color", silent_bw_from_color_dev, in, levels, n_levels, n_frames, channels, out);
 } catch (...) {
     return on_exception(ctx, "silent_bw_from_color");
 }
@@ -1047,13 +905,11 @@ SILENT_EXPORT int silent_max_value_indices_region(silent_ctx* ctx, const float* 
         return silent_max_value_indices_region_dev(ctx, hs.dev<float>(v), levels, n_levels, n_frames, regions, hs.dev<int64_t>(i),
                                                    cap_per_frame, hs.dev<int64_t>(c), nullptr);
     }));
-    bool over = false;
     for (int f = 0; f < n_frames; ++f) {
         const size_t n = (size_t)std::min<int64_t>(counts[f], (int64_t)cap_per_frame), row = (size_t)f * cap_per_frame * 4;
-        if (counts[f] > (int64_t)cap_per_frame) over = true;
         if (n) HIP_TRY(ctx, hipMemcpy(idx + row, hs.dev<int64_t>(i) + row, n * 4 * sizeof(int64_t), hipMemcpyDeviceToHost));
     }
-    if (over) return fail(ctx, SILENT_E_CAPACITY, "silent_max_value_indices_region: cap_per_frame too small; counts hold the need");
+    if (over_capacity(counts, n_frames, cap_per_frame)) return fail(ctx, SILENT_E_CAPACITY, "silent_max_value_indices_region: cap_per_frame too small; counts hold the need");
     return SILENT_OK;
 } catch (...) {
     return on_exception(ctx, "silent_max_value_indices_region");
@@ -1081,9 +937,7 @@ SILENT_EXPORT int silent_rgb_keypoints(silent_ctx* ctx, const float* pyr, const 
                                         hs.dev<int64_t>(n), nullptr);
     }));
     // idx / counts as silent_max_value_indices_region: the host form reports an index buffer that was too small
-    for (int f = 0; f < n_frames; ++f)
-        if (counts[f] > (int64_t)cap_per_frame)
-            return fail(ctx, SILENT_E_CAPACITY, "silent_rgb_keypoints: cap_per_frame too small; counts hold the need");
+    if (over_capacity(counts, n_frames, cap_per_frame)) return fail(ctx, SILENT_E_CAPACITY, "silent_rgb_keypoints: cap_per_frame too small; counts hold the need");
     return SILENT_OK;
 } catch (...) {
     return on_exception(ctx, "silent_rgb_keypoints");
@@ -1091,62 +945,45 @@ SILENT_EXPORT int silent_rgb_keypoints(silent_ctx* ctx, const float* pyr, const 
 
 // the host-pointer forms of silent_gray_keypoints on any frame type: the frames are staged as they are (frame_px_bytes each pixel)
 template <typename FT>
-static int gray_keypoints_host(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames, const float* cs_kernel,
-                               const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
-                               int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out,
-                               int64_t* idx, size_t cap_per_frame, int64_t* counts) {
+static int gray_keypoints_host(silent_ctx* ctx, const silent_pyramid_plan* plan, const FT* frames, int n_frames, const GrayKpArgs& a) {
     const char* who = entry_name<FT>(kGrayKeypoints);
     // (the host form accepts NULL pyr / end_out: the *_dev form needs both maps, they then live in the staging arena)
-    TRY(gray_keypoints_checks<FT>(ctx, who, plan, frames != nullptr, n_frames, cs_kernel, end_bank, n_orient, true, true, pad, selection, regions,
-                                  peak_value_out, idx, cap_per_frame, counts));
+    TRY(gray_keypoints_checks<FT>(ctx, who, plan, frames != nullptr, n_frames, a, true));
     HostStage hs(ctx);
     const size_t b1 = (size_t)plan->tab.frame_px_out * n_frames * 4;
     const int x = hs.in(frames_host(frames), frames_bytes(plan, frames, n_frames)),
-              p = pyr ? hs.out(pyr, b1) : hs.scratch(b1), cs = hs.out(cs_out, b1),
-              end = end_out ? hs.out(end_out, b1 * n_orient) : hs.scratch(b1 * n_orient), v = hs.out(value_out, b1),
-              pv = hs.out(peak_value_out, b1), i = hs.out(idx, (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
-              n = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
+              p = a.pyr ? hs.out(a.pyr, b1) : hs.scratch(b1), cs = hs.out(a.cs_out, b1),
+              end = a.end_out ? hs.out(a.end_out, b1 * a.n_orient) : hs.scratch(b1 * a.n_orient), v = hs.out(a.value_out, b1),
+              pv = hs.out(a.peak_value_out, b1), i = hs.out(a.idx, (size_t)n_frames * a.cap_per_frame * 4 * sizeof(int64_t)),
+              n = hs.out(a.counts, (size_t)n_frames * sizeof(int64_t));
     TRY(hs.run([&] {
         const StagedFrames<FT> staged(frames, hs.dev<char>(x));
-        return gray_keypoints_dev(ctx, plan, staged.p, n_frames, cs_kernel, end_bank, n_orient, clip_hi, hs.dev<float>(p),
-                                  hs.dev<float>(cs), hs.dev<float>(end), pad, selection, top_percent, regions, hs.dev<float>(v),
-                                  hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame, hs.dev<int64_t>(n), nullptr);
+        GrayKpArgs d = a;   // the same call on the staged buffers (pyr / end_out: the arena's, where the caller has none)
+        d.pyr = hs.dev<float>(p), d.cs_out = hs.dev<float>(cs), d.end_out = hs.dev<float>(end);
+        d.value_out = hs.dev<float>(v), d.peak_value_out = hs.dev<float>(pv), d.idx = hs.dev<int64_t>(i), d.counts = hs.dev<int64_t>(n);
+        return gray_keypoints_dev(ctx, plan, staged.p, n_frames, d, nullptr);
     }));
-    for (int f = 0; f < n_frames; ++f)
-        if (counts[f] > (int64_t)cap_per_frame)
-            return fail(ctx, SILENT_E_CAPACITY, std::string(who) + ": cap_per_frame too small; counts hold the need");
+    if (over_capacity(a.counts, n_frames, a.cap_per_frame)) return fail(ctx, SILENT_E_CAPACITY, std::string(who) + ": cap_per_frame too small; counts hold the need");
     return SILENT_OK;
 }
 
-SILENT_EXPORT int silent_gray_keypoints(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames,
-        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
-        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-        size_t cap_per_frame, int64_t* counts) try {
+SILENT_EXPORT int silent_gray_keypoints(silent_ctx* ctx, const silent_pyramid_plan* plan, const float* frames, int n_frames, KP_ARGS) try {
     NEED_CTX(ctx);
-    return gray_keypoints_host(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
-                               top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts);
+    return gray_keypoints_host(ctx, plan, frames, n_frames, KP_PACK);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints");
 }
 
-SILENT_EXPORT int silent_gray_keypoints_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
-        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
-        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-        size_t cap_per_frame, int64_t* counts) try {
+SILENT_EXPORT int silent_gray_keypoints_u8(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, KP_ARGS) try {
     NEED_CTX(ctx);
-    return gray_keypoints_host(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
-                               top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts);
+    return gray_keypoints_host(ctx, plan, frames, n_frames, KP_PACK);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u8");
 }
 
-SILENT_EXPORT int silent_gray_keypoints_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames,
-        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
-        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-        size_t cap_per_frame, int64_t* counts) try {
+SILENT_EXPORT int silent_gray_keypoints_u8x3(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint8_t* frames, int n_frames, KP_ARGS) try {
     NEED_CTX(ctx);
-    return gray_keypoints_host(ctx, plan, rgb8(frames), n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
-                               top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts);
+    return gray_keypoints_host(ctx, plan, rgb8(frames), n_frames, KP_PACK);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u8x3");
 }
@@ -1154,58 +991,38 @@ SILENT_EXPORT int silent_gray_keypoints_u8x3(silent_ctx* ctx, const silent_pyram
 // Strided uint8 views (silent_hip.h): the view's own refusals and those of the *_u8 form under the view's name, then the frame kind
 // that reads it (with_view: a packed view takes the packed kernels).
 static int gray_keypoints_view(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_frame_view* view, int n_frames,
-                               const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out,
-                               float* end_out, int pad, int selection, double top_percent, const silent_extent* regions, float* value_out,
-                               float* peak_value_out, int64_t* idx, size_t cap_per_frame, int64_t* counts, silent_stream stream) {
+                               const GrayKpArgs& a, silent_stream stream) {
     const char* who = "silent_gray_keypoints_view";
     TRY(check_view(ctx, who, plan, view, n_frames, nullptr));
     // (the host form accepts NULL pyr / end_out, see gray_keypoints_host)
-    TRY(gray_keypoints_checks<View8>(ctx, who, plan, true, n_frames, cs_kernel, end_bank, n_orient, host || pyr, host || end_out, pad, selection,
-                                     regions, peak_value_out, idx, cap_per_frame, counts));
+    TRY(gray_keypoints_checks<View8>(ctx, who, plan, true, n_frames, a, host));
     return with_view(plan, view, n_frames, [&](auto frames) {
-        if (host)
-            return gray_keypoints_host(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
-                                       top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts);
-        return gray_keypoints_dev(ctx, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
-                                  top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
+        if (host) return gray_keypoints_host(ctx, plan, frames, n_frames, a);
+        return gray_keypoints_dev(ctx, plan, frames, n_frames, a, stream);
     });
 }
 
 SILENT_EXPORT int silent_gray_keypoints_view_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
-        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
-        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-        size_t cap_per_frame, int64_t* counts, silent_stream stream) try {
+                                                 KP_ARGS, silent_stream stream) try {
     NEED_CTX(ctx);
-    return gray_keypoints_view(ctx, false, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
-                               top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
+    return gray_keypoints_view(ctx, false, plan, frames, n_frames, KP_PACK, stream);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_view_dev");
 }
 
 SILENT_EXPORT int silent_gray_keypoints_view(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view* frames, int n_frames,
-        const float* cs_kernel, const float* end_bank, int n_orient, float clip_hi, float* pyr, float* cs_out, float* end_out, int pad,
-        int selection, double top_percent, const silent_extent* regions, float* value_out, float* peak_value_out, int64_t* idx,
-        size_t cap_per_frame, int64_t* counts) try {
+                                             KP_ARGS) try {
     NEED_CTX(ctx);
-    return gray_keypoints_view(ctx, true, plan, frames, n_frames, cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection,
-                               top_percent, regions, value_out, peak_value_out, idx, cap_per_frame, counts, nullptr);
+    return gray_keypoints_view(ctx, true, plan, frames, n_frames, KP_PACK, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_view");
 }
 
 // uint16 frames (silent_hip.h): the *_u8 forms with an unsigned 16-bit element, 2-byte aligned; strided uint16 views as the *_view forms
-#define KP_ARGS                                                                                                                           \
-    const float *cs_kernel, const float *end_bank, int n_orient, float clip_hi, float *pyr, float *cs_out, float *end_out, int pad,       \
-        int selection, double top_percent, const silent_extent *regions, float *value_out, float *peak_value_out, int64_t *idx,           \
-        size_t cap_per_frame, int64_t *counts
-#define KP_PASS                                                                                                                           \
-    cs_kernel, end_bank, n_orient, clip_hi, pyr, cs_out, end_out, pad, selection, top_percent, regions, value_out, peak_value_out, idx,   \
-        cap_per_frame, counts
-SILENT_EXPORT int silent_gray_keypoints_u16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames, KP_ARGS,
-                                                silent_stream stream) try {
+SILENT_EXPORT int silent_gray_keypoints_u16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames, KP_ARGS, silent_stream stream) try {
     NEED_CTX(ctx);
     TRY(check_u16_aligned(ctx, "silent_gray_keypoints_u16", frames));
-    return gray_keypoints_dev(ctx, plan, frames, n_frames, KP_PASS, stream);
+    return gray_keypoints_dev(ctx, plan, frames, n_frames, KP_PACK, stream);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u16_dev");
 }
@@ -1213,28 +1030,27 @@ SILENT_EXPORT int silent_gray_keypoints_u16_dev(silent_ctx* ctx, const silent_py
 SILENT_EXPORT int silent_gray_keypoints_u16(silent_ctx* ctx, const silent_pyramid_plan* plan, const uint16_t* frames, int n_frames, KP_ARGS) try {
     NEED_CTX(ctx);
     TRY(check_u16_aligned(ctx, "silent_gray_keypoints_u16", frames));
-    return gray_keypoints_host(ctx, plan, frames, n_frames, KP_PASS);
+    return gray_keypoints_host(ctx, plan, frames, n_frames, KP_PACK);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_u16");
 }
 
-static int gray_keypoints_view16(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_frame_view16* view, int n_frames, KP_ARGS,
-                                 silent_stream stream) {
+static int gray_keypoints_view16(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_frame_view16* view, int n_frames,
+                                 const GrayKpArgs& a, silent_stream stream) {
     const char* who = "silent_gray_keypoints_view16";
     TRY(check_view16(ctx, who, plan, view, n_frames, nullptr));
     // (the host form accepts NULL pyr / end_out, see gray_keypoints_host)
-    TRY(gray_keypoints_checks<View16>(ctx, who, plan, true, n_frames, cs_kernel, end_bank, n_orient, host || pyr, host || end_out, pad, selection,
-                                      regions, peak_value_out, idx, cap_per_frame, counts));
+    TRY(gray_keypoints_checks<View16>(ctx, who, plan, true, n_frames, a, host));
     return with_view16(plan, view, n_frames, [&](auto frames) {
-        if (host) return gray_keypoints_host(ctx, plan, frames, n_frames, KP_PASS);
-        return gray_keypoints_dev(ctx, plan, frames, n_frames, KP_PASS, stream);
+        if (host) return gray_keypoints_host(ctx, plan, frames, n_frames, a);
+        return gray_keypoints_dev(ctx, plan, frames, n_frames, a, stream);
     });
 }
 
 SILENT_EXPORT int silent_gray_keypoints_view16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view16* frames, int n_frames,
                                                    KP_ARGS, silent_stream stream) try {
     NEED_CTX(ctx);
-    return gray_keypoints_view16(ctx, false, plan, frames, n_frames, KP_PASS, stream);
+    return gray_keypoints_view16(ctx, false, plan, frames, n_frames, KP_PACK, stream);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_view16_dev");
 }
@@ -1242,12 +1058,12 @@ SILENT_EXPORT int silent_gray_keypoints_view16_dev(silent_ctx* ctx, const silent
 SILENT_EXPORT int silent_gray_keypoints_view16(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_frame_view16* frames, int n_frames,
                                                KP_ARGS) try {
     NEED_CTX(ctx);
-    return gray_keypoints_view16(ctx, true, plan, frames, n_frames, KP_PASS, nullptr);
+    return gray_keypoints_view16(ctx, true, plan, frames, n_frames, KP_PACK, nullptr);
 } catch (...) {
     return on_exception(ctx, "silent_gray_keypoints_view16");
 }
 #undef KP_ARGS
-#undef KP_PASS
+#undef KP_PACK
 
 SILENT_EXPORT int silent_centroids(silent_ctx* ctx, const float* value, const silent_extent* levels, int n_levels,
                                    int n_frames, int region_h, int region_w, float* dist_out, float* total_out) try {
@@ -1256,7 +1072,7 @@ SILENT_EXPORT int silent_centroids(silent_ctx* ctx, const float* value, const si
     long long px;
     TRY(check_levels(ctx, "silent_centroids", levels, n_levels, n_frames, &px));
     CellTab ct;
-    TRY(build_cell_tab(ctx, "silent_centroids", levels, n_levels, region_h, region_w, &ct));
+    TRY(refuse(ctx, "silent_centroids", build_cell_tab(levels, n_levels, region_h, region_w, &ct)));
     HostStage hs(ctx);
     const int v = hs.in(value, (size_t)px * 4), d = hs.out(dist_out, (size_t)px * 4),
               t = hs.out(total_out, (size_t)ct.frame_cells * n_frames * 4);
@@ -1274,7 +1090,7 @@ SILENT_EXPORT int silent_boosting_step(silent_ctx* ctx, const float* input, cons
     NEED_CTX(ctx);
     if (!input || !energy || !fired_out) return fail(ctx, SILENT_E_INVALID, "silent_boosting_step: NULL pointer");
     BoostP bp;
-    TRY(check_boost_params(ctx, params, &bp));
+    TRY(refuse(ctx, "silent_boosting_step", boost_params(params, &bp)));
     long long px;
     TRY(check_levels(ctx, "silent_boosting_step", levels, n_levels, n_frames, &px));
     HostStage hs(ctx);
@@ -1381,9 +1197,7 @@ SILENT_EXPORT int silent_select_keypoints(silent_ctx* ctx, const float* color, c
                                            regions, hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame, hs.dev<int64_t>(n), nullptr);
     }));
     // idx / counts as silent_max_value_indices_region: the host form reports an index buffer that was too small
-    for (int f = 0; f < n_frames; ++f)
-        if (counts[f] > (int64_t)cap_per_frame)
-            return fail(ctx, SILENT_E_CAPACITY, "silent_select_keypoints: cap_per_frame too small; counts hold the need");
+    if (over_capacity(counts, n_frames, cap_per_frame)) return fail(ctx, SILENT_E_CAPACITY, "silent_select_keypoints: cap_per_frame too small; counts hold the need");
     return SILENT_OK;
 } catch (...) {
     return on_exception(ctx, "silent_select_keypoints");
