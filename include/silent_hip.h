@@ -981,6 +981,43 @@ int silent_displayer_input(silent_displayer* d, void** frame_buffer, size_t* byt
 int silent_displayer_get_state(silent_displayer* d, float* energy_host);       /* [L, ch, cw] */
 int silent_displayer_set_state(silent_displayer* d, const float* energy_host);
 
+/* ---------------------------------------------------------------------------- the same tail for a batch of streams
+ * What LineEndDisplayer.compile computes after the line-end map (recognition_testing.py:77-100), on a PACKED pyramid batch: every frame
+ * slot is a camera stream of its own, every level has its own extents.  value: packed 1-channel maps, the layout of
+ * silent_rgb_line_end's value_out (get_value_from_color(pad_inwards(line_end))).  Results and the advanced state are those of this
+ * sequence of the entry points above on the same value, BIT FOR BIT, NaNs included (an empty cell gives 0 / 0):
+ *     g      = affine_clip(value, div = 255)                   dist,  tot = centroids(g, region_h, region_w)
+ *     imp    = affine_clip(tot, 255 / 4, 0, 1, 256, -1)        im2        = resize_nearest(value, half)
+ *     dist2, _ = centroids(affine_clip(im2, div = 255), ...)   fired, upd = boosting_step(imp, energy, boosting)
+ *     centroids_out = affine_clip(dist, -255, 255)     centroids2_out = affine_clip(dist2, -255, 255)
+ *     fired_out     = affine_clip(fired, 255)          update_out     = upd
+ * in two launches, with no intermediate map in memory (8 + 8 + 4 + 4 bytes per cell of workspace).
+ *   energy          caller-owned state [n_frames][cells of every level], updated in place (the contract of silent_boosting_step)
+ *   centroids_out   255 - dist * 255, laid out like value
+ *   centroids2_out  the same on the nearest-neighbour half map: level l has (int)((float)h / resize_div) x (int)((float)w / resize_div)
+ *                   pixels (float32 division, truncated: recognition_testing.py:82-83), packed with those extents
+ *   fired_out       fired * 255, update_out: update_importances; packed with the cell extents (level l: ceil(h / region_h) x
+ *                   ceil(w / region_w)), 3 channels when boosting.visualize is set, else 1
+ * Any of the four outputs may be NULL; with centroids2_out == NULL nothing of the half map is computed.  SILENT_E_INVALID: NULL value,
+ * energy or params; n_levels outside 1 .. SILENT_MAX_LEVELS; n_frames < 1; a region extent below 1; a non-positive level extent;
+ * resize_div below 1 or not finite; a level whose half extent would be 0.
+ * silent_attention_extents: host only, no GPU work and no context (its message: silent_last_error(NULL)): per level the cell extents
+ * of the map, the half extents, the cell extents of the half map; each output may be NULL. */
+typedef struct silent_attention_params {
+    int32_t region_h, region_w;        /* centroid_region_shape[1:3] = 3, 3 (recognition_testing.py:39) */
+    float resize_div;                  /* float32(e ** .5) (:82-83) */
+    silent_boosting_params boosting;   /* as silent_boosting_step takes them */
+} silent_attention_params;
+
+int silent_attention_extents(const silent_extent* levels, int n_levels, const silent_attention_params* params, silent_extent* cells,
+                             silent_extent* half, silent_extent* cells2);
+int silent_attention_tail(silent_ctx* ctx, const float* value, const silent_extent* levels, int n_levels, int n_frames,
+                          const silent_attention_params* params, float* energy, float* centroids_out, float* centroids2_out,
+                          float* fired_out, float* update_out);
+int silent_attention_tail_dev(silent_ctx* ctx, const float* value, const silent_extent* levels, int n_levels, int n_frames,
+                              const silent_attention_params* params, float* energy, float* centroids_out, float* centroids2_out,
+                              float* fired_out, float* update_out, silent_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

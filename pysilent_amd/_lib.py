@@ -61,6 +61,11 @@ class AffineParams(C.Structure):
                 ("post_add", C.c_float)]
 
 
+class AttentionParams(C.Structure):
+    """silent_attention_params (include/silent_hip.h)."""
+    _fields_ = [("region_h", C.c_int32), ("region_w", C.c_int32), ("resize_div", C.c_float), ("boosting", BoostingParams)]
+
+
 class DisplayerParams(C.Structure):
     """silent_displayer_params (include/silent_hip.h)."""
     _fields_ = [("frame_h", C.c_int32), ("frame_w", C.c_int32), ("frame_dtype", C.c_int32), ("centroid_region_h", C.c_int32),
@@ -266,6 +271,9 @@ _SIGNATURES = {
     "silent_displayer_input": [_vp, C.POINTER(_vp), C.POINTER(_sz)],
     "silent_displayer_get_state": [_vp, _fp],
     "silent_displayer_set_state": [_vp, _fp],
+    "silent_attention_extents": [_ep, _i, C.POINTER(AttentionParams), _ep, _ep, _ep],
+    "silent_attention_tail": [_vp, _fp, _ep, _i, _i, C.POINTER(AttentionParams), _fp, _fp, _fp, _fp, _fp],
+    "silent_attention_tail_dev": [_vp, _fp, _ep, _i, _i, C.POINTER(AttentionParams), _fp, _fp, _fp, _fp, _fp, _vp],
 }
 _RESTYPES = {"silent_destroy": None, "silent_pyramid_plan_destroy": None, "silent_displayer_destroy": None, "silent_last_error": C.c_char_p}
 

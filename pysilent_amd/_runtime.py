@@ -607,6 +607,64 @@ def boosting_step(x, energy, exhaustion_max=1.0, excitation_max=1.0, recovery_mo
     return op.wrap(fired, c), op.wrap(eout, c)
 
 
+ATTENTION_RESIZE_DIV = float(np.float32(float(np.e) ** .5))      # recognition_testing.py:82-83: float32(e ** .5)
+
+
+def attention_params(region=(3, 3), resize_div=None, exhaustion_max=1.0, excitation_max=1.0, recovery_mode=_lib.RECOVERY_CONSTANT,
+                     visualize=True, recovery_amount=10.0, recovery_percentage=0.8):
+    """A silent_attention_params: the centroid region, the divisor of the half map and the boosting parameters."""
+    rh, rw = (int(v) for v in region)
+    if rh < 1 or rw < 1:
+        raise ValueError("region extents must be >= 1")
+    return _lib.AttentionParams(rh, rw, ATTENTION_RESIZE_DIV if resize_div is None else float(resize_div),
+                                _lib.BoostingParams(float(exhaustion_max), float(excitation_max), int(recovery_mode), float(recovery_amount),
+                                                    float(recovery_percentage), 1 if visualize else 0))
+
+
+def attention_extents(extents, params):
+    """silent_attention_extents (host only, no GPU work): per level the cell extents of the map, the half extents and the cell extents
+    of the half map, as three lists of (h, w).  ValueError for what silent_attention_tail refuses of the geometry."""
+    n = len(extents)
+    levels = (_lib.Extent * max(n, 1))(*[_lib.Extent(int(h), int(w)) for h, w in extents])
+    out = [(_lib.Extent * max(n, 1))() for _ in range(3)]
+    _lib.check(_lib.load().silent_attention_extents(levels, n, C.byref(params), *out))
+    return tuple([(int(e.h), int(e.w)) for e in o[:n]] for o in out)
+
+
+def attention_tail(value, energy, region=(3, 3), resize_div=None, exhaustion_max=1.0, excitation_max=1.0,
+                   recovery_mode=_lib.RECOVERY_CONSTANT, visualize=True, recovery_amount=10.0, recovery_percentage=0.8,
+                   want=("centroids", "centroids2", "fired", "update")):
+    """silent_attention_tail: what LineEndDisplayer.compile computes after the line-end map (recognition_testing.py:77-100) on a batch
+    of 1-channel value maps -- a PackedPyramid or an NHWC tensor, every frame a stream of its own -- in two launches.  ``energy``: the
+    boosting state, one value per centroid cell (a PackedPyramid with the cell extents / a tensor [n, ceil(h / rh), ceil(w / rw), 1]),
+    advanced in place.  Returns (255 - centroids * 255, the same on the nearest-neighbour half map, fired * 255, update_importances) as
+    PackedPyramids / tensors like ``value``; fired and update have 3 channels when ``visualize``.  ``want``: the results to compute
+    (None in the place of the others; without "centroids2" nothing of the half map is computed)."""
+    unknown = set(want) - {"centroids", "centroids2", "fired", "update"}
+    if unknown:
+        raise ValueError("attention_tail: unknown result %s" % sorted(unknown))
+    _require_inplace(energy)
+    op, st = _Operand(value, channels=1), _Operand(energy, channels=1)
+    params = attention_params(region, resize_div, exhaustion_max, excitation_max, recovery_mode, visualize, recovery_amount, recovery_percentage)
+    cells, half, _ = attention_extents(op.extents, params)
+    if st.extents != cells or st.n_frames != op.n_frames or st.dev != op.dev:
+        raise ValueError("attention_tail: the state must hold one value per centroid cell, %s per frame, placed like the value map" % (cells,))
+    c = 3 if visualize else 1
+    n_cells = op.n_frames * sum(h * w for h, w in cells)
+    sizes = {"centroids": op.n_frames * op.frame_px, "centroids2": op.n_frames * sum(h * w for h, w in half), "fired": n_cells * c,
+             "update": n_cells * c}
+    bufs = {k: op.empty(sizes[k]) if k in want else (None, None) for k in ("centroids", "centroids2", "fired", "update")}
+    op.call("attention_tail", op.ptr, *op.geom(), C.byref(params), st.ptr, *[bufs[k][1] for k in ("centroids", "centroids2", "fired", "update")])
+
+    def wrap(k, ext, ch):
+        if bufs[k][0] is None:
+            return None
+        if op.packed:
+            return PackedPyramid(bufs[k][0], ext, ch, op.n_frames)
+        return bufs[k][0].reshape(op.n_frames, ext[0][0], ext[0][1], ch)
+    return wrap("centroids", op.extents, 1), wrap("centroids2", half, 1), wrap("fired", cells, c), wrap("update", cells, c)
+
+
 def affine_clip(x, mul=1.0, add=0.0, lo=-float("inf"), hi=float("inf"), post_add=0.0, div=1.0):
     """silent_affine_clip: clip(x * mul / div + add, lo, hi) + post_add, any channel count."""
     op = _Operand(x)

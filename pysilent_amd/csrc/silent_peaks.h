@@ -1350,4 +1350,143 @@ __global__ __launch_bounds__(64) void disp_signal_kernel(unsigned long long* seq
     }
 }
 
+// ---- the same tail for a BATCH of packed pyramids (silent_attention_tail: every frame slot a stream of its own, every level its own
+// extents) in two launches.  DispTail above knows L canvases of ONE extent and spends a division and a modulo per pixel -- nothing on a
+// 640 x 480 frame at the launch floor, wrong at 88 Mpx a step.  Here the index spaces are LevelTabs (locate_tile): the pixels of the
+// map and of the nearest-neighbour half map as 2-D tiles, the map's cells as chunks; per cell and per pixel the arithmetic is the
+// per-op kernels' own (affine_px, centroid_cell_of, centroid_dist_px, boost_update_px, boost_power_kernel's float64 pow), so the results
+// are those of the per-op sequence bit for bit.  Nothing but the cell tables goes through memory between the two launches: 8 + 8 + 4 + 4
+// bytes per cell (centroids of both maps, importances, importances ** energy).
+constexpr int kAttnTW = 64, kAttnRows = 16, kAttnTH = 4 * kAttnRows;   // a tile: 64 columns (a lane each) x 4 waves x 16 rows
+
+struct AttnTab {
+    LevelTab tab1, tab2, tabc;                     // tiles of the map, tiles of the half map, chunks of the map's cell grids
+    CellTab ct1, ct2;                              // cells of the map, of the half map
+    float yscale_r[kMaxLevels], xscale_r[kMaxLevels];   // float32 h / h2, w / w2: the nearest-neighbour resize
+    AffineP by255, imp, inv, x255;
+    BoostP bp;
+    unsigned b1, b2;                               // attn_pixels_kernel: blocks [0, b1) the map, [b1, b2) the half map, from b2 on the cells
+    int n_frames;
+    long long n_cells, n_cells2;                   // of all frames (n_cells2 = 0: nothing of the half map is computed)
+};
+struct AttnPtr {
+    const float* value;                            // packed 1-channel map
+    float* energy;                                 // [n_frames][cells of every level], advanced in place
+    float *cxy, *cxy2, *imp, *m;                   // workspace (AttnLayout)
+    float *out1, *out2, *fired, *update;           // any may be NULL
+};
+static_assert(sizeof(AttnTab) + sizeof(AttnPtr) <= 3584, "the four index spaces of 16 levels travel as a kernel argument (4 KB)");
+
+// (1) one thread per cell of both maps: value / 255 -- and for the half map the nearest-neighbour source index -- at the load; for the
+//     map's cells also the importance and importance ** energy.  A wave's 64 adjacent cells read 64 x rw contiguous floats per row.
+template <bool HALF>
+__device__ __forceinline__ void attn_cell(const AttnTab& t, const AttnPtr& p, long long q) {
+    const CellTab& ct = HALF ? t.ct2 : t.ct1;
+    const int frame = (int)(q / ct.frame_cells);
+    long long rem = q - (long long)frame * ct.frame_cells;
+    int l = 0;
+#pragma unroll
+    for (int i = 1; i < kMaxLevels; ++i)
+        if (i < t.tab1.n_levels && rem >= ct.cell_off[i]) l = i;
+    const int r = (int)(rem - ct.cell_off[l]), ow = ct.ow[l];
+    const int j = r / ow, i = r - j * ow;
+    const int H = t.tab1.h[l], W = t.tab1.w[l];
+    const float* __restrict__ v = p.value + (long long)frame * t.tab1.frame_px + t.tab1.px_off[l];
+    float tot, cx, cy;
+    if constexpr (!HALF) {
+        centroid_cell_of([&](int y, int x) { return affine_px(v[(long long)y * W + x], t.by255); }, H, W, ct.y_first[l], ct.x_first[l], ct.rh, ct.rw,
+                         j, i, &tot, &cx, &cy);
+        p.cxy[q * 2] = cx;
+        p.cxy[q * 2 + 1] = cy;
+        const float imp = affine_px(tot, t.imp);
+        p.imp[q] = imp;
+        p.m[q] = (float)pow((double)imp, (double)p.energy[q]);          // boost_power_kernel
+    } else {
+        const float ys = t.yscale_r[l], xs = t.xscale_r[l];
+        centroid_cell_of(
+            [&](int y, int x) {                                         // resize_nearest_kernel, then value / 255
+                const int sy = min((int)floorf(__fmul_rn((float)y, ys)), H - 1);
+                const int sx = min((int)floorf(__fmul_rn((float)x, xs)), W - 1);
+                return affine_px(v[(long long)sy * W + sx], t.by255);
+            },
+            t.tab2.h[l], t.tab2.w[l], ct.y_first[l], ct.x_first[l], ct.rh, ct.rw, j, i, &tot, &cx, &cy);
+        p.cxy2[q * 2] = cx;
+        p.cxy2[q * 2 + 1] = cy;
+    }
+}
+__global__ __launch_bounds__(256) void attn_cells_kernel(const AttnTab t, const AttnPtr p) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid < t.n_cells) attn_cell<false>(t, p, gid);
+    else if (gid - t.n_cells < t.n_cells2) attn_cell<true>(t, p, gid - t.n_cells);
+}
+
+// (the stores of the two distance maps: nobody on the device reads them again.  SILENT_ATTN_NT makes them non-temporal -- a build
+// variant for the measurement of profiles/attention_tail, not the default)
+__device__ __forceinline__ void attn_store(float* dst, float v) {
+#ifdef SILENT_ATTN_NT
+    __builtin_nontemporal_store(v, dst);
+#else
+    *dst = v;
+#endif
+}
+
+// (2) 255 - dist * 255 of one tile of the map / the half map: a wave owns kAttnRows rows, a lane a column.  x is fixed per lane and y
+//     per wave and row, so the compiler keeps centroid_dist_px's column lookup out of the row loop and nothing is divided by W; a row
+//     is one contiguous 256-byte store per wave.  Rows come in groups of four so that four centroid loads are in flight.
+template <bool HALF>
+__device__ __forceinline__ void attn_dist_tile(const AttnTab& t, const AttnPtr& p, unsigned tile) {
+    const LevelTab& tab = HALF ? t.tab2 : t.tab1;
+    const CellTab& ct = HALF ? t.ct2 : t.ct1;
+    const TileCoord tc = locate_tile(tab, tile);
+    const int l = tc.level, H = tab.h[l], W = tab.w[l];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int y0 = tc.ty * kAttnTH + wave * kAttnRows;
+    if (y0 >= H) return;   // wave-uniform
+    const int x = tc.tx * kAttnTW + lane, xc = min(x, W - 1);
+    const float* __restrict__ c = (HALF ? p.cxy2 : p.cxy) + ((long long)tc.frame * ct.frame_cells + ct.cell_off[l]) * 2;
+    float* __restrict__ out = (HALF ? p.out2 : p.out1) + (long long)tc.frame * tab.frame_px + tab.px_off[l];
+    const int oh = ct.oh[l], ow = ct.ow[l];
+    const float ysc = ct.yscale[l], xsc = ct.xscale[l];
+#pragma unroll 1
+    for (int k0 = 0; k0 < kAttnRows; k0 += 4) {
+        if (y0 + k0 >= H) break;   // wave-uniform
+        float d[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) d[k] = centroid_dist_px(c, min(y0 + k0 + k, H - 1), xc, oh, ow, ysc, xsc);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int y = y0 + k0 + k;
+            if (y < H && x < W) attn_store(out + (long long)y * W + x, affine_px(d[k], t.inv));
+        }
+    }
+}
+
+// and, beside them (it needs nothing of theirs), boost_update_kernel + fired * 255 on a chunk of one (frame, level) cell grid
+__device__ __forceinline__ void attn_boost_chunk(const AttnTab& t, const AttnPtr& p, unsigned tile) {
+    const TileCoord tc = locate_tile(t.tabc, tile);
+    const int H = t.tabc.h[tc.level], W = t.tabc.w[tc.level], n = H * W;
+    const long long base = (long long)tc.frame * t.tabc.frame_px + t.tabc.px_off[tc.level];
+    const float* __restrict__ src = p.m + base;
+    const int C = t.bp.visualize ? 3 : 1;
+    for (int k = 0; k < 4; ++k) {
+        const int q = tc.tx * kChunk + k * 256 + threadIdx.x;
+        if (q >= n) break;
+        float f_out, e_out;
+        p.energy[base + q] = boost_update_px(src, H, W, q, p.imp[base + q], p.energy[base + q], t.bp, &f_out, &e_out);
+        const float shown = affine_px(f_out, t.x255);
+        for (int c = 0; c < C; ++c) {
+            if (p.fired) p.fired[(base + q) * C + c] = shown;
+            if (p.update) p.update[(base + q) * C + c] = e_out;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void attn_pixels_kernel(const AttnTab t, const AttnPtr p) {
+    const unsigned b = blockIdx.x;   // block-uniform branches
+    if (b < t.b1) attn_dist_tile<false>(t, p, b);
+    else if (b < t.b2) attn_dist_tile<true>(t, p, b - t.b1);
+    else attn_boost_chunk(t, p, b - t.b2);
+}
+
 }  // namespace silent

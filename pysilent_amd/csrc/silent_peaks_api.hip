@@ -605,6 +605,67 @@ int displayer_tail(silent_ctx* ctx, int L, int h, int w, int rh, int rw, int h2,
     return check_launch(ctx, who);
 }
 
+// ------------------------------------------------------------------------------------------ the attention tail of a batch
+// (silent_peaks.h, AttnTab; the planning: silent_peaks_plan.h, attention_plan)
+
+SILENT_EXPORT int silent_attention_extents(const silent_extent* levels, int n_levels, const silent_attention_params* p, silent_extent* cells,
+                                           silent_extent* half, silent_extent* cells2) try {
+    const char* who = "silent_attention_extents";
+    if (!p) return fail(nullptr, SILENT_E_INVALID, std::string(who) + ": NULL params");
+    return refuse(nullptr, who, attention_extents(levels, n_levels, p->region_h, p->region_w, p->resize_div, cells, half, cells2));
+} catch (...) {
+    return on_exception(nullptr, "silent_attention_extents");
+}
+
+SILENT_EXPORT int silent_attention_tail_dev(silent_ctx* ctx, const float* value, const silent_extent* levels, int n_levels, int n_frames,
+                                            const silent_attention_params* params, float* energy, float* centroids_out,
+                                            float* centroids2_out, float* fired_out, float* update_out, silent_stream stream) try {
+    NEED_CTX(ctx);
+    const char* who = "silent_attention_tail";
+    if (!value || !energy || !params) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer (value, energy and params are required)");
+    AttnPlan ap;
+    TRY(refuse(ctx, who, attention_plan(levels, n_levels, n_frames, params, centroids_out != nullptr, centroids2_out != nullptr, &ap)));
+    hipStream_t s = (hipStream_t)stream;
+    TRY(workspace(ctx, s, ap.ws.total));
+    char* ws = (char*)ctx->ws.p;
+    AttnPtr p;
+    p.value = value;
+    p.energy = energy;
+    p.cxy = (float*)(ws + ap.ws.cxy);
+    p.cxy2 = (float*)(ws + ap.ws.cxy2);
+    p.imp = (float*)(ws + ap.ws.imp);
+    p.m = (float*)(ws + ap.ws.m);
+    p.out1 = centroids_out;
+    p.out2 = centroids2_out;
+    p.fired = fired_out;
+    p.update = update_out;
+    hipLaunchKernelGGL(attn_cells_kernel, dim3((unsigned)((ap.n_cells + ap.n_cells2 + 255) / 256)), dim3(256), 0, s, ap.t, p);
+    hipLaunchKernelGGL(attn_pixels_kernel, dim3((unsigned)(ap.px_blocks + ap.px2_blocks + ap.cell_blocks)), dim3(256), 0, s, ap.t, p);
+    return check_launch(ctx, who);
+} catch (...) {
+    return on_exception(ctx, "silent_attention_tail_dev");
+}
+
+SILENT_EXPORT int silent_attention_tail(silent_ctx* ctx, const float* value, const silent_extent* levels, int n_levels, int n_frames,
+                                        const silent_attention_params* params, float* energy, float* centroids_out, float* centroids2_out,
+                                        float* fired_out, float* update_out) try {
+    NEED_CTX(ctx);
+    const char* who = "silent_attention_tail";
+    if (!value || !energy || !params) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer (value, energy and params are required)");
+    AttnPlan ap;   // (the sizes of the staged buffers; the _dev form plans again)
+    TRY(refuse(ctx, who, attention_plan(levels, n_levels, n_frames, params, centroids_out != nullptr, centroids2_out != nullptr, &ap)));
+    const size_t nf = (size_t)n_frames, cells = (size_t)ap.t.ct1.frame_cells * nf * 4, c = ap.t.bp.visualize ? 3 : 1;
+    HostStage hs(ctx);
+    const int v = hs.in(value, (size_t)ap.frame_px * nf * 4), e = hs.inout(energy, cells), o1 = hs.out(centroids_out, (size_t)ap.frame_px * nf * 4),
+              o2 = hs.out(centroids2_out, (size_t)ap.frame_px2 * nf * 4), f = hs.out(fired_out, cells * c), u = hs.out(update_out, cells * c);
+    return hs.run([&] {
+        return silent_attention_tail_dev(ctx, hs.dev<float>(v), levels, n_levels, n_frames, params, hs.dev<float>(e), hs.dev<float>(o1),
+                                         hs.dev<float>(o2), hs.dev<float>(f), hs.dev<float>(u), nullptr);
+    });
+} catch (...) {
+    return on_exception(ctx, "silent_attention_tail");
+}
+
 // ------------------------------------------------------------------------------------------ RGB chain + keypoints
 
 // what silent_sparse_tail_stats reads back of the call that just laid its tail out: whether it ran sparse, where its flags / counters live

@@ -6,6 +6,7 @@
 #include "silent_peaks.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -178,6 +179,124 @@ inline Refusal boost_params(const silent_boosting_params* p, BoostP* bp) {
     const double span = (double)p->exhaustion_max + (double)p->excitation_max;
     bp->normer = (float)(255.0 / span);
     bp->centerer = (float)(((double)p->excitation_max / span) * 255.0);
+    return {};
+}
+
+// ------------------------------------------------------------------------------------------ attention tail
+// (silent_attention_tail: centroids at two scales + the boosting state on a packed pyramid, silent_peaks.h AttnTab)
+// The geometry: per level the cells of the map, the extents of the nearest-neighbour half map -- (int)((float)h / resize_div), the
+// float32 division and truncation of recognition_testing.py:82-83 -- and its cells
+inline Refusal attention_extents(const silent_extent* levels, int n_levels, int rh, int rw, float resize_div, silent_extent* cells,
+                                 silent_extent* half, silent_extent* cells2) {
+    if (!levels) return {SILENT_E_INVALID, ": levels is NULL"};
+    if (n_levels < 1 || n_levels > kMaxLevels) return {SILENT_E_INVALID, ": n_levels must be in [1, SILENT_MAX_LEVELS]"};
+    if (rh < 1 || rw < 1) return {SILENT_E_INVALID, ": region extents must be >= 1"};
+    if (!(resize_div >= 1.0f) || !(resize_div <= 3.402823466e+38f)) return {SILENT_E_INVALID, ": resize_div must be finite and >= 1"};
+    for (int l = 0; l < n_levels; ++l) {
+        const long long h = levels[l].h, w = levels[l].w;
+        if (h < 1 || w < 1 || h * w > (1ll << 30)) return {SILENT_E_INVALID, ": a level extent is not positive (or above 2^30 pixels)"};
+        const silent_extent hf = {(int)((float)levels[l].h / resize_div), (int)((float)levels[l].w / resize_div)};
+        if (hf.h < 1 || hf.w < 1) return {SILENT_E_INVALID, ": a level is too small for a half extent (h or w below resize_div)"};
+        if (cells) cells[l] = silent_extent{(levels[l].h + rh - 1) / rh, (levels[l].w + rw - 1) / rw};
+        if (half) half[l] = hf;
+        if (cells2) cells2[l] = silent_extent{(hf.h + rh - 1) / rh, (hf.w + rw - 1) / rw};
+    }
+    return {};
+}
+
+// One index space of attn_pixels_kernel as a LevelTab: 2-D tiles of kAttnTW x kAttnTH pixels (tile_h > 0), or chunks of `tile_w`
+// flattened elements (tile_h == 0).  *tiles: of all frames.  (build_level_tab's layout, silent_core.hip, without a context.)
+inline void attn_level_tab(const silent_extent* ext, int n_levels, int n_frames, int tile_w, int tile_h, LevelTab* tab, long long* tiles) {
+    std::memset(tab, 0, sizeof(*tab));
+    tab->n_levels = n_levels;
+    long long px = 0, t = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        const long long h = ext[l].h, w = ext[l].w;
+        tab->h[l] = (int)h;
+        tab->w[l] = (int)w;
+        tab->px_off[l] = px;
+        tab->tile_start[l] = (int)std::min<long long>(t, 0x7fffffffll);
+        const long long tx = tile_h ? (w + tile_w - 1) / tile_w : (h * w + tile_w - 1) / tile_w;
+        const long long ty = tile_h ? (h + tile_h - 1) / tile_h : 1;
+        tab->tiles_x[l] = (int)tx;
+        t += tx * ty;
+        px += h * w;
+    }
+    tab->tile_start[n_levels] = (int)std::min<long long>(t, 0x7fffffffll);
+    tab->tiles_per_frame = (int)std::min<long long>(t, 0x7fffffffll);
+    tab->frame_px = px;
+    *tiles = t * (long long)n_frames;
+}
+
+// Byte offsets of the pieces of the tail's workspace, in workspace order: the centroids of both maps ([cells][2]), the importances
+// and importances ** energy of the map's cells -- 8 + 8 + 4 + 4 bytes per cell, every piece 256-aligned
+struct AttnLayout {
+    size_t cxy, cxy2, imp, m, total;
+};
+inline AttnLayout attention_layout(long long cells, long long cells2) {
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        const size_t off = at;
+        at += (bytes + 255) / 256 * 256;
+        return off;
+    };
+    AttnLayout k;
+    k.cxy = take((size_t)cells * 2 * sizeof(float));
+    k.cxy2 = take((size_t)cells2 * 2 * sizeof(float));
+    k.imp = take((size_t)cells * sizeof(float));
+    k.m = take((size_t)cells * sizeof(float));
+    k.total = at;
+    return k;
+}
+
+// Everything the two launches need but the pointers: the tables (AttnTab, a kernel argument), block counts, cell totals, workspace.
+// with_half = false (no centroids2_out): nothing of the half map is planned -- no cells, no blocks, no workspace.
+struct AttnPlan {
+    AttnTab t;
+    silent_extent cells[kMaxLevels], half[kMaxLevels], cells2[kMaxLevels];
+    long long n_cells, n_cells2;          // of all frames
+    long long px_blocks, px2_blocks, cell_blocks;   // attn_pixels_kernel: tiles of the map, of the half map, chunks of the map's cells
+    long long frame_px, frame_px2;
+    AttnLayout ws;
+};
+inline Refusal attention_plan(const silent_extent* levels, int n_levels, int n_frames, const silent_attention_params* p, bool with_dist,
+                              bool with_half, AttnPlan* ap) {
+    if (!p) return {SILENT_E_INVALID, ": NULL params"};
+    if (n_levels < 1 || n_levels > kMaxLevels) return {SILENT_E_INVALID, ": n_levels must be in [1, SILENT_MAX_LEVELS]"};
+    if (n_frames < 1) return {SILENT_E_INVALID, ": n_frames must be >= 1"};
+    Refusal r = attention_extents(levels, n_levels, p->region_h, p->region_w, p->resize_div, ap->cells, ap->half, ap->cells2);
+    if (r.status != SILENT_OK) return r;
+    AttnTab& t = ap->t;
+    std::memset(&t, 0, sizeof(t));
+    r = boost_params(&p->boosting, &t.bp);
+    if (r.status != SILENT_OK) return r;
+    (void)build_cell_tab(levels, n_levels, p->region_h, p->region_w, &t.ct1);       // (the region extents were checked above)
+    (void)build_cell_tab(ap->half, n_levels, p->region_h, p->region_w, &t.ct2);
+    for (int l = 0; l < n_levels; ++l) {
+        t.yscale_r[l] = (float)levels[l].h / (float)ap->half[l].h;                  // (silent_resize_nearest: float32 in / out)
+        t.xscale_r[l] = (float)levels[l].w / (float)ap->half[l].w;
+    }
+    attn_level_tab(levels, n_levels, n_frames, kAttnTW, kAttnTH, &t.tab1, &ap->px_blocks);
+    attn_level_tab(ap->half, n_levels, n_frames, kAttnTW, kAttnTH, &t.tab2, &ap->px2_blocks);
+    attn_level_tab(ap->cells, n_levels, n_frames, kChunk, 0, &t.tabc, &ap->cell_blocks);
+    ap->frame_px = t.tab1.frame_px;
+    ap->frame_px2 = t.tab2.frame_px;
+    ap->n_cells = t.ct1.frame_cells * n_frames;
+    ap->n_cells2 = with_half ? t.ct2.frame_cells * n_frames : 0;
+    if (!with_dist) ap->px_blocks = 0;
+    if (!with_half) ap->px2_blocks = 0;
+    t.b1 = (unsigned)std::min<long long>(ap->px_blocks, 0x7fffffffll);
+    t.b2 = (unsigned)std::min<long long>(ap->px_blocks + ap->px2_blocks, 0x7fffffffll);
+    t.n_frames = n_frames;
+    t.n_cells = ap->n_cells;
+    t.n_cells2 = ap->n_cells2;
+    if (ap->px_blocks + ap->px2_blocks + ap->cell_blocks > 0x7fffffffll || (ap->n_cells + ap->n_cells2 + 255) / 256 > 0x7fffffffll)
+        return {SILENT_E_INVALID, ": too many tiles for one launch"};
+    t.by255 = AffineP{1.f, 255.f, 0.f, -INFINITY, INFINITY, 0.f};                   // value / 255
+    t.imp = AffineP{255.f / 4.0f, 1.f, 0.f, 1.f, 256.f, -1.f};                      // clip(total * 255 / 4, 1, 256) - 1
+    t.inv = AffineP{-255.f, 1.f, 255.f, -INFINITY, INFINITY, 0.f};                  // 255 - dist * 255
+    t.x255 = AffineP{255.f, 1.f, 0.f, -INFINITY, INFINITY, 0.f};                    // fired * 255
+    ap->ws = attention_layout(ap->n_cells, ap->n_cells2);
     return {};
 }
 

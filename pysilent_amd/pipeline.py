@@ -127,7 +127,23 @@ class _RawBlock(object):
             pass
 
 
-class LineEndPipeline(object):
+# The keywords of the attention tail (LineEndPipeline(..., mode="rgb", attention=True, centroid_region=(3, 3), ...)) and their defaults
+ATTENTION_KEYWORDS = dict(attention=False, centroid_region=(3, 3), input_based_recovery=False, constant_recovery=True, attention_visualize=True)
+
+
+class _PipelineCall(type):
+    """The call ``LineEndPipeline(...)``: the keywords of ATTENTION_KEYWORDS are taken off the arguments and handed to the instance
+    before ``__init__`` runs, which reads them where it checks its other arguments.  ``__init__`` keeps its parameter list: that list
+    is pinned by the suite (the source keywords are its last four), and these five belong to one optional stage of the step."""
+
+    def __call__(cls, *args, **kw):
+        self = cls.__new__(cls)
+        self._attention_keywords = dict(ATTENTION_KEYWORDS, **{k: kw.pop(k) for k in ATTENTION_KEYWORDS if k in kw})
+        self.__init__(*args, **kw)
+        return self
+
+
+class LineEndPipeline(object, metaclass=_PipelineCall):
     def __init__(self, frame_hw, mode="gray", n_levels=5, scale=2.0, n_orient=4, batch=1, device=None,
                  constants=None, center_dimensions=None, clip_hi=255.0, flat_policy="ieee", pad=2,
                  max_keypoints_per_frame=None, selection=False, top_percent=0.1, keep_selection_maps=False, value_map=None,
@@ -215,6 +231,24 @@ class LineEndPipeline(object):
         # rgba16[..., 1], a window of larger frames).
         # Refused here as well: unknown names, mode "rgb", frame_dtype="float32", accumulation="float64"
         self.frame_layout = _runtime.check_frame_layout(frame_layout, mode, frame_dtype, accumulation)
+        # attention=True (mode "rgb"): after the chain every step runs the second half of the reference's graph
+        # (recognition_testing.py:77-100) on the step's value map -- centroid maps at two scales and get_boosting with a per-stream
+        # energy state -- in two launches (silent_attention_tail_dev): every frame slot of the batch is a camera stream of its own,
+        # ``energy`` its state.  centroid_region, input_based_recovery / constant_recovery and attention_visualize are the reference's
+        # centroid_region_shape[1:3], its two recovery flags and get_boosting's for_visualizing.  Refused here, before any GPU or torch
+        # work: mode "gray", value_map=False, overlap, a region extent below 1, no recovery, a level too small for a half extent
+        attention, centroid_region, input_based_recovery, constant_recovery, attention_visualize = (
+            getattr(self, "_attention_keywords", ATTENTION_KEYWORDS)[k] for k in ATTENTION_KEYWORDS)
+        self.attention = bool(attention)
+        if self.attention:
+            if mode != "rgb":
+                raise ValueError("attention=True is for mode 'rgb' (the tail reads the RGB chain's value map)")
+            if value_map is not None and not value_map:
+                raise ValueError("attention=True needs the value map: value_map=False is refused")
+            if overlap not in (False, None):
+                raise ValueError("attention=True does not support overlap (overlapped steps with the tail are not built)")
+            self._attention_params = self._checked_attention_params(frame_hw, center_dimensions, scale, n_levels, centroid_region,
+                                                                    input_based_recovery, constant_recovery, attention_visualize)
         if self.rgb_frame_dtype == "uint8":
             self.frame_dtype = "uint8"         # what step() takes: the ingest ring, the tuners' frames and the byte accounting follow it
         import torch
@@ -288,6 +322,8 @@ class LineEndPipeline(object):
             # nowhere (silent_rgb_keypoints), and BASELINE config 3 returns line_end + keypoints (+ orient) only
             self.value_map = bool(value_map) or not selection or bool(keep_selection_maps)
         self._adopt_maps(self._alloc_maps())
+        if self.attention:
+            self._alloc_attention()
         if self.keypoints:
             if regions is None:
                 regions = [(max(eh // 2, 1), max(ew // 2, 1)) for eh, ew in self.extents]
@@ -330,6 +366,98 @@ class LineEndPipeline(object):
             self.overlap = True
         elif self._overlap_auto:
             self.tune_overlap()
+
+    # -- attention=True: the tail's geometry, state and outputs ---------------------------------------------
+    @staticmethod
+    def _checked_attention_params(frame_hw, center_dimensions, scale, n_levels, centroid_region, input_based_recovery, constant_recovery,
+                                  visualize):
+        """The silent_attention_params of the constructor's keywords, checked against the pyramid's level extents (host work only:
+        the level generators and silent_attention_extents).  Every refusal names ``attention``."""
+        from .util.energy.recovery import recovery_mode
+        try:
+            rh, rw = (int(v) for v in centroid_region)
+        except (TypeError, ValueError):
+            raise ValueError("attention=True: centroid_region must be a pair (rH, rW)")
+        if rh < 1 or rw < 1:
+            raise ValueError("attention=True: the extents of centroid_region must be >= 1, got %s" % ((rh, rw),))
+        try:
+            mode = recovery_mode(input_based_recovery, constant_recovery)
+        except ValueError as e:
+            raise ValueError("attention=True: %s" % e)
+        params = _runtime.attention_params((rh, rw), recovery_mode=mode, visualize=visualize)
+        hw = (int(frame_hw[0]), int(frame_hw[1]))
+        levels = reference_levels(hw, center_dimensions, scale) if center_dimensions is not None else classic_levels(hw, scale, n_levels)
+        try:
+            _runtime.attention_extents([(l[6], l[7]) for l in levels], params)
+        except ValueError as e:
+            raise ValueError("attention=True: %s" % e)
+        return params
+
+    def _alloc_attention(self):
+        """The state (8 in every cell: boosting.py:6-7) and the four results of the tail, allocated ONCE: they are no part of a
+        placement draw (tune_placement)."""
+        torch = self.torch
+        self.attention_cells, self.attention_half, self.attention_cells2 = _runtime.attention_extents(self.extents, self._attention_params)
+        self.attention_channels = 3 if self._attention_params.boosting.visualize else 1
+        self.cells_per_frame = sum(h * w for h, w in self.attention_cells)
+        f32 = dict(dtype=torch.float32, device=self.tdev)
+        self.energy = torch.full((self.batch, self.cells_per_frame), 8.0, **f32)
+        self.centroids = torch.empty(self.batch * self.frame_px, **f32)
+        self.centroids2 = torch.empty(self.batch * sum(h * w for h, w in self.attention_half), **f32)
+        self.fired = torch.empty(self.batch * self.cells_per_frame * self.attention_channels, **f32)
+        self.update = torch.empty(self.batch * self.cells_per_frame * self.attention_channels, **f32)
+        self._attention_state = self.energy          # what run_attention advances: a scratch copy while a tuner times steps
+
+    def run_attention(self, stream=None):
+        """The tail on the step's value map (silent_attention_tail_dev): advances every slot's state by one step."""
+        p = lambda t: C.c_void_p(t.data_ptr())
+        self.ctx.check(self._lib.silent_attention_tail_dev(
+            self.ctx.handle, p(self.value), self.levels_c, self.n_levels, self.batch, C.byref(self._attention_params),
+            p(self._attention_state), p(self.centroids), p(self.centroids2), p(self.fired), p(self.update), stream or self._stream()))
+
+    def _parked_state(self):
+        """Context of a tuner's timed steps: they run the tail on a SCRATCH state, so no stream advances (bit for bit)."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def parked():
+            if not self.attention:
+                yield
+                return
+            self._attention_state = self.energy.clone()
+            try:
+                yield
+            finally:
+                self.torch.cuda.synchronize(self.tdev)
+                self._attention_state = self.energy
+        return parked()
+
+    def get_state(self):
+        """Host copy of the boosting state, [batch, cells per frame] (attention=True)."""
+        self._need_attention("get_state")
+        return self.energy.cpu().numpy()
+
+    def set_state(self, state):
+        self._need_attention("set_state")
+        state = np.ascontiguousarray(state, np.float32)
+        if tuple(state.shape) != tuple(self.energy.shape):
+            raise ValueError("state shape %s does not match [batch, cells per frame] = %s" % (state.shape, tuple(self.energy.shape)))
+        self.energy.copy_(self.torch.from_numpy(state))
+
+    def reset_state(self, slots=None):
+        """8 in every cell of the named frame slots (default: all) -- a camera that reconnects starts a new stream."""
+        self._need_attention("reset_state")
+        if slots is None:
+            self.energy.fill_(8.0)
+            return
+        for s in slots:
+            if not 0 <= int(s) < self.batch:
+                raise ValueError("reset_state: slot %d of a batch of %d" % (int(s), self.batch))
+            self.energy[int(s)].fill_(8.0)
+
+    def _need_attention(self, what):
+        if not self.attention:
+            raise ValueError("%s needs attention=True" % what)
 
     # -- the maps a step streams through: pyramid + every dense output ---------------------------------
     def _alloc_maps(self):
@@ -417,6 +545,9 @@ class LineEndPipeline(object):
         ``PackedPyramid`` views an earlier ``outputs()`` handed out keep pointing at the old buffers (alive, but no longer written)
         -- call ``outputs()`` again.  The decision is in ``placement_tuning``."""
         import time
+        if self.attention and self._attention_state is self.energy:
+            with self._parked_state():             # the timed steps run the tail on a scratch state: no stream advances
+                return self.tune_placement(frames, tries, steps, budget_s, spacer_gib, max_held_gib)
         torch = self.torch
         if frames is None:
             frames = self._synthetic_frames()
@@ -532,6 +663,8 @@ class LineEndPipeline(object):
         paths)."""
         if self.mode == "gray" and self.keypoints:
             raise ValueError("keypoints=True does not support overlap (the two-part gray step)")
+        if self.attention:
+            raise ValueError("attention=True does not support overlap (overlapped steps with the tail are not built)")
         import time
         torch = self.torch
         pending = self._placement_pending
@@ -615,7 +748,16 @@ class LineEndPipeline(object):
         if self.crop_px is not None:
             h, w = 1, self.crop_px
         outs = (1 + self.n_orient) if self.mode == "gray" else (3 + (3 if self.orient_map else 0) + (1 if self.value_map else 0))
-        return int(self._frame_bytes * h * w * fc) + 4 * 2 * self.frame_px * c + self._map_bytes * self.frame_px * outs
+        return int(self._frame_bytes * h * w * fc) + 4 * 2 * self.frame_px * c + self._map_bytes * self.frame_px * outs + self.attention_bytes_per_frame()
+
+    def attention_bytes_per_frame(self):
+        """What the tail moves per frame (0 without attention=True): the value map read once and the half map's gathers (one value
+        per half-map pixel); both distance maps written; per cell the state read twice and written once and the two cell results
+        (C channels each) written.  The 8 + 8 + 4 + 4 bytes per cell of workspace between the two launches are not counted."""
+        if not getattr(self, "attention", False):
+            return 0
+        half_px = sum(h * w for h, w in self.attention_half)
+        return 4 * (2 * self.frame_px + 2 * half_px + self.cells_per_frame * (3 + 2 * self.attention_channels))
 
     @property
     def _map_bytes(self):
@@ -694,7 +836,9 @@ class LineEndPipeline(object):
                 "(top 10 % > NMS > value), cell-max / count / scan / write keypoint kernels"
                 + (", uint8 frames read in place (1 byte per frame element)" if getattr(self, "frame_dtype", "float32") == "uint8" else "")
                 + (", read in place from a strided view" if getattr(self, "rgb_frame_layout", "packed") == "strided" else "")
-                + self._source_summary())
+                + self._source_summary()
+                + (", attention tail (attn_cells_kernel + attn_pixels_kernel: centroids at two scales, boosting state per frame slot)"
+                   if getattr(self, "attention", False) else ""))
 
     def _source_summary(self):
         """launch_summary's words on a YUV-family source: its planes and the bytes step() reads per pixel."""
@@ -1070,9 +1214,11 @@ class LineEndPipeline(object):
         self.run_pyramid(frames, s)
         if self.selection and not self.keep_selection_maps:
             self.run_filters_keypoints(s)
-            return
-        self.run_filters(s)
-        self.run_keypoints(s)
+        else:
+            self.run_filters(s)
+            self.run_keypoints(s)
+        if self.attention:
+            self.run_attention(s)
 
     # -- results as PackedPyramids over the pipeline's buffers ---------------------------------------
     def outputs(self, allow_truncated=False):
@@ -1103,6 +1249,12 @@ class LineEndPipeline(object):
                     out["peaks"] = P(self.peaks, self.extents, 3, self.batch)
                 if self.peak_value is not None:
                     out["peak_value"] = P(self.peak_value, self.extents, 1, self.batch)
+            if self.attention:
+                c = self.attention_channels
+                out["centroids"] = P(self.centroids, self.extents, 1, self.batch)
+                out["centroids2"] = P(self.centroids2, self.attention_half, 1, self.batch)
+                out["fired"] = P(self.fired, self.attention_cells, c, self.batch)
+                out["update"] = P(self.update, self.attention_cells, c, self.batch)
             self._keypoint_outputs(out, allow_truncated)
         return out
 
