@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <type_traits>
 
@@ -27,6 +28,33 @@ struct LevelTab {
 };
 
 constexpr int kChunk = 1024;  // pixels per block for the 1-D (flattened level) kernels: 256 threads x 4
+
+// Host: fills `tab` for levels of the given extents -- 2-D tiles of tile_w x tile_h pixels, or (tile_h == 0) chunks of tile_w flattened
+// pixels -- and returns the tiles of all frames.  A skipped level keeps its place in the layout and gets no tiles.  Pure: it checks
+// nothing (extents >= 1 and at most 2^30 pixels a level are the caller's to see to, and so is a count no launch takes; the int fields
+// saturate at 2^31 - 1 then).  build_level_tab (silent_core.hip) and attention_plan (silent_peaks_plan.h) are its callers.
+inline long long fill_level_tab(const silent_extent* levels, int n_levels, int n_frames, int tile_w, int tile_h, const bool* skip, LevelTab* tab) {
+    const auto sat = [](long long v) { return (int)(v < 0x7fffffffll ? v : 0x7fffffffll); };
+    memset(tab, 0, sizeof(*tab));
+    tab->n_levels = n_levels;
+    long long px = 0, tiles = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        const long long h = levels[l].h, w = levels[l].w;
+        tab->h[l] = (int)h;
+        tab->w[l] = (int)w;
+        tab->px_off[l] = px;
+        tab->tile_start[l] = sat(tiles);
+        const long long tx = tile_h ? (w + tile_w - 1) / tile_w : (h * w + tile_w - 1) / tile_w;
+        const long long ty = tile_h ? (h + tile_h - 1) / tile_h : 1;
+        tab->tiles_x[l] = (int)tx;
+        if (!(skip && skip[l])) tiles += tx * ty;
+        px += h * w;
+    }
+    tab->tile_start[n_levels] = sat(tiles);
+    tab->tiles_per_frame = sat(tiles);
+    tab->frame_px = px;
+    return tiles * (long long)n_frames;
+}
 
 struct TileCoord {
     int frame, level, ty, tx;

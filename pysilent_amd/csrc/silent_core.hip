@@ -309,35 +309,13 @@ int build_level_tab(silent_ctx* ctx, const char* who, const silent_extent* level
     if (n_levels < 1 || n_levels > kMaxLevels)
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_levels must be in [1, " + std::to_string(kMaxLevels) + "]");
     if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
-    std::memset(tab, 0, sizeof(*tab));
-    tab->n_levels = n_levels;
-    long long px = 0, tiles = 0;
     for (int l = 0; l < n_levels; ++l) {
         const long long h = levels[l].h, w = levels[l].w;
         if (h < 1 || w < 1 || h * w > (1ll << 30))
             return fail(ctx, SILENT_E_INVALID, std::string(who) + ": level " + std::to_string(l) + " extent " +
                                                    std::to_string(h) + "x" + std::to_string(w) + " is invalid");
-        tab->h[l] = (int)h;
-        tab->w[l] = (int)w;
-        tab->px_off[l] = px;
-        tab->tile_start[l] = (int)tiles;
-        long long tx, ty;
-        if (tile_h == 0) {
-            const long long chunk = tile_w > 0 ? tile_w : kChunk;
-            tx = (h * w + chunk - 1) / chunk;
-            ty = 1;
-        } else {
-            tx = (w + tile_w - 1) / tile_w;
-            ty = (h + tile_h - 1) / tile_h;
-        }
-        tab->tiles_x[l] = (int)tx;
-        if (!(skip && skip[l])) tiles += tx * ty;  // a skipped level keeps its place in the layout, gets no tiles
-        px += h * w;
     }
-    tab->tile_start[n_levels] = (int)tiles;
-    tab->tiles_per_frame = (int)tiles;
-    tab->frame_px = px;
-    const long long total = tiles * (long long)n_frames;
+    const long long total = fill_level_tab(levels, n_levels, n_frames, tile_h == 0 && tile_w <= 0 ? kChunk : tile_w, tile_h, skip, tab);
     if (total > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many tiles for one launch");
     *n_blocks = total;
     return SILENT_OK;

@@ -30,7 +30,7 @@ struct silent_displayer {
     // device
     void* slab = nullptr;
     void* d_raw = nullptr;
-    float *d_frame = nullptr, *d_pyr = nullptr, *d_value = nullptr, *d_tot1 = nullptr, *d_imp = nullptr, *d_energy = nullptr;
+    float *d_frame = nullptr, *d_pyr = nullptr, *d_value = nullptr, *d_imp = nullptr, *d_energy = nullptr;
     // pinned host: the frame, and the result slots -- two at creation (silent_displayer_step alternates between them: the results of
     // step n stay valid until step n + 2), more on demand (silent_displayer_add_slot / silent_displayer_step_slot: a caller that hands
     // the results out zero-copy steps into a slot nobody holds any more)
@@ -106,8 +106,8 @@ static int displayer_enqueue(silent_displayer* d, int slot) {
     // (:86, advances energy_values); what the reference fetches (:99-100): 255 - centroids * 255 (both), fired * 255, update --
     // fifteen launches of the per-op path (affine, centroid cells / dist, resize, boost power / update) as two (silent_peaks.h, DispTail)
     TRY(displayer_tail(c, L, d->h, d->w, d->prm.centroid_region_h, d->prm.centroid_region_w, d->hh, d->hw, &d->prm.boosting, d->d_value,
-                       nullptr, nullptr, d->d_tot1, d->d_imp, d->d_energy, out + d->out_off[1], out + d->out_off[2], out + d->out_off[3],
-                       out + d->out_off[4], d->stream, d->d_seq, d->h_flag));
+                       d->d_imp, d->d_energy, out + d->out_off[1], out + d->out_off[2], out + d->out_off[3], out + d->out_off[4], d->stream,
+                       d->d_seq, d->h_flag));
     return SILENT_OK;
 }
 
@@ -179,14 +179,14 @@ SILENT_EXPORT int silent_displayer_create(silent_ctx* ctx, const silent_displaye
         d->out_total += (outs[i] + 15) / 16 * 16;
     }
     (void)px2;
-    const size_t want[] = {d->in_bytes, (size_t)p->frame_h * p->frame_w * 12, px * 12, px * 4, cells * 4, cells * 4, cells * 4, 64};
+    const size_t want[] = {d->in_bytes, (size_t)p->frame_h * p->frame_w * 12, px * 12, px * 4, cells * 4, cells * 4, 64};
     size_t total = 0;
     for (size_t b : want) total += align_up(b);
     HIP_TRY(ctx, hipMalloc(&d->slab, total));
     char* at = (char*)d->slab;
     auto take = [&](size_t b) { char* r = at; at += align_up(b); return r; };
     d->d_raw = take(want[0]);
-    float** f[] = {&d->d_frame, &d->d_pyr, &d->d_value, &d->d_tot1, &d->d_imp, &d->d_energy};
+    float** f[] = {&d->d_frame, &d->d_pyr, &d->d_value, &d->d_imp, &d->d_energy};
     for (size_t i = 0; i < sizeof(f) / sizeof(f[0]); ++i) *f[i] = (float*)take(want[i + 1]);
     {
         char* sig = take(64);

@@ -1268,15 +1268,10 @@ struct DispTail {
     AffineP by255, imp, inv, x255;
     BoostP bp;
     const float* value;                            // [L, h, w]
-    float *g, *im2n;                               // (value / 255; resized value / 255: intermediates of the per-op path, not written here since round 6)
-    float *cxy, *cxy2, *tot1;                      // centroids of both maps [cells][2]; cell totals of the first
+    float *cxy, *cxy2;                             // centroids of both maps [cells][2]
     float *imp_out, *m;                            // importances; importances ** energy
     float *energy;                                 // [L, ch, cw] state, advanced in place
     float *out1, *out2, *out3, *update;            // 255 - dist * 255 (both maps), fired * 255, update_importances
-    // completion signal (NULL: none): disp_signal_kernel, one thread behind the last kernel, bumps *seq and stores it to *flag -- a
-    // word in pinned host memory the caller polls instead of paying a stream synchronisation (silent_displayer_step)
-    unsigned long long* seq;                       // frames completed (device)
-    unsigned long long* flag;                      // = *seq, in pinned host memory
 };
 
 // Round 6: TWO launches instead of four (each costs ~5 us on the critical path of a camera frame).
@@ -1292,7 +1287,6 @@ __global__ __launch_bounds__(256) void disp_cells_kernel(const DispTail t) {
         float tot;
         centroid_cell_of([&](int y, int x) { return affine_px(v[(long long)y * t.w + x], t.by255); }, t.h, t.w, t.y_first, t.x_first, t.rh, t.rw,
                          r / t.cw, r % t.cw, &tot, &t.cxy[gid * 2], &t.cxy[gid * 2 + 1]);
-        t.tot1[gid] = tot;
         const float imp = affine_px(tot, t.imp);
         t.imp_out[gid] = imp;
         t.m[gid] = (float)pow((double)imp, (double)t.energy[gid]);          // boost_power_kernel
@@ -1339,9 +1333,11 @@ __global__ __launch_bounds__(256) void disp_dist_boost_kernel(const DispTail t) 
     }
 }
 
-// The frame's completion word.  A kernel of its own BEHIND the last one: the kernels in front have ended, their stores (some of them
-// into pinned host memory) are visible system-wide.  (Counting finished blocks inside the last kernel, with a system-scope fence per
-// block, made that kernel wait for the link 700 times: + 60 us per frame, measured.)
+// The frame's completion word: one thread bumps *seq (frames completed, device) and stores it to *flag, a word in pinned host memory
+// the caller polls instead of paying a stream synchronisation (silent_displayer_step).  A kernel of its own BEHIND the last one: the
+// kernels in front have ended, their stores (some of them into pinned host memory) are visible system-wide.  (Counting finished
+// blocks inside the last kernel, with a system-scope fence per block, made that kernel wait for the link 700 times: + 60 us per frame,
+// measured.)
 __global__ __launch_bounds__(64) void disp_signal_kernel(unsigned long long* seq, unsigned long long* flag) {
     if (threadIdx.x == 0) {
         const unsigned long long n = *seq + 1;
@@ -1352,7 +1348,10 @@ __global__ __launch_bounds__(64) void disp_signal_kernel(unsigned long long* seq
 
 // ---- the same tail for a BATCH of packed pyramids (silent_attention_tail: every frame slot a stream of its own, every level its own
 // extents) in two launches.  DispTail above knows L canvases of ONE extent and spends a division and a modulo per pixel -- nothing on a
-// 640 x 480 frame at the launch floor, wrong at 88 Mpx a step.  Here the index spaces are LevelTabs (locate_tile): the pixels of the
+// 640 x 480 frame at the launch floor, wrong at 88 Mpx a step.  The reverse holds as geometry -- the displayer's frame is this form with
+// n_levels = 1, n_frames = L, bit for bit -- and was measured: + 6 us (640 x 480) to + 10 us (1920 x 1080) of device time per frame
+// (profiles/displayer_tail), so both forms stay; what they share on the host -- the four affine steps, the cell tables, the boosting
+// parameters -- is built in one place (silent_peaks_plan.h).  Here the index spaces are LevelTabs (locate_tile): the pixels of the
 // map and of the nearest-neighbour half map as 2-D tiles, the map's cells as chunks; per cell and per pixel the arithmetic is the
 // per-op kernels' own (affine_px, centroid_cell_of, centroid_dist_px, boost_update_px, boost_power_kernel's float64 pow), so the results
 // are those of the per-op sequence bit for bit.  Nothing but the cell tables goes through memory between the two launches: 8 + 8 + 4 + 4
@@ -1420,15 +1419,9 @@ __global__ __launch_bounds__(256) void attn_cells_kernel(const AttnTab t, const 
     else if (gid - t.n_cells < t.n_cells2) attn_cell<true>(t, p, gid - t.n_cells);
 }
 
-// (the stores of the two distance maps: nobody on the device reads them again.  SILENT_ATTN_NT makes them non-temporal -- a build
-// variant for the measurement of profiles/attention_tail, not the default)
-__device__ __forceinline__ void attn_store(float* dst, float v) {
-#ifdef SILENT_ATTN_NT
-    __builtin_nontemporal_store(v, dst);
-#else
-    *dst = v;
-#endif
-}
+// (the stores of the two distance maps.  Through a pointer that is not __restrict__: written into `out` below directly, the row loop
+// compiles to other instructions than the measured ones)
+__device__ __forceinline__ void attn_store(float* dst, float v) { *dst = v; }
 
 // (2) 255 - dist * 255 of one tile of the map / the half map: a wave owns kAttnRows rows, a lane a column.  x is fixed per lane and y
 //     per wave and row, so the compiler keeps centroid_dist_px's column lookup out of the row loop and nothing is divided by W; a row

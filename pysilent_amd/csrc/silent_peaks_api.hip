@@ -568,10 +568,10 @@ SILENT_EXPORT int silent_resize_nearest_dev(silent_ctx* ctx, const float* in, co
 
 // ------------------------------------------------------------------------------------------ the displayer's fused tail
 // (silent_displayer_api.hip) value [L, h, w] -> the four small results + the advanced state, in two launches (silent_peaks.h, DispTail);
-// g / im2n: unused since round 6 (value / 255 and its resize are computed on the fly), may be NULL
+// seq / flag: the frame's completion signal, one launch behind them (NULL: none)
 int displayer_tail(silent_ctx* ctx, int L, int h, int w, int rh, int rw, int h2, int w2, const silent_boosting_params* boost, const float* value,
-                   float* g, float* im2n, float* tot1, float* imp, float* energy, float* out1, float* out2, float* out3, float* update,
-                   hipStream_t s, unsigned long long* seq, unsigned long long* flag) {
+                   float* imp, float* energy, float* out1, float* out2, float* out3, float* update, hipStream_t s, unsigned long long* seq,
+                   unsigned long long* flag) {
     const char* who = "silent_displayer_step";
     DispTail t;
     std::memset(&t, 0, sizeof(t));
@@ -586,18 +586,14 @@ int displayer_tail(silent_ctx* ctx, int L, int h, int w, int rh, int rw, int h2,
     t.yscale_c = c1.yscale[0]; t.xscale_c = c1.xscale[0]; t.yscale_c2 = c2.yscale[0]; t.xscale_c2 = c2.xscale[0];
     t.yscale_r = (float)h / (float)h2;      // (silent_resize_nearest_dev: float32 in / out)
     t.xscale_r = (float)w / (float)w2;
-    t.by255 = AffineP{1.f, 255.f, 0.f, -INFINITY, INFINITY, 0.f};
-    t.imp = AffineP{255.f / 4.0f, 1.f, 0.f, 1.f, 256.f, -1.f};
-    t.inv = AffineP{-255.f, 1.f, 255.f, -INFINITY, INFINITY, 0.f};
-    t.x255 = AffineP{255.f, 1.f, 0.f, -INFINITY, INFINITY, 0.f};
+    tail_affines(&t);
     const long long px = (long long)L * h * w, px2 = (long long)L * h2 * w2, cells = (long long)L * t.ch * t.cw, cells2 = (long long)L * t.ch2 * t.cw2;
     TRY(workspace(ctx, s, (size_t)(cells * 2 + cells2 * 2 + cells) * sizeof(float)));
     t.cxy = (float*)ctx->ws.p;
     t.cxy2 = t.cxy + cells * 2;
     t.m = t.cxy2 + cells2 * 2;
-    t.value = value; t.g = g; t.im2n = im2n; t.tot1 = tot1; t.imp_out = imp; t.energy = energy;
+    t.value = value; t.imp_out = imp; t.energy = energy;
     t.out1 = out1; t.out2 = out2; t.out3 = out3; t.update = update;
-    t.seq = seq; t.flag = flag;
     auto grid = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
     hipLaunchKernelGGL(disp_cells_kernel, grid(cells + cells2), dim3(256), 0, s, t);
     hipLaunchKernelGGL(disp_dist_boost_kernel, grid(px + px2 + cells), dim3(256), 0, s, t);

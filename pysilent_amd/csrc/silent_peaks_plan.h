@@ -204,28 +204,13 @@ inline Refusal attention_extents(const silent_extent* levels, int n_levels, int 
     return {};
 }
 
-// One index space of attn_pixels_kernel as a LevelTab: 2-D tiles of kAttnTW x kAttnTH pixels (tile_h > 0), or chunks of `tile_w`
-// flattened elements (tile_h == 0).  *tiles: of all frames.  (build_level_tab's layout, silent_core.hip, without a context.)
-inline void attn_level_tab(const silent_extent* ext, int n_levels, int n_frames, int tile_w, int tile_h, LevelTab* tab, long long* tiles) {
-    std::memset(tab, 0, sizeof(*tab));
-    tab->n_levels = n_levels;
-    long long px = 0, t = 0;
-    for (int l = 0; l < n_levels; ++l) {
-        const long long h = ext[l].h, w = ext[l].w;
-        tab->h[l] = (int)h;
-        tab->w[l] = (int)w;
-        tab->px_off[l] = px;
-        tab->tile_start[l] = (int)std::min<long long>(t, 0x7fffffffll);
-        const long long tx = tile_h ? (w + tile_w - 1) / tile_w : (h * w + tile_w - 1) / tile_w;
-        const long long ty = tile_h ? (h + tile_h - 1) / tile_h : 1;
-        tab->tiles_x[l] = (int)tx;
-        t += tx * ty;
-        px += h * w;
-    }
-    tab->tile_start[n_levels] = (int)std::min<long long>(t, 0x7fffffffll);
-    tab->tiles_per_frame = (int)std::min<long long>(t, 0x7fffffffll);
-    tab->frame_px = px;
-    *tiles = t * (long long)n_frames;
+// The four affine steps of the tail (recognition_testing.py:79-81, :99), the same for its two forms: T is AttnTab or DispTail
+template <class T>
+inline void tail_affines(T* t) {
+    t->by255 = AffineP{1.f, 255.f, 0.f, -INFINITY, INFINITY, 0.f};                  // value / 255
+    t->imp = AffineP{255.f / 4.0f, 1.f, 0.f, 1.f, 256.f, -1.f};                     // clip(total * 255 / 4, 1, 256) - 1
+    t->inv = AffineP{-255.f, 1.f, 255.f, -INFINITY, INFINITY, 0.f};                 // 255 - dist * 255
+    t->x255 = AffineP{255.f, 1.f, 0.f, -INFINITY, INFINITY, 0.f};                   // fired * 255
 }
 
 // Byte offsets of the pieces of the tail's workspace, in workspace order: the centroids of both maps ([cells][2]), the importances
@@ -276,9 +261,10 @@ inline Refusal attention_plan(const silent_extent* levels, int n_levels, int n_f
         t.yscale_r[l] = (float)levels[l].h / (float)ap->half[l].h;                  // (silent_resize_nearest: float32 in / out)
         t.xscale_r[l] = (float)levels[l].w / (float)ap->half[l].w;
     }
-    attn_level_tab(levels, n_levels, n_frames, kAttnTW, kAttnTH, &t.tab1, &ap->px_blocks);
-    attn_level_tab(ap->half, n_levels, n_frames, kAttnTW, kAttnTH, &t.tab2, &ap->px2_blocks);
-    attn_level_tab(ap->cells, n_levels, n_frames, kChunk, 0, &t.tabc, &ap->cell_blocks);
+    // the three index spaces of attn_pixels_kernel: tiles of kAttnTW x kAttnTH pixels of both maps, chunks of kChunk cells
+    ap->px_blocks = fill_level_tab(levels, n_levels, n_frames, kAttnTW, kAttnTH, nullptr, &t.tab1);
+    ap->px2_blocks = fill_level_tab(ap->half, n_levels, n_frames, kAttnTW, kAttnTH, nullptr, &t.tab2);
+    ap->cell_blocks = fill_level_tab(ap->cells, n_levels, n_frames, kChunk, 0, nullptr, &t.tabc);
     ap->frame_px = t.tab1.frame_px;
     ap->frame_px2 = t.tab2.frame_px;
     ap->n_cells = t.ct1.frame_cells * n_frames;
@@ -292,10 +278,7 @@ inline Refusal attention_plan(const silent_extent* levels, int n_levels, int n_f
     t.n_cells2 = ap->n_cells2;
     if (ap->px_blocks + ap->px2_blocks + ap->cell_blocks > 0x7fffffffll || (ap->n_cells + ap->n_cells2 + 255) / 256 > 0x7fffffffll)
         return {SILENT_E_INVALID, ": too many tiles for one launch"};
-    t.by255 = AffineP{1.f, 255.f, 0.f, -INFINITY, INFINITY, 0.f};                   // value / 255
-    t.imp = AffineP{255.f / 4.0f, 1.f, 0.f, 1.f, 256.f, -1.f};                      // clip(total * 255 / 4, 1, 256) - 1
-    t.inv = AffineP{-255.f, 1.f, 255.f, -INFINITY, INFINITY, 0.f};                  // 255 - dist * 255
-    t.x255 = AffineP{255.f, 1.f, 0.f, -INFINITY, INFINITY, 0.f};                    // fired * 255
+    tail_affines(&t);
     ap->ws = attention_layout(ap->n_cells, ap->n_cells2);
     return {};
 }

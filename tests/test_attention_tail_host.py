@@ -16,7 +16,8 @@ from conftest import ROOT
 needs_hipcc = pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
 MAX_LEVELS = 16
 DIV = np.float32(math.e ** .5)            # recognition_testing.py:82-83
-GEOMETRIES = {"A": [(16, 24)] * 2, "B": [(37, 53), (19, 27), (10, 14), (5, 7), (2, 2)], "C": [(4, 300), (3, 65), (3, 64), (3, 63), (65, 2)]}
+GEOMETRIES = {"A": [(16, 24)] * 2, "B": [(37, 53), (19, 27), (10, 14), (5, 7), (2, 2)], "C": [(4, 300), (3, 65), (3, 64), (3, 63), (65, 2)],
+              "D": [(64, 96)], "E": [(17, 68)]}          # D, E: one level -- with n_frames > 1 the shape of a displayer frame
 REGIONS = [(3, 3), (2, 3), (4, 5), (7, 7)]
 CONFIG3 = [(1080, 1920), (540, 960), (270, 480), (135, 240), (68, 120), (34, 60)]      # 1080p, six levels at scale 2
 REFERENCE = [(192, 288)] * 4
@@ -121,7 +122,19 @@ def test_the_extents_are_the_restated_geometry(name, region):
 
 
 def test_the_geometries_are_the_ones_asked_for():
-    """A: SAME padding on both sides at 3 x 3, half map 9 x 14; B: down to a 1 x 1 half map; (7, 7): a stride above a half map."""
+    """A: SAME padding on both sides at 3 x 3, half map 9 x 14; B: down to a 1 x 1 half map; (7, 7): a stride above a half map.
+    D and E are single levels, the shape of a displayer frame.  D (64, 96) is the canvas of the displayer tests: exactly one row of 64 x 64
+    tiles, half map 38 x 58.  E (17, 68): the width is just past one 64-column tile; row 16 is the only row of a tile's second wave and
+    the first of a group of four rows; half map 10 x 41, and at region (7, 7) -- the worst case -- cells 3 x 10 and cells2 2 x 6.  Every
+    half extent of both is >= 1 at every region in REGIONS, so the per-op sequence (resize_nearest, centroids) accepts them all and
+    no GPU case of tests/test_gpu_attention_tail.py is skipped."""
+    d, e = geometry(GEOMETRIES["D"], (7, 7))[0], geometry(GEOMETRIES["E"], (7, 7))[0]
+    assert d["half"] == (38, 58) and -(-64 // 64) == 1 and -(-96 // 64) == 2
+    assert e["half"] == (10, 41) and e["cells"] == (3, 10) and e["cells2"] == (2, 6) and -(-68 // 64) == 2 and 17 % 16 == 1
+    for name in "DE":
+        for region in REGIONS:
+            for g in geometry(GEOMETRIES[name], region):
+                assert min(g["half"]) >= 1 and min(g["cells"]) >= 1 and min(g["cells2"]) >= 1, (name, region, g)
     a, b = geometry(GEOMETRIES["A"], (3, 3)), geometry(GEOMETRIES["B"], (3, 3))
     assert a[0]["half"] == (9, 14) and a[0]["first"] == (-1, 0) and a[0]["cells"] == (6, 8)
     assert b[-1]["half"] == (1, 1) and b[-1]["cells2"] == (1, 1)
