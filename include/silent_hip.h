@@ -934,6 +934,40 @@ int silent_rgb_line_end_dev(silent_ctx* ctx, const float* pyr, const silent_exte
                             int n_frames, const silent_rgb_chain_params* params, float* orient_out,
                             float* line_end_out, float* value_out, silent_stream stream);
 
+/* FLOAT16 STORAGE of the orient and line_end maps: silent_rgb_line_end[_dev] with orient_out / line_end_out as IEEE binary16
+ * (uint16_t bit patterns, 2-byte aligned, the same NHWC [.., h, w, 3] layout at 6 bytes per pixel).  All arithmetic is the float32
+ * call's: the same kernel instantiation and tile height as silent_rgb_line_end with the same arguments and context tuning, and every
+ * stored element is the float32 call's element rounded ONCE at the store -- to nearest even, overflow to +-inf (a clip_hi above 65504
+ * can reach it), a NaN stays a NaN (payload unspecified), binary16 subnormals are kept.  value_out stays float32 and is bit-identical
+ * to the float32 call's (it is taken from the unrounded line_end).  Half the bytes written and kept for the two colour maps.
+ * RGB knob bits 4 (one-pixel kernel) and 7 (16-byte stores) are float32 store forms and are not honoured.  SILENT_E_UNSUPPORTED where
+ * the float32 call would leave the pair kernel: a blur that is not channel-uniform (the stage-per-launch route), or a level too large
+ * for that kernel's addressing.  Every other refusal is silent_rgb_line_end's. */
+int silent_rgb_line_end_h(silent_ctx* ctx, const float* pyr, const silent_extent* levels, int n_levels, int n_frames,
+                          const silent_rgb_chain_params* params, uint16_t* orient_out, uint16_t* line_end_out,
+                          float* value_out);
+int silent_rgb_line_end_h_dev(silent_ctx* ctx, const float* pyr, const silent_extent* levels, int n_levels,
+                              int n_frames, const silent_rgb_chain_params* params, uint16_t* orient_out,
+                              uint16_t* line_end_out, float* value_out, silent_stream stream);
+
+/* silent_rgb_keypoints[_dev] with float16 orient / line_end maps:
+ * = silent_rgb_line_end_h, then silent_select_keypoints(color = (float)line_end_h, value = the FLOAT32 value map, channels = 3):
+ * idx, counts and peak_value_out equal that pair of calls bit for bit; the maps are silent_rgb_line_end_h's.  line_end_out is
+ * required in both forms (the tail reads it; it widens each element where it loads it).  The threshold (the value map's per-level
+ * extrema) and the set of pixels that pass it come from the float32 value map and are those of silent_rgb_keypoints.  The
+ * keypoints themselves can differ from silent_rgb_keypoints' where rounding makes or breaks a TIE: the 3x3 non-maximum suppression
+ * compares a rounded colour with the rounded maximum of its neighbourhood, and a region's keypoints are the pixels that reach its
+ * rounded maximum -- two float32 values that differ below binary16's resolution become equal.  Refusals as silent_rgb_keypoints,
+ * and SILENT_E_UNSUPPORTED as silent_rgb_line_end_h. */
+int silent_rgb_keypoints_h(silent_ctx* ctx, const float* pyr, const silent_extent* levels, int n_levels, int n_frames,
+                           const silent_rgb_chain_params* params, double top_percent, const silent_extent* regions,
+                           uint16_t* orient_out, uint16_t* line_end_out, float* value_out, float* peak_value_out, int64_t* idx,
+                           size_t cap_per_frame, int64_t* counts);
+int silent_rgb_keypoints_h_dev(silent_ctx* ctx, const float* pyr, const silent_extent* levels, int n_levels, int n_frames,
+                               const silent_rgb_chain_params* params, double top_percent, const silent_extent* regions,
+                               uint16_t* orient_out, uint16_t* line_end_out, float* value_out, float* peak_value_out, int64_t* idx,
+                               size_t cap_per_frame, int64_t* counts, silent_stream stream);
+
 /* ---------------------------------------------------------------------------- one camera frame, one call
  * LineEndDisplayer.callback + run, slam_recognition/recognition_testing.py:106-144: a frame in host memory ->
  * np.asarray(frame, float32) (:141) -> zoom.from_image(frame, 3, output_size, zoom_ratio) (:142) -> the graph of compile()

@@ -246,6 +246,8 @@ _SIGNATURES = {
     "silent_rgb_chain_structure": [C.POINTER(RgbChainParams), C.POINTER(C.c_uint), C.POINTER(C.c_uint)],
     "silent_rgb_keypoints": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _d, _ep, _fp, _fp, _fp, _fp, _vp, _sz, _vp],
     "silent_rgb_keypoints_dev": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _d, _ep, _fp, _fp, _fp, _fp, _vp, _sz, _vp, _vp],
+    "silent_rgb_keypoints_h": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _d, _ep, _hp, _hp, _fp, _fp, _vp, _sz, _vp],
+    "silent_rgb_keypoints_h_dev": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _d, _ep, _hp, _hp, _fp, _fp, _vp, _sz, _vp, _vp],
     "silent_gray_keypoints": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp],
     "silent_gray_keypoints_dev": [_vp, _vp, _fp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp, _vp],
     "silent_gray_keypoints_u8": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _fp, _fp, _i, _i, _d, _ep, _fp, _fp, _vp, _sz, _vp],
@@ -262,6 +264,8 @@ _SIGNATURES = {
     "silent_rgb_chain_stream": [C.POINTER(RgbChainParams), C.c_uint, _fp, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "silent_rgb_line_end": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _fp, _fp, _fp],
     "silent_rgb_line_end_dev": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _fp, _fp, _fp, _vp],
+    "silent_rgb_line_end_h": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _hp, _hp, _fp],
+    "silent_rgb_line_end_h_dev": [_vp, _fp, _ep, _i, _i, C.POINTER(RgbChainParams), _hp, _hp, _fp, _vp],
     "silent_displayer_create": [_vp, C.POINTER(DisplayerParams), C.POINTER(PyrLevel), _i, C.POINTER(_vp)],
     "silent_displayer_destroy": [_vp],
     "silent_displayer_shape": [_vp, C.POINTER(C.c_int32), C.POINTER(_sz)],

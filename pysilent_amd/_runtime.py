@@ -711,9 +711,13 @@ def resize_nearest(x, out_extents):
 
 
 def rgb_line_end(x, kernels, regulation_value=1.0, regulation_root=0.1, flat_policy="ieee", clip_hi=255.0, pad=2,
-                 want=("orient", "line_end", "value")):
+                 want=("orient", "line_end", "value"), storage="float32"):
     """The reference graph recognition_testing.py:69-77 on 3-channel levels.  ``kernels``: dict with
-    rgc, rgby, stripe, end ([3,3,3,3]) and blur ([7,7,3,3]).  Returns dict of the requested outputs."""
+    rgc, rgby, stripe, end ([3,3,3,3]) and blur ([7,7,3,3]).  Returns dict of the requested outputs.  ``storage="float16"``:
+    orient and line_end come back as float16 maps (silent_rgb_line_end_h: the float32 results rounded once at the store)."""
+    if storage not in STORAGES:
+        raise ValueError("storage must be 'float32' or 'float16', got %r" % (storage,))
+    half = storage == "float16"
     op = _Operand(x, channels=3)
     ks = {}
     for name, shape in (("rgc", (3, 3, 3, 3)), ("rgby", (3, 3, 3, 3)), ("stripe", (3, 3, 3, 3)),
@@ -728,12 +732,20 @@ def rgb_line_end(x, kernels, regulation_value=1.0, regulation_root=0.1, flat_pol
                                  {"ieee": _lib.FLAT_IEEE, "zero": _lib.FLAT_ZERO}[flat_policy], float(clip_hi), int(pad))
     outs, ptrs = {}, {}
     for name, ch in (("orient", 3), ("line_end", 3), ("value", 1)):
-        if name in want:
+        if name in want and half and ch == 3:
+            outs[name], ptrs[name] = op.empty(op.n_frames * op.frame_px * ch, np.float16)
+            ptrs[name] = _lib.half_ptr(ptrs[name].value)
+        elif name in want:
             outs[name], ptrs[name] = op.alloc(ch)
         else:
             ptrs[name] = None
-    op.call("rgb_line_end", op.ptr, *op.geom(), C.byref(params), ptrs["orient"], ptrs["line_end"], ptrs["value"])
-    return {n: op.wrap(o, 1 if n == "value" else 3) for n, o in outs.items()}
+    op.call("rgb_line_end_h" if half else "rgb_line_end", op.ptr, *op.geom(), C.byref(params), ptrs["orient"], ptrs["line_end"], ptrs["value"])
+
+    def wrap(n, o):
+        if half and n != "value":
+            return PackedPyramid(o, op.extents, 3, op.n_frames, dtype=np.float16) if op.packed else o.reshape(op.n_frames, *op.extents[0], 3)
+        return op.wrap(o, 1 if n == "value" else 3)
+    return {n: wrap(n, o) for n, o in outs.items()}
 
 
 # ----------------------------------------------------------------------------- pyramid plans
@@ -920,6 +932,20 @@ def check_storage(storage, mode="gray", accumulation="float32", keypoints=False)
         if keypoints:
             raise ValueError("storage='float16' does not combine with keypoints=True (the keypoint tail reads the end map as float32)")
     return storage
+
+
+def check_rgb_storage(rgb_storage, mode="rgb", keep_selection_maps=False):
+    """The rgb_storage argument of LineEndPipeline: "float32" (default) or "float16" (the orient and line_end maps of the RGB chain
+    stored as IEEE binary16, silent_rgb_line_end_h / silent_rgb_keypoints_h).  The name is checked first; then mode "gray" (its
+    float16 option is storage="float16") and keep_selection_maps=True (the top / peaks maps come from the float32 per-op kernels)."""
+    if rgb_storage not in STORAGES:
+        raise ValueError("rgb_storage must be 'float32' or 'float16', got %r" % (rgb_storage,))
+    if rgb_storage == "float16":
+        if mode != "rgb":
+            raise ValueError("rgb_storage='float16' is for mode 'rgb' (the gray pass takes storage='float16')")
+        if keep_selection_maps:
+            raise ValueError("rgb_storage='float16' does not combine with keep_selection_maps=True (the top / peaks maps come from the float32 per-op kernels)")
+    return rgb_storage
 
 
 FRAME_DTYPES = ("float32", "uint8", "uint16")

@@ -163,14 +163,17 @@ int check_levels(silent_ctx* ctx, const char* who, const silent_extent* levels, 
 int launch_regulate_sum(silent_ctx* ctx, const float* in, const silent_extent* levels, int n_levels, int n_frames, const float* blur_hwio,
                         float regulation_value, float regulation_root, int flat_policy, float* out, hipStream_t s);
 // (silent_rgb_api.hip) which fused kernel a chain launch over these levels uses and its tile height (output rows per tile)
-int rgb_chain_tile_height(const silent_ctx* ctx, const silent_extent* levels, int n_levels, int n_frames, bool* pair, bool with_extrema);
+// (half16: for the float16-storage calls, which ignore RGB knob bit 4 -- the one-pixel kernel has no float16 form)
+int rgb_chain_tile_height(const silent_ctx* ctx, const silent_extent* levels, int n_levels, int n_frames, bool* pair, bool with_extrema,
+                          bool half16 = false);
 // (silent_rgb_api.hip) mm: optional per-level extrema slots (already initialised); *mm_done tells whether the launch filled them
 // (only the pair kernel's two-group instantiation does -- everything else leaves them to level_maxmin_kernel); st / sum /
-// nan_flags: the value summary of the sparse keypoint tail (silent_peaks_api.hip)
+// nan_flags: the value summary of the sparse keypoint tail (silent_peaks_api.hip); half16: orient_out / line_end_out are float16
+// maps (silent_rgb_line_end_h: the pair kernel's ST = rgb_half instantiations), otherwise float32 ones
 int rgb_chain_launch(silent_ctx* ctx, const char* who, const float* pyr, const silent_extent* levels, int n_levels, int n_frames,
-                     const silent_rgb_chain_params* p, float* orient_out, float* line_end_out, float* value_out, unsigned* mm,
+                     const silent_rgb_chain_params* p, void* orient_out, void* line_end_out, float* value_out, unsigned* mm,
                      bool* mm_done, silent_stream stream, const silent::SumTab* st = nullptr, float* sum = nullptr,
-                     int* nan_flags = nullptr);
+                     int* nan_flags = nullptr, bool half16 = false);
 // (silent_peaks_api.hip) the widening cast of a rectangle of an interleaved frame (the displayer: the part of the frame its pyramid reads)
 int cast_rect_launch(silent_ctx* ctx, const void* in, int in_dtype, int W, int C, int y0, int x0, int h, int w, float* out, hipStream_t s);
 // (silent_peaks_api.hip) the tail of the displayer's graph after the chain, fused into two launches (silent_peaks.h, DispTail); seq / flag: the completion signal

@@ -317,8 +317,10 @@ constexpr int kSelCols = 60, kSelTW = 4 * kSelCols, kSelTH = 32;
 // PAD: `color` is the UNPADDED map and every colour value read is multiplied by pad_inwards' 0 / 1 mask first (pad pixels at each
 // border of the level; silent_gray_keypoints, whose end map stays unpadded) -- the same operation as pad_inwards_kernel, so the
 // results are those of the padded map.
-template <int C, bool CELLS, bool PAD = false>
-__device__ __forceinline__ void select_peaks_tile(const float* __restrict__ color, const float* __restrict__ value,
+// CT: the element type of `color` -- float, or _Float16 (silent_rgb_keypoints_h: the float16 line_end map, widened at the load; every
+// operation after the load is the float32 one, so the results are those of the widened map).
+template <int C, bool CELLS, bool PAD = false, typename CT = float>
+__device__ __forceinline__ void select_peaks_tile(const CT* __restrict__ color, const float* __restrict__ value,
                                                   float* __restrict__ top_out, float* __restrict__ peaks_out,
                                                   float* __restrict__ pv_out, const LevelTab& tab, float one_minus_p, float p_f,
                                                   const unsigned* __restrict__ mm, const RegionTab& rt, unsigned* __restrict__ cells,
@@ -381,7 +383,7 @@ __device__ __forceinline__ void select_peaks_tile(const float* __restrict__ colo
             const int y = y0 - 1 + i0 + j;
             const long long px = base_px + (long long)min(max(y, 0), H - 1) * W + xc;
 #pragma unroll
-            for (int c = 0; c < C; ++c) col[j][c] = color[px * C + c];
+            for (int c = 0; c < C; ++c) col[j][c] = (float)color[px * C + c];
             if constexpr (PAD) {
                 const int yc = min(max(y, 0), H - 1);
                 const float pm = (yc >= pad && yc < H - pad && xc >= pad && xc < W - pad) ? 1.0f : 0.0f;
@@ -457,8 +459,8 @@ __device__ __forceinline__ void select_peaks_tile(const float* __restrict__ colo
 }
 
 // n_tiles: tiles of `tab` (the sparse tail launches fewer blocks than that: for_live_tiles)
-template <int C, bool CELLS, bool PAD = false>
-__global__ __launch_bounds__(256) void select_peaks_kernel(const float* __restrict__ color,
+template <int C, bool CELLS, bool PAD = false, typename CT = float>
+__global__ __launch_bounds__(256) void select_peaks_kernel(const CT* __restrict__ color,
                                                            const float* __restrict__ value,
                                                            float* __restrict__ top_out, float* __restrict__ peaks_out,
                                                            float* __restrict__ pv_out, const LevelTab tab,
@@ -473,7 +475,7 @@ __global__ __launch_bounds__(256) void select_peaks_kernel(const float* __restri
             return dense_flags[tc.frame * tab.n_levels + tc.level] == kTailDense;
         },
         [&](unsigned t) {
-            select_peaks_tile<C, CELLS, PAD>(color, value, top_out, peaks_out, pv_out, tab, one_minus_p, p_f, mm, rt, cells, dense_flags, t,
+            select_peaks_tile<C, CELLS, PAD, CT>(color, value, top_out, peaks_out, pv_out, tab, one_minus_p, p_f, mm, rt, cells, dense_flags, t,
                                              pad);
         });
 }
@@ -759,15 +761,17 @@ struct Candidate {
 // (max_pool SAME ignores such taps).  The address is clamped and the load unconditional: the 9 taps of a passer are requested
 // together, not one dependent round trip after the other.
 // C channels; PAD: the colour values are multiplied by pad_inwards' mask first (select_peaks_tile).
-template <int C, bool PAD = false>
-__device__ __forceinline__ void sparse_top(const float* __restrict__ lev, int H, int W, int y, int x, float thr, float (&t)[C],
-                                           bool* passer = nullptr, int pad = 0) {
+// CT = _Float16 (select_peaks_tile): the colours are widened at the load and the value that is compared with the threshold is READ
+// from the float32 value map's level `vlev` -- the rounded colours do not give it back (silent_rgb_keypoints_h).
+template <int C, bool PAD = false, typename CT = float>
+__device__ __forceinline__ void sparse_top(const CT* __restrict__ lev, int H, int W, int y, int x, float thr, float (&t)[C],
+                                           bool* passer = nullptr, int pad = 0, const float* __restrict__ vlev = nullptr) {
     const bool inside = y >= 0 && y < H && x >= 0 && x < W;
     const int yc = min(max(y, 0), H - 1), xc = min(max(x, 0), W - 1);
-    const float* __restrict__ px = lev + ((long long)yc * W + xc) * C;
+    const CT* __restrict__ px = lev + ((long long)yc * W + xc) * C;
     float c[C];
 #pragma unroll
-    for (int k = 0; k < C; ++k) c[k] = px[k];
+    for (int k = 0; k < C; ++k) c[k] = (float)px[k];
     if constexpr (PAD) {
         const float pm = (yc >= pad && yc < H - pad && xc >= pad && xc < W - pad) ? 1.0f : 0.0f;
 #pragma unroll
@@ -777,6 +781,7 @@ __device__ __forceinline__ void sparse_top(const float* __restrict__ lev, int H,
 #pragma unroll
     for (int k = 1; k < C; ++k) v = __fadd_rn(v, c[k]);
     v = __fmul_rn(v, 1.0f / (float)C);
+    if constexpr (!std::is_same<CT, float>::value) v = vlev[(long long)yc * W + xc];
     const float m = v >= thr ? 1.0f : 0.0f;
     if (passer) *passer = inside && v >= thr;
 #pragma unroll
@@ -786,12 +791,13 @@ __device__ __forceinline__ void sparse_top(const float* __restrict__ lev, int H,
 // grid: x = 256-entry chunks of one frame's summary, y = frame.  A lane looks at one entry; the entries that reach their level's
 // threshold are then handled one after the other by the WHOLE wave (lane i takes pixel i of the entry's 2 x kSumRows pixels),
 // so that a group costs two memory round trips instead of 32 dependent ones.
-template <int C, bool PAD = false>
-__global__ __launch_bounds__(256) void sparse_select_kernel(const float* __restrict__ color, const LevelTab tab, const SumTab st,
+template <int C, bool PAD = false, typename CT = float>
+__global__ __launch_bounds__(256) void sparse_select_kernel(const CT* __restrict__ color, const LevelTab tab, const SumTab st,
                                                             const float* __restrict__ sum, int n_frames, float one_minus_p,
                                                             float p_f, const unsigned* __restrict__ mm, const RegionTab rt,
                                                             unsigned* __restrict__ cells, Candidate* __restrict__ cand,
-                                                            int* __restrict__ cand_n, int pad = 0) {
+                                                            int* __restrict__ cand_n, int pad = 0,
+                                                            const float* __restrict__ value = nullptr /* CT = _Float16: the float32 value map */) {
     static_assert(2 * kSumRows <= 64, "one lane per pixel of a group");
     const int frame = blockIdx.y;
     const int e = (int)(blockIdx.x * 256 + threadIdx.x);   // (entries per frame < 2^31: host-checked)
@@ -817,11 +823,12 @@ __global__ __launch_bounds__(256) void sparse_select_kernel(const float* __restr
         const int ty = gy / st.gpt, k = gy - ty * st.gpt;
         const int r0 = ty * st.th + k * kSumRows;
         const int r1 = min(min(r0 + kSumRows, (ty + 1) * st.th), H);
-        const float* __restrict__ lev = color + ((long long)frame * tab.frame_px + tab.px_off[gl]) * C;
+        const CT* __restrict__ lev = color + ((long long)frame * tab.frame_px + tab.px_off[gl]) * C;
+        const float* __restrict__ vlev = value + ((long long)frame * tab.frame_px + tab.px_off[gl]);   // (read by the CT = _Float16 form only)
         const int y = r0 + (lane >> 1), x = 2 * xp + (lane & 1);
         float tc_[C];
         bool passer = false;
-        sparse_top<C, PAD>(lev, H, W, min(y, H - 1), x, gthr, tc_, &passer, pad);
+        sparse_top<C, PAD, CT>(lev, H, W, min(y, H - 1), x, gthr, tc_, &passer, pad, vlev);
         passer = passer && lane < 2 * kSumRows && y < r1;
         if (!passer) continue;   // (no wave-level operation below)
         float mx[C];
@@ -829,7 +836,7 @@ __global__ __launch_bounds__(256) void sparse_select_kernel(const float* __restr
         for (int c = 0; c < C; ++c) mx[c] = kPoolLowest;
         float t[9][C];
 #pragma unroll
-        for (int j = 0; j < 9; ++j) sparse_top<C, PAD>(lev, H, W, y + j / 3 - 1, x + j % 3 - 1, gthr, t[j], nullptr, pad);
+        for (int j = 0; j < 9; ++j) sparse_top<C, PAD, CT>(lev, H, W, y + j / 3 - 1, x + j % 3 - 1, gthr, t[j], nullptr, pad, vlev);
 #pragma unroll
         for (int j = 0; j < 9; ++j)
 #pragma unroll

@@ -310,18 +310,24 @@ struct SelectPlan : RegionPlan {   // (ctab also serves the reduction pass of th
     unsigned* mm;   // [n_frames][n_levels][2] ordered-uint extrema, at the head of the context workspace
     int nmm;
     SumTab st;      // sparse tail: geometry of the chain kernel's value summary (frame_entries = 0: none)
+    float* value_ws = nullptr;   // a float32 value map behind the extrema (select_prepare's value_px), for a caller that passes none
 };
 
 // tables, workspace, and the init kernels.  sparse_th > 0: also lay out the sparse tail for a chain launch with that tile
 // height; pv_ws: keep room for a peak-value map in the workspace (the caller has none)
 static int select_prepare(silent_ctx* ctx, const char* who, const silent_extent* levels, int n_levels, int n_frames,
-                          const silent_extent* regions, hipStream_t s, SelectPlan* sp, int sparse_th = 0, bool pv_ws = false) {
+                          const silent_extent* regions, hipStream_t s, SelectPlan* sp, int sparse_th = 0, bool pv_ws = false,
+                          bool value_ws = false) {
     TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, kSelTW, kSelTH, &sp->stab, &sp->sblocks));
     TRY(region_tables(ctx, who, levels, n_levels, n_frames, regions, sp));
     sp->nmm = n_frames * n_levels;
     build_sum_tab(levels, n_levels, n_frames, sparse_th, sp->general, &sp->st);
-    TRY(keypoint_workspace(ctx, s, n_levels, n_frames, sizeof(unsigned) * 2 * (size_t)sp->nmm, sp, sp->st.frame_entries, pv_ws ? sp->tab.frame_px : 0));
+    // the head the caller keeps: the extrema, then (value_ws) a whole float32 value map
+    const size_t mm_bytes = sizeof(unsigned) * 2 * (size_t)sp->nmm;
+    const size_t head = value_ws ? align_up(mm_bytes) + (size_t)sp->tab.frame_px * n_frames * sizeof(float) : mm_bytes;
+    TRY(keypoint_workspace(ctx, s, n_levels, n_frames, head, sp, sp->st.frame_entries, pv_ws ? sp->tab.frame_px : 0));
     sp->mm = (unsigned*)ctx->ws.p;
+    sp->value_ws = value_ws ? (float*)((char*)ctx->ws.p + align_up(mm_bytes)) : nullptr;
     const long long n_init = std::max<long long>(2ll * sp->nmm, (long long)sp->w.n_cells);
     const long long n_zero16 = sp->st.frame_entries > 0 ? (long long)(sp->w.zero_bytes / 16) : 0;   // (every piece of the workspace is align_up'ed)
     const long long init_blocks = std::max((n_init + 255) / 256, std::min<long long>((n_zero16 + 255) / 256, 8ll * ctx->n_cus));
@@ -332,21 +338,21 @@ static int select_prepare(silent_ctx* ctx, const char* who, const silent_extent*
 
 // The selection launches of select_run for C channels; PAD: `color` is unpadded, pad_inwards' mask is applied as it is read
 // (silent_gray_keypoints).  sparse_pass: sparse_select_kernel; otherwise the streaming selection pass.
-template <int C, bool PAD>
-static void select_launches(const SelectPlan& sp, bool sparse_pass, const float* color, const float* value, float* pv_map, float a,
+template <int C, bool PAD, typename CT>
+static void select_launches(const SelectPlan& sp, bool sparse_pass, const CT* color, const float* value, float* pv_map, float a,
                             float b, const int* dense_flags, int n_frames, int pad, hipStream_t s) {
     const RegionTab& rt = sp.rt;
     const KeypointWs& w = sp.w;
     if (sparse_pass) {
-        hipLaunchKernelGGL((sparse_select_kernel<C, PAD>), dim3((unsigned)((sp.st.frame_entries + 255) / 256), (unsigned)n_frames), dim3(256), 0, s,
-                           color, sp.tab, sp.st, w.sum, n_frames, a, b, sp.mm, rt, w.cells, w.cand, w.cand_n, pad);
+        hipLaunchKernelGGL((sparse_select_kernel<C, PAD, CT>), dim3((unsigned)((sp.st.frame_entries + 255) / 256), (unsigned)n_frames), dim3(256), 0, s,
+                           color, sp.tab, sp.st, w.sum, n_frames, a, b, sp.mm, rt, w.cells, w.cand, w.cand_n, pad, value);
     } else if (sp.general) {
         // many windows: the selection pass without the folded cell maxima (the separable window maxima follow)
-        hipLaunchKernelGGL((select_peaks_kernel<C, false, PAD>), dim3((unsigned)sp.sblocks), dim3(256), 0, s, color, value, nullptr, nullptr,
+        hipLaunchKernelGGL((select_peaks_kernel<C, false, PAD, CT>), dim3((unsigned)sp.sblocks), dim3(256), 0, s, color, value, nullptr, nullptr,
                            pv_map, sp.stab, a, b, sp.mm, rt, nullptr, nullptr, (unsigned)sp.sblocks, pad);
     } else {
         // (sparse tail: a bounded grid -- usually no (frame, level) runs this pass)
-        hipLaunchKernelGGL((select_peaks_kernel<C, true, PAD>), dim3(dense_flags ? sparse_grid(sp.sblocks) : (unsigned)sp.sblocks), dim3(256), 0, s,
+        hipLaunchKernelGGL((select_peaks_kernel<C, true, PAD, CT>), dim3(dense_flags ? sparse_grid(sp.sblocks) : (unsigned)sp.sblocks), dim3(256), 0, s,
                            color, value, nullptr, nullptr, pv_map, sp.stab, a, b, sp.mm, rt, w.cells, dense_flags, (unsigned)sp.sblocks, pad);
     }
 }
@@ -354,7 +360,10 @@ static void select_launches(const SelectPlan& sp, bool sparse_pass, const float*
 // have_mm: the extrema are already in sp.mm (no reduction pass).  sparse: the chain kernel left its value summary in sp.w.sum
 // (geometry sp.st) -- the sparse tail runs and the dense kernels only where it could not settle a (frame, level).  pad > 0: `color`
 // is the unpadded map of silent_gray_keypoints (select_launches); the extrema must then be present (have_mm).
-static int select_run(silent_ctx* ctx, const char* who, const float* color, const float* value, const silent_extent* levels,
+// CT = _Float16 (silent_rgb_keypoints_h): `color` is the float16 line_end map, widened where it is loaded; `value` is then required
+// (the float32 value map: every comparison with the threshold reads it), channels = 3, pad = 0.
+template <typename CT>
+static int select_run(silent_ctx* ctx, const char* who, const CT* color, const float* value, const silent_extent* levels,
                       int n_levels, int n_frames, int channels, double top_percent, const SelectPlan& sp, bool have_mm,
                       float* peak_value_out, int64_t* idx, size_t cap_per_frame, int64_t* counts, hipStream_t s,
                       bool sparse = false, int pad = 0) {
@@ -362,16 +371,21 @@ static int select_run(silent_ctx* ctx, const char* who, const float* color, cons
     const RegionTab& rt = sp.rt;
     const KeypointWs& w = sp.w;
     if (!have_mm)
-        hipLaunchKernelGGL(level_maxmin_kernel, dim3((unsigned)sp.cblocks), dim3(256), 0, s, value, value ? nullptr : color,
+        hipLaunchKernelGGL(level_maxmin_kernel, dim3((unsigned)sp.cblocks), dim3(256), 0, s, value,
+                           value ? nullptr : reinterpret_cast<const float*>(color) /* (CT = float: a float16 map comes with its value map) */,
                            channels, sp.ctab, mm);
     const float a = (float)(1.0 - top_percent), b = (float)top_percent;
     const int* dense_flags = nullptr;
     float* const caller_map = peak_value_out;
     auto launches = [&](bool sparse_pass, float* pv_map) {
+        if constexpr (!std::is_same<CT, float>::value) {
+            select_launches<3, false, CT>(sp, sparse_pass, color, value, pv_map, a, b, dense_flags, n_frames, 0, s);
+        } else {
         with_channels(channels, [&](auto C) {
-            if (pad > 0) select_launches<decltype(C)::value, true>(sp, sparse_pass, color, value, pv_map, a, b, dense_flags, n_frames, pad, s);
-            else select_launches<decltype(C)::value, false>(sp, sparse_pass, color, value, pv_map, a, b, dense_flags, n_frames, pad, s);
+            if (pad > 0) select_launches<decltype(C)::value, true, float>(sp, sparse_pass, color, value, pv_map, a, b, dense_flags, n_frames, pad, s);
+            else select_launches<decltype(C)::value, false, float>(sp, sparse_pass, color, value, pv_map, a, b, dense_flags, n_frames, pad, s);
         });
+        }
     };
     if (sparse) {
         // (sparse implies: cell tables, extrema present; select_prepare zeroed the counters)
@@ -678,13 +692,16 @@ static void publish_sparse_tail(silent_ctx* ctx, const SelectPlan& sp, hipStream
 // When the chain runs as the pair kernel's two-group instantiation, that kernel also accumulates the per-level extrema of the
 // value map (a-10's max / min), so the reduction pass is skipped and nobody needs the value map in memory: the selection pass
 // takes the value from line_end (same three operations, same bits) and the map is written only if the caller asks for it.
-SILENT_EXPORT int silent_rgb_keypoints_dev(silent_ctx* ctx, const float* pyr, const silent_extent* levels, int n_levels,
-                                           int n_frames, const silent_rgb_chain_params* p, double top_percent,
-                                           const silent_extent* regions, float* orient_out, float* line_end_out,
-                                           float* value_out, float* peak_value_out, int64_t* idx, size_t cap_per_frame,
-                                           int64_t* counts, silent_stream stream) try {
-    NEED_CTX(ctx);
-    const char* who = "silent_rgb_keypoints";
+// MT: the element type of the orient / line_end maps -- float (silent_rgb_keypoints), or uint16_t = IEEE binary16 bits
+// (silent_rgb_keypoints_h: the chain stores them as float16, the tail widens line_end where it loads it and compares the FLOAT32
+// value map with the threshold, so the value map exists -- the caller's, or one in the workspace)
+template <typename MT>
+static int rgb_keypoints_dev(silent_ctx* ctx, const char* who, const float* pyr, const silent_extent* levels, int n_levels,
+                             int n_frames, const silent_rgb_chain_params* p, double top_percent,
+                             const silent_extent* regions, MT* orient_out, MT* line_end_out,
+                             float* value_out, float* peak_value_out, int64_t* idx, size_t cap_per_frame,
+                             int64_t* counts, silent_stream stream) {
+    constexpr bool half16 = !std::is_same<MT, float>::value;
     if (!pyr || !p || !regions || !line_end_out || !counts || (!idx && cap_per_frame))
         return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (!p->rgc || !p->rgby || !p->stripe || !p->blur || !p->end)
@@ -699,27 +716,63 @@ SILENT_EXPORT int silent_rgb_keypoints_dev(silent_ctx* ctx, const float* pyr, co
     for (int l = 0; l < n_levels; ++l)
         if (levels[l].h < 1 || levels[l].w < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": bad level extent");
     if (!uniform_blur) {
-        TRY(rgb_chain_launch(ctx, who, pyr, levels, n_levels, n_frames, p, orient_out, line_end_out, value_out, nullptr, nullptr, stream));
-        return silent_select_keypoints_dev(ctx, line_end_out, value_out, levels, n_levels, n_frames, 3, top_percent, regions,
-                                           peak_value_out, idx, cap_per_frame, counts, stream);
+        if constexpr (half16) {   // the launch's own refusal, the only one: the staged route writes float32 maps
+            return rgb_chain_launch(ctx, who, pyr, levels, n_levels, n_frames, p, orient_out, line_end_out, value_out, nullptr, nullptr, stream,
+                                    nullptr, nullptr, nullptr, true);
+        } else {
+            TRY(rgb_chain_launch(ctx, who, pyr, levels, n_levels, n_frames, p, orient_out, line_end_out, value_out, nullptr, nullptr, stream));
+            return silent_select_keypoints_dev(ctx, line_end_out, value_out, levels, n_levels, n_frames, 3, top_percent, regions,
+                                               peak_value_out, idx, cap_per_frame, counts, stream);
+        }
     }
     // Without a caller-side peak-value map the tail runs sparse (silent_peaks.h, sparse_select_kernel): the chain kernel leaves
     // a per-group maximum of the value map, and selection / NMS / keypoint search look only at the groups that reach their
     // level's threshold; whatever that cannot settle exactly runs the dense kernels on a map in the workspace.
     bool pair_kernel = false;
-    const int th = rgb_chain_tile_height(ctx, levels, n_levels, n_frames, &pair_kernel, true);
-    const bool want_sparse = pair_kernel && !(ctx->tune[SILENT_TUNE_RGB] & 32u);
+    const int th = rgb_chain_tile_height(ctx, levels, n_levels, n_frames, &pair_kernel, true, half16);
+    if (half16 && !pair_kernel)   // (the chain launch's refusal, before the tail lays out a workspace for such a level)
+        return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": a level is too large for the pair kernel's addressing (float16 storage has no other kernel)");
+    // (float16: a line_end above 65504 is stored as +inf, and inf * 0 is a NaN peak value at a pixel whose VALUE is no NaN -- the
+    // sparse tail places NaNs by the value map's NaN flags only, so such a clip bound keeps the dense kernels)
+    const bool want_sparse = pair_kernel && !(ctx->tune[SILENT_TUNE_RGB] & 32u) && (!half16 || p->clip_hi <= 65504.0f);
     SelectPlan sp;
-    TRY(select_prepare(ctx, who, levels, n_levels, n_frames, regions, s, &sp, want_sparse ? th : 0, !peak_value_out));
+    TRY(select_prepare(ctx, who, levels, n_levels, n_frames, regions, s, &sp, want_sparse ? th : 0, !peak_value_out, half16 && !value_out));
+    if (half16 && !value_out) value_out = sp.value_ws;
     bool mm_done = false;
     TRY(rgb_chain_launch(ctx, who, pyr, levels, n_levels, n_frames, p, orient_out, line_end_out, value_out, sp.mm, &mm_done, stream,
-                         &sp.st, sp.w.sum, sp.w.nan_flags));
+                         &sp.st, sp.w.sum, sp.w.nan_flags, half16));
     const bool sparse = want_sparse && mm_done && sp.st.frame_entries > 0;
     publish_sparse_tail(ctx, sp, s, n_frames, n_levels, sparse);
-    return select_run(ctx, who, line_end_out, mm_done ? nullptr : value_out, levels, n_levels, n_frames, 3, top_percent, sp, mm_done,
-                      peak_value_out, idx, cap_per_frame, counts, s, sparse);
+    if constexpr (half16)
+        return select_run(ctx, who, reinterpret_cast<const _Float16*>(line_end_out), value_out, levels, n_levels, n_frames, 3, top_percent, sp,
+                          mm_done, peak_value_out, idx, cap_per_frame, counts, s, sparse);
+    else
+        return select_run(ctx, who, line_end_out, mm_done ? nullptr : value_out, levels, n_levels, n_frames, 3, top_percent, sp, mm_done,
+                          peak_value_out, idx, cap_per_frame, counts, s, sparse);
+}
+
+SILENT_EXPORT int silent_rgb_keypoints_dev(silent_ctx* ctx, const float* pyr, const silent_extent* levels, int n_levels,
+                                           int n_frames, const silent_rgb_chain_params* p, double top_percent,
+                                           const silent_extent* regions, float* orient_out, float* line_end_out,
+                                           float* value_out, float* peak_value_out, int64_t* idx, size_t cap_per_frame,
+                                           int64_t* counts, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return rgb_keypoints_dev<float>(ctx, "silent_rgb_keypoints", pyr, levels, n_levels, n_frames, p, top_percent, regions, orient_out,
+                                    line_end_out, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
 } catch (...) {
     return on_exception(ctx, "silent_rgb_keypoints_dev");
+}
+
+SILENT_EXPORT int silent_rgb_keypoints_h_dev(silent_ctx* ctx, const float* pyr, const silent_extent* levels, int n_levels,
+                                             int n_frames, const silent_rgb_chain_params* p, double top_percent,
+                                             const silent_extent* regions, uint16_t* orient_out, uint16_t* line_end_out,
+                                             float* value_out, float* peak_value_out, int64_t* idx, size_t cap_per_frame,
+                                             int64_t* counts, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return rgb_keypoints_dev<uint16_t>(ctx, "silent_rgb_keypoints_h", pyr, levels, n_levels, n_frames, p, top_percent, regions, orient_out,
+                                       line_end_out, value_out, peak_value_out, idx, cap_per_frame, counts, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_rgb_keypoints_h_dev");
 }
 
 // ------------------------------------------------------------------------------------------ gray pass + keypoints
@@ -998,6 +1051,31 @@ SILENT_EXPORT int silent_rgb_keypoints(silent_ctx* ctx, const float* pyr, const 
     return SILENT_OK;
 } catch (...) {
     return on_exception(ctx, "silent_rgb_keypoints");
+}
+
+SILENT_EXPORT int silent_rgb_keypoints_h(silent_ctx* ctx, const float* pyr, const silent_extent* levels, int n_levels,
+                                         int n_frames, const silent_rgb_chain_params* p, double top_percent,
+                                         const silent_extent* regions, uint16_t* orient_out, uint16_t* line_end_out, float* value_out,
+                                         float* peak_value_out, int64_t* idx, size_t cap_per_frame, int64_t* counts) try {
+    NEED_CTX(ctx);
+    if (!pyr || !p || !regions || !line_end_out || !counts || (!idx && cap_per_frame))
+        return fail(ctx, SILENT_E_INVALID, "silent_rgb_keypoints_h: NULL pointer");
+    long long px;
+    TRY(check_levels(ctx, "silent_rgb_keypoints_h", levels, n_levels, n_frames, &px));
+    HostStage hs(ctx);
+    const size_t b1 = (size_t)px * 4, b3 = (size_t)px * 3 * sizeof(uint16_t);
+    const int x = hs.in(pyr, b1 * 3), o = hs.out(orient_out, b3), l = hs.out(line_end_out, b3), v = hs.out(value_out, b1),
+              pv = hs.out(peak_value_out, b1), i = hs.out(idx, (size_t)n_frames * cap_per_frame * 4 * sizeof(int64_t)),
+              n = hs.out(counts, (size_t)n_frames * sizeof(int64_t));
+    TRY(hs.run([&] {
+        return silent_rgb_keypoints_h_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, p, top_percent, regions, hs.dev<uint16_t>(o),
+                                          hs.dev<uint16_t>(l), hs.dev<float>(v), hs.dev<float>(pv), hs.dev<int64_t>(i), cap_per_frame,
+                                          hs.dev<int64_t>(n), nullptr);
+    }));
+    if (over_capacity(counts, n_frames, cap_per_frame)) return fail(ctx, SILENT_E_CAPACITY, "silent_rgb_keypoints_h: cap_per_frame too small; counts hold the need");
+    return SILENT_OK;
+} catch (...) {
+    return on_exception(ctx, "silent_rgb_keypoints_h");
 }
 
 // the host-pointer forms of silent_gray_keypoints on any frame type: the frames are staged as they are (frame_px_bytes each pixel)

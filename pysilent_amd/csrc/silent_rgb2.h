@@ -467,10 +467,19 @@ __device__ __forceinline__ float relu_max3_poisoned(float v, float u) {   // u: 
 // PAIR of rows instead of four 12-byte ones -- see the store section below; host-checked: every level's width, pixel offset and
 // the map pointers are multiples of 4 pixels / 16 bytes (all BASELINE extents are).  Bit-identical and, measured, exactly as
 // fast as the 12-byte form (0.806 vs 0.804 ms per config-3 launch): not the default.
+// ST (silent_rgb_line_end_h): the element type of the orient and line_end maps -- float, or rgb_half = float16 storage.  Only the
+// store sites of those two maps differ: every stored element is (_Float16)v of the float32 v that the ST = float instantiation
+// stores there (v_cvt_f16_f32: nearest even, overflow to inf, NaN stays NaN, subnormals kept); the arithmetic, the value map, the
+// extrema, the value summary and the NaN flags are the float32 ones, taken from the unrounded values.  A lane's pixel pair is then
+// 12 contiguous bytes: rows leave straight from the registers, no LDS transpose (store_row3h below).  ST4 has no float16 form.
+typedef _Float16 rgb_half;
 template <unsigned RGC_PAIRS, bool STRIPE_SUM, unsigned RGBY_A, unsigned END_A0, unsigned END_A1, unsigned END_A2, bool MM = false, bool SYM = false,
-          bool ST4 = false>
+          bool ST4 = false, typename ST = float>
 __global__ __launch_bounds__(64 * kRgb2Waves) __attribute__((amdgpu_waves_per_eu((MM || ST4) ? 3 : 4, 8))) void rgb_line_end2_kernel(const Rgb2Args args) {
     typedef Rgb2Layout<RGC_PAIRS, STRIPE_SUM, RGBY_A != kDense, END_A0 != kDense, SYM> L;
+    constexpr bool kHalf = std::is_same<ST, rgb_half>::value;
+    static_assert(kHalf || std::is_same<ST, float>::value, "orient / line_end are stored as float32 or float16");
+    static_assert(!(kHalf && ST4), "ST4 is a float32 store form");
     static_assert(L::blocks * kRgb2Blk <= kRgb2StreamMax, "stream fits its kernarg array");
     static_assert((RGC_PAIRS & 0x1ffu) == 0x1ffu || (RGC_PAIRS & 0x1ffu) == 0x111u, "rgc: dense or channel-diagonal");
     constexpr bool kRgcDiag = (RGC_PAIRS & 0x1ffu) == 0x111u;   // zero weights skipped: the outputs are poisoned (rgc stage)
@@ -517,8 +526,21 @@ __global__ __launch_bounds__(64 * kRgb2Waves) __attribute__((amdgpu_waves_per_eu
     const unsigned tile_bytes = (unsigned)rows_t * (unsigned)rb;
     const long long tile_px = base_px + (long long)y0 * W;
     const __amdgpu_buffer_rsrc_t r_src = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, lvl_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_orient = __builtin_amdgcn_make_buffer_rsrc((void*)(orient_out + tile_px * 3), 0, orient_out ? tile_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_line = __builtin_amdgcn_make_buffer_rsrc((void*)(line_out + tile_px * 3), 0, line_out ? tile_bytes : 0u, 0x00020000);
+    // float16 maps (Rgb2Args carries the ABI's uint16_t* as float*): 6 bytes per pixel, so a tile can start on a 2-byte boundary
+    // only.  The resource's base is the dword at or below the tile's first byte and `mis` (0 or 2, wave-uniform) the tile's offset
+    // from it: with it inside every store's offset, "the row starts on a dword" is a test of the offset alone (store_row3h).
+    __amdgpu_buffer_rsrc_t r_orient = __builtin_amdgcn_make_buffer_rsrc((void*)(orient_out + tile_px * 3), 0, orient_out ? tile_bytes : 0u, 0x00020000);
+    __amdgpu_buffer_rsrc_t r_line = __builtin_amdgcn_make_buffer_rsrc((void*)(line_out + tile_px * 3), 0, line_out ? tile_bytes : 0u, 0x00020000);
+    unsigned mis_o = 0, mis_l = 0;
+    if constexpr (kHalf) {
+        auto half_rsrc = [&](float* p, unsigned& mis) {
+            const unsigned long long b = reinterpret_cast<unsigned long long>(p) + (unsigned long long)(tile_px * 6);
+            mis = (unsigned)__builtin_amdgcn_readfirstlane((int)(b & 2ull));
+            return __builtin_amdgcn_make_buffer_rsrc((void*)(b - mis), 0, p ? tile_bytes / 2u + mis : 0u, 0x00020000);
+        };
+        r_orient = half_rsrc(orient_out, mis_o);
+        r_line = half_rsrc(line_out, mis_l);
+    }
     const __amdgpu_buffer_rsrc_t r_value = __builtin_amdgcn_make_buffer_rsrc((void*)(value_out + tile_px), 0, value_out ? tile_bytes / 3u : 0u, 0x00020000);
     const int in0 = col0 ? x0 * 12 : kRgb2Out, in1 = col1 ? x1 * 12 : kRgb2Out;     // byte offsets inside a row, or out of range
     // Stores: a lane's own pixel pair would make every x3 store instruction write 12 of every 24 bytes (its partner instruction
@@ -555,7 +577,7 @@ __global__ __launch_bounds__(64 * kRgb2Waves) __attribute__((amdgpu_waves_per_eu
         (void*)(args.sum + (long long)tc.frame * args.sum_frame + args.sum_off[tc.level] + (long long)tc.ty * gpt * nxp), 0, sum_bytes, 0x00020000);
     const int ssum = out0 ? (x0 >> 1) * 4 : kRgb2Out;
     // [wave][one output row of the wave's 128 columns x 3 channels]; ST4: [wave][map: orient, line_end][row A, row B][384]
-    __shared__ __attribute__((aligned(16))) float s_tr[kRgb2Waves][ST4 ? 4 * 384 : 384];
+    __shared__ __attribute__((aligned(16))) float s_tr[kRgb2Waves][ST4 ? 4 * 384 : kHalf ? 1 : 384];   // (float16 rows: no transpose)
     float* const tr = s_tr[wave];
     // lane-major in AS HELD -- [lane][channel][half]: three 8-byte writes of the register pairs, no shuffling moves --, pixel-major
     // out: pixel p of the wave's 128 columns is half p & 1 of lane p >> 1, its channels 2 floats apart.  The reading lane j takes
@@ -571,6 +593,57 @@ __global__ __launch_bounds__(64 * kRgb2Waves) __attribute__((amdgpu_waves_per_eu
         const i3 db = {__float_as_int(tr_out[192]), __float_as_int(tr_out[194]), __float_as_int(tr_out[196])};
         __builtin_amdgcn_raw_buffer_store_b96(da, rsrc, (int)((unsigned)sta + (unsigned)ro), 0, kRgb2StoreAux);
         __builtin_amdgcn_raw_buffer_store_b96(db, rsrc, (int)((unsigned)stb + (unsigned)ro), 0, kRgb2StoreAux);
+    };
+    // float16 rows (ST = rgb_half).  The lane's pair (x0, x0 + 1) is the six halves h0 .. h5 = 12 bytes at byte x0 * 6 of the row, a
+    // multiple of 12 (x0 is even): where the row starts on a dword (EVEN form) the lane stores its own three dwords; a last odd
+    // column leaves one pixel = a dword + a half.  A row of an odd-width level on an odd row, of a level at an odd pixel offset or
+    // of frame f of an odd frame_px starts 2 bytes off the dword grid (ODD form); no store is issued off its natural alignment,
+    // so there the lane stores the three ALIGNED dwords from byte + 2 on -- (h1 h2) (h3 h4) (h5, h0 of lane + 1: one DPP) -- which
+    // tile the run; its ends are the first pixel's h0 (lane 3, the lane before the first output lane, stores lane 4's: a half), and
+    // in the run's last lane either two dwords + h5 (two pixels) or one dword (a last odd column).  Both forms are ONE instruction
+    // sequence: the window (e0 e1 e2) = the 12 bytes from byte `sh / 8` of the lane's pair on is a funnel shift by sh = 0 or 16,
+    // and the form -- wave-uniform per row, `ro & 2` with ro = the row's byte offset from the resource's dword-aligned base --
+    // picks between two per-lane offsets as a bitwise blend with the opaque mask m = 0 / -1 (v_bfi_b32).  A branch per form
+    // would do with fewer VALU operations, but the compiler turns it into two guarded blocks and then counts neither block's
+    // stores: the wait for the input rows would wait for the previous step's stores (and plain selects come back as that branch
+    // plus a table of the offsets in scratch).  Four stores per map and row (b96, b64, b32, b16), the same in both forms -- the vmcnt distances of the row
+    // loop are static --; what a lane or a form does not use goes to kRgb2Out, a dropped store.  Rows outside the tile are dropped
+    // by ro = kRgb2Out (the caller's): with the base up to 2 bytes below the tile, a negative row offset alone would not keep the
+    // last half of the row above out of range.
+    const int hb = x0 * 6;
+    const bool h_two = out0 && out1, h_one = out0 && !out1;
+    const bool h_next = lane + 1 < 64 - kRgb2Halo / 2 && x0 + 2 < W;   // lane + 1 holds an output pixel: its h0 ends this lane's window
+    const bool h_lead = lane == kRgb2Halo / 2 - 1;                      // (the wave's first output column xw0 < W always exists)
+    const int he96 = h_two ? hb : kRgb2Out, ho96 = (h_two && h_next) ? hb + 2 : kRgb2Out;
+    const int ho64 = (h_two && !h_next) ? hb + 2 : kRgb2Out;
+    const int h32 = h_one ? hb : kRgb2Out;                              // (+ 2 in the odd form: with the row offset)
+    const int he16 = h_one ? hb + 4 : kRgb2Out;                         // the single pixel's third half: e1's low half
+    const int ho16 = h_lead ? hb + 12 : (h_two && !h_next) ? hb + 10 : kRgb2Out;   // lane + 1's h0: e2's high half; h5: e2's low half
+    const unsigned lead_sh = h_lead ? 16u : 0u;
+    auto store_row3h = [&](const f2 (&val)[3], __amdgpu_buffer_rsrc_t rsrc, unsigned ro) {
+        typedef rgb_half h2 __attribute__((ext_vector_type(2)));
+        typedef int i2h __attribute__((ext_vector_type(2)));
+        const int d0 = __builtin_bit_cast(int, h2{(rgb_half)val[0].x, (rgb_half)val[1].x});
+        const int d1 = __builtin_bit_cast(int, h2{(rgb_half)val[2].x, (rgb_half)val[0].y});
+        const int d2 = __builtin_bit_cast(int, h2{(rgb_half)val[1].y, (rgb_half)val[2].y});
+        int m = -(int)((ro >> 1) & 1u);   // wave-uniform: -1 in the odd form
+        asm volatile("" : "+s"(m));
+        auto pick = [&](int even, int odd) { return (odd & m) | (even & ~m); };
+        const unsigned sh = (unsigned)(m & 16);
+        const int up = __builtin_amdgcn_update_dpp(0, d0, 0x130 /* wave_shl:1 */, 0xf, 0xf, true);   // lane + 1's (h0 h1)
+        const int e0 = (int)__builtin_amdgcn_alignbit((unsigned)d1, (unsigned)d0, sh);
+        const int e1 = (int)__builtin_amdgcn_alignbit((unsigned)d2, (unsigned)d1, sh);
+        const int e2 = (int)__builtin_amdgcn_alignbit((unsigned)up, (unsigned)d2, sh);
+        const int last = pick(e1, (int)((unsigned)e2 >> lead_sh));
+        __builtin_amdgcn_raw_buffer_store_b96(i3{e0, e1, e2}, rsrc, (int)((unsigned)pick(he96, ho96) + ro), 0, kRgb2StoreAux);
+        __builtin_amdgcn_raw_buffer_store_b64(i2h{e0, e1}, rsrc, (int)((unsigned)pick(kRgb2Out, ho64) + ro), 0, kRgb2StoreAux);
+        __builtin_amdgcn_raw_buffer_store_b32(e0, rsrc, (int)((unsigned)h32 + (ro + (unsigned)(m & 2))), 0, kRgb2StoreAux);
+        __builtin_amdgcn_raw_buffer_store_b16((short)last, rsrc, (int)((unsigned)pick(he16, ho16) + ro), 0, kRgb2StoreAux);
+    };
+    // the byte offset of output row k of a float16 map from its resource's base, or kRgb2Out for a row outside the tile
+    auto row_off_h = [&](int k, unsigned mis) {
+        const int norow = (k | (rows_t - 1 - k)) >> 31;
+        return norow != 0 ? (unsigned)kRgb2Out : mis + (unsigned)(k * (W * 6));
     };
     // ST4: a row of the wave's 128 columns is 1536 bytes = 96 sixteen-byte chunks, of which chunks 6 .. 89 (the 112 output columns;
     // 4 pixels = 3 chunks and everything is a multiple of 4 pixels, so no chunk straddles a column bound) are stored.  84 chunks
@@ -633,9 +706,10 @@ __global__ __launch_bounds__(64 * kRgb2Waves) __attribute__((amdgpu_waves_per_eu
     // The wait at the head of the row loop merges two paths: the back edge (14 younger operations behind the loads it waits for:
     // 6 + 6 stores and 2 loads) and this prologue (2: the second fetch) -- the compiler takes the minimum, vmcnt(2), which on
     // the back edge waits for the previous iteration's 12 stores.  Twelve out-of-range (dropped) stores make both paths 14
-    // (MM: one summary store more per step, 14 make both 16).
+    // (MM: one summary store more per step, 14 make both 16).  float16 maps: four stores per map and row instead of two
+    // (store_row3h), 10 or 11 stores per step: 20 or 22 dummies.
 #pragma unroll
-    for (int k = 0; k < (MM ? 14 : 12); ++k) __builtin_amdgcn_raw_buffer_store_b32(k, r_value, kRgb2Out + 64 * k, 0, 0);   // (distinct: identical ones are merged)
+    for (int k = 0; k < (MM ? 14 : 12) + (kHalf ? 8 : 0); ++k) __builtin_amdgcn_raw_buffer_store_b32(k, r_value, kRgb2Out + 64 * k, 0, 0);   // (distinct: identical ones are merged)
 
     // Masks.  Every stage's row is forced to 0 outside the level (the next stage's SAME padding) and the line-end map inside the
     // pad border.  For most steps of most waves nothing of that can bite: `inside` (one unsigned compare per step) says that the
@@ -933,6 +1007,8 @@ __global__ __launch_bounds__(64 * kRgb2Waves) __attribute__((amdgpu_waves_per_eu
             // orient row t - y0 = row - 13: even on the odd steps (slot A), the pair completes on the even ones
             st4_put(o3, 0, PAR == 1 ? 0 : 1);
             if constexpr (PAR == 0) st4_flush(0, r_orient, (t - y0 - 1) * rb);
+        } else if constexpr (kHalf) {
+            store_row3h(o3, r_orient, row_off_h(t - y0, mis_o));
         } else {
             store_row3(o3, r_orient, (t - y0) * rb);
         }
@@ -961,6 +1037,8 @@ __global__ __launch_bounds__(64 * kRgb2Waves) __attribute__((amdgpu_waves_per_eu
                 // line_end row k = row - 14: even on the even steps (slot A), the pair completes on the odd ones
                 st4_put(le, 1, PAR == 0 ? 0 : 1);
                 if constexpr (PAR == 1) st4_flush(1, r_line, (k - 1) * rb);
+            } else if constexpr (kHalf) {
+                store_row3h(le, r_line, row_off_h(k, mis_l));
             } else {
                 store_row3(le, r_line, k * rb);
             }

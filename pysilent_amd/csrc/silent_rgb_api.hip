@@ -230,10 +230,10 @@ SILENT_EXPORT int silent_rgb_chain_structure(const silent_rgb_chain_params* para
 
 
 // Which fused kernel a chain launch over these levels uses and its tile height (output rows per tile).
-int rgb_chain_tile_height(const silent_ctx* ctx, const silent_extent* levels, int n_levels, int n_frames, bool* pair, bool with_extrema) {
+int rgb_chain_tile_height(const silent_ctx* ctx, const silent_extent* levels, int n_levels, int n_frames, bool* pair, bool with_extrema, bool half16) {
     const unsigned kopts = ctx->tune[SILENT_TUNE_RGB];  // 1: dense, 2: no two-group, 8: 90-row tiles, bits 8-15: tile height / 2
     // two pixels per lane on packed f32 (silent_rgb2.h; its buffer addressing wants levels below 2^30 bytes per map); 16: one pixel per lane
-    bool pair_kernel = !(kopts & 16u);
+    bool pair_kernel = half16 || !(kopts & 16u);
     // (its range-check addressing: (H + 16) rows of a map below kRgb2Out, (H + tile height + 16) rows below 2^32 - kRgb2Out)
     for (int l = 0; l < n_levels; ++l)
         if ((long long)(levels[l].h + 16) * levels[l].w * 12 >= (long long)kRgb2Out ||
@@ -284,9 +284,9 @@ int rgb_chain_tile_height(const silent_ctx* ctx, const silent_extent* levels, in
 // mm: optional per-level extrema slots (already initialised); *mm_done tells whether the launch filled them (only the pair
 // kernel's two-group instantiation does -- everything else leaves them to level_maxmin_kernel)
 int rgb_chain_launch(silent_ctx* ctx, const char* who, const float* pyr, const silent_extent* levels, int n_levels,
-                            int n_frames, const silent_rgb_chain_params* p, float* orient_out, float* line_end_out,
+                            int n_frames, const silent_rgb_chain_params* p, void* orient_out, void* line_end_out,
                             float* value_out, unsigned* mm, bool* mm_done, silent_stream stream, const SumTab* st,
-                            float* sum, int* nan_flags) {
+                            float* sum, int* nan_flags, bool half16) {
     if (mm_done) *mm_done = false;
     if (!pyr || !p) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
     if (!p->rgc || !p->rgby || !p->stripe || !p->blur || !p->end)
@@ -304,19 +304,27 @@ int rgb_chain_launch(silent_ctx* ctx, const char* who, const float* pyr, const s
     for (int t = 0; t < 49 && uniform_blur; ++t)
         for (int io = 1; io < 9; ++io)
             if (p->blur[t * 9 + io] != p->blur[t * 9]) uniform_blur = false;
+    if (half16) {   // float16 storage exists in the pair kernel only; its 6-byte pixels want 2-byte aligned maps
+        if (!uniform_blur)
+            return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": float16 storage needs a channel-uniform blur (the stage-per-launch route writes float32 maps)");
+        if ((uintptr_t)orient_out % 2 || (uintptr_t)line_end_out % 2)
+            return fail(ctx, SILENT_E_INVALID, std::string(who) + ": orient_out / line_end_out must be 2-byte aligned");
+    }
     if (uniform_blur) {
         LevelTab tab;
         long long blocks;
         const unsigned kopts = ctx->tune[SILENT_TUNE_RGB];  // 1: dense, 2: no two-group, 8: 90-row tiles, bits 8-15: tile height / 2
         bool pair_kernel;
-        const int th = rgb_chain_tile_height(ctx, levels, n_levels, n_frames, &pair_kernel, mm != nullptr);
+        const int th = rgb_chain_tile_height(ctx, levels, n_levels, n_frames, &pair_kernel, mm != nullptr, half16);
+        if (half16 && !pair_kernel)
+            return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": a level is too large for the pair kernel's addressing (float16 storage has no other kernel)");
         TRY(build_level_tab(ctx, who, levels, n_levels, n_frames, pair_kernel ? kRgb2TW : kRgbTW, th, &tab, &blocks));
         if (p->flat_policy != SILENT_FLAT_IEEE && p->flat_policy != SILENT_FLAT_ZERO)
             return fail(ctx, SILENT_E_INVALID, std::string(who) + ": flat_policy must be SILENT_FLAT_IEEE or SILENT_FLAT_ZERO");
         RgbArgs a;
         a.pyr = pyr;
-        a.orient_out = orient_out;
-        a.line_out = line_end_out;
+        a.orient_out = static_cast<float*>(orient_out);   // (half16: the pair kernel's ST = rgb_half instantiations read them as float16 maps)
+        a.line_out = static_cast<float*>(line_end_out);
         a.value_out = value_out;
         a.tab = tab;
         a.th = th;
@@ -345,7 +353,7 @@ int rgb_chain_launch(silent_ctx* ctx, const char* who, const float* pyr, const s
             // instructions are not what the kernel waits for, so the simpler form stays the default): every row of every map must
             // start on a 16-byte boundary -- widths, level offsets and the frame stride multiples of 4 pixels, the map pointers
             // 16-byte aligned (all BASELINE extents; anything else keeps the 12-byte form).
-            bool st4 = (kopts & 128u) && tab.frame_px % 4 == 0 && (uintptr_t)orient_out % 16 == 0 && (uintptr_t)line_end_out % 16 == 0;
+            bool st4 = !half16 && (kopts & 128u) && tab.frame_px % 4 == 0 && (uintptr_t)orient_out % 16 == 0 && (uintptr_t)line_end_out % 16 == 0;
             for (int l = 0; l < n_levels && st4; ++l) st4 = levels[l].w % 4 == 0 && tab.px_off[l] % 4 == 0;
             // silent_set_profiling: HIP events around THIS launch, on the stream it runs on (the fused RGB chain is the dominant
             // kernel of silent_rgb_line_end / silent_rgb_keypoints, like gray_stream_kernel is of silent_gray_pass)
@@ -362,6 +370,8 @@ int rgb_chain_launch(silent_ctx* ctx, const char* who, const float* pyr, const s
                     } else (void)hipGetLastError();
                 }
             } prof_end{ctx, prof, prof_slot, s, tab.frame_px * n_frames};
+            // rgb_line_end2_kernel<..., MM, SYM, ST4, ST> on this launch's grid
+#define SILENT_RGB2_LAUNCH(...) hipLaunchKernelGGL((rgb_line_end2_kernel<__VA_ARGS__>), dim3((unsigned)blocks), dim3(64 * kRgb2Waves), 0, s, a2)
             if (two && mm) {
                 a2.mm = mm;
                 if (st && sum && st->frame_entries > 0 && st->th == th) {   // value summary for the sparse selection tail
@@ -370,16 +380,24 @@ int rgb_chain_launch(silent_ctx* ctx, const char* who, const float* pyr, const s
                     a2.sum_frame = st->frame_entries;
                     for (int l = 0; l < kMaxLevels; ++l) a2.sum_off[l] = st->off[l];
                 }
-                if (use_sym && st4) hipLaunchKernelGGL((rgb_line_end2_kernel<0x111u, true, kRgbyA, kEndA0, kEndA1, kEndA2, true, true, true>), dim3((unsigned)blocks), dim3(64 * kRgb2Waves), 0, s, a2);
+                if (half16 && use_sym) SILENT_RGB2_LAUNCH(0x111u, true, kRgbyA, kEndA0, kEndA1, kEndA2, true, true, false, rgb_half);
+                else if (half16) SILENT_RGB2_LAUNCH(0x111u, true, kRgbyA, kEndA0, kEndA1, kEndA2, true, false, false, rgb_half);
+                else if (use_sym && st4) hipLaunchKernelGGL((rgb_line_end2_kernel<0x111u, true, kRgbyA, kEndA0, kEndA1, kEndA2, true, true, true>), dim3((unsigned)blocks), dim3(64 * kRgb2Waves), 0, s, a2);
                 else if (use_sym) hipLaunchKernelGGL((rgb_line_end2_kernel<0x111u, true, kRgbyA, kEndA0, kEndA1, kEndA2, true, true>), dim3((unsigned)blocks), dim3(64 * kRgb2Waves), 0, s, a2);
                 else hipLaunchKernelGGL((rgb_line_end2_kernel<0x111u, true, kRgbyA, kEndA0, kEndA1, kEndA2, true>), dim3((unsigned)blocks), dim3(64 * kRgb2Waves), 0, s, a2);
                 if (mm_done) *mm_done = true;
+            } else if (half16) {
+                if (use_sym) SILENT_RGB2_LAUNCH(0x111u, true, kRgbyA, kEndA0, kEndA1, kEndA2, false, true, false, rgb_half);
+                else if (two) SILENT_RGB2_LAUNCH(0x111u, true, kRgbyA, kEndA0, kEndA1, kEndA2, false, false, false, rgb_half);
+                else if (basic) SILENT_RGB2_LAUNCH(0x111u, true, kDense, kDense, kDense, kDense, false, false, false, rgb_half);
+                else SILENT_RGB2_LAUNCH(0x1ffu, false, kDense, kDense, kDense, kDense, false, false, false, rgb_half);
             } else
             if (use_sym && st4) hipLaunchKernelGGL((rgb_line_end2_kernel<0x111u, true, kRgbyA, kEndA0, kEndA1, kEndA2, false, true, true>), dim3((unsigned)blocks), dim3(64 * kRgb2Waves), 0, s, a2);
             else if (use_sym) hipLaunchKernelGGL((rgb_line_end2_kernel<0x111u, true, kRgbyA, kEndA0, kEndA1, kEndA2, false, true>), dim3((unsigned)blocks), dim3(64 * kRgb2Waves), 0, s, a2);
             else if (two) hipLaunchKernelGGL((rgb_line_end2_kernel<0x111u, true, kRgbyA, kEndA0, kEndA1, kEndA2>), dim3((unsigned)blocks), dim3(64 * kRgb2Waves), 0, s, a2);
             else if (basic) hipLaunchKernelGGL((rgb_line_end2_kernel<0x111u, true, kDense, kDense, kDense, kDense>), dim3((unsigned)blocks), dim3(64 * kRgb2Waves), 0, s, a2);
             else hipLaunchKernelGGL((rgb_line_end2_kernel<0x1ffu, false, kDense, kDense, kDense, kDense>), dim3((unsigned)blocks), dim3(64 * kRgb2Waves), 0, s, a2);
+#undef SILENT_RGB2_LAUNCH
         } else if (two) {
             hipLaunchKernelGGL((rgb_line_end_kernel<0x111u, true, kRgbyA, kEndA0, kEndA1, kEndA2>), dim3((unsigned)blocks), dim3(256), 0, s, a);
         } else if (basic) {
@@ -400,12 +418,12 @@ int rgb_chain_launch(silent_ctx* ctx, const char* who, const float* pyr, const s
     TRY(silent_conv2d_same_dev(ctx, pyr, levels, n_levels, n_frames, 3, p->rgc, 3, 3, 3, SILENT_RELU, 0.f, t0, stream));
     TRY(silent_conv2d_same_dev(ctx, t0, levels, n_levels, n_frames, 3, p->rgby, 3, 3, 3, SILENT_RELU, 0.f, t1, stream));
     TRY(silent_conv2d_same_dev(ctx, t1, levels, n_levels, n_frames, 3, p->stripe, 3, 3, 3, SILENT_RELU, 0.f, t0, stream));
-    float* orient = orient_out ? orient_out : t1;
+    float* orient = orient_out ? static_cast<float*>(orient_out) : t1;
     TRY(silent_regulate_dev(ctx, t0, levels, n_levels, n_frames, 3, p->blur, 7, 7, p->regulation_value, p->regulation_root, p->flat_policy,
                             orient, stream));
     if (!line_end_out && !value_out) return SILENT_OK;
     TRY(silent_conv2d_same_dev(ctx, orient, levels, n_levels, n_frames, 3, p->end, 3, 3, 3, SILENT_RELU | SILENT_CLIP, p->clip_hi, t0, stream));
-    float* padded = line_end_out ? line_end_out : t2;
+    float* padded = line_end_out ? static_cast<float*>(line_end_out) : t2;
     TRY(silent_pad_inwards_dev(ctx, t0, levels, n_levels, n_frames, 3, p->pad, p->pad, p->pad, p->pad, padded, stream));
     if (value_out) TRY(silent_value_from_color_dev(ctx, padded, levels, n_levels, n_frames, 3, value_out, stream));
     return SILENT_OK;
@@ -452,4 +470,34 @@ SILENT_EXPORT int silent_rgb_line_end(silent_ctx* ctx, const float* pyr, const s
     });
 } catch (...) {
     return on_exception(ctx, "silent_rgb_line_end");
+}
+
+// float16 storage of the orient and line_end maps (include/silent_hip.h): the same launch with the pair kernel's ST = rgb_half
+// instantiation of the form the float32 call takes
+SILENT_EXPORT int silent_rgb_line_end_h_dev(silent_ctx* ctx, const float* pyr, const silent_extent* levels, int n_levels,
+                                            int n_frames, const silent_rgb_chain_params* p, uint16_t* orient_out,
+                                            uint16_t* line_end_out, float* value_out, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return rgb_chain_launch(ctx, "silent_rgb_line_end_h", pyr, levels, n_levels, n_frames, p, orient_out, line_end_out, value_out,
+                            nullptr, nullptr, stream, nullptr, nullptr, nullptr, true);
+} catch (...) {
+    return on_exception(ctx, "silent_rgb_line_end_h_dev");
+}
+
+SILENT_EXPORT int silent_rgb_line_end_h(silent_ctx* ctx, const float* pyr, const silent_extent* levels, int n_levels,
+                                        int n_frames, const silent_rgb_chain_params* p, uint16_t* orient_out,
+                                        uint16_t* line_end_out, float* value_out) try {
+    NEED_CTX(ctx);
+    if (!pyr || !p) return fail(ctx, SILENT_E_INVALID, "silent_rgb_line_end_h: NULL pointer");
+    long long px;
+    TRY(check_levels(ctx, "silent_rgb_line_end_h", levels, n_levels, n_frames, &px));
+    HostStage hs(ctx);
+    const size_t b1 = (size_t)px * 4, b3 = (size_t)px * 3 * sizeof(uint16_t);
+    const int x = hs.in(pyr, b1 * 3), o = hs.out(orient_out, b3), l = hs.out(line_end_out, b3), v = hs.out(value_out, b1);
+    return hs.run([&] {
+        return silent_rgb_line_end_h_dev(ctx, hs.dev<float>(x), levels, n_levels, n_frames, p, hs.dev<uint16_t>(o), hs.dev<uint16_t>(l),
+                                         hs.dev<float>(v), nullptr);
+    });
+} catch (...) {
+    return on_exception(ctx, "silent_rgb_line_end_h");
 }

@@ -131,19 +131,28 @@ class _RawBlock(object):
 ATTENTION_KEYWORDS = dict(attention=False, centroid_region=(3, 3), input_based_recovery=False, constant_recovery=True, attention_visualize=True)
 
 
+# rgb_storage="float16" (mode "rgb"): the orient and line_end maps are stored as float16 (silent_rgb_line_end_h / silent_rgb_keypoints_h).
+# A keyword of its own: storage="float16" keeps raising on mode "rgb" (pinned by the suite), and it travels like the attention keywords
+RGB_STORAGE_KEYWORDS = dict(rgb_storage="float32")
+
+
 class _PipelineCall(type):
-    """The call ``LineEndPipeline(...)``: the keywords of ATTENTION_KEYWORDS are taken off the arguments and handed to the instance
-    before ``__init__`` runs, which reads them where it checks its other arguments.  ``__init__`` keeps its parameter list: that list
-    is pinned by the suite (the source keywords are its last four), and these five belong to one optional stage of the step."""
+    """The call ``LineEndPipeline(...)``: the keywords of ATTENTION_KEYWORDS and RGB_STORAGE_KEYWORDS are taken off the arguments and
+    handed to the instance before ``__init__`` runs, which reads them where it checks its other arguments.  ``__init__`` keeps its
+    parameter list: that list is pinned by the suite (the source keywords are its last four), and these belong to optional stages /
+    forms of the step."""
 
     def __call__(cls, *args, **kw):
         self = cls.__new__(cls)
         self._attention_keywords = dict(ATTENTION_KEYWORDS, **{k: kw.pop(k) for k in ATTENTION_KEYWORDS if k in kw})
+        self._rgb_storage_keywords = dict(RGB_STORAGE_KEYWORDS, **{k: kw.pop(k) for k in RGB_STORAGE_KEYWORDS if k in kw})
         self.__init__(*args, **kw)
         return self
 
 
 class LineEndPipeline(object, metaclass=_PipelineCall):
+    rgb_storage = "float32"      # (the default of RGB_STORAGE_KEYWORDS: what an instance that never ran __init__ reports)
+
     def __init__(self, frame_hw, mode="gray", n_levels=5, scale=2.0, n_orient=4, batch=1, device=None,
                  constants=None, center_dimensions=None, clip_hi=255.0, flat_policy="ieee", pad=2,
                  max_keypoints_per_frame=None, selection=False, top_percent=0.1, keep_selection_maps=False, value_map=None,
@@ -208,6 +217,14 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
         # float32 result rounded to nearest even, half the bytes written and kept; the pyramid stays float32.  Also refused before
         # any GPU or torch work: unknown names, mode "rgb", accumulation="float64", keypoints=True
         self.storage = _runtime.check_storage(storage, mode, accumulation, bool(keypoints))
+        # rgb_storage="float16" (mode "rgb"): orient and line_end are stored as float16 (silent_rgb_line_end_h_dev /
+        # silent_rgb_keypoints_h_dev) -- every element the float32 result rounded once at the store, half the bytes written and
+        # kept for the pipeline's two largest maps; pyramid, value, peak_value and the attention tail stay float32.  Without
+        # selection the keypoints are the float32 pipeline's bit for bit (they come from the value map); with selection they are
+        # silent_rgb_keypoints_h's (include/silent_hip.h: ties).  Refused before any GPU or torch work: unknown names, mode "gray",
+        # keep_selection_maps=True
+        self.rgb_storage = _runtime.check_rgb_storage(getattr(self, "_rgb_storage_keywords", RGB_STORAGE_KEYWORDS)["rgb_storage"], mode,
+                                                      bool(keep_selection_maps))
         # frame_dtype="uint8" (mode "gray"): step() takes uint8 frames as a camera or decoder delivers them and the kernels read the
         # bytes themselves (the silent_*_u8 entry points) -- no widening cast, no float32 copy of the batch, every map bit-identical
         # to the float32 pipeline's on the widened frames.  Refused here as well: unknown names, mode "rgb", accumulation="float64"
@@ -472,8 +489,9 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
             m["cs"] = torch.empty(n, **maps)
             m["end"] = torch.empty(n * self.n_orient, **maps)
         else:
-            m["orient"] = torch.empty(n * 3, **f32) if self.orient_map else None
-            m["line_end"] = torch.empty(n * 3, **f32)
+            maps = dict(f32, dtype=torch.float16) if self.rgb_storage == "float16" else f32
+            m["orient"] = torch.empty(n * 3, **maps) if self.orient_map else None
+            m["line_end"] = torch.empty(n * 3, **maps)
             m["value"] = torch.empty(n, **f32) if self.value_map else None
         return m
 
@@ -747,8 +765,10 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
         c = self.channels
         if self.crop_px is not None:
             h, w = 1, self.crop_px
-        outs = (1 + self.n_orient) if self.mode == "gray" else (3 + (3 if self.orient_map else 0) + (1 if self.value_map else 0))
-        return int(self._frame_bytes * h * w * fc) + 4 * 2 * self.frame_px * c + self._map_bytes * self.frame_px * outs + self.attention_bytes_per_frame()
+        # (rgb_storage="float16": a colour map's three channels cost 6 bytes per pixel -- 1.5 float32 channels; _map_bytes is 4 on mode "rgb")
+        cc = 1.5 if self.rgb_storage == "float16" else 3
+        outs = (1 + self.n_orient) if self.mode == "gray" else (cc + (cc if self.orient_map else 0) + (1 if self._value_written else 0))
+        return int(self._frame_bytes * h * w * fc) + 4 * 2 * self.frame_px * c + int(self._map_bytes * self.frame_px * outs) + self.attention_bytes_per_frame()
 
     def attention_bytes_per_frame(self):
         """What the tail moves per frame (0 without attention=True): the value map read once and the half map's gathers (one value
@@ -758,6 +778,12 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
             return 0
         half_px = sum(h * w for h, w in self.attention_half)
         return 4 * (2 * self.frame_px + 2 * half_px + self.cells_per_frame * (3 + 2 * self.attention_channels))
+
+    @property
+    def _value_written(self):
+        """mode "rgb": the chain writes a float32 value map -- the kept one, or, with rgb_storage="float16" and selection, the one
+        silent_rgb_keypoints_h keeps in the context workspace for its tail (the rounded colours do not give the value back)."""
+        return self.value_map or (self.rgb_storage == "float16" and self.selection)
 
     @property
     def _map_bytes(self):
@@ -813,8 +839,10 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
     def filter_bytes_per_frame(self):
         """The filter pass alone: pyramid read once + every returned map written once."""
         c = self.channels
-        outs = (1 + self.n_orient) if self.mode == "gray" else (3 + (3 if self.orient_map else 0) + (1 if self.value_map else 0))
-        return self.frame_px * (4 * c + self._map_bytes * outs)
+        # (rgb_storage="float16": a colour map's three channels cost 6 bytes per pixel -- 1.5 float32 channels; _map_bytes is 4 on mode "rgb")
+        cc = 1.5 if self.rgb_storage == "float16" else 3
+        outs = (1 + self.n_orient) if self.mode == "gray" else (cc + (cc if self.orient_map else 0) + (1 if self._value_written else 0))
+        return int(self.frame_px * (4 * c + self._map_bytes * outs))
 
     def pyramid_bytes_per_frame(self):
         h, w, fc = self.frame_shape
@@ -939,6 +967,8 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
                 C.c_void_p(self.consts["cs"].ctypes.data), C.c_void_p(self.consts["end"].ctypes.data), self.n_orient,
                 self.clip_hi, C.c_void_p(self.cs.data_ptr()), C.c_void_p(self.end.data_ptr()), s))
         else:
+            if self.rgb_storage == "float16":
+                raise ValueError("rgb_storage='float16' has no per-op filter pass (silent_rgb_line_end writes float32): use run_chain_h")
             self.ctx.check(self._lib.silent_rgb_line_end_dev(
                 self.ctx.handle, C.c_void_p(self.pyr.data_ptr()), self.levels_c, self.n_levels, self.batch,
                 C.byref(self._params), C.c_void_p(self.orient.data_ptr()) if self.orient is not None else None,
@@ -948,12 +978,33 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
     def run_filters_keypoints(self, stream=None):
         """rgb, selection without the intermediate colour maps: chain + a-10 -> a-9 -> a-8 -> a-11 in one C-ABI call
         (silent_rgb_keypoints_dev): the chain kernel accumulates the per-level extrema of a-10 itself."""
+        if self.rgb_storage == "float16":
+            raise ValueError("rgb_storage='float16' has no float32 fused step (silent_rgb_keypoints writes float32 maps into buffers of half "
+                             "the size): use run_chain_h")
         s = stream or self._stream()
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         self.ctx.check(self._lib.silent_rgb_keypoints_dev(
             self.ctx.handle, p(self.pyr), self.levels_c, self.n_levels, self.batch, C.byref(self._params), self.top_percent,
             self.regions, p(self.orient), p(self.line_end), p(self.value), p(self.peak_value), p(self.kp_idx), self.kp_cap,
             p(self.kp_counts), s))
+
+    def run_chain_h(self, stream=None):
+        """rgb, rgb_storage="float16": the chain with float16 orient / line_end maps and the keypoints.  selection=True:
+        silent_rgb_keypoints_h_dev (chain + selection tail in one call); selection=False: silent_rgb_line_end_h_dev, then the
+        keypoints from the float32 value map (silent_max_value_indices_region_dev) -- the float32 pipeline's, bit for bit."""
+        s = stream or self._stream()
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        h = lambda t: _lib.half_ptr(t.data_ptr()) if t is not None else None
+        geom = (self.levels_c, self.n_levels, self.batch)
+        if self.selection:
+            self.ctx.check(self._lib.silent_rgb_keypoints_h_dev(
+                self.ctx.handle, p(self.pyr), *geom, C.byref(self._params), self.top_percent, self.regions, h(self.orient),
+                h(self.line_end), p(self.value), p(self.peak_value), p(self.kp_idx), self.kp_cap, p(self.kp_counts), s))
+            return
+        self.ctx.check(self._lib.silent_rgb_line_end_h_dev(
+            self.ctx.handle, p(self.pyr), *geom, C.byref(self._params), h(self.orient), h(self.line_end), p(self.value), s))
+        self.ctx.check(self._lib.silent_max_value_indices_region_dev(
+            self.ctx.handle, p(self.value), *geom, self.regions, p(self.kp_idx), self.kp_cap, p(self.kp_counts), s))
 
     def sparse_tail_stats(self):
         """What the sparse keypoint tail of the last fused step did: dict(ran, pairs, dense_pairs, candidates)."""
@@ -963,6 +1014,8 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
                 "candidates": int(st[3])}
 
     def run_keypoints(self, stream=None):
+        if self.rgb_storage == "float16":
+            raise ValueError("rgb_storage='float16' has no per-op keypoint pass (the per-op kernels read float32 maps): use run_chain_h")
         s = stream or self._stream()
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # (no value map: the selection takes it from line_end)
         geom = (self.levels_c, self.n_levels, self.batch)
@@ -1040,6 +1093,8 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
         s = C.c_void_p(cs.cuda_stream)
         if self.mode == "gray":
             self.run_gray_pass(frames, s, parts=_lib.GRAY_PART_FILTER)
+        elif self.rgb_storage == "float16":
+            self.run_chain_h(s)
         elif self.selection and not self.keep_selection_maps:
             self.run_filters_keypoints(s)
         else:
@@ -1212,7 +1267,9 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
                 self.run_gray_pass(frames, s)
             return
         self.run_pyramid(frames, s)
-        if self.selection and not self.keep_selection_maps:
+        if self.rgb_storage == "float16":
+            self.run_chain_h(s)
+        elif self.selection and not self.keep_selection_maps:
             self.run_filters_keypoints(s)
         else:
             self.run_filters(s)
@@ -1238,9 +1295,10 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
                         out[name] = P(getattr(self, name), self.extents, 1, self.batch)
                 self._keypoint_outputs(out, allow_truncated)
         else:
+            dt = np.float16 if self.rgb_storage == "float16" else np.float32
             if self.orient is not None:
-                out["orient"] = P(self.orient, self.extents, 3, self.batch)
-            out["line_end"] = P(self.line_end, self.extents, 3, self.batch)
+                out["orient"] = P(self.orient, self.extents, 3, self.batch, dtype=dt)
+            out["line_end"] = P(self.line_end, self.extents, 3, self.batch, dtype=dt)
             if self.value_map:
                 out["value"] = P(self.value, self.extents, 1, self.batch)
             if self.selection:
