@@ -516,6 +516,56 @@ int silent_pyramid_yuv16_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, c
 int silent_yuv16_to_rgb(silent_ctx* ctx, const silent_yuv16_frames* frames, int n_frames, int H, int W, float* rgb);
 int silent_yuv16_to_rgb_dev(silent_ctx* ctx, const silent_yuv16_frames* frames, int n_frames, int H, int W, float* rgb, silent_stream stream);
 
+/* Raw 8-bit Bayer mosaics, read in place: what machine-vision and robotics cameras on GigE Vision, USB3 Vision or MIPI deliver
+ * (BayerRG8 / BayerGR8 / BayerGB8 / BayerBG8) -- ONE BYTE per pixel, the colours in a 2 x 2 pattern, a third of packed BGR.  One plane:
+ * m(f, y, x) is the byte at data + f * frame_stride + y * row_stride + x * pixel_stride, strides in bytes and positive, frame and row
+ * terms 64-bit -- a pitched buffer, a window of a larger sensor image and every-second-byte layouts are all just strides.  H, W >= 2,
+ * odd extents allowed.
+ * pattern names the top-left 2 x 2 cell of THE VIEW THAT IS PASSED (a window that starts on an odd row or column of a sensor has another
+ * name than the sensor):            red at (y & 1, x & 1)   blue at
+ *     0  rggb (BayerRG8)                 (0, 0)             (1, 1)
+ *     1  grbg (BayerGR8)                 (0, 1)             (1, 0)
+ *     2  gbrg (BayerGB8)                 (1, 0)             (0, 1)
+ *     3  bggr (BayerBG8)                 (1, 1)             (0, 0)
+ * order: 0 = channels (b, g, r), 1 = (r, g, b).
+ * The conversion is BILINEAR demosaicing in registers at the kernels' loads.  Indices outside the frame are reflected without repeating
+ * the edge (-1 -> 1, H -> H - 2, the same along x): reflection keeps the parity of an index, so a reflected neighbour has the colour
+ * its position calls for.  Every pixel gets three float32 channels:
+ *     at a red or blue site:  its own colour (float)m(y, x);  green (m(y-1,x) + m(y+1,x) + m(y,x-1) + m(y,x+1)) * 0.25;  the opposite
+ *                             colour (the four diagonal neighbours) * 0.25
+ *     at a green site:        green (float)m(y, x);  the colour whose samples lie in the same row (m(y,x-1) + m(y,x+1)) * 0.5;  the other
+ *                             colour (m(y-1,x) + m(y+1,x)) * 0.5
+ * Each sum is an integer (at most 1020), converted once to float32 and multiplied once by 0.25 or 0.5 -- all exact: the value is a
+ * multiple of 1/4 in [0, 255], is NOT rounded to an integer and has the same bits in any evaluation order.
+ * This is NOT OpenCV's COLOR_Bayer*2BGR, which rounds to uint8 and treats the border differently; and OpenCV's pattern names are
+ * shifted against the sensor's (its "BayerBG" is a sensor's RGGB): go by the table above, not by OpenCV's constant.
+ * pyr is IDENTICAL, bit for bit, to silent_pyramid[_dev] on the frames silent_bayer_to_rgb[_dev] writes for the same struct, on every
+ * route: the walk kernel, union plans with their border blocks (inside and behind the walk's launch), per-level plans, the unit +
+ * region kernels, every SILENT_TUNE_PYRAMID value.  A crop of a plan that starts on an odd row or column reads the FRAME's parity.
+ * Reads: every load is ONE BYTE that is some pixel of the view -- nothing between pixels (pixel_stride > 1), nothing behind a row's W
+ * pixels, nothing outside [data, data + span), span = (n - 1) frame_stride + (H - 1) row_stride + (W - 1) pixel_stride + 1.  The frame
+ * stride is not read when n_frames == 1.
+ * Refusals, before any launch or staging: a NULL ctx; SILENT_E_INVALID for a NULL plan / struct / data, a pattern outside 0 .. 3, an
+ * order outside 0 .. 1, H or W below 2, a pixel stride < 1, a row stride below (W - 1) pixel_stride + 1, a frame stride below the
+ * frame's extent (n_frames > 1), a span above 2^63 - 1 bytes; then a NULL pyr / rgb, a plan of another context, n_frames < 1
+ * (SILENT_E_INVALID), a single-channel plan or a SILENT_PLAN_ACCUM_F64 plan (SILENT_E_UNSUPPORTED).
+ * The host forms refuse everything their _dev forms refuse before anything is staged, and stage the view's span, not a byte more.  The
+ * _dev forms are stream-ordered and asynchronous; the struct is dead at return.
+ * silent_bayer_to_rgb[_dev] writes the converted frames themselves, [n_frames, H, W, 3] float32, with the same device function, one
+ * thread per pixel; H and W are arguments, refusals as above under its own name.  8-bit mosaics only: 10 / 12 / 16-bit mosaics, a
+ * gray value from a mosaic and higher-order demosaicing are not provided.  (ABI additions only: SILENT_ABI_VERSION is unchanged.) */
+typedef struct silent_bayer_frames {
+    const uint8_t* data;
+    int64_t pixel_stride, row_stride, frame_stride;
+    int32_t pattern;
+    int32_t order;
+} silent_bayer_frames;
+int silent_pyramid_bayer(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_bayer_frames* frames, int n_frames, float* pyr);
+int silent_pyramid_bayer_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_bayer_frames* frames, int n_frames, float* pyr,
+                             silent_stream stream);
+int silent_bayer_to_rgb(silent_ctx* ctx, const silent_bayer_frames* frames, int n_frames, int H, int W, float* rgb);
+int silent_bayer_to_rgb_dev(silent_ctx* ctx, const silent_bayer_frames* frames, int n_frames, int H, int W, float* rgb, silent_stream stream);
+
 /* uint16 frames, read as they are: 10 / 12 / 16-bit machine-vision and scientific cameras (Mono10 / Mono12 / Mono16), thermal and
  * depth sensors (Y16, Z16), 16-bit TIFF / PNG, and the luma of the P010 / P016 surfaces a hardware decoder hands over for 10-bit
  * HEVC / AV1.  The twins of the *_u8 entry points -- same argument lists, maps_f16 / parts / stream arguments, status codes and order

@@ -118,6 +118,13 @@ class Yuv16Frames(C.Structure):
                 ("shift", C.c_int32), ("depth", C.c_int32)]
 
 
+class BayerFrames(C.Structure):
+    """silent_bayer_frames (include/silent_hip.h): a batch of raw 8-bit Bayer mosaics -- one byte plane, three BYTE strides, the pattern
+    (0 .. 3: rggb, grbg, gbrg, bggr -- the top-left 2 x 2 cell of the view) and the channel order (0: bgr, 1: rgb)."""
+    _fields_ = [("data", C.c_void_p), ("pixel_stride", C.c_int64), ("row_stride", C.c_int64), ("frame_stride", C.c_int64),
+                ("pattern", C.c_int32), ("order", C.c_int32)]
+
+
 class SilentLibraryError(RuntimeError):
     """libsilent_hip.so is missing or cannot be loaded."""
 
@@ -135,6 +142,7 @@ _np = C.POINTER(Nv12Frames)   # an NV12 batch (silent_pyramid_nv12, silent_nv12_
 _pp = C.POINTER(P010Frames)   # a P010 batch (silent_pyramid_p010, silent_p010_to_rgb); p010_ptr() makes one from _runtime.p010_frames_of's tuple
 _yp = C.POINTER(YuvFrames)    # a planar / packed YUV batch (silent_pyramid_yuv, silent_yuv_to_rgb); yuv_ptr() makes one from _runtime.yuv_frames_of's tuple
 _y16p = C.POINTER(Yuv16Frames)  # a 16-bit YUV batch (silent_pyramid_yuv16, silent_yuv16_to_rgb); yuv16_ptr() makes one from _runtime.yuv16_frames_of's tuple
+_byp = C.POINTER(BayerFrames)   # a batch of Bayer mosaics (silent_pyramid_bayer, silent_bayer_to_rgb); bayer_ptr() makes one from _runtime.bayer_frames_of's tuple
 _ep = C.POINTER(Extent)
 _i, _u, _f, _d, _sz = C.c_int, C.c_uint, C.c_float, C.c_double, C.c_size_t
 
@@ -192,6 +200,10 @@ _SIGNATURES = {
     "silent_pyramid_yuv16_dev": [_vp, _vp, _y16p, _i, _fp, _vp],
     "silent_yuv16_to_rgb": [_vp, _y16p, _i, _i, _i, _fp],
     "silent_yuv16_to_rgb_dev": [_vp, _y16p, _i, _i, _i, _fp, _vp],
+    "silent_pyramid_bayer": [_vp, _vp, _byp, _i, _fp],
+    "silent_pyramid_bayer_dev": [_vp, _vp, _byp, _i, _fp, _vp],
+    "silent_bayer_to_rgb": [_vp, _byp, _i, _i, _i, _fp],
+    "silent_bayer_to_rgb_dev": [_vp, _byp, _i, _i, _i, _fp, _vp],
     "silent_gray_pass_u8": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8x3": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i],
     "silent_gray_pass_u8_dev": [_vp, _vp, _bp, _i, _fp, _fp, _i, _f, _fp, _vp, _vp, _i, _u, _vp],
@@ -350,6 +362,11 @@ def yuv_ptr(frames):
 def yuv16_ptr(frames):
     """_runtime.yuv16_frames_of's tuple as the const silent_yuv16_frames* of the 16-bit YUV entry points."""
     return struct_ptr(Yuv16Frames, frames)
+
+
+def bayer_ptr(frames):
+    """_runtime.bayer_frames_of's tuple as the const silent_bayer_frames* of the Bayer entry points."""
+    return struct_ptr(BayerFrames, frames)
 
 
 def gray_entry(family, frame_dtype="float32", frame_channels=1, storage="float32", dev=False, parts=None, frame_layout="packed"):

@@ -1073,6 +1073,9 @@ YUV_SHIFTS = {"yuv420": (1, 1), "yuv422": (1, 0), "yuv444": (0, 0)}
 YUV16_FORMATS = dict(("yuv%sp%d%s" % (x, d, a), (sx, sy, d, 16 - d if a else 0))
                      for x, (sx, sy) in (("420", (1, 1)), ("422", (1, 0)), ("444", (0, 0)))
                      for d, a in ((10, ""), (12, ""), (10, "msb"), (12, "msb"), (16, "")))
+# and the formats that take ONE uint8 view [n, H, W] of a raw Bayer mosaic: rgb_frame_format -> pattern of silent_bayer_frames (the
+# top-left 2 x 2 cell of the VIEW: red at (pattern >> 1, pattern & 1))
+BAYER_FORMATS = {"bayer_rggb": 0, "bayer_grbg": 1, "bayer_gbrg": 2, "bayer_bggr": 3}
 NV12_MATRICES = {"bt601": (.299, .114), "bt709": (.2126, .0722)}      # (Kr, Kb)
 NV12_RANGES = ("limited", "full")
 NV12_ORDERS = ("bgr", "rgb")
@@ -1092,11 +1095,36 @@ def check_rgb_frame_format(rgb_frame_format, mode="rgb", rgb_frame_dtype="float3
     name gives the chroma subsampling -- read in place by silent_pyramid_yuv) or one of YUV16_FORMATS, "yuv420p10" ... "yuv444p16" (the
     same triple as UINT16 views, read in place by silent_pyramid_yuv16: "yuvXp10" / "yuvXp12" with the code in the low bits, FFmpeg's
     yuvXp10le / yuvXp12le; "yuvXp10msb" / "yuvXp12msb" with the code in the high bits, P210 / P410 / Y210; "yuvXp16").  The name is checked first; then the mode; then that the format is not combined with
-    rgb_frame_dtype="uint8", rgb_frame_layout="strided" or the gray frame_* keywords; then that H and W (hw, when given) are even ("yuv422": W; "yuv444": nothing)."""
-    if not isinstance(rgb_frame_format, str) or rgb_frame_format not in RGB_FRAME_FORMATS + tuple(YUV_SHIFTS) + tuple(YUV16_FORMATS):
+    rgb_frame_dtype="uint8", rgb_frame_layout="strided" or the gray frame_* keywords; then that H and W (hw, when given) are even ("yuv422": W; "yuv444": nothing).
+    One of BAYER_FORMATS, "bayer_rggb" / "bayer_grbg" / "bayer_gbrg" / "bayer_bggr": the frames are ONE uint8 view [n, H, W] of a raw
+    Bayer mosaic (any positive strides), read in place by silent_pyramid_bayer and demosaiced in registers; the same refusals, and H
+    and W of at least 2 (odd extents are fine)."""
+    if not isinstance(rgb_frame_format, str) or rgb_frame_format not in RGB_FRAME_FORMATS + tuple(YUV_SHIFTS) + tuple(YUV16_FORMATS) + tuple(BAYER_FORMATS):
+        # (the text up to here is as it was; a name that reads like a Bayer format gets the Bayer names appended)
+        bayer = isinstance(rgb_frame_format, str) and rgb_frame_format.lower().startswith("bayer")
         raise ValueError("rgb_frame_format must be 'interleaved' or 'nv12', or 'p010' / 'p012' / 'p016', or 'yuv420' / 'yuv422' / "
                          "'yuv444', got %r (or, for uint16 planes, 'yuvXp10' / 'yuvXp12' / 'yuvXp10msb' / 'yuvXp12msb' / 'yuvXp16' with X "
-                         "one of 420, 422, 444)" % (rgb_frame_format,))
+                         "one of 420, 422, 444)%s" % (rgb_frame_format, " (or, for raw Bayer mosaics, 'bayer_rggb' / 'bayer_grbg' / 'bayer_gbrg' / "
+                                                      "'bayer_bggr'; util.zoom.BAYER_LAYOUTS maps the GenICam names)" if bayer else ""))
+    if rgb_frame_format in BAYER_FORMATS:
+        name = "rgb_frame_format=%r" % (rgb_frame_format,)
+        if mode != "rgb":
+            raise ValueError("%s is for mode 'rgb' (a gray value from a mosaic is not provided)" % name)
+        if rgb_frame_dtype != "float32":
+            raise ValueError("%s does not combine with rgb_frame_dtype=%r (the mosaic is uint8, one byte per pixel; the converted "
+                             "channels are float32)" % (name, rgb_frame_dtype))
+        if rgb_frame_layout != "packed":
+            raise ValueError("%s does not combine with rgb_frame_layout=%r (the mosaic carries its own strides)" % (name, rgb_frame_layout))
+        if frame_dtype != "float32":
+            raise ValueError("%s does not combine with frame_dtype=%r (frame_dtype describes the frames of mode 'gray')" % (name, frame_dtype))
+        if frame_channels != 1:
+            raise ValueError("%s does not combine with frame_channels=%r (frame_channels describes the frames of mode 'gray')"
+                             % (name, frame_channels))
+        if frame_layout != "packed":
+            raise ValueError("%s does not combine with frame_layout=%r (frame_layout describes the frames of mode 'gray')" % (name, frame_layout))
+        if hw is not None and min(int(hw[0]), int(hw[1])) < 2:
+            raise ValueError("%s needs H and W of at least 2, got %s" % (name, tuple(int(v) for v in hw)))
+        return rgb_frame_format
     if rgb_frame_format != "interleaved":
         name = "rgb_frame_format=%r" % (rgb_frame_format,)
         src, sx, sy = rgb_source(rgb_frame_format)[:3]
@@ -1403,6 +1431,67 @@ def yuv16_to_rgb(planes, hw, fmt="yuv420p10", nv12_matrix="bt709", nv12_range="l
     return _to_rgb("yuv16", fmt, planes, hw, lambda: yuv16_frames_of(planes, hw, fmt, m, oy, oc), device)
 
 
+# Raw Bayer mosaics: neither a pair nor a triple -- ONE uint8 view -- so a description outside RGB_SOURCES (kind: the stem of
+# silent_pyramid_bayer / silent_bayer_to_rgb and of _lib.bayer_ptr) and functions of its own.
+BAYER_SOURCE = RgbSource("bayer", "Bayer", 1, 1, "uint8", None, False)
+
+
+def check_bayer_conversion(rgb_frame_format, nv12_matrix="bt709", nv12_range="limited", nv12_order="bgr"):
+    """The nv12_* keywords beside a Bayer rgb_frame_format: nv12_order selects the channel order as for every other source ("bgr" ->
+    0, "rgb" -> 1: returned); a non-default nv12_matrix or nv12_range is refused -- a mosaic has no YUV matrix and no range, the
+    keyword would silently mean nothing."""
+    name = "rgb_frame_format=%r" % (rgb_frame_format,)
+    if not (isinstance(nv12_matrix, str) and nv12_matrix == "bt709"):
+        raise ValueError("%s does not combine with nv12_matrix (a Bayer mosaic is demosaiced, no YUV matrix is applied)" % name)
+    if not (isinstance(nv12_range, str) and nv12_range == "limited"):
+        raise ValueError("%s does not combine with nv12_range=%r (a Bayer mosaic has no YUV range)" % (name, nv12_range))
+    if nv12_order not in NV12_ORDERS:
+        raise ValueError("nv12_order must be 'bgr' or 'rgb', got %r" % (nv12_order,))
+    return NV12_ORDERS.index(nv12_order)
+
+
+def bayer_frames_of(frames, hw, fmt, nv12_order="bgr"):
+    """A batch of raw 8-bit Bayer mosaics -- a uint8 ndarray or a uint8 GPU tensor [n, H, W] or [n, H, W, 1], ANY view with positive
+    strides (a pitched buffer, a window of a larger sensor image, every second byte); ``fmt`` (one of BAYER_FORMATS) names the top-left
+    2 x 2 cell of THIS view -- as what _lib.bayer_ptr takes: (address, pixel_stride, row_stride, frame_stride (BYTES), pattern, order).
+    Returns (that tuple, n, on_device).  Nothing is converted or copied."""
+    if fmt not in BAYER_FORMATS:
+        raise ValueError("fmt must be one of %s, got %r" % (", ".join(BAYER_FORMATS), fmt))
+    order = check_bayer_conversion(fmt, nv12_order=nv12_order)
+    dev = is_torch_tensor(frames)
+    if not dev and not isinstance(frames, np.ndarray):
+        raise TypeError(TYPE_ERROR_MESSAGE)
+    h, w = int(hw[0]), int(hw[1])
+    if min(h, w) < 2:
+        raise ValueError("rgb_frame_format=%r needs H and W of at least 2, got %s" % (fmt, (h, w)))
+    shape, st, address = _plane_geometry(BAYER_SOURCE, frames)
+    if len(shape) == 4 and shape[3] == 1:
+        shape, st = shape[:3], st[:3]
+    if len(shape) != 3 or shape[1:] != (h, w) or shape[0] < 1:
+        raise ValueError("a Bayer mosaic batch must be [n, %d, %d] or [n, %d, %d, 1], got %s" % (h, w, h, w, tuple(int(s) for s in frames.shape)))
+    n = shape[0]
+    # (a stride of an axis of extent 1 is never used: the smallest legal value stands in for it)
+    ps, rs = st[2], st[1]
+    fs = st[0] if n > 1 else (h - 1) * rs + (w - 1) * ps + 1
+    if ps < 1 or rs < (w - 1) * ps + 1 or fs < (h - 1) * rs + (w - 1) * ps + 1:
+        raise ValueError("Bayer mosaics: rows or frames overlap, or a stride is not positive (strides %s)" % (st,))
+    return (address, ps, rs, fs, BAYER_FORMATS[fmt], order), n, dev
+
+
+def bayer_to_rgb(frames, hw, fmt, nv12_order="bgr", device=None):
+    """The float32 frames [n, H, W, 3] the pyramid kernels see for a batch of Bayer mosaics of format ``fmt`` (silent_bayer_to_rgb[_dev]:
+    the loaders' own device function, one thread per pixel): bilinear demosaicing on the 0 .. 255 scale, multiples of 1/4, not rounded
+    -- for display, and as the reference of the bit-identity contract.  frames: bayer_frames_of.  This is not OpenCV's
+    COLOR_Bayer*2BGR (which rounds to uint8 and treats borders differently), and OpenCV's pattern names are shifted against the
+    sensor's."""
+    args = bayer_frames_of(frames, hw, fmt, nv12_order)
+    op = _SourceOperand(BAYER_SOURCE, (frames,), hw, args, None if device is None else get_context(device))
+    h, w = int(hw[0]), int(hw[1])
+    out, optr = op.empty((op.n_frames, h, w, 3))
+    op.call("bayer_to_rgb", op.ptr, op.n_frames, h, w, optr)
+    return out
+
+
 class PyramidPlan(object):
     """Tap tables of one (frame size, level geometry) on the device.  ``levels`` is a list of dicts / tuples
     (src_y0, src_x0, src_h, src_w, zoom_h, zoom_w, out_h, out_w).  accumulation="float64" (single-channel plans): every op of
@@ -1486,6 +1575,15 @@ class PyramidPlan(object):
         mode = "gray" if self.frame_shape[2] == 1 else "rgb"
         fmt = check_rgb_frame_format(rgb_frame_format, mode, rgb_frame_dtype, rgb_frame_layout, frame_dtype, frame_channels, frame_layout,
                                      self.frame_shape[:2])
+        if fmt in BAYER_FORMATS:
+            # a raw Bayer mosaic: ONE uint8 view [n, H, W] read in place and demosaiced in registers (silent_pyramid_bayer), the pyramid
+            # of the float32 call on bayer_to_rgb(frames, hw, fmt) bit for bit.  nv12_order: the channel order; a matrix or a range
+            # beside a mosaic is refused
+            check_bayer_conversion(fmt, nv12_matrix, nv12_range, nv12_order)
+            op = _SourceOperand(BAYER_SOURCE, (frames,), self.frame_shape[:2], bayer_frames_of(frames, self.frame_shape[:2], fmt, nv12_order), self.ctx)
+            out, optr = op.empty(op.n_frames * self.frame_px * 3)
+            op.call("pyramid_bayer", self.handle, op.ptr, op.n_frames, optr)
+            return PackedPyramid(out, self.extents, 3, op.n_frames)
         if fmt != "interleaved":
             # a YUV-family source (rgb_source): the planes read in place (silent_pyramid_<kind>; the format's coefficients --
             # p010_coefficients also knows "bt2020"), the pyramid of the float32 call on <kind>_to_rgb(frames) bit for bit

@@ -104,19 +104,19 @@ HOST_ASAN_FLAGS = ["--offload-host-only", "-cuid=silenthost", "-DSILENT_HOST_ONL
                    "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 # tests/gray_bytes_host_main.cpp, once per frame type: the entry-point suffix and the bytes of one frame pixel
 HOST_DRIVERS = {"u8": ["-DSILENT_SFX=_u8", "-DSILENT_FRAME_BYTES=1"], "u8x3": ["-DSILENT_SFX=_u8x3", "-DSILENT_FRAME_BYTES=3"],
-                "f32": ["-DSILENT_FRAME_BYTES=4"], "view": [], "u16": [], "rgb8": [], "rgb8_view": [], "rgb_nv12": [], "rgb_p010": [], "rgb_yuv": [], "rgb_yuv16": [], "plan_tables": [], "kp_tables": [], "attn_tables": [], "rgb_h": []}
+                "f32": ["-DSILENT_FRAME_BYTES=4"], "view": [], "u16": [], "rgb8": [], "rgb8_view": [], "rgb_nv12": [], "rgb_p010": [], "rgb_yuv": [], "rgb_yuv16": [], "rgb_bayer": [], "plan_tables": [], "kp_tables": [], "attn_tables": [], "rgb_h": []}
 # "view": the strided *_view entry points have a driver of their own (both channel counts in one program); "u16": so have the twelve
 # uint16 entry points (*_u16 and *_view16); "rgb8": and silent_pyramid_rgb8[_dev] (uint8 colour frames of 3-channel plans); "rgb8_view": and silent_pyramid_rgb8_view[_dev] (strided
 # views of such frames, with the walk loader's address enumeration); "rgb_nv12": and silent_pyramid_nv12[_dev] / silent_nv12_to_rgb[_dev]
 # (NV12 surfaces, with the same enumeration for the luma and chroma planes); "rgb_p010": and silent_pyramid_p010[_dev] /
 # silent_p010_to_rgb[_dev] (P010 / P012 / P016 surfaces: uint16 elements, the enumeration with element alignment); "rgb_yuv": and
 # silent_pyramid_yuv[_dev] / silent_yuv_to_rgb[_dev] (planar and packed 8-bit YUV: three planes, the merged staging, the enumeration
-# per layout); "rgb_yuv16": and silent_pyramid_yuv16[_dev] / silent_yuv16_to_rgb[_dev] (the same for uint16 elements: even offsets); "plan_tables": and silent_pyramid_plan_create_ex (every scalar and table of a plan as text, its allocation-failure exits under LeakSanitizer); "kp_tables": and the keypoint tail's host planning (region tables, summary geometry, workspace layout, cell tables, boost parameters as text); "attn_tables": and
+# per layout); "rgb_bayer": and silent_pyramid_bayer[_dev] / silent_bayer_to_rgb[_dev] (raw Bayer mosaics: the enumeration of the three-row loader with its neighbour columns); "rgb_yuv16": and silent_pyramid_yuv16[_dev] / silent_yuv16_to_rgb[_dev] (the same for uint16 elements: even offsets); "plan_tables": and silent_pyramid_plan_create_ex (every scalar and table of a plan as text, its allocation-failure exits under LeakSanitizer); "kp_tables": and the keypoint tail's host planning (region tables, summary geometry, workspace layout, cell tables, boost parameters as text); "attn_tables": and
 # silent_attention_tail[_dev] / silent_attention_extents (argument validation, the planned tables of the two launches and the workspace layout as text); "rgb_h": and
 # silent_rgb_line_end_h[_dev] / silent_rgb_keypoints_h[_dev] (every refusal of the float16-storage RGB entry points in order, beside their float32 twins')
 HOST_DRIVER_SOURCES = {"view": "gray_view_host_main.cpp", "u16": "gray_u16_host_main.cpp", "rgb8": "rgb8_host_main.cpp",
                        "rgb8_view": "rgb8_view_host_main.cpp", "rgb_nv12": "rgb_nv12_host_main.cpp", "rgb_p010": "rgb_p010_host_main.cpp", "rgb_yuv": "rgb_yuv_host_main.cpp",
-                       "rgb_yuv16": "rgb_yuv16_host_main.cpp", "plan_tables": "plan_tables_host_main.cpp", "kp_tables": "kp_tables_host_main.cpp", "attn_tables": "attention_tail_host_main.cpp", "rgb_h": "rgb_h_host_main.cpp"}
+                       "rgb_yuv16": "rgb_yuv16_host_main.cpp", "rgb_bayer": "rgb_bayer_host_main.cpp", "plan_tables": "plan_tables_host_main.cpp", "kp_tables": "kp_tables_host_main.cpp", "attn_tables": "attention_tail_host_main.cpp", "rgb_h": "rgb_h_host_main.cpp"}
 
 
 def _fresh(out, dep):

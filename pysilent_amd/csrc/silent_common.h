@@ -358,9 +358,18 @@ template <typename FT>
 constexpr bool kFrameYuvWide = kFrameP010<FT> || kFrameYuv16<FT>;
 template <typename FT>
 constexpr bool kFrameYuvFamily = kFrameYuvPair<FT> || kFrameYuvTriple<FT>;
-// the 3-channel kinds that are read through a `src` struct with at(y, x, ch) / atf(y, i) (strided colour views and the YUV family)
+// raw 8-bit Bayer mosaics (silent_pyramid_bayer): one byte per pixel in a strided view, demosaiced at the load (below)
+struct FrameBayer {
+    const unsigned char* data;
+    long long pixel_stride, row_stride, frame_stride;   // bytes
+    int H, W;                                            // the frame's extents: the neighbourhood is reflected at the FRAME's edges
+    int pattern, order;                                  // 0 .. 3: rggb, grbg, gbrg, bggr; 0: bgr, 1: rgb
+};
 template <typename FT>
-constexpr bool kFrameRgbSrc = kFrameRgbView<FT> || kFrameYuvFamily<FT>;
+constexpr bool kFrameBayer = std::is_same<FT, FrameBayer>::value;
+// the 3-channel kinds that are read through a `src` struct with at(y, x, ch) / atf(y, i) (strided colour views, the YUV family, mosaics)
+template <typename FT>
+constexpr bool kFrameRgbSrc = kFrameRgbView<FT> || kFrameYuvFamily<FT> || kFrameBayer<FT>;
 __device__ __forceinline__ float nv12_channel(float yv, float uv, float vv, float m0, float m1, float m2) {
     return fminf(fmaxf(__fadd_rn(__fadd_rn(__fmul_rn(yv, m0), __fmul_rn(uv, m1)), __fmul_rn(vv, m2)), 0.0f), 255.0f);
 }
@@ -553,11 +562,98 @@ __device__ __forceinline__ frame_src<FT> frame_of(const FT& f, int frame) {
     return s;
 }
 
+// Raw 8-bit Bayer mosaics (silent_pyramid_bayer, 3-channel plans only): m(y, x) is the byte at data + frame * frame_stride +
+// y * row_stride + x * pixel_stride (64-bit bytes), one colour sample per pixel in a 2 x 2 pattern whose name is that of the top-left
+// cell of THE VIEW: red sits at (y & 1, x & 1) == (pattern >> 1, pattern & 1), blue on the other diagonal site, green on the two others.
+// Bilinear demosaicing, with indices outside the frame reflected without repeating the edge (-1 -> 1, n -> n - 2: the parity of an index
+// is kept, so a reflected neighbour has the colour its position calls for):
+//     at a red / blue site:  own colour (float)m(y, x);  green (m(y-1,x) + m(y+1,x) + m(y,x-1) + m(y,x+1)) * 0.25;  the opposite colour
+//                            the four diagonal neighbours * 0.25
+//     at a green site:       green (float)m(y, x);  the colour of the same row (m(y,x-1) + m(y,x+1)) * 0.5;  the other (m(y-1,x) + m(y+1,x)) * 0.5
+// -- every sum an integer (at most 1020), converted once (exact) and multiplied once by a power of two (exact): a multiple of 1/4 in
+// [0, 255], NOT rounded to an integer, the same bits in any evaluation order.  This is not OpenCV's COLOR_Bayer*2BGR (which rounds to
+// uint8 and treats the border differently), and OpenCV's pattern names are shifted against the sensor's.
+// bayer_rgb is THE conversion: c the pixel's own sample, h / v / d the SUMS of its two horizontal, two vertical and four diagonal
+// neighbours (the parts of the 3 x 3 neighbourhood a site can need), (py, px) the parities of its frame row and column.  The loader of
+// the walk kernel, BayerSrc::at (unit, region and border kernels) and source_to_rgb_kernel (silent_bayer_to_rgb) all go through it.
+// Integer arguments: a uint16 twin passes wider samples and another scale.
+__device__ __forceinline__ void bayer_rgb(int c, int h, int v, int d, int py, int px, int pattern, int order, float& c0, float& c1, float& c2) {
+    const bool red_row = py == (pattern >> 1), red_col = px == (pattern & 1);
+    const bool green = red_row != red_col;
+    const float g = green ? (float)c : __fmul_rn((float)(h + v), 0.25f);
+    // the colour whose samples share this row (green site) / the site's own colour, and the other one
+    const float a = green ? __fmul_rn((float)h, 0.5f) : (float)c;
+    const float b = green ? __fmul_rn((float)v, 0.5f) : __fmul_rn((float)d, 0.25f);
+    const float red = red_row ? a : b, blue = red_row ? b : a;
+    c0 = order ? red : blue;
+    c1 = g;
+    c2 = order ? blue : red;
+}
+// an index one step outside [0, n) reflected into it (n >= 2); host-callable: the walk loader's address function uses it
+__host__ __device__ __forceinline__ int bayer_reflect(int i, int n) { return i < 0 ? 1 : (i > n - 1 ? n - 2 : i); }
+// one frame of a batch of mosaics inside a kernel
+struct BayerSrc {
+    const unsigned char* p;
+    long long pixel_stride, row_stride;
+    int H, W, pattern, order;
+    // the three channels of pixel (x, y): nine byte loads, each the sample of a pixel of the frame
+    __device__ __forceinline__ void rgb(long long yy, long long x, float& c0, float& c1, float& c2) const {
+        const unsigned char* r1 = p + yy * row_stride;
+        const unsigned char* r0 = p + (long long)bayer_reflect((int)yy - 1, H) * row_stride;
+        const unsigned char* r2 = p + (long long)bayer_reflect((int)yy + 1, H) * row_stride;
+        const long long x1 = x * pixel_stride, x0 = (long long)bayer_reflect((int)x - 1, W) * pixel_stride,
+                        x2 = (long long)bayer_reflect((int)x + 1, W) * pixel_stride;
+        const int m00 = r0[x0], m01 = r0[x1], m02 = r0[x2], m10 = r1[x0], m11 = r1[x1], m12 = r1[x2], m20 = r2[x0], m21 = r2[x1], m22 = r2[x2];
+        bayer_rgb(m11, m10 + m12, m01 + m21, (m00 + m02) + (m20 + m22), (int)yy & 1, (int)x & 1, pattern, order, c0, c1, c2);
+    }
+    // channel ch of pixel (x, y) / float i of the virtual packed row y (pixel i / 3, channel i % 3)
+    __device__ __forceinline__ float at(long long yy, long long x, int ch) const {
+        float c0, c1, c2;
+        rgb(yy, x, c0, c1, c2);
+        return ch == 0 ? c0 : (ch == 1 ? c1 : c2);
+    }
+    // the same value from the PART of the neighbourhood this one channel needs -- the pixel's own sample, its horizontal pair, its
+    // vertical pair, both pairs, or the four diagonals: at most four byte loads, behind lane-divergent branches -- with zeros for the
+    // parts bayer_rgb does not read for it.  For the border pixels inside the walk kernel (pyramid_border_px, LEAN), whose register
+    // budget is the consumers': with at() there the kernel needs 81 VGPRs (5 waves per SIMD), with this 72 (7, like the other sources).
+    // Everywhere else the branches cost more than the loads they save (pyramid_unit_kernel: 256 VGPRs against 89).
+    __device__ __forceinline__ float at_parts(long long yy, long long x, int ch) const {
+        const bool red_row = ((int)yy & 1) == (pattern >> 1), green = red_row != (((int)x & 1) == (pattern & 1));
+        const bool own_or_row = (ch == (order ? 0 : 2)) == red_row;   // (ch != 1) the channel is the site's own colour / that of a green site's row
+        const bool need_c = ch == 1 ? green : (!green && own_or_row), need_h = ch == 1 ? !green : (green && own_or_row);
+        const bool need_v = ch == 1 ? !green : (green && !own_or_row), need_d = ch != 1 && !green && !own_or_row;
+        const unsigned char* r1 = p + yy * row_stride;
+        const long long up = (long long)(bayer_reflect((int)yy - 1, H) - (int)yy) * row_stride, down = (long long)(bayer_reflect((int)yy + 1, H) - (int)yy) * row_stride;
+        const long long x1 = x * pixel_stride, x0 = (long long)bayer_reflect((int)x - 1, W) * pixel_stride,
+                        x2 = (long long)bayer_reflect((int)x + 1, W) * pixel_stride;
+        int c = 0, h = 0, v = 0, d = 0;
+        if (need_c) c = r1[x1];
+        if (need_h) h = (int)r1[x0] + (int)r1[x2];
+        if (need_v) v = (int)r1[up + x1] + (int)r1[down + x1];
+        if (need_d) d = ((int)r1[up + x0] + (int)r1[up + x2]) + ((int)r1[down + x0] + (int)r1[down + x2]);
+        float c0, c1, c2;
+        bayer_rgb(c, h, v, d, (int)yy & 1, (int)x & 1, pattern, order, c0, c1, c2);
+        return ch == 0 ? c0 : (ch == 1 ? c1 : c2);
+    }
+    __device__ __forceinline__ float atf(long long yy, long long i) const {
+        const long long q = i / 3;
+        return at(yy, q, (int)(i - 3 * q));
+    }
+};
+template <>
+struct FrameKind<FrameBayer> {
+    typedef FrameBayer param;
+    typedef BayerSrc src;
+};
+__device__ __forceinline__ BayerSrc frame_of(const FrameBayer& f, int frame) {
+    return BayerSrc{f.data + (long long)frame * f.frame_stride, f.pixel_stride, f.row_stride, f.H, f.W, f.pattern, f.order};
+}
+
 // the frame types that exist for single-channel plans with float32 accumulation only
 template <typename FT>
 constexpr bool kFrameNarrow = kFrameBytes<FT> || kFrameRgb8<FT> || kFrameWords<FT> || kFrameStrided<FT>;
 template <typename FT>
-constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT> || kFrameYuvFamily<FT>;
+constexpr bool kFrameType = std::is_same<FT, float>::value || kFrameNarrow<FT> || kFrameRgbView<FT> || kFrameYuvFamily<FT> || kFrameBayer<FT>;
 // (host) the bytes of one frame pixel as the host-pointer forms stage it -- float frames carry the channels of the plan; a view is
 // staged by its span -- and the suffix of a frame type's entry points
 template <typename FT>
@@ -590,6 +686,11 @@ __device__ __forceinline__ float unit_edge_column(const StridedRgbSrc& src, int 
 // and of channel `ch` of a frame of the YUV family
 template <class D>
 __device__ __forceinline__ float unit_edge_column(const YuvSrcOps<D>& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
+                                                  int src_h, int src_y0, int lane) {
+    return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
+}
+// and of channel `ch` of a mosaic
+__device__ __forceinline__ float unit_edge_column(const BayerSrc& src, int ch, int col, int src_w, int src_x0, int y_first, int n_rows,
                                                   int src_h, int src_y0, int lane) {
     return src.at(mirror_near(y_first + min(lane, n_rows - 1), src_h) + src_y0, mirror_near(col, src_w) + src_x0, ch);
 }

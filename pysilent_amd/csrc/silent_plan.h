@@ -344,6 +344,33 @@ inline YuvStage yuv_stage(const S* v, size_t y_span, size_t c_span) {
     }
     return st;
 }
+// ------------------------------------------------------------------------------------------ raw Bayer mosaics
+// silent_pyramid_bayer / silent_bayer_to_rgb (silent_hip.h): neither a pair nor a triple -- one byte plane in a strided view, so a check
+// and a marshaller of its own.  What the struct refuses on its own for frames of H x W, in the header's order, and its span in bytes.
+using Bayer = silent::FrameBayer;
+inline int check_bayer(silent_ctx* ctx, const char* who, bool has_plan, long long H, long long W, const silent_bayer_frames* v, int n_frames, size_t* span) {
+    auto bad = [&](const std::string& what) { return fail(ctx, SILENT_E_INVALID, std::string(who) + ": " + what); };
+    if (!has_plan || !v || !v->data) return bad("NULL pointer");
+    if (v->pattern < 0 || v->pattern > 3) return bad("pattern must be 0 .. 3 (rggb, grbg, gbrg, bggr)");
+    if (v->order < 0 || v->order > 1) return bad("order must be 0 (bgr) or 1 (rgb)");
+    if (H < 2 || W < 2) return bad("Bayer mosaics need H and W of at least 2");
+    if (H > 0x7fffffffll || W > 0x7fffffffll) return bad("H and W must fit 31 bits");
+    if (v->pixel_stride < 1) return bad("pixel_stride is below 1");
+    typedef unsigned __int128 u128;
+    const u128 row = (u128)(W - 1) * (u128)v->pixel_stride + 1;
+    if (v->row_stride <= 0 || (u128)v->row_stride < row) return bad("row_stride is below (W - 1) * pixel_stride + 1");
+    const u128 frame = (u128)(H - 1) * (u128)v->row_stride + row;
+    if (n_frames > 1 && (v->frame_stride <= 0 || (u128)v->frame_stride < frame))
+        return bad("frame_stride is below (H - 1) * row_stride + (W - 1) * pixel_stride + 1");
+    const u128 all = (n_frames > 1 ? (u128)(n_frames - 1) * (u128)v->frame_stride : 0) + frame;
+    if (all > (u128)0x7fffffffffffffffll) return bad("the view spans more than 2^63 bytes");
+    if (span) *span = (size_t)all;
+    return SILENT_OK;
+}
+// the kernels' argument for a checked struct (the bytes at `data`: those of the struct, or their staged copy)
+inline Bayer bayer_frames(const silent_bayer_frames* v, const uint8_t* data, int n_frames, int H, int W) {
+    return Bayer{data, v->pixel_stride, v->row_stride, n_frames > 1 ? v->frame_stride : 0, H, W, v->pattern, v->order};
+}
 // The same for a silent_frame_view16: one uint16 element per pixel (the bounds of check_view with 2 for `channels`), and 2-byte alignment
 // of every address a kernel forms -- an even data address and even strides.
 inline int check_view16(silent_ctx* ctx, const char* who, const silent_pyramid_plan* plan, const silent_frame_view16* v, int n_frames, size_t* span) {

@@ -433,7 +433,7 @@ struct BorderTab {
 // FT: float, or unsigned char at C == 3 (packed interleaved uint8 colour frames: the byte widened at the load), or FrameStridedRgb
 // (the same bytes in a strided view, by value), or FrameNv12 / FrameP010 (an NV12 / P010 surface, by value: the channel converted at
 // the load), or FrameYuv (planar / packed 8-bit YUV, by value: three byte loads per tap), or FrameYuv16 (16-bit YUV, by value: three
-// 2-byte loads per tap)
+// 2-byte loads per tap), or FrameBayer (a raw mosaic, by value: the part of the tap's 3 x 3 neighbourhood its channel needs, up to four byte loads)
 template <int C, bool LEAN = false, typename FT = float>
 __device__ __forceinline__ void pyramid_border_px(frame_param<FT> frames, float* __restrict__ pyr, const PyrTab& tab,
                                                   const BorderTab& bt, long long gid, int n_frames) {
@@ -477,7 +477,11 @@ __device__ __forceinline__ void pyramid_border_px(frame_param<FT> frames, float*
     auto column = [&](int j) {
         if constexpr (kFrameRgbSrc<FT>) {
             const long long x = xi[j] + lv.src_x0;
-            float a = __builtin_fmaf(wy[0], src.at(yi[0] + lv.src_y0, x, ch), 0.0f);
+            auto tap = [&](long long yy) {
+                if constexpr (kFrameBayer<FT> && LEAN) return src.at_parts(yy, x, ch);   // (at most four loads instead of nine)
+                else return src.at(yy, x, ch);
+            };
+            float a = __builtin_fmaf(wy[0], tap(yi[0] + lv.src_y0), 0.0f);
 #pragma unroll
             for (int i = 1; i < 6; ++i) {
                 // (NV12 / P010 inside the walk kernel: a tap is two loads behind two 64-bit addresses; three taps in flight, not six -- the
@@ -489,7 +493,8 @@ __device__ __forceinline__ void pyramid_border_px(frame_param<FT> frames, float*
                 if constexpr (kFrameYuvTriple<FT> && LEAN) {
                     if (i == 2 || i == 4) asm volatile("" ::: "memory");
                 }
-                a = __builtin_fmaf(wy[i], src.at(yi[i] + lv.src_y0, x, ch), a);
+                if constexpr (kFrameBayer<FT> && LEAN) asm volatile("" ::: "memory");   // (a mosaic: up to four byte loads behind four 64-bit addresses a tap, ONE tap in flight: 72 VGPRs in the walk kernel, 7 waves per SIMD)
+                a = __builtin_fmaf(wy[i], tap(yi[i] + lv.src_y0), a);
             }
             return a;
         } else {
@@ -524,22 +529,27 @@ __global__ __launch_bounds__(256) void pyramid_border_kernel(frame_param<FT> fra
 }
 
 // ------------------------------------------------------------------------------------------ YUV family -> float32 frames
-// silent_nv12_to_rgb / silent_p010_to_rgb / silent_yuv_to_rgb / silent_yuv16_to_rgb: the frames the pyramid kernels see for a batch of
+// silent_nv12_to_rgb / silent_p010_to_rgb / silent_yuv_to_rgb / silent_yuv16_to_rgb / silent_bayer_to_rgb: the frames the pyramid kernels see for a batch of
 // frame kind FT, [n, H, W, 3] float32 -- one thread per pixel, the three channels through the loaders' own device functions (the kind's
 // yuv(), i.e. p010_values / yuv16_values for the uint16 kinds, + nv12_channel).  Blocks of 256 pixels of one frame.
 template <typename FT>
 __global__ __launch_bounds__(256) void source_to_rgb_kernel(const FT frames, float* __restrict__ rgb, int H, int W, int blocks_per_frame) {
-    static_assert(kFrameYuvFamily<FT>, "NV12 / P010 / YUV / 16-bit YUV surfaces");
+    static_assert(kFrameYuvFamily<FT> || kFrameBayer<FT>, "NV12 / P010 / YUV / 16-bit YUV surfaces, Bayer mosaics");
     const int frame = (int)(blockIdx.x / (unsigned)blocks_per_frame);
     const long long p = (long long)(blockIdx.x - (unsigned)frame * (unsigned)blocks_per_frame) * 256 + threadIdx.x;
     if (p >= (long long)H * W) return;
     const int y = (int)(p / W), x = (int)(p - (long long)y * W);
     const frame_src<FT> src = frame_of(frames, frame);
+    if constexpr (kFrameBayer<FT>) {   // silent_bayer_to_rgb: the pixel's 3 x 3 neighbourhood through bayer_rgb
+        float* __restrict__ dst = rgb + ((long long)frame * H * W + p) * 3;
+        src.rgb(y, x, dst[0], dst[1], dst[2]);
+    } else {
     float yv, uv, vv;
     src.yuv(y, x, yv, uv, vv);
     float* __restrict__ dst = rgb + ((long long)frame * H * W + p) * 3;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) dst[ch] = nv12_channel(yv, uv, vv, src.m[3 * ch], src.m[3 * ch + 1], src.m[3 * ch + 2]);
+    }
 }
 
 // ------------------------------------------------------------------------------------------ ZERO FILL

@@ -724,3 +724,74 @@ SILENT_EXPORT int silent_yuv16_to_rgb(silent_ctx* ctx, const silent_yuv16_frames
 } catch (...) {
     return on_exception(ctx, "silent_yuv16_to_rgb");
 }
+
+// Raw 8-bit Bayer mosaics (silent_hip.h; check_bayer / bayer_frames, silent_plan.h): the struct's own refusals, then the shared ones, all
+// under the entry point's name, before a launch or a staged byte.  The host forms stage the view's span.
+static int pyramid_bayer(silent_ctx* ctx, bool host, const silent_pyramid_plan* plan, const silent_bayer_frames* f, int n_frames, float* pyr, silent_stream stream) {
+    const char* who = "silent_pyramid_bayer";
+    size_t span = 0;
+    TRY(check_bayer(ctx, who, plan != nullptr, plan ? plan->tab.H : 0, plan ? plan->tab.W : 0, f, n_frames, &span));
+    TRY(pyramid_checks<float>(ctx, who, plan, true, n_frames, pyr));
+    // (a SILENT_PLAN_ACCUM_F64 plan is single-channel by construction: it is named as such, before the channel count)
+    if (plan->f64) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": Bayer mosaics with a SILENT_PLAN_ACCUM_F64 plan");
+    if (plan->tab.C != 3) return fail(ctx, SILENT_E_UNSUPPORTED, std::string(who) + ": Bayer mosaics are for 3-channel plans");
+    auto launch = [&](const uint8_t* data, float* out, hipStream_t s) {
+        const Bayer frames = bayer_frames(f, data, n_frames, plan->tab.H, plan->tab.W);
+        return launch_pyramid_rgb8(ctx, who, plan, &frames, n_frames, out, s);
+    };
+    if (!host) return launch(f->data, pyr, (hipStream_t)stream);
+    HostStage hs(ctx);
+    const int x = hs.in(f->data, span), o = hs.out(pyr, (size_t)plan->tab.frame_px_out * 3 * 4 * n_frames);
+    return hs.run([&] { return launch(hs.dev<uint8_t>(x), hs.dev<float>(o), nullptr); });
+}
+
+// the converted frames themselves, [n_frames, H, W, 3] float32 (source_to_rgb_kernel: BayerSrc::rgb, the device function of every kernel)
+static int bayer_to_rgb(silent_ctx* ctx, bool host, const silent_bayer_frames* f, int n_frames, int H, int W, float* rgb, silent_stream stream) {
+    const char* who = "silent_bayer_to_rgb";
+    size_t span = 0;
+    TRY(check_bayer(ctx, who, true, H, W, f, n_frames, &span));
+    if (!rgb) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": NULL pointer");
+    if (n_frames < 1) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": n_frames must be >= 1");
+    const long long per_frame = ((long long)H * W + 255) / 256;
+    if (per_frame * n_frames > 0x7fffffffll) return fail(ctx, SILENT_E_INVALID, std::string(who) + ": too many blocks for one launch");
+    auto launch = [&](const uint8_t* data, float* out, hipStream_t s) {
+        hipLaunchKernelGGL(silent::source_to_rgb_kernel<Bayer>, dim3((unsigned)(per_frame * n_frames)), dim3(256), 0, s, bayer_frames(f, data, n_frames, H, W), out,
+                           H, W, (int)per_frame);
+        return check_launch(ctx, who);
+    };
+    if (!host) return launch(f->data, rgb, (hipStream_t)stream);
+    HostStage hs(ctx);
+    const int x = hs.in(f->data, span), o = hs.out(rgb, (size_t)H * W * 3 * 4 * n_frames);
+    return hs.run([&] { return launch(hs.dev<uint8_t>(x), hs.dev<float>(o), nullptr); });
+}
+
+SILENT_EXPORT int silent_pyramid_bayer_dev(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_bayer_frames* frames, int n_frames,
+                                           float* pyr, silent_stream stream) try {
+    NEED_CTX(ctx);
+    return pyramid_bayer(ctx, false, plan, frames, n_frames, pyr, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_bayer_dev");
+}
+
+SILENT_EXPORT int silent_pyramid_bayer(silent_ctx* ctx, const silent_pyramid_plan* plan, const silent_bayer_frames* frames, int n_frames,
+                                       float* pyr) try {
+    NEED_CTX(ctx);
+    return pyramid_bayer(ctx, true, plan, frames, n_frames, pyr, nullptr);
+} catch (...) {
+    return on_exception(ctx, "silent_pyramid_bayer");
+}
+
+SILENT_EXPORT int silent_bayer_to_rgb_dev(silent_ctx* ctx, const silent_bayer_frames* frames, int n_frames, int H, int W, float* rgb,
+                                          silent_stream stream) try {
+    NEED_CTX(ctx);
+    return bayer_to_rgb(ctx, false, frames, n_frames, H, W, rgb, stream);
+} catch (...) {
+    return on_exception(ctx, "silent_bayer_to_rgb_dev");
+}
+
+SILENT_EXPORT int silent_bayer_to_rgb(silent_ctx* ctx, const silent_bayer_frames* frames, int n_frames, int H, int W, float* rgb) try {
+    NEED_CTX(ctx);
+    return bayer_to_rgb(ctx, true, frames, n_frames, H, W, rgb, nullptr);
+} catch (...) {
+    return on_exception(ctx, "silent_bayer_to_rgb");
+}

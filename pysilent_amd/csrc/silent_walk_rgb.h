@@ -280,6 +280,93 @@ __host__ __device__ __forceinline__ W3YuvLoad w3_yuv16_load(const Walk3Args& arg
     return w3_yuv_family_load(args, v, px, bid, chunk, row, lane, k);
 }
 
+// ---- the loader's addresses on raw Bayer mosaics (FrameBayer, silent_pyramid_bayer): ONE PIXEL per lane and load slot like the NV12
+// family, but a pixel needs its 3 x 3 neighbourhood: the lane loads ITS column from three frame rows -- the ring row's frame row yy and
+// yy - 1, yy + 1 reflected at the FRAME's edges (bayer_reflect; the crop's scipy mirror only chooses yy) -- and takes the columns left
+// and right of it from the neighbouring lanes (a wave shift; the last lane of slot k neighbours the first lane of slot k + 1).  So the
+// slots carry ONE MORE COLUMN on each side of the ring row: slot k of a lane holds pixel p0 + 64 k + lane with p0 = floor(A / 3) - 1,
+// and its floats are ring floats 3 (64 k + lane) + (3 p0 - A) + {0, 1, 2} (those outside the row are not written).  Columns are clamped
+// into the frame row; a lane at x == 0 takes its right neighbour for the left one and a lane at x == W - 1 its left one for the right
+// (the reflection), whatever the clamped lanes beside it hold.  Host-callable: tests/rgb_bayer_host_main.cpp enumerates whole launches.
+__host__ __device__ constexpr int w3_bayer_row_loads(int px) { return ((w3_row_f(px) + 4) / 3 + 2 + 63) / 64; }   // load slots per ring row
+__host__ __device__ __forceinline__ int w3_bayer_p0(int A) { return w3_nv12_p0(A) - 1; }
+__host__ __device__ __forceinline__ int w3_bayer_px(const Walk3Args& args, int A, int lane, int k) {
+    const int p = w3_bayer_p0(A) + lane + 64 * k;
+    return p < 0 ? 0 : (p > args.W - 1 ? args.W - 1 : p);
+}
+// stream row s of a block: its frame row and the two rows beside it, and their byte offsets from `data` (scalar 64-bit arithmetic)
+struct W3BayerRows {
+    int row[3];                          // yy - 1 (reflected), yy, yy + 1 (reflected)
+    long long offset[3];
+};
+__host__ __device__ __forceinline__ W3BayerRows w3_bayer_rows(const Walk3Args& args, const FrameBayer& v, const W3ViewBlock& b, int s) {
+    const Walk3Plan& p = args.plan[b.plan];
+    const int yy = w3_mirror_near(b.y_first + s, p.src_h) + p.src_y0;
+    W3BayerRows r;
+    r.row[0] = bayer_reflect(yy - 1, args.H);
+    r.row[1] = yy;
+    r.row[2] = bayer_reflect(yy + 1, args.H);
+    for (int i = 0; i < 3; ++i) r.offset[i] = (long long)b.frame * v.frame_stride + (long long)r.row[i] * v.row_stride;
+    return r;
+}
+// THE address function: the three one-byte loads of (block, chunk, row of the chunk, lane, load slot) -- byte offsets from `data`, the
+// frame rows they lie in and the frame column of the slot
+struct W3BayerLoad {
+    long long offset[3];
+    int row[3];
+    int col;
+};
+__host__ __device__ __forceinline__ W3BayerLoad w3_bayer_load(const Walk3Args& args, const FrameBayer& v, int px, unsigned bid, int chunk, int row, int lane, int k) {
+    const W3ViewBlock b = w3_view_block(args, px, bid);
+    const W3BayerRows r = w3_bayer_rows(args, v, b, chunk * kW3CH + row);
+    W3BayerLoad l;
+    l.col = w3_bayer_px(args, b.A, lane, k);
+    for (int i = 0; i < 3; ++i) {
+        l.row[i] = r.row[i];
+        l.offset[i] = r.offset[i] + (long long)l.col * v.pixel_stride;
+    }
+    return l;
+}
+// the samples of a slot's column on the three rows as one register (row yy - 1 in bits 0 .. 7, yy in 8 .. 15, yy + 1 in 16 .. 23), so
+// that ONE wave shift moves a neighbour's three samples; the column of lane - 1 / lane + 1 across the load slots of a ring row:
+// lane 0 of slot k receives lane 63 of slot k - 1, lane 63 of slot k lane 0 of slot k + 1 (a DPP shift without bound_ctrl keeps `old`
+// in the lane that has no source).  The first lane of slot 0 and the last of the last slot receive 0: carried columns, never converted
+// into a ring float that is read.
+__device__ __forceinline__ int w3_bayer_pack(unsigned char up, unsigned char mid, unsigned char down) { return (int)up | ((int)mid << 8) | ((int)down << 16); }
+template <int N>
+__device__ __forceinline__ int w3_bayer_left(const int (&p)[N], int k) {
+    const int old = k > 0 ? __builtin_amdgcn_readlane(p[k > 0 ? k - 1 : 0], 63) : 0;
+    return __builtin_amdgcn_update_dpp(old, p[k], 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+}
+template <int N>
+__device__ __forceinline__ int w3_bayer_right(const int (&p)[N], int k) {
+    const int old = k + 1 < N ? __builtin_amdgcn_readlane(p[k + 1 < N ? k + 1 : 0], 0) : 0;
+    return __builtin_amdgcn_update_dpp(old, p[k], 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
+}
+// what bayer_rgb takes of a slot's pixel, from its packed column c and those of its neighbours l, r (x: its frame column, W: the frame's
+// width): its own sample and the sums of its horizontal, vertical and diagonal neighbours.  Host-callable (integers only):
+// tests/rgb_bayer_host_main.cpp replays the exchange of a ring row with it and compares the sums with those of the mosaic.
+struct W3BayerSums {
+    int c, h, v, d;
+};
+__host__ __device__ __forceinline__ W3BayerSums w3_bayer_sums(int W, int l, int c, int r, int x) {
+    l = x == 0 ? r : l;                  // reflection at the frame's left / right edge (W >= 2: never both)
+    r = x == W - 1 ? l : r;
+    W3BayerSums s;
+    s.c = (c >> 8) & 0xff;
+    s.h = ((l >> 8) & 0xff) + ((r >> 8) & 0xff);
+    s.v = (c & 0xff) + ((c >> 16) & 0xff);
+    s.d = ((l & 0xff) + (r & 0xff)) + (((l >> 16) & 0xff) + ((r >> 16) & 0xff));
+    return s;
+}
+// ring float of channel 0 of the pixel of (lane, slot)
+__host__ __device__ __forceinline__ int w3_bayer_ring_float(int A, int lane, int k) { return 3 * (lane + 64 * k) + (3 * w3_bayer_p0(A) - A); }
+// the three channels of the slot's pixel (yy: its frame row)
+__device__ __forceinline__ void w3_bayer_values(const FrameBayer& f, int l, int c, int r, int x, int yy, float& c0, float& c1, float& c2) {
+    const W3BayerSums s = w3_bayer_sums(f.W, l, c, r, x);
+    bayer_rgb(s.c, s.h, s.v, s.d, yy & 1, x & 1, f.pattern, f.order, c0, c1, c2);
+}
+
 // ---- the loader's registers on the family: the element types of a load slot (luma element; the chroma pair, or the U element; the V
 // element of the triple kinds), "fetch slot k of a row" (one template: the loads are the register types' sizes) and "loaded elements ->
 // (Yv, Uv, Vv)" per frame kind.  yr / ur / vr: the row's
@@ -344,11 +431,15 @@ __device__ __forceinline__ void w3_yuv_values(const FrameYuv16& f, unsigned shor
 // is NV12's.  Every address is that of a byte that is some pixel's Y, U or V.
 // FT = FrameYuv16 (16-bit YUV, by value): the FrameYuv loader with three 2-byte loads per slot (w3_yuv16_load) and yuv16_values (shift,
 // mask, offsets) in front of the same nv12_channel; depth and alignment of the code are runtime scalars.
+// FT = FrameBayer (raw 8-bit Bayer mosaics, by value): a pixel per lane and load slot, THREE frame rows per ring row (w3_bayer_load): the
+// lane's own column as three byte loads -- the YUV triple's count --, the columns beside it from the neighbouring lanes (w3_bayer_left /
+// _right), bayer_rgb, three ring floats written; issue / wait / barrier order is NV12's.  Every address is that of a pixel of the view.
 template <int G, int PX, typename FT = float>
 __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<FT> frames, float* __restrict__ pyr,
                                                                     const Walk3Args args, const WalkBorderArgs border) {
-    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT> || kFrameYuvFamily<FT>,
-                  "float32, packed uint8 or strided uint8 colour frames, NV12 / P010 / YUV / 16-bit YUV surfaces");
+    static_assert(std::is_same<FT, float>::value || kFrameBytes<FT> || kFrameRgbView<FT> || kFrameYuvFamily<FT> || kFrameBayer<FT>,
+                  "float32, packed uint8 or strided uint8 colour frames, NV12 / P010 / YUV / 16-bit YUV surfaces, Bayer mosaics");
+    constexpr bool kBy = kFrameBayer<FT>;                            // the loader demosaics in registers
     constexpr bool kYuv3 = kFrameYuvTriple<FT>;                      // three loads per slot, byte columns per lane
     constexpr bool kNv = kFrameYuvFamily<FT>;                        // the loader converts (Y, U, V) in registers
     constexpr bool kBytes = kFrameBytes<FT> || kFrameRgbView<FT>;   // the loader widens bytes in registers
@@ -396,6 +487,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
         const ET* __restrict__ src;
         if constexpr (kFrameRgbView<FT>) src = frames.data;    // (rows: w3_view_row)
         else if constexpr (kNv) src = reinterpret_cast<const unsigned char*>(frames.y);   // (rows: w3_yuv_row; strides are bytes)
+        else if constexpr (kBy) src = frames.data;             // (rows: w3_bayer_rows)
         else src = frames + (long long)frame * args.H * args.W * 3;
         const int rowf = args.W * 3;                           // floats (uint8 frames: bytes) of a FRAME row
         // ring float r <-> frame-row float A + r, A = the crop's pixel R0 minus the alignment shift.  Frame widths that are a
@@ -419,7 +511,20 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
             (void)nvd;
             (void)yuy;
             (void)yuc;
-            if constexpr (kNv) {
+            constexpr int kByLoads = w3_bayer_row_loads(PX);
+            int byx[kBy ? kByLoads : 1];                         // Bayer: the lane's frame column per load slot ...
+            long long byc[kBy ? kByLoads : 1];                   // ... and its byte column in a row of the view
+            (void)byx;
+            (void)byc;
+            if constexpr (kBy) {
+                vb = w3_view_block(args, PX, bid);
+                nvd = w3_bayer_ring_float(vb.A, 0, 0);
+#pragma unroll
+                for (int k = 0; k < kByLoads; ++k) {
+                    byx[k] = w3_bayer_px(args, vb.A, lane, k);
+                    byc[k] = (long long)byx[k] * frames.pixel_stride;
+                }
+            } else if constexpr (kNv) {
                 vb = w3_view_block(args, PX, bid);
                 nvd = 3 * w3_nv12_p0(vb.A) - vb.A;
 #pragma unroll
@@ -479,9 +584,26 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                         }
                     }
                 };
+                // Bayer: the lane's column on the three frame rows of every ring row of the chunk (3 kW3CH kByLoads byte loads, all in
+                // flight before one is consumed), then per row: pack, exchange the columns between lanes, demosaic, three ring floats
+                unsigned char byu[kBy ? kW3CH : 1][kBy ? kByLoads : 1], bym[kBy ? kW3CH : 1][kBy ? kByLoads : 1], byd[kBy ? kW3CH : 1][kBy ? kByLoads : 1];
+                int byy[kBy ? kW3CH : 1];                        // the ring rows' frame rows (wave-uniform)
+                (void)byu;
+                (void)bym;
+                (void)byd;
+                (void)byy;
 #pragma unroll
                 for (int r = 0; r < kW3CH; ++r) {
-                    if constexpr (kNv) {
+                    if constexpr (kBy) {
+                        const W3BayerRows rows = w3_bayer_rows(args, frames, vb, c * kW3CH + r);
+                        byy[r] = rows.row[1];
+#pragma unroll
+                        for (int k = 0; k < kByLoads; ++k) {
+                            byu[r][k] = src[rows.offset[0] + byc[k]];
+                            bym[r][k] = src[rows.offset[1] + byc[k]];
+                            byd[r][k] = src[rows.offset[2] + byc[k]];
+                        }
+                    } else if constexpr (kNv) {
                         if (r < kNvRows) nv_load(0, r);
                     } else {
                     const int y = seg_y0 - 4 + c * kW3CH + r;
@@ -515,7 +637,25 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                 if constexpr (NV > 64) {
                     if (lane < NV - 64) __builtin_amdgcn_global_load_lds((walk_glb_ptr)(rp + 256), (walk_lds_ptr)(dst + 256), 16, 0, 0);
                 }
-                if constexpr (kNv) {
+                if constexpr (kBy) {
+#pragma unroll
+                    for (int r = 0; r < kW3CH; ++r) {
+                        float* row = &s_ring[slot * kW3CH + r][0];
+                        int pk[kByLoads];
+#pragma unroll
+                        for (int k = 0; k < kByLoads; ++k) pk[k] = w3_bayer_pack(byu[r][k], bym[r][k], byd[r][k]);
+#pragma unroll
+                        for (int k = 0; k < kByLoads; ++k) {
+                            float ch3[3];
+                            w3_bayer_values(frames, w3_bayer_left(pk, k), pk[k], w3_bayer_right(pk, k), byx[k], byy[r], ch3[0], ch3[1], ch3[2]);
+                            const int q = 3 * (lane + 64 * k) + nvd;     // ring float of channel 0
+#pragma unroll
+                            for (int ch = 0; ch < 3; ++ch)
+                                if (q + ch >= 0 && q + ch < kW3RowF) row[q + ch] = ch3[ch];
+                        }
+                    }
+                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // rows written, records landed
+                } else if constexpr (kNv) {
 #pragma unroll
                     for (int g = 0; g < kW3CH; g += kNvRows) {
                         if (g > 0) {
@@ -582,7 +722,7 @@ __global__ __launch_bounds__(kW3Threads) void pyramid_walk3_kernel(frame_param<F
                 // chunk c has landed when at most the next chunk's loads (three slots: one chunk in flight behind it) are outstanding
                 // (uint8 frames: nothing is outstanding here, issue() ends with vmcnt(0) -- the counted wait would name a mix of register
                 // loads and DMA loads that the compiler is free to reorder)
-                if (!kBytes && !kNv && kWalkSlots == 3 && c + 1 < n_chunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kRowLoads * kW3CH + (kW3CH * PR / 4 > 64 ? 2 : 1)) : "memory");
+                if (!kBytes && !kNv && !kBy && kWalkSlots == 3 && c + 1 < n_chunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kRowLoads * kW3CH + (kW3CH * PR / 4 > 64 ? 2 : 1)) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (any_fix) {
 #pragma unroll

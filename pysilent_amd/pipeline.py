@@ -202,6 +202,15 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
         # silent_pyramid_yuv16_dev, one element per load; pyramid, maps and keypoints are those of the float32 pipeline on
         # _runtime.yuv16_to_rgb(planes, fmt=...), bit for bit.  The conversion is P010's (_runtime.p010_coefficients at the format's
         # depth; "bt2020" is accepted).
+        # rgb_frame_format="bayer_rggb" / "bayer_grbg" / "bayer_gbrg" / "bayer_bggr" (util.zoom.BAYER_LAYOUTS maps the GenICam names): the
+        # frames are ONE uint8 GPU view [batch, H, W] (or [batch, H, W, 1]) of a raw Bayer mosaic as a machine-vision camera delivers
+        # it, any positive strides, the name that of the top-left 2 x 2 cell of the view -- read in place by silent_pyramid_bayer_dev and
+        # demosaiced (bilinear) in registers, 1 B/px; pyramid, maps and keypoints are those of the float32 pipeline on
+        # _runtime.bayer_to_rgb(frames, hw, fmt), bit for bit.  nv12_order selects "bgr" / "rgb" as for every other source; a non-default
+        # nv12_matrix or nv12_range is refused (they would silently mean nothing).  H and W of at least 2, odd extents allowed.
+        if self._bayer is not None:
+            _runtime.check_bayer_conversion(self.rgb_frame_format, nv12_matrix, nv12_range, nv12_order)   # (for its refusals)
+            self.nv12_order = nv12_order
         if self._source and self._source[0].elem == 2:
             self.nv12_m, self.nv12_oy, self.nv12_oc = _runtime.p010_coefficients(nv12_matrix, nv12_range, nv12_order, self._source[3])
         else:
@@ -510,6 +519,8 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
         if self._source:
             src, _, _, depth, shift = self._source
             return tuple((torch.randint(0, 1 << depth, sh, device=self.tdev) << shift).to(getattr(torch, src.dtype)) for sh in self._plane_shapes())
+        if self._bayer is not None:
+            return torch.randint(0, 256, (self.batch,) + self.frame_shape[:2], device=self.tdev).to(torch.uint8)
         frames = torch.randint(0, 256, (self.batch,) + self.frame_shape, device=self.tdev)
         return frames.to(self._frame_torch_dtype)
 
@@ -760,7 +771,7 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
         rgb_frame_format="nv12" counts 1.5 bytes per pixel: the luma byte and half a chroma pair; "p010" / "p012" / "p016" 3 bytes per
         pixel: the luma element and half a pair of elements; "yuv420" / "yuv422" / "yuv444" 1 + 2 / 2^(sx + sy) bytes per pixel --
         1.5, 2 and 3: the luma byte and the pixel's share of a U and a V byte, whatever lies between them in a packed buffer not
-        counted; the 16-bit triples of YUV16_FORMATS twice that -- 3, 4 and 6)."""
+        counted; the 16-bit triples of YUV16_FORMATS twice that -- 3, 4 and 6; a raw Bayer mosaic, "bayer_rggb" ..., 1 byte per pixel)."""
         h, w, fc = self.frame_shape
         c = self.channels
         if self.crop_px is not None:
@@ -797,6 +808,8 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
             src, sx, sy = self._source[:3]
             f = fractions.Fraction(src.elem * (2 ** (sx + sy) + 2), 3 * 2 ** (sx + sy))
             return float(f) if src.planes == 2 else f
+        if self._bayer is not None:                                  # one byte per PIXEL over the three channels -- exact
+            return fractions.Fraction(1, 3)
         return {"uint8": 1, "uint16": 2}.get(self.frame_dtype, 4)
 
     @property
@@ -824,6 +837,11 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
     def _yuv16(self):
         """(sx, sy, depth, shift) of a mode "rgb" pipeline reading a (y, u, v) triple of uint16 views (_runtime.YUV16_FORMATS), else None."""
         return _runtime.YUV16_FORMATS.get(getattr(self, "rgb_frame_format", "interleaved"))
+
+    @property
+    def _bayer(self):
+        """The pattern (0 .. 3) of a mode "rgb" pipeline reading raw Bayer mosaics (_runtime.BAYER_FORMATS), else None."""
+        return _runtime.BAYER_FORMATS.get(getattr(self, "rgb_frame_format", "interleaved"))
 
     @property
     def _frame_torch_dtype(self):
@@ -870,6 +888,8 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
 
     def _source_summary(self):
         """launch_summary's words on a YUV-family source: its planes and the bytes step() reads per pixel."""
+        if self._bayer is not None:
+            return ", %s mosaics read in place (one uint8 view, 1 byte per pixel, demosaiced in registers)" % self.rgb_frame_format
         if not self._source:
             return ""
         src = self._source[0]
@@ -898,6 +918,18 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
             raise ValueError("frames must be a %s of %s GPU planes %s" % ("pair (y, uv)" if src.planes == 2 else "triple (y, u, v)", src.dtype,
                                                                           ", ".join(shapes[:-1]) + " and " + shapes[-1]))
         return getattr(_lib, src.kind + "_ptr")(args)
+
+    def _bayer_arg(self, frames):
+        """The const silent_bayer_frames* of a uint8 GPU view [batch, H, W] (or [batch, H, W, 1]) of this pipeline's batch (refused:
+        anything else)."""
+        (h, w), ok = self.frame_shape[:2], _runtime.is_torch_tensor(frames) and frames.is_cuda
+        if ok:
+            args, n, _ = _runtime.bayer_frames_of(frames, (h, w), self.rgb_frame_format, self.nv12_order)
+            ok = n == self.batch
+        if not ok:
+            raise ValueError("frames must be a uint8 GPU tensor (any view with positive strides) of shape %s or %s"
+                             % ((self.batch, h, w), (self.batch, h, w, 1)))
+        return _lib.bayer_ptr(args)
 
     def _check_frames(self, frames):
         if getattr(self, "rgb_frame_layout", "packed") == "strided":
@@ -928,6 +960,10 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
             entry = getattr(self._lib, "silent_pyramid_%s_dev" % self._source[0].kind)
             self.ctx.check(entry(self.ctx.handle, self.plan.handle, self._source_arg(frames), self.batch, C.c_void_p(self.pyr.data_ptr()),
                                  stream or self._stream()))
+            return
+        if self._bayer is not None:                                  # (mode "rgb", a raw Bayer mosaic: one uint8 GPU view)
+            self.ctx.check(self._lib.silent_pyramid_bayer_dev(self.ctx.handle, self.plan.handle, self._bayer_arg(frames), self.batch,
+                                                              C.c_void_p(self.pyr.data_ptr()), stream or self._stream()))
             return
         self._check_frames(frames)
         if getattr(self, "rgb_frame_layout", "packed") == "strided":   # (mode "rgb", rgb_frame_dtype="uint8")
@@ -1143,10 +1179,13 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
         batch n + 1 overlaps the compute of batch n.  Results are bit-identical to step() on the same frames resident as float32.
         A frame_dtype="uint8" pipeline takes uint8 host frames only: staging -> copy into the slot's uint8 device buffer -> step();
         no cast launch and no float32 frame buffer.  A frame_dtype="uint16" pipeline likewise takes uint16 host frames only, and a
-        mode "rgb" pipeline with rgb_frame_dtype="uint8" uint8 host frames [batch, H, W, 3] only."""
+        mode "rgb" pipeline with rgb_frame_dtype="uint8" uint8 host frames [batch, H, W, 3] only; one reading raw Bayer mosaics
+        (rgb_frame_format="bayer_rggb" ...) a uint8 NumPy array [batch, H, W] or [batch, H, W, 1] (_step_host_bayer)."""
         torch = self.torch
         if self._source:
             return self._step_host_nv12(frames)
+        if self._bayer is not None:
+            return self._step_host_bayer(frames)
         if isinstance(frames, np.ndarray):
             src = torch.from_numpy(np.ascontiguousarray(frames))
         else:
@@ -1228,8 +1267,15 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
             raise ValueError("step_host of an rgb_frame_format=%r pipeline takes a %s of %s arrays of shapes %s"
                              % (self.rgb_frame_format, "triple" if src.planes == 3 else "pair", src.dtype,
                                 " and ".join(str(sh) for sh in shapes)))
+        self._step_host_planes("nv12", frames, shapes, t_dtype, lambda raw: tuple(raw))
+
+    def _step_host_planes(self, key, planes, shapes, t_dtype, frames_of):
+        """The ingest of host planes that step() reads in place (the YUV family's pair / triple, a Bayer mosaic): each plane through a
+        pinned staging buffer and an asynchronous copy on the copy stream into ring ``key`` of two device slots; step(frames_of(the
+        slot's device planes)); the slot is free again where the frame-reading kernels finish."""
+        torch = self.torch
         cs = self._copy_stream_of_the_ingest()
-        ring = self._ingest.setdefault("nv12", {"slots": [], "next": 0})
+        ring = self._ingest.setdefault(key, {"slots": [], "next": 0})
         if not ring["slots"]:
             for _ in range(2):
                 ring["slots"].append({"pinned": [torch.empty(sh, dtype=t_dtype, pin_memory=True) for sh in shapes],
@@ -1239,7 +1285,7 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
         ring["next"] ^= 1
         cur = torch.cuda.current_stream(self.tdev)
         slot["h2d_done"].synchronize()              # the staging buffers' previous copies have left the host
-        for pin, p in zip(slot["pinned"], frames):
+        for pin, p in zip(slot["pinned"], planes):
             _staging_copy(pin, torch.from_numpy(np.ascontiguousarray(p)))
         if slot["raw_free"] is not None:
             cs.wait_event(slot["raw_free"])         # the previous batch of this slot has been read on the device
@@ -1248,10 +1294,23 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
                 raw.copy_(pin, non_blocking=True)
         slot["h2d_done"].record(cs)
         cur.wait_event(slot["h2d_done"])
-        self.step(tuple(slot["raw"]))
+        self.step(frames_of(slot["raw"]))
         if slot["raw_free"] is None:
             slot["raw_free"] = torch.cuda.Event()
         slot["raw_free"].record(self._walk_stream if self.overlap else cur)
+
+    def _step_host_bayer(self, frames):
+        """step_host of a Bayer pipeline: ``frames`` is the mosaic batch [batch, H, W] (or [batch, H, W, 1]) as a uint8 NumPy array (any
+        strides: the staging copy packs).  It goes through a pinned staging buffer and an asynchronous copy on the copy stream into a
+        ring of two device slots of MOSAICS, 1 B/px, which step() reads in place; no cast, no demosaic launch."""
+        torch = self.torch
+        shape = (self.batch,) + self.frame_shape[:2]
+        if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.shape[3] == 1:
+            frames = frames[..., 0]
+        if not isinstance(frames, np.ndarray) or frames.dtype != np.uint8 or tuple(frames.shape) != shape:
+            raise ValueError("step_host of an rgb_frame_format=%r pipeline takes a uint8 array of shape %s or %s"
+                             % (self.rgb_frame_format, shape, shape + (1,)))
+        self._step_host_planes("bayer", [frames], [shape], torch.uint8, lambda raw: raw[0])
 
     def step(self, frames):
         """One pass of the hot path over one batch of frames (asynchronous)."""

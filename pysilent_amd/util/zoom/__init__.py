@@ -5,3 +5,4 @@ from .nv12 import nv12_planes
 from .p010 import p010_planes
 from .yuv import yuv_planes
 from .yuv16 import yuv16_planes, YUV16_LAYOUTS
+from .bayer import bayer_window, BAYER_LAYOUTS

@@ -463,8 +463,72 @@ def case_crop_walk(rng, k):
     return desc + (" [walk %d x %d]" % (n_plans, px) if n_plans else " [region]")
 
 
+def case_bayer(rng, k):
+    """Raw Bayer mosaics (silent_bayer_to_rgb, silent_pyramid_bayer): random extents (odd ones too), strides (a pixel stride of 1 .. 3,
+    padded rows, a gap between the frames, a window origin inside a parent filled with 0x00 or 0xFF), pattern, order and plan (classic,
+    the reference's crops, free-form) -- the conversion against the NumPy restatement of tests/rgb_bayer_frames.py bit for bit, _dev and
+    host form, and the pyramid against the float32 call on the restatement's frames bit for bit on the plan's route and on the unit +
+    region kernels."""
+    import torch
+    import rgb_bayer_frames as bf
+    from pysilent_amd.util.zoom.from_image import reference_levels
+    h, w = int(rng.integers(2, 300)), int(rng.integers(2, 420))
+    if rng.integers(0, 6) == 0:
+        h, w = int(rng.integers(2, 6)), int(rng.integers(2, 6))       # every neighbour reflected
+    B = int(rng.integers(1, 4))
+    ps = int(rng.integers(1, 4))
+    rs = (w - 1) * ps + 1 + int(rng.integers(0, 40))
+    fs = (h - 1) * rs + (w - 1) * ps + 1 + int(rng.integers(0, 300))
+    off, fill = int(rng.integers(0, 70)), int(rng.choice(bf.FILLS))
+    pattern, order = str(rng.choice(bf.PATTERNS)), str(rng.choice(bf.ORDERS))
+    s = dict(n=B, H=h, W=w, size=off + B * fs + int(rng.integers(0, 50)), offset=off, strides=(fs, rs, ps))
+    desc = "bayer h=%d w=%d B=%d strides=%s offset=%d fill=%#x %s %s" % (h, w, B, s["strides"], off, fill, pattern, order)
+    m = rng.integers(0, 256, (B, h, w)).astype(np.uint8)
+    parent = bf.place(s, m, fill)
+    host, dev = bf.view(s, parent), bf.torch_view(s, torch.from_numpy(parent).cuda(0))
+    want = bf.truth(m, pattern, order)
+    fmt = "bayer_" + pattern
+    for frames in (dev, host):
+        got = rt.bayer_to_rgb(frames, (h, w), fmt, order)
+        got = got.cpu().numpy() if hasattr(got, "cpu") else got
+        np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32), err_msg=desc + " conversion")
+    levels = draw_levels(rng, h, w, 3) if min(h, w) >= 40 else None
+    if levels is None:
+        try:
+            if rng.integers(0, 2) == 0:
+                scale, n = float(rng.choice([2 ** .5, 1.6, math.e ** .5, 2.0, 2.5])), int(rng.integers(1, 6))
+                levels, desc = classic_levels((h, w), scale, n), desc + " classic scale=%.3f n=%d" % (scale, n)
+            else:
+                cw, ch, scale = int(rng.integers(2, max(3, w // 2))), int(rng.integers(2, max(3, h // 2))), float(rng.choice([math.e ** .5, 2.0]))
+                levels, desc = reference_levels((h, w), (cw, ch), scale), desc + " reference center=(%d,%d) scale=%.3f" % (cw, ch, scale)
+        except (ValueError, ZeroDivisionError):
+            return desc + " (no such pyramid)"
+        if not levels or len(levels) > 12:
+            return desc + " (no such pyramid)"
+    else:
+        desc += " free-form levels=%s" % (levels,)
+    try:
+        plan = rt.PyramidPlan(h, w, 3, levels)
+    except ValueError as e:
+        return desc + " (plan refused: %s)" % str(e)[:60]
+    f32 = torch.from_numpy(want).cuda(0)
+    kw = dict(rgb_frame_format=fmt, nv12_order=order)
+    for knob in (0, 2):
+        rt.get_context().set_tuning(_lib.TUNE_PYRAMID, knob)
+        try:
+            ref = plan.run(f32).data.cpu().numpy()
+            np.testing.assert_array_equal(plan.run(dev, **kw).data.cpu().numpy().view(np.uint32), ref.view(np.uint32), err_msg=desc + " knob %d _dev" % knob)
+            if knob == 0:
+                np.testing.assert_array_equal(np.asarray(plan.run(host, **kw).data).view(np.uint32), ref.view(np.uint32), err_msg=desc + " host")
+        finally:
+            rt.get_context().set_tuning(_lib.TUNE_PYRAMID, 0)
+    n_plans, px = plan.walk_plans
+    plan.close()
+    return desc + (" [walk %d x %d]" % (n_plans, px) if n_plans else " [region]")
+
+
 CASES = {"gray_pass": case_gray_pass, "rgb": case_rgb, "select": case_select, "ops": case_ops, "rgb_keypoints": case_rgb_keypoints,
-         "sparse_tail": case_sparse_tail, "crop_walk": case_crop_walk}
+         "sparse_tail": case_sparse_tail, "crop_walk": case_crop_walk, "bayer": case_bayer}
 BIG = {"big": case_big}
 
 
