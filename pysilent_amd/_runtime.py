@@ -1661,6 +1661,8 @@ class PyramidPlan(object):
                        cap_per_frame=None, frame_dtype="float32", frame_channels=1, frame_layout="packed"):
         """silent_gray_keypoints (host form): gray_pass + pad_inwards -> value -> [top_value_points -> NMS -> value ->]
         max_value_indices_region on the K-channel end map.  Returns (pyramid, cs, end, idx [n, cap, 4], counts [n]).
+        regions: one (rH, rW) per level (default: half the level), the strides of TF1's max_pool(k = the whole level, SAME) whose
+        window maxima a keypoint must reach; more than 4 windows per axis on any level runs the general path, without the sparse tail.
         frame_dtype="uint8" (silent_gray_keypoints_u8): uint8 frames read as they are, the same results.  frame_channels=3 (with
         "uint8"; silent_gray_keypoints_u8x3): [n,H,W,3] interleaved colour frames, the results of the frame of values.
         frame_layout="strided" (with "uint8"; silent_gray_keypoints_view): any uint8 view with positive strides, read in place.

@@ -351,6 +351,9 @@ class LineEndPipeline(object, metaclass=_PipelineCall):
         if self.attention:
             self._alloc_attention()
         if self.keypoints:
+            # regions: one (rH, rW) per level (default: half the level) -- the strides of max_value_indices_region's pool, TF1
+            # max_pool(k = the whole level, stride = region, SAME): a pixel is a keypoint where it reaches the maximum of its window.
+            # More than 4 windows per axis on any level runs the general window-maxima path for the whole call, without the sparse tail
             if regions is None:
                 regions = [(max(eh // 2, 1), max(ew // 2, 1)) for eh, ew in self.extents]
             if len(regions) != self.n_levels:

@@ -191,9 +191,10 @@ def test_against_the_cpu_oracle(rt):
 REGIONS = [(max(h // 2, 1), max(w // 2, 1)) for h, w in EXTENTS]
 
 
-def _kp_calls(rt, flat, ks, top_percent, peak_map, clip=255.0):
+def _kp_calls(rt, flat, ks, top_percent, peak_map, clip=255.0, regions=None):
     """(h: silent_rgb_keypoints_h_dev, pair: silent_rgb_line_end_h_dev + silent_select_keypoints_dev on the widened line_end,
-    f32: silent_rgb_keypoints_dev) -> dicts of host arrays; stats: the sparse tail's of the _h call."""
+    f32: silent_rgb_keypoints_dev) -> dicts of host arrays; stats: the sparse tail's of the _h call.  regions: one (rH, rW) per
+    level of EXTENTS (default: REGIONS, half the level)."""
     import torch
     lib = _lib.load()
     ctx = rt.get_context(0)
@@ -201,7 +202,8 @@ def _kp_calls(rt, flat, ks, top_percent, peak_map, clip=255.0):
     s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     x = torch.from_numpy(flat).to(dev)
     lv = (_lib.Extent * len(EXTENTS))(*[_lib.Extent(h, w) for h, w in EXTENTS])
-    rg = (_lib.Extent * len(EXTENTS))(*[_lib.Extent(h, w) for h, w in REGIONS])
+    rg = (_lib.Extent * len(EXTENTS))(*[_lib.Extent(int(h), int(w)) for h, w in (REGIONS if regions is None else regions)])
+    assert len(rg) == len(EXTENTS)
     fp = C.POINTER(C.c_float)
     arrs = [np.ascontiguousarray(ks[k], np.float32) for k in cw.RGB_NAMES]
     prm = _lib.RgbChainParams(*[a.ctypes.data_as(fp) for a in arrs], 1.0, 0.1, _lib.FLAT_IEEE, float(clip), 2)
