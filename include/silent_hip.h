@@ -659,7 +659,11 @@ int silent_get_tuning(const silent_ctx* ctx, int which, unsigned* value);
 
 /* ---------------------------------------------------------------------------- a-6 regulator
  * Replaces regulate_tensor, slam_recognition/util/regulator/gaussian_regulator_tensor.py:10-36:
- *   y = x * (rv / pow(min(conv(x, blur), 1), root)); blur is HWIO [kh, kw, C, C]. */
+ *   y = x * (rv / pow(min(conv(x, blur), 1), root)); blur is HWIO [kh, kw, C, C].
+ * The power is powf over the blur's whole range: a denormal blur is not flushed (the factor overflows to inf once
+ * pow(b, root) is below rv / FLT_MAX), b = 0 gives rv / 0 = inf (0 * inf = NaN under SILENT_FLAT_IEEE), and a negative
+ * blur follows pow: NaN unless root is an integer (root 1: rv / b; root 0: rv).  Within 8 * 2^-24 of |y| of the float64
+ * power rounded per op (tests/test_gpu_regulator_domain.py). */
 int silent_regulate(silent_ctx* ctx, const float* in, const silent_extent* levels, int n_levels, int n_frames,
                     int channels, const float* blur_hwio, int kh, int kw, float regulation_value,
                     float regulation_root, int flat_policy, float* out);
@@ -842,7 +846,12 @@ int silent_resize_nearest_dev(silent_ctx* ctx, const float* in, const silent_ext
  *   orient   = regulate(relu(conv(relu(conv(relu(conv(x, rgc)), rgby)), stripe)), blur, rv, root)   (:69-71)
  *   line_end = pad_inwards(clip(relu(conv(orient, end)), 0, clip_hi), pad)                          (:73-75)
  *   value    = get_value_from_color(line_end)                                                        (:77)
- * Every kernel is HWIO [3,3,3,3] except blur [7,7,3,3].  Any of the three outputs may be NULL. */
+ * Every kernel is HWIO [3,3,3,3] except blur [7,7,3,3].  Any of the three outputs may be NULL.
+ * The regulator of the fused launch, m = min(blur sum, 1): rv * exp2(-root * log2(m)) for m >= 7.8886e-31 (just below
+ * 2^-100), powf and a division below it (denormal sums included, none flushed) and for root = 0; within
+ * (3 ln2 root |log2 m| + 8) * 2^-24 of |orient| of silent_regulate's definition for 0 <= root <= 1, which stays below 1e-5
+ * (tests/test_gpu_regulator_domain.py).  The blur sum of a relu'd stripe map under non-negative blur weights is never
+ * negative; for a negative sum the fused launch gives NaN for every root but 0, unlike silent_regulate at root 1. */
 typedef struct silent_rgb_chain_params {
     const float* rgc;    /* midget_rgc(2)              filters/rgc.py:9      */
     const float* rgby;   /* rgby_3(2)                  filters/rgby.py:9     */

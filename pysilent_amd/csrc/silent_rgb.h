@@ -205,10 +205,14 @@ __device__ __forceinline__ void conv3_roll_sum(const float (&s)[3], kfloat_p wst
 }
 
 // The regulator's factor rv / min(b, 1) ** root, evaluated as rv * exp2(-root * log2(m)) on the transcendental unit
-// (v_log_f32, v_exp_f32: 1 ulp each; <= 3 ulp in all since |root * log2 m| stays small) -- no powf (~100 instructions) and no
-// IEEE division (~10).  m = 0 gives exp2(+inf) = inf like rv / 0.  v_log_f32 treats denormal inputs as 0: below 2^-100 the
-// accurate powf and a true division run (a lane-divergent branch that no lane takes in practice), and for root = 0
-// (0 * -inf; pow(0, 0) = 1).  silent_regulate / conv2d_same_kernel keep powf.
+// (v_log_f32, v_exp_f32: 1 ulp each) -- no powf (~100 instructions) and no IEEE division (~10).  The error of the factor grows
+// with t = root * |log2 m|: v_log_f32's ulp of |log2 m| and the rounding of the product reach the result multiplied by ln2 * t, so
+// the factor is within (3 ln2 t + 8) * 2^-24 of the correctly rounded one, NOT within a few ulp (correctly rounded float32 log2 /
+// exp2 already give 11 / 25 / 46 ulp at root 0.1 / 0.5 / 1 for m in 2^-100 .. 2^-60).  Measured on exact blur values down to 2^-100,
+// roots 0.1 / 0.5 / 1: at most 0.63 of that allowance, below 1e-5 everywhere (tests/test_gpu_regulator_domain.py).
+// m = 0 gives exp2(+inf) = inf like rv / 0.  v_log_f32 treats denormal inputs as 0: below 2^-100 the accurate powf and a true
+// division run (a lane-divergent branch that no lane takes in practice), and for root = 0 (0 * -inf; pow(0, 0) = 1).
+// silent_regulate / conv2d_same_kernel keep powf.
 __device__ __forceinline__ float regulator_ratio(float bd, float rv, float root) {
     const float m = bd > 1.0f ? 1.0f : bd;
     if ((m > 0.0f && m < 7.8886e-31f) || root == 0.0f) return rv / powf(m, root);

@@ -21,6 +21,7 @@ except ImportError:                     # a tests/ directory from before that he
     pg = None
 
 RTOL = 1e-5
+DIM_K = (0, 0, 0, 20, 60, 100)          # the RGB cases multiply their frames by 2^-k: half of them run the regulator far below 1
 
 
 def make_kernels():
@@ -166,7 +167,9 @@ def case_rgb(rng, k):
         levels = classic_levels((h, w), scale, n)
     except ValueError:
         return desc + " (no such pyramid)"
-    frames = np.stack([frame(rng, h, w, 3) for _ in range(B)])
+    dim = int(rng.choice(DIM_K))                  # frames * 2^-dim: the regulator's blur far below 1 (exact scaling)
+    desc += " dim=2^-%d" % dim
+    frames = np.stack([frame(rng, h, w, 3) for _ in range(B)]) * np.float32(2.0 ** -dim)
     try:
         plan = rt.PyramidPlan(h, w, 3, levels)
     except ValueError as e:
@@ -175,7 +178,7 @@ def case_rgb(rng, k):
     f = int(rng.integers(0, B))
     want = so.classic_pyramid(frames[f], scale, n)
     for l in range(n):
-        assert_close(pyr.level(l)[f:f + 1], want[l], RTOL, scale=255.0, what=desc + " pyr %d" % l)
+        assert_close(pyr.level(l)[f:f + 1], want[l], RTOL, scale=255.0 * 2.0 ** -dim, what=desc + " pyr %d" % l)
     ks = {x: k[x] for x in ("rgc", "rgby", "stripe", "blur", "end")}
     policy = "zero" if rng.integers(0, 2) else "ieee"
     got = rt.rgb_line_end(pyr, ks, flat_policy=policy)
@@ -190,7 +193,7 @@ def case_rgb(rng, k):
         assert_close(got["orient"].level(l)[f:f + 1], w_["orient"], RTOL, what=desc + " orient %d" % l)
         le = so.pad_inwards(so.conv2d_same(np.ascontiguousarray(got["orient"].level(l)[f:f + 1]), ks["end"], relu=True,
                                            clip_hi=255.0), [[0, 0], [2, 2], [2, 2], [0, 0]])
-        assert_close(got["line_end"].level(l)[f:f + 1], le, RTOL, scale=255.0, what=desc + " line_end %d" % l)
+        assert_close(got["line_end"].level(l)[f:f + 1], le, RTOL, scale=255.0 * 2.0 ** (-0.9 * dim), what=desc + " line_end %d" % l)      # (orient scales with frame ** (1 - root), root 0.1)
         np.testing.assert_array_equal(got["value"].level(l)[f:f + 1],
                                       so.value_from_color(np.ascontiguousarray(got["line_end"].level(l)[f:f + 1])), err_msg=desc)
     return desc + " " + policy
@@ -338,7 +341,8 @@ def case_rgb_keypoints(rng, k):
     vm = bool(rng.integers(0, 2))
     p = float(rng.choice([0.0, 0.1, 0.1, 0.37, 1.0]))
     k, wdesc = draw_weights(rng, k)
-    desc = "rgb_keypoints h=%d w=%d n=%d B=%d knob=%d %s value_map=%s p=%g" % (h, w, n, B, kr, policy, vm, p) + wdesc
+    dim = int(rng.choice(DIM_K))
+    desc = "rgb_keypoints h=%d w=%d n=%d B=%d knob=%d %s value_map=%s p=%g dim=2^-%d" % (h, w, n, B, kr, policy, vm, p, dim) + wdesc
     try:
         consts = {x: k[x] for x in ("rgc", "rgby", "stripe", "blur", "end")}
         kw = dict(mode="rgb", n_levels=n, batch=B, selection=True, top_percent=p, flat_policy=policy, constants=consts,
@@ -347,7 +351,7 @@ def case_rgb_keypoints(rng, k):
         plain = LineEndPipeline((h, w), **kw)
     except ValueError as e:
         return desc + " (no such pyramid)" if "pyramid" in str(e) or "level" in str(e) else desc + " (plan refused: %s)" % str(e)[:60]
-    frames = np.stack([frame(rng, h, w, 3) for _ in range(B)])
+    frames = np.stack([frame(rng, h, w, 3) for _ in range(B)]) * np.float32(2.0 ** -dim)
     if rng.integers(0, 4) == 0:
         frames[0, int(rng.integers(0, h)), int(rng.integers(0, w)), int(rng.integers(0, 3))] = rng.choice([np.nan, np.inf, -np.inf])
     t = torch.from_numpy(frames).cuda()

@@ -316,6 +316,209 @@ def dim_frames():
     return np.stack([a, b.astype(np.float32)])
 
 
+def dimmed(frames, k):
+    """frames * 2^-k.  Scaling by a power of two is exact and everything before the regulator is positively homogeneous, so the
+    stripe and blur maps of the dimmed frame are those of the frame times 2^-k, bit for bit, as long as nothing becomes denormal
+    (k <= 110 on 0 .. 255 frames): every weight class and kernel form reaches any blur magnitude without new weights."""
+    return (np.asarray(frames, np.float32) * np.float32(2.0 ** -int(k))).astype(np.float32)
+
+
+DIM_K = (0, 13, 40, 70, 90, 100, 105, 110)      # the dimming sweep of tests/test_gpu_regulator_domain.py: blur from above 1 to 2^-113
+DIM_ROOTS = (0.1, 0.5, 1.0)
+DIM_RVS = (1.0, 0.7)
+
+
+# ----------------------------------------------------------------------------- dyadic weights: stripe and blur exact in float32
+# (tests/test_regulator_domain.py checks the premises on the CPU, tests/test_gpu_regulator_domain.py uses them: with an exact
+# stripe and an exact blur the only inexact operations left in orient are the regulator's own)
+
+EXACT_UNIT_LOG2 = {"frame": 0, "rgc": -2, "rgby": -6, "stripe": -8, "blur": -11}     # every map is an integer multiple of 2^this
+DYADIC_SEED = 3
+
+
+def _quarters(rng, choices, shape=None):
+    return rng.choice(np.asarray(choices, np.float64), shape) / 4.0
+
+
+def rgb_dyadic(seed=DYADIC_SEED):
+    """Weights of the symmetric class (variant 3) whose factors are small dyadic numbers: rgc diagonal with (corner, edge_h, edge_v,
+    centre) in quarters, rgby = S (x) A + B with S, A, B in quarters (S = 1 on the corners: the host's least-squares factors are then
+    the quarters themselves), a channel-sum stripe in quarters, a folded channel-uniform blur in eighths (centre 1) and a two-group
+    end bank of sixteenth mixes and quarter scales (scale 1 on the centre tap and on the first tap of the other group, so that
+    scale * mix reconstructs every weight exactly).  On exact_frames() every partial sum of rgc, rgby, stripe and blur is an
+    integer multiple of one unit (EXACT_UNIT_LOG2) below 2^24: exact in float32 in any order and any regrouping."""
+    rng, ref = _rng(seed, "rgb_dyadic"), reference()
+    rgc = np.zeros((3, 3, 3, 3))
+    for c in range(3):
+        co, eh, ev, ce = -0.25, _quarters(rng, [-1, -2]), _quarters(rng, [-1, -2]), _quarters(rng, [3, 4])
+        rgc[:, :, c, c] = [[co, eh, co], [ev, ce, ev], [co, eh, co]]
+    while True:
+        A = _quarters(rng, [-2, -1, -1, 1], (3, 3))
+        B = _quarters(rng, [-1, 1, 2], (3, 3))
+        B[np.arange(3), np.arange(3)] = _quarters(rng, [3, 4], 3)
+        if all(np.abs(np.cross(A[i], B[i])).max() > 0 for i in range(3)):      # A[i] not parallel to B[i]: the centre stays a group
+            break
+    eh, ev = rng.permutation([1, 2, 3])[:2] / 4.0
+    S = np.array([[1.0, eh, 1.0], [ev, 0.0, ev], [1.0, eh, 1.0]])
+    rgby = S[:, :, None, None] * A[None, None]
+    rgby[1, 1] = B
+    s = np.round(4.0 * _jit(rng, ref["stripe"][:, :, :1, :])) / 4.0
+    s = np.where(s == 0, _quarters(rng, [-1, 1], s.shape), s)
+    stripe = np.repeat(s, 3, axis=2)
+    q = np.clip(np.round(8.0 * _jit(rng, ref["blur"][3:, :4, 0, 0])), 1, 8) / 8.0
+    b = np.zeros((7, 7))
+    for dy in range(7):
+        for dx in range(7):
+            b[dy, dx] = q[abs(dy - 3), min(dx, 6 - dx)]
+    blur = np.repeat(np.repeat(_centre_one(b)[:, :, None, None], 3, 2), 3, 3)
+    e = ref["end"].reshape(9, 3, 3)
+    end = np.zeros((9, 3, 3))
+    for i in range(3):
+        tb = [t for t in range(9) if not END_MASKS[i] >> t & 1]
+        while True:
+            mix_a, mix_b = (np.round(16.0 * _jit(rng, e[t, i])) / 16.0 for t in (4, tb[0]))
+            mix_a, mix_b = (np.where(m == 0, 1.0 / 16.0, m) for m in (mix_a, mix_b))
+            if np.abs(np.cross(mix_a, mix_b)).max() > 0:
+                break
+        scale = _quarters(rng, [-3, -2, -1, 1, 2, 3], 9)
+        scale[4] = 1.0
+        scale[tb[0]] = 1.0          # the first and strictly largest tap of group B: the host's reference tap
+        for t in range(9):
+            end[t, i] = scale[t] * (mix_a if END_MASKS[i] >> t & 1 else mix_b)
+    return dict(rgc=rgc, rgby=rgby, stripe=stripe, blur=blur, end=end.reshape(3, 3, 3, 3))
+
+
+def exact_frames(seed=DYADIC_SEED):
+    """2 x 48 x 70 x 3 frames for rgb_dyadic: 3 % (frame 0) and 6 % (frame 1) of the pixels non-zero with values 1 .. 3 per channel,
+    and one black block (exact zeros: the flat policies).  Denser frames leave the 2^24 units (tests/test_regulator_domain.py)."""
+    rng = _rng(seed, "exact_frames")
+    frames = np.zeros((2, 48, 70, 3), np.float32)
+    for f, density in enumerate((0.03, 0.06)):
+        on = rng.random((48, 70)) < density
+        frames[f] = np.where(on[:, :, None], rng.integers(1, 4, (48, 70, 3)), 0)
+    frames[0, 8:28, 20:50] = 0.0
+    return frames
+
+
+EXACT_K_UNIT_AT_2M149 = 149 + EXACT_UNIT_LOG2["blur"]       # dimmed(exact_frames(), 138): the blur's unit is the smallest denormal
+# where the stripe of exact_frames() is non-zero its blur spans 2^2.9 .. 2^6.7 (2^-7.4 .. where it is zero): dimmed by these k it
+# lies across 1, near 2^-40 and 2^-80, across 2^-100, inside [2^-126, 2^-101], across 2^-126 and wholly in the denormals
+EXACT_K = (5, 45, 85, 105, 120, 131, EXACT_K_UNIT_AT_2M149)
+
+
+def regulator_allowance(y, m, root, fused):
+    """|got - oracle| allowed on orient = f32(x * f32(rv / f32(pow64(m, root)))) for an EXACT stripe x and an EXACT m = min(blur, 1),
+    element by element (float64).  U = 2^-24, t = root * |log2 m|.
+      powf path (the per-op kernels everywhere; the fused kernels for 0 < m < 7.8886e-31 and for root == 0):  8 U |y| -- ocml's
+        powf is 1 ulp = 2 U, the division and the product half an ulp each, the oracle's three roundings 1.5 U: about 4 U, doubled;
+      exp2 / log2 path (the fused kernels elsewhere):  (3 ln2 t + 8) U |y| -- v_log_f32 is 1 ulp of |log2 m| (2 ln2 t U on the
+        factor), the product root * log2 m half an ulp of t (ln2 t U), v_exp_f32 1 ulp, two products, the oracle's roundings.
+    Plus 2^-149 for the product's rounding on either side where y is denormal (half a denormal ulp each).  Derived, not tuned;
+    valid while the oracle's power stays a normal float32: the callers keep t <= 120 (root 1 may go on: pow(m, 1) = m is exact)."""
+    y64, m64 = np.abs(np.asarray(y, np.float64)), np.asarray(m, np.float64)
+    U = 2.0 ** -24
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(m64 > 0, float(root) * np.abs(np.log2(np.where(m64 > 0, m64, 1.0))), 0.0)
+    assert float(root) == 1.0 or t.max(initial=0.0) <= 120.0, "t = root * |log2 m| = %g > 120" % t.max()
+    powf_path = (not fused) | (float(root) == 0.0) | ((m64 > 0) & (m64 < float(np.float32(7.8886e-31))))
+    c = np.where(powf_path, 8.0, 3.0 * np.log(2.0) * t + 8.0)
+    return c * U * y64 + 2.0 ** -149
+
+
+BLUR_RANGES = (("m = 1", 1.0), ("2^-60 .. 1", 2.0 ** -60), ("2^-100 .. 2^-60", float(np.float32(7.8886e-31))),
+               ("2^-126 .. 2^-100", 2.0 ** -126), ("denormal", 0.0))      # (name, lower edge of m = min(blur, 1))
+
+
+def assert_regulator_sharp(got, want, m, root, fused, what, worst=None, form=None):
+    """The sharp assertion on orient for an exact stripe and blur: where the oracle gives 0, inf or NaN the same class (zero,
+    same-signed inf, NaN); elsewhere |got - want| <= regulator_allowance.  Returns the worst |err| / allowance and, with ``worst``
+    (a dict), keeps the worst per (form, range of m) in it."""
+    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
+    m = np.broadcast_to(np.asarray(m, np.float32), want.shape)
+    assert got.shape == want.shape, what
+    assert np.array_equal(np.isnan(got), np.isnan(want)), "%s: NaN pattern differs (%d vs %d)" % (what, np.isnan(got).sum(), np.isnan(want).sum())
+    inf = np.isinf(want)
+    assert np.array_equal(np.isinf(got), inf) and np.array_equal(got[inf], want[inf]), "%s: infinities differ" % what
+    zero = want == 0
+    assert (got[zero] == 0).all(), "%s: %d of the oracle's %d zeros are not zero" % (what, (got[zero] != 0).sum(), zero.sum())
+    fin = np.isfinite(want) & ~zero
+    if not fin.any():
+        return 0.0
+    err = np.abs(got[fin].astype(np.float64) - want[fin].astype(np.float64))
+    ratio = err / regulator_allowance(want[fin], m[fin], root, fused)
+    if worst is not None:
+        hi = np.inf
+        for name, lo in BLUR_RANGES:
+            sel = (m[fin] >= lo) & (m[fin] < hi) if lo > 0 else (m[fin] < hi)
+            if sel.any():
+                worst[(form, name)] = max(worst.get((form, name), 0.0), float(ratio[sel].max()))
+            hi = lo
+    i = int(np.argmax(ratio))
+    assert ratio[i] <= 1.0, "%s: %d / %d elements beyond the regulator's allowance; worst |err| %.3e = %.2f allowances on a value of %.6g, m = %.6g" % (
+        what, (ratio > 1.0).sum(), ratio.size, err[i], ratio[i], want[fin][i], m[fin][i])
+    return float(ratio[i])
+
+
+def print_worst(title, worst):
+    """The summary the regulator tests print (pytest -s): worst |err| / allowance per form and range of m."""
+    print("\n" + title)
+    for form in sorted({f for f, _ in worst}, key=str):
+        print("  %-28s %s" % (form, "   ".join("%s: %.3f" % (n, worst[(form, n)]) for n, _ in BLUR_RANGES if (form, n) in worst)))
+
+
+PRESCRIBED_ROOTS = (0.0, 0.1, 0.5, 1.0)
+
+
+def prescribed_pixels():
+    """The map of the per-op regulate test: one pixel per value, 8 columns apart (a NaN / inf pixel poisons its own 7 x 7 window only),
+    the value in channel i % 3, the other two channels 0.  Returns (x, values)."""
+    f = np.float32
+    up, down = (lambda v: np.nextafter(f(v), f(np.inf))), (lambda v: np.nextafter(f(v), f(-np.inf)))
+    thr, two100 = f(7.8886e-31), f(2.0 ** -100)
+    values = [f(-0.0), f(2.0 ** -149), down(2.0 ** -126), f(2.0 ** -126), down(thr), thr, up(thr), down(two100), two100,
+              up(two100), f(2.0 ** -50), f(0.3), down(1.0), f(1.0), up(1.0), f(np.finfo(f).max), f(np.inf), f(np.nan), f(-0.5), f(-2.0)]
+    x = np.zeros((1, 9, 8 * len(values) + 8, 3), f)
+    for i, v in enumerate(values):
+        x[0, 4, 8 * i + 8, i % 3] = v
+    return x, values
+
+
+def delta_blur(size, uniform):
+    """A centre-delta blur: per channel (the conv kernels with the regulator epilogue) or channel-uniform (the channel-sum kernel)."""
+    k = np.zeros((size, size, 3, 3))
+    k[size // 2, size // 2] = 1.0 if uniform else np.eye(3)
+    return k
+
+
+PRESCRIBED_FORMS = (("REG conv 7x7", 7, False), ("generic conv 5x5", 5, False), ("regulate_sum", 7, True))
+
+
+def check_prescribed(regulate, policy, worst):
+    """``regulate(x, blur, rv, root)`` on prescribed_pixels() with the three delta blurs, every root and rv, against the oracle with the
+    powf allowance (0 / inf / NaN by class)."""
+    import silent_oracle as so
+    x, values = prescribed_pixels()
+    at = [(0, 4, 8 * i + 8, i % 3) for i in range(len(values))]
+    for form, size, uniform in PRESCRIBED_FORMS:
+        blur = delta_blur(size, uniform)
+        with np.errstate(invalid="ignore"):
+            b = so.conv2d_same(x, blur)
+        m = np.where(b > 1, np.float32(1), b).astype(np.float32)
+        for p, v in zip(at, values):                 # the blur IS the pixel
+            assert (np.isnan(v) and np.isnan(b[p])) or b[p] == v, (form, v, b[p])
+        for root in PRESCRIBED_ROOTS:
+            for rv in DIM_RVS:
+                with np.errstate(invalid="ignore"):
+                    want = so.regulate(x, blur, rv, root, policy)
+                got = regulate(x, blur, rv, root)
+                assert_regulator_sharp(got, want, m, root, False, "%s root %g rv %g %s" % (form, root, rv, policy), worst, form)
+        # the contract of a negative blur (include/silent_hip.h, silent_regulate), on the oracle's side: pow's own
+        neg = at[len(values) - 2]                    # x = b = -0.5
+        with np.errstate(invalid="ignore"):
+            assert so.regulate(x, blur, 1.0, 1.0, policy)[neg] == np.float32(1.0) and so.regulate(x, blur, 0.7, 0.0, policy)[neg] == np.float32(-0.35)
+            assert np.isnan(so.regulate(x, blur, 1.0, 0.5, policy)[neg]) and np.isnan(so.regulate(x, blur, 1.0, 0.1, policy)[neg])
+
+
 STORE_EXTENTS = [(90, 224), (45, 112), (23, 56), (12, 28), (7, 4)]      # rows start on 16-byte boundaries (widths multiples of 4)
 
 

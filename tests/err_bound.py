@@ -75,7 +75,10 @@ def regulate(x, blur, rv, root, e_x=None, flat_policy="ieee"):
     with np.errstate(over="ignore"):
         dr = np.where(b - e_b < 1.0, root * rv * bc ** (-root - 1.0), 0.0)
     y = x64 * r
-    # log2 / exp2 route of the fused kernels, powf elsewhere: a few ulp of the factor, 24 covers both
+    # log2 / exp2 route of the fused kernels, powf elsewhere: a few ulp of the factor, 24 covers both near m = 1.
+    # This term is not what bounds the chain tests: the blur's own uncertainty, root * e_b / b, is some 30 times larger, so a
+    # factor that is off by several 1e-6 passes here.  The factor itself is held to its derived allowance, which grows with
+    # root * |log2 m|, on exact stripe and blur maps by tests/test_gpu_regulator_domain.py (chain_weights.regulator_allowance).
     with np.errstate(over="ignore", invalid="ignore"):
         e = r * e_x + np.abs(x64) * dr * e_b + 24 * U * np.abs(y)
     e = np.where((b <= 4.0 * e_b) | unbounded(e_b) | unbounded(e_x) | ~np.isfinite(e), BIG, np.minimum(e, BIG))

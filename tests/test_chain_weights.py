@@ -83,9 +83,16 @@ def _take_blur_folded(it):          # mirror-symmetric form: for j = min(dx, 6 -
     return b
 
 
-def _walk_stream(stream, n, variant, a, masks):
+def _walk_stream(stream, n, variant, a, masks, exact=False):
     """Walks the weight stream the way the pair kernel consumes it (as test_rgb_weight_stream_is_the_kernels_consumption_order of
-    tests/test_host_logic.py does for the reference's kernels) and compares the kernels it rebuilds with the ones that went in."""
+    tests/test_host_logic.py does for the reference's kernels) and compares the kernels it rebuilds with the ones that went in.
+    ``exact``: the factored kernels (scale * mix) must reproduce the weights bit for bit as well (dyadic weights)."""
+    def same_product(got, want):
+        if exact:
+            np.testing.assert_array_equal(got, want)
+        else:
+            np.testing.assert_allclose(got, want, rtol=2e-6, atol=1e-9)
+
     assert not np.isnan(stream).any() and not stream[n:].any()
     it = iter(stream[:n])
     eye = np.eye(3, dtype=np.float32)
@@ -102,10 +109,10 @@ def _walk_stream(stream, n, variant, a, masks):
         np.testing.assert_array_equal(_take_conv(it, 0x1ff), a["end"])
     elif variant == 2:
         np.testing.assert_array_equal(_take_conv(it, 0x111), a["rgc"] * eye)
-        np.testing.assert_allclose(_take_two(it, masks[:3]), a["rgby"], rtol=2e-6, atol=1e-9)
+        same_product(_take_two(it, masks[:3]), a["rgby"])
         np.testing.assert_array_equal(_take_sum(it), a["stripe"][:, :, 0, :])
         np.testing.assert_array_equal(_take_blur_folded(it), a["blur"][:, :, 0, 0])
-        np.testing.assert_allclose(_take_two(it, masks[3:]), a["end"], rtol=2e-6, atol=1e-9)
+        same_product(_take_two(it, masks[3:]), a["end"])
     else:
         q = np.array([next(it) for _ in range(12)], np.float32).reshape(4, 3)            # [corner, edge_v, edge_h, centre][channel]
         rgc = np.zeros((3, 3, 3, 3), np.float32)
@@ -122,7 +129,7 @@ def _walk_stream(stream, n, variant, a, masks):
         B = np.array([next(it) for _ in range(9)], np.float32).reshape(3, 3)
         rgby = S[:, :, None, None] * A[None, None].astype(np.float64)
         rgby[1, 1] += B
-        np.testing.assert_allclose(rgby, a["rgby"], rtol=2e-6, atol=1e-9)
+        same_product(rgby, a["rgby"])
         assert next(it) == 0.0                                                            # the pair block starts on an even position
         stripe = np.zeros((3, 3, 3), np.float32)                                          # [dy][dx][o]
         for o in range(3):
@@ -134,7 +141,7 @@ def _walk_stream(stream, n, variant, a, masks):
             assert blk[9] == 0.0
         np.testing.assert_array_equal(stripe, a["stripe"][:, :, 0, :])
         np.testing.assert_array_equal(_take_blur_folded(it), a["blur"][:, :, 0, 0])
-        np.testing.assert_allclose(_take_two(it, masks[3:]), a["end"], rtol=2e-6, atol=1e-9)
+        same_product(_take_two(it, masks[3:]), a["end"])
     assert next(it, None) is None
 
 
